@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: frames/s of the ORB front-end + frame-to-frame matching on synthetic KITTI-shape frames.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch 512 | --frames-per-gpu B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch 512 | --frames-per-gpu B] [--dump-outputs DIR] [--full]
 
 Headline workload (BASELINE.json metric "ORB extract+match, KITTI 1241x376 @1000 feat"; configs[1] + the
 SearchByProjection half of configs[2]): a global batch of 512 synthetic 1241x376 uint8 frames (BASELINE.json configs[3]:
@@ -9,16 +9,20 @@ SearchByProjection half of configs[2]): a global batch of 512 synthetic 1241x376
 pairs.  One "step" = ORBextractor::operator() over the B frames (nFeatures=1000,
 scaleFactor 1.2, 8 levels, iniThFAST 20 / minThFAST 7) + ORBmatcher::SearchByProjection(CurrentFrame, LastFrame,
 th=15, bMono) for the B/2 pairs (src/Tracking.cc:880-885), projection prologue included, everything device resident.
-`value` = frames through that step per second.
+A plain run sets up, runs W warm-up steps, times exactly K steps (`value` = frames through that step per second,
+`ms_per_step` = milliseconds of one of them), writes the outputs of the last timed step when --dump-outputs is given,
+and prints the line.
 
 For N > 1 the driver launches one rank per GPU with torch.distributed.run; `python bench.py --gpus N` without that
 environment spawns the N ranks itself (before anything touches a GPU).  Pair p of the global batch goes to rank
 p mod N; every step ends with the RCCL gather of the fixed-capacity result slots to rank 0 (configs[3]).
 
-Named secondary objects in the same JSON line (never `value`): extract_only (configs[1]), stereo (configs[2] as one leg:
-extract L+R on two handles + Frame::ComputeStereoMatches + SearchByProjection at th = 7 with the `ur` gate), euroc_init (configs[4]: 752x480 @2000 + SearchForInitialization),
-bow (extract + ComputeBoW + SearchByBoW).  Rank 0 prints ONE JSON line; README/DESIGN.md describe `roofline` and
-`cpu_baseline`.
+--full adds everything else, after the K timed steps and without changing `value`: the same step R x K more times with
+HIP events around every stage (`timing.long_region`, `roofline`), the named secondary objects (never `value`):
+extract_only (configs[1]), stereo (configs[2] as one leg: extract L+R on two handles + Frame::ComputeStereoMatches +
+SearchByProjection at th = 7 with the `ur` gate), euroc_init (configs[4]: 752x480 @2000 + SearchForInitialization),
+bow (extract + ComputeBoW + SearchByBoW), `cpu_baseline` and, with N > 1, the 128-frames-per-GPU weak-scaling step.
+Rank 0 prints ONE JSON line; README/DESIGN.md describe `roofline` and `cpu_baseline`.
 """
 import argparse
 import json
@@ -56,7 +60,9 @@ KITTI_FX, KITTI_FY, KITTI_CX, KITTI_CY, KITTI_BF = 718.856, 718.856, 607.1928, 1
 TRACK_TH, DEPTH = 15.0, 12.0                            # src/Tracking.cc:880 (mono th = 15); synthetic scene depth [m]
 STEREO_TH = 7.0                                         # src/Tracking.cc:882-885 (stereo th = 7)
 GLOBAL_BATCH = 512                                      # BASELINE.json configs[3]
-MIN_TIMED_S = 1.0                                       # the timed region of every leg lasts at least this long
+MIN_TIMED_S = 1.0                                       # --full: the timed region of every extra leg lasts at least this long
+DUMP_PAIRS = 64                                         # --dump-outputs: pairs in the seeded sample of the per-slot arrays
+DUMP_LIMIT_BYTES = 64 << 20                             # --dump-outputs: all files together
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -205,24 +211,63 @@ def emit_json(obj):
         os.write(_REAL_STDOUT, line)
 
 
+def dump_outputs(out_dir, k, d, n, st, a, m, seed=0):
+    """--dump-outputs: what a caller of the headline step receives, as float32 .npy files (every value is exact in
+    float32).  Inputs are the host copies of one output set: k int32 [B][cap][7] (KeyPoint records: x y size angle response
+    as float32 bits, octave, class_id), d uint8 [B][cap][32], n and st int32 [B], a int32 [B/2][cap], m int32 [B/2]; pair p
+    is (LastFrame 2p, CurrentFrame 2p+1).  Per-frame counts and statuses and per-pair match counts are written whole;
+    keypoints, descriptors and assignments for a fixed seeded sample of pairs (sample_pairs.npy), slots past a frame's
+    keypoint count set to 0 (-1 in the assignments), since the library leaves them undefined.  Returns the bytes written."""
+    B, cap = k.shape[0], k.shape[1]
+    pairs = B // 2
+    per_pair = cap * (2 * 7 + 2 * 32 + 1) * 4
+    whole = (2 * B + pairs) * 4
+    ns = min(pairs, DUMP_PAIRS, max(1, (DUMP_LIMIT_BYTES - whole - 4 * DUMP_PAIRS - 4096) // per_pair))
+    sample = np.sort(np.random.default_rng(seed).choice(pairs, size=ns, replace=False))
+    frames = np.stack([2 * sample, 2 * sample + 1], 1)                       # [ns][2]: last, current
+    live = np.arange(cap)[None, None, :] < n[frames][..., None]              # [ns][2][cap]
+    kp = np.concatenate([k[frames].view(np.float32)[..., :5], k[frames][..., 5:].astype(np.float32)], -1)
+    kp[~live] = 0.0
+    desc = d[frames].astype(np.float32)
+    desc[~live] = 0.0
+    assign = a[sample].astype(np.float32)
+    assign[~live[:, 1]] = -1.0
+    arrays = {"keypoints": kp, "descriptors": desc, "match_assign": assign, "sample_pairs": sample.astype(np.float32),
+              "keypoint_counts": n.astype(np.float32), "status": st.astype(np.float32), "match_counts": m.astype(np.float32)}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "dump of %d bytes exceeds the %d-byte limit" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30, help="timed steps: `value` and `ms_per_step` come from exactly these")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline: the stage-event region "
+                         "(timing.long_region, roofline), the secondary legs, cpu_baseline and, with N > 1, the weak-scaling step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rank 0's share) to DIR/<name>.npy as float32: "
+                         "keypoint_counts, status, match_counts whole; keypoints, descriptors, match_assign for a seeded "
+                         "sample of pairs (sample_pairs)")
     ap.add_argument("--global-batch", type=int, default=GLOBAL_BATCH,
                     help="frames per step over all GPUs (BASELINE.json configs[3]: 512); every GPU gets global/N of them, "
                          "split over --handles pipelines")
     ap.add_argument("--frames-per-gpu", type=int, default=None,
                     help="fix the frames per GPU and step instead (weak scaling: the global batch grows with N)")
     ap.add_argument("--min-time", type=float, default=MIN_TIMED_S,
-                    help="minimum length in seconds of every timed region (profiler runs pass 0: one repeat of --steps)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: minimum length in seconds of the stage-event region and of every secondary leg (profiler "
+                         "runs pass 0: one repeat of --steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--trace-run", action="store_true",
                     help="for kernel-trace tools: warm-up + K plain steps of the headline (no HIP events between the stages, no "
                          "secondary legs), one short JSON line")
     ap.add_argument("--no-secondary", "--no-match", dest="no_secondary", action="store_true",
-                    help="skip the secondary legs (extract-only, stereo, EuRoC initialisation, BoW)")
+                    help="--full: skip the secondary legs (extract-only, stereo, EuRoC initialisation, BoW) and the weak-scaling step")
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (= RCCL; default) or gloo (rehearsal of the multi-rank control flow: ranks share cuda:0 "
                          "when there is one, and the gather goes through host memory)")
@@ -243,6 +288,10 @@ def main():
                          "on separate HIP streams (extractor + matcher handle each).  Default: 3 from 64 frames per GPU up (64 frames per GPU, "
                          "configs[3] on 8 GPUs, without gates: 227 k frames/s per GPU against 223 k with 2 and 196 k with 1), 2 below")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs is not None:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args))
@@ -303,67 +352,39 @@ def main():
            "multi": multi, "rehearsal": rehearsal, "gather_into": gather_into, "gather_to_rank0": gather_to_rank0}
     head = Headline(ctx, B)
     if args.trace_run:
-        res = head.measure(stages=False)
+        res = head.measure(full=False)
         if rank == 0:
             emit_json({"metric": "trace run (headline steps only)", "value": round(res["fps"], 1), "unit": "frames/s", "n_gpus": world,
-                       "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(res["dt_long"] / res["steps_long"] * 1e3, 4)})
+                       "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(res["dt_k"] / args.steps * 1e3, 4)})
         return
-    res = head.measure()
+    res = head.measure(full=args.full)
     if rank == 0:
-        print("[bench] headline done: %.1f frames/s; secondary legs ..." % res["fps"], file=sys.stderr, flush=True)
+        print("[bench] headline done: %.1f frames/s" % res["fps"], file=sys.stderr, flush=True)
     secondary = None
-    if not args.no_secondary and world == 1 and not multi:
+    if args.full and not args.no_secondary and world == 1 and not multi:
+        print("[bench] secondary legs ...", file=sys.stderr, flush=True)
         secondary = secondary_legs(args, torch, dev, local_rank, head)
     weak = None
-    if world > 1 and scaling == "strong" and not args.no_secondary:
+    if args.full and world > 1 and scaling == "strong" and not args.no_secondary:
         # the round-2 workload beside it: 128 frames per GPU whatever N is (weak scaling), never `value`
         head.close()
         w = Headline(ctx, 128)
-        wr = w.measure(stages=False)
+        wr = w.measure(full=False, min_time=args.min_time)
         weak = {"value": round(wr["fps"], 1), "unit": "frames/s", "scaling": "weak",
                 "what": "the same step with 128 frames per GPU (global batch %d)" % (128 * world),
                 "ms_per_step": round(wr["dt_long"] / wr["steps_long"] * 1e3, 4), "timed_s": round(wr["dt_long"], 4)}
         w.close()
 
     if rank == 0:
-        stage, stage_alone, Bm = res["stage"], res["stage_alone"], res["frames_per_launch"]
-        fps, steps_long, dt_long, dt_k, reps = res["fps"], res["steps_long"], res["dt_long"], res["dt_k"], res["reps"]
-        fps_k = B * world * args.steps / dt_k                   # exactly K steps
-        # dominant single kernel: the largest launch among the one-launch stages when a pipeline runs alone (a property of
-        # the kernel: rocprofv3 --stats of a single pipeline has k_fast_cells at 30 % of the GPU time, k_describe_fused at
-        # 21 %; how much a launch is stretched while other pipelines share the GPU is a property of the schedule).  Its
-        # launch time in the timed region is what `achieved` uses.
-        kern = max(("fast", "describe"), key=lambda k: stage_alone[k])
-        # frames per launch: the pipelines get 172 / 170 / 170 frames of a 512-frame step; stage times are means over
-        # the pipelines, so the bytes are those of the MEAN launch
-        algo = ALGO_BYTES[kern] * Bm
-        achieved = algo / (stage[kern] * 1e-6) / 1e9
-        traffic, valu = None, None
-        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tpath):
-            try:
-                pm = json.load(open(tpath))[kern]
-                traffic = round(pm["hbm_bytes_per_frame"] * Bm)
-                if "valu_issue_us_per_frame" in pm:
-                    # the kernel is priced against HBM as the contract asks, but what bounds it is VALU issue: PMC
-                    # instruction count x the measured issue cost of its instruction mix (tools/micro)
-                    vi = pm["valu_issue_us_per_frame"] * Bm
-                    valu = {"insts_per_launch": pm["valu_insts_per_frame"] * Bm, "issue_us_per_launch": round(vi, 1),
-                            "frac_of_launch": round(vi / stage[kern], 3), "model": pm.get("valu_issue_model")}
-            except Exception:
-                traffic, valu = None, None
+        fps, dt_k = res["fps"], res["dt_k"]                     # exactly K steps
         try:
             metric_name = json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
         except Exception:
             metric_name = "frames/sec ORB extract+match, KITTI 1241x376 @1000 feat; HBM GB/s vs peak"
-        other_denoms = {"pyramid": "SURVEY 8d K1 without the level-0 copy, which these monocular handles do not execute: (SumP - P7) read "
-                                   "+ (SumP - P0) written (the full K1 figure, P0 + (SumP - P7) + SumP, applies to the stereo leg)",
-                        "describe": "SURVEY 8d K5+K7: N*(749+512) read + N*60 written; K6's 2*SumP is not moved (the blur is fused) "
-                                    "and not counted"}
         out = {
             "metric": metric_name,
             "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt_long / steps_long * 1e3, 4),
+            "warmup": args.warmup, "ms_per_step": round(dt_k / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "u8",
             "data": "synthetic",
             "config": {"workload": "configs[1]+[2]+[3]: a global batch of %d synthetic 1241x376 u8 frames per step, %d per GPU, resident in "
@@ -373,45 +394,85 @@ def main():
                                    "(orbhip_extractor_set_lazy_level0), never asked for here" % (B * world, B) +
                                    ("; pairs round-robin over the GPUs + RCCL gather of the result slots to rank 0" if world > 1 else ""),
                        "frames_per_gpu_per_step": B, "pairs_per_gpu_per_step": B // 2, "handles_per_gpu": head.Hn, "stage_gates": head.gates,
-                       "frames_per_launch": head.splits, "mean_frames_per_launch": Bm, "global_batch": B * world, "nfeatures": NFEAT,
+                       "frames_per_launch": head.splits, "mean_frames_per_launch": sum(head.splits) / len(head.splits),
+                       "global_batch": B * world, "nfeatures": NFEAT,
                        "levels": NLEVELS, "mean_keypoints_per_frame": res["mean_kp"],
                        "mean_matches_per_pair": res["mean_matches"],
                        "parallelism": "pair-sharded x%d" % world,
                        "gather_bytes_per_rank_per_step": head.flat_bytes if multi else 0},
-            "timing": {"timed_steps": steps_long, "timed_s": round(dt_long, 4), "timed_repeats_of_steps": reps,
-                       "exactly_k_steps": {"steps": args.steps, "s": round(dt_k, 5), "ms_per_step": round(dt_k / args.steps * 1e3, 4),
-                                           "frames_per_s": round(fps_k, 1)}},
-            "roofline": {"bound": "hbm", "kernel": KERNEL_NAME[kern],
-                         "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "valu_issue": valu,
-                         "algorithmic_bytes_per_launch": round(algo),
-                         "avg_launch_us": round(stage[kern], 2),
-                         "alone": {"what": "a launch of pipeline 0 (%d frames) with no other pipeline on the GPU" % head.splits[0],
-                                   "avg_launch_us": round(stage_alone[kern], 2),
-                                   "achieved": round(ALGO_BYTES[kern] * head.splits[0] / (stage_alone[kern] * 1e-6) / 1e9, 2),
-                                   "frac": round(ALGO_BYTES[kern] * head.splits[0] / (stage_alone[kern] * 1e-6) / 1e9 / HBM_PEAK_GBPS, 5),
-                                   "stage_us": {k: round(v, 2) for k, v in stage_alone.items()}},
-                         "other_stages": {k: {"kernel": KERNEL_NAME[k], "algorithmic_bytes_per_launch": round(ALGO_BYTES[k] * Bm),
-                                              "denominator": other_denoms[k],
-                                              "frac": round(ALGO_BYTES[k] * Bm / (stage[k] * 1e-6) / 1e9 / HBM_PEAK_GBPS, 5),
-                                              "frac_alone": round(ALGO_BYTES[k] * head.splits[0] / (stage_alone[k] * 1e-6) / 1e9 / HBM_PEAK_GBPS, 5)}
-                                          for k in ("pyramid", "describe") if stage[k] > 0 and stage_alone[k] > 0},
-                         "stage_us": {k: round(v, 2) for k, v in stage.items()},
-                         "whole_path_GBps_model": round(FRAME_BYTES_MODEL * fps / world / 1e9, 2)},
+            "timing": {"timed_steps": args.steps, "timed_s": round(dt_k, 5)},
         }
+        if args.full:
+            full_fields(out, res, head, B, world)
         if weak:
             out["weak_128_per_gpu"] = weak
         if secondary:
             out.update(secondary)
-        if not args.no_cpu_baseline and world == 1:
-            print("[bench] GPU legs done; cpu_baseline (~25 s) ...", file=sys.stderr, flush=True)
-            out["cpu_baseline"] = cpu_baseline(head.frames[:16])
-        else:
-            out["cpu_baseline"] = None
+        if args.full:
+            if not args.no_cpu_baseline and world == 1:
+                print("[bench] GPU legs done; cpu_baseline (~25 s) ...", file=sys.stderr, flush=True)
+                out["cpu_baseline"] = cpu_baseline(head.frames[:16])
+            else:
+                out["cpu_baseline"] = None
         emit_json(out)
     if multi:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def full_fields(out, res, head, B, world):
+    """--full: the stage-event region of Headline.measure as `timing.long_region`, and `roofline` from its HIP events."""
+    stage, stage_alone, Bm = res["stage"], res["stage_alone"], res["frames_per_launch"]
+    steps_long, dt_long, reps = res["steps_long"], res["dt_long"], res["reps"]
+    fps_long = B * world * steps_long / dt_long
+    # dominant single kernel: the largest launch among the one-launch stages when a pipeline runs alone (a property of
+    # the kernel: rocprofv3 --stats of a single pipeline has k_fast_cells at 30 % of the GPU time, k_describe_fused at
+    # 21 %; how much a launch is stretched while other pipelines share the GPU is a property of the schedule).  Its
+    # launch time in the stage-event region is what `achieved` uses.
+    kern = max(("fast", "describe"), key=lambda k: stage_alone[k])
+    # frames per launch: the pipelines get 172 / 170 / 170 frames of a 512-frame step; stage times are means over
+    # the pipelines, so the bytes are those of the MEAN launch
+    algo = ALGO_BYTES[kern] * Bm
+    achieved = algo / (stage[kern] * 1e-6) / 1e9
+    traffic, valu = None, None
+    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    if os.path.exists(tpath):
+        try:
+            pm = json.load(open(tpath))[kern]
+            traffic = round(pm["hbm_bytes_per_frame"] * Bm)
+            if "valu_issue_us_per_frame" in pm:
+                # the kernel is priced against HBM as the contract asks, but what bounds it is VALU issue: PMC
+                # instruction count x the measured issue cost of its instruction mix (tools/micro, DESIGN.md section 6)
+                vi = pm["valu_issue_us_per_frame"] * Bm
+                valu = {"insts_per_launch": pm["valu_insts_per_frame"] * Bm, "issue_us_per_launch": round(vi, 1),
+                        "frac_of_launch": round(vi / stage[kern], 3), "model": pm.get("valu_issue_model")}
+        except Exception:
+            traffic, valu = None, None
+    other_denoms = {"pyramid": "SURVEY 8d K1 without the level-0 copy, which these monocular handles do not execute: (SumP - P7) read "
+                               "+ (SumP - P0) written (the full K1 figure, P0 + (SumP - P7) + SumP, applies to the stereo leg)",
+                    "describe": "SURVEY 8d K5+K7: N*(749+512) read + N*60 written; K6's 2*SumP is not moved (the blur is fused) "
+                                "and not counted"}
+    out["timing"]["long_region"] = {"what": "the same step again, R x K times (>= --min-time s), with HIP events around every "
+                                            "stage: the times behind roofline / stage_us",
+                                    "steps": steps_long, "s": round(dt_long, 4), "repeats_of_steps": reps,
+                                    "ms_per_step": round(dt_long / steps_long * 1e3, 4), "frames_per_s": round(fps_long, 1)}
+    out["roofline"] = {"bound": "hbm", "kernel": KERNEL_NAME[kern],
+                       "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                       "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "valu_issue": valu,
+                       "algorithmic_bytes_per_launch": round(algo),
+                       "avg_launch_us": round(stage[kern], 2),
+                       "alone": {"what": "a launch of pipeline 0 (%d frames) with no other pipeline on the GPU" % head.splits[0],
+                                 "avg_launch_us": round(stage_alone[kern], 2),
+                                 "achieved": round(ALGO_BYTES[kern] * head.splits[0] / (stage_alone[kern] * 1e-6) / 1e9, 2),
+                                 "frac": round(ALGO_BYTES[kern] * head.splits[0] / (stage_alone[kern] * 1e-6) / 1e9 / HBM_PEAK_GBPS, 5),
+                                 "stage_us": {k: round(v, 2) for k, v in stage_alone.items()}},
+                       "other_stages": {k: {"kernel": KERNEL_NAME[k], "algorithmic_bytes_per_launch": round(ALGO_BYTES[k] * Bm),
+                                            "denominator": other_denoms[k],
+                                            "frac": round(ALGO_BYTES[k] * Bm / (stage[k] * 1e-6) / 1e9 / HBM_PEAK_GBPS, 5),
+                                            "frac_alone": round(ALGO_BYTES[k] * head.splits[0] / (stage_alone[k] * 1e-6) / 1e9 / HBM_PEAK_GBPS, 5)}
+                                        for k in ("pyramid", "describe") if stage[k] > 0 and stage_alone[k] > 0},
+                       "stage_us": {k: round(v, 2) for k, v in stage.items()},
+                       "whole_path_GBps_model": round(FRAME_BYTES_MODEL * fps_long / world / 1e9, 2)}
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -505,6 +566,7 @@ class Headline:
             d_world[0::2, :, 2] = z
 
         self.obuf = obuf = [out_set()]
+        self.last_out = obuf[0]                      # the output set of the latest step()
         nbuf = args.out_buffers if multi and not rehearsal else 1
         for _ in range(nbuf - 1):
             obuf.append(out_set())
@@ -544,7 +606,7 @@ class Headline:
         def step():
             k = stepno[0] % nbuf
             stepno[0] += 1
-            o = obuf[k]
+            o = self.last_out = obuf[k]
             if gdone[k] is not None:                 # the gather that last read this buffer must be finished
                 for st in streams:
                     st.wait_event(gdone[k])
@@ -585,7 +647,11 @@ class Headline:
         self.ctx["dist"].all_reduce(t, op=self.ctx["dist"].ReduceOp.MAX)
         return float(t.item())
 
-    def measure(self, stages=True):
+    def measure(self, full=False, min_time=None):
+        """W warm-up steps, then EXACTLY K timed steps between barriers (`value`, `ms_per_step`; --dump-outputs writes
+        the outputs of the last of them).  full: then the stage-event region, R x K more steps with the per-stage HIP
+        events on (>= --min-time s), and pipeline 0 alone.  min_time without full: R x K more plain steps (the weak-
+        scaling step)."""
         args, torch, dev, world = self.ctx["args"], self.ctx["torch"], self.ctx["dev"], self.ctx["world"]
         exts, step, barrier, allreduce_max = self.exts, self.step, self.barrier, self.allreduce_max
         for _ in range(args.warmup):
@@ -597,12 +663,24 @@ class Headline:
             step()
         barrier()
         dt_k = allreduce_max(time.perf_counter() - t0)
+        res = {"dt_k": dt_k, "fps": self.B * world * args.steps / dt_k}
+        o = self.last_out
+        n_host, nm_host, st_host = o["n"].cpu().numpy(), o["m"].cpu().numpy(), o["st"].cpu().numpy()
+        if args.dump_outputs is not None and self.ctx["rank"] == 0:
+            nb = dump_outputs(args.dump_outputs, o["k"].cpu().numpy(), o["d"].cpu().numpy(), n_host, st_host,
+                              o["a"].cpu().numpy(), nm_host)
+            print("[bench] outputs of the last timed step: %d bytes in %s" % (nb, args.dump_outputs), file=sys.stderr, flush=True)
+        assert int(np.abs(st_host).sum()) == 0 and n_host.min() > 0, "extraction failed"
+        assert nm_host.min() > 100, "SearchByProjection found too few matches: the synthetic pairs are broken"
+        res["mean_kp"], res["mean_matches"] = round(float(n_host.mean()), 1), round(float(nm_host.mean()), 1)
+        if not full and min_time is None:
+            return res
         # ---- the same steps again, R x K of them (>= 1 s), with the per-stage HIP events on: stage_us / roofline -----
-        if stages:
+        if full:
             for e in exts:
                 e.set_profiling(True)                   # HIP events around every stage, on the launch stream
             self.record_match[0] = True
-        reps = max(1, int(np.ceil(args.min_time / max(dt_k, 1e-6))))
+        reps = max(1, int(np.ceil((args.min_time if min_time is None else min_time) / max(dt_k, 1e-6))))
         reps = int(allreduce_max(float(reps)))
         barrier()
         t0 = time.perf_counter()
@@ -611,14 +689,8 @@ class Headline:
         barrier()
         dt_long = allreduce_max(time.perf_counter() - t0)
         steps_long = reps * args.steps
-        res = {"dt_k": dt_k, "dt_long": dt_long, "reps": reps, "steps_long": steps_long,
-               "fps": self.B * world * steps_long / dt_long}                      # the >= 1 s region; `value`
-        o = self.obuf[0]
-        n_host, nm_host = o["n"].cpu().numpy(), o["m"].cpu().numpy()
-        assert int(o["st"].abs().sum().item()) == 0 and n_host.min() > 0, "extraction failed"
-        assert nm_host.min() > 100, "SearchByProjection found too few matches: the synthetic pairs are broken"
-        res["mean_kp"], res["mean_matches"] = round(float(n_host.mean()), 1), round(float(nm_host.mean()), 1)
-        if not stages:
+        res.update({"dt_long": dt_long, "reps": reps, "steps_long": steps_long})
+        if not full:
             return res
         self.record_match[0] = False
         st_all = [e.stage_times_us() for e in exts]

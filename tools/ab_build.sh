@@ -7,7 +7,7 @@ IFS='|' read -r -a VARS <<< "$1"; shift
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
 run() {
-  python3 $R/bench.py --no-cpu-baseline --no-secondary "$@" 2>/dev/null | python3 -c "
+  python3 $R/bench.py --full --no-cpu-baseline --no-secondary "$@" 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('$TAG', d['value'], d['ms_per_step'], d['roofline']['alone']['stage_us'])"
 }

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 for i in 1 2; do
   for v in "${VARS[@]}"; do
     make -s -B -C $R/orb_slam2_comment_amd/csrc EXTRA="$v" > /dev/null 2>&1 || echo "build failed: $v"
-    python3 $R/bench.py --no-cpu-baseline --no-secondary --handles 1 --frames-per-gpu 64 --min-time 0.5 "$@" 2>/dev/null | python3 -c "
+    python3 $R/bench.py --full --no-cpu-baseline --no-secondary --handles 1 --frames-per-gpu 64 --min-time 0.5 "$@" 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('[$v]', d['value'], d['roofline']['alone']['stage_us'], 'match', d['roofline']['stage_us']['match'])"
   done

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/pmc
 rm -rf $OUT; mkdir -p $OUT
-ARGS="$R/bench.py --steps 4 --warmup 2 --min-time 0 --no-cpu-baseline --no-secondary --handles 1 --frames-per-gpu 64"
+ARGS="$R/bench.py --full --steps 4 --warmup 2 --min-time 0 --no-cpu-baseline --no-secondary --handles 1 --frames-per-gpu 64"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- python3 $ARGS > $OUT/fetch.log 2>&1
 echo "fetch pass done"
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -- python3 $ARGS > $OUT/write.log 2>&1

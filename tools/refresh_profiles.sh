@@ -7,17 +7,17 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/refresh
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats2 -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary > $OUT/bench_under_rocprof_handles3.json 2> $OUT/stats2.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats2 -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-secondary > $OUT/bench_under_rocprof_handles3.json 2> $OUT/stats2.err
 cp $(find $OUT/stats2 -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_handles3.csv
 echo "stats (3 pipelines) done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats1 -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --handles 1 --frames-per-gpu 64 > $OUT/bench_under_rocprof_handles1.json 2> $OUT/stats1.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats1 -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --handles 1 --frames-per-gpu 64 > $OUT/bench_under_rocprof_handles1.json 2> $OUT/stats1.err
 cp $(find $OUT/stats1 -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_handles1.csv
 echo "stats (1 pipeline) done"
 bash $R/tools/pmc_profile.sh > $OUT/pmc.log 2>&1
 cd $R
 python3 tools/pmc_summarize.py gpurun_out/pmc > $OUT/pmc_summary.json
 echo "pmc done"
-python3 bench.py > $OUT/bench_final.json 2> $OUT/bench_final.err
+python3 bench.py --full > $OUT/bench_final.json 2> $OUT/bench_final.err
 echo "bench done"
 python3 tools/bench_host_path.py > $OUT/host_path.json 2> $OUT/host_path.err
 python3 tools/bench_host_path.py --pinned > $OUT/host_path_pinned.json 2>> $OUT/host_path.err
