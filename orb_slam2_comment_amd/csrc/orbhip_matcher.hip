@@ -6,10 +6,11 @@
 // Structure: a fully parallel "window search" kernel (one wavefront per query:
 // Frame::GetFeaturesInArea membership test + 256-bit XOR/popcount Hamming
 // distance, candidates compacted with wave ballots and sorted by
-// (distance, reference visiting order)), followed by a single-wavefront
-// "resolve" kernel that replays the reference's order-dependent bookkeeping
-// (slots taken by earlier queries, match stealing, rotation histogram) over
-// state held in LDS.  Integer/bitwise path: no MFMA.
+// (distance, reference visiting order)), followed by a one-workgroup-per-pair
+// "resolve" kernel that reaches the outcome of the reference's order-dependent
+// bookkeeping (slots taken by earlier queries, match stealing, rotation
+// histogram) by parallel rounds over state held in LDS.  Integer/bitwise path:
+// no MFMA.
 #include "orbhip_internal.h"
 
 #include <algorithm>
@@ -21,7 +22,7 @@ namespace orbhip {
 
 constexpr int TH_HIGH = 100, TH_LOW = 50, HISTO_LENGTH = 30;
 constexpr int GRID_ROWS = 48, GRID_COLS = 64;   // include/Frame.h:37-38
-constexpr int kResolveMax = 4096;               // LDS-resident state of the resolve kernel
+constexpr int kResolveMax = 4096;               // LDS-resident state of the resolve kernels
 constexpr uint32_t kNoCell = 0xffffffffu;
 
 struct DevFrame {
@@ -32,11 +33,11 @@ struct DevFrame {
     float min_x, min_y, inv_w, inv_h;
 };
 
-// Batched (device-resident) calls: pair p = blockIdx.y uses element strides cap / qcap; the single-pair
-// host path passes zero strides and null count pointers.
+// Pair p of a call (blockIdx.y, or blockIdx.x for one workgroup per pair) uses element strides cap / qcap.  A host-pointer
+// call is a one-pair batch: cap = n, qcap = nq and null count pointers.
 struct Batch {
-    const int *n_dev;    // per-frame train keypoint counts, or null (use F.n)
-    const int *nq_dev;   // per-pair query counts, or null (use the nq argument)
+    const int *n_dev;    // per-frame train keypoint counts, or null (count = cap = F.n)
+    const int *nq_dev;   // per-pair query counts, or null (count = qcap)
     int cap, qcap;
     int t0 = 0, ts = 1;    // train side of pair p = frame t0 + p*ts of the extractor-layout arrays
     int qd0 = 0, qds = 1;  // query descriptors of pair p = frame qd0 + p*qds of their array
@@ -148,7 +149,7 @@ __device__ __forceinline__ void grid_build_body(DevFrame F, int *__restrict__ ce
     __shared__ int s_scan[8];
     const int tid = threadIdx.x;
     batch_frame(F, B, pair);
-    const size_t rbase = (size_t)pair * (B.cap > 0 ? B.cap : F.n);
+    const size_t rbase = (size_t)pair * B.cap;
     cell_start += (size_t)pair * (kGridCells + 1);
     rec += rbase; rdesc += rbase * 2; rur += rbase;
     for (int c = tid; c < kGridCells; c += 256) s_cnt[c] = 0;
@@ -209,7 +210,7 @@ __global__ __launch_bounds__(256) void k_window_search(DevFrame F, const int *__
                                                        const GridRec *__restrict__ rec, const uint4 *__restrict__ rdesc,
                                                        const float *__restrict__ rur,
                                                        const orbhip_query *__restrict__ q,
-                                                       const uint8_t *__restrict__ qdesc, int nq,
+                                                       const uint8_t *__restrict__ qdesc,
                                                        unsigned long long *__restrict__ cand,
                                                        unsigned long long *__restrict__ ccand,
                                                        int *__restrict__ cnt, int stride, int use_ur, Batch B,
@@ -221,7 +222,7 @@ __global__ __launch_bounds__(256) void k_window_search(DevFrame F, const int *__
     const int pair = blockIdx.y;
     const bool has_ur = F.u_right != nullptr;
     batch_frame(F, B, pair);
-    const size_t rbase = (size_t)pair * (B.cap > 0 ? B.cap : F.n);
+    const size_t rbase = (size_t)pair * B.cap;
     cell_start += (size_t)pair * (kGridCells + 1);
     rec += rbase; rdesc += rbase * 2; rur += rbase;
     q += (size_t)pair * B.qcap;
@@ -230,7 +231,7 @@ __global__ __launch_bounds__(256) void k_window_search(DevFrame F, const int *__
     ccand += (size_t)pair * B.qcap * kCompact;
     cnt += (size_t)pair * B.qcap;
     if (taken) taken += (size_t)pair * B.cap;
-    if (B.nq_dev) nq = min(B.nq_dev[pair], B.qcap);
+    const int nq = B.nq_dev ? min(B.nq_dev[pair], B.qcap) : B.qcap;
     const int qi = blockIdx.x * 4 + wv;
     if (qi >= nq) return;
     const orbhip_query Q = q[qi];
@@ -786,25 +787,7 @@ __global__ __launch_bounds__(256) void k_best_in_window(DevFrame F, const uint32
     }
 }
 
-// ---- resolve ---------------------------------------------------------------------------
-// mode 0: SearchByProjection(Frame,Frame)  ORBmatcher.cc:1397-1467
-// mode 1: SearchByProjection(Frame,points) ORBmatcher.cc:76-125
-// mode 2: SearchForInitialization          ORBmatcher.cc:432-511
-struct ResolveShared {
-    unsigned short block[kResolveMax];   // mode 0/1: slot taken (0/1); mode 2: vMatchedDistance (0xffff = INT_MAX)
-    int assign[kResolveMax];             // mode 0/1: assign[]; mode 2: vnMatches21
-    int m12[kResolveMax];                // mode 2: vnMatches12
-    unsigned char evbin[kResolveMax];    // rotation-histogram bin of the event of query i (0xff none)
-    unsigned short evidx[kResolveMax];   // mode 0: bestIdx2 pushed into rotHist
-    // read-only operands staged once so that the serial loop never waits on HBM
-    float t_angle[kResolveMax];          // train keypoint angle
-    float q_angle[kResolveMax];          // query keypoint angle
-    int q_cnt[kResolveMax];              // candidate count per query (sign = unsorted)
-    unsigned char t_oct[kResolveMax];    // train keypoint octave
-    unsigned char q_obs[kResolveMax];    // query map point observed
-    int hist[HISTO_LENGTH];
-};
-
+// ---- rotation histogram: bin of a match, three largest bins ------------------------------------
 __device__ __forceinline__ int rot_bin(float a1, float a2)
 {
     const float factor = 1.0f / HISTO_LENGTH;
@@ -815,43 +798,6 @@ __device__ __forceinline__ int rot_bin(float a1, float a2)
     // keypoint angles are caller data: outside [0, 360) (or NaN) the reference trips its assert(bin>=0 && bin<HISTO_LENGTH);
     // here such a match simply takes no part in the rotation histogram (-1) instead of writing outside it
     return (bin >= 0 && bin < HISTO_LENGTH) ? bin : -1;
-}
-
-// First / second usable candidate of a query.  `usable(idx, dist)` is evaluated by every lane.
-template <class Usable>
-__device__ __forceinline__ void pick2(const unsigned long long *list, unsigned long long v, int c, int lane, Usable usable,
-                                      unsigned long long &k1, unsigned long long &k2)
-{
-    k1 = ~0ull; k2 = ~0ull;
-    if (c > 0) {  // sorted, <= 64; `v` = list[lane], prefetched by the caller
-        bool u = lane < c && usable((int)(v & 0xfffffu), (int)(v >> 32));
-        unsigned long long bal = __ballot(u);
-        if (bal) {   // the winning lanes are wave-uniform: v_readlane, not a ds_bpermute round trip
-            const int l1 = __ffsll((long long)bal) - 1;
-            k1 = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), l1) << 32) |
-                 (unsigned)__builtin_amdgcn_readlane((int)v, l1);
-            bal &= bal - 1;
-            if (bal) {
-                const int l2 = __ffsll((long long)bal) - 1;
-                k2 = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), l2) << 32) |
-                     (unsigned)__builtin_amdgcn_readlane((int)v, l2);
-            }
-        }
-    } else if (c < 0) {  // unsorted: two masked min-reductions
-        c = -c;
-        unsigned long long m1 = ~0ull;
-        for (int i = lane; i < c; i += 64) {
-            unsigned long long v = list[i];
-            if (usable((int)(v & 0xfffffu), (int)(v >> 32))) m1 = v < m1 ? v : m1;
-        }
-        k1 = wave_min_u64(m1);
-        unsigned long long m2 = ~0ull;
-        for (int i = lane; i < c; i += 64) {
-            unsigned long long v = list[i];
-            if (v != k1 && usable((int)(v & 0xfffffu), (int)(v >> 32))) m2 = v < m2 ? v : m2;
-        }
-        k2 = wave_min_u64(m2);
-    }
 }
 
 __device__ __forceinline__ void three_maxima(const int *h, int &ind1, int &ind2, int &ind3)
@@ -873,143 +819,6 @@ __device__ __forceinline__ void three_maxima(const int *h, int &ind1, int &ind2,
     if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { i2 = -1; i3 = -1; }
     else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { i3 = -1; }
     ind1 = i1; ind2 = i2; ind3 = i3;
-}
-
-__global__ __launch_bounds__(64) void k_resolve(int mode, DevFrame F, const orbhip_keypoint *__restrict__ qkeys,
-                                                const orbhip_query *__restrict__ q, int nq,
-                                                const unsigned long long *__restrict__ cand,
-                                                const unsigned long long *__restrict__ ccand,
-                                                const int *__restrict__ cnt, int stride,
-                                                const uint8_t *__restrict__ taken_in, float nnratio,
-                                                int check_ori, int *__restrict__ out, int *__restrict__ out_n, Batch B)
-{
-    extern __shared__ unsigned char resolve_lds[];
-    ResolveShared &S = *reinterpret_cast<ResolveShared *>(resolve_lds);
-    const int lane = threadIdx.x;
-    if (B.qcap > 0) {   // batched (device-resident) call: one wavefront per pair
-        const int pair = blockIdx.x;
-        batch_frame(F, B, pair);
-        if (qkeys) qkeys += (size_t)(B.qd0 + pair * B.qds) * B.qcap;
-        q += (size_t)pair * B.qcap;
-        cand += (size_t)pair * B.qcap * stride;
-        ccand += (size_t)pair * B.qcap * kCompact;
-        cnt += (size_t)pair * B.qcap;
-        if (taken_in) taken_in += (size_t)pair * B.cap;
-        out += (size_t)pair * (mode == 2 ? B.qcap : B.cap);
-        out_n += pair;
-        if (B.nq_dev) nq = min(B.nq_dev[pair], B.qcap);
-    }
-    const int n = F.n;
-    for (int i = lane; i < n; i += 64) {
-        S.block[i] = (mode == 2) ? 0xffff : (unsigned short)(taken_in ? taken_in[i] != 0 : 0);
-        S.assign[i] = -1;
-        S.t_angle[i] = F.keys[i].angle;
-        S.t_oct[i] = (unsigned char)F.keys[i].octave;
-    }
-    for (int i = lane; i < nq; i += 64) {
-        S.evbin[i] = 0xff;
-        if (mode == 2) S.m12[i] = -1;
-        S.q_cnt[i] = cnt[i];
-        S.q_angle[i] = (mode == 2) ? qkeys[i].angle : q[i].angle;
-        S.q_obs[i] = (unsigned char)(mode == 2 ? 0 : (q[i].observed != 0));
-    }
-    if (lane < HISTO_LENGTH) S.hist[lane] = 0;
-    __syncthreads();
-    int nmatches = 0;
-    // software prefetch: the list head of query i+1 is in flight while query i is resolved
-    int c_next = nq > 0 ? S.q_cnt[0] : 0;
-    unsigned long long v_next = (c_next > 0 && lane < c_next) ? ccand[lane] : ~0ull;   // sorted lists live in the compact array
-    for (int i = 0; i < nq; ++i) {
-        const int c = c_next;
-        const unsigned long long v = v_next;
-        if (i + 1 < nq) {
-            c_next = S.q_cnt[i + 1];
-            v_next = (c_next > 0 && lane < c_next) ? ccand[(size_t)(i + 1) * kCompact + lane] : ~0ull;
-        }
-        if (c == 0) continue;
-        const unsigned long long *list = cand + (size_t)i * stride;
-        unsigned long long k1, k2;
-        if (mode == 2) pick2(list, v, c, lane, [&](int idx, int dist) { return !((int)S.block[idx] <= dist); }, k1, k2);
-        else pick2(list, v, c, lane, [&](int idx, int) { return S.block[idx] == 0; }, k1, k2);
-        if (k1 == ~0ull) continue;
-        const int bestDist = (int)(k1 >> 32), bestIdx = (int)(k1 & 0xfffffu);
-        if (mode == 0) {
-            if (bestDist <= TH_HIGH) {
-                if (lane == 0) {
-                    S.assign[bestIdx] = i;
-                    S.block[bestIdx] = (unsigned short)S.q_obs[i];
-                    if (check_ori) {
-                        int bin = rot_bin(S.q_angle[i], S.t_angle[bestIdx]);
-                        if (bin >= 0) {
-                            S.hist[bin]++;
-                            S.evbin[i] = (unsigned char)bin;
-                            S.evidx[i] = (unsigned short)bestIdx;
-                        }
-                    }
-                }
-                nmatches++;
-            }
-        } else if (mode == 1) {
-            if (bestDist <= TH_HIGH) {
-                const int bestDist2 = k2 == ~0ull ? 256 : (int)(k2 >> 32);
-                const int bestLevel = S.t_oct[bestIdx];
-                const int bestLevel2 = k2 == ~0ull ? -1 : (int)S.t_oct[(int)(k2 & 0xfffffu)];
-                if (!(bestLevel == bestLevel2 && (float)bestDist > __fmul_rn(nnratio, (float)bestDist2))) {
-                    if (lane == 0) {
-                        S.assign[bestIdx] = i;
-                        S.block[bestIdx] = (unsigned short)S.q_obs[i];
-                    }
-                    nmatches++;
-                }
-            }
-        } else {
-            if (bestDist <= TH_LOW) {
-                // bestDist < (float)bestDist2 * mfNNratio with bestDist2 = INT_MAX when absent
-                const float d2 = k2 == ~0ull ? (float)INT_MAX : (float)(int)(k2 >> 32);
-                if ((float)bestDist < __fmul_rn(d2, nnratio)) {
-                    const int prev = S.assign[bestIdx];  // vnMatches21
-                    if (prev >= 0) nmatches--;
-                    if (lane == 0) {
-                        if (prev >= 0) S.m12[prev] = -1;
-                        S.m12[i] = bestIdx;
-                        S.assign[bestIdx] = i;
-                        S.block[bestIdx] = (unsigned short)bestDist;
-                        if (check_ori) {
-                            int bin = rot_bin(S.q_angle[i], S.t_angle[bestIdx]);
-                            if (bin >= 0) { S.hist[bin]++; S.evbin[i] = (unsigned char)bin; }
-                        }
-                    }
-                    nmatches++;
-                }
-            }
-        }
-        // single wavefront: DS operations execute in issue order, so the next query's LDS reads see lane 0's
-        // writes; no s_barrier / vmcnt(0) here -- it would drain the prefetch of the next list head
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    if (check_ori && mode != 1) {
-        int ind1, ind2, ind3;
-        three_maxima(S.hist, ind1, ind2, ind3);
-        // events are independent of each other: every one in a losing bin clears its slot
-        int dec = 0;
-        if (mode == 0) {
-            for (int i = lane; i < nq; i += 64) {
-                int b = S.evbin[i];
-                if (b != 0xff && b != ind1 && b != ind2 && b != ind3) { S.assign[S.evidx[i]] = -1; dec++; }
-            }
-        } else {
-            for (int i = lane; i < nq; i += 64) {
-                int b = S.evbin[i];
-                if (b != 0xff && b != ind1 && b != ind2 && b != ind3 && S.m12[i] >= 0) { S.m12[i] = -1; dec++; }
-            }
-        }
-        nmatches -= wave_reduce_add_i(dec);
-    }
-    __syncthreads();
-    if (mode == 2) for (int i = lane; i < nq; i += 64) out[i] = S.m12[i];
-    else for (int i = lane; i < n; i += 64) out[i] = S.assign[i];
-    if (lane == 0) *out_n = nmatches;
 }
 
 // ---- parallel resolve: modes 0 / 1 (SearchByProjection overloads) and 4 (SearchForTriangulation: one pre-gated
@@ -1075,7 +884,7 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
                                                       const uint8_t *__restrict__ taken_in, float nnratio,
                                                       int check_ori, int *__restrict__ out, int *__restrict__ out_n, Batch B,
                                                       int th_accept, int all_block, unsigned char *__restrict__ gstate,
-                                                      size_t gstate_stride, int n_alloc, int nq_alloc, int lcn)
+                                                      size_t gstate_stride, int lcn)
 {
     extern __shared__ unsigned char resolve_lds[];
     const int tid = threadIdx.x, T = blockDim.x;
@@ -1094,7 +903,7 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
     const int n = F.n;
     ResolveParState S;
     if (GS) resolve_par_carve(S, gstate + (size_t)blockIdx.x * gstate_stride, (size_t)n, (size_t)nq);
-    else resolve_par_carve(S, resolve_lds, (size_t)n_alloc, (size_t)nq_alloc, lcn);
+    else resolve_par_carve(S, resolve_lds, (size_t)B.cap, (size_t)B.qcap, lcn);   // laid out for the capacities
     int *holder = S.owner[0];
     unsigned short *cur1 = S.cur1, *cur2 = S.cur2;
     // The list heads of this thread's first query are requested before anything else, without waiting for the list
@@ -1466,8 +1275,7 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
 // Jacobi iteration reaches it (query i is final once all j < i are).  A round rebuilds, per slot, a linked list of this
 // round's claimants (atomicExch on the slot's head); the next round's queries walk the list of a candidate slot and take
 // the minimum claimed distance among the claimants with a smaller index.  One workgroup per pair, state in LDS
-// (n, nq <= 4096: the limit the entry points already state); the serial replay (k_resolve mode 2) this replaces took
-// about 200 ns per query on one wavefront.
+// (n, nq <= kResolveMax: the limit the entry points already state, and the state fits the LDS budget there).
 struct InitState {
     int *q_cnt; float *q_angle, *t_angle;
     uint32_t *claim[2];          // per query: distance << 20 | slot, or kNoClaim
@@ -1481,7 +1289,7 @@ struct InitState {
     uint32_t *lc; int lcn;
 };
 constexpr uint32_t kNoClaim = 0xffffffffu;
-__host__ __device__ inline size_t init_state_bytes(size_t n, size_t nq, size_t lcn)
+__host__ __device__ constexpr size_t init_state_bytes(size_t n, size_t nq, size_t lcn)
 {
     n = (n + 3) & ~(size_t)3; nq = (nq + 3) & ~(size_t)3;
     return nq * 4 + nq * 4 + n * 4 + 2 * nq * 4 + 2 * n * 4 + 2 * nq * 2 + nq + 4 * nq + (HISTO_LENGTH + 2 + 64) * 4 + (lcn ? nq * (lcn + 1) * 4 : 0);
@@ -1490,12 +1298,11 @@ __global__ __launch_bounds__(1024) void k_resolve_init(DevFrame F, const orbhip_
                                                        const unsigned long long *__restrict__ cand,
                                                        const unsigned long long *__restrict__ ccand,
                                                        const int *__restrict__ cnt, int stride, float nnratio, int check_ori,
-                                                       int *__restrict__ out, int *__restrict__ out_n, Batch B, int n_alloc,
-                                                       int nq_alloc, int lcn)
+                                                       int *__restrict__ out, int *__restrict__ out_n, Batch B, int lcn)
 {
     extern __shared__ unsigned char resolve_lds[];
     const int tid = threadIdx.x, T = blockDim.x;
-    if (B.qcap > 0) {   // batched (device-resident) call: one workgroup per pair
+    {
         const int pair = blockIdx.x;
         batch_frame(F, B, pair);
         if (qkeys) qkeys += (size_t)(B.qd0 + pair * B.qds) * B.qcap;
@@ -1508,8 +1315,8 @@ __global__ __launch_bounds__(1024) void k_resolve_init(DevFrame F, const orbhip_
     }
     const int n = F.n;
     InitState S;
-    {
-        const size_t na = ((size_t)n_alloc + 3) & ~(size_t)3, nqa = ((size_t)nq_alloc + 3) & ~(size_t)3;
+    {   // laid out for the capacities
+        const size_t na = ((size_t)B.cap + 3) & ~(size_t)3, nqa = ((size_t)B.qcap + 3) & ~(size_t)3;
         int *p = reinterpret_cast<int *>(resolve_lds);
         S.q_cnt = p; p += nqa;
         S.q_angle = reinterpret_cast<float *>(p); p += nqa;
@@ -1970,12 +1777,12 @@ __device__ __forceinline__ float det_logf(float xf)
 struct ProjBatch {
     const float *Tcw, *Tlw;            // [pairs][12]
     const orbhip_keypoint *keys;       // [frames][cap]
-    const int *n_dev;                  // [frames] or null (use n)
+    const int *n_dev;                  // [frames]
     const float *world;                // [frames][cap][3]
     const uint8_t *flags;              // [frames][cap]
     orbhip_query *q;                   // [pairs][cap]
     int *nq;                           // [pairs] or null
-    int n, cap, l0, ls;
+    int cap, l0, ls;
 };
 
 // src/ORBmatcher.cc:1339-1390
@@ -1983,7 +1790,7 @@ __device__ __forceinline__ void project_last_frame_body(const ProjBatch &B, cons
                                                         const int pair, const int i)
 {
     const size_t fl = (size_t)(B.l0 + pair * B.ls);
-    const int n = B.n_dev ? min(B.n_dev[fl], B.cap) : B.n;
+    const int n = min(B.n_dev[fl], B.cap);
     if (i == 0 && B.nq) B.nq[pair] = n;
     if (i >= n) return;
     const float *Tcw = B.Tcw + (size_t)pair * 12, *Tlw = B.Tlw + (size_t)pair * 12;
@@ -2043,20 +1850,20 @@ struct ProjLaunch { ProjBatch P; orbhip_camera cam; float th; int mono; };
 
 struct FrustumBatch {
     const float *Tcw;                       // [frames][12]
-    const int *np_dev;                      // [frames] or null (use n)
+    const int *np_dev;                      // [frames]
     const float *world, *normal;            // [frames][pcap][3]
     const float *max_dist, *min_dist;       // [frames][pcap]
     const uint8_t *flags;                   // [frames][pcap]
     orbhip_query *q;                        // [frames][pcap]
     float *view_cos;                        // [frames][pcap] or null
-    int n, pcap;
+    int pcap;
 };
 
 // src/Frame.cc:269-325, src/MapPoint.cc:400-418, src/ORBmatcher.cc:52-69, :131-137
 __global__ __launch_bounds__(256) void k_frustum_queries(FrustumBatch B, orbhip_camera cam, float cos_limit, float th)
 {
     const int fr = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    const int n = B.np_dev ? min(B.np_dev[fr], B.pcap) : B.n;
+    const int n = min(B.np_dev[fr], B.pcap);
     if (i >= n) return;
     const size_t e = (size_t)fr * B.pcap + i;
     const float *Tcw = B.Tcw + (size_t)fr * 12;
@@ -2232,7 +2039,7 @@ struct StereoScales;
 static StereoScales stereo_scales(const StereoGeom &G);
 // Batched stereo: pair p uses frame l0 + p*ls of the left arrays/pyramids and r0 + p*rs of the right ones.
 struct StereoBatch {
-    const int *n_l, *n_r;   // per-frame keypoint counts on the device, or null (use the nl / nr arguments)
+    const int *n_l, *n_r;   // per-frame keypoint counts on the device
     int l0, ls, r0, rs;     // frame index mapping
     int cap;                // keypoint stride per frame
     unsigned fb_l, fb_r;    // pyramid bytes per frame of the two extractor handles
@@ -2255,7 +2062,7 @@ __global__ __launch_bounds__(256) void k_stereo_sort(const orbhip_keypoint *__re
     kr += (size_t)fr * B.cap;
     rowstart += (size_t)pair * (nrows + 1);
     order += (size_t)pair * B.cap;
-    if (B.n_r) nr = min(B.n_r[fr], B.cap);
+    if (B.n_r) nr = min(B.n_r[fr], B.cap);   // always set; the test is kept because dropping it costs the kernel an SGPR
     for (int r = tid; r < nrows; r += 256) s_cnt[r] = 0;
     __syncthreads();
     for (int i = tid; i < nr; i += 256) atomicAdd(&s_cnt[min(max((int)floorf(kr[i].y), 0), nrows - 1)], 1);
@@ -2288,9 +2095,9 @@ __global__ __launch_bounds__(256) void k_stereo_sort(const orbhip_keypoint *__re
 }
 
 __global__ __launch_bounds__(256) void k_stereo_match(const orbhip_keypoint *__restrict__ kl,
-                                                      const uint8_t *__restrict__ dl, int nl,
+                                                      const uint8_t *__restrict__ dl,
                                                       const orbhip_keypoint *__restrict__ kr,
-                                                      const uint8_t *__restrict__ dr, int nr,
+                                                      const uint8_t *__restrict__ dr,
                                                       const int *__restrict__ rowstart, const int4 *__restrict__ order, int R,
                                                       StereoGeom G,
                                                       float *__restrict__ uRight, float *__restrict__ depth,
@@ -2298,6 +2105,7 @@ __global__ __launch_bounds__(256) void k_stereo_match(const orbhip_keypoint *__r
 {
     const int lane = threadIdx.x & 63;
     size_t pyr_off_l, pyr_off_r;   // this pair's frames inside the two pyramid batches
+    int nl, nr;
     {
         const int pair = blockIdx.y, fl = B.l0 + pair * B.ls, fr = B.r0 + pair * B.rs;
         pyr_off_l = (size_t)fl * B.fb_l; pyr_off_r = (size_t)fr * B.fb_r;
@@ -2305,8 +2113,8 @@ __global__ __launch_bounds__(256) void k_stereo_match(const orbhip_keypoint *__r
         kr += (size_t)fr * B.cap; dr += (size_t)fr * B.cap * 32;
         if (rowstart) { rowstart += (size_t)pair * (G.nrows + 1); order += (size_t)pair * B.cap; }
         uRight += (size_t)pair * B.cap; depth += (size_t)pair * B.cap; sad += (size_t)pair * B.cap;
-        if (B.n_l) nl = min(B.n_l[fl], B.cap);
-        if (B.n_r) nr = min(B.n_r[fr], B.cap);
+        nl = min(B.n_l[fl], B.cap);
+        nr = min(B.n_r[fr], B.cap);
     }
     const int iL = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (iL >= nl) return;
@@ -2480,16 +2288,17 @@ static StereoScales stereo_scales(const StereoGeom &G)
 
 // median-based outlier cull (:626-639): thDist = 1.5f*1.4f*median of the SAD list sorted by
 // (dist, iL); entries with dist >= thDist are removed.
-__global__ __launch_bounds__(256) void k_stereo_cull(int nl, const int *__restrict__ sad, float *__restrict__ uRight,
+__global__ __launch_bounds__(256) void k_stereo_cull(const int *__restrict__ sad, float *__restrict__ uRight,
                                                      float *__restrict__ depth, int *__restrict__ out_n, StereoBatch B)
 {
     __shared__ int s_nd, s_med, s_cnt;
     const int tid = threadIdx.x;
+    int nl;
     {
         const int pair = blockIdx.x;
         sad += (size_t)pair * B.cap; uRight += (size_t)pair * B.cap; depth += (size_t)pair * B.cap;
         out_n += pair;
-        if (B.n_l) nl = min(B.n_l[B.l0 + pair * B.ls], B.cap);
+        nl = min(B.n_l[B.l0 + pair * B.ls], B.cap);
     }
     if (tid == 0) { s_nd = 0; s_med = 0; s_cnt = 0; }
     __syncthreads();
@@ -2580,15 +2389,35 @@ struct orbhip_matcher {
 
 static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// The inputs of a call, gathered in the pinned staging buffer and sent in one copy by stage_commit.  Every piece starts
+// on a 256-byte boundary.  A piece that would pass the size given to stage_begin is refused (null pointers) and the call
+// fails with ORBHIP_E_CAPACITY instead of writing past the buffer.
 struct Stage {
     uint8_t *h, *d;
-    size_t off;
-    void *put(const void *src, size_t bytes)
+    size_t off, cap;
+    bool overrun;
+    // room for `count` T, filled in place: returns the host address, *dev the device address of the same bytes
+    template <class T> T *take(size_t count, const T **dev)
     {
-        void *dev = d + off;
-        if (bytes) memcpy(h + off, src, bytes);
-        off += al256(bytes);
+        const size_t bytes = al256(count * sizeof(T));
+        if (overrun || bytes > cap - off) { overrun = true; *dev = nullptr; return nullptr; }
+        *dev = reinterpret_cast<const T *>(d + off);
+        T *host = reinterpret_cast<T *>(h + off);
+        off += bytes;
+        return host;
+    }
+    template <class T> const T *put(const T *src, size_t count)   // a copy of src[0 .. count)
+    {
+        const T *dev;
+        T *host = take(count, &dev);
+        if (host && count) memcpy(host, src, count * sizeof(T));
         return dev;
+    }
+    int status() const
+    {
+        if (!overrun) return ORBHIP_OK;
+        set_error("matcher: staged inputs exceed the %zu bytes reserved for them", cap);
+        return ORBHIP_E_CAPACITY;
     }
 };
 
@@ -2610,33 +2439,38 @@ enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_
 
 static int stage_begin(orbhip_matcher *m, size_t total, Stage *st)
 {
-    total = al256(total) + 256;
+    total = al256(total);
     ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));   // previous call's staging is free
-    if (total > m->h_stage_bytes) {
+    if (total + 256 > m->h_stage_bytes) {
         if (m->h_stage) (void)hipHostFree(m->h_stage);
         m->h_stage = nullptr; m->h_stage_bytes = 0;
-        ORBHIP_HIP_CHECK(hipHostMalloc((void **)&m->h_stage, total, hipHostMallocDefault));
-        m->h_stage_bytes = total;
+        ORBHIP_HIP_CHECK(hipHostMalloc((void **)&m->h_stage, total + 256, hipHostMallocDefault));
+        m->h_stage_bytes = total + 256;
     }
     void *d;
-    int rc = scratch(m, S_MISC, total, &d);
+    int rc = scratch(m, S_MISC, total + 256, &d);
     if (rc) return rc;
-    st->h = m->h_stage; st->d = (uint8_t *)d; st->off = 0;
+    st->h = m->h_stage; st->d = (uint8_t *)d; st->off = 0; st->cap = total; st->overrun = false;
     return ORBHIP_OK;
 }
 static int stage_commit(orbhip_matcher *m, Stage *st)
 {
+    if (int rc = st->status()) return rc;
     ORBHIP_HIP_CHECK(hipMemcpyAsync(st->d, st->h, st->off, hipMemcpyHostToDevice, m->stream));
     return ORBHIP_OK;
 }
-static int out_buffer(orbhip_matcher *m, size_t bytes, uint8_t **h)
+// The outputs of a call, `bytes` at d, in one copy to the pinned out-buffer: *h = its host address once the stream drained
+static int read_back(orbhip_matcher *m, const void *d, size_t bytes, const uint8_t **h)
 {
+    ORBHIP_HIP_CHECK(hipGetLastError());
     if (bytes > m->h_out_bytes) {
         if (m->h_out) (void)hipHostFree(m->h_out);
         m->h_out = nullptr; m->h_out_bytes = 0;
         ORBHIP_HIP_CHECK(hipHostMalloc((void **)&m->h_out, bytes, hipHostMallocDefault));
         m->h_out_bytes = bytes;
     }
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(m->h_out, d, bytes, hipMemcpyDeviceToHost, m->stream));
+    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
     *h = m->h_out;
     return ORBHIP_OK;
 }
@@ -2644,8 +2478,6 @@ static int out_buffer(orbhip_matcher *m, size_t bytes, uint8_t **h)
 static int ensure_resolve_attr(orbhip_matcher *m)
 {
     if (!m->lds_attr_set) {   // > 64 KB of dynamic LDS needs the opt-in attribute (per device)
-        ORBHIP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)sizeof(ResolveShared)));
         ORBHIP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve_par<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                              kResolveLdsBudget));
         ORBHIP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve_init), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2655,86 +2487,90 @@ static int ensure_resolve_attr(orbhip_matcher *m)
     return ORBHIP_OK;
 }
 
-// SearchForInitialization's resolve: the parallel kernel while its state fits the LDS budget (always, within the
-// 4096-keypoint limit of the entry points), the serial replay otherwise
-static void launch_resolve_init(orbhip_matcher *m, int pairs, const DevFrame &D, const orbhip_keypoint *d_qkeys, const orbhip_query *d_q,
-                                int nq, int n_train, const unsigned long long *d_cand, const unsigned long long *d_ccand,
-                                const int *d_cnt, int stride, float nnratio, int check_ori, int *d_out, int *d_out_n, const Batch &B)
-{
-    const size_t bare = init_state_bytes((size_t)n_train, (size_t)nq, 0);
-    if (n_train <= kResolveMax && nq <= kResolveMax && bare <= (size_t)kResolveLdsBudget) {
-        const int lcn = init_state_bytes((size_t)n_train, (size_t)nq, kResolveHead) <= (size_t)kResolveLdsBudget ? kResolveHead : 0;
-        hipLaunchKernelGGL(k_resolve_init, dim3(pairs), dim3(1024), init_state_bytes((size_t)n_train, (size_t)nq, (size_t)lcn), m->stream,
-                           D, d_qkeys, nq, d_cand, d_ccand, d_cnt, stride, nnratio, check_ori, d_out, d_out_n, B, n_train, nq, lcn);
-    } else {
-        hipLaunchKernelGGL(k_resolve, dim3(pairs), dim3(64), sizeof(ResolveShared), m->stream, 2, D, d_qkeys, d_q, nq, d_cand, d_ccand,
-                           d_cnt, stride, (const uint8_t *)nullptr, nnratio, check_ori, d_out, d_out_n, B);
-    }
-}
+// SearchForInitialization's state always fits the LDS budget within the kResolveMax limit of its entry points
+static_assert(init_state_bytes(kResolveMax, kResolveMax, 0) <= (size_t)kResolveLdsBudget, "k_resolve_init state exceeds LDS");
 
-// launch of the parallel resolve: LDS state up to kResolveMax train keypoints / queries, HBM state beyond
-static int launch_resolve_par(orbhip_matcher *m, int pairs, int mode, const DevFrame &D, const orbhip_query *d_q, int nq,
-                              int n_train, const unsigned long long *d_cand, const unsigned long long *d_ccand,
-                              const int *d_cnt, int stride,
+// launch of the parallel resolve, sized by the batch's capacities: LDS state up to kResolveMax train keypoints / queries,
+// HBM state beyond
+static int launch_resolve_par(orbhip_matcher *m, int pairs, int mode, const DevFrame &D, const orbhip_query *d_q,
+                              const unsigned long long *d_cand, const unsigned long long *d_ccand, const int *d_cnt, int stride,
                               const uint8_t *d_taken, float nnratio, int check_ori, int *d_out, int *d_out_n, const Batch &B,
                               int th_accept, int all_block)
 {
-    const int threads = 1024;
-    if (n_train <= kResolveMax && nq <= kResolveMax) {
-        // LDS state sized by the batch's capacities; the list heads go to LDS when the budget allows
-        const size_t state = resolve_par_bytes((size_t)n_train, (size_t)nq, 0);
-        const int lcn = resolve_par_bytes((size_t)n_train, (size_t)nq, kResolveHead) <= (size_t)kResolveLdsBudget ? kResolveHead : 0;
-        (void)state;
-        hipLaunchKernelGGL(k_resolve_par<false>, dim3(pairs), dim3(threads), resolve_par_bytes((size_t)n_train, (size_t)nq, (size_t)lcn),
-                           m->stream, mode, D, d_q, nq, d_cand, d_ccand, d_cnt, stride, d_taken, nnratio, check_ori, d_out, d_out_n, B,
-                           th_accept, all_block, (unsigned char *)nullptr, (size_t)0, n_train, nq, lcn);
+    if (B.cap <= kResolveMax && B.qcap <= kResolveMax) {
+        // the list heads go to LDS when the budget allows
+        const int lcn = resolve_par_bytes((size_t)B.cap, (size_t)B.qcap, kResolveHead) <= (size_t)kResolveLdsBudget ? kResolveHead : 0;
+        hipLaunchKernelGGL(k_resolve_par<false>, dim3(pairs), dim3(1024), resolve_par_bytes((size_t)B.cap, (size_t)B.qcap, (size_t)lcn),
+                           m->stream, mode, D, d_q, B.qcap, d_cand, d_ccand, d_cnt, stride, d_taken, nnratio, check_ori, d_out, d_out_n, B,
+                           th_accept, all_block, (unsigned char *)nullptr, (size_t)0, lcn);
     } else {
-        const size_t per = al256(resolve_par_bytes((size_t)n_train, (size_t)nq));
+        const size_t per = al256(resolve_par_bytes((size_t)B.cap, (size_t)B.qcap));
         void *p;
         int rc = scratch(m, S_STATE, per * (size_t)pairs, &p);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_resolve_par<true>, dim3(pairs), dim3(1024), 0, m->stream, mode, D, d_q, nq, d_cand, d_ccand, d_cnt,
-                           stride, d_taken, nnratio, check_ori, d_out, d_out_n, B, th_accept, all_block, (unsigned char *)p, per, 0, 0, 0);
+        hipLaunchKernelGGL(k_resolve_par<true>, dim3(pairs), dim3(1024), 0, m->stream, mode, D, d_q, B.qcap, d_cand, d_ccand, d_cnt,
+                           stride, d_taken, nnratio, check_ori, d_out, d_out_n, B, th_accept, all_block, (unsigned char *)p, per, 0);
     }
     return ORBHIP_OK;
 }
 
-// CSR grid of the train frames + the cell-window search: candidates of every query
-static int launch_window_search(orbhip_matcher *m, int pairs, const DevFrame &D, int n_train_cap, const orbhip_query *d_q,
-                                const uint8_t *d_qdesc, int nq, unsigned long long *d_cand, int *d_cnt, int stride, int use_ur,
-                                const Batch &B, unsigned long long **d_ccand_out, const uint8_t *d_taken, int max_dist,
-                                const ProjLaunch *proj = nullptr)
+// The windowed searches, `pairs` pairs of batch B (D.n = B.cap): CSR grid of the train frames (the projection prologue
+// rides in that launch when `proj` is given), the cell-window search, then the resolve -- k_resolve_par for modes 0 / 1
+// (SearchByProjection overloads), k_resolve_init for mode 2 (SearchForInitialization, query keypoints d_qkeys).
+// Modes 0 / 1 only: d_taken (slots blocked on entry, nullable), th_accept (acceptance distance of mode 0), all_block
+// (every accepted match blocks its slot, not only observed ones), use_ur (stereo gate).  Outputs d_out, d_out_n.
+static int launch_search(orbhip_matcher *m, int mode, int pairs, const DevFrame &D, const Batch &B, const orbhip_query *d_q,
+                         const uint8_t *d_qdesc, const orbhip_keypoint *d_qkeys, const uint8_t *d_taken, float nnratio,
+                         int check_ori, int th_accept, int all_block, int use_ur, int *d_out, int *d_out_n,
+                         const ProjLaunch *proj = nullptr)
 {
     void *p;
     int rc;
+    const int stride = (B.cap + 1) & ~1;
+    const size_t nql = (size_t)pairs * B.qcap;   // query lists
+    if ((rc = scratch(m, S_CAND, nql * stride * sizeof(unsigned long long), &p))) return rc;
+    unsigned long long *d_cand = (unsigned long long *)p;
+    if ((rc = scratch(m, S_CNT, nql * sizeof(int), &p))) return rc;
+    int *d_cnt = (int *)p;
+    if ((rc = scratch(m, S_CCAND, nql * kCompact * sizeof(unsigned long long), &p))) return rc;
+    unsigned long long *d_ccand = (unsigned long long *)p;
     // CSR workspace per pair: cell table, records (16 B), descriptors (32 B), uRight (4 B) in CSR order
     const size_t start_bytes = al256((size_t)pairs * (kGridCells + 1) * sizeof(int));
-    const size_t nrec = (size_t)pairs * n_train_cap;
+    const size_t nrec = (size_t)pairs * B.cap;
     if ((rc = scratch(m, S_CSR, start_bytes + al256(nrec * sizeof(GridRec)) + al256(nrec * 32) + al256(nrec * 4), &p))) return rc;
     static_assert(sizeof(GridRec) == 16, "GridRec is one dwordx4");
     int *d_start = (int *)p;
     GridRec *d_rec = (GridRec *)((uint8_t *)p + start_bytes);
     uint4 *d_rdesc = (uint4 *)((uint8_t *)d_rec + al256(nrec * sizeof(GridRec)));
     float *d_rur = (float *)((uint8_t *)d_rdesc + al256(nrec * 32));
-    if ((rc = scratch(m, S_CCAND, (size_t)pairs * nq * kCompact * sizeof(unsigned long long), &p))) return rc;
-    unsigned long long *d_ccand = (unsigned long long *)p;
-    if (proj) {   // the projection prologue rides in the grid launch
+    if ((rc = ensure_resolve_attr(m))) return rc;
+    if (mode == 2) { d_taken = nullptr; use_ur = 0; }
+    if (proj) {
         const int npb = (proj->P.cap + 255) / 256;
         hipLaunchKernelGGL(k_grid_build_project, dim3(pairs * (npb + 1)), dim3(256), 0, m->stream, D, d_start, d_rec, d_rdesc, d_rur, B,
                            proj->P, proj->cam, proj->th, proj->mono, npb);
     } else {
         hipLaunchKernelGGL(k_grid_build, dim3(pairs), dim3(256), 0, m->stream, D, d_start, d_rec, d_rdesc, d_rur, B);
     }
-    hipLaunchKernelGGL(k_window_search, dim3((nq + 3) / 4, pairs), dim3(256), 0, m->stream, D, d_start, d_rec, d_rdesc, d_rur, d_q,
-                       d_qdesc, nq, d_cand, d_ccand, d_cnt, stride, use_ur, B, d_taken, max_dist);
-    *d_ccand_out = d_ccand;
+    // searches that take the best candidate alone list nothing beyond their acceptance threshold
+    hipLaunchKernelGGL(k_window_search, dim3((B.qcap + 3) / 4, pairs), dim3(256), 0, m->stream, D, d_start, d_rec, d_rdesc, d_rur,
+                       d_q, d_qdesc, d_cand, d_ccand, d_cnt, stride, use_ur, B, d_taken, mode == 0 ? th_accept : 256);
+    if (mode == 2) {   // match stealing depends on the running minimum distance per slot
+        const int lcn = init_state_bytes((size_t)B.cap, (size_t)B.qcap, kResolveHead) <= (size_t)kResolveLdsBudget ? kResolveHead : 0;
+        hipLaunchKernelGGL(k_resolve_init, dim3(pairs), dim3(1024), init_state_bytes((size_t)B.cap, (size_t)B.qcap, (size_t)lcn),
+                           m->stream, D, d_qkeys, B.qcap, d_cand, d_ccand, d_cnt, stride, nnratio, check_ori, d_out, d_out_n, B, lcn);
+    } else if ((rc = launch_resolve_par(m, pairs, mode, D, d_q, d_cand, d_ccand, d_cnt, stride, d_taken, nnratio, check_ori, d_out,
+                                        d_out_n, B, th_accept, all_block))) {
+        return rc;
+    }
+    ORBHIP_HIP_CHECK(hipGetLastError());
     return ORBHIP_OK;
 }
 
-// shared driver of the three windowed searches.  Modes 0 / 1 (the SearchByProjection family): queries with valid == 0
-// (no map point, not in view, ...) never reach the device -- local maps and loop-closing point sets are mostly that --
-// and there is no size limit (beyond kResolveMax the resolve state moves from LDS to HBM).  Mode 2
-// (SearchForInitialization) replays the match stealing on one wavefront with its state in LDS: <= kResolveMax.
+// Host-pointer windowed searches, one pair.  Modes 0 / 1 (the SearchByProjection family): queries with valid == 0 (no
+// map point, not in view, ...) never reach the device -- local maps and loop-closing point sets are mostly that -- and
+// there is no size limit (beyond kResolveMax the resolve state moves from LDS to HBM).  Mode 2 (SearchForInitialization)
+// keeps its state in LDS: <= kResolveMax.
 static int run_search(orbhip_matcher *m, int mode, const orbhip_frame_view *train, const orbhip_query *q,
                       const uint8_t *qdesc, const orbhip_keypoint *qkeys, int nq, const uint8_t *taken,
                       float nnratio, int check_ori, int32_t *out, int nout, int *nmatches, int th_accept = TH_HIGH,
@@ -2766,55 +2602,39 @@ static int run_search(orbhip_matcher *m, int mode, const orbhip_frame_view *trai
                                  al256((size_t)nqv * sizeof(orbhip_keypoint)), &st))) return rc;
     DevFrame D;
     D.n = train->n; D.min_x = train->min_x; D.min_y = train->min_y; D.inv_w = train->grid_inv_w; D.inv_h = train->grid_inv_h;
-    D.keys = (const orbhip_keypoint *)st.put(train->keys, n * sizeof(orbhip_keypoint));
-    D.desc = (const uint8_t *)st.put(train->desc, n * 32);
-    D.u_right = train->u_right ? (const float *)st.put(train->u_right, n * sizeof(float)) : nullptr;
-    const uint8_t *d_taken = taken ? (const uint8_t *)st.put(taken, n) : nullptr;
+    D.keys = st.put(train->keys, n);
+    D.desc = st.put(train->desc, n * 32);
+    D.u_right = train->u_right ? st.put(train->u_right, n) : nullptr;
+    const uint8_t *d_taken = taken ? st.put(taken, n) : nullptr;
     const orbhip_query *d_q;
     const uint8_t *d_qdesc;
     if (compact) {
-        orbhip_query *hq = reinterpret_cast<orbhip_query *>(st.h + st.off);
-        d_q = (const orbhip_query *)st.put(nullptr, 0);
-        for (int k = 0; k < nqv; ++k) hq[k] = q[vidx[k]];
-        st.off += al256((size_t)nqv * sizeof(orbhip_query));
-        uint8_t *hd = st.h + st.off;
-        d_qdesc = (const uint8_t *)st.put(nullptr, 0);
-        for (int k = 0; k < nqv; ++k) memcpy(hd + (size_t)k * 32, qdesc + (size_t)vidx[k] * 32, 32);
-        st.off += al256((size_t)nqv * 32);
+        orbhip_query *hq = st.take((size_t)nqv, &d_q);
+        uint8_t *hd = st.take((size_t)nqv * 32, &d_qdesc);
+        if ((rc = st.status())) return rc;
+        for (int k = 0; k < nqv; ++k) {
+            hq[k] = q[vidx[k]];
+            memcpy(hd + (size_t)k * 32, qdesc + (size_t)vidx[k] * 32, 32);
+        }
     } else {
-        d_q = (const orbhip_query *)st.put(q, (size_t)nq * sizeof(orbhip_query));
-        d_qdesc = (const uint8_t *)st.put(qdesc, (size_t)nq * 32);
+        d_q = st.put(q, (size_t)nq);
+        d_qdesc = st.put(qdesc, (size_t)nq * 32);
     }
-    const orbhip_keypoint *d_qkeys = qkeys ? (const orbhip_keypoint *)st.put(qkeys, (size_t)nq * sizeof(orbhip_keypoint)) : nullptr;
+    const orbhip_keypoint *d_qkeys = qkeys ? st.put(qkeys, (size_t)nq) : nullptr;
     if ((rc = stage_commit(m, &st))) return rc;
     void *p;
-    const int stride = (train->n + 1) & ~1;
-    if ((rc = scratch(m, S_CAND, (size_t)nqv * stride * sizeof(unsigned long long), &p))) return rc;
-    unsigned long long *d_cand = (unsigned long long *)p;
-    if ((rc = scratch(m, S_CNT, (size_t)nqv * sizeof(int), &p))) return rc;
-    int *d_cnt = (int *)p;
     if ((rc = scratch(m, S_OUT, (size_t)(nout + 1) * sizeof(int), &p))) return rc;
     int *d_out = (int *)p;
-    uint8_t *h_out;
-    if ((rc = out_buffer(m, (size_t)(nout + 1) * sizeof(int), &h_out))) return rc;
-    const Batch one = {nullptr, nullptr, 0, 0};
-    unsigned long long *d_ccand;
-    if ((rc = launch_window_search(m, 1, D, train->n, d_q, d_qdesc, nqv, d_cand, d_cnt, stride, mode != 2 && use_ur, one, &d_ccand,
-                                   mode != 2 ? d_taken : nullptr, mode == 0 ? th_accept : 256)))
+    const Batch B = {nullptr, nullptr, train->n, nqv};
+    if ((rc = launch_search(m, mode, 1, D, B, d_q, d_qdesc, d_qkeys, d_taken, nnratio, check_ori, th_accept, all_block, use_ur,
+                            d_out, d_out + nout)))
         return rc;
-    if ((rc = ensure_resolve_attr(m))) return rc;
-    if (mode == 2)   // SearchForInitialization: match stealing depends on the running minimum distance per slot
-        launch_resolve_init(m, 1, D, d_qkeys, d_q, nq, train->n, d_cand, d_ccand, d_cnt, stride, nnratio, check_ori, d_out, d_out + nout, one);
-    else if ((rc = launch_resolve_par(m, 1, mode, D, d_q, nqv, train->n, d_cand, d_ccand, d_cnt, stride, d_taken, nnratio, check_ori,
-                                      d_out, d_out + nout, one, th_accept, all_block)))
-        return rc;
-    ORBHIP_HIP_CHECK(hipGetLastError());
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_out, d_out, (size_t)(nout + 1) * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
-    memcpy(out, h_out, (size_t)nout * sizeof(int));
+    const uint8_t *h;
+    if ((rc = read_back(m, d_out, (size_t)(nout + 1) * sizeof(int), &h))) return rc;
+    memcpy(out, h, (size_t)nout * sizeof(int));
     if (compact)   // slots hold indices into the compacted query list: map them back
         for (int i = 0; i < nout; ++i) if (out[i] >= 0) out[i] = vidx[out[i]];
-    *nmatches = reinterpret_cast<const int *>(h_out)[nout];
+    *nmatches = reinterpret_cast<const int *>(h)[nout];
     return ORBHIP_OK;
 }
 
@@ -2866,45 +2686,39 @@ static int run_bow(orbhip_matcher *m, const orbhip_frame_view *f1, const uint32_
     if ((rc = stage_begin(m, al256(n * sizeof(orbhip_keypoint)) + al256(n * 32) + al256((size_t)nt * 4) + al256((size_t)nt) +
                                  al256((size_t)nq * 32) + al256((size_t)nq * 4) + al256((size_t)ng * sizeof(NodeGroup)) +
                                  al256(HISTO_LENGTH * 4), &st))) return rc;
-    const orbhip_keypoint *d_tkeys = (const orbhip_keypoint *)st.put(f2->keys, n * sizeof(orbhip_keypoint));
-    const uint8_t *d_tdesc = (const uint8_t *)st.put(f2->desc, n * 32);
-    const uint32_t *d_torder = (const uint32_t *)st.put(torder.data(), (size_t)nt * 4);
-    uint8_t *hm = st.h + st.off;
-    uint8_t *d_matched = (uint8_t *)st.put(nullptr, 0);
+    const orbhip_keypoint *d_tkeys = st.put(f2->keys, n);
+    const uint8_t *d_tdesc = st.put(f2->desc, n * 32);
+    const uint32_t *d_torder = st.put(reinterpret_cast<const uint32_t *>(torder.data()), (size_t)nt);
+    const uint8_t *d_matched, *d_qdesc;
+    const float *d_qangle;
+    const int *d_hist;
+    uint8_t *hm = st.take((size_t)nt, &d_matched);
+    uint8_t *hqd = st.take((size_t)nq * 32, &d_qdesc);
+    float *hqa = st.take((size_t)nq, &d_qangle);
+    const NodeGroup *d_groups = st.put(groups.data(), (size_t)ng);
+    int *hh = st.take((size_t)HISTO_LENGTH, &d_hist);
+    if ((rc = st.status())) return rc;
     for (int c = 0; c < nt; ++c) hm[c] = (uint8_t)(blocked2 && blocked2[torder[c]]);
-    st.off += al256((size_t)nt);
-    uint8_t *hqd = st.h + st.off;
-    const uint8_t *d_qdesc = (const uint8_t *)st.put(nullptr, 0);
-    st.off += al256((size_t)nq * 32);
-    float *hqa = reinterpret_cast<float *>(st.h + st.off);
-    const float *d_qangle = (const float *)st.put(nullptr, 0);
-    st.off += al256((size_t)nq * 4);
     for (int p = 0; p < nq; ++p) {
         memcpy(hqd + (size_t)p * 32, f1->desc + (size_t)order[p] * 32, 32);
         hqa[p] = f1->keys[order[p]].angle;
     }
-    const NodeGroup *d_groups = (const NodeGroup *)st.put(groups.data(), (size_t)ng * sizeof(NodeGroup));
-    memset(st.h + st.off, 0, HISTO_LENGTH * 4);
-    int *d_hist = (int *)st.put(nullptr, 0);
-    st.off += al256(HISTO_LENGTH * 4);
+    memset(hh, 0, HISTO_LENGTH * 4);
     if ((rc = stage_commit(m, &st))) return rc;
     void *p;
     if ((rc = scratch(m, S_OUT, (size_t)(nq + 1) * sizeof(int), &p))) return rc;
     int *d_out = (int *)p;
     if ((rc = scratch(m, S_CNT, (size_t)nq, &p))) return rc;
     uint8_t *d_bin = (uint8_t *)p;
-    uint8_t *h_out;
-    if ((rc = out_buffer(m, (size_t)(nq + 1) * sizeof(int), &h_out))) return rc;
     // queries whose node does not occur in f2 belong to no group: they stay at -1
     ORBHIP_HIP_CHECK(hipMemsetAsync(d_out, 0xff, (size_t)nq * sizeof(int), m->stream));
     hipLaunchKernelGGL(k_bow_groups, dim3((ng + 3) / 4), dim3(256), 0, m->stream, d_groups, ng, d_qdesc, d_qangle, d_torder,
-                       d_tdesc, d_tkeys, d_matched, max_dist, nnratio, check_ori, d_out, d_bin, d_hist);
-    hipLaunchKernelGGL(k_bow_cull, dim3(1), dim3(1024), 0, m->stream, nq, check_ori, (const int *)d_hist,
-                       (const uint8_t *)d_bin, d_out, d_out + nq);
-    ORBHIP_HIP_CHECK(hipGetLastError());
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_out, d_out, (size_t)(nq + 1) * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
-    const int *res = reinterpret_cast<const int *>(h_out);
+                       d_tdesc, d_tkeys, (uint8_t *)d_matched, max_dist, nnratio, check_ori, d_out, d_bin, (int *)d_hist);
+    hipLaunchKernelGGL(k_bow_cull, dim3(1), dim3(1024), 0, m->stream, nq, check_ori, d_hist, (const uint8_t *)d_bin, d_out,
+                       d_out + nq);
+    const uint8_t *h;
+    if ((rc = read_back(m, d_out, (size_t)(nq + 1) * sizeof(int), &h))) return rc;
+    const int *res = reinterpret_cast<const int *>(h);
     for (const NodeGroup &G : groups)
         for (int q = G.q_begin; q < G.q_end; ++q) matches12[order[q]] = res[q];
     *nmatches = res[nq];
@@ -2942,24 +2756,20 @@ static int run_tri(orbhip_matcher *m, const TriParams *tri, const orbhip_frame_v
                                  al256((size_t)nq * sizeof(orbhip_query)) + al256((size_t)nq * 32), &st))) return rc;
     DevFrame D;
     D.n = n2; D.min_x = D.min_y = 0.f; D.inv_w = D.inv_h = 0.f;
-    D.keys = (const orbhip_keypoint *)st.put(f2->keys, n * sizeof(orbhip_keypoint));
-    D.desc = (const uint8_t *)st.put(f2->desc, n * 32);
-    D.u_right = f2->u_right ? (const float *)st.put(f2->u_right, n * sizeof(float)) : nullptr;
-    const uint32_t *d_tnode = (const uint32_t *)st.put(node2, n * sizeof(uint32_t));
+    D.keys = st.put(f2->keys, n);
+    D.desc = st.put(f2->desc, n * 32);
+    D.u_right = f2->u_right ? st.put(f2->u_right, n) : nullptr;
+    const uint32_t *d_tnode = st.put(node2, n);
     const uint8_t *d_mask = nullptr;   // candidate filter: no map point yet (+ bOnlyStereo :725-729)
-    if (valid2 || only_stereo) {
-        uint8_t *hm = st.h + st.off;
-        d_mask = (const uint8_t *)st.put(nullptr, 0);
+    uint8_t *hm = (valid2 || only_stereo) ? st.take(n, &d_mask) : nullptr;
+    const orbhip_query *d_q;
+    const uint8_t *d_qdesc;
+    orbhip_query *hq = st.take((size_t)nq, &d_q);
+    uint8_t *hqd = st.take((size_t)nq * 32, &d_qdesc);
+    if ((rc = st.status())) return rc;
+    if (hm)
         for (int j = 0; j < n2; ++j)
             hm[j] = (uint8_t)((!valid2 || valid2[j]) && (!only_stereo || (f2->u_right && f2->u_right[j] >= 0)));
-        st.off += al256(n);
-    }
-    orbhip_query *hq = reinterpret_cast<orbhip_query *>(st.h + st.off);
-    const orbhip_query *d_q = (const orbhip_query *)st.put(nullptr, 0);
-    st.off += al256((size_t)nq * sizeof(orbhip_query));
-    uint8_t *hqd = st.h + st.off;
-    const uint8_t *d_qdesc = (const uint8_t *)st.put(nullptr, 0);
-    st.off += al256((size_t)nq * 32);
     for (int p = 0; p < nq; ++p) {
         const int i = order[p];
         orbhip_query &Q = hq[p];
@@ -2980,21 +2790,56 @@ static int run_tri(orbhip_matcher *m, const TriParams *tri, const orbhip_frame_v
     int *d_cnt = (int *)p;
     if ((rc = scratch(m, S_OUT, (size_t)(nq + 1) * sizeof(int), &p))) return rc;
     int *d_out = (int *)p;
-    uint8_t *h_out;
-    if ((rc = out_buffer(m, (size_t)(nq + 1) * sizeof(int), &h_out))) return rc;
-    const Batch one = {nullptr, nullptr, 0, 0};
+    const Batch B = {nullptr, nullptr, n2, nq};
     if ((rc = ensure_resolve_attr(m))) return rc;
     hipLaunchKernelGGL(k_tri_search, dim3((nq + 3) / 4), dim3(256), 0, m->stream, D, d_tnode, d_mask, d_q, d_qdesc, nq,
                        d_cand, d_cnt, stride, *tri);
-    if ((rc = launch_resolve_par(m, 1, 4, D, d_q, nq, f2->n, d_cand, nullptr, d_cnt, stride, (const uint8_t *)nullptr, 0.f, check_ori,
-                                 d_out, d_out + nq, one, TH_LOW, 0)))
+    if ((rc = launch_resolve_par(m, 1, 4, D, d_q, d_cand, nullptr, d_cnt, stride, (const uint8_t *)nullptr, 0.f, check_ori,
+                                 d_out, d_out + nq, B, TH_LOW, 0)))
         return rc;
-    ORBHIP_HIP_CHECK(hipGetLastError());
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_out, d_out, (size_t)(nq + 1) * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
-    const int *res = reinterpret_cast<const int *>(h_out);
+    const uint8_t *h;
+    if ((rc = read_back(m, d_out, (size_t)(nq + 1) * sizeof(int), &h))) return rc;
+    const int *res = reinterpret_cast<const int *>(h);
     for (int q = 0; q < nq; ++q) matches12[order[q]] = res[q];
     *nmatches = res[nq];
+    return ORBHIP_OK;
+}
+
+// ComputeStereoMatches of `pairs` pairs.  B: counts, frame mapping and keypoint capacity of the key arrays (pair p = left
+// frame l0 + p*ls against right frame r0 + p*rs); the pyramids are read at the same frame index plus pyr_l / pyr_r frames
+// (the host entry stages one pair's keypoints as frame 0 of frames pyr_l / pyr_r).  uRight, depth: [pairs][cap].
+static int launch_stereo(orbhip_matcher *m, orbhip_extractor *left, int pyr_l, orbhip_extractor *right, int pyr_r, int pairs,
+                         StereoBatch B, const orbhip_keypoint *d_kl, const uint8_t *d_dl, const orbhip_keypoint *d_kr,
+                         const uint8_t *d_dr, float mbf, float mb, float *d_u_right, float *d_depth, int *d_nmatches)
+{
+    StereoGeom G;
+    memset(&G, 0, sizeof(G));
+    G.nlevels = left->nlevels; G.nrows = left->G.lv[0].h; G.mbf = mbf; G.mb = mb;
+    for (int l = 0; l < G.nlevels; ++l) {
+        const LevelGeom &A = left->G.lv[l], &Bv = right->G.lv[l];
+        G.left[l] = left->d_pyr + (size_t)pyr_l * left->G.frame_bytes + A.plane_off + (size_t)kEdge * A.pitch + kPadL;
+        G.right[l] = right->d_pyr + (size_t)pyr_r * right->G.frame_bytes + Bv.plane_off + (size_t)kEdge * Bv.pitch + kPadL;
+        G.pitch_l[l] = A.pitch; G.pitch_r[l] = Bv.pitch; G.cols_r[l] = Bv.w;
+        G.sf[l] = left->sf[l]; G.isf[l] = left->isf[l];
+    }
+    for (int l = G.nlevels; l < ORBHIP_MAX_LEVELS; ++l) { G.left[l] = G.left[0]; G.right[l] = G.right[0]; }
+    B.fb_l = left->G.frame_bytes; B.fb_r = right->G.frame_bytes;
+    const int cap = B.cap;
+    void *p;
+    int rc;
+    const size_t rs_bytes = al256((size_t)pairs * ((size_t)G.nrows + 1) * sizeof(int));
+    if ((rc = scratch(m, S_ORD, rs_bytes + (size_t)pairs * cap * sizeof(int4), &p))) return rc;
+    int *d_rowstart = (int *)p;
+    int4 *d_order = reinterpret_cast<int4 *>((uint8_t *)p + rs_bytes);
+    if ((rc = scratch(m, S_CNT, (size_t)pairs * cap * sizeof(int), &p))) return rc;
+    int *d_sad = (int *)p;
+    if (G.nrows <= kStereoRowsMax)
+        hipLaunchKernelGGL(k_stereo_sort, dim3(pairs), dim3(256), 0, m->stream, d_kr, cap, G.nrows, d_rowstart, d_order, B, stereo_scales(G));
+    else d_rowstart = nullptr;   // taller images: every right keypoint is a candidate
+    hipLaunchKernelGGL(k_stereo_match, dim3((cap + 3) / 4, pairs), dim3(256), 0, m->stream, d_kl, d_dl, d_kr, d_dr,
+                       (const int *)d_rowstart, (const int4 *)d_order, stereo_row_reach(G), G, d_u_right, d_depth, d_sad, B);
+    hipLaunchKernelGGL(k_stereo_cull, dim3(pairs), dim3(256), 0, m->stream, d_sad, d_u_right, d_depth, d_nmatches, B);
+    ORBHIP_HIP_CHECK(hipGetLastError());
     return ORBHIP_OK;
 }
 
@@ -3133,23 +2978,18 @@ int orbhip_assign_features_to_grid(orbhip_matcher *m, const orbhip_frame_view *f
     Stage st;
     int rc;
     if ((rc = stage_begin(m, al256((size_t)n * sizeof(orbhip_keypoint)) + 256, &st))) return rc;
-    const void *d_keys = st.put(f->keys, (size_t)n * sizeof(orbhip_keypoint));
-    int *hn = reinterpret_cast<int *>(st.h + st.off);
-    *hn = n;
-    const void *d_n = st.put(nullptr, 0);
-    st.off += 256;
+    const orbhip_keypoint *d_keys = st.put(f->keys, (size_t)n);
+    const int *d_n = st.put(&n, 1);
     if ((rc = stage_commit(m, &st))) return rc;
     const size_t ob = ((size_t)2 * n + kGridCells + 1) * sizeof(int);
     void *p;
     if ((rc = scratch(m, S_OUT, ob, &p))) return rc;
     int *d_out = (int *)p;
-    uint8_t *h_out;
-    if ((rc = out_buffer(m, ob, &h_out))) return rc;
     if ((rc = orbhip_assign_features_to_grid_device(m, 1, d_keys, d_n, n, f->min_x, f->min_y, f->grid_inv_w, f->grid_inv_h,
                                                     d_out, d_out + 2 * n, d_out + n))) return rc;
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_out, d_out, ob, hipMemcpyDeviceToHost, m->stream));
-    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
-    const int *r = reinterpret_cast<const int *>(h_out);
+    const uint8_t *h;
+    if ((rc = read_back(m, d_out, ob, &h))) return rc;
+    const int *r = reinterpret_cast<const int *>(h);
     memcpy(cell_of, r, (size_t)n * sizeof(int));
     memcpy(cell_items, r + n, (size_t)n * sizeof(int));
     memcpy(cell_start, r + 2 * n, (size_t)(kGridCells + 1) * sizeof(int));
@@ -3185,20 +3025,15 @@ int orbhip_undistort_keypoints(orbhip_matcher *m, const orbhip_keypoint *keys, i
     Stage st;
     int rc;
     if ((rc = stage_begin(m, al256((size_t)n * sizeof(orbhip_keypoint)) + 256, &st))) return rc;
-    const void *d_keys = st.put(keys, (size_t)n * sizeof(orbhip_keypoint));
-    int *hn = reinterpret_cast<int *>(st.h + st.off);
-    *hn = n;
-    const void *d_n = st.put(nullptr, 0);
-    st.off += 256;
+    const orbhip_keypoint *d_keys = st.put(keys, (size_t)n);
+    const int *d_n = st.put(&n, 1);
     if ((rc = stage_commit(m, &st))) return rc;
     void *p;
     if ((rc = scratch(m, S_OUT, (size_t)n * sizeof(orbhip_keypoint), &p))) return rc;
-    uint8_t *h_out;
-    if ((rc = out_buffer(m, (size_t)n * sizeof(orbhip_keypoint), &h_out))) return rc;
     if ((rc = orbhip_undistort_keypoints_device(m, 1, d_keys, d_n, n, fx, fy, cx, cy, dist5, p))) return rc;
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_out, p, (size_t)n * sizeof(orbhip_keypoint), hipMemcpyDeviceToHost, m->stream));
-    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
-    memcpy(keys_un, h_out, (size_t)n * sizeof(orbhip_keypoint));
+    const uint8_t *h;
+    if ((rc = read_back(m, p, (size_t)n * sizeof(orbhip_keypoint), &h))) return rc;
+    memcpy(keys_un, h, (size_t)n * sizeof(orbhip_keypoint));
     return ORBHIP_OK;
 }
 
@@ -3234,28 +3069,23 @@ int orbhip_compute_stereo_from_rgbd(orbhip_matcher *m, const orbhip_keypoint *ke
     int rc;
     const size_t kb = al256((size_t)n * sizeof(orbhip_keypoint)), ib = al256((size_t)rows * cols * sizeof(float));
     if ((rc = stage_begin(m, 2 * kb + ib + 256, &st))) return rc;
-    const void *d_keys = st.put(keys, (size_t)n * sizeof(orbhip_keypoint));
-    const void *d_un = st.put(keys_un, (size_t)n * sizeof(orbhip_keypoint));
-    float *hd = reinterpret_cast<float *>(st.h + st.off);
-    const void *d_depth = st.put(nullptr, 0);
+    const orbhip_keypoint *d_keys = st.put(keys, (size_t)n);
+    const orbhip_keypoint *d_un = st.put(keys_un, (size_t)n);
+    const float *d_depth;
+    float *hd = st.take((size_t)rows * cols, &d_depth);
+    const int *d_n = st.put(&n, 1);
+    if ((rc = st.status())) return rc;
     for (int r = 0; r < rows; ++r) memcpy(hd + (size_t)r * cols, depth + (size_t)r * stride_floats, (size_t)cols * sizeof(float));
-    st.off += ib;
-    int *hn = reinterpret_cast<int *>(st.h + st.off);
-    *hn = n;
-    const void *d_n = st.put(nullptr, 0);
-    st.off += 256;
     if ((rc = stage_commit(m, &st))) return rc;
     void *p;
     if ((rc = scratch(m, S_OUT, (size_t)2 * n * sizeof(float), &p))) return rc;
     float *d_out = (float *)p;
-    uint8_t *h_out;
-    if ((rc = out_buffer(m, (size_t)2 * n * sizeof(float), &h_out))) return rc;
     if ((rc = orbhip_compute_stereo_from_rgbd_device(m, 1, d_keys, d_un, d_n, n, d_depth, rows, cols, cols, 0, mbf, d_out,
                                                      d_out + n))) return rc;
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_out, d_out, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
-    memcpy(u_right, h_out, (size_t)n * sizeof(float));
-    memcpy(depth_out, h_out + (size_t)n * sizeof(float), (size_t)n * sizeof(float));
+    const uint8_t *h;
+    if ((rc = read_back(m, d_out, (size_t)2 * n * sizeof(float), &h))) return rc;
+    memcpy(u_right, h, (size_t)n * sizeof(float));
+    memcpy(depth_out, h + (size_t)n * sizeof(float), (size_t)n * sizeof(float));
     return ORBHIP_OK;
 }
 
@@ -3279,18 +3109,15 @@ int orbhip_distinctive_descriptors(orbhip_matcher *m, const uint8_t *desc, const
     Stage st;
     int rc;
     if ((rc = stage_begin(m, al256(total * 32) + al256((size_t)(npoints + 1) * 4), &st))) return rc;
-    const uint8_t *d_desc = (const uint8_t *)st.put(desc, total * 32);
-    const int *d_off = (const int *)st.put(offsets, (size_t)(npoints + 1) * 4);
+    const uint8_t *d_desc = st.put(desc, total * 32);
+    const int *d_off = st.put(offsets, (size_t)npoints + 1);
     if ((rc = stage_commit(m, &st))) return rc;
     void *p;
     if ((rc = scratch(m, S_OUT, (size_t)npoints * sizeof(int), &p))) return rc;
-    uint8_t *h_out;
-    if ((rc = out_buffer(m, (size_t)npoints * sizeof(int), &h_out))) return rc;
     hipLaunchKernelGGL(k_distinctive, dim3((npoints + 3) / 4), dim3(256), 0, m->stream, d_desc, d_off, npoints, (int *)p);
-    ORBHIP_HIP_CHECK(hipGetLastError());
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_out, p, (size_t)npoints * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
-    memcpy(best_idx, h_out, (size_t)npoints * sizeof(int));
+    const uint8_t *h;
+    if ((rc = read_back(m, p, (size_t)npoints * sizeof(int), &h))) return rc;
+    memcpy(best_idx, h, (size_t)npoints * sizeof(int));
     return ORBHIP_OK;
 }
 
@@ -3377,31 +3204,28 @@ int orbhip_search_best_in_window(orbhip_matcher *m, const orbhip_frame_view *kf,
                                  al256((size_t)nq * sizeof(orbhip_query)) + al256((size_t)nq * 32), &st))) return rc;
     DevFrame D;
     D.n = kf->n; D.min_x = kf->min_x; D.min_y = kf->min_y; D.inv_w = kf->grid_inv_w; D.inv_h = kf->grid_inv_h;
-    D.keys = (const orbhip_keypoint *)st.put(kf->keys, n * sizeof(orbhip_keypoint));
-    D.desc = (const uint8_t *)st.put(kf->desc, n * 32);
-    D.u_right = kf->u_right ? (const float *)st.put(kf->u_right, n * sizeof(float)) : nullptr;
-    const orbhip_query *d_q = (const orbhip_query *)st.put(q, (size_t)nq * sizeof(orbhip_query));
-    const uint8_t *d_qdesc = (const uint8_t *)st.put(qdesc, (size_t)nq * 32);
+    D.keys = st.put(kf->keys, n);
+    D.desc = st.put(kf->desc, n * 32);
+    D.u_right = kf->u_right ? st.put(kf->u_right, n) : nullptr;
+    const orbhip_query *d_q = st.put(q, (size_t)nq);
+    const uint8_t *d_qdesc = st.put(qdesc, (size_t)nq * 32);
     if ((rc = stage_commit(m, &st))) return rc;
     void *p;
     if ((rc = scratch(m, S_ORD, n * sizeof(uint32_t), &p))) return rc;
     uint32_t *d_ord = (uint32_t *)p;
     if ((rc = scratch(m, S_OUT, (size_t)nq * 2 * sizeof(int), &p))) return rc;
     int *d_out = (int *)p;
-    uint8_t *h_out;
-    if ((rc = out_buffer(m, (size_t)nq * 2 * sizeof(int), &h_out))) return rc;
     SigmaTab sig;
     memset(&sig, 0, sizeof(sig));
     if (inv_level_sigma2) for (int l = 0; l < std::min(kf->n_levels, ORBHIP_MAX_LEVELS); ++l) sig.inv_sigma2[l] = inv_level_sigma2[l];
-    const Batch one = {nullptr, nullptr, 0, 0};
-    hipLaunchKernelGGL(k_grid_order, dim3((kf->n + 255) / 256), dim3(256), 0, m->stream, D, d_ord, one);
+    const Batch B = {nullptr, nullptr, kf->n, nq};
+    hipLaunchKernelGGL(k_grid_order, dim3((kf->n + 255) / 256), dim3(256), 0, m->stream, D, d_ord, B);
     hipLaunchKernelGGL(k_best_in_window, dim3((nq + 3) / 4), dim3(256), 0, m->stream, D, d_ord, d_q, d_qdesc, nq, chi2_gate,
                        sig, d_out, d_out + nq);
-    ORBHIP_HIP_CHECK(hipGetLastError());
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_out, d_out, (size_t)nq * 2 * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
-    memcpy(best_idx, h_out, (size_t)nq * sizeof(int));
-    memcpy(best_dist, h_out + (size_t)nq * sizeof(int), (size_t)nq * sizeof(int));
+    const uint8_t *h;
+    if ((rc = read_back(m, d_out, (size_t)nq * 2 * sizeof(int), &h))) return rc;
+    memcpy(best_idx, h, (size_t)nq * sizeof(int));
+    memcpy(best_dist, h + (size_t)nq * sizeof(int), (size_t)nq * sizeof(int));
     return ORBHIP_OK;
 }
 
@@ -3422,27 +3246,12 @@ static int search_device(orbhip_matcher *m, int mode, int pairs, const void *d_k
     if (!m || pairs <= 0 || !d_kps || !d_desc || !d_n || !d_q || !d_qdesc || !d_nq || !d_assign || !d_nmatches || cap <= 0 || qcap <= 0)
         return ORBHIP_E_ARG;
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
-    int rc;
-    void *p;
-    const int stride = (cap + 1) & ~1;
-    if ((rc = scratch(m, S_CAND, (size_t)pairs * qcap * stride * sizeof(unsigned long long), &p))) return rc;
-    unsigned long long *d_cand = (unsigned long long *)p;
-    if ((rc = scratch(m, S_CNT, (size_t)pairs * qcap * sizeof(int), &p))) return rc;
-    int *d_cnt = (int *)p;
-    if ((rc = ensure_resolve_attr(m))) return rc;
     DevFrame D;
     D.n = cap; D.keys = (const orbhip_keypoint *)d_kps; D.desc = (const uint8_t *)d_desc; D.u_right = (const float *)d_u_right;
     D.min_x = min_x; D.min_y = min_y; D.inv_w = grid_inv_w; D.inv_h = grid_inv_h;
     const Batch B = {(const int *)d_n, (const int *)d_nq, cap, qcap, t0, ts, qd0, qds};
-    unsigned long long *d_ccand;
-    if ((rc = launch_window_search(m, pairs, D, cap, (const orbhip_query *)d_q, (const uint8_t *)d_qdesc, qcap, d_cand, d_cnt, stride, 1,
-                                   B, &d_ccand, (const uint8_t *)d_taken, mode == 0 ? TH_HIGH : 256, proj)))
-        return rc;
-    if ((rc = launch_resolve_par(m, pairs, mode, D, (const orbhip_query *)d_q, qcap, cap, d_cand, d_ccand, d_cnt, stride,
-                                 (const uint8_t *)d_taken, nnratio, check_ori, (int *)d_assign, (int *)d_nmatches, B, TH_HIGH, 0)))
-        return rc;
-    ORBHIP_HIP_CHECK(hipGetLastError());
-    return ORBHIP_OK;
+    return launch_search(m, mode, pairs, D, B, (const orbhip_query *)d_q, (const uint8_t *)d_qdesc, nullptr, (const uint8_t *)d_taken,
+                         nnratio, check_ori, TH_HIGH, 0, 1, (int *)d_assign, (int *)d_nmatches, proj);
 }
 
 int orbhip_search_by_projection_frame_device(orbhip_matcher *m, int pairs, const void *d_kps, const void *d_desc,
@@ -3484,37 +3293,10 @@ int orbhip_compute_stereo_matches_device(orbhip_matcher *m, orbhip_extractor *le
     // mvImagePyramid[0] of handles that produce it on demand; this launch is ordered behind the copy
     if (int rc = ensure_level0(left, m->stream)) return rc;
     if (right != left) { if (int rc = ensure_level0(right, m->stream)) return rc; }
-    StereoGeom G;
-    memset(&G, 0, sizeof(G));
-    G.nlevels = left->nlevels; G.nrows = left->G.lv[0].h; G.mbf = mbf; G.mb = mb;
-    for (int l = 0; l < G.nlevels; ++l) {
-        const LevelGeom &A = left->G.lv[l], &Bv = right->G.lv[l];
-        G.left[l] = left->d_pyr + A.plane_off + (size_t)kEdge * A.pitch + kPadL;
-        G.right[l] = right->d_pyr + Bv.plane_off + (size_t)kEdge * Bv.pitch + kPadL;
-        G.pitch_l[l] = A.pitch; G.pitch_r[l] = Bv.pitch; G.cols_r[l] = Bv.w;
-        G.sf[l] = left->sf[l]; G.isf[l] = left->isf[l];
-    }
-    for (int l = G.nlevels; l < ORBHIP_MAX_LEVELS; ++l) { G.left[l] = G.left[0]; G.right[l] = G.right[0]; }
-    void *p;
-    int rc;
-    if ((rc = scratch(m, S_ORD, al256((size_t)pairs * ((size_t)G.nrows + 1) * sizeof(int)) + (size_t)pairs * cap * sizeof(int4), &p))) return rc;
-    int *d_rowstart = (int *)p;
-    int4 *d_order = reinterpret_cast<int4 *>((uint8_t *)p + al256((size_t)pairs * ((size_t)G.nrows + 1) * sizeof(int)));
-    if ((rc = scratch(m, S_CNT, (size_t)pairs * cap * sizeof(int), &p))) return rc;
-    int *d_sad = (int *)p;
-    const StereoBatch B = {(const int *)d_n_l, (const int *)d_n_r, l0, ls, r0, rs, cap, left->G.frame_bytes, right->G.frame_bytes};
-    const int R = stereo_row_reach(G);
-    if (G.nrows <= kStereoRowsMax)
-        hipLaunchKernelGGL(k_stereo_sort, dim3(pairs), dim3(256), 0, m->stream, (const orbhip_keypoint *)d_kps_r, cap, G.nrows, d_rowstart,
-                           d_order, B, stereo_scales(G));
-    else d_rowstart = nullptr;   // taller images: every right keypoint is a candidate
-    hipLaunchKernelGGL(k_stereo_match, dim3((cap + 3) / 4, pairs), dim3(256), 0, m->stream, (const orbhip_keypoint *)d_kps_l,
-                       (const uint8_t *)d_desc_l, cap, (const orbhip_keypoint *)d_kps_r, (const uint8_t *)d_desc_r, cap,
-                       (const int *)d_rowstart, (const int4 *)d_order, R, G, (float *)d_u_right, (float *)d_depth, d_sad, B);
-    hipLaunchKernelGGL(k_stereo_cull, dim3(pairs), dim3(256), 0, m->stream, cap, d_sad, (float *)d_u_right, (float *)d_depth,
-                       (int *)d_nmatches, B);
-    ORBHIP_HIP_CHECK(hipGetLastError());
-    return ORBHIP_OK;
+    const StereoBatch B = {(const int *)d_n_l, (const int *)d_n_r, l0, ls, r0, rs, cap, 0, 0};
+    return launch_stereo(m, left, 0, right, 0, pairs, B, (const orbhip_keypoint *)d_kps_l, (const uint8_t *)d_desc_l,
+                         (const orbhip_keypoint *)d_kps_r, (const uint8_t *)d_desc_r, mbf, mb, (float *)d_u_right, (float *)d_depth,
+                         (int *)d_nmatches);
 }
 
 int orbhip_search_for_initialization_device(orbhip_matcher *m, int pairs, const void *d_kps, const void *d_desc,
@@ -3532,16 +3314,10 @@ int orbhip_search_for_initialization_device(orbhip_matcher *m, int pairs, const 
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     int rc;
     void *p;
-    const int stride = (cap + 1) & ~1;
-    if ((rc = scratch(m, S_CAND, (size_t)pairs * cap * stride * sizeof(unsigned long long), &p))) return rc;
-    unsigned long long *d_cand = (unsigned long long *)p;
-    if ((rc = scratch(m, S_CNT, (size_t)pairs * cap * sizeof(int), &p))) return rc;
-    int *d_cnt = (int *)p;
     if ((rc = scratch(m, S_Q, (size_t)pairs * cap * sizeof(orbhip_query), &p))) return rc;
     orbhip_query *d_q = (orbhip_query *)p;
     if ((rc = scratch(m, S_TAKEN, (size_t)pairs * sizeof(int), &p))) return rc;
     int *d_nq = (int *)p;
-    if ((rc = ensure_resolve_attr(m))) return rc;
     const orbhip_keypoint *keys = (const orbhip_keypoint *)d_kps;
     hipLaunchKernelGGL(k_init_queries, dim3((cap + 255) / 256, pairs), dim3(256), 0, m->stream, keys, (const int *)d_n, cap,
                        f1_first, f1_step, (float *)d_prev_matched, reset_prev, (float)window_size, d_q, d_nq);
@@ -3549,10 +3325,9 @@ int orbhip_search_for_initialization_device(orbhip_matcher *m, int pairs, const 
     D.n = cap; D.keys = keys; D.desc = (const uint8_t *)d_desc; D.u_right = nullptr;
     D.min_x = min_x; D.min_y = min_y; D.inv_w = grid_inv_w; D.inv_h = grid_inv_h;
     const Batch B = {(const int *)d_n, d_nq, cap, cap, f2_first, f2_step, f1_first, f1_step};
-    unsigned long long *d_ccand;
-    if ((rc = launch_window_search(m, pairs, D, cap, d_q, (const uint8_t *)d_desc, cap, d_cand, d_cnt, stride, 0, B, &d_ccand, nullptr, 256))) return rc;
-    launch_resolve_init(m, pairs, D, keys, d_q, cap, cap, d_cand, d_ccand, d_cnt, stride, nnratio, check_ori, (int *)d_matches12,
-                        (int *)d_nmatches, B);
+    if ((rc = launch_search(m, 2, pairs, D, B, d_q, (const uint8_t *)d_desc, keys, nullptr, nnratio, check_ori, TH_HIGH, 0, 0,
+                            (int *)d_matches12, (int *)d_nmatches)))
+        return rc;
     hipLaunchKernelGGL(k_init_update_prev, dim3((cap + 255) / 256, pairs), dim3(256), 0, m->stream, keys, cap, f2_first, f2_step,
                        d_nq, (const int *)d_matches12, (float *)d_prev_matched);
     ORBHIP_HIP_CHECK(hipGetLastError());
@@ -3569,7 +3344,7 @@ int orbhip_project_last_frame_device(orbhip_matcher *m, int pairs, const orbhip_
         return ORBHIP_E_ARG;
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     ProjBatch B = {(const float *)d_Tcw, (const float *)d_Tlw, (const orbhip_keypoint *)d_kps, (const int *)d_n,
-                   (const float *)d_world, (const uint8_t *)d_flags, (orbhip_query *)d_q, (int *)d_nq, 0, cap, last_first, last_step};
+                   (const float *)d_world, (const uint8_t *)d_flags, (orbhip_query *)d_q, (int *)d_nq, cap, last_first, last_step};
     hipLaunchKernelGGL(k_project_last_frame, dim3((cap + 255) / 256, pairs), dim3(256), 0, m->stream, B, *cam, th, mono);
     ORBHIP_HIP_CHECK(hipGetLastError());
     return ORBHIP_OK;
@@ -3593,7 +3368,7 @@ int orbhip_track_last_frame_device(orbhip_matcher *m, int pairs, const orbhip_ca
     int *d_nq = (int *)p;
     ProjLaunch proj;
     proj.P = {(const float *)d_Tcw, (const float *)d_Tlw, (const orbhip_keypoint *)d_kps, (const int *)d_n,
-              (const float *)d_world, (const uint8_t *)d_flags, d_q, d_nq, 0, cap, last_first, last_step};
+              (const float *)d_world, (const uint8_t *)d_flags, d_q, d_nq, cap, last_first, last_step};
     proj.cam = *cam; proj.th = th; proj.mono = mono;
     // Frame::ComputeImageBounds / mfGridElement{Width,Height}Inv (src/Frame.cc:99-100) from the camera's bounds
     const float inv_w = (float)GRID_COLS / (cam->max_x - cam->min_x), inv_h = (float)GRID_ROWS / (cam->max_y - cam->min_y);
@@ -3612,7 +3387,7 @@ int orbhip_frustum_queries_device(orbhip_matcher *m, int frames, const orbhip_ca
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     FrustumBatch B = {(const float *)d_Tcw, (const int *)d_np, (const float *)d_world, (const float *)d_normal,
                       (const float *)d_max_dist, (const float *)d_min_dist, (const uint8_t *)d_flags, (orbhip_query *)d_q,
-                      (float *)d_view_cos, 0, pcap};
+                      (float *)d_view_cos, pcap};
     hipLaunchKernelGGL(k_frustum_queries, dim3((pcap + 255) / 256, frames), dim3(256), 0, m->stream, B, *cam, viewing_cos_limit, th);
     ORBHIP_HIP_CHECK(hipGetLastError());
     return ORBHIP_OK;
@@ -3627,20 +3402,20 @@ int orbhip_project_last_frame(orbhip_matcher *m, const orbhip_camera *cam, const
     if (!world || !flags || !last_keys) return ORBHIP_E_ARG;
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     Stage st;
-    int rc = stage_begin(m, 2 * al256(48) + al256((size_t)n * 12) + al256((size_t)n) + al256((size_t)n * sizeof(orbhip_keypoint)), &st);
+    int rc = stage_begin(m, 2 * al256(48) + al256((size_t)n * 12) + al256((size_t)n) + al256((size_t)n * sizeof(orbhip_keypoint)) + 256, &st);
     if (rc) return rc;
-    const float *dT = (const float *)st.put(Tcw, 48), *dL = (const float *)st.put(Tlw, 48);
-    const float *dW = (const float *)st.put(world, (size_t)n * 12);
-    const uint8_t *dF = (const uint8_t *)st.put(flags, (size_t)n);
-    const orbhip_keypoint *dK = (const orbhip_keypoint *)st.put(last_keys, (size_t)n * sizeof(orbhip_keypoint));
+    const float *dT = st.put(Tcw, 12), *dL = st.put(Tlw, 12);
+    const float *dW = st.put(world, (size_t)n * 3);
+    const uint8_t *dF = st.put(flags, (size_t)n);
+    const orbhip_keypoint *dK = st.put(last_keys, (size_t)n);
+    const int *dN = st.put(&n, 1);
     if ((rc = stage_commit(m, &st))) return rc;
     void *p;
     if ((rc = scratch(m, S_Q, (size_t)n * sizeof(orbhip_query), &p))) return rc;
-    ProjBatch B = {dT, dL, dK, nullptr, dW, dF, (orbhip_query *)p, nullptr, n, n, 0, 0};
-    hipLaunchKernelGGL(k_project_last_frame, dim3((n + 255) / 256, 1), dim3(256), 0, m->stream, B, *cam, th, mono);
-    ORBHIP_HIP_CHECK(hipGetLastError());
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(q, p, (size_t)n * sizeof(orbhip_query), hipMemcpyDeviceToHost, m->stream));
-    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
+    if ((rc = orbhip_project_last_frame_device(m, 1, cam, dT, dL, dK, dN, n, 0, 0, dW, dF, th, mono, p, nullptr))) return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, p, (size_t)n * sizeof(orbhip_query), &h))) return rc;
+    memcpy(q, h, (size_t)n * sizeof(orbhip_query));
     return ORBHIP_OK;
 }
 
@@ -3653,22 +3428,25 @@ int orbhip_frustum_queries(orbhip_matcher *m, const orbhip_camera *cam, const fl
     if (!world || !normal || !max_dist || !min_dist || !flags) return ORBHIP_E_ARG;
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     Stage st;
-    int rc = stage_begin(m, al256(48) + 2 * al256((size_t)n * 12) + 2 * al256((size_t)n * 4) + al256((size_t)n), &st);
+    int rc = stage_begin(m, al256(48) + 2 * al256((size_t)n * 12) + 2 * al256((size_t)n * 4) + al256((size_t)n) + 256, &st);
     if (rc) return rc;
-    const float *dT = (const float *)st.put(Tcw, 48);
-    const float *dW = (const float *)st.put(world, (size_t)n * 12), *dN = (const float *)st.put(normal, (size_t)n * 12);
-    const float *dMx = (const float *)st.put(max_dist, (size_t)n * 4), *dMn = (const float *)st.put(min_dist, (size_t)n * 4);
-    const uint8_t *dF = (const uint8_t *)st.put(flags, (size_t)n);
+    const float *dT = st.put(Tcw, 12);
+    const float *dW = st.put(world, (size_t)n * 3), *dNr = st.put(normal, (size_t)n * 3);
+    const float *dMx = st.put(max_dist, (size_t)n), *dMn = st.put(min_dist, (size_t)n);
+    const uint8_t *dF = st.put(flags, (size_t)n);
+    const int *dN = st.put(&n, 1);
     if ((rc = stage_commit(m, &st))) return rc;
-    void *p, *pv;
-    if ((rc = scratch(m, S_Q, (size_t)n * sizeof(orbhip_query), &p))) return rc;
-    if ((rc = scratch(m, S_OUT, (size_t)n * sizeof(float), &pv))) return rc;
-    FrustumBatch B = {dT, nullptr, dW, dN, dMx, dMn, dF, (orbhip_query *)p, (float *)pv, n, n};
-    hipLaunchKernelGGL(k_frustum_queries, dim3((n + 255) / 256, 1), dim3(256), 0, m->stream, B, *cam, viewing_cos_limit, th);
-    ORBHIP_HIP_CHECK(hipGetLastError());
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(q, p, (size_t)n * sizeof(orbhip_query), hipMemcpyDeviceToHost, m->stream));
-    if (view_cos) ORBHIP_HIP_CHECK(hipMemcpyAsync(view_cos, pv, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
+    // outputs contiguous: q[n] | view_cos[n] (when asked for)
+    const size_t qb = (size_t)n * sizeof(orbhip_query), ob = qb + (view_cos ? (size_t)n * sizeof(float) : 0);
+    void *p;
+    if ((rc = scratch(m, S_OUT, ob, &p))) return rc;
+    if ((rc = orbhip_frustum_queries_device(m, 1, cam, dT, n, dN, dW, dNr, dMx, dMn, dF, viewing_cos_limit, th, p,
+                                            view_cos ? (uint8_t *)p + qb : nullptr)))
+        return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, p, ob, &h))) return rc;
+    memcpy(q, h, qb);
+    if (view_cos) memcpy(view_cos, h + qb, (size_t)n * sizeof(float));
     return ORBHIP_OK;
 }
 
@@ -3697,22 +3475,22 @@ int orbhip_keyframe_queries(orbhip_matcher *m, const orbhip_camera *cam, int mod
     int rc = stage_begin(m, 2 * al256(48) + 2 * al256((size_t)n * 12) + 2 * al256((size_t)n * 4) + al256((size_t)n), &st);
     if (rc) return rc;
     KfQueryArgs A;
-    A.T1 = (const float *)st.put(T1, 48);
-    A.T2 = T2 ? (const float *)st.put(T2, 48) : nullptr;
-    A.world = (const float *)st.put(world, (size_t)n * 12);
-    A.normal = normal ? (const float *)st.put(normal, (size_t)n * 12) : nullptr;
-    A.max_dist = (const float *)st.put(max_dist, (size_t)n * 4);
-    A.min_dist = (const float *)st.put(min_dist, (size_t)n * 4);
-    A.flags = (const uint8_t *)st.put(flags, (size_t)n);
+    A.T1 = st.put(T1, 12);
+    A.T2 = T2 ? st.put(T2, 12) : nullptr;
+    A.world = st.put(world, (size_t)n * 3);
+    A.normal = normal ? st.put(normal, (size_t)n * 3) : nullptr;
+    A.max_dist = st.put(max_dist, (size_t)n);
+    A.min_dist = st.put(min_dist, (size_t)n);
+    A.flags = st.put(flags, (size_t)n);
     A.n = n; A.mode = mode; A.double_invz = double_invz;
     if ((rc = stage_commit(m, &st))) return rc;
     void *p;
     if ((rc = scratch(m, S_Q, (size_t)n * sizeof(orbhip_query), &p))) return rc;
     A.q = (orbhip_query *)p;
     hipLaunchKernelGGL(k_keyframe_queries, dim3((n + 255) / 256), dim3(256), 0, m->stream, A, *cam, th);
-    ORBHIP_HIP_CHECK(hipGetLastError());
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(q, p, (size_t)n * sizeof(orbhip_query), hipMemcpyDeviceToHost, m->stream));
-    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
+    const uint8_t *h;
+    if ((rc = read_back(m, p, (size_t)n * sizeof(orbhip_query), &h))) return rc;
+    memcpy(q, h, (size_t)n * sizeof(orbhip_query));
     return ORBHIP_OK;
 }
 
@@ -3800,48 +3578,30 @@ int orbhip_compute_stereo_matches(orbhip_matcher *m, orbhip_extractor *left, int
     // the pyramids were produced on the extractors' streams
     ORBHIP_HIP_CHECK(hipStreamSynchronize(left->stream));
     ORBHIP_HIP_CHECK(hipStreamSynchronize(right->stream));
-    StereoGeom G;
-    memset(&G, 0, sizeof(G));
-    G.nlevels = left->nlevels; G.nrows = left->G.lv[0].h; G.mbf = mbf; G.mb = mb;
-    for (int l = 0; l < G.nlevels; ++l) {
-        const LevelGeom &A = left->G.lv[l], &B = right->G.lv[l];
-        G.left[l] = left->d_pyr + (size_t)frame_l * left->G.frame_bytes + A.plane_off + (size_t)kEdge * A.pitch + kPadL;
-        G.right[l] = right->d_pyr + (size_t)frame_r * right->G.frame_bytes + B.plane_off + (size_t)kEdge * B.pitch + kPadL;
-        G.pitch_l[l] = A.pitch; G.pitch_r[l] = B.pitch; G.cols_r[l] = B.w;
-        G.sf[l] = left->sf[l]; G.isf[l] = left->isf[l];
-    }
-    void *p;
-    int rc;
     Stage st;
+    int rc;
     if ((rc = stage_begin(m, al256((size_t)nl * sizeof(orbhip_keypoint)) + al256((size_t)nl * 32) +
-                                 al256((size_t)nr * sizeof(orbhip_keypoint)) + al256((size_t)nr * 32), &st))) return rc;
-    const orbhip_keypoint *d_kl = (const orbhip_keypoint *)st.put(keys_l, (size_t)nl * sizeof(orbhip_keypoint));
-    const uint8_t *d_dl = (const uint8_t *)st.put(desc_l, (size_t)nl * 32);
-    const orbhip_keypoint *d_kr = (const orbhip_keypoint *)st.put(keys_r, (size_t)nr * sizeof(orbhip_keypoint));
-    const uint8_t *d_dr = (const uint8_t *)st.put(desc_r, (size_t)nr * 32);
+                                 al256((size_t)nr * sizeof(orbhip_keypoint)) + al256((size_t)nr * 32) + 256, &st))) return rc;
+    const orbhip_keypoint *d_kl = st.put(keys_l, (size_t)nl);
+    const uint8_t *d_dl = st.put(desc_l, (size_t)nl * 32);
+    const orbhip_keypoint *d_kr = st.put(keys_r, (size_t)nr);
+    const uint8_t *d_dr = st.put(desc_r, (size_t)nr * 32);
+    const int counts[2] = {nl, nr};
+    const int *d_counts = st.put(counts, 2);
     if ((rc = stage_commit(m, &st))) return rc;
-    if ((rc = scratch(m, S_ORD, al256(((size_t)G.nrows + 1) * sizeof(int)) + (size_t)nr * sizeof(int4), &p))) return rc;
-    int *d_rowstart = (int *)p;
-    int4 *d_order = reinterpret_cast<int4 *>((uint8_t *)p + al256(((size_t)G.nrows + 1) * sizeof(int)));
-    // outputs contiguous: u_right[nl] | depth[nl] | sad[nl] | n
-    if ((rc = scratch(m, S_OUT, (size_t)(3 * nl + 1) * sizeof(float), &p))) return rc;
+    // outputs contiguous: u_right[nl] | depth[nl] | n
+    void *p;
+    if ((rc = scratch(m, S_OUT, (size_t)(2 * nl + 1) * sizeof(float), &p))) return rc;
     float *d_ur = (float *)p, *d_depth = d_ur + nl;
-    int *d_sad = (int *)(d_depth + nl), *d_n = d_sad + nl;
-    uint8_t *h_out;
-    if ((rc = out_buffer(m, (size_t)(3 * nl + 1) * sizeof(float), &h_out))) return rc;
-    const StereoBatch one = {nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0};
-    if (G.nrows <= kStereoRowsMax)
-        hipLaunchKernelGGL(k_stereo_sort, dim3(1), dim3(256), 0, m->stream, d_kr, nr, G.nrows, d_rowstart, d_order, one, stereo_scales(G));
-    else d_rowstart = nullptr;
-    hipLaunchKernelGGL(k_stereo_match, dim3((nl + 3) / 4), dim3(256), 0, m->stream, d_kl, d_dl, nl, d_kr, d_dr, nr,
-                       (const int *)d_rowstart, (const int4 *)d_order, stereo_row_reach(G), G, d_ur, d_depth, d_sad, one);
-    hipLaunchKernelGGL(k_stereo_cull, dim3(1), dim3(256), 0, m->stream, nl, d_sad, d_ur, d_depth, d_n, one);
-    ORBHIP_HIP_CHECK(hipGetLastError());
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_out, d_ur, (size_t)(3 * nl + 1) * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
-    memcpy(u_right, h_out, (size_t)nl * sizeof(float));
-    memcpy(depth, h_out + (size_t)nl * sizeof(float), (size_t)nl * sizeof(float));
-    *nmatches = reinterpret_cast<const int *>(h_out)[3 * nl];
+    const StereoBatch B = {d_counts, d_counts + 1, 0, 0, 0, 0, std::max(nl, nr), 0, 0};
+    if ((rc = launch_stereo(m, left, frame_l, right, frame_r, 1, B, d_kl, d_dl, d_kr, d_dr, mbf, mb, d_ur, d_depth,
+                            (int *)(d_depth + nl))))
+        return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, d_ur, (size_t)(2 * nl + 1) * sizeof(float), &h))) return rc;
+    memcpy(u_right, h, (size_t)nl * sizeof(float));
+    memcpy(depth, h + (size_t)nl * sizeof(float), (size_t)nl * sizeof(float));
+    *nmatches = reinterpret_cast<const int *>(h)[2 * nl];
     return ORBHIP_OK;
 }
 
