@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from orb_slam2_comment_amd.synth import synth_frame
+from seqref import extractor as SX
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -133,30 +134,13 @@ def test_resize_properties(oracle):
     dst = np.zeros((42, 50), np.uint8)
     L.oracle_resize_linear(src.ctypes.data, 60, 60, 50, dst.ctypes.data, 50, 50, 42)
     assert np.all(dst == 137)
-    # independent numpy restatement of the fixed-point bilinear formula
+    # independent numpy restatement of the fixed-point bilinear formula (tests/seqref)
     rng = np.random.default_rng(5)
     src = rng.integers(0, 256, (37, 53), dtype=np.uint8)
     dw, dh = 44, 31
     dst = np.zeros((dh, dw), np.uint8)
     L.oracle_resize_linear(src.ctypes.data, 53, 53, 37, dst.ctypes.data, dw, dw, dh)
-
-    def taps(d, s):
-        scale = 1.0 / (d / s)
-        f = ((np.arange(d) + 0.5) * scale - 0.5).astype(np.float32)
-        i = np.floor(f).astype(int)
-        f = (f - i).astype(np.float32)
-        return i, f
-    sx, fx = taps(dw, 53)
-    lo, hi = sx < 0, sx >= 52
-    fx[lo | hi] = 0; sx[lo] = 0; sx[hi] = 52
-    a0 = np.rint((np.float32(1) - fx) * np.float32(2048)).astype(int); a1 = np.rint(fx * np.float32(2048)).astype(int)
-    sy, fy = taps(dh, 37)
-    b0 = np.rint((np.float32(1) - fy) * np.float32(2048)).astype(int); b1 = np.rint(fy * np.float32(2048)).astype(int)
-    y0 = np.clip(sy, 0, 36); y1 = np.clip(sy + 1, 0, 36)
-    S = src.astype(int)
-    x1 = np.minimum(sx + 1, 52)
-    H = S[:, sx] * a0 + S[:, x1] * a1
-    out = (((b0[:, None] * (H[y0] >> 4)) >> 16) + ((b1[:, None] * (H[y1] >> 4)) >> 16) + 2) >> 2
+    out = SX.resize_linear(src, dw, dh)
     assert np.array_equal(dst, out.astype(np.uint8))
 
 
@@ -166,11 +150,8 @@ def test_gauss7_matches_numpy(oracle):
     src = rng.integers(0, 256, (40, 45), dtype=np.uint8)
     dst = np.zeros_like(src)
     L.oracle_gauss7(src.ctypes.data, 45, 45, 40, dst.ctypes.data, 45)
-    w = np.array([18, 34, 49, 55, 49, 34, 18])
-    p = np.pad(src.astype(int), 3, mode="reflect")      # numpy 'reflect' == BORDER_REFLECT_101
-    rows = sum(w[k] * p[:, k:k + 45] for k in range(7))
-    out = sum(w[k] * rows[k:k + 40] for k in range(7))
-    assert np.array_equal(dst, np.minimum((out + 32768) >> 16, 255).astype(np.uint8))
+    out = SX.gauss7(SX.pad_reflect101(src, 3))          # numpy 'reflect' == BORDER_REFLECT_101 (tests/seqref)
+    assert np.array_equal(dst, out)
     white = np.full((20, 20), 255, np.uint8); o = np.zeros_like(white)
     L.oracle_gauss7(white.ctypes.data, 20, 20, 20, o.ctypes.data, 20)
     assert np.all(o == 255)       # weights sum to 257: saturates, does not wrap
