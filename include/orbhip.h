@@ -10,6 +10,8 @@
  *   orbhip_extractor_*        replaces class ORBextractor
  *                             (include/ORBextractor.h:45-110, src/ORBextractor.cc:410-1132)
  *   orbhip_extract            replaces ORBextractor::operator()  (include/ORBextractor.h:59-61)
+ *   orbhip_extract_color*     the cvtColor(.., CV_{RGB,BGR,RGBA,BGRA}2GRAY) of Tracking::GrabImage{Monocular,Stereo,RGBD}
+ *                             (src/Tracking.cc:172-197, 212-225, 242-256) followed by ORBextractor::operator()
  *   orbhip_pyramid_level*     replaces the public member mvImagePyramid (include/ORBextractor.h:85)
  *   orbhip_matcher_*          replaces class ORBmatcher (include/ORBmatcher.h:37-103)
  *   orbhip_descriptor_distance  ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:1647-1663)
@@ -28,6 +30,8 @@
  *   orbhip_undistort_keypoints        Frame::UndistortKeyPoints (src/Frame.cc:404-434)
  *   orbhip_assign_features_to_grid    Frame::AssignFeaturesToGrid (src/Frame.cc:230-245)
  *   orbhip_compute_stereo_from_rgbd   Frame::ComputeStereoFromRGBD (src/Frame.cc:643-664)
+ *   orbhip_compute_stereo_from_rgbd_raw  the same on the sensor's depth image: imDepth.convertTo(CV_32F, mDepthMapFactor)
+ *                                     (src/Tracking.cc:227-228) applied to the samples the keypoints read
  *   orbhip_distinctive_descriptors    MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307), batched
  *   orbhip_vocabulary_*               ORBVocabulary (DBoW2::TemplatedVocabulary<FORB>) loadFromTextFile + transform,
  *                                     i.e. Frame::ComputeBoW (src/Frame.cc:395-402)
@@ -94,7 +98,8 @@ int orbhip_extractor_set_blur_kernel(orbhip_extractor *e, const int32_t w[7]);
  * image (BORDER_REFLECT_101 by index where a border keypoint's window overshoots it), results are bit-identical.  The
  * first accessor that needs the plane afterwards (orbhip_pyramid_level / _download / orbhip_blurred_level_download for
  * level 0, orbhip_compute_stereo_matches*) writes it then, from the image buffer of the last extraction: callers of
- * orbhip_extract_batch_device must leave that buffer untouched until then (host entry points keep their own copy).
+ * orbhip_extract_batch_device must leave that buffer untouched until then (host entry points keep their own copy, and
+ * so do the colour entries orbhip_extract_color*: their level 0 comes from the handle's grey frames).
  * Default 0: every extraction materialises it, as the reference does. */
 int orbhip_extractor_set_lazy_level0(orbhip_extractor *e, int on);
 
@@ -128,6 +133,45 @@ int orbhip_extract_batch(orbhip_extractor *e, const uint8_t *images, int batch, 
 int orbhip_extract_batch_device(orbhip_extractor *e, const void *d_images, int batch, int rows,
                                 int cols, int stride, size_t frame_stride, void *d_kps,
                                 void *d_desc, int cap, void *d_n, void *d_status);
+
+/* ---- colour input ----
+ * Tracking::GrabImage{Monocular,Stereo,RGBD} turn a 3- or 4-channel frame into grey with cvtColor(CV_RGB2GRAY /
+ * CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY), chosen by the channel count and Camera.RGB (src/Tracking.cc:103-109,
+ * 172-197, 212-225, 242-256), before the extractor sees it.  The orbhip_extract_color* entries do that conversion on the
+ * device, into a grey buffer the handle owns, and run the unchanged pipeline on it:
+ *     Y = min(255, (R*wR + G*wG + B*wB + (1 << (shift-1))) >> shift)
+ * with wR, wG, wB = 4899, 9617, 1868 and shift = 14 by default: the integer RGB2Gray<uchar> of OpenCV 2.4 - 3.3, restated
+ * from the published algorithm; parity with a given OpenCV build is unpinned.  A shim linked against
+ * another OpenCV installs that build's table: 0 <= w < 65536, 1 <= shift <= 16 (ORBHIP_E_ARG otherwise). */
+#define ORBHIP_COLOR_BGR 0
+#define ORBHIP_COLOR_RGB 1          /* = Camera.RGB (src/Tracking.cc:103-104) */
+int orbhip_extractor_set_gray_weights(orbhip_extractor *e, const int32_t w_rgb[3], int shift);
+
+/* image: rows x cols pixels of `channels` (3 or 4) interleaved uint8, row stride `stride` bytes >= cols*channels; rgb:
+ * ORBHIP_COLOR_RGB = byte 0 of a pixel is R, ORBHIP_COLOR_BGR = byte 0 is B; a fourth channel is ignored.  Anything else
+ * about the call is orbhip_extract / orbhip_extract_batch / orbhip_extract_batch_device: outputs, capacity rule, an empty
+ * host image gives zero keypoints.  channels other than 3 or 4 (1 is not an alias of the grey entries), a short stride or
+ * a null pointer: ORBHIP_E_ARG before any device work.  No more than the last byte a frame's pixels occupy,
+ * (rows-1)*stride + cols*channels, is read.
+ * The host entries upload the packed colour bytes with one 1-D copy from page-locked staging the handle owns; they launch
+ * eagerly and in one chunk (the graph replay and the chunk pipeline of the grey host entries are not reproduced).
+ * The conversion belongs to stage 0: it runs behind that stage's gate (orbhip_extractor_set_stage_gate) and
+ * orbhip_extractor_stage_times [0] includes it.
+ * After a colour extraction the grey frames are "the image of the last extraction": every accessor
+ * (orbhip_pyramid_level*, orbhip_blurred_level_download, orbhip_level_candidates, orbhip_compute_stereo_matches*) works
+ * as after a grey one, and the level-0 ROI is the converted image.  With orbhip_extractor_set_lazy_level0 the level-0
+ * plane is written later from the handle's grey frames, NOT from the caller's buffer: the lifetime rule stated there does
+ * not apply to colour input, the colour buffer may be reused as soon as the work enqueued by the call has run (stream
+ * order is enough). */
+int orbhip_extract_color(orbhip_extractor *e, const uint8_t *image, int rows, int cols, int channels, int rgb, int stride,
+                         orbhip_keypoint *kps, uint8_t *desc, int cap, int *n);
+int orbhip_extract_color_batch(orbhip_extractor *e, const uint8_t *images, int batch, int rows, int cols, int channels,
+                               int rgb, int stride, size_t frame_stride, orbhip_keypoint *kps, uint8_t *desc, int cap,
+                               int32_t *n);
+int orbhip_extract_color_batch_device(orbhip_extractor *e, const void *d_images, int batch, int rows, int cols,
+                                      int channels, int rgb, int stride, size_t frame_stride, void *d_kps, void *d_desc,
+                                      int cap, void *d_n, void *d_status);
+
 int orbhip_extractor_sync(orbhip_extractor *e);
 void *orbhip_extractor_stream(orbhip_extractor *e); /* hipStream_t */
 /* Launch on a caller-owned hipStream_t instead (NULL: back to the handle's own stream). */
@@ -331,6 +375,21 @@ int orbhip_compute_stereo_from_rgbd_device(orbhip_matcher *m, int frames, const 
                                            const void *d_n, int cap, const void *d_depth, int rows, int cols,
                                            int stride_floats, size_t frame_stride_floats, float mbf, void *d_u_right,
                                            void *d_depth_out);
+/* The same on the depth image as the sensor delivers it (src/Tracking.cc:227-228 in front of src/Frame.cc:643-664):
+ * depth_type ORBHIP_DEPTH_U16 (CV_16U, e.g. TUM's PNGs) or ORBHIP_DEPTH_F32; stride_elems in elements.  depth_factor =
+ * mDepthMapFactor as the Tracking constructor leaves it (1 / DepthMapFactor, 1 when the setting is below 1e-5;
+ * src/Tracking.cc:140-147).  U16: d = (float)raw * depth_factor always; F32: d = raw * depth_factor iff
+ * fabs(depth_factor - 1.0f) > 1e-5, else d = raw.  One rounding of the product, as convertTo(CV_32F, factor) does per
+ * pixel (stated choice): only the N sampled values are converted, no float image exists. */
+#define ORBHIP_DEPTH_U16 0
+#define ORBHIP_DEPTH_F32 1
+int orbhip_compute_stereo_from_rgbd_raw(orbhip_matcher *m, const orbhip_keypoint *keys, const orbhip_keypoint *keys_un, int n,
+                                        const void *depth, int depth_type, int rows, int cols, int stride_elems,
+                                        float depth_factor, float mbf, float *u_right, float *depth_out);
+int orbhip_compute_stereo_from_rgbd_raw_device(orbhip_matcher *m, int frames, const void *d_kps, const void *d_kps_un,
+                                               const void *d_n, int cap, const void *d_depth, int depth_type, int rows,
+                                               int cols, int stride_elems, size_t frame_stride_elems, float depth_factor,
+                                               float mbf, void *d_u_right, void *d_depth_out);
 
 /* ---- DBoW2 vocabulary: ORBVocabulary::loadFromTextFile + transform ---------------------------------------------
  * Replaces, for Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cc:395-402, src/KeyFrame.cc ComputeBoW), the

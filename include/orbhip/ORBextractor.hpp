@@ -24,6 +24,13 @@ struct ImageView {   // the part of cv::Mat the extractor reads (CV_8UC1)
     bool empty() const { return !data || rows <= 0 || cols <= 0; }
 };
 
+struct ColorImageView {   // a CV_8UC3 / CV_8UC4 cv::Mat as Tracking::GrabImage* receives it (src/Tracking.cc:167-260)
+    const uint8_t *data;
+    int rows, cols, channels;
+    size_t step;
+    bool empty() const { return !data || rows <= 0 || cols <= 0; }
+};
+
 struct Error : std::runtime_error {
     int code;
     Error(int c, const char *where) : std::runtime_error(std::string(where) + ": " + orbhip_last_error()), code(c) {}
@@ -84,6 +91,45 @@ public:
             descriptors[b].assign(d.begin() + (size_t)b * cap * 32, d.begin() + ((size_t)b * cap + n[b]) * 32);
         }
     }
+
+    // cvtColor(mImGray, mImGray, CV_RGB2GRAY / CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY) (src/Tracking.cc:172-197, 212-225,
+    // 242-256; rgb = mbRGB) followed by operator(), in one call: the conversion runs on the device in front of the pyramid.
+    void ExtractColor(const ColorImageView &image, bool rgb, std::vector<KeyPoint> &keypoints, std::vector<uint8_t> &descriptors)
+    {
+        keypoints.clear();
+        descriptors.clear();
+        if (image.empty()) return;
+        int cap = 0;
+        check(orbhip_extractor_capacity(h_, image.rows, image.cols, &cap), "orbhip_extractor_capacity");
+        keypoints.resize(cap);
+        descriptors.resize((size_t)cap * 32);
+        int n = 0;
+        check(orbhip_extract_color(h_, image.data, image.rows, image.cols, image.channels, rgb ? ORBHIP_COLOR_RGB : ORBHIP_COLOR_BGR,
+                                   (int)image.step, keypoints.data(), descriptors.data(), cap, &n), "orbhip_extract_color");
+        keypoints.resize(n);
+        descriptors.resize((size_t)n * 32);
+    }
+    void ExtractColorBatch(const uint8_t *images, int batch, int rows, int cols, int channels, bool rgb, size_t step,
+                           size_t frame_stride, std::vector<std::vector<KeyPoint> > &keypoints,
+                           std::vector<std::vector<uint8_t> > &descriptors)
+    {
+        keypoints.assign(batch, std::vector<KeyPoint>());
+        descriptors.assign(batch, std::vector<uint8_t>());
+        if (!images || batch <= 0 || rows <= 0 || cols <= 0) return;
+        int cap = 0;
+        check(orbhip_extractor_capacity(h_, rows, cols, &cap), "orbhip_extractor_capacity");
+        std::vector<KeyPoint> k((size_t)batch * cap);
+        std::vector<uint8_t> d((size_t)batch * cap * 32);
+        std::vector<int32_t> n(batch, 0);
+        check(orbhip_extract_color_batch(h_, images, batch, rows, cols, channels, rgb ? ORBHIP_COLOR_RGB : ORBHIP_COLOR_BGR, (int)step,
+                                         frame_stride, k.data(), d.data(), cap, n.data()), "orbhip_extract_color_batch");
+        for (int b = 0; b < batch; ++b) {
+            keypoints[b].assign(k.begin() + (size_t)b * cap, k.begin() + (size_t)b * cap + n[b]);
+            descriptors[b].assign(d.begin() + (size_t)b * cap * 32, d.begin() + ((size_t)b * cap + n[b]) * 32);
+        }
+    }
+    // the grey weights are data (default: OpenCV 2.4 - 3.3's 4899, 9617, 1868 >> 14)
+    void SetGrayWeights(const int32_t wRGB[3], int shift) { check(orbhip_extractor_set_gray_weights(h_, wRGB, shift), "orbhip_extractor_set_gray_weights"); }
 
     // mvImagePyramid[0] on demand: a monocular Tracking thread never reads it (only Frame::ComputeStereoMatches does)
     void SetLazyLevel0(bool on) { check(orbhip_extractor_set_lazy_level0(h_, on ? 1 : 0), "orbhip_extractor_set_lazy_level0"); }
@@ -360,6 +406,21 @@ public:
         mvDepth.assign(keys.size() ? keys.size() : 1, -1.f);
         check(orbhip_compute_stereo_from_rgbd(m_, keys.data(), keysUn.data(), (int)keys.size(), depth, rows, cols, strideFloats, mbf,
                                               mvuRight.data(), mvDepth.data()), "orbhip_compute_stereo_from_rgbd");
+        mvuRight.resize(keys.size());
+        mvDepth.resize(keys.size());
+    }
+
+    // the same on the sensor's depth image (CV_16U: depthType ORBHIP_DEPTH_U16, or CV_32F): the convertTo(CV_32F,
+    // mDepthMapFactor) of src/Tracking.cc:227-228 is applied to the sampled values; depthFactor = mDepthMapFactor
+    void ComputeStereoFromRGBD(const std::vector<KeyPoint> &keys, const std::vector<KeyPoint> &keysUn, const void *depth, int depthType,
+                               int rows, int cols, int strideElems, float depthFactor, float mbf, std::vector<float> &mvuRight,
+                               std::vector<float> &mvDepth)
+    {
+        mvuRight.assign(keys.size() ? keys.size() : 1, -1.f);
+        mvDepth.assign(keys.size() ? keys.size() : 1, -1.f);
+        check(orbhip_compute_stereo_from_rgbd_raw(m_, keys.data(), keysUn.data(), (int)keys.size(), depth, depthType, rows, cols,
+                                                  strideElems, depthFactor, mbf, mvuRight.data(), mvDepth.data()),
+              "orbhip_compute_stereo_from_rgbd_raw");
         mvuRight.resize(keys.size());
         mvDepth.resize(keys.size());
     }

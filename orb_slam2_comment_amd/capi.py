@@ -41,6 +41,8 @@ class Camera(C.Structure):
 
 
 POINT_PRESENT, POINT_OBSERVED = 1, 2
+COLOR_BGR, COLOR_RGB = 0, 1
+DEPTH_U16, DEPTH_F32 = 0, 1
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
@@ -59,6 +61,10 @@ SYMBOLS = [
     ("orbhip_extract", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _pi]),
     ("orbhip_extract_batch", _i, [_vp, _vp, _i, _i, _i, _i, _sz, _vp, _vp, _i, _vp]),
     ("orbhip_extract_batch_device", _i, [_vp, _vp, _i, _i, _i, _i, _sz, _vp, _vp, _i, _vp, _vp]),
+    ("orbhip_extractor_set_gray_weights", _i, [_vp, _vp, _i]),
+    ("orbhip_extract_color", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _pi]),
+    ("orbhip_extract_color_batch", _i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _sz, _vp, _vp, _i, _vp]),
+    ("orbhip_extract_color_batch_device", _i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _sz, _vp, _vp, _i, _vp, _vp]),
     ("orbhip_extractor_sync", _i, [_vp]),
     ("orbhip_extractor_stream", _vp, [_vp]),
     ("orbhip_extractor_set_stream", _i, [_vp, _vp]),
@@ -91,6 +97,9 @@ SYMBOLS = [
     ("orbhip_assign_features_to_grid_device", _i, [_vp, _i, _vp, _vp, _i, _f, _f, _f, _f, _vp, _vp, _vp]),
     ("orbhip_compute_stereo_from_rgbd", _i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _f, _vp, _vp]),
     ("orbhip_compute_stereo_from_rgbd_device", _i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _sz, _f, _vp, _vp]),
+    ("orbhip_compute_stereo_from_rgbd_raw", _i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp]),
+    ("orbhip_compute_stereo_from_rgbd_raw_device", _i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _sz, _f, _f, _vp,
+                                                        _vp]),
     ("orbhip_distinctive_descriptors", _i, [_vp, _vp, _vp, _i, _vp]),
     ("orbhip_vocabulary_load_text", _i, [C.c_char_p, _i, C.POINTER(_vp)]),
     ("orbhip_vocabulary_create", _i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, C.POINTER(_vp)]),

@@ -11,6 +11,7 @@
 #include "rbrief_pattern.h"
 
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <ctime>
 #include <mutex>
@@ -415,6 +416,83 @@ __global__ __launch_bounds__(256) void k_pyr_rows(uint8_t *__restrict__ pyr, uin
     if (unit >= T.units) return;
     uint8_t *frame = pyr + (size_t)fr * frame_bytes;
     pyr_resize_rows(T, unit, frame + T.src_off, T.src_pitch, frame + T.plane_off);
+}
+
+// ---------------------------------------------------------------------------
+// Packed colour -> grey in front of the pyramid: the cvtColor(CV_{RGB,BGR,RGBA,BGRA}2GRAY) of Tracking::GrabImage*
+// (src/Tracking.cc:172-197, 212-225, 242-256).  Y = min(255, (c0*w0 + c1*w1 + c2*w2 + (1 << (shift-1))) >> shift) with
+// w[k] = the weight of source byte k of a pixel (the host puts wR / wB at byte 0 according to Camera.RGB and 0 at the
+// alpha byte).  16-bit weights go through two byte dot products, w = 256*hi + lo: every term and the sum fit 32 bits
+// (3 * 255 * 65535 + 2^15 < 2^26), so the split is exact.
+//
+// A lane owns one destination dword (4 pixels) of kCvtRows consecutive rows: one byte-unaligned 12- or 16-byte load per
+// row (all issued before the arithmetic), one dword store per row.  The lane of a row's tail (cols not a multiple of 4)
+// reads its 1..3 pixels byte by byte, so nothing beyond (rows-1)*stride + cols*channels of a frame is addressed; the
+// tail bytes of its destination dword are 0 (the grey plane's pitch is a multiple of 64).  No LDS.
+// ---------------------------------------------------------------------------
+constexpr int kCvtRows = 4;
+struct GrayW { uint32_t lo, hi, round; int shift; };   // lo / hi: low / high bytes of (w0, w1, w2, 0) packed per source byte
+
+__device__ __forceinline__ uint32_t gray_px(uint32_t px, const GrayW &W)
+{
+    const uint32_t s = (__builtin_amdgcn_udot4(px, W.hi, 0u, false) << 8) + __builtin_amdgcn_udot4(px, W.lo, W.round, false);
+    return min(s >> W.shift, 255u);
+}
+
+template <int CH>
+__global__ __launch_bounds__(256) void k_cvt_gray(const uint8_t *__restrict__ color, int cstride, size_t cframe_stride,
+                                                  uint8_t *__restrict__ gray, int pitch, size_t gframe_bytes, int rows,
+                                                  int cols, int words, GrayW W)
+{
+    int bx, fr;
+    xcd_remap(bx, fr);
+    // Lanes are dealt linearly over (row group, dword): a wavefront's 64 dwords may straddle two rows and start anywhere in a
+    // cache line.  Measured (profiles/color_stage.json): WRITE_SIZE is 1.11x the grey bytes because of those partial lines.
+    const uint32_t idx = (uint32_t)bx * 256u + threadIdx.x;
+    const uint32_t rg = idx / (uint32_t)words, dw = idx - rg * (uint32_t)words;
+    const int row0 = (int)rg * kCvtRows;
+    if (row0 >= rows) return;
+    const uint8_t *src = color + (size_t)fr * cframe_stride + (size_t)dw * (4 * CH);
+    uint8_t *dst = gray + (size_t)fr * gframe_bytes + (size_t)dw * 4;
+    const int npx = min(4, cols - (int)dw * 4);   // >= 1: words = ceil(cols / 4)
+    uint32_t px[kCvtRows][4];
+    if (npx == 4) {
+#pragma unroll
+        for (int r = 0; r < kCvtRows; ++r) {
+            const uint8_t *p = src + (size_t)min(row0 + r, rows - 1) * (size_t)cstride;   // 64-bit: the caller's stride is not bounded
+            if constexpr (CH == 4) {
+                uint4 v;
+                __builtin_memcpy(&v, p, 16);
+                px[r][0] = v.x; px[r][1] = v.y; px[r][2] = v.z; px[r][3] = v.w;
+            } else {
+                uint32_t v[3];
+                __builtin_memcpy(v, p, 12);
+                // pixel k starts at byte 3k; the byte above a pixel's three meets weight 0
+                px[r][0] = v[0];
+                px[r][1] = __builtin_amdgcn_alignbyte(v[1], v[0], 3);
+                px[r][2] = __builtin_amdgcn_alignbyte(v[2], v[1], 2);
+                px[r][3] = v[2] >> 8;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < kCvtRows; ++r) {
+            const uint8_t *p = src + (size_t)min(row0 + r, rows - 1) * (size_t)cstride;   // 64-bit: the caller's stride is not bounded
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                px[r][k] = 0;
+                if (k < npx) px[r][k] = (uint32_t)p[CH * k] | ((uint32_t)p[CH * k + 1] << 8) | ((uint32_t)p[CH * k + 2] << 16);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < kCvtRows; ++r) {
+        if (row0 + r >= rows) break;
+        uint32_t o = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o |= (k < npx ? gray_px(px[r][k], W) : 0u) << (8 * k);
+        *reinterpret_cast<uint32_t *>(dst + (size_t)((uint32_t)(row0 + r) * (uint32_t)pitch)) = o;
+    }
 }
 
 constexpr int kSubMax = 72;              // max (wCell+6), (hCell+6)
@@ -1589,6 +1667,7 @@ static void free_batch(orbhip_extractor *e)
     (void)hipFree(e->d_keys); (void)hipFree(e->d_knode); (void)hipFree(e->d_sel); (void)hipFree(e->d_sel_cnt); (void)hipFree(e->d_status);
     e->d_pyr = e->d_blur = nullptr; e->d_cell_cnt = nullptr; e->d_cell_kp = nullptr; e->d_keys = nullptr;
     e->d_knode = nullptr; e->d_sel = nullptr; e->d_sel_cnt = nullptr; e->d_status = nullptr;
+    (void)hipFree(e->d_gray); e->d_gray = nullptr; e->gray_cap = 0;
     e->batch_cap = 0;
     e->blur_valid = false;
 }
@@ -1999,9 +2078,14 @@ int orbhip::ensure_level0(orbhip_extractor *e, hipStream_t consumer)
 
 // `frame0`: first internal frame slot of this launch (the host path runs a batch as several chunks, each in its own
 // slots, so that every frame's pyramid stays resident for orbhip_pyramid_level / ComputeStereoMatches afterwards)
+//
+// `color`: the frames arrive as packed colour; stage 0 starts by converting them into d_images (= the handle's grey
+// buffer), behind the stage's gate and inside its profiling interval
+struct ColorSrc { const uint8_t *d_color; int channels, rgb, stride; size_t frame_stride; };
+static int gray_pitch(int cols) { return (cols + 63) & ~63; }
 static int launch_pipeline(orbhip_extractor *e, const uint8_t *d_images, int batch, int stride,
                            size_t frame_stride, orbhip_keypoint *d_kps, uint8_t *d_desc, int cap,
-                           int *d_n, int *d_status, int frame0 = 0)
+                           int *d_n, int *d_status, int frame0 = 0, const ColorSrc *color = nullptr)
 {
     const PyrGeom &G = e->G;
     hipStream_t s = e->stream;
@@ -2024,6 +2108,21 @@ static int launch_pipeline(orbhip_extractor *e, const uint8_t *d_images, int bat
 #define ORBHIP_GATE_IN(st) do { if (e->gate_wait[st]) (void)hipStreamWaitEvent(s, e->gate_wait[st], 0); } while (0)
 #define ORBHIP_GATE_OUT(st) do { if (e->gate_rec[st]) (void)hipEventRecord(e->gate_rec[st], s); } while (0)
     ORBHIP_GATE_IN(0);
+    if (color) {
+        const int wb = color->rgb ? 2 : 0;   // source byte that holds B
+        const uint32_t w[4] = {(uint32_t)e->gray_w[2 - wb], (uint32_t)e->gray_w[1], (uint32_t)e->gray_w[wb], 0u};
+        GrayW W = {0, 0, 1u << (e->gray_shift - 1), e->gray_shift};
+        for (int k = 0; k < 3; ++k) { W.lo |= (w[k] & 255u) << (8 * k); W.hi |= (w[k] >> 8) << (8 * k); }
+        const int words = (G.cols + 3) >> 2, nrg = (G.rows + kCvtRows - 1) / kCvtRows;
+        const dim3 grid((unsigned)(((long long)words * nrg + 255) / 256), batch);
+        uint8_t *gray = const_cast<uint8_t *>(d_images);
+        if (color->channels == 4)
+            hipLaunchKernelGGL(k_cvt_gray<4>, grid, dim3(256), 0, s, color->d_color, color->stride, color->frame_stride, gray, stride,
+                               frame_stride, G.rows, G.cols, words, W);
+        else
+            hipLaunchKernelGGL(k_cvt_gray<3>, grid, dim3(256), 0, s, color->d_color, color->stride, color->frame_stride, gray, stride,
+                               frame_stride, G.rows, G.cols, words, W);
+    }
     if (sm & 1) {
         // level 0 and, when its taps allow, level 1 in one launch
         const bool l1_rows = G.nlevels > 1 && e->ptab_rows[1];
@@ -2106,6 +2205,48 @@ static int launch_pipeline(orbhip_extractor *e, const uint8_t *d_images, int bat
     e->last_batch = frame0 + batch;
     ORBHIP_HIP_CHECK(hipGetLastError());
     return ORBHIP_OK;
+}
+
+// Output side of the host-pointer entries (grey and colour): device result arrays and their page-locked host twin
+static int ensure_out_staging(orbhip_extractor *e, int batch, int cap)
+{
+    if ((size_t)cap * batch > e->out_slots || batch > e->out_batch) {
+        drop_graph(e);
+        (void)hipFree(e->d_okp); (void)hipFree(e->d_odesc); (void)hipFree(e->d_on);
+        e->d_okp = nullptr; e->d_odesc = nullptr; e->d_on = nullptr;
+        e->out_slots = 0; e->out_batch = 0;
+        const size_t slots = (size_t)cap * batch;
+        ORBHIP_HIP_CHECK(hipMalloc(&e->d_okp, slots * sizeof(orbhip_keypoint)));
+        ORBHIP_HIP_CHECK(hipMalloc(&e->d_odesc, slots * 32));
+        ORBHIP_HIP_CHECK(hipMalloc(&e->d_on, (size_t)batch * sizeof(int)));
+        e->out_slots = slots; e->out_batch = batch;
+    }
+    const size_t out_bytes = (size_t)batch * (2 * sizeof(int) + (size_t)cap * (sizeof(orbhip_keypoint) + 32));
+    if (out_bytes > e->h_out_bytes) {
+        drop_graph(e);
+        if (e->h_out) (void)hipHostFree(e->h_out);
+        e->h_out = nullptr; e->h_out_bytes = 0;
+        ORBHIP_HIP_CHECK(hipHostMalloc((void **)&e->h_out, out_bytes, hipHostMallocDefault));
+        e->h_out_bytes = out_bytes;
+    }
+    return ORBHIP_OK;
+}
+
+// Grey frames of a colour extraction: batch x rows x gray_pitch(cols), plus slack for the pipeline's window loads
+static int ensure_gray(orbhip_extractor *e, int batch)
+{
+    if (batch <= e->gray_cap) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
+    (void)hipFree(e->d_gray); e->d_gray = nullptr; e->gray_cap = 0;
+    ORBHIP_HIP_CHECK(hipMalloc(&e->d_gray, (size_t)batch * e->G.rows * gray_pitch(e->G.cols) + 256));
+    e->gray_cap = batch;
+    return ORBHIP_OK;
+}
+
+static bool color_args_ok(int batch, int rows, int cols, int channels, int stride, int cap)
+{
+    return batch > 0 && rows > 0 && cols > 0 && (channels == 3 || channels == 4) && cols <= INT_MAX / 4 &&
+           stride >= cols * channels && cap > 0;
 }
 
 extern "C" {
@@ -2241,6 +2382,8 @@ void orbhip_extractor_destroy(orbhip_extractor *e)
     free_geometry(e);
     free_batch(e);
     (void)hipFree(e->d_patternf); (void)hipFree(e->d_desc_tab); (void)hipFree(e->d_img); (void)hipFree(e->d_okp); (void)hipFree(e->d_odesc); (void)hipFree(e->d_on);
+    (void)hipFree(e->d_cimg);
+    if (e->h_cin) (void)hipHostFree(e->h_cin);
     if (e->h_in) (void)hipHostFree(e->h_in);
     if (e->h_out) (void)hipHostFree(e->h_out);
     for (hipEvent_t v : e->ev) (void)hipEventDestroy(v);
@@ -2361,17 +2504,7 @@ int orbhip_extract_batch(orbhip_extractor *e, const uint8_t *images, int batch, 
         ORBHIP_HIP_CHECK(hipMalloc(&e->d_img, img_bytes));
         e->d_img_bytes = img_bytes;
     }
-    if ((size_t)cap * batch > e->out_slots || batch > e->out_batch) {
-        drop_graph(e);
-        (void)hipFree(e->d_okp); (void)hipFree(e->d_odesc); (void)hipFree(e->d_on);
-        e->d_okp = nullptr; e->d_odesc = nullptr; e->d_on = nullptr;
-        e->out_slots = 0; e->out_batch = 0;
-        const size_t slots = (size_t)cap * batch;
-        ORBHIP_HIP_CHECK(hipMalloc(&e->d_okp, slots * sizeof(orbhip_keypoint)));
-        ORBHIP_HIP_CHECK(hipMalloc(&e->d_odesc, slots * 32));
-        ORBHIP_HIP_CHECK(hipMalloc(&e->d_on, (size_t)batch * sizeof(int)));
-        e->out_slots = slots; e->out_batch = batch;
-    }
+    if ((rc = ensure_out_staging(e, batch, cap))) return rc;
     // host -> pinned staging (row copies on the CPU) -> one DMA
     if (!pinned_src && img_bytes > e->h_in_bytes) {
         drop_graph(e);
@@ -2379,14 +2512,6 @@ int orbhip_extract_batch(orbhip_extractor *e, const uint8_t *images, int batch, 
         e->h_in = nullptr; e->h_in_bytes = 0;
         ORBHIP_HIP_CHECK(hipHostMalloc((void **)&e->h_in, img_bytes, hipHostMallocDefault));
         e->h_in_bytes = img_bytes;
-    }
-    const size_t out_bytes = (size_t)batch * (2 * sizeof(int) + (size_t)cap * (sizeof(orbhip_keypoint) + 32));
-    if (out_bytes > e->h_out_bytes) {
-        drop_graph(e);
-        if (e->h_out) (void)hipHostFree(e->h_out);
-        e->h_out = nullptr; e->h_out_bytes = 0;
-        ORBHIP_HIP_CHECK(hipHostMalloc((void **)&e->h_out, out_bytes, hipHostMallocDefault));
-        e->h_out_bytes = out_bytes;
     }
     ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));   // the staging buffer of the previous call is free
     rc = ensure_batch(e, batch);
@@ -2518,6 +2643,111 @@ int orbhip_extract(orbhip_extractor *e, const uint8_t *image, int rows, int cols
     if (!n) return ORBHIP_E_ARG;
     int32_t nn = 0;
     int rc = orbhip_extract_batch(e, image, 1, rows, cols, stride, 0, kps, desc, cap, &nn);
+    *n = nn;
+    return rc;
+}
+
+int orbhip_extractor_set_gray_weights(orbhip_extractor *e, const int32_t w_rgb[3], int shift)
+{
+    if (!e || !w_rgb || shift < 1 || shift > 16) return ORBHIP_E_ARG;
+    for (int i = 0; i < 3; ++i) if (w_rgb[i] < 0 || w_rgb[i] > 65535) return ORBHIP_E_ARG;
+    for (int i = 0; i < 3; ++i) e->gray_w[i] = w_rgb[i];
+    e->gray_shift = shift;   // by-value arguments of k_cvt_gray, which no captured graph holds
+    return ORBHIP_OK;
+}
+
+int orbhip_extract_color_batch_device(orbhip_extractor *e, const void *d_images, int batch, int rows, int cols, int channels,
+                                      int rgb, int stride, size_t frame_stride, void *d_kps, void *d_desc, int cap, void *d_n,
+                                      void *d_status)
+{
+    if (!e || !d_images || !d_kps || !d_desc || !d_n || !color_args_ok(batch, rows, cols, channels, stride, cap)) {
+        set_error("orbhip_extract_color_batch_device: bad argument");
+        return ORBHIP_E_ARG;
+    }
+    ORBHIP_HIP_CHECK(hipSetDevice(e->device));
+    int rc = bind_geometry(e, rows, cols);
+    if (rc) return rc;
+    if ((rc = ensure_batch(e, batch))) return rc;
+    if ((rc = ensure_gray(e, batch))) return rc;
+    // from here on the handle's grey frames are "the image" of this extraction (also for a lazy level 0)
+    const int pitch = gray_pitch(cols);
+    const size_t gframe = (size_t)rows * pitch;
+    if ((rc = begin_extraction(e, e->d_gray, pitch, gframe))) return rc;
+    const ColorSrc C = {(const uint8_t *)d_images, channels, rgb != 0, stride, frame_stride};
+    return launch_pipeline(e, e->d_gray, batch, pitch, gframe, (orbhip_keypoint *)d_kps, (uint8_t *)d_desc, cap, (int *)d_n,
+                           (int *)d_status, 0, &C);
+}
+
+// Host colour frames: rows packed into page-locked staging by the CPU, ONE 1-D copy to the device, then the device path
+// on the handle's stream and one copy per output array back.  Eager launches, one chunk (the grey host entries' graph
+// replay and three-stream chunk pipeline are not reproduced here).
+int orbhip_extract_color_batch(orbhip_extractor *e, const uint8_t *images, int batch, int rows, int cols, int channels, int rgb,
+                               int stride, size_t frame_stride, orbhip_keypoint *kps, uint8_t *desc, int cap, int32_t *n)
+{
+    if (!e || !kps || !desc || !n || batch <= 0 || cap <= 0 || (channels != 3 && channels != 4)) {
+        set_error("orbhip_extract_color_batch: bad argument");
+        return ORBHIP_E_ARG;
+    }
+    if (!images || rows <= 0 || cols <= 0) {  // empty image: silent return (:1046-1047)
+        for (int b = 0; b < batch; ++b) n[b] = 0;
+        return ORBHIP_OK;
+    }
+    if (!color_args_ok(batch, rows, cols, channels, stride, cap)) { set_error("orbhip_extract_color_batch: bad argument"); return ORBHIP_E_ARG; }
+    ORBHIP_HIP_CHECK(hipSetDevice(e->device));
+    int rc = bind_geometry(e, rows, cols);
+    if (rc) return rc;
+    const size_t rbytes = (size_t)cols * channels, fbytes = (size_t)rows * rbytes, img_bytes = (size_t)batch * fbytes;
+    if (img_bytes > e->d_cimg_bytes) {
+        ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
+        (void)hipFree(e->d_cimg); e->d_cimg = nullptr; e->d_cimg_bytes = 0;
+        ORBHIP_HIP_CHECK(hipMalloc(&e->d_cimg, img_bytes));
+        e->d_cimg_bytes = img_bytes;
+    }
+    if (img_bytes > e->h_cin_bytes) {
+        ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
+        if (e->h_cin) (void)hipHostFree(e->h_cin);
+        e->h_cin = nullptr; e->h_cin_bytes = 0;
+        ORBHIP_HIP_CHECK(hipHostMalloc((void **)&e->h_cin, img_bytes, hipHostMallocDefault));
+        e->h_cin_bytes = img_bytes;
+    }
+    if ((rc = ensure_out_staging(e, batch, cap))) return rc;
+    ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));   // the staging buffers of the previous call are free
+    for (int b = 0; b < batch; ++b) {
+        const uint8_t *src = images + b * frame_stride;
+        uint8_t *dst = e->h_cin + (size_t)b * fbytes;
+        if ((size_t)stride == rbytes) memcpy(dst, src, fbytes);
+        else for (int r = 0; r < rows; ++r) memcpy(dst + (size_t)r * rbytes, src + (size_t)r * stride, rbytes);
+    }
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(e->d_cimg, e->h_cin, img_bytes, hipMemcpyHostToDevice, e->stream));
+    if ((rc = orbhip_extract_color_batch_device(e, e->d_cimg, batch, rows, cols, channels, rgb, (int)rbytes, fbytes, e->d_okp,
+                                                e->d_odesc, cap, e->d_on, nullptr))) return rc;
+    int *h_n = reinterpret_cast<int *>(e->h_out), *h_st = h_n + batch;
+    orbhip_keypoint *h_kp = reinterpret_cast<orbhip_keypoint *>(h_st + batch);
+    uint8_t *h_desc = reinterpret_cast<uint8_t *>(h_kp + (size_t)batch * cap);
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_n, e->d_on, batch * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_st, e->d_status, batch * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_kp, e->d_okp, (size_t)batch * cap * sizeof(orbhip_keypoint), hipMemcpyDeviceToHost, e->stream));
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_desc, e->d_odesc, (size_t)batch * cap * 32, hipMemcpyDeviceToHost, e->stream));
+    ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
+    int bad = -1;   // as orbhip_extract_batch: truncated frames are delivered before the capacity error is reported
+    for (int b = 0; b < batch; ++b) {
+        n[b] = std::min(h_n[b], cap);
+        if (h_st[b] != 0 && bad < 0) bad = b;
+        if (n[b] > 0) {
+            memcpy(kps + (size_t)b * cap, h_kp + (size_t)b * cap, (size_t)n[b] * sizeof(orbhip_keypoint));
+            memcpy(desc + (size_t)b * cap * 32, h_desc + (size_t)b * cap * 32, (size_t)n[b] * 32);
+        }
+    }
+    if (bad >= 0) { set_error("frame %d: capacity exceeded (cap %d); outputs are truncated", bad, cap); return ORBHIP_E_CAPACITY; }
+    return ORBHIP_OK;
+}
+
+int orbhip_extract_color(orbhip_extractor *e, const uint8_t *image, int rows, int cols, int channels, int rgb, int stride,
+                         orbhip_keypoint *kps, uint8_t *desc, int cap, int *n)
+{
+    if (!n) return ORBHIP_E_ARG;
+    int32_t nn = 0;
+    int rc = orbhip_extract_color_batch(e, image, 1, rows, cols, channels, rgb, stride, 0, kps, desc, cap, &nn);
     *n = nn;
     return rc;
 }

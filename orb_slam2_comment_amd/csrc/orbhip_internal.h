@@ -117,6 +117,13 @@ struct orbhip_extractor {
     uint32_t *d_sel = nullptr;
     int *d_sel_cnt = nullptr;
     int *d_status = nullptr;
+    // colour input (orbhip_extract_color*): the grey frames k_cvt_gray writes, which the pipeline then reads as "the image".
+    // Allocated by the first colour extraction of a (geometry, batch) and freed with the per-batch buffers.
+    uint8_t *d_gray = nullptr;
+    int gray_cap = 0;               // frames d_gray holds
+    int gray_w[3] = {4899, 9617, 1868}, gray_shift = 14;   // wR, wG, wB (orbhip_extractor_set_gray_weights)
+    uint8_t *d_cimg = nullptr; size_t d_cimg_bytes = 0;    // host colour entries: packed colour frames on the device ...
+    uint8_t *h_cin = nullptr; size_t h_cin_bytes = 0;      // ... and their page-locked staging
     // staging for the host-pointer API
     uint8_t *d_img = nullptr; size_t d_img_bytes = 0;
     orbhip_keypoint *d_okp = nullptr; uint8_t *d_odesc = nullptr; int *d_on = nullptr;

@@ -1732,6 +1732,38 @@ __global__ void k_stereo_from_rgbd(const orbhip_keypoint *__restrict__ keys, con
     depth_out[i] = dp;
 }
 
+// The same on the depth image as the sensor delivers it: Tracking::GrabImageRGBD's
+//     if ((fabs(mDepthMapFactor - 1.0f) > 1e-5) || imDepth.type() != CV_32F) imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor);
+// (src/Tracking.cc:227-228) is applied to the one sample a keypoint reads instead of to rows x cols pixels.  Equal bit
+// for bit to convert-then-sample: convertTo with a zero shift computes saturate_cast<float>(src * alpha + 0) per pixel
+// in float; a 16-bit integer is exact in float, and adding +0 to the rounded product -- or fusing it into an fma, whose
+// single rounding is then the rounding of the product alone -- leaves fl(src * alpha).  (A product of -0 would become
+// +0; neither passes d > 0.)  `convert`: that condition, evaluated once on the host.
+template <typename T>
+__global__ void k_stereo_from_rgbd_raw(const orbhip_keypoint *__restrict__ keys, const orbhip_keypoint *__restrict__ keys_un,
+                                       const int *__restrict__ n_dev, int cap, const T *__restrict__ depth, int rows, int cols,
+                                       int stride, size_t frame_stride, float factor, int convert, float mbf,
+                                       float *__restrict__ u_right, float *__restrict__ depth_out)
+{
+    const int frame = blockIdx.y;
+    keys += (size_t)frame * cap; keys_un += (size_t)frame * cap;
+    u_right += (size_t)frame * cap; depth_out += (size_t)frame * cap;
+    depth += (size_t)frame * frame_stride;
+    const int n = min(n_dev[frame], cap);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int v = (int)keys[i].y, u = (int)keys[i].x;      // Mat::at<float>(int,int) with float arguments: truncation
+    float d = 0.f;
+    if (v >= 0 && v < rows && u >= 0 && u < cols) {
+        d = (float)depth[(size_t)v * stride + u];
+        if (convert) d = __fmul_rn(d, factor);
+    }
+    float ur = -1.0f, dp = -1.0f;
+    if (d > 0) { dp = d; ur = __fsub_rn(keys_un[i].x, __fdiv_rn(mbf, d)); }
+    u_right[i] = ur;
+    depth_out[i] = dp;
+}
+
 // ---- Frame::ComputeStereoMatches (Frame.cc:466-640) -----------------------------------------
 // ---------------------------------------------------------------------------
 // Projection prologues (include/orbhip.h "projection prologues on the device"): one thread per map point.  Every
@@ -3082,6 +3114,69 @@ int orbhip_compute_stereo_from_rgbd(orbhip_matcher *m, const orbhip_keypoint *ke
     float *d_out = (float *)p;
     if ((rc = orbhip_compute_stereo_from_rgbd_device(m, 1, d_keys, d_un, d_n, n, d_depth, rows, cols, cols, 0, mbf, d_out,
                                                      d_out + n))) return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, d_out, (size_t)2 * n * sizeof(float), &h))) return rc;
+    memcpy(u_right, h, (size_t)n * sizeof(float));
+    memcpy(depth_out, h + (size_t)n * sizeof(float), (size_t)n * sizeof(float));
+    return ORBHIP_OK;
+}
+
+int orbhip_compute_stereo_from_rgbd_raw_device(orbhip_matcher *m, int frames, const void *d_kps, const void *d_kps_un,
+                                               const void *d_n, int cap, const void *d_depth, int depth_type, int rows, int cols,
+                                               int stride_elems, size_t frame_stride_elems, float depth_factor, float mbf,
+                                               void *d_u_right, void *d_depth_out)
+{
+    if (!m || frames < 0 || cap < 1 || !d_kps || !d_n || !d_depth || rows < 1 || cols < 1 || stride_elems < cols ||
+        !d_u_right || !d_depth_out || (depth_type != ORBHIP_DEPTH_U16 && depth_type != ORBHIP_DEPTH_F32))
+        return ORBHIP_E_ARG;
+    if (frames == 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const orbhip_keypoint *k = (const orbhip_keypoint *)d_kps, *ku = (const orbhip_keypoint *)(d_kps_un ? d_kps_un : d_kps);
+    const dim3 grid((cap + 255) / 256, frames);
+    if (depth_type == ORBHIP_DEPTH_U16) {
+        hipLaunchKernelGGL(k_stereo_from_rgbd_raw<uint16_t>, grid, dim3(256), 0, m->stream, k, ku, (const int *)d_n, cap,
+                           (const uint16_t *)d_depth, rows, cols, stride_elems, frame_stride_elems, depth_factor, 1, mbf,
+                           (float *)d_u_right, (float *)d_depth_out);
+    } else {
+        volatile float diff = depth_factor - 1.0f;   // float subtraction, then fabs and the comparison in double (:227)
+        const int convert = fabs((double)diff) > 1e-5;
+        hipLaunchKernelGGL(k_stereo_from_rgbd_raw<float>, grid, dim3(256), 0, m->stream, k, ku, (const int *)d_n, cap,
+                           (const float *)d_depth, rows, cols, stride_elems, frame_stride_elems, depth_factor, convert, mbf,
+                           (float *)d_u_right, (float *)d_depth_out);
+    }
+    ORBHIP_HIP_CHECK(hipGetLastError());
+    return ORBHIP_OK;
+}
+
+int orbhip_compute_stereo_from_rgbd_raw(orbhip_matcher *m, const orbhip_keypoint *keys, const orbhip_keypoint *keys_un, int n,
+                                        const void *depth, int depth_type, int rows, int cols, int stride_elems,
+                                        float depth_factor, float mbf, float *u_right, float *depth_out)
+{
+    if (!m || n < 0 || (n > 0 && (!keys || !u_right || !depth_out)) || !depth || rows < 1 || cols < 1 || stride_elems < cols ||
+        (depth_type != ORBHIP_DEPTH_U16 && depth_type != ORBHIP_DEPTH_F32))
+        return ORBHIP_E_ARG;
+    if (n == 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    if (!keys_un) keys_un = keys;
+    // the raw depth image travels as the float one does: packed rows through the pinned staging buffer, half the bytes for uint16
+    Stage st;
+    int rc;
+    const size_t esz = depth_type == ORBHIP_DEPTH_U16 ? 2 : 4, rb = (size_t)cols * esz;
+    const size_t kb = al256((size_t)n * sizeof(orbhip_keypoint)), ib = al256((size_t)rows * rb);
+    if ((rc = stage_begin(m, 2 * kb + ib + 256, &st))) return rc;
+    const orbhip_keypoint *d_keys = st.put(keys, (size_t)n);
+    const orbhip_keypoint *d_un = st.put(keys_un, (size_t)n);
+    const uint8_t *d_depth;
+    uint8_t *hd = st.take((size_t)rows * rb, &d_depth);
+    const int *d_n = st.put(&n, 1);
+    if ((rc = st.status())) return rc;
+    for (int r = 0; r < rows; ++r) memcpy(hd + (size_t)r * rb, (const uint8_t *)depth + (size_t)r * stride_elems * esz, rb);
+    if ((rc = stage_commit(m, &st))) return rc;
+    void *p;
+    if ((rc = scratch(m, S_OUT, (size_t)2 * n * sizeof(float), &p))) return rc;
+    float *d_out = (float *)p;
+    if ((rc = orbhip_compute_stereo_from_rgbd_raw_device(m, 1, d_keys, d_un, d_n, n, d_depth, depth_type, rows, cols, cols, 0,
+                                                         depth_factor, mbf, d_out, d_out + n))) return rc;
     const uint8_t *h;
     if ((rc = read_back(m, d_out, (size_t)2 * n * sizeof(float), &h))) return rc;
     memcpy(u_right, h, (size_t)n * sizeof(float));

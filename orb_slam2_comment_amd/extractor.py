@@ -139,6 +139,62 @@ class ORBextractor:
               "orbhip_extract_batch_device")
         self._shape = (rows, cols)
 
+    # -- colour input: cvtColor(.., CV_{RGB,BGR,RGBA,BGRA}2GRAY) of Tracking::GrabImage* (src/Tracking.cc:172-256) + operator()
+    def set_gray_weights(self, w_rgb=(4899, 9617, 1868), shift=14):
+        """Y = min(255, (R*wR + G*wG + B*wB + (1 << (shift-1))) >> shift); the default is OpenCV 2.4 - 3.3's table."""
+        w = np.ascontiguousarray(w_rgb, np.int32)
+        assert w.shape == (3,)
+        check(self._lib.orbhip_extractor_set_gray_weights(self._h, ptr(w), int(shift)), "orbhip_extractor_set_gray_weights")
+
+    @staticmethod
+    def _color_view(images, ndim):
+        if images.dtype != np.uint8 or images.ndim != ndim or images.shape[-1] not in (3, 4):
+            raise TypeError("expected a CV_8UC3 / CV_8UC4 image")
+        if images.strides[-1] != 1 or images.strides[-2] != images.shape[-1] or \
+                any(s < images.shape[-2] * images.shape[-1] for s in images.strides[:-2]):   # flipped / broadcast / overlapping rows
+            images = np.ascontiguousarray(images)
+        return images
+
+    def extract_color(self, image, rgb):
+        """image: uint8 [rows, cols, 3|4]; rgb: Camera.RGB (True: byte 0 is R).  Returns (keypoints, descriptors)."""
+        if image is None or image.size == 0:
+            return np.zeros(0, KP_DTYPE), np.zeros((0, 32), np.uint8)
+        image = self._color_view(image, 3)
+        rows, cols, ch = image.shape
+        cap = self.capacity(rows, cols)
+        kps = np.zeros(cap, KP_DTYPE)
+        desc = np.zeros((cap, 32), np.uint8)
+        n = C.c_int()
+        check(self._lib.orbhip_extract_color(self._h, ptr(image), rows, cols, ch, int(bool(rgb)), image.strides[0], ptr(kps),
+                                             ptr(desc), cap, C.byref(n)), "orbhip_extract_color")
+        self._shape = (rows, cols)
+        return kps[:n.value].copy(), desc[:n.value].copy()
+
+    def extract_color_batch(self, images, rgb):
+        """images: uint8 [B, rows, cols, 3|4] on the host.  Returns list of (keypoints, descriptors)."""
+        images = self._color_view(images, 4)
+        B, rows, cols, ch = images.shape
+        cap = self.capacity(rows, cols)
+        kps = np.zeros((B, cap), KP_DTYPE)
+        desc = np.zeros((B, cap, 32), np.uint8)
+        n = np.zeros(B, np.int32)
+        check(self._lib.orbhip_extract_color_batch(self._h, ptr(images), B, rows, cols, ch, int(bool(rgb)), images.strides[1],
+                                                   images.strides[0], ptr(kps), ptr(desc), cap, ptr(n)),
+              "orbhip_extract_color_batch")
+        self._shape = (rows, cols)
+        return [(kps[b, :n[b]].copy(), desc[b, :n[b]].copy()) for b in range(B)]
+
+    def extract_color_batch_device(self, d_images, batch, rows, cols, channels, rgb, d_kps, d_desc, cap, d_n, d_status=0,
+                                   stride=None, frame_stride=None):
+        """Device-pointer entry (ints from torch .data_ptr()); asynchronous on the handle's stream.  The colour buffer
+        may be reused once this call's work has run: a lazy level 0 is built from the handle's grey frames."""
+        stride = cols * channels if stride is None else stride
+        frame_stride = rows * stride if frame_stride is None else frame_stride
+        check(self._lib.orbhip_extract_color_batch_device(self._h, d_images, batch, rows, cols, channels, int(bool(rgb)),
+                                                          stride, frame_stride, d_kps, d_desc, cap, d_n, d_status),
+              "orbhip_extract_color_batch_device")
+        self._shape = (rows, cols)
+
     def sync(self):
         check(self._lib.orbhip_extractor_sync(self._h), "orbhip_extractor_sync")
 

@@ -251,6 +251,36 @@ class ORBmatcher:
               "orbhip_compute_stereo_from_rgbd")
         return ur[:len(k)].copy(), dp[:len(k)].copy()
 
+    def ComputeStereoFromRGBDRaw(self, keys, keys_un, imDepth, depth_factor, mbf):
+        """Frame::ComputeStereoFromRGBD on the depth image as the sensor delivers it: imDepth 2-D uint16 or float32,
+        depth_factor = mDepthMapFactor (settings.depth_map_factor).  The convertTo of src/Tracking.cc:227-228 is applied to
+        the sampled values only.  Returns (mvuRight, mvDepth)."""
+        k = np.ascontiguousarray(keys, KP_DTYPE)
+        ku = k if keys_un is None else np.ascontiguousarray(keys_un, KP_DTYPE)
+        d = np.asarray(imDepth)
+        if d.ndim != 2 or d.dtype not in (np.uint16, np.float32):
+            raise TypeError("expected a CV_16U or CV_32F depth image")
+        d = np.ascontiguousarray(d)
+        typ = capi.DEPTH_U16 if d.dtype == np.uint16 else capi.DEPTH_F32
+        ur = np.full(max(len(k), 1), -1, np.float32)
+        dp = np.full(max(len(k), 1), -1, np.float32)
+        check(self._lib.orbhip_compute_stereo_from_rgbd_raw(self._h, ptr(k), ptr(ku), len(k), ptr(d), typ, d.shape[0],
+                                                            d.shape[1], d.shape[1], float(np.float32(depth_factor)),
+                                                            float(mbf), ptr(ur), ptr(dp)),
+              "orbhip_compute_stereo_from_rgbd_raw")
+        return ur[:len(k)].copy(), dp[:len(k)].copy()
+
+    def compute_stereo_from_rgbd_raw_device(self, frames, d_kps, d_kps_un, d_n, cap, d_depth, depth_type, rows, cols,
+                                            depth_factor, mbf, d_u_right, d_depth_out, stride=None, frame_stride=None):
+        """Batched, device-resident form (device pointers as ints); strides in elements.  Asynchronous."""
+        stride = cols if stride is None else stride
+        frame_stride = rows * stride if frame_stride is None else frame_stride
+        check(self._lib.orbhip_compute_stereo_from_rgbd_raw_device(self._h, frames, d_kps, d_kps_un, d_n, cap, d_depth,
+                                                                   depth_type, rows, cols, stride, frame_stride,
+                                                                   float(np.float32(depth_factor)), float(mbf), d_u_right,
+                                                                   d_depth_out),
+              "orbhip_compute_stereo_from_rgbd_raw_device")
+
     # -- device-resident, batched SearchByProjection ---------------------------
     def set_stream(self, stream):
         check(self._lib.orbhip_matcher_set_stream(self._h, stream), "orbhip_matcher_set_stream")

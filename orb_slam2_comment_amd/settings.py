@@ -1,6 +1,8 @@
 """The part of the example harness that feeds the front-end: the settings file (cv::FileStorage YAML subset read by the
-Tracking constructor, src/Tracking.cc:51-125) and the KITTI sequence layout of Examples/Monocular/mono_kitti.cc:127-157.
-No OpenCV: scalars are parsed from the text, images are decoded by a small 8-bit grayscale PNG / PGM reader."""
+Tracking constructor, src/Tracking.cc:51-147), the KITTI sequence layout of Examples/Monocular/mono_kitti.cc:127-157 and
+the TUM lists of Examples/RGB-D/rgbd_tum.cc:142-167 / Examples/Monocular/mono_tum.cc:127-160.
+No OpenCV: scalars are parsed from the text, images are decoded by a small PNG (8-bit grey / RGB / RGBA, 16-bit grey) /
+PGM reader."""
 import os
 import struct
 import zlib
@@ -109,6 +111,16 @@ def _read_gray_image_py(path):
         if maxval != 255:
             raise ValueError("%s: only 8-bit PGM is supported" % path)
         return np.frombuffer(data, np.uint8, w * h, pos + 1).reshape(h, w).copy()
+    hdr, rows = _png_rows(path, data)
+    w, h, depth, ctype = hdr
+    if depth != 8 or ctype != 0:
+        raise ValueError("%s: only non-interlaced 8-bit grayscale PNG is supported (depth %d, colour type %d)"
+                         % (path, depth, ctype))
+    return rows
+
+
+def _png_rows(path, data):
+    """Defiltered scanlines of a non-interlaced PNG with whole-byte samples: ((w, h, depth, colour type), uint8 [h, w*bpp])."""
     if data[:8] != b"\x89PNG\r\n\x1a\n":
         raise ValueError("%s: not a PNG / PGM / npy file" % path)
     pos, idat, hdr = 8, [], None
@@ -125,34 +137,121 @@ def _read_gray_image_py(path):
     if hdr is None:
         raise ValueError("%s: no IHDR" % path)
     w, h, depth, ctype, _, _, interlace = hdr
-    if depth != 8 or ctype != 0 or interlace != 0:
-        raise ValueError("%s: only non-interlaced 8-bit grayscale PNG is supported (depth %d, colour type %d)"
-                         % (path, depth, ctype))
-    raw = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8).reshape(h, w + 1)
-    out = np.zeros((h, w), np.uint8)
-    prev = np.zeros(w, np.uint8)
+    samples = {0: 1, 2: 3, 4: 2, 6: 4}.get(ctype)
+    if interlace != 0 or depth not in (8, 16) or samples is None:
+        raise ValueError("%s: only non-interlaced PNG with 8- or 16-bit samples is supported (depth %d, colour type %d, "
+                         "interlace %d)" % (path, depth, ctype, interlace))
+    bpp = samples * depth // 8                       # the filters' "pixel to the left" is bpp bytes back
+    nb = w * bpp
+    raw = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8).reshape(h, nb + 1)
+    out = np.zeros((h, nb), np.uint8)
+    prev = np.zeros(nb, np.uint8)
     for y in range(h):
         ft, line = int(raw[y, 0]), raw[y, 1:]
         if ft == 0:
             cur = line.copy()
         elif ft == 2:
             cur = line + prev                        # uint8 wrap-around is the PNG arithmetic
-        elif ft == 1:
-            cur = np.cumsum(line, dtype=np.uint64).astype(np.uint8)
+        elif ft == 1:                                # Sub: a running sum per byte lane of the pixel
+            cur = np.zeros(nb, np.uint8)
+            for k in range(bpp):
+                cur[k::bpp] = np.cumsum(line[k::bpp], dtype=np.uint64).astype(np.uint8)
         else:                                        # Average / Paeth depend on the pixel to the left: serial in x
-            cur = np.zeros(w, np.uint8)
-            left = 0
+            cur = np.zeros(nb, np.uint8)
             up = prev.astype(np.int32)
-            for x in range(w):
+            ln = line.astype(np.int32)
+            for x in range(nb):
+                left = int(cur[x - bpp]) if x >= bpp else 0
                 if ft == 3:
                     pred = (left + int(up[x])) >> 1
                 else:
-                    ul = int(up[x - 1]) if x else 0
+                    ul = int(up[x - bpp]) if x >= bpp else 0
                     p = left + int(up[x]) - ul
                     pa, pb, pc = abs(p - left), abs(p - int(up[x])), abs(p - ul)
                     pred = left if (pa <= pb and pa <= pc) else (int(up[x]) if pb <= pc else ul)
-                left = (int(line[x]) + pred) & 255
-                cur[x] = left
+                cur[x] = (int(ln[x]) + pred) & 255
         out[y] = cur
         prev = cur
-    return out
+    return (w, h, depth, ctype), out
+
+
+def read_color_image(path):
+    """What cv::imread(.., CV_LOAD_IMAGE_UNCHANGED) hands Examples/RGB-D/rgbd_tum.cc:76 and mono_tum.cc:69 for an 8-bit
+    image: uint8 [rows, cols, 3|4] in imread's channel order, B first (BGR / BGRA; a PNG stores R first, so bytes 0 and
+    2 of every pixel are swapped on the way), for PNG colour types 2 / 6; uint8 [rows, cols] for a grey file.  What the
+    bytes mean is then the settings file's business, as in the reference: Camera.RGB (camera_rgb) says whether
+    Tracking reads byte 0 as R.  .npy arrays of those shapes are returned as they are (the writer chose the order)."""
+    if path.endswith(".npy"):
+        a = np.load(path)
+        if a.dtype != np.uint8 or not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] in (3, 4))):
+            raise ValueError("%s: expected a uint8 [rows, cols] or [rows, cols, 3|4] array" % path)
+        return np.ascontiguousarray(a)
+    data = open(path, "rb").read()
+    if data[:2] == b"P5":
+        return _read_gray_image_py(path)
+    (w, h, depth, ctype), rows = _png_rows(path, data)
+    if depth != 8 or ctype not in (0, 2, 6):
+        raise ValueError("%s: expected an 8-bit grey, RGB or RGBA PNG (depth %d, colour type %d)" % (path, depth, ctype))
+    if ctype == 0:
+        return rows
+    img = rows.reshape(h, w, 3 if ctype == 2 else 4)
+    img[..., [0, 2]] = img[..., [2, 0]]              # R G B [A] in the file -> B G R [A], as imread delivers it
+    return img
+
+
+def read_depth_image(path):
+    """The depth image of rgbd_tum.cc:77 as stored: uint16 [rows, cols] from a 16-bit grey PNG (big-endian samples) or a
+    uint16 / float32 .npy.  Scaling is left to ComputeStereoFromRGBDRaw (src/Tracking.cc:227-228)."""
+    if path.endswith(".npy"):
+        a = np.load(path)
+        if a.ndim != 2 or a.dtype not in (np.uint16, np.float32):
+            raise ValueError("%s: expected a 2-D uint16 or float32 array" % path)
+        return np.ascontiguousarray(a)
+    (w, h, depth, ctype), rows = _png_rows(path, open(path, "rb").read())
+    if depth != 16 or ctype != 0:
+        raise ValueError("%s: expected a 16-bit grey PNG (depth %d, colour type %d)" % (path, depth, ctype))
+    return rows.view(">u2").astype(np.uint16)
+
+
+def camera_rgb(settings):
+    """mbRGB (src/Tracking.cc:103-104): Camera.RGB != 0, absent = 0 (BGR)."""
+    return bool(int(settings.get("Camera.RGB", 0)))
+
+
+def depth_map_factor(settings):
+    """mDepthMapFactor as the Tracking constructor leaves it (src/Tracking.cc:140-147), a float32: 1 / DepthMapFactor, or 1
+    when |DepthMapFactor| < 1e-5.  Only stereo / RGB-D sensors read the key; absent = 1."""
+    if "DepthMapFactor" not in settings:
+        return np.float32(1.0)
+    f = np.float32(settings["DepthMapFactor"])
+    if abs(float(f)) < 1e-5:
+        return np.float32(1.0)
+    return np.float32(1.0) / f
+
+
+def load_tum_association(path):
+    """LoadImages of Examples/RGB-D/rgbd_tum.cc:142-167: lines `t rgb_file t depth_file`, empty lines skipped.
+    Returns (rgb filenames, depth filenames, timestamps)."""
+    rgb, dep, stamps = [], [], []
+    with open(path) as f:
+        for s in f:
+            s = s.rstrip("\n")
+            if not s:
+                continue
+            p = s.split()
+            stamps.append(float(p[0])); rgb.append(p[1]); dep.append(p[3])
+    return rgb, dep, stamps
+
+
+def load_tum_rgb_list(path):
+    """LoadImages of Examples/Monocular/mono_tum.cc:127-160: three header lines skipped, then `t file`.
+    Returns (filenames, timestamps)."""
+    names, stamps = [], []
+    with open(path) as f:
+        lines = f.read().split("\n")[3:]
+    for s in lines:
+        if not s:
+            continue
+        p = s.split()
+        stamps.append(float(p[0])); names.append(p[1])
+    return names, stamps

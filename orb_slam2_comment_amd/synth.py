@@ -98,6 +98,37 @@ def synth_batch(first_seed, count, W=1241, H=376):
     return np.stack([synth_frame(first_seed + i, W, H) for i in range(count)])
 
 
+def synth_color_frame(seed, W=1241, H=376, channels=3, rgb=True):
+    """uint8 [H, W, channels] colour frame: three differently seeded renders of one scene as R, G, B (so the channels
+    differ), stored R first when `rgb` else B first; with channels == 4 the alpha plane is uniform noise, so that a
+    conversion which reads it shows."""
+    assert channels in (3, 4)
+    grid, shapes = _scene(seed, W, H, 400, 200)
+    planes = []
+    for c in range(3):
+        rng = np.random.default_rng((seed << 8) + 64 + c)
+        tint = [(k, a, b, cc, d, int(rng.integers(0, 256)), disp) for k, a, b, cc, d, _, disp in shapes]
+        planes.append(_render(grid + rng.uniform(-30, 30, grid.shape), tint, W, H, False, (seed << 8) + 80 + c))
+    if not rgb:
+        planes.reverse()
+    if channels == 4:
+        planes.append(np.random.default_rng((seed << 8) + 99).integers(0, 256, (H, W), dtype=np.uint8))
+    return np.ascontiguousarray(np.stack(planes, axis=2))
+
+
+def synth_depth(seed, W=640, H=480):
+    """uint16 [H, W] raw depth image in the manner of a TUM RGB-D frame (5000 units per metre): smooth ramps between
+    0.5 m and 8 m, about 10 % zero holes (no reading) in blocks, and a few saturated 65535 pixels."""
+    rng = np.random.default_rng((seed << 8) + 7)
+    grid = rng.uniform(2500, 40000, size=(5, 7))
+    d = np.rint(_background(grid, W, H)).astype(np.uint16)
+    holes = rng.uniform(size=((H + 7) // 8, (W + 7) // 8)) < 0.10
+    d[np.kron(holes, np.ones((8, 8), bool))[:H, :W]] = 0
+    ys, xs = rng.integers(0, H, 24), rng.integers(0, W, 24)
+    d[ys, xs] = 65535
+    return d
+
+
 def synth_vocabulary(k=10, L=6, seed=1):
     """Regular k-ary vocabulary tree with the shape of ORBvoc.txt (k=10, L=6: 1.1 M nodes, 10^6 words) in
     saveToTextFile (BFS) order, for benchmarks: the real vocabulary is not part of the reference checkout.
