@@ -12,6 +12,8 @@
  *   orbhip_extract            replaces ORBextractor::operator()  (include/ORBextractor.h:59-61)
  *   orbhip_extract_color*     the cvtColor(.., CV_{RGB,BGR,RGBA,BGRA}2GRAY) of Tracking::GrabImage{Monocular,Stereo,RGBD}
  *                             (src/Tracking.cc:172-197, 212-225, 242-256) followed by ORBextractor::operator()
+ *   orbhip_init_undistort_rectify_map / orbhip_extract_remap*   the cv::initUndistortRectifyMap and cv::remap of the
+ *                             stereo example (Examples/Stereo/stereo_euroc.cc:63-98, 136-137) followed by operator()
  *   orbhip_pyramid_level*     replaces the public member mvImagePyramid (include/ORBextractor.h:85)
  *   orbhip_matcher_*          replaces class ORBmatcher (include/ORBmatcher.h:37-103)
  *   orbhip_descriptor_distance  ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:1647-1663)
@@ -171,6 +173,54 @@ int orbhip_extract_color_batch(orbhip_extractor *e, const uint8_t *images, int b
 int orbhip_extract_color_batch_device(orbhip_extractor *e, const void *d_images, int batch, int rows, int cols,
                                       int channels, int rgb, int stride, size_t frame_stride, void *d_kps, void *d_desc,
                                       int cap, void *d_n, void *d_status);
+
+/* ---- stereo rectification ----
+ * Examples/Stereo/stereo_euroc.cc:63-98 builds two map pairs with cv::initUndistortRectifyMap(K, D, R, P(0:3,0:3), size,
+ * CV_32F, M1, M2) and sends every left and right frame through cv::remap(im, imRect, M1, M2, cv::INTER_LINEAR) (:136-137)
+ * before TrackStereo.  Both are restated here from the published OpenCV 2.4 - 3.3 algorithms; parity with a given OpenCV
+ * build is unpinned.
+ *
+ * orbhip_init_undistort_rectify_map: host code, needs no device.  K, R, P3x3: row-major 3x3 doubles (P3x3 = the left 3x3 of
+ * the 3x4 projection matrix; R may be NULL = identity); D: nD = 4, 5 or 8 coefficients k1 k2 p1 p2 [k3 [k4 k5 k6]];
+ * map1 / map2: rows x cols floats (x and y source coordinate of every destination pixel).  fp64 throughout,
+ * iR = (P3x3 * R)^-1 by the adjugate, the homogeneous coordinates advance along a row by repeated addition, one rounding
+ * to float at the end. */
+int orbhip_init_undistort_rectify_map(const double K[9], const double *D, int nD, const double *R, const double P3x3[9],
+                                      int cols, int rows, float *map1, float *map2);
+
+/* Install (map1, map2: dst_rows x dst_cols floats, as above) or remove (both NULL) the remap of a handle.  The maps are
+ * turned into what cv::remap computes from them for INTER_LINEAR on 8-bit data: sx = cvRound(map1 * 32), sy =
+ * cvRound(map2 * 32) (round half to even, saturated to int; NaN counts as outside the source), integer tap (sx >> 5,
+ * sy >> 5), weight row (sy & 31) * 32 + (sx & 31); the per-pixel records live on the device, belong to the handle and
+ * serve every frame of every later batch.  1 <= src_rows, src_cols <= 32767, src_rows * src_cols < 2^31. */
+int orbhip_extractor_set_remap(orbhip_extractor *e, int dst_rows, int dst_cols, int src_rows, int src_cols, const float *map1,
+                               const float *map2);
+/* The 1024 x 4 weight table is data: row (fy * 32 + fx) holds the weights of the taps (x, y), (x+1, y), (x, y+1),
+ * (x+1, y+1).  Default: (32 - fx | fx) * (32 - fy | fy) * 32, the published fixed-point table of initInterTab2D, every
+ * row summing to 32768 (row 0 is 32768, 0, 0, 0: DESIGN.md section 3).  0 <= w <= 65535; NULL restores the default. */
+#define ORBHIP_REMAP_TABLE_SIZE 4096
+int orbhip_extractor_set_remap_table(orbhip_extractor *e, const int32_t *w);
+
+/* image: rows x cols uint8 grey source pixels (the RAW camera frame; rows, cols must equal the src_rows, src_cols of the
+ * installed map), row stride `stride` bytes >= cols.  The device computes, for every pixel of the dst_rows x dst_cols
+ * rectified image,
+ *     min(255, (sum of 4 taps * weights + (1 << 14)) >> 15),    a tap outside the source = 0 (BORDER_CONSTANT, value 0)
+ * into grey frames the handle owns and runs the unchanged pipeline on them; cap, outputs and the capacity rule are those
+ * of orbhip_extract* at dst_rows x dst_cols.
+ * Grey input only: channels must be 1.  A colour frame (channels 3 or 4) is ORBHIP_E_ARG; convert it first.
+ * No map installed, a size other than the map's source size, a short stride or a null pointer: ORBHIP_E_ARG before any
+ * device work; an empty host image gives zero keypoints.  No more than (rows-1)*stride + cols bytes of a frame are read.
+ * Host entries: one 1-D upload from page-locked staging, eager launches, one chunk (as orbhip_extract_color*).  The remap
+ * belongs to stage 0.  Afterwards the rectified frames are "the image of the last extraction" for every accessor
+ * (orbhip_pyramid_level*, a lazy level 0, orbhip_compute_stereo_matches*), and the caller's buffer may be reused as soon
+ * as the work enqueued by the call has run (stream order is enough). */
+int orbhip_extract_remap(orbhip_extractor *e, const uint8_t *image, int rows, int cols, int channels, int stride,
+                         orbhip_keypoint *kps, uint8_t *desc, int cap, int *n);
+int orbhip_extract_remap_batch(orbhip_extractor *e, const uint8_t *images, int batch, int rows, int cols, int channels,
+                               int stride, size_t frame_stride, orbhip_keypoint *kps, uint8_t *desc, int cap, int32_t *n);
+int orbhip_extract_remap_batch_device(orbhip_extractor *e, const void *d_images, int batch, int rows, int cols, int channels,
+                                      int stride, size_t frame_stride, void *d_kps, void *d_desc, int cap, void *d_n,
+                                      void *d_status);
 
 int orbhip_extractor_sync(orbhip_extractor *e);
 void *orbhip_extractor_stream(orbhip_extractor *e); /* hipStream_t */

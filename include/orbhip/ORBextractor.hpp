@@ -131,6 +131,70 @@ public:
     // the grey weights are data (default: OpenCV 2.4 - 3.3's 4899, 9617, 1868 >> 14)
     void SetGrayWeights(const int32_t wRGB[3], int shift) { check(orbhip_extractor_set_gray_weights(h_, wRGB, shift), "orbhip_extractor_set_gray_weights"); }
 
+    // Stereo rectification (Examples/Stereo/stereo_euroc.cc:96-98, 136-137).  SetRemap installs M1, M2 (CV_32F, dstRows x
+    // dstCols) for raw frames of srcRows x srcCols; ExtractRemap is cv::remap(im, imRect, M1, M2, cv::INTER_LINEAR) followed
+    // by operator() in one call, the remap running on the device in front of the pyramid.  Grey frames only.
+    void SetRemap(int dstRows, int dstCols, int srcRows, int srcCols, const float *map1, const float *map2)
+    {
+        check(orbhip_extractor_set_remap(h_, dstRows, dstCols, srcRows, srcCols, map1, map2), "orbhip_extractor_set_remap");
+        remapRows_ = map1 ? dstRows : 0;
+        remapCols_ = map1 ? dstCols : 0;
+    }
+    void ClearRemap() { SetRemap(0, 0, 0, 0, nullptr, nullptr); }
+    // the 1024 x 4 bilinear weights are data (NULL: the default table)
+    void SetRemapTable(const int32_t *w) { check(orbhip_extractor_set_remap_table(h_, w), "orbhip_extractor_set_remap_table"); }
+    void ExtractRemap(const ImageView &image, std::vector<KeyPoint> &keypoints, std::vector<uint8_t> &descriptors)
+    {
+        keypoints.clear();
+        descriptors.clear();
+        if (image.empty()) return;
+        int cap = 0;
+        check(orbhip_extractor_capacity(h_, remapRows_ ? remapRows_ : image.rows, remapCols_ ? remapCols_ : image.cols, &cap),
+              "orbhip_extractor_capacity");
+        keypoints.resize(cap);
+        descriptors.resize((size_t)cap * 32);
+        int n = 0;
+        check(orbhip_extract_remap(h_, image.data, image.rows, image.cols, 1, (int)image.step, keypoints.data(), descriptors.data(),
+                                   cap, &n), "orbhip_extract_remap");
+        keypoints.resize(n);
+        descriptors.resize((size_t)n * 32);
+    }
+    void ExtractRemapBatch(const uint8_t *images, int batch, int rows, int cols, size_t step, size_t frame_stride,
+                           std::vector<std::vector<KeyPoint> > &keypoints, std::vector<std::vector<uint8_t> > &descriptors)
+    {
+        keypoints.assign(batch, std::vector<KeyPoint>());
+        descriptors.assign(batch, std::vector<uint8_t>());
+        if (!images || batch <= 0 || rows <= 0 || cols <= 0) return;
+        int cap = 0;
+        check(orbhip_extractor_capacity(h_, remapRows_ ? remapRows_ : rows, remapCols_ ? remapCols_ : cols, &cap),
+              "orbhip_extractor_capacity");
+        std::vector<KeyPoint> k((size_t)batch * cap);
+        std::vector<uint8_t> d((size_t)batch * cap * 32);
+        std::vector<int32_t> n(batch, 0);
+        check(orbhip_extract_remap_batch(h_, images, batch, rows, cols, 1, (int)step, frame_stride, k.data(), d.data(), cap, n.data()),
+              "orbhip_extract_remap_batch");
+        for (int b = 0; b < batch; ++b) {
+            keypoints[b].assign(k.begin() + (size_t)b * cap, k.begin() + (size_t)b * cap + n[b]);
+            descriptors[b].assign(d.begin() + (size_t)b * cap * 32, d.begin() + ((size_t)b * cap + n[b]) * 32);
+        }
+    }
+    // device frames: orbhip_extract_remap_batch_device with the mirror's handle
+    void ExtractRemapBatchDevice(const void *dImages, int batch, int rows, int cols, size_t step, size_t frame_stride, void *dKps,
+                                 void *dDesc, int cap, void *dN, void *dStatus)
+    {
+        check(orbhip_extract_remap_batch_device(h_, dImages, batch, rows, cols, 1, (int)step, frame_stride, dKps, dDesc, cap, dN,
+                                                dStatus), "orbhip_extract_remap_batch_device");
+    }
+    // cv::initUndistortRectifyMap(K, D, R, P.rowRange(0,3).colRange(0,3), Size(cols, rows), CV_32F, M1, M2); host code
+    static void InitUndistortRectifyMap(const double K[9], const std::vector<double> &D, const double *R, const double P3x3[9], int cols,
+                                        int rows, std::vector<float> &map1, std::vector<float> &map2)
+    {
+        map1.assign((size_t)(rows > 0 ? rows : 0) * (cols > 0 ? cols : 0), 0.f);
+        map2 = map1;
+        check(orbhip_init_undistort_rectify_map(K, D.data(), (int)D.size(), R, P3x3, cols, rows, map1.data(), map2.data()),
+              "orbhip_init_undistort_rectify_map");
+    }
+
     // mvImagePyramid[0] on demand: a monocular Tracking thread never reads it (only Frame::ComputeStereoMatches does)
     void SetLazyLevel0(bool on) { check(orbhip_extractor_set_lazy_level0(h_, on ? 1 : 0), "orbhip_extractor_set_lazy_level0"); }
 
@@ -171,6 +235,7 @@ private:
     }
     orbhip_extractor *h_;
     int nlevels_;
+    int remapRows_ = 0, remapCols_ = 0;   // destination size of the installed remap (0: none)
 };
 
 class ORBmatcher {

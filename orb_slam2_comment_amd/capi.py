@@ -43,6 +43,7 @@ class Camera(C.Structure):
 POINT_PRESENT, POINT_OBSERVED = 1, 2
 COLOR_BGR, COLOR_RGB = 0, 1
 DEPTH_U16, DEPTH_F32 = 0, 1
+REMAP_TABLE_SIZE = 4096
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
@@ -65,6 +66,12 @@ SYMBOLS = [
     ("orbhip_extract_color", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _pi]),
     ("orbhip_extract_color_batch", _i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _sz, _vp, _vp, _i, _vp]),
     ("orbhip_extract_color_batch_device", _i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _sz, _vp, _vp, _i, _vp, _vp]),
+    ("orbhip_init_undistort_rectify_map", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    ("orbhip_extractor_set_remap", _i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    ("orbhip_extractor_set_remap_table", _i, [_vp, _vp]),
+    ("orbhip_extract_remap", _i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _pi]),
+    ("orbhip_extract_remap_batch", _i, [_vp, _vp, _i, _i, _i, _i, _i, _sz, _vp, _vp, _i, _vp]),
+    ("orbhip_extract_remap_batch_device", _i, [_vp, _vp, _i, _i, _i, _i, _i, _sz, _vp, _vp, _i, _vp, _vp]),
     ("orbhip_extractor_sync", _i, [_vp]),
     ("orbhip_extractor_stream", _vp, [_vp]),
     ("orbhip_extractor_set_stream", _i, [_vp, _vp]),

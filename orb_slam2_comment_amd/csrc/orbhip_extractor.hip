@@ -495,6 +495,92 @@ __global__ __launch_bounds__(256) void k_cvt_gray(const uint8_t *__restrict__ co
     }
 }
 
+// ---------------------------------------------------------------------------
+// Stereo rectification in front of the pyramid: the cv::remap(im, imRect, M1, M2, INTER_LINEAR) of
+// Examples/Stereo/stereo_euroc.cc:136-137 on 8-bit grey frames, BORDER_CONSTANT with value 0.
+//     dst = min(255, (t00*w0 + t01*w1 + t10*w2 + t11*w3 + (1 << 14)) >> 15)
+// The map is frame-invariant: the host turns it into one 8-byte record per destination pixel (integer tap, weight row,
+// border flags; orbhip_extractor_set_remap).  A lane owns one destination dword (4 pixels) and keeps its four records,
+// decoded into source offsets, and its four weight rows in registers while it loops over the frames of its group:
+// grid.y = min(batch, 8) frame groups, and with xcd_remap group g runs on the XCD that reads frames
+// [g*B/8, (g+1)*B/8) next, so an XCD fetches the records once per batch, not once per frame.  Weights are 16 bits, taps 8:
+// two v_dot2_u32_u16 with the rounding term as accumulator, 4*255*65535 + 2^14 < 2^32.
+// A wavefront covers 64 x 4 destination pixels, a workgroup 64 x 16.  Fast path (every tap of the wavefront inside the
+// source): two byte-unaligned 2-byte loads per pixel, all eight issued before the arithmetic, no bounds logic.  Slow path,
+// chosen per wavefront from the records: every tap is checked against the source rectangle and reads 0 outside; the
+// padding pixels of a row's last dword carry the "outside" flag and store 0.  No LDS.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kRemapBorder = 1u << 16, kRemapOutside = 2u << 16;   // flags in .y of a record, above the weight row
+constexpr int kRemapGroups = 8;
+
+__device__ __forceinline__ uint32_t remap_pair(const uint8_t *p)
+{
+    uint16_t v;
+    __builtin_memcpy(&v, p, 2);
+    return ((uint32_t)v & 0xffu) | (((uint32_t)v & 0xff00u) << 8);   // two adjacent pixels as 16-bit halves
+}
+__device__ __forceinline__ uint32_t remap_px(uint32_t top, uint32_t bot, uint2 w)
+{
+    return min(udot2(bot, w.y, udot2(top, w.x, 1u << 14)) >> 15, 255u);
+}
+
+__global__ __launch_bounds__(256) void k_remap(const uint8_t *__restrict__ src, int sstride, size_t sframe_stride, int srows,
+                                               int scols, uint8_t *__restrict__ gray, int pitch, size_t gframe_bytes, int rows,
+                                               int words, int tiles_x, const uint4 *__restrict__ rec,
+                                               const uint2 *__restrict__ tab, int batch)
+{
+    int tile, grp;
+    xcd_remap(tile, grp);
+    const int f0 = (int)((long long)grp * batch / (int)gridDim.y), f1 = (int)((long long)(grp + 1) * batch / (int)gridDim.y);
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int dw = tx * 16 + (lane & 15), row = ty * 16 + wave * 4 + (lane >> 4);
+    if (dw >= words || row >= rows) return;
+    const uint4 *r = rec + ((size_t)row * words + dw) * 2;
+    const uint4 r01 = r[0], r23 = r[1];
+    const uint32_t tap[4] = {r01.x, r01.z, r23.x, r23.z}, wr[4] = {r01.y, r01.w, r23.y, r23.w};
+    int off[4];
+    uint2 w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        off[k] = ((int)(tap[k] >> 16) - 1) * sstride + ((int)(tap[k] & 0xffffu) - 1);
+        w[k] = tab[wr[k] & 1023u];
+    }
+    const bool slow = __ballot(((wr[0] | wr[1] | wr[2] | wr[3]) >> 16) != 0) != 0ull;
+    uint8_t *dst = gray + (size_t)((uint32_t)row * (uint32_t)pitch) + (size_t)dw * 4;
+    if (!slow) {
+        for (int f = f0; f < f1; ++f) {
+            const uint8_t *s = src + (size_t)f * sframe_stride;
+            uint32_t t[4], b[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                t[k] = remap_pair(s + off[k]);
+                b[k] = remap_pair(s + off[k] + sstride);
+            }
+            uint32_t o = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o |= remap_px(t[k], b[k], w[k]) << (8 * k);
+            *reinterpret_cast<uint32_t *>(dst + (size_t)f * gframe_bytes) = o;
+        }
+        return;
+    }
+    for (int f = f0; f < f1; ++f) {
+        const uint8_t *s = src + (size_t)f * sframe_stride;
+        uint32_t o = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (wr[k] & kRemapOutside) continue;
+            const int x0 = (int)(tap[k] & 0xffffu) - 1, y0 = (int)(tap[k] >> 16) - 1;
+            const bool xa = x0 >= 0, xb = x0 + 1 < scols, ya = y0 >= 0, yb = y0 + 1 < srows;
+            const uint8_t *p = s + off[k];
+            const uint32_t t00 = ya && xa ? p[0] : 0u, t01 = ya && xb ? p[1] : 0u;
+            const uint32_t t10 = yb && xa ? p[sstride] : 0u, t11 = yb && xb ? p[sstride + 1] : 0u;
+            o |= remap_px(t00 | (t01 << 16), t10 | (t11 << 16), w[k]) << (8 * k);
+        }
+        *reinterpret_cast<uint32_t *>(dst + (size_t)f * gframe_bytes) = o;
+    }
+}
+
 constexpr int kSubMax = 72;              // max (wCell+6), (hCell+6)
 constexpr int kFastStageU = 12;         // k_fast_cells: row groups per staging batch (48 rows of a stride <= 16 dwords)
 constexpr int kFastLdsPerCu = 160 * 1024;  // gfx950
@@ -2081,11 +2167,15 @@ int orbhip::ensure_level0(orbhip_extractor *e, hipStream_t consumer)
 //
 // `color`: the frames arrive as packed colour; stage 0 starts by converting them into d_images (= the handle's grey
 // buffer), behind the stage's gate and inside its profiling interval
+//
+// `rmp`: the frames arrive unrectified; stage 0 starts by remapping them into d_images (the same grey buffer)
 struct ColorSrc { const uint8_t *d_color; int channels, rgb, stride; size_t frame_stride; };
+struct RemapSrc { const uint8_t *d_src; int stride; size_t frame_stride; };
 static int gray_pitch(int cols) { return (cols + 63) & ~63; }
 static int launch_pipeline(orbhip_extractor *e, const uint8_t *d_images, int batch, int stride,
                            size_t frame_stride, orbhip_keypoint *d_kps, uint8_t *d_desc, int cap,
-                           int *d_n, int *d_status, int frame0 = 0, const ColorSrc *color = nullptr)
+                           int *d_n, int *d_status, int frame0 = 0, const ColorSrc *color = nullptr,
+                           const RemapSrc *rmp = nullptr)
 {
     const PyrGeom &G = e->G;
     hipStream_t s = e->stream;
@@ -2122,6 +2212,13 @@ static int launch_pipeline(orbhip_extractor *e, const uint8_t *d_images, int bat
         else
             hipLaunchKernelGGL(k_cvt_gray<3>, grid, dim3(256), 0, s, color->d_color, color->stride, color->frame_stride, gray, stride,
                                frame_stride, G.rows, G.cols, words, W);
+    }
+    if (rmp) {
+        const int words = (G.cols + 3) >> 2, tiles_x = (words + 15) >> 4, tiles_y = (G.rows + 15) >> 4;
+        hipLaunchKernelGGL(k_remap, dim3(tiles_x * tiles_y, std::min(batch, kRemapGroups)), dim3(256), 0, s, rmp->d_src, rmp->stride,
+                           rmp->frame_stride, e->rmap_srows, e->rmap_scols, const_cast<uint8_t *>(d_images), stride, frame_stride,
+                           G.rows, words, tiles_x, reinterpret_cast<const uint4 *>(e->d_rmap),
+                           reinterpret_cast<const uint2 *>(e->d_rtab), batch);
     }
     if (sm & 1) {
         // level 0 and, when its taps allow, level 1 in one launch
@@ -2240,6 +2337,49 @@ static int ensure_gray(orbhip_extractor *e, int batch)
     (void)hipFree(e->d_gray); e->d_gray = nullptr; e->gray_cap = 0;
     ORBHIP_HIP_CHECK(hipMalloc(&e->d_gray, (size_t)batch * e->G.rows * gray_pitch(e->G.cols) + 256));
     e->gray_cap = batch;
+    return ORBHIP_OK;
+}
+
+// Input side of the host colour / remap entries: the packed frames on the device and their page-locked staging
+static int ensure_color_staging(orbhip_extractor *e, size_t img_bytes)
+{
+    if (img_bytes > e->d_cimg_bytes) {
+        ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
+        (void)hipFree(e->d_cimg); e->d_cimg = nullptr; e->d_cimg_bytes = 0;
+        ORBHIP_HIP_CHECK(hipMalloc(&e->d_cimg, img_bytes));
+        e->d_cimg_bytes = img_bytes;
+    }
+    if (img_bytes > e->h_cin_bytes) {
+        ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
+        if (e->h_cin) (void)hipHostFree(e->h_cin);
+        e->h_cin = nullptr; e->h_cin_bytes = 0;
+        ORBHIP_HIP_CHECK(hipHostMalloc((void **)&e->h_cin, img_bytes, hipHostMallocDefault));
+        e->h_cin_bytes = img_bytes;
+    }
+    return ORBHIP_OK;
+}
+
+// Output side of the same entries: one copy per result array back on the handle's stream, then the per-frame split
+static int download_results(orbhip_extractor *e, int batch, int cap, orbhip_keypoint *kps, uint8_t *desc, int32_t *n)
+{
+    int *h_n = reinterpret_cast<int *>(e->h_out), *h_st = h_n + batch;
+    orbhip_keypoint *h_kp = reinterpret_cast<orbhip_keypoint *>(h_st + batch);
+    uint8_t *h_desc = reinterpret_cast<uint8_t *>(h_kp + (size_t)batch * cap);
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_n, e->d_on, batch * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_st, e->d_status, batch * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_kp, e->d_okp, (size_t)batch * cap * sizeof(orbhip_keypoint), hipMemcpyDeviceToHost, e->stream));
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_desc, e->d_odesc, (size_t)batch * cap * 32, hipMemcpyDeviceToHost, e->stream));
+    ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
+    int bad = -1;   // as orbhip_extract_batch: truncated frames are delivered before the capacity error is reported
+    for (int b = 0; b < batch; ++b) {
+        n[b] = std::min(h_n[b], cap);
+        if (h_st[b] != 0 && bad < 0) bad = b;
+        if (n[b] > 0) {
+            memcpy(kps + (size_t)b * cap, h_kp + (size_t)b * cap, (size_t)n[b] * sizeof(orbhip_keypoint));
+            memcpy(desc + (size_t)b * cap * 32, h_desc + (size_t)b * cap * 32, (size_t)n[b] * 32);
+        }
+    }
+    if (bad >= 0) { set_error("frame %d: capacity exceeded (cap %d); outputs are truncated", bad, cap); return ORBHIP_E_CAPACITY; }
     return ORBHIP_OK;
 }
 
@@ -2383,6 +2523,7 @@ void orbhip_extractor_destroy(orbhip_extractor *e)
     free_batch(e);
     (void)hipFree(e->d_patternf); (void)hipFree(e->d_desc_tab); (void)hipFree(e->d_img); (void)hipFree(e->d_okp); (void)hipFree(e->d_odesc); (void)hipFree(e->d_on);
     (void)hipFree(e->d_cimg);
+    (void)hipFree(e->d_rmap); (void)hipFree(e->d_rtab);
     if (e->h_cin) (void)hipHostFree(e->h_cin);
     if (e->h_in) (void)hipHostFree(e->h_in);
     if (e->h_out) (void)hipHostFree(e->h_out);
@@ -2697,19 +2838,7 @@ int orbhip_extract_color_batch(orbhip_extractor *e, const uint8_t *images, int b
     int rc = bind_geometry(e, rows, cols);
     if (rc) return rc;
     const size_t rbytes = (size_t)cols * channels, fbytes = (size_t)rows * rbytes, img_bytes = (size_t)batch * fbytes;
-    if (img_bytes > e->d_cimg_bytes) {
-        ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
-        (void)hipFree(e->d_cimg); e->d_cimg = nullptr; e->d_cimg_bytes = 0;
-        ORBHIP_HIP_CHECK(hipMalloc(&e->d_cimg, img_bytes));
-        e->d_cimg_bytes = img_bytes;
-    }
-    if (img_bytes > e->h_cin_bytes) {
-        ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
-        if (e->h_cin) (void)hipHostFree(e->h_cin);
-        e->h_cin = nullptr; e->h_cin_bytes = 0;
-        ORBHIP_HIP_CHECK(hipHostMalloc((void **)&e->h_cin, img_bytes, hipHostMallocDefault));
-        e->h_cin_bytes = img_bytes;
-    }
+    if ((rc = ensure_color_staging(e, img_bytes))) return rc;
     if ((rc = ensure_out_staging(e, batch, cap))) return rc;
     ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));   // the staging buffers of the previous call are free
     for (int b = 0; b < batch; ++b) {
@@ -2721,25 +2850,7 @@ int orbhip_extract_color_batch(orbhip_extractor *e, const uint8_t *images, int b
     ORBHIP_HIP_CHECK(hipMemcpyAsync(e->d_cimg, e->h_cin, img_bytes, hipMemcpyHostToDevice, e->stream));
     if ((rc = orbhip_extract_color_batch_device(e, e->d_cimg, batch, rows, cols, channels, rgb, (int)rbytes, fbytes, e->d_okp,
                                                 e->d_odesc, cap, e->d_on, nullptr))) return rc;
-    int *h_n = reinterpret_cast<int *>(e->h_out), *h_st = h_n + batch;
-    orbhip_keypoint *h_kp = reinterpret_cast<orbhip_keypoint *>(h_st + batch);
-    uint8_t *h_desc = reinterpret_cast<uint8_t *>(h_kp + (size_t)batch * cap);
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_n, e->d_on, batch * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_st, e->d_status, batch * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_kp, e->d_okp, (size_t)batch * cap * sizeof(orbhip_keypoint), hipMemcpyDeviceToHost, e->stream));
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(h_desc, e->d_odesc, (size_t)batch * cap * 32, hipMemcpyDeviceToHost, e->stream));
-    ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
-    int bad = -1;   // as orbhip_extract_batch: truncated frames are delivered before the capacity error is reported
-    for (int b = 0; b < batch; ++b) {
-        n[b] = std::min(h_n[b], cap);
-        if (h_st[b] != 0 && bad < 0) bad = b;
-        if (n[b] > 0) {
-            memcpy(kps + (size_t)b * cap, h_kp + (size_t)b * cap, (size_t)n[b] * sizeof(orbhip_keypoint));
-            memcpy(desc + (size_t)b * cap * 32, h_desc + (size_t)b * cap * 32, (size_t)n[b] * 32);
-        }
-    }
-    if (bad >= 0) { set_error("frame %d: capacity exceeded (cap %d); outputs are truncated", bad, cap); return ORBHIP_E_CAPACITY; }
-    return ORBHIP_OK;
+    return download_results(e, batch, cap, kps, desc, n);
 }
 
 int orbhip_extract_color(orbhip_extractor *e, const uint8_t *image, int rows, int cols, int channels, int rgb, int stride,
@@ -2748,6 +2859,198 @@ int orbhip_extract_color(orbhip_extractor *e, const uint8_t *image, int rows, in
     if (!n) return ORBHIP_E_ARG;
     int32_t nn = 0;
     int rc = orbhip_extract_color_batch(e, image, 1, rows, cols, channels, rgb, stride, 0, kps, desc, cap, &nn);
+    *n = nn;
+    return rc;
+}
+
+// ---- stereo rectification ---------------------------------------------------------------------------------------
+// cv::initUndistortRectifyMap(K, D, R, P, size, CV_32F, map1, map2), restated from the published OpenCV 2.4 - 3.3
+// algorithm.  Stated choices: A = P * R with each element summed left to right over k = 0, 1, 2;
+// iR = adj(A) * (1 / det A), det expanded along the first row.
+int orbhip_init_undistort_rectify_map(const double K[9], const double *D, int nD, const double *R, const double P3x3[9],
+                                      int cols, int rows, float *map1, float *map2)
+{
+    if (!K || !D || !P3x3 || !map1 || !map2 || (nD != 4 && nD != 5 && nD != 8) || cols <= 0 || rows <= 0) {
+        set_error("orbhip_init_undistort_rectify_map: bad argument");
+        return ORBHIP_E_ARG;
+    }
+    static const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    const double *Rm = R ? R : I3;
+    double A[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) A[i * 3 + j] = P3x3[i * 3] * Rm[j] + P3x3[i * 3 + 1] * Rm[3 + j] + P3x3[i * 3 + 2] * Rm[6 + j];
+    const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[3] * A[8] - A[5] * A[6], c02 = A[3] * A[7] - A[4] * A[6];
+    const double det = A[0] * c00 - A[1] * c01 + A[2] * c02;
+    if (det == 0.0 || det != det) { set_error("orbhip_init_undistort_rectify_map: P * R is singular"); return ORBHIP_E_ARG; }
+    const double id = 1.0 / det;
+    const double ir[9] = {c00 * id, (A[2] * A[7] - A[1] * A[8]) * id, (A[1] * A[5] - A[2] * A[4]) * id,
+                          (A[5] * A[6] - A[3] * A[8]) * id, (A[0] * A[8] - A[2] * A[6]) * id, (A[2] * A[3] - A[0] * A[5]) * id,
+                          c02 * id, (A[1] * A[6] - A[0] * A[7]) * id, (A[0] * A[4] - A[1] * A[3]) * id};
+    const double fx = K[0], fy = K[4], u0 = K[2], v0 = K[5];
+    const double k1 = D[0], k2 = D[1], p1 = D[2], p2 = D[3], k3 = nD >= 5 ? D[4] : 0.0;
+    const double k4 = nD >= 8 ? D[5] : 0.0, k5 = nD >= 8 ? D[6] : 0.0, k6 = nD >= 8 ? D[7] : 0.0;
+    for (int i = 0; i < rows; ++i) {
+        double _x = i * ir[1] + ir[2], _y = i * ir[4] + ir[5], _w = i * ir[7] + ir[8];
+        float *m1 = map1 + (size_t)i * cols, *m2 = map2 + (size_t)i * cols;
+        for (int j = 0; j < cols; ++j, _x += ir[0], _y += ir[3], _w += ir[6]) {
+            const double w = 1. / _w, x = _x * w, y = _y * w;
+            const double x2 = x * x, y2 = y * y;
+            const double r2 = x2 + y2, _2xy = 2 * x * y;
+            const double kr = (1 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2);
+            const double u = fx * (x * kr + p1 * _2xy + p2 * (r2 + 2 * x2)) + u0;
+            const double v = fy * (y * kr + p1 * (r2 + 2 * y2) + p2 * _2xy) + v0;
+            m1[j] = (float)u;
+            m2[j] = (float)v;
+        }
+    }
+    return ORBHIP_OK;
+}
+
+// cvRound(v * 32) of cv::remap's map conversion: round half to even, saturated to int
+static int remap_fix(float v)
+{
+    const double r = nearbyint((double)v * 32.0);
+    return r <= (double)INT_MIN ? INT_MIN : r >= (double)INT_MAX ? INT_MAX : (int)r;
+}
+
+int orbhip_extractor_set_remap(orbhip_extractor *e, int dst_rows, int dst_cols, int src_rows, int src_cols, const float *map1,
+                               const float *map2)
+{
+    if (!e || (!map1) != (!map2)) { set_error("orbhip_extractor_set_remap: bad argument"); return ORBHIP_E_ARG; }
+    if (map1 && (dst_rows <= 0 || dst_cols <= 0 || dst_cols > INT_MAX / 4 || src_rows <= 0 || src_cols <= 0 || src_rows > 32767 ||
+                 src_cols > 32767 || (long long)dst_rows * ((dst_cols + 3) & ~3) > (long long)INT_MAX / 8)) {
+        set_error("orbhip_extractor_set_remap: bad size");
+        return ORBHIP_E_ARG;
+    }
+    ORBHIP_HIP_CHECK(hipSetDevice(e->device));
+    ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));   // no launch in flight reads the old records
+    (void)hipFree(e->d_rmap); e->d_rmap = nullptr;
+    e->rmap_drows = e->rmap_dcols = e->rmap_srows = e->rmap_scols = 0;
+    if (!map1) return ORBHIP_OK;
+    const int pcols = (dst_cols + 3) & ~3;   // a lane's dword is always four records; the padding ones store 0
+    std::vector<uint2> rec((size_t)dst_rows * pcols, make_uint2(0u, kRemapOutside));
+    for (int i = 0; i < dst_rows; ++i)
+        for (int j = 0; j < dst_cols; ++j) {
+            const float mx = map1[(size_t)i * dst_cols + j], my = map2[(size_t)i * dst_cols + j];
+            if (mx != mx || my != my) continue;   // NaN: outside
+            const int sx = remap_fix(mx), sy = remap_fix(my);
+            const int x0 = sx >> 5, y0 = sy >> 5;
+            if (x0 < -1 || x0 >= src_cols || y0 < -1 || y0 >= src_rows) continue;   // all four taps outside
+            const bool border = x0 < 0 || x0 + 1 >= src_cols || y0 < 0 || y0 + 1 >= src_rows;
+            rec[(size_t)i * pcols + j] = make_uint2(((uint32_t)(y0 + 1) << 16) | (uint32_t)(x0 + 1),
+                                                    (uint32_t)((sy & 31) * 32 + (sx & 31)) | (border ? kRemapBorder : 0u));
+        }
+    ORBHIP_HIP_CHECK(hipMalloc(&e->d_rmap, rec.size() * sizeof(uint2)));
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(e->d_rmap, rec.data(), rec.size() * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+    ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));   // rec dies at return
+    e->rmap_drows = dst_rows; e->rmap_dcols = dst_cols; e->rmap_srows = src_rows; e->rmap_scols = src_cols;
+    return ORBHIP_OK;
+}
+
+int orbhip_extractor_set_remap_table(orbhip_extractor *e, const int32_t *w)
+{
+    if (!e) return ORBHIP_E_ARG;
+    if (w)
+        for (int i = 0; i < ORBHIP_REMAP_TABLE_SIZE; ++i)
+            if (w[i] < 0 || w[i] > 65535) { set_error("orbhip_extractor_set_remap_table: weight %d out of range", i); return ORBHIP_E_ARG; }
+    e->rtab.clear();
+    if (w) e->rtab.assign(w, w + ORBHIP_REMAP_TABLE_SIZE);
+    e->rtab_dirty = true;   // uploaded by the next remap extraction, on the handle's stream
+    return ORBHIP_OK;
+}
+
+// the weight table on the device; default: (32 - fx | fx) * (32 - fy | fy) * 32 (initInterTab2D's fixed-point bilinear table)
+static int ensure_remap_table(orbhip_extractor *e)
+{
+    if (e->d_rtab && !e->rtab_dirty) return ORBHIP_OK;
+    std::vector<uint16_t> t(e->rtab);
+    if (t.empty()) {
+        t.resize(ORBHIP_REMAP_TABLE_SIZE);
+        for (int fy = 0; fy < 32; ++fy)
+            for (int fx = 0; fx < 32; ++fx) {
+                uint16_t *q = &t[(size_t)(fy * 32 + fx) * 4];
+                q[0] = (uint16_t)((32 - fx) * (32 - fy) * 32); q[1] = (uint16_t)(fx * (32 - fy) * 32);
+                q[2] = (uint16_t)((32 - fx) * fy * 32); q[3] = (uint16_t)(fx * fy * 32);
+            }
+    }
+    ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
+    if (!e->d_rtab) ORBHIP_HIP_CHECK(hipMalloc(&e->d_rtab, ORBHIP_REMAP_TABLE_SIZE * sizeof(uint16_t)));
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(e->d_rtab, t.data(), t.size() * sizeof(uint16_t), hipMemcpyHostToDevice, e->stream));
+    ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
+    e->rtab_dirty = false;
+    return ORBHIP_OK;
+}
+
+static bool remap_args_ok(const orbhip_extractor *e, int batch, int rows, int cols, int channels, int stride, int cap)
+{
+    return e->d_rmap && batch > 0 && channels == 1 && rows == e->rmap_srows && cols == e->rmap_scols && stride >= cols && cap > 0 &&
+           (long long)rows * stride < (1ll << 31);
+}
+
+int orbhip_extract_remap_batch_device(orbhip_extractor *e, const void *d_images, int batch, int rows, int cols, int channels,
+                                      int stride, size_t frame_stride, void *d_kps, void *d_desc, int cap, void *d_n, void *d_status)
+{
+    if (!e || !d_images || !d_kps || !d_desc || !d_n || !remap_args_ok(e, batch, rows, cols, channels, stride, cap)) {
+        set_error("orbhip_extract_remap_batch_device: bad argument (grey frames of the installed map's source size)");
+        return ORBHIP_E_ARG;
+    }
+    ORBHIP_HIP_CHECK(hipSetDevice(e->device));
+    const int drows = e->rmap_drows, dcols = e->rmap_dcols;
+    int rc = bind_geometry(e, drows, dcols);
+    if (rc) return rc;
+    if ((rc = ensure_batch(e, batch))) return rc;
+    if ((rc = ensure_gray(e, batch))) return rc;
+    if ((rc = ensure_remap_table(e))) return rc;
+    // from here on the handle's rectified frames are "the image" of this extraction (also for a lazy level 0)
+    const int pitch = gray_pitch(dcols);
+    const size_t gframe = (size_t)drows * pitch;
+    if ((rc = begin_extraction(e, e->d_gray, pitch, gframe))) return rc;
+    const RemapSrc M = {(const uint8_t *)d_images, stride, frame_stride};
+    return launch_pipeline(e, e->d_gray, batch, pitch, gframe, (orbhip_keypoint *)d_kps, (uint8_t *)d_desc, cap, (int *)d_n,
+                           (int *)d_status, 0, nullptr, &M);
+}
+
+// Host frames: as orbhip_extract_color_batch (shared staging: packed rows, ONE 1-D copy, eager launches, one chunk)
+int orbhip_extract_remap_batch(orbhip_extractor *e, const uint8_t *images, int batch, int rows, int cols, int channels, int stride,
+                               size_t frame_stride, orbhip_keypoint *kps, uint8_t *desc, int cap, int32_t *n)
+{
+    if (!e || !kps || !desc || !n || batch <= 0 || cap <= 0 || channels != 1 || !e->d_rmap) {
+        set_error("orbhip_extract_remap_batch: bad argument (grey frames, a map installed)");
+        return ORBHIP_E_ARG;
+    }
+    if (!images || rows <= 0 || cols <= 0) {  // empty image: silent return (:1046-1047)
+        for (int b = 0; b < batch; ++b) n[b] = 0;
+        return ORBHIP_OK;
+    }
+    if (!remap_args_ok(e, batch, rows, cols, channels, stride, cap)) {
+        set_error("orbhip_extract_remap_batch: bad argument (frames of the installed map's source size)");
+        return ORBHIP_E_ARG;
+    }
+    ORBHIP_HIP_CHECK(hipSetDevice(e->device));
+    int rc = bind_geometry(e, e->rmap_drows, e->rmap_dcols);
+    if (rc) return rc;
+    const size_t rbytes = (size_t)cols, fbytes = (size_t)rows * rbytes, img_bytes = (size_t)batch * fbytes;
+    if ((rc = ensure_color_staging(e, img_bytes))) return rc;
+    if ((rc = ensure_out_staging(e, batch, cap))) return rc;
+    ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));   // the staging buffers of the previous call are free
+    for (int b = 0; b < batch; ++b) {
+        const uint8_t *src = images + b * frame_stride;
+        uint8_t *dst = e->h_cin + (size_t)b * fbytes;
+        if ((size_t)stride == rbytes) memcpy(dst, src, fbytes);
+        else for (int r = 0; r < rows; ++r) memcpy(dst + (size_t)r * rbytes, src + (size_t)r * stride, rbytes);
+    }
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(e->d_cimg, e->h_cin, img_bytes, hipMemcpyHostToDevice, e->stream));
+    if ((rc = orbhip_extract_remap_batch_device(e, e->d_cimg, batch, rows, cols, 1, (int)rbytes, fbytes, e->d_okp, e->d_odesc, cap,
+                                                e->d_on, nullptr))) return rc;
+    return download_results(e, batch, cap, kps, desc, n);
+}
+
+int orbhip_extract_remap(orbhip_extractor *e, const uint8_t *image, int rows, int cols, int channels, int stride,
+                         orbhip_keypoint *kps, uint8_t *desc, int cap, int *n)
+{
+    if (!n) return ORBHIP_E_ARG;
+    int32_t nn = 0;
+    int rc = orbhip_extract_remap_batch(e, image, 1, rows, cols, channels, stride, 0, kps, desc, cap, &nn);
     *n = nn;
     return rc;
 }

@@ -124,6 +124,13 @@ struct orbhip_extractor {
     int gray_w[3] = {4899, 9617, 1868}, gray_shift = 14;   // wR, wG, wB (orbhip_extractor_set_gray_weights)
     uint8_t *d_cimg = nullptr; size_t d_cimg_bytes = 0;    // host colour entries: packed colour frames on the device ...
     uint8_t *h_cin = nullptr; size_t h_cin_bytes = 0;      // ... and their page-locked staging
+    // stereo rectification (orbhip_extract_remap*): per-destination-pixel records of the installed map, the weight table,
+    // and the sizes the map was built for.  The rectified frames go to d_gray; the host entries stage through d_cimg / h_cin.
+    uint2 *d_rmap = nullptr;
+    int rmap_drows = 0, rmap_dcols = 0, rmap_srows = 0, rmap_scols = 0;
+    uint16_t *d_rtab = nullptr;
+    bool rtab_dirty = true;
+    std::vector<uint16_t> rtab;     // 1024 x 4 (orbhip_extractor_set_remap_table); empty = the default
     // staging for the host-pointer API
     uint8_t *d_img = nullptr; size_t d_img_bytes = 0;
     orbhip_keypoint *d_okp = nullptr; uint8_t *d_odesc = nullptr; int *d_on = nullptr;

@@ -195,6 +195,77 @@ class ORBextractor:
               "orbhip_extract_color_batch_device")
         self._shape = (rows, cols)
 
+    # -- stereo rectification: cv::remap(im, imRect, M1, M2, INTER_LINEAR) of Examples/Stereo/stereo_euroc.cc:136-137 + operator()
+    def set_remap(self, map1, map2=None, src_shape=None):
+        """map1, map2: float32 [dst_rows, dst_cols] (init_undistort_rectify_map); src_shape: (rows, cols) of the raw frames,
+        default the maps' own shape.  set_remap(None) removes the map."""
+        if map1 is None:
+            check(self._lib.orbhip_extractor_set_remap(self._h, 0, 0, 0, 0, None, None), "orbhip_extractor_set_remap")
+            self.__dict__.pop("_remap_shape", None)
+            return
+        map1 = np.ascontiguousarray(map1, np.float32)
+        map2 = np.ascontiguousarray(map2, np.float32)
+        if map1.ndim != 2 or map1.shape != map2.shape:
+            raise TypeError("expected two float32 maps of one 2-D shape")
+        srows, scols = map1.shape if src_shape is None else src_shape
+        check(self._lib.orbhip_extractor_set_remap(self._h, map1.shape[0], map1.shape[1], int(srows), int(scols), ptr(map1),
+                                                   ptr(map2)), "orbhip_extractor_set_remap")
+        self._remap_shape = map1.shape
+
+    def set_remap_table(self, table=None):
+        """table: 1024 x 4 weights in 0..65535 (row (fy*32 + fx): taps (x,y), (x+1,y), (x,y+1), (x+1,y+1)); None: default."""
+        if table is not None:
+            table = np.ascontiguousarray(table, np.int32).reshape(-1)
+            assert table.size == capi.REMAP_TABLE_SIZE
+        check(self._lib.orbhip_extractor_set_remap_table(self._h, ptr(table)), "orbhip_extractor_set_remap_table")
+
+    @staticmethod
+    def _remap_view(images, ndim):
+        if images.dtype != np.uint8 or images.ndim != ndim:
+            raise TypeError("expected CV_8UC1 frames (grey input only)")
+        if images.strides[-1] != 1 or any(s < images.shape[-1] for s in images.strides[:-1]):
+            images = np.ascontiguousarray(images)
+        return images
+
+    def extract_remap(self, image):
+        """image: uint8 [src_rows, src_cols], the raw frame.  Returns (keypoints, descriptors) of the rectified image."""
+        if image is None or image.size == 0:
+            return np.zeros(0, KP_DTYPE), np.zeros((0, 32), np.uint8)
+        image = self._remap_view(image, 2)
+        drows, dcols = getattr(self, "_remap_shape", image.shape)
+        cap = self.capacity(drows, dcols)
+        kps = np.zeros(cap, KP_DTYPE)
+        desc = np.zeros((cap, 32), np.uint8)
+        n = C.c_int()
+        check(self._lib.orbhip_extract_remap(self._h, ptr(image), image.shape[0], image.shape[1], 1, image.strides[0], ptr(kps),
+                                             ptr(desc), cap, C.byref(n)), "orbhip_extract_remap")
+        self._shape = (drows, dcols)
+        return kps[:n.value].copy(), desc[:n.value].copy()
+
+    def extract_remap_batch(self, images):
+        """images: uint8 [B, src_rows, src_cols] on the host.  Returns list of (keypoints, descriptors)."""
+        images = self._remap_view(images, 3)
+        B, rows, cols = images.shape
+        drows, dcols = getattr(self, "_remap_shape", (rows, cols))
+        cap = self.capacity(drows, dcols)
+        kps = np.zeros((B, cap), KP_DTYPE)
+        desc = np.zeros((B, cap, 32), np.uint8)
+        n = np.zeros(B, np.int32)
+        check(self._lib.orbhip_extract_remap_batch(self._h, ptr(images), B, rows, cols, 1, images.strides[1], images.strides[0],
+                                                   ptr(kps), ptr(desc), cap, ptr(n)), "orbhip_extract_remap_batch")
+        self._shape = (drows, dcols)
+        return [(kps[b, :n[b]].copy(), desc[b, :n[b]].copy()) for b in range(B)]
+
+    def extract_remap_batch_device(self, d_images, batch, rows, cols, d_kps, d_desc, cap, d_n, d_status=0, stride=None,
+                                   frame_stride=None):
+        """Device-pointer entry (ints from torch .data_ptr()); rows, cols: the SOURCE size; cap: capacity at the map's
+        destination size.  Asynchronous on the handle's stream; the source buffer may be reused once this call's work has run."""
+        stride = cols if stride is None else stride
+        frame_stride = rows * stride if frame_stride is None else frame_stride
+        check(self._lib.orbhip_extract_remap_batch_device(self._h, d_images, batch, rows, cols, 1, stride, frame_stride, d_kps,
+                                                          d_desc, cap, d_n, d_status), "orbhip_extract_remap_batch_device")
+        self._shape = tuple(getattr(self, "_remap_shape", (rows, cols)))
+
     def sync(self):
         check(self._lib.orbhip_extractor_sync(self._h), "orbhip_extractor_sync")
 
@@ -241,3 +312,18 @@ class ORBextractor:
         check(self._lib.orbhip_level_candidates(self._h, frame, level, ptr(x), ptr(y), ptr(s), cap,
                                                 C.byref(n)), "orbhip_level_candidates")
         return x[:n.value].copy(), y[:n.value].copy(), s[:n.value].copy()
+
+
+def init_undistort_rectify_map(K, D, R, P, size):
+    """cv::initUndistortRectifyMap(K, D, R, P, size, CV_32F): K 3x3, D 4 / 5 / 8 coefficients, R 3x3 or None, P 3x3 or 3x4
+    (its left 3x3 is used, as stereo_euroc.cc:97-98 passes it), size = (cols, rows).  Host code; returns (map1, map2)."""
+    K = np.ascontiguousarray(K, np.float64).reshape(3, 3)
+    D = np.ascontiguousarray(D, np.float64).reshape(-1)
+    P = np.ascontiguousarray(np.asarray(P, np.float64)[:3, :3])
+    R = None if R is None else np.ascontiguousarray(R, np.float64).reshape(3, 3)
+    cols, rows = int(size[0]), int(size[1])
+    m1 = np.zeros((max(rows, 0), max(cols, 0)), np.float32)
+    m2 = np.zeros_like(m1)
+    check(capi.lib().orbhip_init_undistort_rectify_map(ptr(K), ptr(D), D.size, ptr(R), ptr(P), cols, rows, ptr(m1), ptr(m2)),
+          "orbhip_init_undistort_rectify_map")
+    return m1, m2

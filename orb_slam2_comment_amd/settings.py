@@ -1,6 +1,7 @@
 """The part of the example harness that feeds the front-end: the settings file (cv::FileStorage YAML subset read by the
 Tracking constructor, src/Tracking.cc:51-147), the KITTI sequence layout of Examples/Monocular/mono_kitti.cc:127-157 and
-the TUM lists of Examples/RGB-D/rgbd_tum.cc:142-167 / Examples/Monocular/mono_tum.cc:127-160.
+the TUM lists of Examples/RGB-D/rgbd_tum.cc:142-167 / Examples/Monocular/mono_tum.cc:127-160, and the stereo
+rectification matrices and list layout of Examples/Stereo/stereo_euroc.cc:63-98, 192-216.
 No OpenCV: scalars are parsed from the text, images are decoded by a small PNG (8-bit grey / RGB / RGBA, 16-bit grey) /
 PGM reader."""
 import os
@@ -255,3 +256,80 @@ def load_tum_rgb_list(path):
         p = s.split()
         stamps.append(float(p[0])); names.append(p[1])
     return names, stamps
+
+
+# ---- stereo rectification settings and the EuRoC list layout (Examples/Stereo/stereo_euroc.cc) -------------------------
+def load_matrices(path):
+    """Every `key: !!opencv-matrix` block of an OpenCV YAML file as a dict of float64 [rows, cols] arrays.  `rows`, `cols`,
+    `dt` (d or f) and `data: [...]`, which may run over several lines and may be written `data:[` without a space
+    (Examples/Stereo/EuRoC.yaml:43)."""
+    out = {}
+    key, fields, data = None, {}, None
+
+    def close():
+        if key is None:
+            return
+        if data is None or "rows" not in fields or "cols" not in fields:
+            raise ValueError("%s: matrix %s is incomplete" % (path, key))
+        vals = [float(v) for v in data.replace("[", " ").replace("]", " ").split(",") if v.strip()]
+        r, c = int(fields["rows"]), int(fields["cols"])
+        if len(vals) != r * c:
+            raise ValueError("%s: matrix %s has %d values for %dx%d" % (path, key, len(vals), r, c))
+        if fields.get("dt", "d") not in ("d", "f"):
+            raise ValueError("%s: matrix %s: unsupported dt %r" % (path, key, fields.get("dt")))
+        out[key] = np.array(vals, np.float64).reshape(r, c)
+
+    with open(path) as f:
+        for raw in f:
+            line = raw.split("#", 1)[0].rstrip()
+            if not line.strip() or line.startswith("%"):
+                continue
+            if line[0] not in " \t":                     # a top-level key ends the block before it
+                close()
+                key, fields, data = None, {}, None
+                k, _, v = line.partition(":")
+                if v.strip().startswith("!!opencv-matrix"):
+                    key = k.strip()
+                continue
+            if key is None:
+                continue
+            body = line.strip()
+            if data is not None and "]" not in data:      # continuation of a data list
+                data += " " + body
+                continue
+            k, _, v = body.partition(":")
+            if k.strip() == "data":
+                data = v.strip()
+            else:
+                fields[k.strip()] = v.strip().strip('"')
+    close()
+    return out
+
+
+def stereo_rectification(path):
+    """What stereo_euroc.cc:63-94 reads: {"left" | "right": {"K", "D", "R", "P", "width", "height"}}, K / R 3x3, P 3x4, D a
+    flat coefficient vector.  Raises ValueError with the example's message when a matrix is empty or a size is 0."""
+    st, mats = load_settings(path), load_matrices(path)
+    out = {}
+    for side, pre in (("left", "LEFT."), ("right", "RIGHT.")):
+        cam = {k: mats.get(pre + k) for k in "KDRP"}
+        cam["height"], cam["width"] = int(st.get(pre + "height", 0)), int(st.get(pre + "width", 0))
+        if any(cam[k] is None or cam[k].size == 0 for k in "KDRP") or cam["height"] == 0 or cam["width"] == 0:
+            raise ValueError("ERROR: Calibration parameters to rectify stereo are missing!")
+        cam["D"] = cam["D"].reshape(-1)
+        out[side] = cam
+    return out
+
+
+def load_euroc_sequence(left_dir, right_dir, times_file):
+    """LoadImages of Examples/Stereo/stereo_euroc.cc:192-216: one stamp per non-empty line of the times file, images
+    <dir>/<line>.png, time = line / 1e9.  Returns (left names, right names, timestamps)."""
+    left, right, stamps = [], [], []
+    with open(times_file) as f:
+        for s in f:
+            s = s.strip()
+            if s:
+                left.append(left_dir + "/" + s + ".png")
+                right.append(right_dir + "/" + s + ".png")
+                stamps.append(float(s) / 1e9)
+    return left, right, stamps

@@ -129,6 +129,43 @@ def synth_depth(seed, W=640, H=480):
     return d
 
 
+def unrectify(img, K, D, R, P, size=None):
+    """The raw camera frame whose rectification (initUndistortRectifyMap + remap with the same K, D, R, P) shows `img`:
+    every raw pixel is normalised with K, undistorted by the usual 5-step fixed point, rotated by R, projected by P and
+    `img` is sampled there bilinearly (edge pixels repeated).  Test / benchmark input only: nothing is compared with it.
+    size = (cols, rows) of the raw frame, default img's."""
+    K, P = np.asarray(K, np.float64).reshape(3, 3), np.asarray(P, np.float64)[:3, :3]
+    R = np.eye(3) if R is None else np.asarray(R, np.float64).reshape(3, 3)
+    D = list(np.asarray(D, np.float64).reshape(-1)) + [0.0] * 8
+    k1, k2, p1, p2, k3 = D[:5]
+    cols, rows = (img.shape[1], img.shape[0]) if size is None else size
+    u, v = np.meshgrid(np.arange(cols, dtype=np.float64), np.arange(rows, dtype=np.float64))
+    x0, y0 = (u - K[0, 2]) / K[0, 0], (v - K[1, 2]) / K[1, 1]
+    x, y = x0.copy(), y0.copy()
+    for _ in range(5):
+        r2 = x * x + y * y
+        icd = 1.0 / (1 + ((k3 * r2 + k2) * r2 + k1) * r2)
+        dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+        dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+        x, y = (x0 - dx) * icd, (y0 - dy) * icd
+    A = P @ R
+    w = A[2, 0] * x + A[2, 1] * y + A[2, 2]
+    xr = np.clip((A[0, 0] * x + A[0, 1] * y + A[0, 2]) / w, 0, img.shape[1] - 1)
+    yr = np.clip((A[1, 0] * x + A[1, 1] * y + A[1, 2]) / w, 0, img.shape[0] - 1)
+    xi, yi = np.minimum(xr.astype(np.int64), img.shape[1] - 2), np.minimum(yr.astype(np.int64), img.shape[0] - 2)
+    fx, fy = xr - xi, yr - yi
+    f = img.astype(np.float64)
+    out = (f[yi, xi] * (1 - fx) + f[yi, xi + 1] * fx) * (1 - fy) + (f[yi + 1, xi] * (1 - fx) + f[yi + 1, xi + 1] * fx) * fy
+    return np.clip(np.rint(out), 0, 255).astype(np.uint8)
+
+
+def synth_raw_stereo(seed, calib, W=752, H=480):
+    """A raw (unrectified) stereo pair for settings.stereo_rectification's `calib`: synth_stereo seen through the two
+    cameras' distortion and rotation.  Returns (raw_left, raw_right)."""
+    left, right = synth_stereo(seed, W, H)
+    return tuple(unrectify(im, c["K"], c["D"], c["R"], c["P"]) for im, c in ((left, calib["left"]), (right, calib["right"])))
+
+
 def synth_vocabulary(k=10, L=6, seed=1):
     """Regular k-ary vocabulary tree with the shape of ORBvoc.txt (k=10, L=6: 1.1 M nodes, 10^6 words) in
     saveToTextFile (BFS) order, for benchmarks: the real vocabulary is not part of the reference checkout.
