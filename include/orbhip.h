@@ -609,6 +609,56 @@ int orbhip_frustum_queries_device(orbhip_matcher *m, int frames, const orbhip_ca
                                   const void *d_min_dist, const void *d_flags, float viewing_cos_limit, float th,
                                   void *d_q, void *d_view_cos);
 
+/* ---- seeding stereo / RGB-D map points -------------------------------------------------------------------------
+ * The step between mvDepth (orbhip_compute_stereo_matches*, orbhip_compute_stereo_from_rgbd*) and the world / flags arrays
+ * orbhip_track_last_frame_device reads: which keypoints become new map points, and where they are.
+ *   ORBHIP_SEED_CLOSEST  Tracking::UpdateLastFrame (src/Tracking.cc:812-864) and Tracking::CreateNewKeyFrame (:1073-1133):
+ *     vDepthIdx = the (z, i) of every keypoint with z = depth[i] > 0, sorted ascending (std::sort on pair<float,int>: by z,
+ *     then by i); the walk counts every entry it visits and stops after the first entry with z > th_depth once more than
+ *     100 have been visited (that entry is still processed).  A visited entry is created iff its slot has no map point or
+ *     a map point nobody observes: !(flags[i] & ORBHIP_POINT_PRESENT) || !(flags[i] & ORBHIP_POINT_OBSERVED) (:839-845).
+ *   ORBHIP_SEED_ALL      Tracking::StereoInitialization (:523-538): every keypoint with z > 0, in index order, is created.
+ * Flag meaning for these entries: ORBHIP_POINT_PRESENT = mvpMapPoints[i] != NULL (outliers included: the loop does not
+ * read mvbOutlier), ORBHIP_POINT_OBSERVED = pMP->Observations() > 0.
+ * A created entry gets Frame::UnprojectStereo(i) (src/Frame.cc:666-680): x = ((u - cx) * z) * invfx, y = ((v - cy) * z) *
+ * invfy with invfx = 1.0f / fx (src/Frame.cc:108-109), (u, v) = keys[i]; X = mRwc * (x, y, z) + mOw with mRwc = Rcw^T and
+ * mOw = -Rcw^T * tcw, all in float in the operation order DESIGN.md section 3 states.  keys = mvKeysUn.
+ * KeyFrame::UnprojectStereo (src/KeyFrame.cc:615-631, called from src/LocalMapping.cc:342,346) has the same arithmetic but
+ * reads mvKeys, NOT mvKeysUn (src/KeyFrame.cc:620): a caller restating the KeyFrame form passes mvKeys.
+ * Tcw: top three rows of mTcw, row-major.  world [n][3] / flags [n] are updated in place: created entries get their
+ * position and flags[i] = created_flags (ORBHIP_POINT_PRESENT for UpdateLastFrame's temporal points, | ORBHIP_POINT_OBSERVED
+ * where the caller adds the observation at once, :1115, :530); every other entry keeps the caller's values.
+ * order [n] (nullable): order[j] = i for the j-th visited entry, the order in which the caller creates its MapPoints;
+ * created [n] (nullable): 1 where entry i was created, else 0; counts [3] = {n_valid (z > 0), n_visited, n_created}.
+ * n == 0 or no positive depth: success, zero counts.  n <= 4096 (ORBHIP_E_CAPACITY beyond: the sort is LDS resident).
+ * Host buffers, synchronous. */
+#define ORBHIP_SEED_ALL     0   /* StereoInitialization, src/Tracking.cc:523-538 */
+#define ORBHIP_SEED_CLOSEST 1   /* UpdateLastFrame :812-864, CreateNewKeyFrame :1073-1133 */
+int orbhip_seed_stereo_points(orbhip_matcher *m, const orbhip_camera *cam, const float *Tcw, const orbhip_keypoint *keys,
+                              const float *depth, int n, float th_depth, int mode, int created_flags, float *world,
+                              uint8_t *flags, int32_t *order, uint8_t *created, int32_t *counts);
+/* Device-resident, batched, asynchronous on the matcher's stream: output frame f (0 .. frames-1) reads the keypoints and
+ * the count of frame kp_first + f*kp_step of d_kps [..][cap] / d_n [..] (the left frames of an interleaved stereo batch:
+ * kp_first = 0, kp_step = 2) and d_Tcw [frames][12], d_depth [frames][cap]; d_world [frames][cap][3] and d_flags
+ * [frames][cap] in/out, d_order [frames][cap] int32 and d_created [frames][cap] uint8 nullable, d_counts [frames][3] int32.
+ * d_depth is what orbhip_compute_stereo_matches_device writes; orbhip_track_last_frame_device addresses d_world / d_flags by
+ * the last frame's index in the extractor arrays, so a caller feeding it allocates them [frames of the batch][cap] and
+ * output frame f here is row f of them.  cap <= 4096. */
+int orbhip_seed_stereo_points_device(orbhip_matcher *m, int frames, const orbhip_camera *cam, const void *d_Tcw, const void *d_kps,
+                                     const void *d_n, int cap, int kp_first, int kp_step, const void *d_depth, float th_depth,
+                                     int mode, int created_flags, void *d_world, void *d_flags, void *d_order, void *d_created,
+                                     void *d_counts);
+/* Tracking::NeedNewKeyFrame's close-point counts (src/Tracking.cc:1001-1018): over the keypoints with depth[i] > 0 &&
+ * depth[i] < th_depth (strict), *tracked = nTrackedClose counts those with ORBHIP_POINT_PRESENT, *non_tracked =
+ * nNonTrackedClose the others.  Flag meaning for THIS entry: ORBHIP_POINT_PRESENT = mvpMapPoints[i] && !mvbOutlier[i]
+ * (:1010), not the bare "map point exists" of the seeding entries.  Host buffers, synchronous; any n. */
+int orbhip_count_close_points(orbhip_matcher *m, const float *depth, const uint8_t *flags, int n, float th_depth, int *tracked,
+                              int *non_tracked);
+/* device-resident, batched: d_depth [frames][cap] float, d_flags [frames][cap] uint8, d_n [frames] int32 (indexed by the
+ * output frame, like the other arrays); d_counts [frames][2] int32 = {nTrackedClose, nNonTrackedClose}.  Asynchronous. */
+int orbhip_count_close_points_device(orbhip_matcher *m, int frames, const void *d_depth, const void *d_flags, const void *d_n,
+                                     int cap, float th_depth, void *d_counts);
+
 /* Launch on a caller-owned hipStream_t (NULL: the handle's own stream); wait for the handle's stream. */
 int orbhip_matcher_set_stream(orbhip_matcher *m, void *stream);
 int orbhip_matcher_sync(orbhip_matcher *m);

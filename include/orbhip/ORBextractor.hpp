@@ -490,6 +490,78 @@ public:
         mvDepth.resize(keys.size());
     }
 
+    // Seeding stereo / RGB-D map points: the depth-sorted creation loop of Tracking::UpdateLastFrame (src/Tracking.cc:812-864)
+    // and Tracking::CreateNewKeyFrame (:1073-1133) with mode ORBHIP_SEED_CLOSEST, Tracking::StereoInitialization (:523-538)
+    // with ORBHIP_SEED_ALL, positions by Frame::UnprojectStereo (src/Frame.cc:666-680).  flags[i]: ORBHIP_POINT_PRESENT =
+    // mvpMapPoints[i] != NULL, ORBHIP_POINT_OBSERVED = Observations() > 0.  world (3 floats per keypoint) and flags are
+    // updated in place; order = the visited keypoints in the order the caller creates its MapPoints; created[i] = 0 / 1.
+    // Returns the number of created points.  keysUn = mvKeysUn (the KeyFrame form, src/KeyFrame.cc:615-631, passes mvKeys).
+    struct SeedCounts { int nValid, nVisited, nCreated; };
+    int SeedStereoPoints(const orbhip_camera &cam, const float Tcw[12], const std::vector<KeyPoint> &keysUn,
+                         const std::vector<float> &mvDepth, float thDepth, int mode, int createdFlags, std::vector<float> &world,
+                         std::vector<uint8_t> &flags, std::vector<int> &order, std::vector<uint8_t> &created,
+                         SeedCounts *countsOut = nullptr)
+    {
+        const size_t n = keysUn.size();
+        if (mvDepth.size() != n || world.size() != 3 * n || flags.size() != n) throw Error(ORBHIP_E_ARG, "SeedStereoPoints");
+        order.assign(n ? n : 1, -1);
+        created.assign(n ? n : 1, 0);
+        int32_t counts[3] = {0, 0, 0};
+        check(orbhip_seed_stereo_points(m_, &cam, Tcw, keysUn.data(), mvDepth.data(), (int)n, thDepth, mode, createdFlags, world.data(),
+                                        flags.data(), order.data(), created.data(), counts), "orbhip_seed_stereo_points");
+        order.resize((size_t)counts[1]);
+        created.resize(n);
+        if (countsOut) { countsOut->nValid = counts[0]; countsOut->nVisited = counts[1]; countsOut->nCreated = counts[2]; }
+        return counts[2];
+    }
+    // device frames, asynchronous on the matcher's stream: orbhip_seed_stereo_points_device with the mirror's handle
+    void SeedStereoPointsDevice(int frames, const orbhip_camera &cam, const void *dTcw, const void *dKps, const void *dN, int cap,
+                                int kpFirst, int kpStep, const void *dDepth, float thDepth, int mode, int createdFlags, void *dWorld,
+                                void *dFlags, void *dOrder, void *dCreated, void *dCounts)
+    {
+        check(orbhip_seed_stereo_points_device(m_, frames, &cam, dTcw, dKps, dN, cap, kpFirst, kpStep, dDepth, thDepth, mode,
+                                               createdFlags, dWorld, dFlags, dOrder, dCreated, dCounts),
+              "orbhip_seed_stereo_points_device");
+    }
+    // cv::Mat Frame::UnprojectStereo(const int &i) (src/Frame.cc:666-680) for every keypoint: mode ORBHIP_SEED_ALL on scratch
+    // arrays.  x3D holds 3 floats per keypoint; valid[i] = 0 where the reference returns an empty cv::Mat (z <= 0).
+    void UnprojectStereo(const orbhip_camera &cam, const float Tcw[12], const std::vector<KeyPoint> &keysUn,
+                         const std::vector<float> &mvDepth, std::vector<float> &x3D, std::vector<uint8_t> &valid)
+    {
+        std::vector<uint8_t> flags(keysUn.size(), 0);
+        std::vector<int> order;
+        x3D.assign(3 * keysUn.size(), 0.f);
+        SeedStereoPoints(cam, Tcw, keysUn, mvDepth, 0.f, ORBHIP_SEED_ALL, ORBHIP_POINT_PRESENT, x3D, flags, order, valid);
+    }
+    // one keypoint, like the reference's signature; false = empty cv::Mat
+    bool UnprojectStereo(int i, const orbhip_camera &cam, const float Tcw[12], const std::vector<KeyPoint> &keysUn,
+                         const std::vector<float> &mvDepth, float x3D[3])
+    {
+        if (i < 0 || (size_t)i >= keysUn.size() || mvDepth.size() != keysUn.size()) throw Error(ORBHIP_E_ARG, "UnprojectStereo");
+        const std::vector<KeyPoint> k(1, keysUn[(size_t)i]);
+        const std::vector<float> z(1, mvDepth[(size_t)i]);
+        std::vector<float> X;
+        std::vector<uint8_t> valid;
+        UnprojectStereo(cam, Tcw, k, z, X, valid);
+        x3D[0] = X[0]; x3D[1] = X[1]; x3D[2] = X[2];
+        return valid[0] != 0;
+    }
+    // Tracking::NeedNewKeyFrame's nTrackedClose / nNonTrackedClose (src/Tracking.cc:1001-1018).  Here ORBHIP_POINT_PRESENT
+    // means mvpMapPoints[i] && !mvbOutlier[i].
+    void CountClosePoints(const std::vector<float> &mvDepth, const std::vector<uint8_t> &flags, float thDepth, int &nTrackedClose,
+                          int &nNonTrackedClose)
+    {
+        if (mvDepth.size() != flags.size()) throw Error(ORBHIP_E_ARG, "CountClosePoints");
+        check(orbhip_count_close_points(m_, mvDepth.data(), flags.data(), (int)mvDepth.size(), thDepth, &nTrackedClose,
+                                        &nNonTrackedClose), "orbhip_count_close_points");
+    }
+    void CountClosePointsDevice(int frames, const void *dDepth, const void *dFlags, const void *dN, int cap, float thDepth,
+                                void *dCounts)
+    {
+        check(orbhip_count_close_points_device(m_, frames, dDepth, dFlags, dN, cap, thDepth, dCounts),
+              "orbhip_count_close_points_device");
+    }
+
     // the Frame statics the prologues read (src/Frame.cc:97-112), as one record
     static orbhip_camera MakeCamera(float fx, float fy, float cx, float cy, float mbf, float mb, float minX, float maxX, float minY,
                                     float maxY, const std::vector<float> &scaleFactors, float logScaleFactor)

@@ -43,6 +43,7 @@ class Camera(C.Structure):
 POINT_PRESENT, POINT_OBSERVED = 1, 2
 COLOR_BGR, COLOR_RGB = 0, 1
 DEPTH_U16, DEPTH_F32 = 0, 1
+SEED_ALL, SEED_CLOSEST = 0, 1
 REMAP_TABLE_SIZE = 4096
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
@@ -135,6 +136,11 @@ SYMBOLS = [
                                             _vp, _vp, _vp, _f, _i, _i, _vp, _vp]),
     ("orbhip_frustum_queries_device", _i, [_vp, _i, C.POINTER(Camera), _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp,
                                            _vp]),
+    ("orbhip_seed_stereo_points", _i, [_vp, C.POINTER(Camera), _vp, _vp, _vp, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("orbhip_seed_stereo_points_device", _i, [_vp, _i, C.POINTER(Camera), _vp, _vp, _vp, _i, _i, _i, _vp, _f, _i, _i, _vp, _vp,
+                                              _vp, _vp, _vp]),
+    ("orbhip_count_close_points", _i, [_vp, _vp, _vp, _i, _f, _pi, _pi]),
+    ("orbhip_count_close_points_device", _i, [_vp, _i, _vp, _vp, _vp, _i, _f, _vp]),
     ("orbhip_matcher_set_stream", _i, [_vp, _vp]),
     ("orbhip_matcher_sync", _i, [_vp]),
     ("orbhip_compute_stereo_matches_device", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,

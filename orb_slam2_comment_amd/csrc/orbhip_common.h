@@ -106,6 +106,19 @@ __device__ __forceinline__ int wave_min(int v)
     return __builtin_amdgcn_readlane(v, 63);
 }
 
+// XCD-aware work mapping (speed only, never correctness): workgroups are dealt round-robin over the
+// 8 XCDs in linear order, each XCD has a private 4 MB L2.  Re-index so that XCD k owns a contiguous
+// run of (frame, unit) pairs: with a batch that is a multiple of 8 every kernel of the pipeline
+// then touches frame f from the same XCD, and neighbouring cells/tiles share their cache lines.
+__device__ __forceinline__ void xcd_remap(int &unit, int &frame)
+{
+    const unsigned T = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
+    const unsigned q = T >> 3, r = T & 7, x = lin & 7;
+    const unsigned lin2 = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (lin >> 3);
+    frame = (int)(lin2 / gridDim.x);
+    unit = (int)(lin2 - (unsigned)frame * gridDim.x);
+}
+
 __device__ __forceinline__ int reflect101(int p, int len)
 {
     // BORDER_REFLECT_101; |overshoot| < len is guaranteed by the callers (19-px border)

@@ -2401,6 +2401,178 @@ __global__ __launch_bounds__(256) void k_stereo_cull(const int *__restrict__ sad
     if (tid == 0) *out_n = s_cnt;
 }
 
+// ---- Seeding stereo / RGB-D map points: Tracking::UpdateLastFrame (src/Tracking.cc:812-864), CreateNewKeyFrame
+// (:1073-1133), StereoInitialization (:523-538), all through Frame::UnprojectStereo (src/Frame.cc:666-680) ------------
+// One workgroup per frame.  The keypoints with a positive depth are compacted in index order (vDepthIdx before the sort);
+// mode CLOSEST sorts them by (z, i): for z > 0 the float's bit pattern is monotone as an unsigned integer, so the 64-bit
+// key bits(z) << 32 | i sorted as an integer is std::sort's order on pair<float,int> (a total order: +inf last, no ties).
+// The walk with its stop rule (:833-864) visits the first min(n_valid, max(101, c + 1)) sorted entries, c = the number of
+// entries that do not satisfy z > mThDepth: nPoints is j + 1 after entry j, so the loop breaks at the first j >= 100 whose
+// z exceeds the threshold, which in sorted order is j = max(100, c), and that entry is still processed.
+// LDS: 32 KB of keys + 4 KB of created marks.
+constexpr int kSeedMax = 4096;
+struct SeedBatch {
+    const float *Tcw;                  // [frames][12]
+    const orbhip_keypoint *keys;       // [..][cap], frame k0 + f*ks
+    const int *n_dev;                  // [..], frame k0 + f*ks
+    const float *depth;                // [frames][cap]
+    float *world;                      // [frames][cap][3] in/out
+    uint8_t *flags;                    // [frames][cap] in/out
+    int *order;                        // [frames][cap] or null
+    uint8_t *created;                  // [frames][cap] or null
+    int *counts;                       // [frames][3]
+    int cap, k0, ks;
+};
+
+__device__ __forceinline__ void seed_compare_exchange(unsigned long long *key, int t, int j, int k)
+{
+    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+    const unsigned long long a = key[i], b = key[l];
+    if ((a > b) == ((i & k) == 0)) { key[i] = b; key[l] = a; }
+}
+
+__global__ __launch_bounds__(1024) void k_seed_stereo_points(SeedBatch B, float fx, float fy, float cx, float cy, float th_depth,
+                                                             int mode, int created_flags)
+{
+    __shared__ unsigned long long key[kSeedMax];
+    __shared__ uint8_t made[kSeedMax];
+    __shared__ int wsum[16];
+    __shared__ int s_close, s_created;
+    int unit, f;
+    xcd_remap(unit, f);
+    const int tid = threadIdx.x, NT = 1024, lane = tid & 63, wv = tid >> 6;
+    const size_t kf = (size_t)(B.k0 + f * B.ks);
+    const int n = max(min(min(B.n_dev[kf], B.cap), kSeedMax), 0);
+    const orbhip_keypoint *keys = B.keys + kf * B.cap;
+    const float *depth = B.depth + (size_t)f * B.cap;
+    float *world = B.world + (size_t)f * B.cap * 3;
+    uint8_t *flags = B.flags + (size_t)f * B.cap;
+    if (tid == 0) { s_close = 0; s_created = 0; }
+    // compaction in index order: thread t owns keypoints 4t .. 4t+3
+    float z[4];
+    int cnt = 0, close = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int i = 4 * tid + e;
+        z[e] = i < n ? depth[i] : 0.f;
+        const bool ok = z[e] > 0.f;                  // drops NaN, -1 and 0 (:818-822)
+        cnt += ok;
+        close += ok && !(z[e] > th_depth);
+        made[i] = 0;
+    }
+    const int incl = wave_incl_scan_add(cnt);
+    if (lane == 63) wsum[wv] = incl;
+    close = wave_sum(close);
+    __syncthreads();
+    if (lane == 0 && close) atomicAdd(&s_close, close);
+    int pos = incl - cnt, n_valid = 0;
+    for (int w = 0; w < 16; ++w) {
+        const int s = wsum[w];
+        if (w < wv) pos += s;
+        n_valid += s;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (z[e] > 0.f) key[pos++] = ((unsigned long long)__float_as_uint(z[e]) << 32) | (uint32_t)(4 * tid + e);
+    int P = 2;
+    if (mode == ORBHIP_SEED_CLOSEST) {
+        while (P < n_valid) P <<= 1;
+        for (int i = n_valid + tid; i < P; i += NT) key[i] = ~0ull;
+    }
+    __syncthreads();
+    int n_visit = n_valid;
+    if (mode == ORBHIP_SEED_CLOSEST) {
+        // bitonic sort of P keys, one compare-exchange per pair index t.  Pairs 64c .. 64c+63 of a stride <= 64 touch keys
+        // 128c .. 128c+127 only: one wavefront takes those strides of its chunks without a workgroup barrier.
+        const int half = P >> 1;
+        for (int k = 2; k <= P; k <<= 1) {
+            int j = k >> 1;
+            for (; j > 64; j >>= 1) {
+                for (int t = tid; t < half; t += NT) seed_compare_exchange(key, t, j, k);
+                __syncthreads();
+            }
+            for (int c = wv; c * 64 < half; c += 16) {
+                const int t = c * 64 + lane;
+                for (int jj = j; jj > 0; jj >>= 1) {
+                    if (t < half) seed_compare_exchange(key, t, jj, k);
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                }
+            }
+            __syncthreads();
+        }
+        n_visit = min(n_valid, max(101, s_close + 1));
+    }
+    // mRwc = mRcw^T, mOw = -mRcw^T * mtcw (src/Frame.cc:258-264); a dozen flops, recomputed per thread
+    const float *T = B.Tcw + (size_t)f * 12;
+    float Ow[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        Ow[c] = -__fadd_rn(__fadd_rn(__fmul_rn(T[c], T[3]), __fmul_rn(T[4 + c], T[7])), __fmul_rn(T[8 + c], T[11]));
+    const float invfx = __fdiv_rn(1.0f, fx), invfy = __fdiv_rn(1.0f, fy);      // src/Frame.cc:108-109
+    int *order = B.order ? B.order + (size_t)f * B.cap : nullptr;
+    int made_cnt = 0;
+    for (int j = tid; j < n_visit; j += NT) {
+        const unsigned long long kk = key[j];
+        const int i = (int)(uint32_t)kk;
+        const float zz = __uint_as_float((uint32_t)(kk >> 32));
+        if (order) order[j] = i;
+        bool create = mode == ORBHIP_SEED_ALL;
+        if (!create) {
+            const unsigned fg = flags[i];          // :839-845: no map point, or one nobody observes
+            create = !(fg & ORBHIP_POINT_PRESENT) || !(fg & ORBHIP_POINT_OBSERVED);
+        }
+        if (create) {
+            const orbhip_keypoint kp = keys[i];
+            const float x = __fmul_rn(__fmul_rn(__fsub_rn(kp.x, cx), zz), invfx);
+            const float y = __fmul_rn(__fmul_rn(__fsub_rn(kp.y, cy), zz), invfy);
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+                world[(size_t)i * 3 + r] =
+                    __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[r], x), __fmul_rn(T[4 + r], y)), __fmul_rn(T[8 + r], zz)), Ow[r]);
+            flags[i] = (uint8_t)created_flags;
+            made[i] = 1;
+            ++made_cnt;
+        }
+    }
+    made_cnt = wave_sum(made_cnt);
+    if (lane == 0 && made_cnt) atomicAdd(&s_created, made_cnt);
+    __syncthreads();
+    if (B.created) {
+        uint8_t *created = B.created + (size_t)f * B.cap;
+        for (int i = tid; i < n; i += NT) created[i] = made[i];
+    }
+    if (tid == 0) {
+        int *counts = B.counts + (size_t)f * 3;
+        counts[0] = n_valid; counts[1] = n_visit; counts[2] = s_created;
+    }
+}
+
+// Tracking::NeedNewKeyFrame's close-point counts (src/Tracking.cc:1006-1015): one workgroup per frame
+__global__ __launch_bounds__(256) void k_count_close_points(const float *__restrict__ depth, const uint8_t *__restrict__ flags,
+                                                            const int *__restrict__ n_dev, int cap, float th_depth,
+                                                            int *__restrict__ counts)
+{
+    __shared__ int s_cnt[2];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const int n = min(n_dev[f], cap);
+    depth += (size_t)f * cap; flags += (size_t)f * cap;
+    if (tid < 2) s_cnt[tid] = 0;
+    __syncthreads();
+    int tracked = 0, other = 0;
+    for (int i = tid; i < n; i += 256) {
+        const float z = depth[i];
+        if (z > 0.f && z < th_depth) {
+            if (flags[i] & ORBHIP_POINT_PRESENT) ++tracked; else ++other;
+        }
+    }
+    tracked = wave_sum(tracked); other = wave_sum(other);
+    if ((tid & 63) == 0) { if (tracked) atomicAdd(&s_cnt[0], tracked); if (other) atomicAdd(&s_cnt[1], other); }
+    __syncthreads();
+    if (tid < 2) counts[(size_t)f * 2 + tid] = s_cnt[tid];
+}
+
 }  // namespace orbhip
 
 // =============================================================================================
@@ -3542,6 +3714,109 @@ int orbhip_frustum_queries(orbhip_matcher *m, const orbhip_camera *cam, const fl
     if ((rc = read_back(m, p, ob, &h))) return rc;
     memcpy(q, h, qb);
     if (view_cos) memcpy(view_cos, h + qb, (size_t)n * sizeof(float));
+    return ORBHIP_OK;
+}
+
+static bool seed_args_ok(const orbhip_camera *cam, int mode, int created_flags)
+{
+    return cam && cam->fx != 0.f && cam->fy != 0.f && (mode == ORBHIP_SEED_ALL || mode == ORBHIP_SEED_CLOSEST) &&
+           created_flags >= 0 && created_flags <= 255;
+}
+
+int orbhip_seed_stereo_points_device(orbhip_matcher *m, int frames, const orbhip_camera *cam, const void *d_Tcw, const void *d_kps,
+                                     const void *d_n, int cap, int kp_first, int kp_step, const void *d_depth, float th_depth,
+                                     int mode, int created_flags, void *d_world, void *d_flags, void *d_order, void *d_created,
+                                     void *d_counts)
+{
+    if (!m || frames < 0 || cap < 1 || !seed_args_ok(cam, mode, created_flags) || !d_Tcw || !d_kps || !d_n || !d_depth ||
+        !d_world || !d_flags || !d_counts || kp_first < 0 || kp_step < 0)
+        return ORBHIP_E_ARG;
+    if (cap > kSeedMax) { set_error("seed_stereo_points: capacity %d exceeds %d", cap, kSeedMax); return ORBHIP_E_CAPACITY; }
+    if (frames == 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const SeedBatch B = {(const float *)d_Tcw, (const orbhip_keypoint *)d_kps, (const int *)d_n, (const float *)d_depth,
+                         (float *)d_world, (uint8_t *)d_flags, (int *)d_order, (uint8_t *)d_created, (int *)d_counts,
+                         cap, kp_first, kp_step};
+    hipLaunchKernelGGL(k_seed_stereo_points, dim3(1, frames), dim3(1024), 0, m->stream, B, cam->fx, cam->fy, cam->cx, cam->cy,
+                       th_depth, mode, created_flags);
+    ORBHIP_HIP_CHECK(hipGetLastError());
+    return ORBHIP_OK;
+}
+
+int orbhip_seed_stereo_points(orbhip_matcher *m, const orbhip_camera *cam, const float *Tcw, const orbhip_keypoint *keys,
+                              const float *depth, int n, float th_depth, int mode, int created_flags, float *world,
+                              uint8_t *flags, int32_t *order, uint8_t *created, int32_t *counts)
+{
+    if (!m || !seed_args_ok(cam, mode, created_flags) || !Tcw || !counts || n < 0 ||
+        (n > 0 && (!keys || !depth || !world || !flags)))
+        return ORBHIP_E_ARG;
+    if (n > kSeedMax) { set_error("seed_stereo_points: %d keypoints exceed %d", n, kSeedMax); return ORBHIP_E_CAPACITY; }
+    counts[0] = counts[1] = counts[2] = 0;
+    if (n == 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    // inputs in one copy; world | flags are staged last and order | created | counts follow them in the same device
+    // buffer, so that everything the call returns comes back in one copy as well
+    const size_t kb = al256((size_t)n * sizeof(orbhip_keypoint)), fb = al256((size_t)n * sizeof(float)), wb = al256((size_t)n * 12),
+                 bb = al256((size_t)n), ob = wb + bb + fb + bb + 256;
+    Stage st;
+    int rc;
+    if ((rc = stage_begin(m, 256 + 256 + kb + fb + ob, &st))) return rc;
+    const float *dT = st.put(Tcw, 12);
+    const int *dN = st.put(&n, 1);
+    const orbhip_keypoint *dK = st.put(keys, (size_t)n);
+    const float *dZ = st.put(depth, (size_t)n);
+    const float *dW = st.put(world, (size_t)n * 3);
+    const uint8_t *dF = st.put(flags, (size_t)n);
+    if ((rc = stage_commit(m, &st))) return rc;
+    uint8_t *d_out = const_cast<uint8_t *>(reinterpret_cast<const uint8_t *>(dW));
+    int *d_order = reinterpret_cast<int *>(d_out + wb + bb);
+    uint8_t *d_created = d_out + wb + bb + fb;
+    int *d_counts = reinterpret_cast<int *>(d_out + wb + bb + fb + bb);
+    if ((rc = orbhip_seed_stereo_points_device(m, 1, cam, dT, dK, dN, n, 0, 0, dZ, th_depth, mode, created_flags, d_out,
+                                               const_cast<uint8_t *>(dF), d_order, d_created, d_counts))) return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, d_out, ob - 256 + 3 * sizeof(int), &h))) return rc;
+    memcpy(world, h, (size_t)n * 12);
+    memcpy(flags, h + wb, (size_t)n);
+    memcpy(counts, h + wb + bb + fb + bb, 3 * sizeof(int));
+    if (order) memcpy(order, h + wb + bb, (size_t)counts[1] * sizeof(int));
+    if (created) memcpy(created, h + wb + bb + fb, (size_t)n);
+    return ORBHIP_OK;
+}
+
+int orbhip_count_close_points_device(orbhip_matcher *m, int frames, const void *d_depth, const void *d_flags, const void *d_n,
+                                     int cap, float th_depth, void *d_counts)
+{
+    if (!m || frames < 0 || cap < 1 || !d_depth || !d_flags || !d_n || !d_counts) return ORBHIP_E_ARG;
+    if (frames == 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    hipLaunchKernelGGL(k_count_close_points, dim3(frames), dim3(256), 0, m->stream, (const float *)d_depth, (const uint8_t *)d_flags,
+                       (const int *)d_n, cap, th_depth, (int *)d_counts);
+    ORBHIP_HIP_CHECK(hipGetLastError());
+    return ORBHIP_OK;
+}
+
+int orbhip_count_close_points(orbhip_matcher *m, const float *depth, const uint8_t *flags, int n, float th_depth, int *tracked,
+                              int *non_tracked)
+{
+    if (!m || n < 0 || (n > 0 && (!depth || !flags)) || !tracked || !non_tracked) return ORBHIP_E_ARG;
+    *tracked = *non_tracked = 0;
+    if (n == 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    Stage st;
+    int rc;
+    if ((rc = stage_begin(m, al256((size_t)n * sizeof(float)) + al256((size_t)n) + 256, &st))) return rc;
+    const float *dZ = st.put(depth, (size_t)n);
+    const uint8_t *dF = st.put(flags, (size_t)n);
+    const int *dN = st.put(&n, 1);
+    if ((rc = stage_commit(m, &st))) return rc;
+    void *p;
+    if ((rc = scratch(m, S_OUT, 2 * sizeof(int), &p))) return rc;
+    if ((rc = orbhip_count_close_points_device(m, 1, dZ, dF, dN, n, th_depth, p))) return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, p, 2 * sizeof(int), &h))) return rc;
+    *tracked = reinterpret_cast<const int *>(h)[0];
+    *non_tracked = reinterpret_cast<const int *>(h)[1];
     return ORBHIP_OK;
 }
 

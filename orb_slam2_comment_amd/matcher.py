@@ -281,6 +281,55 @@ class ORBmatcher:
                                                                    d_depth_out),
               "orbhip_compute_stereo_from_rgbd_raw_device")
 
+    # -- seeding stereo / RGB-D map points (src/Tracking.cc:523-538, 812-864, 1073-1133; src/Frame.cc:666-680) --------
+    def SeedStereoPoints(self, cam, Tcw, keys_un, depth, th_depth, mode, created_flags, world, flags):
+        """The depth-sorted map-point creation of Tracking::UpdateLastFrame / CreateNewKeyFrame (mode capi.SEED_CLOSEST)
+        or the one of StereoInitialization (capi.SEED_ALL) with Frame::UnprojectStereo.  flags [n] uint8: POINT_PRESENT =
+        the slot has a map point, POINT_OBSERVED = it has observations; world [n,3] = their positions.  Returns
+        (world, flags, order, created, (n_valid, n_visited, n_created)): copies of world / flags with the created entries
+        filled in, the visited keypoint indices in visiting order, and a 0 / 1 mark per keypoint."""
+        Tc = np.ascontiguousarray(np.asarray(Tcw, np.float32)[:3, :4])
+        k = np.ascontiguousarray(keys_un, KP_DTYPE)
+        n = len(k)
+        z = np.ascontiguousarray(depth, np.float32)
+        w = np.array(world, np.float32, order="C").reshape(-1, 3)
+        fg = np.array(flags, np.uint8, order="C")
+        if len(z) != n or len(w) != n or len(fg) != n:
+            raise ValueError("depth, world and flags must have one entry per keypoint")
+        order = np.full(max(n, 1), -1, np.int32)
+        created = np.zeros(max(n, 1), np.uint8)
+        counts = np.zeros(3, np.int32)
+        check(self._lib.orbhip_seed_stereo_points(self._h, C.byref(cam), ptr(Tc), ptr(k), ptr(z), n, float(np.float32(th_depth)),
+                                                  int(mode), int(created_flags), ptr(w), ptr(fg), ptr(order), ptr(created),
+                                                  ptr(counts)), "orbhip_seed_stereo_points")
+        return w, fg, order[:counts[1]].copy(), created[:n].copy(), tuple(int(c) for c in counts)
+
+    def SeedStereoPointsDevice(self, frames, cam, d_Tcw, d_kps, d_n, cap, kp_first, kp_step, d_depth, th_depth, mode,
+                               created_flags, d_world, d_flags, d_counts, d_order=0, d_created=0):
+        """Batched, device-resident form (device pointers as ints): d_world / d_flags are updated in place, ready for
+        TrackLastFrameDevice.  Asynchronous on the matcher's stream."""
+        check(self._lib.orbhip_seed_stereo_points_device(self._h, frames, C.byref(cam), d_Tcw, d_kps, d_n, cap, kp_first,
+                                                         kp_step, d_depth, float(np.float32(th_depth)), int(mode),
+                                                         int(created_flags), d_world, d_flags, d_order, d_created, d_counts),
+              "orbhip_seed_stereo_points_device")
+
+    def CountClosePoints(self, depth, flags, th_depth):
+        """Tracking::NeedNewKeyFrame's (nTrackedClose, nNonTrackedClose) (src/Tracking.cc:1001-1018); here POINT_PRESENT
+        means mvpMapPoints[i] && !mvbOutlier[i]."""
+        z = np.ascontiguousarray(depth, np.float32)
+        fg = np.ascontiguousarray(flags, np.uint8)
+        if len(z) != len(fg):
+            raise ValueError("depth and flags must have one entry per keypoint")
+        a, b = C.c_int(), C.c_int()
+        check(self._lib.orbhip_count_close_points(self._h, ptr(z), ptr(fg), len(z), float(np.float32(th_depth)), C.byref(a),
+                                                  C.byref(b)), "orbhip_count_close_points")
+        return a.value, b.value
+
+    def CountClosePointsDevice(self, frames, d_depth, d_flags, d_n, cap, th_depth, d_counts):
+        check(self._lib.orbhip_count_close_points_device(self._h, frames, d_depth, d_flags, d_n, cap,
+                                                         float(np.float32(th_depth)), d_counts),
+              "orbhip_count_close_points_device")
+
     # -- device-resident, batched SearchByProjection ---------------------------
     def set_stream(self, stream):
         check(self._lib.orbhip_matcher_set_stream(self._h, stream), "orbhip_matcher_set_stream")
@@ -439,6 +488,41 @@ class ORBmatcher:
                                                       len(kr), mbf, mb, ptr(ur), ptr(dp), C.byref(n)),
               "orbhip_compute_stereo_matches")
         return n.value, ur[:len(kl)].copy(), dp[:len(kl)].copy()
+
+
+class SeedReplay:
+    """The --seed option of the replay tools: what Tracking does with mvDepth when no pose estimation runs (identity pose).
+    The first frame with N > 500 is Tracking::StereoInitialization (src/Tracking.cc:509-540): mode SEED_ALL and the
+    reference's line "New map created with <n> points"; every later frame is the depth-sorted creation loop of
+    UpdateLastFrame / CreateNewKeyFrame (:812-864, :1073-1133) on a frame without map points: mode SEED_CLOSEST, empty flags.
+    summary() is the line the tools print at the end."""
+
+    def __init__(self, matcher, settings):
+        from .settings import th_depth
+        self.matcher = matcher
+        fx, fy, cx, cy = (float(settings["Camera." + k]) for k in ("fx", "fy", "cx", "cy"))
+        self.cam = make_camera(fx, fy, cx, cy, (0.0, 0.0, 1.0, 1.0), [1.0], mbf=float(settings["Camera.bf"]))
+        self.th_depth = th_depth(settings)
+        self.Tcw = np.eye(4, dtype=np.float32)
+        self.initialised = False
+        self.close = []
+
+    def frame(self, keys_un, depth):
+        n = len(keys_un)
+        world, flags = np.zeros((n, 3), np.float32), np.zeros(n, np.uint8)
+        if not self.initialised:
+            if n > 500:                                                  # src/Tracking.cc:511
+                counts = self.matcher.SeedStereoPoints(self.cam, self.Tcw, keys_un, depth, self.th_depth, capi.SEED_ALL,
+                                                       capi.POINT_PRESENT | capi.POINT_OBSERVED, world, flags)[4]
+                print("New map created with %d points" % counts[2])
+                self.initialised = True
+            return
+        counts = self.matcher.SeedStereoPoints(self.cam, self.Tcw, keys_un, depth, self.th_depth, capi.SEED_CLOSEST,
+                                               capi.POINT_PRESENT, world, flags)[4]
+        self.close.append(counts[2])
+
+    def summary(self):
+        return "mean close points per frame: %.2f" % (sum(self.close) / len(self.close) if self.close else 0.0)
 
 
 def RadiusByViewingCos(viewCos):

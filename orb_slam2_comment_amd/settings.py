@@ -230,6 +230,14 @@ def depth_map_factor(settings):
     return np.float32(1.0) / f
 
 
+def th_depth(settings):
+    """mThDepth as the Tracking constructor evaluates it for a stereo / RGB-D sensor (src/Tracking.cc:134-138), a float32:
+    mbf * (float)ThDepth / fx with mbf = Camera.bf and fx = Camera.fx read as floats, the product first.  A monocular
+    settings file has neither Camera.bf nor ThDepth: KeyError."""
+    mbf, fx = np.float32(settings["Camera.bf"]), np.float32(settings["Camera.fx"])
+    return np.float32(np.float32(mbf * np.float32(settings["ThDepth"])) / fx)
+
+
 def load_tum_association(path):
     """LoadImages of Examples/RGB-D/rgbd_tum.cc:142-167: lines `t rgb_file t depth_file`, empty lines skipped.
     Returns (rgb filenames, depth filenames, timestamps)."""

@@ -20,6 +20,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from orb_slam2_comment_amd import ORBmatcher, init_undistort_rectify_map  # noqa: E402
+from orb_slam2_comment_amd.matcher import SeedReplay  # noqa: E402
 from orb_slam2_comment_amd.settings import (STEREO, load_euroc_sequence, load_settings, make_extractors, read_gray_image,  # noqa: E402
                                             stereo_rectification)
 
@@ -31,6 +32,8 @@ def main():
     ap.add_argument("right_dir")
     ap.add_argument("times")
     ap.add_argument("--max-frames", type=int, default=0)
+    ap.add_argument("--seed", action="store_true", help="seed map points from the depths (StereoInitialization, "
+                                                        "src/Tracking.cc:509-540, then the closest-points rule, :812-864)")
     args = ap.parse_args()
     left, right, stamps = load_euroc_sequence(args.left_dir, args.right_dir, args.times)
     if not left:
@@ -53,6 +56,7 @@ def main():
     matcher = ORBmatcher(0.9, True)
     mbf = np.float32(st["Camera.bf"])
     mb = np.float32(mbf / np.float32(st["Camera.fx"]))                   # src/Frame.cc:114
+    seeder = SeedReplay(matcher, st) if args.seed else None
     times, counts, matches = [], [], []
     for ni in range(len(left)):
         iml, imr = read_gray_image(left[ni]), read_gray_image(right[ni])
@@ -62,7 +66,9 @@ def main():
         t1 = time.perf_counter()
         kl, dl = ex["left"].extract_remap(iml)
         kr, dr = ex["right"].extract_remap(imr)
-        n, _, _ = matcher.ComputeStereoMatches(ex["left"], ex["right"], kl, dl, kr, dr, float(mbf), float(mb))
+        n, _, depth = matcher.ComputeStereoMatches(ex["left"], ex["right"], kl, dl, kr, dr, float(mbf), float(mb))
+        if seeder is not None:
+            seeder.frame(kl, depth)
         times.append(time.perf_counter() - t1)
         counts.append(len(kl))
         matches.append(n)
@@ -73,6 +79,8 @@ def main():
     print("mean tracking time: %.6f" % (sum(times) / n))
     print("mean keypoints: %.2f" % (sum(counts) / n))
     print("mean stereo matches: %.2f" % (sum(matches) / n))
+    if seeder is not None:
+        print(seeder.summary())
     return 0
 
 

@@ -12,7 +12,12 @@ runs them on two threads, src/Frame.cc:78-81) and Frame::ComputeStereoMatches (C
 file, src/Tracking.cc:86 and src/Frame.cc:108-112); --match then tracks with the stereo window th = 7
 (src/Tracking.cc:880) and the stereo consistency gate.
 
-  python tools/replay_kitti.py path/to/KITTI00-02.yaml path/to/sequence [--max-frames N] [--match] [--stereo]
+With --stereo --seed the depths of every pair also go through the map-point seeding of Tracking (orbhip_seed_stereo_points
+with the identity pose): the first frame with more than 500 keypoints is StereoInitialization (src/Tracking.cc:509-540, its
+line "New map created with <n> points" is printed), every later frame the closest-points rule of UpdateLastFrame /
+CreateNewKeyFrame (:812-864, :1073-1133, ThDepth of the settings file); the mean number of points created is printed last.
+
+  python tools/replay_kitti.py path/to/KITTI00-02.yaml path/to/sequence [--max-frames N] [--match] [--stereo [--seed]]
 """
 import argparse
 import os
@@ -24,6 +29,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from orb_slam2_comment_amd import FrameView, ORBmatcher, QUERY_DTYPE  # noqa: E402
+from orb_slam2_comment_amd.matcher import SeedReplay  # noqa: E402
 from orb_slam2_comment_amd.settings import (MONOCULAR, STEREO, load_kitti_sequence, load_settings, make_extractors,  # noqa: E402
                                             read_gray_image)
 
@@ -35,6 +41,8 @@ def main():
     ap.add_argument("--max-frames", type=int, default=0)
     ap.add_argument("--match", action="store_true")
     ap.add_argument("--stereo", action="store_true", help="stereo_kitti.cc: image_0 / image_1 pairs + ComputeStereoMatches")
+    ap.add_argument("--seed", action="store_true", help="with --stereo: seed map points from the depths (StereoInitialization, "
+                                                        "then the closest-points rule)")
     args = ap.parse_args()
     st = load_settings(args.settings)
     names, stamps = load_kitti_sequence(args.sequence)
@@ -89,6 +97,7 @@ def stereo(args, st, names_left, stamps):
     fx, bf = float(st["Camera.fx"]), float(st["Camera.bf"])       # mbf = Camera.bf; mb = mbf / fx (src/Frame.cc:112)
     print("Images in the sequence: %d" % len(names_left))
     matcher = ORBmatcher(0.9, True)
+    seeder = SeedReplay(matcher, st) if args.seed else None
     times, counts, stereo_counts, matches = [], [], [], []
     last = None
     for ni, (nl, nr) in enumerate(zip(names_left, names_right)):
@@ -113,6 +122,8 @@ def stereo(args, st, names_left, stamps):
             q["min_level"] = lk["octave"] - 1; q["max_level"] = lk["octave"] + 1; q["angle"] = lk["angle"]; q["observed"] = 1
             q["ur"] = np.where(lur > 0, lur, lk["x"])      # identity motion: the point keeps its right-image coordinate
             matches.append(matcher.SearchByProjectionFrame(cur, q, ld)[0])
+        if seeder is not None:
+            seeder.frame(kl, depth)
         times.append(time.perf_counter() - t1)
         counts.append(len(kl)); stereo_counts.append(ns)
         last = (kl, dl, ur)
@@ -125,6 +136,8 @@ def stereo(args, st, names_left, stamps):
     print("mean stereo matches per pair: %.1f" % (sum(stereo_counts) / n))
     if matches:
         print("mean matches to the previous frame: %.1f" % (sum(matches) / len(matches)))
+    if seeder is not None:
+        print(seeder.summary())
     return 0
 
 

@@ -24,6 +24,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from orb_slam2_comment_amd import ORBmatcher  # noqa: E402
+from orb_slam2_comment_amd.matcher import SeedReplay  # noqa: E402
 from orb_slam2_comment_amd.settings import (MONOCULAR, RGBD, camera_rgb, depth_map_factor, load_settings, load_tum_association,  # noqa: E402
                                             load_tum_rgb_list, make_extractors, read_color_image, read_depth_image)
 
@@ -38,6 +39,8 @@ def main():
     ap.add_argument("sequence")
     ap.add_argument("association", nargs="?")
     ap.add_argument("--max-frames", type=int, default=0)
+    ap.add_argument("--seed", action="store_true", help="RGB-D: seed map points from the depths (StereoInitialization, "
+                                                        "src/Tracking.cc:509-540, then the closest-points rule, :812-864)")
     args = ap.parse_args()
     st = load_settings(args.settings)
     if args.association:
@@ -56,6 +59,7 @@ def main():
     cam = [float(st["Camera." + k]) for k in ("fx", "fy", "cx", "cy")]
     dist = [float(st.get("Camera." + k, 0.0)) for k in ("k1", "k2", "p1", "p2", "k3")]
     factor, mbf, rgb = depth_map_factor(st), float(st.get("Camera.bf", 0.0)), camera_rgb(st)
+    seeder = SeedReplay(matcher, st) if args.seed and depths is not None else None
     times, counts, with_depth = [], [], []
     for ni, name in enumerate(names):
         im = read_color_image(os.path.join(args.sequence, name))
@@ -69,6 +73,8 @@ def main():
             kun = matcher.UndistortKeyPoints(kps, cam[0], cam[1], cam[2], cam[3], dist)
             _, dp = matcher.ComputeStereoFromRGBDRaw(kps, kun, imd, factor, mbf)
             with_depth.append(int((dp > 0).sum()))
+            if seeder is not None:
+                seeder.frame(kun, dp)
         else:
             kps, _ = extract(ex["ini"] if ni == 0 else ex["left"], im, rgb)
         times.append(time.perf_counter() - t1)
@@ -81,6 +87,8 @@ def main():
     print("mean keypoints: %.2f" % (sum(counts) / n))
     if with_depth:
         print("mean keypoints with depth: %.2f" % (sum(with_depth) / n))
+    if seeder is not None:
+        print(seeder.summary())
     return 0
 
 
