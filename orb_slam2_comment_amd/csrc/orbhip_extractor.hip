@@ -955,6 +955,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORBHIP_FAST_
 // list order (new children reversed in front, survivors behind) and relabels keys.
 // ---------------------------------------------------------------------------
 constexpr int kOctU = 4;            // independent keys per thread in the key loops
+constexpr int kOctR = 8;           // keys a thread can keep in registers: kOctR / kOctU groups of kOctU
+static_assert(kOctR % kOctU == 0 && kOctR % 2 == 0, "whole groups, labels packed in pairs");
+// A (level, frame) with at most T * kOctR candidates (4,096 at 512 threads; the KITTI-shape frames of the benchmark have
+// 2,872 .. 3,376 on level 0) keeps them in registers: thread t owns keys k = u * T + t and their node labels (u16, two
+// per dword) for the whole kernel, every loop over them is fully unrolled so that the arrays never leave the VGPRs, and
+// a group of kOctU keys that lies wholly past K is skipped by a scalar branch.  What follows is for the others.
 // The candidate keys and their owning nodes live in the HBM workspace (L2-resident while a workgroup works on them), not
 // in LDS: with them the workgroup needed 70 KB and two fitted a CU; at 34 KB four do, which is what hides the latencies
 // of this kernel -- 170 frames alone 98 -> 84 us, three pipelines 278.8 -> 283.4 k frames/s; a single frame and a
@@ -973,18 +979,116 @@ struct OctShared {
     int vars[8];
 };
 
-template <int MAXN, int T>
+// node label of register key u (u is a constant after unrolling)
+__device__ __forceinline__ int oct_nd(const uint32_t (&p)[kOctR / 2], const int u)
+{
+    return (u & 1) ? (int)(p[u >> 1] >> 16) : (int)(p[u >> 1] & 0xffffu);
+}
+__device__ __forceinline__ void oct_nd_set(uint32_t (&p)[kOctR / 2], const int u, const int v)
+{
+    p[u >> 1] = (u & 1) ? (p[u >> 1] & 0xffffu) | ((uint32_t)v << 16) : (p[u >> 1] & 0xffff0000u) | ((uint32_t)v & 0xffffu);
+}
+
+// Register-resident keys: the one loop over the keys that a pass needs.  Every key is relabelled from what the node-table
+// wavefront has just published (FIRST: the initial nodes, where labels only shift when an initial node was empty;
+// otherwise survivors through nmap, keys of a split node through the child slot in CC) and, with `count`, filed at once
+// under the child it falls into for the NEXT pass against the new table `tb`, into the counter buffer CN the table
+// wavefront has cleared.  Relabel of pass p and count of pass p + 1 touch the same key of the same thread and need no
+// barrier between them, so they are one sweep.
+template <int MAXN, int T, bool FIRST>
+__device__ __forceinline__ void oct_sweep(OctShared<MAXN> &S, const uint32_t (&kv)[kOctR], uint32_t (&ndp)[kOctR / 2],
+                                          const int K, const int tid, const int cur, const int tb, const int *CC, int *CN,
+                                          const bool remap, const bool count)
+{
+#pragma unroll
+    for (int g = 0; g < kOctR / kOctU; ++g) {
+        if (g * kOctU * T < K) {
+            int nd[kOctU];
+#pragma unroll
+            for (int u = 0; u < kOctU; ++u) nd[u] = oct_nd(ndp, g * kOctU + u);
+            if constexpr (FIRST) {
+                if (remap) {
+#pragma unroll
+                    for (int u = 0; u < kOctU; ++u) nd[u] = S.nmap[nd[u]];
+                }
+            } else {
+                int mp[kOctU], bx0[kOctU], bx1[kOctU], by0[kOctU], by1[kOctU];
+#pragma unroll
+                for (int u = 0; u < kOctU; ++u) mp[u] = S.nmap[nd[u]];
+#pragma unroll
+                for (int u = 0; u < kOctU; ++u) {
+                    bx0[u] = S.x0[cur][nd[u]]; bx1[u] = S.x1[cur][nd[u]];
+                    by0[u] = S.y0[cur][nd[u]]; by1[u] = S.y1[cur][nd[u]];
+                }
+#pragma unroll
+                for (int u = 0; u < kOctU; ++u) {
+                    if (mp[u] & 0x40000000) {
+                        const uint32_t v = kv[g * kOctU + u];
+                        const int x = v & 0xfff, y = (v >> 12) & 0xfff;
+                        const int mx = bx0[u] + ((bx1[u] - bx0[u] + 1) >> 1), my = by0[u] + ((by1[u] - by0[u] + 1) >> 1);
+                        nd[u] = CC[4 * nd[u] + (x < mx ? 0 : 1) + (y < my ? 0 : 2)];
+                    } else {
+                        nd[u] = mp[u];
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kOctU; ++u) {
+                if ((g * kOctU + u) * T + tid >= K) nd[u] = 0;    // slots past K keep a label that is always a valid index
+                oct_nd_set(ndp, g * kOctU + u, nd[u]);
+            }
+            if (count) {
+                int cn[kOctU], bx0[kOctU], bx1[kOctU], by0[kOctU], by1[kOctU];
+#pragma unroll
+                for (int u = 0; u < kOctU; ++u) cn[u] = S.cnt[tb][nd[u]];
+#pragma unroll
+                for (int u = 0; u < kOctU; ++u) {
+                    bx0[u] = S.x0[tb][nd[u]]; bx1[u] = S.x1[tb][nd[u]];
+                    by0[u] = S.y0[tb][nd[u]]; by1[u] = S.y1[tb][nd[u]];
+                }
+#pragma unroll
+                for (int u = 0; u < kOctU; ++u) {
+                    if ((g * kOctU + u) * T + tid < K && cn[u] > 1) {
+                        const uint32_t v = kv[g * kOctU + u];
+                        const int x = v & 0xfff, y = (v >> 12) & 0xfff;
+                        const int mx = bx0[u] + ((bx1[u] - bx0[u] + 1) >> 1), my = by0[u] + ((by1[u] - by0[u] + 1) >> 1);
+                        atomicAdd(&CN[4 * nd[u] + (x < mx ? 0 : 1) + (y < my ? 0 : 2)], 1);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Diagnostic build only (STAMPS = true is instantiated under -DORBHIP_DEVTOOLS alone): per-phase s_memtime sums of
+// thread 0 of the level-0 workgroups (it sits in the wavefront that does the node-table work, and every phase ends at a
+// barrier, so its stamps are the workgroup's), read by tools/octree_ab.py through orbhip_dev_octree_stamps.
+#ifdef ORBHIP_DEVTOOLS
+__device__ unsigned long long g_oct_stamps[16];
+#endif
+
+// REG: the keys and their labels live in this thread's registers (K <= T * kOctR); otherwise in gkeys / gnode.
+template <int MAXN, int T, bool REG, bool STAMPS>
 __device__ __forceinline__ void octree_body(OctShared<MAXN> &S, const PyrGeom &G, const LevelGeom &L,
                                             const int level, const int b, const int K,
                                             const int *__restrict__ ccnt_in, const uint32_t *__restrict__ ckp_in,
                                             uint32_t *__restrict__ gkeys, unsigned short *__restrict__ gnode,
                                             uint32_t *__restrict__ sel_kp, int *__restrict__ sel_cnt,
-                                            int *__restrict__ frame_status)
+                                            int *__restrict__ frame_status, unsigned long long tprev)
 {
 #define keys(k) gkeys[k]        // candidate keys (x | y<<12 | score<<24)
 #define knode(k) gnode[k]      // owning node of each key
+    unsigned long long tacc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    [[maybe_unused]] int npass = 0;
+#define OCT_STAMP(i) do { if constexpr (STAMPS) { const unsigned long long t_ = stamp_now(); tacc[i] += t_ - tprev; tprev = t_; } } while (0)
+    OCT_STAMP(0);   // cell-offset scan of the caller
     const int tid = threadIdx.x;
     const int N = L.quota;
+    uint32_t rkey[kOctR], rlab[kOctR / 2];  // REG: this thread's keys and their labels
+#pragma unroll
+    for (int u = 0; u < kOctR; ++u) rkey[u] = 0;
+#pragma unroll
+    for (int u = 0; u < kOctR / 2; ++u) rlab[u] = 0;
     // ---- initial nodes (:543-585); their key counters live in counter buffer 1 (buffer 0 holds the cell offsets) ----
     const int nIni = L.nIni;
     const int height = L.maxBY - 16;
@@ -1001,8 +1105,7 @@ __device__ __forceinline__ void octree_body(OctShared<MAXN> &S, const PyrGeom &G
     // binary search over the exclusive offsets, loads stay independent) and, in the same pass, file every key under
     // its initial node; with a handful of initial nodes all keys would hammer the same few LDS counters, so a
     // wavefront adds its keys up with ballots first
-    for (int k0 = 0; k0 < K; k0 += T * 4) {
-        uint32_t v[4];
+    auto gather4 = [&](const int k0, uint32_t (&v)[4], int (&bin)[4]) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int k = k0 + u * T + tid;
@@ -1020,20 +1123,47 @@ __device__ __forceinline__ void octree_body(OctShared<MAXN> &S, const PyrGeom &G
         for (int u = 0; u < 4; ++u) {
             const int k = k0 + u * T + tid;
             const bool ok = k < K;
-            const int bin = min((int)__fdiv_rn((float)(v[u] & 0xfffu), L.hX), nIni - 1);
-            if (ok) { keys(k) = v[u]; knode(k) = (unsigned short)bin; }
+            bin[u] = min((int)__fdiv_rn((float)(v[u] & 0xfffu), L.hX), nIni - 1);
             if (nIni <= 4) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const unsigned long long mk = __ballot(ok && bin == j);
+                    const unsigned long long mk = __ballot(ok && bin[u] == j);
                     if ((tid & 63) == 0 && mk) atomicAdd(&RC[j], __popcll(mk));
                 }
             } else if (ok) {
-                atomicAdd(&RC[bin], 1);
+                atomicAdd(&RC[bin[u]], 1);
+            }
+        }
+    };
+    if constexpr (REG) {
+        static_assert(kOctU == 4, "the gather works in groups of four");
+#pragma unroll
+        for (int g = 0; g < kOctR / 4; ++g) {
+            if (g * 4 * T < K) {
+                uint32_t v[4];
+                int bin[4];
+                gather4(g * 4 * T, v, bin);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    rkey[g * 4 + u] = v[u];
+                    oct_nd_set(rlab, g * 4 + u, (g * 4 + u) * T + tid < K ? bin[u] : 0);
+                }
+            }
+        }
+    } else {
+        for (int k0 = 0; k0 < K; k0 += T * 4) {
+            uint32_t v[4];
+            int bin[4];
+            gather4(k0, v, bin);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int k = k0 + u * T + tid;
+                if (k < K) { keys(k) = v[u]; knode(k) = (unsigned short)bin[u]; }
             }
         }
     }
     __syncthreads();
+    OCT_STAMP(1);   // gather
     // one wavefront drops the empty initial nodes (order kept) and clears the first pass's child counters
     if (tid < 64) {
         const int lane = tid;
@@ -1060,7 +1190,11 @@ __device__ __forceinline__ void octree_body(OctShared<MAXN> &S, const PyrGeom &G
     }
     __syncthreads();
     int n = S.vars[0];  // list size
-    if (n != nIni) {    // some initial node was empty: the keys' node labels shift
+    OCT_STAMP(2);   // initial node table
+    if constexpr (REG) {
+        // the label shift of an empty initial node and the first pass's count in one sweep
+        oct_sweep<MAXN, T, true>(S, rkey, rlab, K, tid, 0, 1, nullptr, S.ccnt[0], n != nIni, true);
+    } else if (n != nIni) {    // some initial node was empty: the keys' node labels shift
         for (int k0 = 0; k0 < K; k0 += T * kOctU) {
             int nd[kOctU];
 #pragma unroll
@@ -1071,6 +1205,7 @@ __device__ __forceinline__ void octree_body(OctShared<MAXN> &S, const PyrGeom &G
             for (int u = 0; u < kOctU; ++u) { const int k = k0 + u * T + tid; if (k < K) knode(k) = (unsigned short)nd[u]; }
         }
     }
+    OCT_STAMP(3);   // label shift (register keys: and the first pass's count)
     int cur = 1;
     int phase = 1;
     bool finish = (K == 0);
@@ -1082,39 +1217,45 @@ __device__ __forceinline__ void octree_body(OctShared<MAXN> &S, const PyrGeom &G
     // at most; doing its scans with the whole workgroup cost 15 barriers and 8 wavefronts' worth of instructions per
     // pass on a CU whose issue slots the workgroup shares with another level's, so one wavefront does it with
     // wave-level scans (a lane owns `per` consecutive nodes) while the others wait at the barrier.
+    // With the keys in registers the relabelling of one pass and the counting of the next are one loop (oct_sweep), so a
+    // pass is barrier -> table -> barrier -> sweep, and the keys are touched once per pass.
     while (!finish) {
         const int prevSize = n;
         int *CC = S.ccnt[cb];
         // B: count children of expandable nodes (DivideNode :481-526)
-        for (int k0 = 0; k0 < K; k0 += T * kOctU) {
-            // kOctU independent keys per thread: the LDS round trips of the chains overlap
-            int nd[kOctU], cn[kOctU];
-            uint32_t kv[kOctU];
+        // (register keys: the sweep after the previous table step has counted already)
+        if constexpr (!REG) {
+            for (int k0 = 0; k0 < K; k0 += T * kOctU) {
+                // kOctU independent keys per thread: the LDS round trips of the chains overlap
+                int nd[kOctU], cn[kOctU];
+                uint32_t kv[kOctU];
 #pragma unroll
-            for (int u = 0; u < kOctU; ++u) {
-                const int k = k0 + u * T + tid;
-                nd[u] = k < K ? (int)knode(k) : 0;
-                kv[u] = k < K ? keys(k) : 0u;
-            }
+                for (int u = 0; u < kOctU; ++u) {
+                    const int k = k0 + u * T + tid;
+                    nd[u] = k < K ? (int)knode(k) : 0;
+                    kv[u] = k < K ? keys(k) : 0u;
+                }
 #pragma unroll
-            for (int u = 0; u < kOctU; ++u) cn[u] = S.cnt[cur][nd[u]];
-            int bx0[kOctU], bx1[kOctU], by0[kOctU], by1[kOctU];
+                for (int u = 0; u < kOctU; ++u) cn[u] = S.cnt[cur][nd[u]];
+                int bx0[kOctU], bx1[kOctU], by0[kOctU], by1[kOctU];
 #pragma unroll
-            for (int u = 0; u < kOctU; ++u) {
-                bx0[u] = S.x0[cur][nd[u]]; bx1[u] = S.x1[cur][nd[u]];
-                by0[u] = S.y0[cur][nd[u]]; by1[u] = S.y1[cur][nd[u]];
-            }
+                for (int u = 0; u < kOctU; ++u) {
+                    bx0[u] = S.x0[cur][nd[u]]; bx1[u] = S.x1[cur][nd[u]];
+                    by0[u] = S.y0[cur][nd[u]]; by1[u] = S.y1[cur][nd[u]];
+                }
 #pragma unroll
-            for (int u = 0; u < kOctU; ++u) {
-                const int k = k0 + u * T + tid;
-                if (k < K && cn[u] > 1) {
-                    const int x = kv[u] & 0xfff, y = (kv[u] >> 12) & 0xfff;
-                    const int mx = bx0[u] + ((bx1[u] - bx0[u] + 1) >> 1), my = by0[u] + ((by1[u] - by0[u] + 1) >> 1);
-                    atomicAdd(&CC[4 * nd[u] + (x < mx ? 0 : 1) + (y < my ? 0 : 2)], 1);
+                for (int u = 0; u < kOctU; ++u) {
+                    const int k = k0 + u * T + tid;
+                    if (k < K && cn[u] > 1) {
+                        const int x = kv[u] & 0xfff, y = (kv[u] >> 12) & 0xfff;
+                        const int mx = bx0[u] + ((bx1[u] - bx0[u] + 1) >> 1), my = by0[u] + ((by1[u] - by0[u] + 1) >> 1);
+                        atomicAdd(&CC[4 * nd[u] + (x < mx ? 0 : 1) + (y < my ? 0 : 2)], 1);
+                    }
                 }
             }
         }
         __syncthreads();
+        OCT_STAMP(4);   // count (the wait for the slowest wavefront included)
         if (phase == 2) {
             // processing order of the careful phase: (size desc, list position asc) -- the reference sorts (size, node
             // address) ascending and walks from the back (:684-685); "newer node first" stands in for the address.
@@ -1135,6 +1276,7 @@ __device__ __forceinline__ void octree_body(OctShared<MAXN> &S, const PyrGeom &G
                 }
             }
             __syncthreads();
+            OCT_STAMP(5);   // processing order of the careful phase
         }
         const int nxt = cur ^ 1;
         if (tid < 64) {
@@ -1234,37 +1376,44 @@ __device__ __forceinline__ void octree_body(OctShared<MAXN> &S, const PyrGeom &G
             for (int i = lane; i < n_new * 4; i += 64) CN[i] = 0;
         }
         __syncthreads();
-        // F: relabel keys
-        for (int k0 = 0; k0 < K; k0 += T * kOctU) {
-            int nd[kOctU], mp[kOctU];
-            uint32_t kv[kOctU];
+        OCT_STAMP(6);   // node-table wavefront
+        ++npass;
+        // F: relabel keys (register keys: and count the next pass, unless this was the last)
+        if constexpr (REG) {
+            oct_sweep<MAXN, T, false>(S, rkey, rlab, K, tid, cur, nxt, CC, S.ccnt[cb ^ 1], false, S.vars[1] == 0);
+        } else {
+            for (int k0 = 0; k0 < K; k0 += T * kOctU) {
+                int nd[kOctU], mp[kOctU];
+                uint32_t kv[kOctU];
 #pragma unroll
-            for (int u = 0; u < kOctU; ++u) {
-                const int k = k0 + u * T + tid;
-                nd[u] = k < K ? (int)knode(k) : 0;
-                kv[u] = k < K ? keys(k) : 0u;
-            }
+                for (int u = 0; u < kOctU; ++u) {
+                    const int k = k0 + u * T + tid;
+                    nd[u] = k < K ? (int)knode(k) : 0;
+                    kv[u] = k < K ? keys(k) : 0u;
+                }
 #pragma unroll
-            for (int u = 0; u < kOctU; ++u) mp[u] = S.nmap[nd[u]];
-            int bx0[kOctU], bx1[kOctU], by0[kOctU], by1[kOctU];
+                for (int u = 0; u < kOctU; ++u) mp[u] = S.nmap[nd[u]];
+                int bx0[kOctU], bx1[kOctU], by0[kOctU], by1[kOctU];
 #pragma unroll
-            for (int u = 0; u < kOctU; ++u) {
-                bx0[u] = S.x0[cur][nd[u]]; bx1[u] = S.x1[cur][nd[u]];
-                by0[u] = S.y0[cur][nd[u]]; by1[u] = S.y1[cur][nd[u]];
-            }
+                for (int u = 0; u < kOctU; ++u) {
+                    bx0[u] = S.x0[cur][nd[u]]; bx1[u] = S.x1[cur][nd[u]];
+                    by0[u] = S.y0[cur][nd[u]]; by1[u] = S.y1[cur][nd[u]];
+                }
 #pragma unroll
-            for (int u = 0; u < kOctU; ++u) {
-                const int k = k0 + u * T + tid;
-                if (k >= K) continue;
-                if (mp[u] & 0x40000000) {
-                    const int x = kv[u] & 0xfff, y = (kv[u] >> 12) & 0xfff;
-                    const int mx = bx0[u] + ((bx1[u] - bx0[u] + 1) >> 1), my = by0[u] + ((by1[u] - by0[u] + 1) >> 1);
-                    knode(k) = (unsigned short)CC[4 * nd[u] + (x < mx ? 0 : 1) + (y < my ? 0 : 2)];
-                } else {
-                    knode(k) = (unsigned short)mp[u];
+                for (int u = 0; u < kOctU; ++u) {
+                    const int k = k0 + u * T + tid;
+                    if (k >= K) continue;
+                    if (mp[u] & 0x40000000) {
+                        const int x = kv[u] & 0xfff, y = (kv[u] >> 12) & 0xfff;
+                        const int mx = bx0[u] + ((bx1[u] - bx0[u] + 1) >> 1), my = by0[u] + ((by1[u] - by0[u] + 1) >> 1);
+                        knode(k) = (unsigned short)CC[4 * nd[u] + (x < mx ? 0 : 1) + (y < my ? 0 : 2)];
+                    } else {
+                        knode(k) = (unsigned short)mp[u];
+                    }
                 }
             }
         }
+        OCT_STAMP(7);   // relabel / fused sweep
         n = S.vars[0];
         finish = S.vars[1] != 0;
         phase = S.vars[2];
@@ -1279,42 +1428,88 @@ __device__ __forceinline__ void octree_body(OctShared<MAXN> &S, const PyrGeom &G
     unsigned int *best = reinterpret_cast<unsigned int *>(S.ccnt[0]);
     for (int i = tid; i < n; i += T) best[i] = 0;
     __syncthreads();
-    for (int k0 = 0; k0 < K; k0 += T * kOctU) {
-        int nd[kOctU];
-        uint32_t kv[kOctU];
-#pragma unroll
-        for (int u = 0; u < kOctU; ++u) {
-            const int k = k0 + u * T + tid;
-            nd[u] = k < K ? (int)knode(k) : 0;
-            kv[u] = k < K ? keys(k) : 0u;
-        }
-#pragma unroll
-        for (int u = 0; u < kOctU; ++u) {
-            const int k = k0 + u * T + tid;
-            if (k < K) atomicMax(&best[nd[u]], ((kv[u] >> 24) << 24) | (0xffffffu - (uint32_t)k));
-        }
-    }
-    __syncthreads();
     uint32_t *out = sel_kp + (size_t)b * G.kp_cap_total + L.kp_base;
     const int nout = min(n, L.kp_cap);
-    for (int i = tid; i < nout; i += T) out[i] = keys(0xffffffu - (best[i] & 0xffffffu));
+    if constexpr (REG) {
+        // the packed (score, ~k) values are distinct, so exactly one key equals its node's maximum: its owner writes it
+#pragma unroll
+        for (int g = 0; g < kOctR / kOctU; ++g) {
+            if (g * kOctU * T < K) {
+#pragma unroll
+                for (int u = 0; u < kOctU; ++u) {
+                    const int k = (g * kOctU + u) * T + tid;
+                    if (k < K) atomicMax(&best[oct_nd(rlab, g * kOctU + u)], ((rkey[g * kOctU + u] >> 24) << 24) | (0xffffffu - (uint32_t)k));
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int g = 0; g < kOctR / kOctU; ++g) {
+            if (g * kOctU * T < K) {
+                unsigned int bv[kOctU];
+#pragma unroll
+                for (int u = 0; u < kOctU; ++u) bv[u] = best[oct_nd(rlab, g * kOctU + u)];
+#pragma unroll
+                for (int u = 0; u < kOctU; ++u) {
+                    const int k = (g * kOctU + u) * T + tid, nd = oct_nd(rlab, g * kOctU + u);
+                    if (k < K && nd < nout && bv[u] == (((rkey[g * kOctU + u] >> 24) << 24) | (0xffffffu - (uint32_t)k)))
+                        out[nd] = rkey[g * kOctU + u];
+                }
+            }
+        }
+    } else {
+        for (int k0 = 0; k0 < K; k0 += T * kOctU) {
+            int nd[kOctU];
+            uint32_t kv[kOctU];
+#pragma unroll
+            for (int u = 0; u < kOctU; ++u) {
+                const int k = k0 + u * T + tid;
+                nd[u] = k < K ? (int)knode(k) : 0;
+                kv[u] = k < K ? keys(k) : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < kOctU; ++u) {
+                const int k = k0 + u * T + tid;
+                if (k < K) atomicMax(&best[nd[u]], ((kv[u] >> 24) << 24) | (0xffffffu - (uint32_t)k));
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < nout; i += T) out[i] = keys(0xffffffu - (best[i] & 0xffffffu));
+    }
     if (tid == 0) {
         sel_cnt[b * ORBHIP_MAX_LEVELS + level] = nout;
         if (n > L.kp_cap) atomicExch(&frame_status[b], ORBHIP_E_CAPACITY);
     }
+    OCT_STAMP(8);   // best key of every node
+#ifdef ORBHIP_DEVTOOLS
+    if constexpr (STAMPS) {
+        if (tid == 0 && level == 0) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) atomicAdd(&g_oct_stamps[i], tacc[i]);
+            atomicAdd(&g_oct_stamps[9], (unsigned long long)npass);
+            atomicAdd(&g_oct_stamps[10], 1ull);
+            atomicAdd(&g_oct_stamps[11], (unsigned long long)K);
+        }
+    }
+#endif
+#undef OCT_STAMP
 #undef keys
 #undef knode
 }
 
-template <int MAXN, int T>
-__global__ __launch_bounds__(T) void k_octree(PyrGeom G, const int *__restrict__ cell_cnt,
+// 34 KB of LDS admit four workgroups per CU; at 512 threads those are 8 wavefronts per SIMD, i.e. 64 VGPRs each
+template <int MAXN, int T, bool STAMPS = false>
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MAXN == 512 && T == 512 ? 8 : 1))) void k_octree(PyrGeom G, const int *__restrict__ cell_cnt,
                                                 const uint32_t *__restrict__ cell_kp,
                                                 uint32_t *__restrict__ keys_ws,
                                                 unsigned short *__restrict__ node_ws,
                                                 uint32_t *__restrict__ sel_kp,
-                                                int *__restrict__ sel_cnt, int *__restrict__ frame_status)
+                                                int *__restrict__ sel_cnt, int *__restrict__ frame_status,
+                                                const int reg_cap)   // most keys the register path takes: T * kOctR
 {
     __shared__ OctShared<MAXN> S;
+    unsigned long long t0 = 0;
+    if constexpr (STAMPS) t0 = stamp_now();
     int level, b;
     xcd_remap(level, b);
     const int tid = threadIdx.x;
@@ -1333,7 +1528,11 @@ __global__ __launch_bounds__(T) void k_octree(PyrGeom G, const int *__restrict__
         if (c < L.ncells) S.ccnt[0][c] = K + base;  // ncells <= MAXN*4 checked on the host
         K += tot;
     }
-    octree_body<MAXN, T>(S, G, L, level, b, K, ccnt_in, ckp_in, gkeys, gnode, sel_kp, sel_cnt, frame_status);
+    K = __builtin_amdgcn_readfirstlane(K);   // the same in every thread: the choice below is one scalar branch
+    if (K <= reg_cap)
+        octree_body<MAXN, T, true, STAMPS>(S, G, L, level, b, K, ccnt_in, ckp_in, gkeys, gnode, sel_kp, sel_cnt, frame_status, t0);
+    else
+        octree_body<MAXN, T, false, STAMPS>(S, G, L, level, b, K, ccnt_in, ckp_in, gkeys, gnode, sel_kp, sel_cnt, frame_status, t0);
 }
 
 // ---------------------------------------------------------------------------
@@ -2260,8 +2459,20 @@ static int launch_pipeline(orbhip_extractor *e, const uint8_t *d_images, int bat
     ORBHIP_GATE_IN(2);
     if (sm & 4) {
         const int ot = e->octree_threads;
+        // (level, frame)s with at most Tv * kOctR candidates keep them in registers, the others in b_keys / b_knode
+#ifdef ORBHIP_DEVTOOLS
+        const bool oct_ws = (e->octree_variant & 1) != 0;      // every workgroup through the workspace path
+#else
+        const bool oct_ws = false;
+#endif
 #define ORBHIP_OCT(MAXNv, Tv) hipLaunchKernelGGL((k_octree<MAXNv, Tv>), dim3(G.nlevels, batch), dim3(Tv), 0, s, G, b_cell_cnt, b_cell_kp, \
-                                                 b_keys, b_knode, b_sel, b_sel_cnt, status)
+                                                 b_keys, b_knode, b_sel, b_sel_cnt, status, oct_ws ? -1 : Tv * kOctR)
+#ifdef ORBHIP_DEVTOOLS
+        if ((e->octree_variant & 2) && e->octree_maxn == 512 && ot == 512)   // stamped diagnostic build (tools/octree_ab.py)
+            hipLaunchKernelGGL((k_octree<512, 512, true>), dim3(G.nlevels, batch), dim3(512), 0, s, G, b_cell_cnt, b_cell_kp,
+                               b_keys, b_knode, b_sel, b_sel_cnt, status, oct_ws ? -1 : 512 * kOctR);
+        else
+#endif
         if (e->octree_maxn == 512) {
             if (ot == 1024) ORBHIP_OCT(512, 1024); else if (ot == 512) ORBHIP_OCT(512, 512); else ORBHIP_OCT(512, 256);
         } else {
@@ -3161,6 +3372,8 @@ int orbhip_level_candidates(orbhip_extractor *e, int frame, int level, int32_t *
 // development exports (not part of include/orbhip.h, absent from the product library): tools/coexec.py, tools/fast_ab.py
 int orbhip_dev_set_stage_mask(orbhip_extractor *e, int mask) { if (!e) return ORBHIP_E_ARG; e->stage_mask = mask; return ORBHIP_OK; }
 int orbhip_dev_set_octree_threads(orbhip_extractor *e, int t) { if (!e) return ORBHIP_E_ARG; e->octree_threads = t; return ORBHIP_OK; }
+// bit 0: every (level, frame) through the workspace path of k_octree; bit 1: the stamped build (512 nodes, 512 threads)
+int orbhip_dev_set_octree_variant(orbhip_extractor *e, int v) { if (!e) return ORBHIP_E_ARG; e->octree_variant = v; return ORBHIP_OK; }
 int orbhip_dev_set_fast_variant(orbhip_extractor *e, int v)
 {
     if (!e) return ORBHIP_E_ARG;
@@ -3174,6 +3387,16 @@ int orbhip_dev_fast_stamps(unsigned long long out[8])
     unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(orbhip::g_fast_stamps), sizeof(z)) != hipSuccess) return ORBHIP_E_HIP;
     if (hipMemcpyToSymbol(HIP_SYMBOL(orbhip::g_fast_stamps), z, sizeof(z)) != hipSuccess) return ORBHIP_E_HIP;
+    return ORBHIP_OK;
+}
+
+// diagnostic: read (and clear) the per-phase cycle sums of the stamped octree build (variant bit 1): [0..8] phases,
+// [9] passes, [10] level-0 workgroups, [11] their keys
+int orbhip_dev_octree_stamps(unsigned long long out[16])
+{
+    unsigned long long z[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(orbhip::g_oct_stamps), sizeof(z)) != hipSuccess) return ORBHIP_E_HIP;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(orbhip::g_oct_stamps), z, sizeof(z)) != hipSuccess) return ORBHIP_E_HIP;
     return ORBHIP_OK;
 }
 #endif

@@ -83,6 +83,7 @@ struct orbhip_extractor {
 #ifdef ORBHIP_DEVTOOLS
     int stage_mask = 31;        // development build (tools/coexec.py): stages launch_pipeline runs
     int fast_variant = 0;       // development build (tools/fast_ab.py): 2 stamped build, 3 / 4 timing floors
+    int octree_variant = 0;     // development build (tools/octree_ab.py): bit 0 workspace path for all, bit 1 stamped build
 #endif
     orbhip::CellDesc *d_cells = nullptr;
     std::vector<orbhip::FastCell> cells2;
