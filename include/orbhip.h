@@ -568,6 +568,45 @@ int orbhip_fuse(orbhip_matcher *m, const orbhip_frame_view *kf, const orbhip_cam
                 const uint8_t *flags, const uint8_t *point_desc, float th, const float *inv_level_sigma2, int32_t *best_idx,
                 int32_t *best_dist);
 
+/* ORBmatcher::Fuse up to the decision for K key frames at once: what LocalMapping::SearchInNeighbors
+ * (src/LocalMapping.cc:454-515: matcher.Fuse(pKFi, vpMapPointMatches) for every covisible key frame and second
+ * neighbour) and LoopClosing::SearchAndFuse (src/LoopClosing.cc:585-610: one Sim3 per key frame) ask of
+ * ORBmatcher::Fuse (src/ORBmatcher.cc:825-950 / :975-1075).  One set of map points, K targets, one launch; row k of the
+ * outputs is bit-identical to one orbhip_fuse call with key frame k, Tcw[k] and flags[k].  The decision (:952-971) stays
+ * in the caller, which applies the rows in key-frame order: the call sees the map as it is at call time (INTEGRATION.md,
+ * "Fusing into many key frames").
+ *
+ * orbhip_fuse_device: device-resident, asynchronous on the matcher's stream, no host synchronisation, no staging copy.
+ *   key frames: d_kf_index [K] int32; target k is frame row d_kf_index[k] (any order, gaps and repeats allowed) of
+ *     d_kps [..][cap] (mvKeysUn), d_desc [..][cap][32], d_n [..] int32 and the optional d_u_right [..][cap] (mvuRight; NULL:
+ *     monocular), in the extractor's output layout.  d_Tcw [K][12]: [Rcw | tcw] of target k; sim3_form != 0: the Scw
+ *     overload, the caller passes Rcw = sRcw/scw, tcw = t/scw as for orbhip_fuse.
+ *     d_cell_start [..][3073] / d_cell_items [..][cap]: mGrid of the same frame rows as
+ *     orbhip_assign_features_to_grid_device writes it; both NULL: the call builds the grids of the K targets itself.
+ *     The grid origin and scale are cam's (min_x, min_y, 64/(max_x-min_x), 48/(max_y-min_y)).
+ *   map points (shared by all targets): np points in arrays of pcap entries: d_world / d_normal [pcap][3],
+ *     d_max_dist / d_min_dist [pcap], d_point_desc [pcap][32]; d_flags [K][pcap] uint8, ORBHIP_POINT_PRESENT = good map
+ *     point and !pMP->IsInKeyFrame(target k) (:849, one row per target).  inv_level_sigma2: host, cam->n_levels floats.
+ *   outputs: d_best_idx / d_best_dist [K][pcap] int32 (-1 / 256 where nothing passes; entries >= np untouched);
+ *     d_q [K][pcap] orbhip_query or NULL: the prologue's records (those of orbhip_keyframe_queries mode 0).
+ *   cap <= 4096 (ORBHIP_E_CAPACITY beyond); K >= 0, 0 <= np <= pcap (ORBHIP_E_ARG otherwise); refused before any device
+ *   work.  K == 0 or np == 0: success, nothing written.
+ *
+ * orbhip_fuse_batch: host buffers, synchronous; what a host-side LocalMapping thread calls.  kfs [K] key frames,
+ *   Tcw [K][12], flags [K][n], best_idx / best_dist [K][n]; everything is staged in one copy, fused by one
+ *   orbhip_fuse_device call that builds the grids, and read back in one copy.  A key frame with more than 4096 key points,
+ *   or whose grid or level count differs from cam's, takes the orbhip_fuse path for its row. */
+int orbhip_fuse_device(orbhip_matcher *m, int K, const void *d_kf_index, const orbhip_camera *cam, const void *d_Tcw,
+                       int sim3_form, const void *d_kps, const void *d_desc, const void *d_n, int cap, const void *d_u_right,
+                       const void *d_cell_start, const void *d_cell_items, int np, int pcap, const void *d_world,
+                       const void *d_normal, const void *d_max_dist, const void *d_min_dist, const void *d_point_desc,
+                       const void *d_flags, float th, const float *inv_level_sigma2, void *d_best_idx, void *d_best_dist,
+                       void *d_q);
+int orbhip_fuse_batch(orbhip_matcher *m, int K, const orbhip_frame_view *const *kfs, const orbhip_camera *cam,
+                      const float *Tcw, int sim3_form, int n, const float *world, const float *normal,
+                      const float *max_dist, const float *min_dist, const uint8_t *flags, const uint8_t *point_desc,
+                      float th, const float *inv_level_sigma2, int32_t *best_idx, int32_t *best_dist);
+
 /* ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1102-1326), complete: both projection directions, both searches
  * (accept bestDist <= TH_HIGH) and the mutual-agreement pass.  kf1 / kf2: the key frames' keypoints, descriptors and
  * grid; per key-frame slot i: world*[i], max/min_dist*[i], desc*[i] = the slot's map point (GetWorldPos,

@@ -413,6 +413,36 @@ public:
         bestDist.resize(n);
     }
 
+    // Fuse for K key frames and one set of n map points in one call: the matching of LocalMapping::SearchInNeighbors
+    // (src/LocalMapping.cc:454-515) and LoopClosing::SearchAndFuse (src/LoopClosing.cc:585-610), ORBmatcher::Fuse
+    // src/ORBmatcher.cc:825-950 / :975-1075 up to the decision.  Tcw [K][12], flags [K][n] (!IsInKeyFrame per target);
+    // bestIdx / bestDist [K][n], row k = what Fuse(*KFs[k], cam, Tcw + 12*k, ..., flags + n*k, ...) gives.  The caller
+    // applies the rows in key-frame order ("Fusing into many key frames").
+    void FuseBatch(const std::vector<const orbhip_frame_view *> &KFs, const orbhip_camera &cam, const float *Tcw, bool sim3Form,
+                   int n, const float *world, const float *normal, const float *maxDist, const float *minDist,
+                   const uint8_t *flags, const uint8_t *pointDesc, float th, const float *invLevelSigma2,
+                   std::vector<int> &bestIdx, std::vector<int> &bestDist)
+    {
+        const size_t total = KFs.size() * (size_t)(n > 0 ? n : 0);
+        bestIdx.assign(total ? total : 1, -1);
+        bestDist.assign(total ? total : 1, 256);
+        check(orbhip_fuse_batch(m_, (int)KFs.size(), KFs.data(), &cam, Tcw, sim3Form ? 1 : 0, n, world, normal, maxDist, minDist,
+                                flags, pointDesc, th, invLevelSigma2, bestIdx.data(), bestDist.data()), "orbhip_fuse_batch");
+        bestIdx.resize(total);
+        bestDist.resize(total);
+    }
+    // device frames and points, asynchronous on the matcher's stream: orbhip_fuse_device with the mirror's handle
+    void FuseDevice(int K, const void *dKfIndex, const orbhip_camera &cam, const void *dTcw, bool sim3Form, const void *dKps,
+                    const void *dDesc, const void *dN, int cap, const void *dURight, const void *dCellStart,
+                    const void *dCellItems, int np, int pcap, const void *dWorld, const void *dNormal, const void *dMaxDist,
+                    const void *dMinDist, const void *dPointDesc, const void *dFlags, float th, const float *invLevelSigma2,
+                    void *dBestIdx, void *dBestDist, void *dQ = nullptr)
+    {
+        check(orbhip_fuse_device(m_, K, dKfIndex, &cam, dTcw, sim3Form ? 1 : 0, dKps, dDesc, dN, cap, dURight, dCellStart,
+                                 dCellItems, np, pcap, dWorld, dNormal, dMaxDist, dMinDist, dPointDesc, dFlags, th,
+                                 invLevelSigma2, dBestIdx, dBestDist, dQ), "orbhip_fuse_device");
+    }
+
     // int SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches12, const float &s12, const cv::Mat &R12,
     // const cv::Mat &t12, const float th) (src/ORBmatcher.cc:1102-1326), complete.  T1w / T2w: [R | t] of the two key
     // frames; S21 = [sR21 | t21], S12 = [sR12 | t12] as the reference computes them (:1119-1121).  Per key-frame slot: the

@@ -128,6 +128,9 @@ SYMBOLS = [
     ("orbhip_keyframe_queries", _i, [_vp, C.POINTER(Camera), _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp]),
     ("orbhip_fuse", _i, [_vp, C.POINTER(FrameView), C.POINTER(Camera), _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp,
                          _vp]),
+    ("orbhip_fuse_device", _i, [_vp, _i, _vp, C.POINTER(Camera), _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    ("orbhip_fuse_batch", _i, [_vp, _i, _vp, C.POINTER(Camera), _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     ("orbhip_search_by_sim3", _i, [_vp, C.POINTER(FrameView), C.POINTER(FrameView), C.POINTER(Camera), _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _pi]),
     ("orbhip_project_last_frame_device", _i, [_vp, _i, C.POINTER(Camera), _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _i,

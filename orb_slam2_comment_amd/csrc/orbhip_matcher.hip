@@ -1616,17 +1616,14 @@ __global__ __launch_bounds__(256) void k_distinctive(const uint8_t *__restrict__
 // (cell << 12 | index) are bitonic-sorted in LDS, which is push_back order inside every cell; cell sizes come from LDS
 // atomics and an exclusive scan.
 constexpr int kGridMax = 4096;
-__global__ __launch_bounds__(1024) void k_grid_csr(DevFrame F, Batch B, int *__restrict__ cell_of,
-                                                   int *__restrict__ cell_start, int *__restrict__ cell_items)
+// F and the three output rows are those of the workgroup's frame already
+__device__ __forceinline__ void grid_csr_body(const DevFrame &F, int *__restrict__ cell_of, int *__restrict__ cell_start,
+                                              int *__restrict__ cell_items)
 {
     __shared__ uint32_t key[kGridMax];
     __shared__ int cnt[kGridCells + 1];
     __shared__ int wsum[16];
-    const int tid = threadIdx.x, NT = 1024, frame = blockIdx.x;
-    batch_frame(F, B, frame);
-    cell_of += (size_t)frame * B.cap;
-    cell_items += (size_t)frame * B.cap;
-    cell_start += (size_t)frame * (kGridCells + 1);
+    const int tid = threadIdx.x, NT = 1024;
     const int n = min(F.n, kGridMax);
     int P = 1024;
     while (P < n) P <<= 1;
@@ -1672,6 +1669,25 @@ __global__ __launch_bounds__(1024) void k_grid_csr(DevFrame F, Batch B, int *__r
     const int excl = base + incl - (v0 + v1 + v2);
     cell_start[c0] = excl; cell_start[c0 + 1] = excl + v0; cell_start[c0 + 2] = excl + v0 + v1;
     if (tid == NT - 1) cell_start[kGridCells] = excl + v0 + v1 + v2;
+}
+__global__ __launch_bounds__(1024) void k_grid_csr(DevFrame F, Batch B, int *__restrict__ cell_of,
+                                                   int *__restrict__ cell_start, int *__restrict__ cell_items)
+{
+    const int frame = blockIdx.x;
+    batch_frame(F, B, frame);
+    grid_csr_body(F, cell_of + (size_t)frame * B.cap, cell_start + (size_t)frame * (kGridCells + 1),
+                  cell_items + (size_t)frame * B.cap);
+}
+// the same for the targets of orbhip_fuse_device: workgroup k builds the grid of frame row kf_index[k] into row k
+__global__ __launch_bounds__(1024) void k_grid_csr_indexed(DevFrame F, const int *__restrict__ kf_index,
+                                                           const int *__restrict__ n_dev, int cap, int *__restrict__ cell_of,
+                                                           int *__restrict__ cell_start, int *__restrict__ cell_items)
+{
+    const int k = blockIdx.x;
+    const size_t f = (size_t)kf_index[k];
+    F.keys += f * cap;
+    F.n = min(n_dev[f], cap);
+    grid_csr_body(F, cell_of + (size_t)k * cap, cell_start + (size_t)k * (kGridCells + 1), cell_items + (size_t)k * cap);
 }
 
 // Frame::UndistortKeyPoints (Frame.cc:404-434) = cv::undistortPoints(mat, mat, mK, mDistCoef, Mat(), mK): OpenCV 2.4 - 3.3
@@ -1994,10 +2010,9 @@ struct KfQueryArgs {
     orbhip_query *q;
     int n, mode, double_invz;
 };
-__global__ __launch_bounds__(256) void k_keyframe_queries(KfQueryArgs A, orbhip_camera cam, float th)
+// the record of map point i: the one statement of this float sequence, shared by k_keyframe_queries and k_fuse_batch
+__device__ __forceinline__ orbhip_query keyframe_query(const KfQueryArgs &A, const orbhip_camera &cam, const float th, const int i)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= A.n) return;
     orbhip_query Q;
     Q.valid = 0; Q.u = 0; Q.v = 0; Q.radius = 0; Q.min_level = 0; Q.max_level = 0; Q.ur = 0; Q.level_aux = 0; Q.angle = 0; Q.observed = 0;
     do {
@@ -2049,7 +2064,158 @@ __global__ __launch_bounds__(256) void k_keyframe_queries(KfQueryArgs A, orbhip_
         Q.ur = A.mode == 0 ? __fsub_rn(u, __fmul_rn(cam.mbf, invz)) : 0.0f;
         Q.level_aux = lvl;
     } while (0);
-    A.q[i] = Q;
+    return Q;
+}
+__global__ __launch_bounds__(256) void k_keyframe_queries(KfQueryArgs A, orbhip_camera cam, float th)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.n) return;
+    A.q[i] = keyframe_query(A, cam, th, i);
+}
+
+// ORBmatcher::Fuse up to the decision for K key frames in one launch (LocalMapping::SearchInNeighbors,
+// src/LocalMapping.cc:454-515; LoopClosing::SearchAndFuse, src/LoopClosing.cc:585-610): blockIdx.y = target k = frame row
+// kf_index[k] of the extractor-layout arrays, blockIdx.x = 256 of the shared map points.
+//   1. one thread per point: keyframe_query (the prologue of orbhip_fuse).  The records stay in registers; they reach
+//      memory only when the caller asks for them (A.q).
+//   2. the wavefront's valid records are packed to its low lanes with one ds_permute per field (a stable partition of
+//      the 64 lanes, so every lane is a destination exactly once); no LDS allocation, no barrier.
+//   3. LPQ lanes per query (64 / LPQ queries of the wavefront at a time) walk the window's cells in the order of
+//      Frame::GetFeaturesInArea (src/Frame.cc:332-378): for every column ix the cells (ix, nMinCellY..nMaxCellY) are
+//      consecutive in c = ix*48 + iy, so their key points are ONE run of cell_items.  Candidate p of the run goes to
+//      lane p % LPQ: |dx|,|dy| < r, level window, chi-square gate, 256-bit Hamming distance exactly as k_best_in_window.
+//      The key is distance << 32 | position in cell_items << 12 | index: cell_items is sorted by (cell, index), so the
+//      position orders candidates as cell << 20 | index does and the group minimum is the reference's first minimum.
+struct FuseBatchArgs {
+    const int *kf_index;                    // [K]
+    const float *Tcw;                       // [K][12]
+    const orbhip_keypoint *keys;            // [..][cap]
+    const uint8_t *desc;                    // [..][cap][32]
+    const int *n_dev;                       // [..]
+    const float *u_right;                   // [..][cap] or null
+    const int *cell_start, *cell_items;     // [..][3073], [..][cap]
+    const float *world, *normal, *max_dist, *min_dist;
+    const uint8_t *point_desc, *flags;      // [np][32], [K][pcap]
+    int *best_idx, *best_dist;              // [K][pcap]
+    orbhip_query *q;                        // [K][pcap] or null
+    int cap, np, pcap, double_invz;
+    int csr_by_target;                      // CSR rows are indexed by k (built by this call), not by the frame row
+    float min_x, min_y, inv_w, inv_h;
+};
+
+template <int LPQ> __device__ __forceinline__ unsigned long long group_min_u64(unsigned long long v);
+template <> __device__ __forceinline__ unsigned long long group_min_u64<64>(unsigned long long v) { return wave_min_u64(v); }
+// minimum over 8 consecutive lanes, in all of them: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror
+template <> __device__ __forceinline__ unsigned long long group_min_u64<8>(unsigned long long v)
+{
+#define ORBHIP_GMIN_STEP(ctrl)                                                                                \
+    {                                                                                                         \
+        const uint32_t lo_ = (uint32_t)v, hi_ = (uint32_t)(v >> 32);                                          \
+        const uint32_t ol_ = (uint32_t)__builtin_amdgcn_update_dpp((int)lo_, (int)lo_, ctrl, 0xf, 0xf, false); \
+        const uint32_t oh_ = (uint32_t)__builtin_amdgcn_update_dpp((int)hi_, (int)hi_, ctrl, 0xf, 0xf, false); \
+        const unsigned long long o_ = ((unsigned long long)oh_ << 32) | ol_;                                  \
+        v = o_ < v ? o_ : v;                                                                                  \
+    }
+    ORBHIP_GMIN_STEP(0xB1)
+    ORBHIP_GMIN_STEP(0x4E)
+    ORBHIP_GMIN_STEP(0x141)
+#undef ORBHIP_GMIN_STEP
+    return v;
+}
+
+template <int LPQ>
+__global__ __launch_bounds__(256) void k_fuse_batch(FuseBatchArgs A, orbhip_camera cam, float th, SigmaTab sig)
+{
+    const int k = blockIdx.y, lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const size_t f = (size_t)A.kf_index[k], orow = (size_t)k * A.pcap;
+    orbhip_query Q;
+    Q.valid = 0; Q.u = 0; Q.v = 0; Q.radius = 0; Q.min_level = 0; Q.ur = 0;
+    if (i < A.np) {
+        KfQueryArgs P;
+        P.T1 = A.Tcw + (size_t)k * 12; P.T2 = nullptr;
+        P.world = A.world; P.normal = A.normal; P.max_dist = A.max_dist; P.min_dist = A.min_dist;
+        P.flags = A.flags + orow; P.q = nullptr; P.n = A.np; P.mode = 0; P.double_invz = A.double_invz;
+        Q = keyframe_query(P, cam, th, i);
+        if (A.q) A.q[orow + i] = Q;
+        if (!Q.valid) { A.best_idx[orow + i] = -1; A.best_dist[orow + i] = 256; }
+    }
+    const bool valid = i < A.np && Q.valid != 0;
+    const unsigned long long vmask = __ballot(valid);
+    const int nvalid = __popcll(vmask);
+    if (nvalid == 0) return;                          // wave-uniform
+    // stable partition: valid lanes to 0 .. nvalid-1 in lane order, the others behind them
+    const int before = __popcll(vmask & ((1ull << lane) - 1ull));
+    const int dest = (valid ? before : nvalid + (lane - before)) << 2;
+    const float cu = __int_as_float(__builtin_amdgcn_ds_permute(dest, __float_as_int(Q.u)));
+    const float cv = __int_as_float(__builtin_amdgcn_ds_permute(dest, __float_as_int(Q.v)));
+    const float cr = __int_as_float(__builtin_amdgcn_ds_permute(dest, __float_as_int(Q.radius)));
+    const float cur = __int_as_float(__builtin_amdgcn_ds_permute(dest, __float_as_int(Q.ur)));
+    const int cml = __builtin_amdgcn_ds_permute(dest, Q.min_level);
+    const int cqi = __builtin_amdgcn_ds_permute(dest, i);
+
+    const int n = min(A.n_dev[f], A.cap);
+    const orbhip_keypoint *keys = A.keys + f * A.cap;
+    const uint8_t *desc = A.desc + f * A.cap * 32;
+    const float *u_right = A.u_right ? A.u_right + f * A.cap : nullptr;
+    const size_t crow = A.csr_by_target ? (size_t)k : f;
+    const int *cs = A.cell_start + crow * (kGridCells + 1);
+    const int *items = A.cell_items + crow * A.cap;
+
+    constexpr int G = 64 / LPQ;
+    const int sub = lane & (LPQ - 1), grp = lane / LPQ;
+    for (int s0 = 0; s0 < nvalid; s0 += G) {          // wave-uniform trip count
+        const int slot = s0 + grp;
+        const bool active = slot < nvalid;
+        const int src = active ? slot : 0;
+        const float x = __shfl(cu, src), y = __shfl(cv, src), r = __shfl(cr, src), qur = __shfl(cur, src);
+        const int min_level = __shfl(cml, src), qi = __shfl(cqi, src);
+        unsigned long long best = ~0ull;
+        if (active) {
+            const int nMinCellX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, A.min_x), r), A.inv_w)));
+            const int nMaxCellX = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, A.min_x), r), A.inv_w)));
+            const int nMinCellY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, A.min_y), r), A.inv_h)));
+            const int nMaxCellY = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, A.min_y), r), A.inv_h)));
+            if (!(nMinCellX >= GRID_COLS || nMaxCellX < 0 || nMinCellY >= GRID_ROWS || nMaxCellY < 0) &&
+                nMinCellY <= nMaxCellY) {
+                uint32_t qd[8];
+                const uint4 *qp = reinterpret_cast<const uint4 *>(A.point_desc + (size_t)qi * 32);
+                const uint4 q0 = qp[0], q1 = qp[1];
+                qd[0] = q0.x; qd[1] = q0.y; qd[2] = q0.z; qd[3] = q0.w; qd[4] = q1.x; qd[5] = q1.y; qd[6] = q1.z; qd[7] = q1.w;
+                for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
+                    const int c0 = ix * GRID_ROWS;
+                    const int pb = max(cs[c0 + nMinCellY], 0), pe = min(cs[c0 + nMaxCellY + 1], A.cap);
+                    for (int p = pb + sub; p < pe; p += LPQ) {
+                        const int j = items[p];
+                        if ((unsigned)j >= (unsigned)n) continue;   // never for a grid of these key points
+                        const orbhip_keypoint kp = keys[j];
+                        if (!(fabsf(__fsub_rn(kp.x, x)) < r && fabsf(__fsub_rn(kp.y, y)) < r)) continue;
+                        if (kp.octave < min_level || kp.octave > min_level + 1) continue;   // kpLevel<pred-1 || kpLevel>pred
+                        const float ex = __fsub_rn(x, kp.x), ey = __fsub_rn(y, kp.y);
+                        float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+                        const float kpr = u_right ? u_right[j] : -1.0f;
+                        const float is2 = sig.inv_sigma2[kp.octave & (ORBHIP_MAX_LEVELS - 1)];
+                        if (kpr >= 0) {
+                            const float er = __fsub_rn(qur, kpr);
+                            e2 = __fadd_rn(e2, __fmul_rn(er, er));
+                            if ((double)__fmul_rn(e2, is2) > 7.8) continue;
+                        } else if ((double)__fmul_rn(e2, is2) > 5.99) continue;
+                        const uint4 *tp = reinterpret_cast<const uint4 *>(desc + (size_t)j * 32);
+                        const uint4 t0 = tp[0], t1 = tp[1];
+                        const int d = __popc(qd[0] ^ t0.x) + __popc(qd[1] ^ t0.y) + __popc(qd[2] ^ t0.z) + __popc(qd[3] ^ t0.w) +
+                                      __popc(qd[4] ^ t1.x) + __popc(qd[5] ^ t1.y) + __popc(qd[6] ^ t1.z) + __popc(qd[7] ^ t1.w);
+                        const unsigned long long key = ((unsigned long long)d << 32) | ((uint32_t)p << 12) | (uint32_t)j;
+                        best = key < best ? key : best;
+                    }
+                }
+            }
+        }
+        best = group_min_u64<LPQ>(best);
+        if (active && sub == 0) {
+            A.best_idx[orow + qi] = best == ~0ull ? -1 : (int)(best & 0xfffu);
+            A.best_dist[orow + qi] = best == ~0ull ? 256 : (int)(best >> 32);
+        }
+    }
 }
 
 struct StereoGeom {
@@ -3876,6 +4042,156 @@ int orbhip_fuse(orbhip_matcher *m, const orbhip_frame_view *kf, const orbhip_cam
     int rc = orbhip_keyframe_queries(m, cam, 0, sim3_form ? 1 : 0, Tcw, nullptr, n, world, normal, max_dist, min_dist, flags, th, q.data());
     if (rc) return rc;
     return orbhip_search_best_in_window(m, kf, q.data(), point_desc, n, 1, inv_level_sigma2, best_idx, best_dist);
+}
+
+// lanes per query of k_fuse_batch: 8 is the mapping kept; development builds can select the
+// one-wavefront-per-query mapping for tools/bench_fuse.py
+static int g_fuse_lanes = 8;
+#ifdef ORBHIP_DEVTOOLS
+int orbhip_dev_fuse_lanes(int lanes)
+{
+    if (lanes != 8 && lanes != 64) return ORBHIP_E_ARG;
+    g_fuse_lanes = lanes;
+    return ORBHIP_OK;
+}
+#endif
+
+int orbhip_fuse_device(orbhip_matcher *m, int K, const void *d_kf_index, const orbhip_camera *cam, const void *d_Tcw,
+                       int sim3_form, const void *d_kps, const void *d_desc, const void *d_n, int cap, const void *d_u_right,
+                       const void *d_cell_start, const void *d_cell_items, int np, int pcap, const void *d_world,
+                       const void *d_normal, const void *d_max_dist, const void *d_min_dist, const void *d_point_desc,
+                       const void *d_flags, float th, const float *inv_level_sigma2, void *d_best_idx, void *d_best_dist,
+                       void *d_q)
+{
+    if (!m || K < 0 || np < 0 || np > pcap || cap < 1 || !cam || cam->n_levels < 1 || cam->n_levels > ORBHIP_MAX_LEVELS)
+        return ORBHIP_E_ARG;
+    if (cap > kGridMax) { set_error("fuse_device: capacity %d exceeds %d", cap, kGridMax); return ORBHIP_E_CAPACITY; }
+    if ((d_cell_start == nullptr) != (d_cell_items == nullptr)) return ORBHIP_E_ARG;
+    if (K == 0 || np == 0) return ORBHIP_OK;
+    if (!d_kf_index || !d_Tcw || !d_kps || !d_desc || !d_n || !d_world || !d_normal || !d_max_dist || !d_min_dist ||
+        !d_point_desc || !d_flags || !inv_level_sigma2 || !d_best_idx || !d_best_dist)
+        return ORBHIP_E_ARG;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    FuseBatchArgs A;
+    A.kf_index = (const int *)d_kf_index; A.Tcw = (const float *)d_Tcw;
+    A.keys = (const orbhip_keypoint *)d_kps; A.desc = (const uint8_t *)d_desc; A.n_dev = (const int *)d_n;
+    A.u_right = (const float *)d_u_right;
+    A.cell_start = (const int *)d_cell_start; A.cell_items = (const int *)d_cell_items;
+    A.world = (const float *)d_world; A.normal = (const float *)d_normal;
+    A.max_dist = (const float *)d_max_dist; A.min_dist = (const float *)d_min_dist;
+    A.point_desc = (const uint8_t *)d_point_desc; A.flags = (const uint8_t *)d_flags;
+    A.best_idx = (int *)d_best_idx; A.best_dist = (int *)d_best_dist; A.q = (orbhip_query *)d_q;
+    A.cap = cap; A.np = np; A.pcap = pcap; A.double_invz = sim3_form ? 1 : 0; A.csr_by_target = 0;
+    // Frame::ComputeImageBounds / mfGridElement{Width,Height}Inv (src/Frame.cc:99-100) from the camera's bounds
+    A.min_x = cam->min_x; A.min_y = cam->min_y;
+    A.inv_w = (float)GRID_COLS / (cam->max_x - cam->min_x); A.inv_h = (float)GRID_ROWS / (cam->max_y - cam->min_y);
+    if (!d_cell_start) {   // mGrid of the K targets into the handle's scratch: cell_of | cell_items | cell_start
+        void *p;
+        const size_t rows = al256((size_t)K * cap * sizeof(int));
+        if (int rc = scratch(m, S_CSR, 2 * rows + (size_t)K * (kGridCells + 1) * sizeof(int), &p)) return rc;
+        int *cell_of = (int *)p, *cell_items = (int *)((uint8_t *)p + rows), *cell_start = (int *)((uint8_t *)p + 2 * rows);
+        DevFrame D;
+        D.n = 0; D.keys = A.keys; D.desc = nullptr; D.u_right = nullptr;
+        D.min_x = A.min_x; D.min_y = A.min_y; D.inv_w = A.inv_w; D.inv_h = A.inv_h;
+        hipLaunchKernelGGL(k_grid_csr_indexed, dim3(K), dim3(1024), 0, m->stream, D, A.kf_index, A.n_dev, cap, cell_of,
+                           cell_start, cell_items);
+        A.cell_start = cell_start; A.cell_items = cell_items; A.csr_by_target = 1;
+    }
+    SigmaTab sig;
+    memset(&sig, 0, sizeof(sig));
+    for (int l = 0; l < cam->n_levels; ++l) sig.inv_sigma2[l] = inv_level_sigma2[l];
+    const dim3 grid((np + 255) / 256, K);
+    if (g_fuse_lanes == 64) hipLaunchKernelGGL(k_fuse_batch<64>, grid, dim3(256), 0, m->stream, A, *cam, th, sig);
+    else hipLaunchKernelGGL(k_fuse_batch<8>, grid, dim3(256), 0, m->stream, A, *cam, th, sig);
+    ORBHIP_HIP_CHECK(hipGetLastError());
+    return ORBHIP_OK;
+}
+
+int orbhip_fuse_batch(orbhip_matcher *m, int K, const orbhip_frame_view *const *kfs, const orbhip_camera *cam,
+                      const float *Tcw, int sim3_form, int n, const float *world, const float *normal,
+                      const float *max_dist, const float *min_dist, const uint8_t *flags, const uint8_t *point_desc,
+                      float th, const float *inv_level_sigma2, int32_t *best_idx, int32_t *best_dist)
+{
+    if (!m || K < 0 || n < 0 || !cam || cam->n_levels < 1 || cam->n_levels > ORBHIP_MAX_LEVELS) return ORBHIP_E_ARG;
+    if (K == 0 || n == 0) return ORBHIP_OK;
+    if (!kfs || !Tcw || !world || !normal || !max_dist || !min_dist || !flags || !point_desc || !inv_level_sigma2 ||
+        !best_idx || !best_dist)
+        return ORBHIP_E_ARG;
+    for (int k = 0; k < K; ++k)
+        if (!kfs[k] || kfs[k]->n < 0 || (kfs[k]->n > 0 && (!kfs[k]->keys || !kfs[k]->desc))) return ORBHIP_E_ARG;
+    for (size_t i = 0; i < (size_t)K * n; ++i) { best_idx[i] = -1; best_dist[i] = 256; }
+    // A key frame goes with the batch when the one launch computes what orbhip_fuse would for it: at most 4096 key
+    // points and the grid / level count of the shared camera.  Any other takes the single-frame path for its row.
+    const float inv_w = (float)GRID_COLS / (cam->max_x - cam->min_x), inv_h = (float)GRID_ROWS / (cam->max_y - cam->min_y);
+    std::vector<int> rows, single;
+    int cap = 1;
+    bool any_ur = false;
+    for (int k = 0; k < K; ++k) {
+        const orbhip_frame_view *f = kfs[k];
+        if (f->n <= kGridMax && f->min_x == cam->min_x && f->min_y == cam->min_y && f->grid_inv_w == inv_w &&
+            f->grid_inv_h == inv_h && f->n_levels == cam->n_levels) {
+            rows.push_back(k);
+            cap = std::max(cap, f->n);
+            any_ur = any_ur || (f->u_right && f->n > 0);
+        } else single.push_back(k);
+    }
+    const int Kb = (int)rows.size();
+    if (Kb > 0) {
+        ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+        const size_t kc = (size_t)Kb * cap, sn = (size_t)n;
+        Stage st;
+        int rc;
+        if ((rc = stage_begin(m, 2 * al256((size_t)Kb * 4) + al256((size_t)Kb * 48) + al256(kc * sizeof(orbhip_keypoint)) +
+                                     al256(kc * 32) + al256(kc * 4) + 2 * al256(sn * 12) + 2 * al256(sn * 4) +
+                                     al256((size_t)Kb * sn) + al256(sn * 32), &st))) return rc;
+        const int *d_index, *d_n;
+        const float *d_T, *d_ur = nullptr;
+        const orbhip_keypoint *d_keys;
+        const uint8_t *d_desc, *d_flags;
+        int *h_index = st.take((size_t)Kb, &d_index), *h_n = st.take((size_t)Kb, &d_n);
+        float *h_T = st.take((size_t)Kb * 12, &d_T);
+        orbhip_keypoint *h_keys = st.take(kc, &d_keys);
+        uint8_t *h_desc = st.take(kc * 32, &d_desc);
+        float *h_ur = any_ur ? st.take(kc, &d_ur) : nullptr;
+        uint8_t *h_flags = st.take((size_t)Kb * sn, &d_flags);
+        const float *d_world = st.put(world, sn * 3), *d_normal = st.put(normal, sn * 3);
+        const float *d_max = st.put(max_dist, sn), *d_min = st.put(min_dist, sn);
+        const uint8_t *d_pdesc = st.put(point_desc, sn * 32);
+        if ((rc = st.status())) return rc;
+        for (int b = 0; b < Kb; ++b) {
+            const int k = rows[b];
+            const orbhip_frame_view *f = kfs[k];
+            const size_t fn = (size_t)f->n;
+            h_index[b] = b; h_n[b] = f->n;
+            memcpy(h_T + (size_t)b * 12, Tcw + (size_t)k * 12, 12 * sizeof(float));
+            if (fn) {
+                memcpy(h_keys + (size_t)b * cap, f->keys, fn * sizeof(orbhip_keypoint));
+                memcpy(h_desc + (size_t)b * cap * 32, f->desc, fn * 32);
+            }
+            if (h_ur)
+                for (size_t j = 0; j < fn; ++j) h_ur[(size_t)b * cap + j] = f->u_right ? f->u_right[j] : -1.0f;
+            memcpy(h_flags + (size_t)b * sn, flags + (size_t)k * sn, sn);
+        }
+        if ((rc = stage_commit(m, &st))) return rc;
+        void *p;
+        const size_t ob = (size_t)Kb * sn * sizeof(int);
+        if ((rc = scratch(m, S_OUT, 2 * ob, &p))) return rc;
+        int *d_out = (int *)p;
+        if ((rc = orbhip_fuse_device(m, Kb, d_index, cam, d_T, sim3_form, d_keys, d_desc, d_n, cap, d_ur, nullptr, nullptr, n, n,
+                                     d_world, d_normal, d_max, d_min, d_pdesc, d_flags, th, inv_level_sigma2, d_out,
+                                     d_out + (size_t)Kb * sn, nullptr))) return rc;
+        const uint8_t *h;
+        if ((rc = read_back(m, d_out, 2 * ob, &h))) return rc;
+        for (int b = 0; b < Kb; ++b) {
+            memcpy(best_idx + (size_t)rows[b] * sn, h + (size_t)b * sn * sizeof(int), sn * sizeof(int));
+            memcpy(best_dist + (size_t)rows[b] * sn, h + ob + (size_t)b * sn * sizeof(int), sn * sizeof(int));
+        }
+    }
+    for (int k : single)
+        if (int rc = orbhip_fuse(m, kfs[k], cam, Tcw + (size_t)k * 12, sim3_form, n, world, normal, max_dist, min_dist,
+                                 flags + (size_t)k * n, point_desc, th, inv_level_sigma2, best_idx + (size_t)k * n,
+                                 best_dist + (size_t)k * n)) return rc;
+    return ORBHIP_OK;
 }
 
 int orbhip_search_by_sim3(orbhip_matcher *m, const orbhip_frame_view *kf1, const orbhip_frame_view *kf2,

@@ -239,6 +239,15 @@ class ORBmatcher:
               "orbhip_assign_features_to_grid")
         return cell_of[:F.N].copy(), start, items[:start[-1]].copy()
 
+    def AssignFeaturesToGridDevice(self, frames, d_kps_un, d_n, cap, bounds, d_cell_of, d_cell_start, d_cell_items):
+        """Batched, device-resident form (device pointers as ints): d_cell_of / d_cell_items [frames][cap] int32,
+        d_cell_start [frames][3073] int32.  Asynchronous on the matcher's stream."""
+        b = [np.float32(v) for v in bounds]
+        check(self._lib.orbhip_assign_features_to_grid_device(
+            self._h, frames, d_kps_un, d_n, cap, b[0], b[1], np.float32(FRAME_GRID_COLS) / (b[2] - b[0]),
+            np.float32(FRAME_GRID_ROWS) / (b[3] - b[1]), d_cell_of, d_cell_start, d_cell_items),
+            "orbhip_assign_features_to_grid_device")
+
     def ComputeStereoFromRGBD(self, keys, keys_un, imDepth, mbf):
         """Frame::ComputeStereoFromRGBD (src/Frame.cc:643-664); imDepth: 2-D float32.  Returns (mvuRight, mvDepth)."""
         k = np.ascontiguousarray(keys, KP_DTYPE)
@@ -418,6 +427,43 @@ class ORBmatcher:
         check(self._lib.orbhip_fuse(self._h, C.byref(v), C.byref(cam), ptr(Tc), int(sim3_form), len(w), ptr(w), ptr(nn), ptr(mx),
                                     ptr(mn), ptr(fg), ptr(pd), float(th), ptr(sig), ptr(bi), ptr(bd)), "orbhip_fuse")
         return bi[:len(w)].copy(), bd[:len(w)].copy()
+
+    def FuseBatch(self, KFs, cam, Tcw, world, normal, max_dist, min_dist, flags, point_desc, th, inv_level_sigma2,
+                  sim3_form=False):
+        """Fuse up to the decision for K key frames and one set of n map points (LocalMapping::SearchInNeighbors,
+        src/LocalMapping.cc:454-515; LoopClosing::SearchAndFuse, src/LoopClosing.cc:585-610; ORBmatcher::Fuse,
+        src/ORBmatcher.cc:825-950 / :975-1075) in one staged copy, one launch and one read-back.  KFs: K FrameViews;
+        Tcw [K] poses (4x4 or 3x4); flags [K, n] (POINT_PRESENT = good and not IsInKeyFrame of that target).  Returns
+        (best_idx[K, n], best_dist[K, n]); row k equals Fuse(KFs[k], cam, Tcw[k], ..., flags[k], ...)."""
+        K = len(KFs)
+        Tc = np.ascontiguousarray(np.asarray(Tcw, np.float32).reshape(K, -1, 4)[:, :3, :]).reshape(K, 12)
+        w, nn, mx, mn, _ = self._pts(world, normal, max_dist, min_dist, np.zeros(0, np.uint8))
+        n = len(w)
+        fg = np.ascontiguousarray(flags, np.uint8).reshape(K, n)
+        pd = np.ascontiguousarray(point_desc, np.uint8).reshape(-1, 32)
+        sig = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        bi, bd = np.full((K, n), -1, np.int32), np.full((K, n), 256, np.int32)
+        views = [kf.c_view() for kf in KFs]
+        arr = (C.POINTER(capi.FrameView) * max(K, 1))(*[C.pointer(v) for v in views])
+        check(self._lib.orbhip_fuse_batch(self._h, K, arr, C.byref(cam), ptr(Tc), int(sim3_form), n, ptr(w), ptr(nn), ptr(mx),
+                                          ptr(mn), ptr(fg), ptr(pd), float(th), ptr(sig), ptr(bi), ptr(bd)),
+              "orbhip_fuse_batch")
+        return bi, bd
+
+    def FuseDevice(self, K, d_kf_index, cam, d_Tcw, d_kps, d_desc, d_n, cap, np_, pcap, d_world, d_normal, d_max_dist,
+                   d_min_dist, d_point_desc, d_flags, th, inv_level_sigma2, d_best_idx, d_best_dist, sim3_form=False,
+                   d_u_right=0, d_cell_start=0, d_cell_items=0, d_q=0):
+        """Device-resident FuseBatch (device pointers as ints; see orbhip_fuse_device in include/orbhip.h): target k is
+        frame row kf_index[k] of the extractor-layout arrays, d_flags [K][pcap], outputs [K][pcap].  d_cell_start /
+        d_cell_items: the arrays AssignFeaturesToGridDevice wrote for the same frames, or 0 to build the grids inside the
+        call.  Asynchronous on the matcher's stream."""
+        sig = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        if len(sig) < cam.n_levels:
+            raise ValueError("inv_level_sigma2 needs one entry per pyramid level")
+        check(self._lib.orbhip_fuse_device(self._h, int(K), d_kf_index, C.byref(cam), d_Tcw, int(sim3_form), d_kps, d_desc, d_n,
+                                           int(cap), d_u_right, d_cell_start, d_cell_items, int(np_), int(pcap), d_world,
+                                           d_normal, d_max_dist, d_min_dist, d_point_desc, d_flags, float(th), ptr(sig),
+                                           d_best_idx, d_best_dist, d_q), "orbhip_fuse_device")
 
     def SearchBySim3(self, KF1, KF2, cam, T1w, T2w, S21, S12, pts1, pts2, th):
         """pts = (world, max_dist, min_dist, flags, desc) per key-frame slot.  Returns (nFound, matches12[N1])."""

@@ -1,0 +1,388 @@
+"""orbhip_fuse_device / orbhip_fuse_batch (ORBmatcher::Fuse for the K key frames of LocalMapping::SearchInNeighbors /
+LoopClosing::SearchAndFuse in one call) against the oracle's keyframe_queries + search_best_in_window run per key frame:
+every query record and every (best_idx, best_dist) bit-identical, row by row.
+
+The scene: six 1241x376 frames extracted in one batch at 1000 features (row 3 is a blank image: n == 0; a batch holds one
+image size, so the blank frame has the size of the others), one pose per frame, and ONE set of map points shared by all
+targets: about 350 key points of every non-empty frame back-projected with that frame's pose (so every target finds its
+own points and sees the other frames' points somewhere else or nowhere), plus points placed behind the camera, outside
+the image, outside the scale-invariance range and seen from the side."""
+import numpy as np
+import pytest
+
+from helpers import synth_frame
+from test_projection_gpu import (KITTI_BF, KITTI_CX, KITTI_CY, KITTI_FX, KITTI_FY, _assert_queries_equal, _back_project, _pose,
+                                 _synthetic_map_for)
+
+pytestmark = pytest.mark.gpu
+
+W, H, NF = 1241, 376, 1000
+FRAMES = [(31, (0, 0)), (31, (5, 2)), (32, (0, 0)), None, (33, (0, 0)), (33, (4, 1))]   # None: blank
+BLANK = 3
+KF_INDEX = [4, 0, 2, 2, 5, 1, BLANK]          # unordered, with a gap, a repeat and the empty frame
+PER_FRAME = 350
+SENTINEL = -77
+
+
+def frame_images():
+    return np.stack([np.full((H, W), 127, np.uint8) if f is None else synth_frame(f[0], W, H, shift_xy=f[1]) for f in FRAMES])
+
+
+def build_scene(kd, sf, seed=5, kf_index=None):
+    """kd: per frame (keys, desc); kf_index: the targets (one flag row each).  Everything the calls and the oracle need,
+    as host arrays."""
+    kf_index = KF_INDEX if kf_index is None else kf_index
+    from orb_slam2_comment_amd.matcher import make_camera
+    rng = np.random.default_rng(seed)
+    cam = make_camera(KITTI_FX, KITTI_FY, KITTI_CX, KITTI_CY, (0.0, 0.0, float(W), float(H)), sf, mbf=KITTI_BF,
+                      mb=KITTI_BF / KITTI_FX)
+    S = dict(cam=cam, sf=np.asarray(sf, np.float32), kd=kd)
+    S["inv_sigma2"] = (1.0 / (S["sf"] * S["sf"])).astype(np.float32)
+    S["T"] = [_pose(rng) for _ in kd]
+    S["ur"] = [np.where(rng.random(len(k)) < 0.5, k["x"] - rng.uniform(2, 60, len(k)), -1).astype(np.float32) for k, _ in kd]
+    parts, descs = [], []
+    for f, (k, d) in enumerate(kd):
+        if len(k) == 0:
+            continue
+        sel = np.sort(rng.choice(len(k), min(PER_FRAME, len(k)), replace=False))
+        X, nrm, max_d, min_d = _synthetic_map_for(k[sel], cam, S["T"][f], rng)
+        X += rng.normal(0, 0.01, X.shape).astype(np.float32)
+        parts.append((X, nrm, max_d, min_d))
+        descs.append(d[sel] ^ (rng.random(d[sel].shape) < 0.03).astype(np.uint8) * rng.integers(1, 256, d[sel].shape, dtype=np.uint8))
+    # the gates of the prologue, each failed on purpose, as seen from the first target
+    f0 = kf_index[0]
+    k0 = kd[f0][0][:120]
+    Xs, ns, mxs, mns = _synthetic_map_for(k0, cam, S["T"][f0], rng)
+    z = rng.uniform(4, 40, 30).astype(np.float32)
+    Xs[0:30] = _back_project(k0[0:30], -z, cam, S["T"][f0])                         # behind the camera
+    far = k0[30:60].copy()
+    far["x"] += np.where(rng.random(30) < 0.5, -2000, 2000).astype(np.float32)
+    Xs[30:60] = _back_project(far, z, cam, S["T"][f0])                             # outside the image
+    mxs[60:75] *= np.float32(0.3); mns[60:75] *= np.float32(0.3)                   # too far for the range
+    mxs[75:90] *= np.float32(300.0); mns[75:90] *= np.float32(300.0)               # too close for the range
+    ns[90:120] = -ns[90:120]                                                       # seen from behind the surface
+    S["special"] = dict(behind=(0, 30), outside=(30, 60), range=(60, 90), normal=(90, 120))
+    parts.append((Xs, ns, mxs, mns))
+    descs.append(kd[f0][1][:120].copy())
+    S["n_regular"] = sum(len(p[0]) for p in parts[:-1])
+    S["X"], S["nrm"], S["max_d"], S["min_d"] = (np.ascontiguousarray(np.concatenate([p[i] for p in parts])) for i in range(4))
+    S["pdesc"] = np.ascontiguousarray(np.concatenate(descs))
+    S["np"] = len(S["X"])
+    S["flags"] = (rng.random((len(kf_index), S["np"])) < 0.9).astype(np.uint8)     # IsInKeyFrame differs per target
+    S["flags"][:, S["n_regular"]:] = 1
+    return S
+
+
+def oracle_rows(O, S, kf_index, flags, th, sim3_form, X=None, nrm=None, max_d=None, min_d=None, pdesc=None, ur=None, kd=None):
+    """Expected (queries, best_idx, best_dist) per row: the oracle's prologue and search, one key frame at a time."""
+    X = S["X"] if X is None else X
+    nrm = S["nrm"] if nrm is None else nrm
+    max_d = S["max_d"] if max_d is None else max_d
+    min_d = S["min_d"] if min_d is None else min_d
+    pdesc = S["pdesc"] if pdesc is None else pdesc
+    kd = S["kd"] if kd is None else kd
+    rows = []
+    for r, f in enumerate(kf_index):
+        oq = O.keyframe_queries(S["cam"], 0, sim3_form, S["T"][f], None, X, nrm, max_d, min_d, flags[r], th)
+        k, d = kd[f]
+        if len(k) == 0:
+            rows.append((oq, np.full(len(X), -1, np.int32), np.full(len(X), 256, np.int32)))
+            continue
+        keep = []
+        u = None if ur is None else ur[f]
+        ov = O.make_frame(k, d, u, (0.0, 0.0, float(W), float(H)), S["sf"], keep)
+        obi, obd = O.search_best_in_window(ov, oq, pdesc, S["inv_sigma2"])
+        rows.append((oq, obi, obd))
+    return rows
+
+
+def check_not_vacuous(S, rows, kf_index):
+    for r, f in enumerate(kf_index):
+        if len(S["kd"][f][0]) == 0:
+            continue
+        oq, obi, obd = rows[r]
+        assert 200 < oq["valid"].sum() < S["np"], (r, oq["valid"].sum())
+        assert (obd <= 50).sum() > 150, (r, (obd <= 50).sum())
+    q0 = rows[0][0]["valid"][S["n_regular"]:]
+    for name, (a, b) in S["special"].items():
+        assert b > a and (q0[a:b] == 0).all(), name
+
+
+class Device:
+    """The extracted batch and the scene on the device."""
+
+    def __init__(self, pkg, S, ext_out, torch):
+        self.torch = torch
+        self.d_k, self.d_d, self.d_n, self.cap = ext_out
+        dev = self.d_k.device
+        B = len(FRAMES)
+        ur = np.full((B, self.cap), -1, np.float32)
+        for f in range(B):
+            ur[f, :len(S["ur"][f])] = S["ur"][f]
+        self.d_ur = torch.from_numpy(ur).to(dev)
+        self.d_T = torch.from_numpy(np.stack([np.ascontiguousarray(T[:3, :4]).reshape(12) for T in S["T"]])).to(dev)
+        self.dev = dev
+
+    def points(self, X, nrm, max_d, min_d, pdesc, pad):
+        t, dev, n = self.torch, self.dev, len(X)
+
+        def up(a, fill):
+            full = np.full((n + pad,) + a.shape[1:], fill, a.dtype)
+            full[:n] = a
+            return t.from_numpy(full).to(dev)
+        return up(X, 1e9), up(nrm, 1e9), up(max_d, 1e9), up(min_d, 1e9), up(pdesc, 0xAA)
+
+    def run(self, m, S, kf_index, flags, th, sim3_form, pts=None, pad=37, csr=None, u_right=True, want_q=True, sync=True):
+        t, dev = self.torch, self.dev
+        X, nrm, max_d, min_d, pdesc = pts if pts is not None else (S["X"], S["nrm"], S["max_d"], S["min_d"], S["pdesc"])
+        n, K = len(X), len(kf_index)
+        pcap = n + pad
+        dX, dN, dMx, dMn, dP = self.points(X, nrm, max_d, min_d, pdesc, pad)
+        fl = np.full((K, pcap), 1, np.uint8)
+        fl[:, :n] = flags
+        d_fl = t.from_numpy(fl).to(dev)
+        d_idx = t.tensor(kf_index, dtype=t.int32, device=dev)
+        d_Tk = self.d_T[t.tensor(kf_index, dtype=t.int64, device=dev)].contiguous()
+        d_bi = t.full((K, pcap), SENTINEL, dtype=t.int32, device=dev)
+        d_bd = t.full((K, pcap), SENTINEL, dtype=t.int32, device=dev)
+        d_q = t.full((K, pcap, 10), SENTINEL, dtype=t.int32, device=dev)
+        t.cuda.synchronize()
+        m.FuseDevice(K, d_idx.data_ptr(), S["cam"], d_Tk.data_ptr(), self.d_k.data_ptr(), self.d_d.data_ptr(), self.d_n.data_ptr(),
+                     self.cap, n, pcap, dX.data_ptr(), dN.data_ptr(), dMx.data_ptr(), dMn.data_ptr(), dP.data_ptr(),
+                     d_fl.data_ptr(), th, S["inv_sigma2"], d_bi.data_ptr(), d_bd.data_ptr(), sim3_form=sim3_form,
+                     d_u_right=self.d_ur.data_ptr() if u_right else 0, d_cell_start=csr[0].data_ptr() if csr else 0,
+                     d_cell_items=csr[1].data_ptr() if csr else 0, d_q=d_q.data_ptr() if want_q else 0)
+        keep = (dX, dN, dMx, dMn, dP, d_fl, d_idx, d_Tk)
+        if not sync:
+            return d_bi, d_bd, d_q, keep
+        m.sync()
+        return d_bi.cpu().numpy(), d_bd.cpu().numpy(), d_q.cpu().numpy(), keep
+
+
+def compare(pkg, out, rows, n, with_q=True):
+    bi, bd, q = out[:3]
+    for r, (oq, obi, obd) in enumerate(rows):
+        if with_q:
+            got = np.ascontiguousarray(q[r, :n]).view(pkg.QUERY_DTYPE).reshape(n)
+            _assert_queries_equal(got, oq, "row %d" % r)
+        assert np.array_equal(bi[r, :n], obi), (r, np.nonzero(bi[r, :n] != obi)[0][:5])
+        assert np.array_equal(bd[r, :n], obd), (r, np.nonzero(bd[r, :n] != obd)[0][:5])
+    assert (bi[:, n:] == SENTINEL).all() and (bd[:, n:] == SENTINEL).all()
+    if with_q:
+        assert (q[:, n:] == SENTINEL).all()
+
+
+@pytest.fixture(scope="module")
+def env(oracle):
+    import torch
+    import orb_slam2_comment_amd as pkg
+    ext = pkg.ORBextractor(NF, 1.2, 8, 20, 7)
+    cap = ext.capacity(H, W)
+    dev = torch.device("cuda:0")
+    B = len(FRAMES)
+    d_img = torch.from_numpy(frame_images()).to(dev)
+    d_k = torch.zeros((B, cap, 7), dtype=torch.int32, device=dev)
+    d_d = torch.zeros((B, cap, 32), dtype=torch.uint8, device=dev)
+    d_n = torch.zeros(B, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    ext.extract_batch_device(d_img.data_ptr(), B, H, W, d_k.data_ptr(), d_d.data_ptr(), cap, d_n.data_ptr())
+    ext.sync()
+    n = d_n.cpu().numpy()
+    hk = d_k.cpu().numpy().view(np.uint8).reshape(B, cap, 28).view(pkg.KP_DTYPE).reshape(B, cap)
+    hd = d_d.cpu().numpy()
+    kd = [(hk[f, :n[f]].copy(), hd[f, :n[f]].copy()) for f in range(B)]
+    assert n[BLANK] == 0 and all(n[f] > 800 for f in range(B) if f != BLANK) and cap > n.max()
+    S = build_scene(kd, ext.GetScaleFactors())
+    D = Device(pkg, S, (d_k, d_d, d_n, cap), torch)
+    m = pkg.ORBmatcher(0.6, True)
+    expected = {}
+
+    def rows_for(sim3_form, th):
+        if (sim3_form, th) not in expected:
+            expected[(sim3_form, th)] = oracle_rows(oracle, S, KF_INDEX, S["flags"], th, sim3_form, ur=S["ur"])
+        return expected[(sim3_form, th)]
+    return dict(pkg=pkg, O=oracle, S=S, D=D, m=m, torch=torch, rows_for=rows_for)
+
+
+def _csr(env):
+    t, D, S = env["torch"], env["D"], env["S"]
+    B = len(FRAMES)
+    d_cell = t.full((B, D.cap), -9, dtype=t.int32, device=D.dev)
+    d_items = t.full((B, D.cap), -9, dtype=t.int32, device=D.dev)
+    d_start = t.full((B, 64 * 48 + 1), -9, dtype=t.int32, device=D.dev)
+    env["m"].AssignFeaturesToGridDevice(B, D.d_k.data_ptr(), D.d_n.data_ptr(), D.cap, (0.0, 0.0, float(W), float(H)),
+                                        d_cell.data_ptr(), d_start.data_ptr(), d_items.data_ptr())
+    return d_start, d_items, d_cell
+
+
+@pytest.mark.parametrize("sim3_form,th", [(False, 3.0), (True, 4.0)])
+def test_rows_equal_the_oracle_per_key_frame(env, sim3_form, th):
+    """K = 7 targets in any order, with a gap, a repeat and an empty frame; flags differ per row; pcap = np + 37."""
+    S = env["S"]
+    rows = env["rows_for"](sim3_form, th)
+    check_not_vacuous(S, rows, KF_INDEX)
+    assert not np.array_equal(S["flags"][2], S["flags"][3])          # the repeated key frame with two flag rows
+    assert not np.array_equal(rows[2][1], rows[3][1])
+    out = env["D"].run(env["m"], S, KF_INDEX, S["flags"], th, sim3_form)
+    compare(env["pkg"], out, rows, S["np"])
+
+
+def test_internal_grid_equals_the_callers_grid(env):
+    S = env["S"]
+    a = env["D"].run(env["m"], S, KF_INDEX, S["flags"], 3.0, False)
+    b = env["D"].run(env["m"], S, KF_INDEX, S["flags"], 3.0, False, csr=_csr(env))
+    for x, y in zip(a[:3], b[:3]):
+        assert np.array_equal(x, y)
+    compare(env["pkg"], b, env["rows_for"](False, 3.0), S["np"])
+
+
+def tie_groups(k, sf, th):
+    """Pairs (a, b) of same-octave key points in different grid cells, close enough to share the window (th >= 3) of a point
+    projected between them, disjoint, where GetFeaturesInArea's order (cell-major, x outer) visits the HIGHER index first."""
+    f32 = np.float32
+    cx = np.round(k["x"] * (f32(64) / f32(W))).astype(np.int64)
+    cy = np.round(k["y"] * (f32(48) / f32(H))).astype(np.int64)
+    cell = cx * 48 + cy
+    used, groups = set(), []
+    for a in range(len(k)):
+        if a in used:
+            continue
+        s = sf[k["octave"][a]]
+        # half their distance passes the chi-square gate 5.99 at this level (and so lies inside the window th * s, th >= 3)
+        near = np.nonzero((k["octave"] == k["octave"][a]) & (cell != cell[a]) &
+                          ((k["x"] - k["x"][a]) ** 2 + (k["y"] - k["y"][a]) ** 2 < 20 * s * s))[0]
+        for b in near:
+            b = int(b)
+            if b in used or b == a:
+                continue
+            first = a if cell[a] < cell[b] else b
+            if first == max(a, b):                      # a lowest-index tie-break would pick the other one
+                groups.append((a, b, first))
+                used.update((a, b))
+                break
+    return groups
+
+
+def tie_scene(S, f, th, seed=9):
+    rng = np.random.default_rng(seed)
+    k, d = S["kd"][f]
+    groups = tie_groups(k, S["sf"], th)
+    d2 = d.copy()
+    mid = np.zeros(len(groups), k.dtype)
+    pdesc = np.zeros((len(groups), 32), np.uint8)
+    for g, (a, b, _) in enumerate(groups):
+        pdesc[g] = rng.integers(0, 256, 32, dtype=np.uint8)
+        d2[a] = pdesc[g]; d2[b] = pdesc[g]
+        mid[g] = k[a]
+        mid["x"][g] = (k["x"][a] + k["x"][b]) / 2
+        mid["y"][g] = (k["y"][a] + k["y"][b]) / 2
+    X, nrm, max_d, min_d = _synthetic_map_for(mid, S["cam"], S["T"][f], rng)
+    # PredictScale lands on the key points' octave: log(max_d / dist) / log(1.2) = octave - 0.3
+    R, t = S["T"][f][:3, :3].astype(np.float64), S["T"][f][:3, 3].astype(np.float64)
+    dist = np.linalg.norm(X.astype(np.float64) + R.T @ t, axis=1)
+    max_d = (dist * 1.2 ** (mid["octave"] - 0.3)).astype(np.float32)
+    min_d = (max_d / np.float32(1.2 ** 7)).astype(np.float32)
+    nrm = ((X.astype(np.float64) + R.T @ t) / dist[:, None]).astype(np.float32)
+    return groups, d2, (X, nrm, max_d, min_d, pdesc)
+
+
+def test_ties_go_to_the_first_in_grid_order(env):
+    """Equal distances: the winner is the first key point GetFeaturesInArea returns (cell-major), not the lowest index."""
+    S, D, t = env["S"], env["D"], env["torch"]
+    f, th = 0, 3.0
+    groups, d2, pts = tie_scene(S, f, th)
+    kd = list(S["kd"])
+    kd[f] = (S["kd"][f][0], d2)
+    flags = np.ones((1, len(groups)), np.uint8)
+    rows = oracle_rows(env["O"], S, [f], flags, th, False, *pts, ur=None, kd=kd)
+    obi, obd = rows[0][1], rows[0][2]
+    tied = [g for g, (a, b, first) in enumerate(groups) if obd[g] == 0 and obi[g] == first and obi[g] != min(a, b)]
+    assert len(tied) >= 5, len(tied)
+    saved = D.d_d[f, :len(d2)].clone()
+    D.d_d[f, :len(d2)] = t.from_numpy(d2).to(D.dev)
+    try:
+        out = D.run(env["m"], S, [f], flags, th, False, pts=pts, u_right=False)
+    finally:
+        D.d_d[f, :len(d2)] = saved
+        t.cuda.synchronize()
+    compare(env["pkg"], out, rows, len(groups))
+
+
+def border_points(S, f, seed=13):
+    """Points that project within 2 px of every edge and corner of the image, over all predicted levels."""
+    rng = np.random.default_rng(seed)
+    us = np.concatenate([rng.uniform(0.01, 2, 40), rng.uniform(W - 2, W - 0.01, 40), rng.uniform(0, W, 80),
+                         rng.uniform(0.01, 2, 20), rng.uniform(W - 2, W - 0.01, 20)])
+    vs = np.concatenate([rng.uniform(0, H, 80), rng.uniform(0.01, 2, 40), rng.uniform(H - 2, H - 0.01, 40),
+                         np.where(rng.random(40) < 0.5, rng.uniform(0.01, 2, 40), rng.uniform(H - 2, H - 0.01, 40))])
+    k = np.zeros(len(us), S["kd"][f][0].dtype)
+    k["x"], k["y"], k["octave"] = us.astype(np.float32), vs.astype(np.float32), rng.integers(0, 8, len(us))
+    X, nrm, max_d, min_d = _synthetic_map_for(k, S["cam"], S["T"][f], rng)
+    return X, nrm, max_d, min_d, rng.integers(0, 256, (len(us), 32), dtype=np.uint8)
+
+
+@pytest.mark.parametrize("th", [3.0, 12.0])
+def test_windows_at_the_image_border(env, th):
+    """Clamped cell ranges: nMinCell < 0 and nMaxCell past the last column / row on every side and in every corner.  (The
+    chi-square gate keeps nearly every such point without a match: the extractor leaves the border free of key points.)"""
+    S = env["S"]
+    f = 1
+    pts = border_points(S, f)
+    n = len(pts[0])
+    kf_index = [f, 5]
+    flags = np.ones((2, n), np.uint8)
+    rows = oracle_rows(env["O"], S, kf_index, flags, th, False, *pts, ur=S["ur"])
+    q = rows[0][0]
+    v = q["valid"] == 1
+    assert v.sum() > 100
+    for lo, hi, c in ((0, 2, "u"), (W - 2, W, "u"), (0, 2, "v"), (H - 2, H, "v")):
+        assert ((q[c][v] >= lo) & (q[c][v] < hi)).sum() > 10, (lo, c)
+    out = env["D"].run(env["m"], S, kf_index, flags, th, False, pts=pts)
+    compare(env["pkg"], out, rows, n)
+
+
+def test_host_entry_equals_single_calls_and_the_oracle(env):
+    pkg, S, m = env["pkg"], env["S"], env["m"]
+    pick = [4, 2, BLANK, 1]                              # rows 0, 2, 6, 5 of KF_INDEX
+    rws = [0, 2, 6, 5]
+    bounds = (0.0, 0.0, float(W), float(H))
+    views = [pkg.FrameView(S["kd"][f][0], S["kd"][f][1], S["sf"], bounds, S["ur"][f] if f != 2 else None) for f in pick]
+    flags = S["flags"][rws]
+    T = [S["T"][f] for f in pick]
+    args = (S["X"], S["nrm"], S["max_d"], S["min_d"])
+    bi, bd = m.FuseBatch(views, S["cam"], T, *args, flags, S["pdesc"], 3.0, S["inv_sigma2"])
+    assert bi.shape == (4, S["np"])
+    ur = list(S["ur"])
+    ur[2] = None
+    rows = oracle_rows(env["O"], S, pick, flags, 3.0, False, ur=ur)
+    for r in range(4):
+        sbi, sbd = m.Fuse(views[r], S["cam"], T[r], *args, flags[r], S["pdesc"], 3.0, S["inv_sigma2"])
+        assert np.array_equal(bi[r], sbi) and np.array_equal(bd[r], sbd), r
+        assert np.array_equal(bi[r], rows[r][1]) and np.array_equal(bd[r], rows[r][2]), r
+    assert (bd[0] <= 50).sum() > 150 and (bi[2] == -1).all() and (bd[2] == 256).all()
+    # K == 0 and n == 0 behave as the single-frame entry does
+    e = np.zeros((0, 3), np.float32)
+    bi0, _ = m.FuseBatch(views, S["cam"], T, e, e, e[:, 0], e[:, 0], np.zeros((4, 0), np.uint8), np.zeros((0, 32), np.uint8), 3.0,
+                         S["inv_sigma2"])
+    assert bi0.shape == (4, 0)
+
+
+def test_call_is_asynchronous_on_the_callers_stream(env):
+    """Issued on a user stream and read only after the device drained; a second, larger call on the same handle regrows
+    the handle's grid scratch."""
+    pkg, S, D, t = env["pkg"], env["S"], env["D"], env["torch"]
+    m = pkg.ORBmatcher(0.6, True)
+    stream = t.cuda.Stream()
+    m.set_stream(stream.cuda_stream)
+    n1 = 500
+    pts = tuple(a[:n1] for a in (S["X"], S["nrm"], S["max_d"], S["min_d"], S["pdesc"]))
+    kf1 = [2, 0]
+    fl1 = S["flags"][[2, 1]][:, :n1]
+    rows1 = oracle_rows(env["O"], S, kf1, fl1, 3.0, False, *pts, ur=S["ur"])
+    o1 = D.run(m, S, kf1, fl1, 3.0, False, pts=pts, sync=False)
+    o2 = D.run(m, S, KF_INDEX, S["flags"], 3.0, False, sync=False)
+    t.cuda.synchronize()
+    compare(pkg, tuple(x.cpu().numpy() for x in o1[:3]), rows1, n1)
+    compare(pkg, tuple(x.cpu().numpy() for x in o2[:3]), env["rows_for"](False, 3.0), S["np"])
+    m.set_stream(0)
+    m.close()
