@@ -698,6 +698,66 @@ int orbhip_count_close_points(orbhip_matcher *m, const float *depth, const uint8
 int orbhip_count_close_points_device(orbhip_matcher *m, int frames, const void *d_depth, const void *d_flags, const void *d_n,
                                      int cap, float th_depth, void *d_counts);
 
+/* ---- creating new map points -------------------------------------------------------------------------------------
+ * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) for the current key frame and K neighbours in one call, up
+ * to the point where the map graph is touched: `new MapPoint`, AddObservation and everything after :434 stay with the
+ * caller, as does ComputeSceneMedianDepth (:256).  Replaces, per neighbour, the baseline gate (:244-261), ComputeF12
+ * (:536-553), the epipole (src/ORBmatcher.cc:664-670), ORBmatcher::SearchForTriangulation (:657-823) and the loop body
+ * :286-431 (parallax test, linear triangulation or UnprojectStereo, two positive-depth tests, two reprojection tests,
+ * scale consistency).  The operation order of the float arithmetic, and the two stated choices (cos(2 atan2) as a rational
+ * expression, one-sided Jacobi SVD of the 4x4 system), are in DESIGN.md section 3.
+ *
+ * Frames are rows of arrays in the extractor's output layout: d_kps [..][cap] orbhip_keypoint (mvKeysUn), d_desc
+ * [..][cap][32], d_n [..] int32, d_u_right / d_depth [..][cap] float (mvuRight / mvDepth; both NULL = monocular), d_node
+ * [..][cap] uint32 as orbhip_vocabulary_transform_device writes it, d_has_point [..][cap] uint8 (the slot already holds a
+ * map point; NULL = none does), d_Tcw [..][12] = [Rcw | tcw] per frame row.  `cur` is the row of mpCurrentKeyFrame,
+ * d_kf_index [K] int32 the neighbour rows: any order, gaps, repeats and `cur` itself are allowed.  One camera for all
+ * frames (the reference itself uses mpCurrentKeyFrame->mbf for key frame 2, :406); mfScaleFactor of ratioFactor (:232) is
+ * cam->scale_factors[1] (scale_factors[0] with one level).  level_sigma2 [cam->n_levels] = mvLevelSigma2 (host).
+ * UnprojectStereo (:342, :346) is evaluated on d_kps; KeyFrame::UnprojectStereo reads mvKeys (src/KeyFrame.cc:620), which
+ * equals mvKeysUn for the rectified stereo / RGB-D input this branch exists for.
+ * Baseline gate: stereo / RGB-D (d_u_right given, d_median_depth NULL) skips a neighbour when baseline < cam->mb;
+ * monocular (d_u_right NULL) needs d_median_depth [K] float = pKF2->ComputeSceneMedianDepth(2) per neighbour and skips
+ * when (float)(baseline / median) < 0.01.
+ * Outputs, row k = neighbour k, entry i = key point i of the current key frame: d_matches12 [K][cap] int32 (what
+ * orbhip_search_for_triangulation returns for that pair), d_nmatches [K] int32, d_x3d [K][cap][3] float (the point where
+ * one was computed, i.e. status 0 or >= ORBHIP_NEWPOINT_BEHIND_1, else zeros), d_status [K][cap] uint8 (ORBHIP_NEWPOINT_*,
+ * one per way out of the loop body), d_skipped [K] uint8 (the baseline gate fired: nmatches 0, every entry NO_MATCH);
+ * optional d_f12 [K][9] / d_epipole [K][2] float (zeros for a skipped row).  Entries >= n[cur] stay untouched.
+ * has_point is read as it is at call time: INTEGRATION.md section 3 says how the caller applies the rows in order.
+ * Asynchronous on the matcher's stream, no host synchronisation, no staging copy: three launches, four with check_ori.
+ * cap <= 4096 (ORBHIP_E_CAPACITY beyond); bad arguments are refused before any device work; K == 0 or n[cur] == 0:
+ * success, nothing written. */
+#define ORBHIP_NEWPOINT_CREATED      0  /* passed every gate: the caller creates the MapPoint (:434) */
+#define ORBHIP_NEWPOINT_NO_MATCH     1  /* SearchForTriangulation gave this key point no partner */
+#define ORBHIP_NEWPOINT_LOW_PARALLAX 2  /* no stereo and very low parallax (:349) */
+#define ORBHIP_NEWPOINT_W_ZERO       3  /* homogeneous coordinate 0 (:333) */
+#define ORBHIP_NEWPOINT_BEHIND_1     4  /* z1 <= 0 (:355) */
+#define ORBHIP_NEWPOINT_BEHIND_2     5  /* z2 <= 0 (:359) */
+#define ORBHIP_NEWPOINT_REPROJ_1     6  /* reprojection error in the current key frame (:374, :385) */
+#define ORBHIP_NEWPOINT_REPROJ_2     7  /* reprojection error in the neighbour (:400, :411) */
+#define ORBHIP_NEWPOINT_ZERO_DIST    8  /* dist1 == 0 || dist2 == 0 (:422) */
+#define ORBHIP_NEWPOINT_SCALE        9  /* scale consistency (:430) */
+int orbhip_create_new_map_points_device(orbhip_matcher *m, int cur, int K, const void *d_kf_index, const orbhip_camera *cam,
+                                        const void *d_Tcw, const void *d_kps, const void *d_desc, const void *d_n, int cap,
+                                        const void *d_u_right, const void *d_depth, const void *d_node, const void *d_has_point,
+                                        const void *d_median_depth, int only_stereo, int check_ori, const float *level_sigma2,
+                                        void *d_matches12, void *d_nmatches, void *d_x3d, void *d_status, void *d_skipped,
+                                        void *d_f12, void *d_epipole);
+/* Host buffers, synchronous: one staging copy, one device call, one read-back.  cur / kfs[K]: views of the current key
+ * frame and the neighbours (u_right set on all non-empty ones or on none); node_cur / node[k], has_point_cur / has_point[k]
+ * (nullable, also per entry), depth_cur / depth[k] (stereo only): one entry per key point; Tcw_cur [12], Tcw [K][12];
+ * median_depth [K] (monocular only).  Outputs are packed by the current key frame's count n = cur->n: matches12 [K][n],
+ * nmatches [K], x3d [K][n][3], status [K][n], skipped [K], optional f12 [K][9] / epipole [K][2].  A key frame with more
+ * than 4096 key points: ORBHIP_E_CAPACITY, as orbhip_search_for_triangulation. */
+int orbhip_create_new_map_points(orbhip_matcher *m, const orbhip_frame_view *cur, const uint32_t *node_cur,
+                                 const uint8_t *has_point_cur, const float *depth_cur, const float *Tcw_cur, int K,
+                                 const orbhip_frame_view *const *kfs, const uint32_t *const *node, const uint8_t *const *has_point,
+                                 const float *const *depth, const float *Tcw, const float *median_depth,
+                                 const orbhip_camera *cam, int only_stereo, int check_ori, const float *level_sigma2,
+                                 int32_t *matches12, int32_t *nmatches, float *x3d, uint8_t *status, uint8_t *skipped,
+                                 float *f12, float *epipole);
+
 /* Launch on a caller-owned hipStream_t (NULL: the handle's own stream); wait for the handle's stream. */
 int orbhip_matcher_set_stream(orbhip_matcher *m, void *stream);
 int orbhip_matcher_sync(orbhip_matcher *m);

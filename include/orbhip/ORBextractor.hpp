@@ -443,6 +443,53 @@ public:
                                  invLevelSigma2, dBestIdx, dBestDist, dQ), "orbhip_fuse_device");
     }
 
+    // void LocalMapping::CreateNewMapPoints() (src/LocalMapping.cc:207-452) up to `new MapPoint`, for the current key frame
+    // and its K neighbours in one call: baseline gate, ComputeF12 (:536-553), SearchForTriangulation and the loop body
+    // :286-431.  Host buffers; per-key-point arrays as orbhip_create_new_map_points takes them (hasPoint* nullable, depth*
+    // stereo only, medianDepth [K] monocular only).  Outputs are packed by the current key frame's count n: matches12 /
+    // status [K][n], x3D [K][n][3], nmatches / skipped [K]; status holds ORBHIP_NEWPOINT_*.  The caller applies the rows
+    // in neighbour order ("Creating new map points").
+    struct NewMapPoints {
+        std::vector<int> matches12, nmatches;
+        std::vector<float> x3D, f12, epipole;
+        std::vector<uint8_t> status, skipped;
+    };
+    void CreateNewMapPoints(const orbhip_frame_view &cur, const uint32_t *nodeCur, const uint8_t *hasPointCur,
+                            const float *depthCur, const float *TcwCur, const std::vector<const orbhip_frame_view *> &KFs,
+                            const std::vector<const uint32_t *> &node, const std::vector<const uint8_t *> &hasPoint,
+                            const std::vector<const float *> &depth, const float *Tcw, const float *medianDepth,
+                            const orbhip_camera &cam, bool onlyStereo, const float *levelSigma2, NewMapPoints &out)
+    {
+        const size_t K = KFs.size(), n = (size_t)(cur.n > 0 ? cur.n : 0), kn = K * n;
+        out.matches12.assign(kn ? kn : 1, -1);
+        out.status.assign(kn ? kn : 1, (uint8_t)ORBHIP_NEWPOINT_NO_MATCH);
+        out.x3D.assign(kn ? kn * 3 : 1, 0.f);
+        out.nmatches.assign(K ? K : 1, 0);
+        out.skipped.assign(K ? K : 1, 0);
+        out.f12.assign(K ? K * 9 : 1, 0.f);
+        out.epipole.assign(K ? K * 2 : 1, 0.f);
+        check(orbhip_create_new_map_points(m_, &cur, nodeCur, hasPointCur, depthCur, TcwCur, (int)K, KFs.data(), node.data(),
+                                           hasPoint.empty() ? nullptr : hasPoint.data(), depth.empty() ? nullptr : depth.data(),
+                                           Tcw, medianDepth, &cam, onlyStereo ? 1 : 0, mbCheckOrientation ? 1 : 0, levelSigma2,
+                                           out.matches12.data(), out.nmatches.data(), out.x3D.data(), out.status.data(),
+                                           out.skipped.data(), out.f12.data(), out.epipole.data()),
+              "orbhip_create_new_map_points");
+        out.matches12.resize(kn); out.status.resize(kn); out.x3D.resize(kn * 3);
+        out.nmatches.resize(K); out.skipped.resize(K); out.f12.resize(K * 9); out.epipole.resize(K * 2);
+    }
+    // device frames, asynchronous on the matcher's stream: orbhip_create_new_map_points_device with the mirror's handle
+    void CreateNewMapPointsDevice(int cur, int K, const void *dKfIndex, const orbhip_camera &cam, const void *dTcw,
+                                  const void *dKps, const void *dDesc, const void *dN, int cap, const void *dURight,
+                                  const void *dDepth, const void *dNode, const void *dHasPoint, const void *dMedianDepth,
+                                  bool onlyStereo, const float *levelSigma2, void *dMatches12, void *dNMatches, void *dX3D,
+                                  void *dStatus, void *dSkipped, void *dF12 = nullptr, void *dEpipole = nullptr)
+    {
+        check(orbhip_create_new_map_points_device(m_, cur, K, dKfIndex, &cam, dTcw, dKps, dDesc, dN, cap, dURight, dDepth, dNode,
+                                                  dHasPoint, dMedianDepth, onlyStereo ? 1 : 0, mbCheckOrientation ? 1 : 0,
+                                                  levelSigma2, dMatches12, dNMatches, dX3D, dStatus, dSkipped, dF12, dEpipole),
+              "orbhip_create_new_map_points_device");
+    }
+
     // int SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches12, const float &s12, const cv::Mat &R12,
     // const cv::Mat &t12, const float th) (src/ORBmatcher.cc:1102-1326), complete.  T1w / T2w: [R | t] of the two key
     // frames; S21 = [sR21 | t21], S12 = [sR12 | t12] as the reference computes them (:1119-1121).  Per key-frame slot: the

@@ -44,6 +44,9 @@ POINT_PRESENT, POINT_OBSERVED = 1, 2
 COLOR_BGR, COLOR_RGB = 0, 1
 DEPTH_U16, DEPTH_F32 = 0, 1
 SEED_ALL, SEED_CLOSEST = 0, 1
+# ORBHIP_NEWPOINT_*: d_status of orbhip_create_new_map_points*, one code per way out of the loop body
+(NEWPOINT_CREATED, NEWPOINT_NO_MATCH, NEWPOINT_LOW_PARALLAX, NEWPOINT_W_ZERO, NEWPOINT_BEHIND_1, NEWPOINT_BEHIND_2,
+ NEWPOINT_REPROJ_1, NEWPOINT_REPROJ_2, NEWPOINT_ZERO_DIST, NEWPOINT_SCALE) = range(10)
 REMAP_TABLE_SIZE = 4096
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
@@ -131,6 +134,10 @@ SYMBOLS = [
     ("orbhip_fuse_device", _i, [_vp, _i, _vp, C.POINTER(Camera), _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp,
                                 _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     ("orbhip_fuse_batch", _i, [_vp, _i, _vp, C.POINTER(Camera), _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
+    ("orbhip_create_new_map_points_device", _i, [_vp, _i, _i, _vp, C.POINTER(Camera), _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp,
+                                                 _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("orbhip_create_new_map_points", _i, [_vp, C.POINTER(FrameView), _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          C.POINTER(Camera), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("orbhip_search_by_sim3", _i, [_vp, C.POINTER(FrameView), C.POINTER(FrameView), C.POINTER(Camera), _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _pi]),
     ("orbhip_project_last_frame_device", _i, [_vp, _i, C.POINTER(Camera), _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _i,

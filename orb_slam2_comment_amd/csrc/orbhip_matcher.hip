@@ -665,6 +665,57 @@ struct TriParams {
     float sigma2[ORBHIP_MAX_LEVELS], sf[ORBHIP_MAX_LEVELS];
 };
 
+// The candidate scan of one query by one wavefront, shared by k_tri_search and k_cnmp_search: lanes over the train
+// keypoints of the query's node; a candidate is left out when tmask[j] != 0 equals mask_skip (tmask nullable) or, with
+// only_stereo, when it has no right coordinate (:725-729).  Returns the wave-uniform best key
+// distance << 32 | (0xfffff - index), ~0 = none.
+__device__ __forceinline__ unsigned long long tri_scan(const int lane, const int n, const orbhip_keypoint *__restrict__ keys,
+                                                       const uint8_t *__restrict__ desc, const float *__restrict__ u_right,
+                                                       const uint32_t *__restrict__ tnode, const uint8_t *__restrict__ tmask,
+                                                       const bool mask_skip, const bool only_stereo, const uint32_t qnode,
+                                                       const uint32_t (&qd)[8], const float qu, const float qv,
+                                                       const bool stereo1, const float (&f12)[9], const float ex,
+                                                       const float ey, const float *__restrict__ sigma2,
+                                                       const float *__restrict__ sf)
+{
+    // epipolar line of the query in image 2, ORBmatcher.cc:143-145
+    const float la = __fadd_rn(__fadd_rn(__fmul_rn(qu, f12[0]), __fmul_rn(qv, f12[3])), f12[6]);
+    const float lb = __fadd_rn(__fadd_rn(__fmul_rn(qu, f12[1]), __fmul_rn(qv, f12[4])), f12[7]);
+    const float lc = __fadd_rn(__fadd_rn(__fmul_rn(qu, f12[2]), __fmul_rn(qv, f12[5])), f12[8]);
+    const float den = __fadd_rn(__fmul_rn(la, la), __fmul_rn(lb, lb));
+    unsigned long long best = ~0ull;
+    for (int j = lane; j < n; j += 64) {
+        if (tnode[j] != qnode || (tmask && (tmask[j] != 0) == mask_skip)) continue;
+        // the right coordinate is read before the descriptor only where it filters (:725-729); k_tri_search, which never
+        // filters on it, reads it after the distance test as it always did
+        bool stereo2 = false;
+        if (only_stereo) {
+            stereo2 = u_right && u_right[j] >= 0;
+            if (!stereo2) continue;
+        }
+        const uint32_t *tp = reinterpret_cast<const uint32_t *>(desc + (size_t)j * 32);
+        uint32_t td[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) td[i] = tp[i];
+        const int dist = hamming256(qd, td);
+        if (dist > TH_LOW) continue;
+        if (!only_stereo) stereo2 = u_right && u_right[j] >= 0;
+        const orbhip_keypoint kp = keys[j];
+        if (!stereo1 && !stereo2) {   // :741-747
+            const float dx = __fsub_rn(ex, kp.x), dy = __fsub_rn(ey, kp.y);
+            if (__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) < __fmul_rn(100.f, sf[kp.octave])) continue;
+        }
+        // CheckDistEpipolarLine :147-156
+        const float num = __fadd_rn(__fadd_rn(__fmul_rn(la, kp.x), __fmul_rn(lb, kp.y)), lc);
+        if (den == 0) continue;
+        const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
+        if (!((double)dsqr < 3.84 * (double)sigma2[kp.octave])) continue;
+        const unsigned long long k = ((unsigned long long)dist << 32) | (uint32_t)(0xfffff - j);
+        best = k < best ? k : best;
+    }
+    return wave_min_u64(best);
+}
+
 __global__ __launch_bounds__(256) void k_tri_search(DevFrame F, const uint32_t *__restrict__ tnode,
                                                     const uint8_t *__restrict__ tvalid,
                                                     const orbhip_query *__restrict__ q,
@@ -676,41 +727,12 @@ __global__ __launch_bounds__(256) void k_tri_search(DevFrame F, const uint32_t *
     const int qi = blockIdx.x * 4 + wv;
     if (qi >= nq) return;
     const orbhip_query Q = q[qi];
-    const uint32_t qnode = (uint32_t)Q.level_aux;
     uint32_t qd[8];
     const uint32_t *qp = reinterpret_cast<const uint32_t *>(qdesc + (size_t)qi * 32);
 #pragma unroll
     for (int i = 0; i < 8; ++i) qd[i] = qp[i];
-    const bool stereo1 = Q.ur >= 0;
-    // epipolar line of the query in image 2, ORBmatcher.cc:143-145
-    const float la = __fadd_rn(__fadd_rn(__fmul_rn(Q.u, P.f12[0]), __fmul_rn(Q.v, P.f12[3])), P.f12[6]);
-    const float lb = __fadd_rn(__fadd_rn(__fmul_rn(Q.u, P.f12[1]), __fmul_rn(Q.v, P.f12[4])), P.f12[7]);
-    const float lc = __fadd_rn(__fadd_rn(__fmul_rn(Q.u, P.f12[2]), __fmul_rn(Q.v, P.f12[5])), P.f12[8]);
-    const float den = __fadd_rn(__fmul_rn(la, la), __fmul_rn(lb, lb));
-    unsigned long long best = ~0ull;
-    for (int j = lane; j < F.n; j += 64) {
-        if (tnode[j] != qnode || (tvalid && !tvalid[j])) continue;
-        const uint32_t *tp = reinterpret_cast<const uint32_t *>(F.desc + (size_t)j * 32);
-        uint32_t td[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) td[i] = tp[i];
-        const int dist = hamming256(qd, td);
-        if (dist > TH_LOW) continue;
-        const orbhip_keypoint kp = F.keys[j];
-        const bool stereo2 = F.u_right && F.u_right[j] >= 0;
-        if (!stereo1 && !stereo2) {   // :741-747
-            const float dx = __fsub_rn(P.ex, kp.x), dy = __fsub_rn(P.ey, kp.y);
-            if (__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) < __fmul_rn(100.f, P.sf[kp.octave])) continue;
-        }
-        // CheckDistEpipolarLine :147-156
-        const float num = __fadd_rn(__fadd_rn(__fmul_rn(la, kp.x), __fmul_rn(lb, kp.y)), lc);
-        if (den == 0) continue;
-        const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
-        if (!((double)dsqr < 3.84 * (double)P.sigma2[kp.octave])) continue;
-        const unsigned long long k = ((unsigned long long)dist << 32) | (uint32_t)(0xfffff - j);
-        best = k < best ? k : best;
-    }
-    best = wave_min_u64(best);
+    const unsigned long long best = tri_scan(lane, F.n, F.keys, F.desc, F.u_right, tnode, tvalid, false, false,
+                                             (uint32_t)Q.level_aux, qd, Q.u, Q.v, Q.ur >= 0, P.f12, P.ex, P.ey, P.sigma2, P.sf);
     if (lane == 0) {
         if (best == ~0ull) cnt[qi] = 0;
         else {
@@ -718,6 +740,402 @@ __global__ __launch_bounds__(256) void k_tri_search(DevFrame F, const uint32_t *
             cnt[qi] = 1;
         }
     }
+}
+
+// ---- LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) up to the map graph --------------------------------
+// For the current key frame (row `cur` of the extractor-layout arrays) and K neighbour rows kf_index[k]:
+//   k_cnmp_rows         one thread per neighbour: camera centres, the baseline gate (:244-261), ComputeF12 (:536-553) and
+//                       the epipole (src/ORBmatcher.cc:664-670) into a [K] table; zeroes nmatches[k]
+//   k_cnmp_search       one wavefront per (current keypoint, neighbour): SearchForTriangulation straight from the frame
+//                       rows (node equality, has_point / only_stereo filters), gates as k_tri_search (shared tri_scan)
+//   k_cnmp_cull         check_ori only, one workgroup per neighbour: the rotation cull of k_resolve_par mode 4 (same
+//                       rot_bin / three_maxima; with one pre-gated candidate per query that resolve does nothing else)
+//   k_cnmp_triangulate  one lane per (neighbour, current keypoint): :286-431, the 4x4 problem in registers
+// Arithmetic: DESIGN.md section 3 ("Creating new map points").
+struct CnmpRow { float f12[9]; float ex, ey; int skip; };
+struct CnmpLevels { float sigma2[ORBHIP_MAX_LEVELS], sf[ORBHIP_MAX_LEVELS]; };
+struct CnmpArgs {
+    const int *kf_index;               // [K]
+    const float *Tcw;                  // [..][12]
+    const orbhip_keypoint *keys;       // [..][cap]
+    const uint8_t *desc;               // [..][cap][32]
+    const int *n_dev;                  // [..]
+    const float *u_right, *depth;      // [..][cap] or both null (monocular)
+    const uint32_t *node;              // [..][cap]
+    const uint8_t *has_point;          // [..][cap] or null
+    const float *median_depth;         // [K], monocular only
+    int *matches12, *nmatches;         // [K][cap], [K]
+    float *x3d;                        // [K][cap][3]
+    uint8_t *status, *skipped;         // [K][cap], [K]
+    float *f12_out, *ep_out;           // [K][9], [K][2] or null
+    CnmpRow *table;                    // [K]
+    int cur, K, cap, only_stereo;
+};
+
+__device__ __forceinline__ float dot3f(float a0, float a1, float a2, float b0, float b1, float b2)
+{
+    return __fadd_rn(__fadd_rn(__fmul_rn(a0, b0), __fmul_rn(a1, b1)), __fmul_rn(a2, b2));
+}
+// C = A * B, 3x3 row-major, every element ((a0*b0 + a1*b1) + a2*b2) in float
+__device__ __forceinline__ void mat3_mul(const float *A, const float *B, float *C)
+{
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) C[r * 3 + c] = dot3f(A[r * 3], A[r * 3 + 1], A[r * 3 + 2], B[c], B[3 + c], B[6 + c]);
+}
+// cv::invert of a 3x3 CV_32F matrix (small-matrix path): cofactors and determinant in double, elements rounded to float
+__device__ __forceinline__ void mat3_inv(const float *M, float *out)
+{
+    const double m00 = M[0], m01 = M[1], m02 = M[2], m10 = M[3], m11 = M[4], m12 = M[5], m20 = M[6], m21 = M[7], m22 = M[8];
+    double d = m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20);
+    if (d == 0.0) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) out[i] = 0.f;
+        return;
+    }
+    d = 1.0 / d;
+    out[0] = (float)((m11 * m22 - m12 * m21) * d);
+    out[1] = (float)((m02 * m21 - m01 * m22) * d);
+    out[2] = (float)((m01 * m12 - m02 * m11) * d);
+    out[3] = (float)((m12 * m20 - m10 * m22) * d);
+    out[4] = (float)((m00 * m22 - m02 * m20) * d);
+    out[5] = (float)((m02 * m10 - m00 * m12) * d);
+    out[6] = (float)((m10 * m21 - m11 * m20) * d);
+    out[7] = (float)((m01 * m20 - m00 * m21) * d);
+    out[8] = (float)((m00 * m11 - m01 * m10) * d);
+}
+// Ow = -Rcw^T * tcw of a [R | t] row (src/KeyFrame.cc:66-67)
+__device__ __forceinline__ void camera_centre(const float *T, float *Ow)
+{
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Ow[c] = -dot3f(T[c], T[4 + c], T[8 + c], T[3], T[7], T[11]);
+}
+// cv::norm of a 3-vector: squares accumulated in double
+__device__ __forceinline__ double norm3d(float x, float y, float z)
+{
+    return __dsqrt_rn(((double)x * (double)x + (double)y * (double)y) + (double)z * (double)z);
+}
+// Frame / KeyFrame::UnprojectStereo (src/Frame.cc:666-680): X = Rcw^T * (x, y, z) + Ow
+__device__ __forceinline__ void unproject_stereo(const float *T, const float *Ow, float u, float v, float z, float cx, float cy,
+                                                 float invfx, float invfy, float *X)
+{
+    const float x = __fmul_rn(__fmul_rn(__fsub_rn(u, cx), z), invfx);
+    const float y = __fmul_rn(__fmul_rn(__fsub_rn(v, cy), z), invfy);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        X[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[r], x), __fmul_rn(T[4 + r], y)), __fmul_rn(T[8 + r], z)), Ow[r]);
+}
+
+__global__ __launch_bounds__(64) void k_cnmp_rows(CnmpArgs A, orbhip_camera cam)
+{
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= A.K) return;
+    const float *T1 = A.Tcw + (size_t)A.cur * 12, *T2 = A.Tcw + (size_t)A.kf_index[k] * 12;
+    float Ow1[3], Ow2[3];
+    camera_centre(T1, Ow1);
+    camera_centre(T2, Ow2);
+    // :246-261
+    const float baseline = (float)norm3d(__fsub_rn(Ow2[0], Ow1[0]), __fsub_rn(Ow2[1], Ow1[1]), __fsub_rn(Ow2[2], Ow1[2]));
+    bool skip;
+    if (A.median_depth) skip = (double)__fdiv_rn(baseline, A.median_depth[k]) < 0.01;
+    else skip = baseline < cam.mb;
+    CnmpRow row;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) row.f12[i] = 0.f;
+    row.ex = 0.f; row.ey = 0.f; row.skip = skip ? 1 : 0;
+    if (!skip) {
+        float R1[9], R2t[9], R12[9], nR12[9], t12[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { R1[r * 3 + c] = T1[r * 4 + c]; R2t[r * 3 + c] = T2[c * 4 + r]; }
+        mat3_mul(R1, R2t, R12);                         // :543
+#pragma unroll
+        for (int i = 0; i < 9; ++i) nR12[i] = -R12[i];  // (-R1w) * R2w.t(): negation commutes with the rounding
+#pragma unroll
+        for (int r = 0; r < 3; ++r)                     // :544
+            t12[r] = __fadd_rn(dot3f(nR12[r * 3], nR12[r * 3 + 1], nR12[r * 3 + 2], T2[3], T2[7], T2[11]), T1[r * 4 + 3]);
+        const float tx[9] = {0.f, -t12[2], t12[1], t12[2], 0.f, -t12[0], -t12[1], t12[0], 0.f};
+        const float Kt[9] = {cam.fx, 0.f, 0.f, 0.f, cam.fy, 0.f, cam.cx, cam.cy, 1.f};
+        const float Km[9] = {cam.fx, 0.f, cam.cx, 0.f, cam.fy, cam.cy, 0.f, 0.f, 1.f};
+        float Kti[9], Ki[9], M1[9], M2[9];
+        mat3_inv(Kt, Kti);
+        mat3_inv(Km, Ki);
+        mat3_mul(Kti, tx, M1);                          // :552, left to right
+        mat3_mul(M1, R12, M2);
+        mat3_mul(M2, Ki, row.f12);
+        // epipole of camera 1 in image 2, src/ORBmatcher.cc:664-670
+        float C2[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            C2[r] = __fadd_rn(dot3f(T2[r * 4], T2[r * 4 + 1], T2[r * 4 + 2], Ow1[0], Ow1[1], Ow1[2]), T2[r * 4 + 3]);
+        const float invz = __fdiv_rn(1.0f, C2[2]);
+        row.ex = __fadd_rn(__fmul_rn(__fmul_rn(cam.fx, C2[0]), invz), cam.cx);
+        row.ey = __fadd_rn(__fmul_rn(__fmul_rn(cam.fy, C2[1]), invz), cam.cy);
+    }
+    A.table[k] = row;
+    if (A.n_dev[A.cur] <= 0) return;   // empty current key frame: the call writes nothing
+    A.nmatches[k] = 0;
+    A.skipped[k] = (uint8_t)row.skip;
+    if (A.f12_out)
+#pragma unroll
+        for (int i = 0; i < 9; ++i) A.f12_out[(size_t)k * 9 + i] = row.f12[i];
+    if (A.ep_out) { A.ep_out[(size_t)k * 2] = row.ex; A.ep_out[(size_t)k * 2 + 1] = row.ey; }
+}
+
+__global__ __launch_bounds__(256) void k_cnmp_search(CnmpArgs A, CnmpLevels L)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int k = blockIdx.y, qi = blockIdx.x * 4 + wv;
+    const size_t c = (size_t)A.cur, f = (size_t)A.kf_index[k];
+    const int n1 = max(min(A.n_dev[c], A.cap), 0);
+    if (qi >= n1) return;
+    int *out = A.matches12 + (size_t)k * A.cap;
+    const CnmpRow row = A.table[k];
+    const int n2 = max(min(A.n_dev[f], A.cap), 0);
+    const size_t q = c * A.cap + qi;
+    const uint32_t qnode = A.node[q];
+    const float ur1 = A.u_right ? A.u_right[q] : -1.0f;
+    const bool stereo1 = ur1 >= 0;
+    // queries of the reference: in the FeatureVector, no map point yet (:697-703), stereo when bOnlyStereo (:706-708)
+    if (row.skip || n2 == 0 || qnode == ORBHIP_NO_NODE || (A.has_point && A.has_point[q]) || (A.only_stereo && !stereo1)) {
+        if (lane == 0) out[qi] = -1;
+        return;
+    }
+    uint32_t qd[8];
+    const uint32_t *qp = reinterpret_cast<const uint32_t *>(A.desc + q * 32);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) qd[i] = qp[i];
+    const orbhip_keypoint kq = A.keys[q];
+    const unsigned long long best =
+        tri_scan(lane, n2, A.keys + f * A.cap, A.desc + f * A.cap * 32, A.u_right ? A.u_right + f * A.cap : nullptr,
+                 A.node + f * A.cap, A.has_point ? A.has_point + f * A.cap : nullptr, true, A.only_stereo != 0, qnode, qd,
+                 kq.x, kq.y, stereo1, row.f12, row.ex, row.ey, L.sigma2, L.sf);
+    if (lane == 0) out[qi] = best == ~0ull ? -1 : 0xfffff - (int)(best & 0xfffffu);
+}
+
+__global__ __launch_bounds__(1024) void k_cnmp_cull(CnmpArgs A)
+{
+    __shared__ int hist[HISTO_LENGTH];
+    __shared__ int ind[3];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const size_t c = (size_t)A.cur, f = (size_t)A.kf_index[k];
+    const int n1 = max(min(A.n_dev[c], A.cap), 0);
+    int *m12 = A.matches12 + (size_t)k * A.cap;
+    const orbhip_keypoint *k1 = A.keys + c * A.cap, *k2 = A.keys + f * A.cap;
+    if (tid < HISTO_LENGTH) hist[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < n1; i += 1024) {
+        const int j = m12[i];
+        if (j < 0) continue;
+        const int bin = rot_bin(k1[i].angle, k2[j].angle);
+        if (bin >= 0) atomicAdd(&hist[bin], 1);
+    }
+    __syncthreads();
+    if (tid < 64) {
+        int i1, i2, i3;
+        three_maxima(hist, i1, i2, i3);
+        if (tid == 0) { ind[0] = i1; ind[1] = i2; ind[2] = i3; }
+    }
+    __syncthreads();
+    const int ind1 = ind[0], ind2 = ind[1], ind3 = ind[2];
+    for (int i = tid; i < n1; i += 1024) {
+        const int j = m12[i];
+        if (j < 0) continue;
+        const int bin = rot_bin(k1[i].angle, k2[j].angle);
+        if (bin >= 0 && bin != ind1 && bin != ind2 && bin != ind3) m12[i] = -1;
+    }
+}
+
+// Correctly rounded fp32 square root.  NOT __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define that
+// one as the native approximation (a bare v_sqrt_f32, 1 ulp); the builtin gets the compiler's correctly rounded expansion.
+__device__ __forceinline__ float sqrt_rn(float x) { return __builtin_sqrtf(x); }
+__device__ __forceinline__ float dot4f(const float (&a)[4], const float (&b)[4])
+{
+    return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(a[0], b[0]), __fmul_rn(a[1], b[1])), __fmul_rn(a[2], b[2])),
+                     __fmul_rn(a[3], b[3]));
+}
+// Right singular vector of the smallest singular value of the 4x4 matrix whose COLUMNS are a[0..3]: one-sided (Hestenes)
+// Jacobi in fp32.  Pairs in the fixed order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); a pair is rotated unless
+// |a_p . a_q| <= 2 eps sqrt(|a_p|^2 |a_q|^2); the sweeps stop after one without a rotation, or after kJacobiSweeps.
+// Smallest = the column with the smallest squared norm, the first one on ties.  All indices are compile-time: registers.
+// The cap: on the triangulation matrices of the test scenes most systems stop by the rule after 4 or 5 sweeps; about one
+// in twelve never does (its null column is rounding noise, which no relative threshold calls orthogonal), but x3D has
+// stopped changing, bit for bit, after sweep 3 in every one of them.  8 leaves that a factor of two.
+constexpr int kJacobiSweeps = 8;
+__device__ __forceinline__ void jacobi_null4(float (&a)[4][4], float (&x)[4])
+{
+    float v[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[i][j] = i == j ? 1.f : 0.f;
+    const float eps = 2.384185791015625e-07f;   // 2 * FLT_EPSILON
+    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+        bool changed = false;
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 4; ++q) {
+                const float alpha = dot4f(a[p], a[p]), beta = dot4f(a[q], a[q]), gamma = dot4f(a[p], a[q]);
+                if (fabsf(gamma) <= __fmul_rn(eps, sqrt_rn(__fmul_rn(alpha, beta)))) continue;
+                changed = true;
+                const float p2 = __fmul_rn(gamma, 2.f), bt = __fsub_rn(alpha, beta);
+                const float g = sqrt_rn(__fadd_rn(__fmul_rn(p2, p2), __fmul_rn(bt, bt)));
+                float cs, sn;
+                if (bt < 0.f) {
+                    const float delta = __fmul_rn(__fsub_rn(g, bt), 0.5f);
+                    sn = sqrt_rn(__fdiv_rn(delta, g));
+                    cs = __fdiv_rn(p2, __fmul_rn(__fmul_rn(g, sn), 2.f));
+                } else {
+                    cs = sqrt_rn(__fdiv_rn(__fadd_rn(g, bt), __fmul_rn(g, 2.f)));
+                    sn = __fdiv_rn(p2, __fmul_rn(__fmul_rn(g, cs), 2.f));
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float ap = a[p][r], aq = a[q][r], vp = v[p][r], vq = v[q][r];
+                    a[p][r] = __fadd_rn(__fmul_rn(cs, ap), __fmul_rn(sn, aq));
+                    a[q][r] = __fsub_rn(__fmul_rn(cs, aq), __fmul_rn(sn, ap));
+                    v[p][r] = __fadd_rn(__fmul_rn(cs, vp), __fmul_rn(sn, vq));
+                    v[q][r] = __fsub_rn(__fmul_rn(cs, vq), __fmul_rn(sn, vp));
+                }
+            }
+        if (!changed) break;
+    }
+    float w = dot4f(a[0], a[0]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) x[r] = v[0][r];
+#pragma unroll
+    for (int c = 1; c < 4; ++c) {
+        const float wc = dot4f(a[c], a[c]);
+        const bool less = wc < w;
+        w = less ? wc : w;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) x[r] = less ? v[c][r] : x[r];
+    }
+}
+
+// (x, y, z) = R * X + t of a [R | t] row as the reference evaluates Rcw.row(i).dot(x3Dt) + tcw(i): Mat::dot accumulates
+// in double, the sum with the float translation is made in double and rounded once
+__device__ __forceinline__ float row_dot_d(const float *T, int r, const float *X)
+{
+    const double d = ((double)T[r * 4] * (double)X[0] + (double)T[r * 4 + 1] * (double)X[1]) + (double)T[r * 4 + 2] * (double)X[2];
+    return (float)(d + (double)T[r * 4 + 3]);
+}
+// Reprojection gate :362-413: true = fails
+__device__ __forceinline__ bool reproj_fails(const orbhip_camera &cam, const float *T, const float *X, float z, bool stereo,
+                                             float ku, float kv, float kur, float sigma2)
+{
+    const float x = row_dot_d(T, 0, X), y = row_dot_d(T, 1, X);
+    const float invz = (float)(1.0 / (double)z);
+    const float u = __fadd_rn(__fmul_rn(__fmul_rn(cam.fx, x), invz), cam.cx);
+    const float v = __fadd_rn(__fmul_rn(__fmul_rn(cam.fy, y), invz), cam.cy);
+    const float ex = __fsub_rn(u, ku), ey = __fsub_rn(v, kv);
+    float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+    if (!stereo) return (double)e2 > 5.991 * (double)sigma2;
+    const float er = __fsub_rn(__fsub_rn(u, __fmul_rn(cam.mbf, invz)), kur);
+    e2 = __fadd_rn(e2, __fmul_rn(er, er));
+    return (double)e2 > 7.8 * (double)sigma2;
+}
+// cos(2 atan2(mb/2, depth)) as (d^2 - h^2) / (d^2 + h^2) in double, h = mb/2 (:312-314)
+__device__ __forceinline__ float cos_parallax_stereo(float mb, float depth)
+{
+    const double h = (double)__fmul_rn(mb, 0.5f), d = (double)depth;
+    return (float)((d * d - h * h) / (d * d + h * h));
+}
+
+__global__ __launch_bounds__(256) void k_cnmp_triangulate(CnmpArgs A, orbhip_camera cam, CnmpLevels L)
+{
+    const int k = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const size_t c = (size_t)A.cur, f = (size_t)A.kf_index[k];
+    const int n1 = max(min(A.n_dev[c], A.cap), 0);
+    const size_t o = (size_t)k * A.cap + i;
+    const int j = i < n1 ? A.matches12[o] : -1;
+    const int cnt = __popcll(__ballot(j >= 0));
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&A.nmatches[k], cnt);
+    if (i >= n1) return;
+    float X[3] = {0.f, 0.f, 0.f};
+    int st = ORBHIP_NEWPOINT_NO_MATCH;
+    if (j >= 0) {
+        // the two poses are wave-uniform: held in scalar registers, the vector registers stay free for the 4x4 problem
+        float T1[12], T2[12];
+#pragma unroll
+        for (int e = 0; e < 12; ++e) {
+            T1[e] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(A.Tcw[c * 12 + e])));
+            T2[e] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(A.Tcw[f * 12 + e])));
+        }
+        const orbhip_keypoint kp1 = A.keys[c * A.cap + i], kp2 = A.keys[f * A.cap + j];
+        const float ur1 = A.u_right ? A.u_right[c * A.cap + i] : -1.0f, ur2 = A.u_right ? A.u_right[f * A.cap + j] : -1.0f;
+        const bool s1 = ur1 >= 0, s2 = ur2 >= 0;
+        const int o1 = min(max(kp1.octave, 0), ORBHIP_MAX_LEVELS - 1), o2 = min(max(kp2.octave, 0), ORBHIP_MAX_LEVELS - 1);
+        const float invfx = __fdiv_rn(1.0f, cam.fx), invfy = __fdiv_rn(1.0f, cam.fy);
+        // parallax between the rays, :300-305
+        const float xn1[2] = {__fmul_rn(__fsub_rn(kp1.x, cam.cx), invfx), __fmul_rn(__fsub_rn(kp1.y, cam.cy), invfy)};
+        const float xn2[2] = {__fmul_rn(__fsub_rn(kp2.x, cam.cx), invfx), __fmul_rn(__fsub_rn(kp2.y, cam.cy), invfy)};
+        float r1[3], r2[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            r1[r] = dot3f(T1[r], T1[4 + r], T1[8 + r], xn1[0], xn1[1], 1.0f);
+            r2[r] = dot3f(T2[r], T2[4 + r], T2[8 + r], xn2[0], xn2[1], 1.0f);
+        }
+        const double dd = ((double)r1[0] * (double)r2[0] + (double)r1[1] * (double)r2[1]) + (double)r1[2] * (double)r2[2];
+        const float cos_rays = (float)(dd / (norm3d(r1[0], r1[1], r1[2]) * norm3d(r2[0], r2[1], r2[2])));
+        float cs1 = __fadd_rn(cos_rays, 1.0f), cs2 = cs1;
+        if (s1) cs1 = cos_parallax_stereo(cam.mb, A.depth[c * A.cap + i]);
+        else if (s2) cs2 = cos_parallax_stereo(cam.mb, A.depth[f * A.cap + j]);
+        const float cs = fminf(cs1, cs2);
+        bool have = true;
+        if (cos_rays < cs && cos_rays > 0.f && (s1 || s2 || (double)cos_rays < 0.9998)) {
+            // linear triangulation :322-337; a[col][row] of A
+            float a[4][4], x[4];
+#pragma unroll
+            for (int col = 0; col < 4; ++col) {
+                a[col][0] = __fsub_rn(__fmul_rn(xn1[0], T1[8 + col]), T1[col]);
+                a[col][1] = __fsub_rn(__fmul_rn(xn1[1], T1[8 + col]), T1[4 + col]);
+                a[col][2] = __fsub_rn(__fmul_rn(xn2[0], T2[8 + col]), T2[col]);
+                a[col][3] = __fsub_rn(__fmul_rn(xn2[1], T2[8 + col]), T2[4 + col]);
+            }
+            jacobi_null4(a, x);
+            if (x[3] == 0.f) { st = ORBHIP_NEWPOINT_W_ZERO; have = false; }
+            else {
+#pragma unroll
+                for (int r = 0; r < 3; ++r) X[r] = __fdiv_rn(x[r], x[3]);
+            }
+        } else if (s1 && cs1 < cs2) {
+            float Ow1[3];
+            camera_centre(T1, Ow1);
+            unproject_stereo(T1, Ow1, kp1.x, kp1.y, A.depth[c * A.cap + i], cam.cx, cam.cy, invfx, invfy, X);
+        } else if (s2 && cs2 < cs1) {
+            float Ow2[3];
+            camera_centre(T2, Ow2);
+            unproject_stereo(T2, Ow2, kp2.x, kp2.y, A.depth[f * A.cap + j], cam.cx, cam.cy, invfx, invfy, X);
+        } else { st = ORBHIP_NEWPOINT_LOW_PARALLAX; have = false; }
+        if (have) {
+            const float z1 = row_dot_d(T1, 2, X), z2 = row_dot_d(T2, 2, X);
+            if (z1 <= 0.f) st = ORBHIP_NEWPOINT_BEHIND_1;
+            else if (z2 <= 0.f) st = ORBHIP_NEWPOINT_BEHIND_2;
+            else if (reproj_fails(cam, T1, X, z1, s1, kp1.x, kp1.y, ur1, L.sigma2[o1])) st = ORBHIP_NEWPOINT_REPROJ_1;
+            else if (reproj_fails(cam, T2, X, z2, s2, kp2.x, kp2.y, ur2, L.sigma2[o2])) st = ORBHIP_NEWPOINT_REPROJ_2;
+            else {
+                // scale consistency :415-431
+                float Ow1[3], Ow2[3];
+                camera_centre(T1, Ow1);
+                camera_centre(T2, Ow2);
+                const float d1 = (float)norm3d(__fsub_rn(X[0], Ow1[0]), __fsub_rn(X[1], Ow1[1]), __fsub_rn(X[2], Ow1[2]));
+                const float d2 = (float)norm3d(__fsub_rn(X[0], Ow2[0]), __fsub_rn(X[1], Ow2[1]), __fsub_rn(X[2], Ow2[2]));
+                if (d1 == 0.f || d2 == 0.f) st = ORBHIP_NEWPOINT_ZERO_DIST;
+                else {
+                    const float ratio_factor = __fmul_rn(1.5f, L.sf[cam.n_levels > 1 ? 1 : 0]);
+                    const float ratio_dist = __fdiv_rn(d2, d1), ratio_oct = __fdiv_rn(L.sf[o1], L.sf[o2]);
+                    st = (__fmul_rn(ratio_dist, ratio_factor) < ratio_oct || ratio_dist > __fmul_rn(ratio_oct, ratio_factor))
+                             ? ORBHIP_NEWPOINT_SCALE : ORBHIP_NEWPOINT_CREATED;
+                }
+            }
+        }
+    }
+    A.status[o] = (uint8_t)st;
+    A.x3d[o * 3] = X[0]; A.x3d[o * 3 + 1] = X[1]; A.x3d[o * 3 + 2] = X[2];
 }
 
 // ---- independent best match per query (no slot blocking) ------------------------------------
@@ -2691,12 +3109,10 @@ __global__ __launch_bounds__(1024) void k_seed_stereo_points(SeedBatch B, float 
         }
         if (create) {
             const orbhip_keypoint kp = keys[i];
-            const float x = __fmul_rn(__fmul_rn(__fsub_rn(kp.x, cx), zz), invfx);
-            const float y = __fmul_rn(__fmul_rn(__fsub_rn(kp.y, cy), zz), invfy);
+            float X[3];
+            unproject_stereo(T, Ow, kp.x, kp.y, zz, cx, cy, invfx, invfy, X);
 #pragma unroll
-            for (int r = 0; r < 3; ++r)
-                world[(size_t)i * 3 + r] =
-                    __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[r], x), __fmul_rn(T[4 + r], y)), __fmul_rn(T[8 + r], zz)), Ow[r]);
+            for (int r = 0; r < 3; ++r) world[(size_t)i * 3 + r] = X[r];
             flags[i] = (uint8_t)created_flags;
             made[i] = 1;
             ++made_cnt;
@@ -2805,7 +3221,7 @@ static int scratch(orbhip_matcher *m, int slot, size_t bytes, void **out)
     return ORBHIP_OK;
 }
 
-enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_NSLOTS };
+enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_NSLOTS };
 
 static int stage_begin(orbhip_matcher *m, size_t total, Stage *st)
 {
@@ -4191,6 +4607,158 @@ int orbhip_fuse_batch(orbhip_matcher *m, int K, const orbhip_frame_view *const *
         if (int rc = orbhip_fuse(m, kfs[k], cam, Tcw + (size_t)k * 12, sim3_form, n, world, normal, max_dist, min_dist,
                                  flags + (size_t)k * n, point_desc, th, inv_level_sigma2, best_idx + (size_t)k * n,
                                  best_dist + (size_t)k * n)) return rc;
+    return ORBHIP_OK;
+}
+
+// LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) up to :433, for K neighbours in one device-resident call
+int orbhip_create_new_map_points_device(orbhip_matcher *m, int cur, int K, const void *d_kf_index, const orbhip_camera *cam,
+                                        const void *d_Tcw, const void *d_kps, const void *d_desc, const void *d_n, int cap,
+                                        const void *d_u_right, const void *d_depth, const void *d_node, const void *d_has_point,
+                                        const void *d_median_depth, int only_stereo, int check_ori, const float *level_sigma2,
+                                        void *d_matches12, void *d_nmatches, void *d_x3d, void *d_status, void *d_skipped,
+                                        void *d_f12, void *d_epipole)
+{
+    if (!m || cur < 0 || K < 0 || cap < 1 || !cam || cam->n_levels < 1 || cam->n_levels > ORBHIP_MAX_LEVELS ||
+        cam->fx == 0.f || cam->fy == 0.f)
+        return ORBHIP_E_ARG;
+    if (cap > kResolveMax) {
+        set_error("create_new_map_points_device: capacity %d exceeds %d", cap, kResolveMax);
+        return ORBHIP_E_CAPACITY;
+    }
+    if ((d_u_right == nullptr) != (d_depth == nullptr)) return ORBHIP_E_ARG;
+    // monocular (no right coordinates) needs the scene median depths, stereo / RGB-D must not pass them (:249-261)
+    if ((d_u_right == nullptr) != (d_median_depth != nullptr)) return ORBHIP_E_ARG;
+    if (!d_Tcw || !d_kps || !d_desc || !d_n || !d_node || !level_sigma2) return ORBHIP_E_ARG;
+    if (K == 0) return ORBHIP_OK;
+    if (!d_kf_index || !d_matches12 || !d_nmatches || !d_x3d || !d_status || !d_skipped) return ORBHIP_E_ARG;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    void *p;
+    if (int rc = scratch(m, S_TRI, (size_t)K * sizeof(CnmpRow), &p)) return rc;
+    CnmpArgs A;
+    A.kf_index = (const int *)d_kf_index; A.Tcw = (const float *)d_Tcw;
+    A.keys = (const orbhip_keypoint *)d_kps; A.desc = (const uint8_t *)d_desc; A.n_dev = (const int *)d_n;
+    A.u_right = (const float *)d_u_right; A.depth = (const float *)d_depth;
+    A.node = (const uint32_t *)d_node; A.has_point = (const uint8_t *)d_has_point;
+    A.median_depth = (const float *)d_median_depth;
+    A.matches12 = (int *)d_matches12; A.nmatches = (int *)d_nmatches; A.x3d = (float *)d_x3d;
+    A.status = (uint8_t *)d_status; A.skipped = (uint8_t *)d_skipped;
+    A.f12_out = (float *)d_f12; A.ep_out = (float *)d_epipole;
+    A.table = (CnmpRow *)p;
+    A.cur = cur; A.K = K; A.cap = cap; A.only_stereo = only_stereo ? 1 : 0;
+    CnmpLevels L;
+    memset(&L, 0, sizeof(L));
+    for (int l = 0; l < cam->n_levels; ++l) { L.sigma2[l] = level_sigma2[l]; L.sf[l] = cam->scale_factors[l]; }
+    hipLaunchKernelGGL(k_cnmp_rows, dim3((K + 63) / 64), dim3(64), 0, m->stream, A, *cam);
+    hipLaunchKernelGGL(k_cnmp_search, dim3((cap + 3) / 4, K), dim3(256), 0, m->stream, A, L);
+    if (check_ori) hipLaunchKernelGGL(k_cnmp_cull, dim3(K), dim3(1024), 0, m->stream, A);
+    hipLaunchKernelGGL(k_cnmp_triangulate, dim3((cap + 255) / 256, K), dim3(256), 0, m->stream, A, *cam, L);
+    ORBHIP_HIP_CHECK(hipGetLastError());
+    return ORBHIP_OK;
+}
+
+int orbhip_create_new_map_points(orbhip_matcher *m, const orbhip_frame_view *cur, const uint32_t *node_cur,
+                                 const uint8_t *has_point_cur, const float *depth_cur, const float *Tcw_cur, int K,
+                                 const orbhip_frame_view *const *kfs, const uint32_t *const *node, const uint8_t *const *has_point,
+                                 const float *const *depth, const float *Tcw, const float *median_depth,
+                                 const orbhip_camera *cam, int only_stereo, int check_ori, const float *level_sigma2,
+                                 int32_t *matches12, int32_t *nmatches, float *x3d, uint8_t *status, uint8_t *skipped,
+                                 float *f12, float *epipole)
+{
+    if (!m || !cur || K < 0 || cur->n < 0 || !cam || cam->n_levels < 1 || cam->n_levels > ORBHIP_MAX_LEVELS ||
+        cam->fx == 0.f || cam->fy == 0.f || !level_sigma2 || !Tcw_cur)
+        return ORBHIP_E_ARG;
+    const bool stereo = cur->u_right != nullptr;
+    if (stereo != (depth_cur != nullptr) || stereo == (median_depth != nullptr)) return ORBHIP_E_ARG;
+    if (cur->n > 0 && (!cur->keys || !cur->desc || !node_cur)) return ORBHIP_E_ARG;
+    if (K > 0 && (!kfs || !node || !Tcw || (stereo && !depth))) return ORBHIP_E_ARG;
+    for (int k = 0; k < K; ++k) {
+        const orbhip_frame_view *f = kfs[k];
+        if (!f || f->n < 0 || (f->n > 0 && (!f->keys || !f->desc || !node[k] || (f->u_right != nullptr) != stereo)) ||
+            (stereo && f->n > 0 && !depth[k]))
+            return ORBHIP_E_ARG;
+    }
+    int cap = std::max(cur->n, 1);
+    for (int k = 0; k < K; ++k) cap = std::max(cap, kfs[k]->n);
+    if (cap > kResolveMax) {
+        set_error("create_new_map_points: %d keypoints exceed the LDS-resident limit %d", cap, kResolveMax);
+        return ORBHIP_E_CAPACITY;
+    }
+    if (K == 0 || cur->n == 0) return ORBHIP_OK;
+    if (!matches12 || !nmatches || !x3d || !status || !skipped) return ORBHIP_E_ARG;
+    for (int k = -1; k < K; ++k) {
+        const orbhip_frame_view *f = k < 0 ? cur : kfs[k];
+        for (int j = 0; j < f->n; ++j)
+            if (f->keys[j].octave < 0 || f->keys[j].octave >= cam->n_levels) {
+                set_error("create_new_map_points: keypoint %d has octave %d outside [0,%d)", j, f->keys[j].octave,
+                          cam->n_levels);
+                return ORBHIP_E_ARG;
+            }
+    }
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    // rows of the staged batch: 0 = the current key frame, 1 + k = neighbour k
+    const int rows = K + 1;
+    const size_t rc_ = (size_t)rows * cap, kc = (size_t)K * cap;
+    const bool any_hp = has_point_cur || has_point;
+    Stage st;
+    int rc;
+    if ((rc = stage_begin(m, 2 * al256((size_t)rows * 4) + al256((size_t)rows * 48) + al256(rc_ * sizeof(orbhip_keypoint)) +
+                                 al256(rc_ * 32) + 3 * al256(rc_ * 4) + al256(rc_) + al256((size_t)K * 4), &st))) return rc;
+    const int *d_index, *d_n;
+    const float *d_T, *d_ur = nullptr, *d_z = nullptr, *d_med = nullptr;
+    const orbhip_keypoint *d_keys;
+    const uint8_t *d_desc, *d_hp = nullptr;
+    const uint32_t *d_node;
+    int *h_index = st.take((size_t)K, &d_index), *h_n = st.take((size_t)rows, &d_n);
+    float *h_T = st.take((size_t)rows * 12, &d_T);
+    orbhip_keypoint *h_keys = st.take(rc_, &d_keys);
+    uint8_t *h_desc = st.take(rc_ * 32, &d_desc);
+    uint32_t *h_node = st.take(rc_, &d_node);
+    float *h_ur = stereo ? st.take(rc_, &d_ur) : nullptr, *h_z = stereo ? st.take(rc_, &d_z) : nullptr;
+    uint8_t *h_hp = any_hp ? st.take(rc_, &d_hp) : nullptr;
+    if (median_depth) d_med = st.put(median_depth, (size_t)K);
+    if ((rc = st.status())) return rc;
+    for (int r = 0; r < rows; ++r) {
+        const int k = r - 1;
+        const orbhip_frame_view *f = r == 0 ? cur : kfs[k];
+        const size_t fn = (size_t)f->n, o = (size_t)r * cap;
+        const uint8_t *hp = r == 0 ? has_point_cur : (has_point ? has_point[k] : nullptr);
+        if (r > 0) h_index[k] = r;
+        h_n[r] = f->n;
+        memcpy(h_T + (size_t)r * 12, r == 0 ? Tcw_cur : Tcw + (size_t)k * 12, 12 * sizeof(float));
+        if (fn) {
+            memcpy(h_keys + o, f->keys, fn * sizeof(orbhip_keypoint));
+            memcpy(h_desc + o * 32, f->desc, fn * 32);
+            memcpy(h_node + o, r == 0 ? node_cur : node[k], fn * 4);
+            if (stereo) {
+                memcpy(h_ur + o, f->u_right, fn * 4);
+                memcpy(h_z + o, r == 0 ? depth_cur : depth[k], fn * 4);
+            }
+            if (h_hp) { if (hp) memcpy(h_hp + o, hp, fn); else memset(h_hp + o, 0, fn); }
+        }
+    }
+    if ((rc = stage_commit(m, &st))) return rc;
+    // outputs in one block: matches12 | nmatches | x3d | f12 | epipole | status | skipped
+    const size_t o_n = kc * 4, o_x = o_n + al256((size_t)K * 4), o_f = o_x + kc * 12, o_e = o_f + al256((size_t)K * 36),
+                 o_s = o_e + al256((size_t)K * 8), o_k = o_s + al256(kc), total = o_k + al256((size_t)K);
+    void *p;
+    if ((rc = scratch(m, S_OUT, total, &p))) return rc;
+    uint8_t *d_out = (uint8_t *)p;
+    ORBHIP_HIP_CHECK(hipMemsetAsync(d_out, 0, total, m->stream));
+    if ((rc = orbhip_create_new_map_points_device(m, 0, K, d_index, cam, d_T, d_keys, d_desc, d_n, cap, d_ur, d_z, d_node, d_hp,
+                                                  d_med, only_stereo, check_ori, level_sigma2, d_out, d_out + o_n, d_out + o_x,
+                                                  d_out + o_s, d_out + o_k, d_out + o_f, d_out + o_e))) return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, d_out, total, &h))) return rc;
+    const size_t n1 = (size_t)cur->n;
+    for (int k = 0; k < K; ++k) {
+        memcpy(matches12 + (size_t)k * n1, h + (size_t)k * cap * 4, n1 * 4);
+        memcpy(x3d + (size_t)k * n1 * 3, h + o_x + (size_t)k * cap * 12, n1 * 12);
+        memcpy(status + (size_t)k * n1, h + o_s + (size_t)k * cap, n1);
+    }
+    memcpy(nmatches, h + o_n, (size_t)K * 4);
+    memcpy(skipped, h + o_k, (size_t)K);
+    if (f12) memcpy(f12, h + o_f, (size_t)K * 36);
+    if (epipole) memcpy(epipole, h + o_e, (size_t)K * 8);
     return ORBHIP_OK;
 }
 

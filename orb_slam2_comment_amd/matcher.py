@@ -465,6 +465,78 @@ class ORBmatcher:
                                            d_normal, d_max_dist, d_min_dist, d_point_desc, d_flags, float(th), ptr(sig),
                                            d_best_idx, d_best_dist, d_q), "orbhip_fuse_device")
 
+    def CreateNewMapPoints(self, cur, node_cur, has_point_cur, depth_cur, Tcw_cur, KFs, nodes, has_points, depths, Tcw,
+                           cam, level_sigma2, median_depth=None, bOnlyStereo=False):
+        """LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) up to `new MapPoint` for the current key frame
+        `cur` and the K neighbours `KFs` (FrameViews; u_right on all or on none) in one staged copy, one device call and
+        one read-back.  nodes[k] / has_points[k] (None = no slot holds a point) / depths[k] (stereo only): one entry per
+        key point; Tcw_cur and Tcw [K]: poses (4x4 or 3x4); median_depth [K]: ComputeSceneMedianDepth(2), monocular only.
+        Returns a dict: matches12 [K, n], nmatches [K], x3d [K, n, 3], status [K, n] (capi.NEWPOINT_*), skipped [K],
+        f12 [K, 3, 3], epipole [K, 2]; INTEGRATION.md section 3 says how the rows are applied in neighbour order."""
+        K, n = len(KFs), cur.N
+        T0 = np.ascontiguousarray(np.asarray(Tcw_cur, np.float32)[:3, :4]).reshape(12)
+        Tc = (np.ascontiguousarray(np.asarray(Tcw, np.float32).reshape(K, -1, 4)[:, :3, :]).reshape(K, 12) if K
+              else np.zeros((1, 12), np.float32))
+        stereo = cur.u_right is not None
+        keep = []
+
+        def arr(a, dt, count):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dt)
+            if len(a) != count:
+                raise ValueError("per-keypoint arrays must have one entry per keypoint")
+            keep.append(a)
+            return a
+
+        def table(seq, dt):
+            if seq is None:
+                return None
+            rows = [arr(seq[k], dt, KFs[k].N) for k in range(K)]
+            return (C.c_void_p * max(K, 1))(*[None if r is None else r.ctypes.data for r in rows])
+
+        nc, hc = arr(node_cur, np.uint32, n), arr(has_point_cur, np.uint8, n)
+        zc = arr(depth_cur, np.float32, n) if stereo else None
+        t_node, t_hp = table(nodes, np.uint32), table(has_points, np.uint8)
+        t_z = table(depths, np.float32) if stereo else None
+        med = None if median_depth is None else np.ascontiguousarray(median_depth, np.float32)
+        sig = np.ascontiguousarray(level_sigma2, np.float32)
+        if len(sig) < cam.n_levels:
+            raise ValueError("level_sigma2 needs one entry per pyramid level")
+        out = {"matches12": np.full((K, n), -1, np.int32), "nmatches": np.zeros(K, np.int32),
+               "x3d": np.zeros((K, n, 3), np.float32), "status": np.full((K, n), capi.NEWPOINT_NO_MATCH, np.uint8),
+               "skipped": np.zeros(K, np.uint8), "f12": np.zeros((K, 3, 3), np.float32),
+               "epipole": np.zeros((K, 2), np.float32)}
+        views = [kf.c_view() for kf in KFs]
+        vc = cur.c_view()
+        varr = (C.POINTER(capi.FrameView) * max(K, 1))(*[C.pointer(v) for v in views])
+        check(self._lib.orbhip_create_new_map_points(
+            self._h, C.byref(vc), ptr(nc), ptr(hc), ptr(zc), ptr(T0), K, varr, t_node, t_hp, t_z, ptr(Tc), ptr(med),
+            C.byref(cam), int(bOnlyStereo), int(self.mbCheckOrientation), ptr(sig), ptr(out["matches12"]),
+            ptr(out["nmatches"]), ptr(out["x3d"]), ptr(out["status"]), ptr(out["skipped"]), ptr(out["f12"]),
+            ptr(out["epipole"])), "orbhip_create_new_map_points")
+        return out
+
+    def CreateNewMapPointsDevice(self, cur, K, d_kf_index, cam, d_Tcw, d_kps, d_desc, d_n, cap, d_node, level_sigma2,
+                                 d_matches12, d_nmatches, d_x3d, d_status, d_skipped, d_u_right=0, d_depth=0,
+                                 d_has_point=0, d_median_depth=0, bOnlyStereo=False, d_f12=0, d_epipole=0):
+        """Device-resident CreateNewMapPoints (see orbhip_create_new_map_points_device in include/orbhip.h).  Every d_*
+        is a torch tensor on the matcher's device or a raw device pointer (int, 0 = NULL): the current key frame is frame
+        row `cur`, neighbour k frame row kf_index[k] of the extractor-layout arrays; outputs [K][cap].  Asynchronous on
+        the matcher's stream."""
+        sig = np.ascontiguousarray(level_sigma2, np.float32)
+        if len(sig) < cam.n_levels:
+            raise ValueError("level_sigma2 needs one entry per pyramid level")
+
+        def dp(a):
+            return int(a.data_ptr()) if hasattr(a, "data_ptr") else (int(a) or None)
+
+        check(self._lib.orbhip_create_new_map_points_device(
+            self._h, int(cur), int(K), dp(d_kf_index), C.byref(cam), dp(d_Tcw), dp(d_kps), dp(d_desc), dp(d_n), int(cap),
+            dp(d_u_right), dp(d_depth), dp(d_node), dp(d_has_point), dp(d_median_depth), int(bOnlyStereo),
+            int(self.mbCheckOrientation), ptr(sig), dp(d_matches12), dp(d_nmatches), dp(d_x3d), dp(d_status),
+            dp(d_skipped), dp(d_f12), dp(d_epipole)), "orbhip_create_new_map_points_device")
+
     def SearchBySim3(self, KF1, KF2, cam, T1w, T2w, S21, S12, pts1, pts2, th):
         """pts = (world, max_dist, min_dist, flags, desc) per key-frame slot.  Returns (nFound, matches12[N1])."""
         mats = [np.ascontiguousarray(np.asarray(T, np.float32)[:3, :4]) for T in (T1w, T2w, S21, S12)]
