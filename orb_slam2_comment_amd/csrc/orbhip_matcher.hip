@@ -117,6 +117,122 @@ __device__ __forceinline__ int wave_sorted_head(unsigned long long a1, unsigned 
     return hl;
 }
 
+// ---- rotation consistency (ORBmatcher.cc rotHist + ComputeThreeMaxima), the one home of the rule -------------------
+// The accepted matches are histogrammed by rot_bin(query angle, train angle), three_maxima picks the winning bins and
+// every match outside them is dropped.  A match without a bin (rot_bin < 0, kept as 0xff where bins are bytes) takes no
+// part: it is neither histogrammed nor dropped.  Used by the fused epilogues of k_resolve_par, k_resolve_init and
+// k_bow_pairs and by rot_cull_body, the stand-alone cull behind k_rot_cull and k_cnmp_cull.
+__device__ __forceinline__ int rot_bin(float a1, float a2)
+{
+    const float factor = 1.0f / HISTO_LENGTH;
+    float rot = __fsub_rn(a1, a2);
+    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
+    const float r = roundf(__fmul_rn(rot, factor));
+    // keypoint angles are caller data: outside [0, 360) (or NaN) the reference trips its assert(bin>=0 && bin<HISTO_LENGTH);
+    // here such a match simply takes no part in the rotation histogram (-1) instead of writing outside it.  Tested on the
+    // float: the conversion of a NaN to int is not defined (the hardware's gives 0, which would be a bin)
+    if (!(r >= 0.0f && r <= (float)HISTO_LENGTH)) return -1;
+    return r == (float)HISTO_LENGTH ? 0 : (int)r;
+}
+
+__device__ __forceinline__ void three_maxima(const int *h, int &ind1, int &ind2, int &ind3)
+{
+    // ComputeThreeMaxima (src/ORBmatcher.cc:1601-1645) as selects on values: with the three indices passed by reference
+    // through a chain of branches the compiler kept them in scratch memory (150 scratch accesses per call)
+    int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
+    int hv[HISTO_LENGTH];   // all bins first (independent loads, one wait), then the scan on registers
+#pragma unroll
+    for (int i = 0; i < HISTO_LENGTH; ++i) hv[i] = h[i];
+#pragma unroll
+    for (int i = 0; i < HISTO_LENGTH; ++i) {
+        const int s = hv[i];
+        const bool g1 = s > max1, g2 = s > max2, g3 = s > max3;
+        max3 = g2 ? max2 : (g3 ? s : max3);  i3 = g2 ? i2 : (g3 ? i : i3);
+        max2 = g1 ? max1 : (g2 ? s : max2);  i2 = g1 ? i1 : (g2 ? i : i2);
+        max1 = g1 ? s : max1;                i1 = g1 ? i : i1;
+    }
+    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { i2 = -1; i3 = -1; }
+    else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { i3 = -1; }
+    ind1 = i1; ind2 = i2; ind3 = i3;
+}
+
+// hist[bin] += 1 for every lane of the wavefront with bin >= 0; all 64 lanes call it.  One atomic per distinct bin of the
+// wavefront (most matches of a frame pair share a rotation bin).
+__device__ __forceinline__ void wave_hist_add(int *hist, int bin)
+{
+    unsigned long long todo = __ballot(bin >= 0);
+    while (todo) {
+        const int first = __ffsll((long long)todo) - 1;
+        const int lead = __builtin_amdgcn_readlane(bin, first);
+        const unsigned long long same = __ballot(bin == lead);
+        if ((threadIdx.x & 63) == first) atomicAdd(&hist[lead], __popcll(same));
+        todo &= ~same;
+    }
+}
+
+// Wavefront 0 ranks the finished histogram (a workgroup's wavefronts share one CU's issue slots) and publishes the three
+// winning bins to ind[0..2] for everybody: the barrier is inside, the one that completes the histogram is the caller's.
+__device__ __forceinline__ void rank_bins_once(const int *hist, int *ind)
+{
+    if (threadIdx.x < 64) {
+        int i1, i2, i3;
+        three_maxima(hist, i1, i2, i3);
+        if (threadIdx.x == 0) { ind[0] = i1; ind[1] = i2; ind[2] = i3; }
+    }
+    __syncthreads();
+}
+
+// the cull predicate: bin b takes part (a bin, not -1 / 0xff) and is none of the three winners
+__device__ __forceinline__ bool rot_culled(int b, int ind1, int ind2, int ind3)
+{
+    return (unsigned)b < (unsigned)HISTO_LENGTH && b != ind1 && b != ind2 && b != ind3;
+}
+
+// The stand-alone cull: one workgroup, one row of matches.  match[i] = train index of query i or -1; query i's angle is the
+// float at qangle + i * qstride bytes (key arrays, query arrays and packed floats alike).  Culls in place; writes the
+// number of surviving matches to *out_n when given.  check_ori == 0 only counts.
+__device__ __forceinline__ void rot_cull_body(int *__restrict__ match, const int n, const void *__restrict__ qangle,
+                                              const size_t qstride, const orbhip_keypoint *__restrict__ tkeys,
+                                              const int check_ori, int *__restrict__ out_n)
+{
+    __shared__ int hist[HISTO_LENGTH], ind[3], kept;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const auto bin_of = [&](int i, int j) {
+        return rot_bin(*reinterpret_cast<const float *>(static_cast<const unsigned char *>(qangle) + i * qstride), tkeys[j].angle);
+    };
+    if (tid < HISTO_LENGTH) hist[tid] = 0;
+    if (tid == 0) kept = 0;
+    __syncthreads();
+    if (check_ori) {
+        for (int i0 = 0; i0 < n; i0 += T) {
+            const int i = i0 + tid, j = i < n ? match[i] : -1;
+            wave_hist_add(hist, j >= 0 ? bin_of(i, j) : -1);
+        }
+        __syncthreads();
+        rank_bins_once(hist, ind);
+    }
+    int cnt = 0;
+    for (int i = tid; i < n; i += T) {
+        const int j = match[i];
+        if (j < 0) continue;
+        if (check_ori && rot_culled(bin_of(i, j), ind[0], ind[1], ind[2])) match[i] = -1;
+        else ++cnt;
+    }
+    if (!out_n) return;
+    cnt = wave_sum(cnt);
+    if ((tid & 63) == 0 && cnt) atomicAdd(&kept, cnt);
+    __syncthreads();
+    if (tid == 0) *out_n = kept;
+}
+
+// the body on a row given by host-known pointers (host SearchByBoW, host SearchForTriangulation)
+__global__ __launch_bounds__(1024) void k_rot_cull(int *__restrict__ match, int n, const void *__restrict__ qangle, int qstride,
+                                                   const orbhip_keypoint *__restrict__ tkeys, int check_ori,
+                                                   int *__restrict__ out_n)
+{
+    rot_cull_body(match, n, qangle, (size_t)qstride, tkeys, check_ori, out_n);
+}
+
 // Visiting-order key of every train keypoint, (posX*48+posY) << 20 | index, or kNoCell when PosInGrid rejects it
 // (k_best_in_window scans the frame with it).
 __global__ void k_grid_order(DevFrame F, uint32_t *__restrict__ ord, Batch B)
@@ -360,16 +476,10 @@ __global__ __launch_bounds__(256) void k_window_search(DevFrame F, const int *__
 // in registers), the "already matched" flags live in slot space and each slot is only ever touched by the lane
 // that owns it.  Best / second-best = two wave minima of (distance << 32 | slot).
 struct NodeGroup { int q_begin, q_end, t_begin, t_end; };
-__device__ __forceinline__ int rot_bin(float a1, float a2);
-__device__ __forceinline__ void three_maxima(const int *h, int &ind1, int &ind2, int &ind3);
-
 __global__ __launch_bounds__(256) void k_bow_groups(const NodeGroup *__restrict__ groups, int ngroups,
-                                                    const uint8_t *__restrict__ qdesc, const float *__restrict__ qangle,
-                                                    const uint32_t *__restrict__ t_order, const uint8_t *__restrict__ tdesc,
-                                                    const orbhip_keypoint *__restrict__ tkeys,
-                                                    uint8_t *__restrict__ matched, int max_dist, float nnratio,
-                                                    int check_ori, int *__restrict__ match_out,
-                                                    uint8_t *__restrict__ bin_out, int *__restrict__ hist)
+                                                    const uint8_t *__restrict__ qdesc, const uint32_t *__restrict__ t_order,
+                                                    const uint8_t *__restrict__ tdesc, uint8_t *__restrict__ matched,
+                                                    int max_dist, float nnratio, int *__restrict__ match_out)
 {
     const int lane = threadIdx.x & 63;
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -425,20 +535,12 @@ __global__ __launch_bounds__(256) void k_bow_groups(const NodeGroup *__restrict_
                 res = (int)t_order[slot];
             }
         }
-        if (lane == 0) {
-            match_out[qi] = res;
-            int bin = 0xff;
-            if (res >= 0 && check_ori) {
-                bin = rot_bin(qangle[qi], tkeys[res].angle);
-                if (bin >= 0) atomicAdd(&hist[bin], 1); else bin = 0xff;
-            }
-            bin_out[qi] = (uint8_t)bin;
-        }
+        if (lane == 0) match_out[qi] = res;
     }
 }
 
 // Device-resident, batched SearchByBoW: one 1024-thread workgroup per (key frame, frame) pair does everything the
-// host path splits between std::sort, k_bow_groups and k_bow_cull: both sides' (node << 32 | index) keys are sorted
+// host path splits between std::sort, k_bow_groups and k_rot_cull: both sides' (node << 32 | index) keys are sorted
 // in LDS (= FeatureVector order), group heads are found on the sorted query keys, the node's candidate range by
 // binary search in the sorted train keys, then the 16 wavefronts take the common nodes round-robin and replay each
 // node's queries in order exactly like k_bow_groups; rotation histogram, cull and count finish in the same launch.
@@ -608,12 +710,13 @@ __global__ __launch_bounds__(1024) void k_bow_pairs(BowSide Q, BowSide T, int ca
     __syncthreads();
     // rotation bins of the accepted matches, all at once: the two angle loads per match used to sit in the replay loop, one
     // dependent memory round trip per accepted query on a single lane
+    // per-thread atomics and a ranking by every thread: wave_hist_add / rank_bins_once are not measured on the bow leg yet
     if (check_ori) {
         for (int p = tid; p < nq; p += NT) {
             const int idx2 = S.mout[p];
             if (idx2 < 0) continue;
             const int b = rot_bin(qk[(uint32_t)S.qkey[p]].angle, tk[idx2].angle);
-            if (b >= 0) { atomicAdd(&S.hist[b], 1); S.bin[p] = (unsigned char)b; }
+            if (b >= 0) { atomicAdd(&S.hist[b], 1); S.bin[p] = (unsigned char)b; }   // stays 0xff otherwise: takes no part
         }
         __syncthreads();
     }
@@ -623,8 +726,7 @@ __global__ __launch_bounds__(1024) void k_bow_pairs(BowSide Q, BowSide T, int ca
     for (int p = tid; p < nq; p += NT) {
         const int mval = S.mout[p];
         if (mval < 0) continue;
-        const int b = S.bin[p];
-        if (check_ori && b != ind1 && b != ind2 && b != ind3) continue;
+        if (check_ori && rot_culled(S.bin[p], ind1, ind2, ind3)) continue;
         matches12[(uint32_t)S.qkey[p]] = mval;
         ++cnt;
     }
@@ -633,32 +735,9 @@ __global__ __launch_bounds__(1024) void k_bow_pairs(BowSide Q, BowSide T, int ca
     if (tid == 0) nmatches[pair] = S.nmatch;
 }
 
-// rotation-consistency cull + count (ORBmatcher.cc:271-285 / :633-651); one workgroup
-__global__ __launch_bounds__(1024) void k_bow_cull(int nq, int check_ori, const int *__restrict__ hist,
-                                                   const uint8_t *__restrict__ bin, int *__restrict__ match, int *out_n)
-{
-    __shared__ int s_hist[HISTO_LENGTH];
-    __shared__ int s_n;
-    if (threadIdx.x < HISTO_LENGTH) s_hist[threadIdx.x] = hist[threadIdx.x];
-    if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    if (check_ori) three_maxima(s_hist, ind1, ind2, ind3);
-    int cntl = 0;
-    for (int i = threadIdx.x; i < nq; i += blockDim.x) {
-        if (match[i] < 0) continue;
-        const int b = bin[i];
-        if (check_ori && b != ind1 && b != ind2 && b != ind3) match[i] = -1;
-        else ++cntl;
-    }
-    if (cntl) atomicAdd(&s_n, cntl);
-    __syncthreads();
-    if (threadIdx.x == 0) *out_n = s_n;
-}
-
 // SearchForTriangulation: one wavefront per query; the epipole and epipolar-line gates are applied here and only the
 // winner (smallest distance, LAST index on ties, ":735 dist>bestDist") is kept.  The reference never sets
-// vbMatched2, so queries are independent; k_resolve_par mode 4 then only does the rotation cull.
+// vbMatched2, so queries are independent: the winner is the match, and only the rotation cull (k_rot_cull) follows.
 struct TriParams {
     float f12[9];
     float ex, ey;
@@ -667,16 +746,14 @@ struct TriParams {
 
 // The candidate scan of one query by one wavefront, shared by k_tri_search and k_cnmp_search: lanes over the train
 // keypoints of the query's node; a candidate is left out when tmask[j] != 0 equals mask_skip (tmask nullable) or, with
-// only_stereo, when it has no right coordinate (:725-729).  Returns the wave-uniform best key
-// distance << 32 | (0xfffff - index), ~0 = none.
-__device__ __forceinline__ unsigned long long tri_scan(const int lane, const int n, const orbhip_keypoint *__restrict__ keys,
-                                                       const uint8_t *__restrict__ desc, const float *__restrict__ u_right,
-                                                       const uint32_t *__restrict__ tnode, const uint8_t *__restrict__ tmask,
-                                                       const bool mask_skip, const bool only_stereo, const uint32_t qnode,
-                                                       const uint32_t (&qd)[8], const float qu, const float qv,
-                                                       const bool stereo1, const float (&f12)[9], const float ex,
-                                                       const float ey, const float *__restrict__ sigma2,
-                                                       const float *__restrict__ sf)
+// only_stereo, when it has no right coordinate (:725-729).  Returns the wave-uniform train index of the winner, -1 = none.
+__device__ __forceinline__ int tri_scan(const int lane, const int n, const orbhip_keypoint *__restrict__ keys,
+                                        const uint8_t *__restrict__ desc, const float *__restrict__ u_right,
+                                        const uint32_t *__restrict__ tnode, const uint8_t *__restrict__ tmask,
+                                        const bool mask_skip, const bool only_stereo, const uint32_t qnode,
+                                        const uint32_t (&qd)[8], const float qu, const float qv, const bool stereo1,
+                                        const float (&f12)[9], const float ex, const float ey,
+                                        const float *__restrict__ sigma2, const float *__restrict__ sf)
 {
     // epipolar line of the query in image 2, ORBmatcher.cc:143-145
     const float la = __fadd_rn(__fadd_rn(__fmul_rn(qu, f12[0]), __fmul_rn(qv, f12[3])), f12[6]);
@@ -710,18 +787,18 @@ __device__ __forceinline__ unsigned long long tri_scan(const int lane, const int
         if (den == 0) continue;
         const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
         if (!((double)dsqr < 3.84 * (double)sigma2[kp.octave])) continue;
-        const unsigned long long k = ((unsigned long long)dist << 32) | (uint32_t)(0xfffff - j);
+        const unsigned long long k = ((unsigned long long)dist << 32) | (uint32_t)(0xfffff - j);   // last index wins a tie
         best = k < best ? k : best;
     }
-    return wave_min_u64(best);
+    best = wave_min_u64(best);
+    return best == ~0ull ? -1 : 0xfffff - (int)(best & 0xfffffu);
 }
 
 __global__ __launch_bounds__(256) void k_tri_search(DevFrame F, const uint32_t *__restrict__ tnode,
                                                     const uint8_t *__restrict__ tvalid,
                                                     const orbhip_query *__restrict__ q,
-                                                    const uint8_t *__restrict__ qdesc, int nq,
-                                                    unsigned long long *__restrict__ cand, int *__restrict__ cnt,
-                                                    int stride, TriParams P)
+                                                    const uint8_t *__restrict__ qdesc, int nq, int *__restrict__ out,
+                                                    TriParams P)
 {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int qi = blockIdx.x * 4 + wv;
@@ -731,15 +808,9 @@ __global__ __launch_bounds__(256) void k_tri_search(DevFrame F, const uint32_t *
     const uint32_t *qp = reinterpret_cast<const uint32_t *>(qdesc + (size_t)qi * 32);
 #pragma unroll
     for (int i = 0; i < 8; ++i) qd[i] = qp[i];
-    const unsigned long long best = tri_scan(lane, F.n, F.keys, F.desc, F.u_right, tnode, tvalid, false, false,
-                                             (uint32_t)Q.level_aux, qd, Q.u, Q.v, Q.ur >= 0, P.f12, P.ex, P.ey, P.sigma2, P.sf);
-    if (lane == 0) {
-        if (best == ~0ull) cnt[qi] = 0;
-        else {
-            cand[(size_t)qi * stride] = (best & 0xffffffff00000000ull) | (uint32_t)(0xfffff - (int)(best & 0xfffffu));
-            cnt[qi] = 1;
-        }
-    }
+    const int best = tri_scan(lane, F.n, F.keys, F.desc, F.u_right, tnode, tvalid, false, false, (uint32_t)Q.level_aux, qd,
+                              Q.u, Q.v, Q.ur >= 0, P.f12, P.ex, P.ey, P.sigma2, P.sf);
+    if (lane == 0) out[qi] = best;
 }
 
 // ---- LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) up to the map graph --------------------------------
@@ -748,8 +819,8 @@ __global__ __launch_bounds__(256) void k_tri_search(DevFrame F, const uint32_t *
 //                       the epipole (src/ORBmatcher.cc:664-670) into a [K] table; zeroes nmatches[k]
 //   k_cnmp_search       one wavefront per (current keypoint, neighbour): SearchForTriangulation straight from the frame
 //                       rows (node equality, has_point / only_stereo filters), gates as k_tri_search (shared tri_scan)
-//   k_cnmp_cull         check_ori only, one workgroup per neighbour: the rotation cull of k_resolve_par mode 4 (same
-//                       rot_bin / three_maxima; with one pre-gated candidate per query that resolve does nothing else)
+//   k_cnmp_cull         check_ori only, one workgroup per neighbour: rot_cull_body on the neighbour's row of matches, as
+//                       k_rot_cull runs it for the host SearchForTriangulation
 //   k_cnmp_triangulate  one lane per (neighbour, current keypoint): :286-431, the 4x4 problem in registers
 // Arithmetic: DESIGN.md section 3 ("Creating new map points").
 struct CnmpRow { float f12[9]; float ex, ey; int skip; };
@@ -908,44 +979,19 @@ __global__ __launch_bounds__(256) void k_cnmp_search(CnmpArgs A, CnmpLevels L)
 #pragma unroll
     for (int i = 0; i < 8; ++i) qd[i] = qp[i];
     const orbhip_keypoint kq = A.keys[q];
-    const unsigned long long best =
+    const int best =
         tri_scan(lane, n2, A.keys + f * A.cap, A.desc + f * A.cap * 32, A.u_right ? A.u_right + f * A.cap : nullptr,
                  A.node + f * A.cap, A.has_point ? A.has_point + f * A.cap : nullptr, true, A.only_stereo != 0, qnode, qd,
                  kq.x, kq.y, stereo1, row.f12, row.ex, row.ey, L.sigma2, L.sf);
-    if (lane == 0) out[qi] = best == ~0ull ? -1 : 0xfffff - (int)(best & 0xfffffu);
+    if (lane == 0) out[qi] = best;
 }
 
 __global__ __launch_bounds__(1024) void k_cnmp_cull(CnmpArgs A)
 {
-    __shared__ int hist[HISTO_LENGTH];
-    __shared__ int ind[3];
-    const int k = blockIdx.x, tid = threadIdx.x;
-    const size_t c = (size_t)A.cur, f = (size_t)A.kf_index[k];
-    const int n1 = max(min(A.n_dev[c], A.cap), 0);
-    int *m12 = A.matches12 + (size_t)k * A.cap;
-    const orbhip_keypoint *k1 = A.keys + c * A.cap, *k2 = A.keys + f * A.cap;
-    if (tid < HISTO_LENGTH) hist[tid] = 0;
-    __syncthreads();
-    for (int i = tid; i < n1; i += 1024) {
-        const int j = m12[i];
-        if (j < 0) continue;
-        const int bin = rot_bin(k1[i].angle, k2[j].angle);
-        if (bin >= 0) atomicAdd(&hist[bin], 1);
-    }
-    __syncthreads();
-    if (tid < 64) {
-        int i1, i2, i3;
-        three_maxima(hist, i1, i2, i3);
-        if (tid == 0) { ind[0] = i1; ind[1] = i2; ind[2] = i3; }
-    }
-    __syncthreads();
-    const int ind1 = ind[0], ind2 = ind[1], ind3 = ind[2];
-    for (int i = tid; i < n1; i += 1024) {
-        const int j = m12[i];
-        if (j < 0) continue;
-        const int bin = rot_bin(k1[i].angle, k2[j].angle);
-        if (bin >= 0 && bin != ind1 && bin != ind2 && bin != ind3) m12[i] = -1;
-    }
+    const size_t k = blockIdx.x, c = (size_t)A.cur, f = (size_t)A.kf_index[k];
+    const orbhip_keypoint *k1 = A.keys + c * A.cap;
+    rot_cull_body(A.matches12 + k * A.cap, max(min(A.n_dev[c], A.cap), 0), &k1->angle, sizeof(orbhip_keypoint),
+                  A.keys + f * A.cap, 1, nullptr);
 }
 
 // Correctly rounded fp32 square root.  NOT __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define that
@@ -1205,46 +1251,11 @@ __global__ __launch_bounds__(256) void k_best_in_window(DevFrame F, const uint32
     }
 }
 
-// ---- rotation histogram: bin of a match, three largest bins ------------------------------------
-__device__ __forceinline__ int rot_bin(float a1, float a2)
-{
-    const float factor = 1.0f / HISTO_LENGTH;
-    float rot = __fsub_rn(a1, a2);
-    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-    int bin = (int)roundf(__fmul_rn(rot, factor));
-    if (bin == HISTO_LENGTH) bin = 0;
-    // keypoint angles are caller data: outside [0, 360) (or NaN) the reference trips its assert(bin>=0 && bin<HISTO_LENGTH);
-    // here such a match simply takes no part in the rotation histogram (-1) instead of writing outside it
-    return (bin >= 0 && bin < HISTO_LENGTH) ? bin : -1;
-}
-
-__device__ __forceinline__ void three_maxima(const int *h, int &ind1, int &ind2, int &ind3)
-{
-    // ComputeThreeMaxima (src/ORBmatcher.cc:1601-1645) as selects on values: with the three indices passed by reference
-    // through a chain of branches the compiler kept them in scratch memory (150 scratch accesses per call)
-    int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-    int hv[HISTO_LENGTH];   // all bins first (independent loads, one wait), then the scan on registers
-#pragma unroll
-    for (int i = 0; i < HISTO_LENGTH; ++i) hv[i] = h[i];
-#pragma unroll
-    for (int i = 0; i < HISTO_LENGTH; ++i) {
-        const int s = hv[i];
-        const bool g1 = s > max1, g2 = s > max2, g3 = s > max3;
-        max3 = g2 ? max2 : (g3 ? s : max3);  i3 = g2 ? i2 : (g3 ? i : i3);
-        max2 = g1 ? max1 : (g2 ? s : max2);  i2 = g1 ? i1 : (g2 ? i : i2);
-        max1 = g1 ? s : max1;                i1 = g1 ? i : i1;
-    }
-    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { i2 = -1; i3 = -1; }
-    else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { i3 = -1; }
-    ind1 = i1; ind2 = i2; ind3 = i3;
-}
-
-// ---- parallel resolve: modes 0 / 1 (SearchByProjection overloads) and 4 (SearchForTriangulation: one pre-gated
-// candidate per query, no blocking, rotation cull, output per query) ---------------------------------------------
+// ---- parallel resolve: modes 0 / 1 (the SearchByProjection overloads) ------------------------------------------
 // The sequential reference loop hands every query, in index order, the first candidate of its list (sorted by
 // (distance, visiting order)) that is neither taken on entry nor already held by an accepted, observed query with a
 // smaller index.  That is serial dictatorship.
-//  * Modes 0 / 4 (frame-to-frame search, triangulation): acceptance depends on the first usable entry alone, so nobody
+//  * Mode 0 (frame-to-frame search): acceptance depends on the first usable entry alone, so nobody
 //    ever gives a held slot up, and the outcome is the unique stable matching of "queries prefer list order, slots
 //    prefer the smaller query index", which deferred acceptance reaches from any proposal order: unsettled queries
 //    propose (atomicMin on the slot's holder) to the first entry no smaller query holds; a holder only ever gets
@@ -1634,7 +1645,7 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
     for (int c = tid; c < n; c += T) assign[c] = -1;
     __syncthreads();
     int acc_local = 0;
-    const bool ori = (mode == 0 || mode == 4) && check_ori;
+    const bool ori = mode == 0 && check_ori;
     for (int i0 = 0; i0 < nq; i0 += T) {
         const int i = i0 + tid;
         const int c = i < nq ? S.choice[i] : -1;
@@ -1647,31 +1658,18 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
                 if (bin >= 0) S.evbin[i] = (unsigned char)bin;
             }
         }
-        // one LDS atomic per distinct bin of the wavefront (most matches of a frame pair share a rotation bin)
-        unsigned long long todo = __ballot(bin >= 0);
-        while (todo) {
-            const int lead = __builtin_amdgcn_readlane(bin, __ffsll((long long)todo) - 1);
-            const unsigned long long same = __ballot(bin == lead);
-            if ((tid & 63) == __ffsll((long long)todo) - 1) atomicAdd(&S.hist[lead], __popcll(same));
-            todo &= ~same;
-        }
+        wave_hist_add(S.hist, bin);
     }
     acc_local = wave_reduce_add_i(acc_local);
     if ((tid & 63) == 0 && acc_local) atomicAdd(&S.vars[1], acc_local);
     __syncthreads();
     if (ori) {
-        if (tid < 64) {   // one wavefront ranks the bins (the pair's 16 wavefronts share one CU's issue slots)
-            int i1, i2, i3;
-            three_maxima(S.hist, i1, i2, i3);
-            if (tid == 0) { S.vars[8] = i1; S.vars[9] = i2; S.vars[10] = i3; }
-        }
-        __syncthreads();
+        rank_bins_once(S.hist, S.vars + 8);
         const int ind1 = S.vars[8], ind2 = S.vars[9], ind3 = S.vars[10];
         int cull = 0;
         for (int i = tid; i < nq; i += T) {
-            const int b = S.evbin[i];
-            if (b != 0xff && b != ind1 && b != ind2 && b != ind3) {
-                if (mode == 4) S.choice[i] = -1; else assign[S.choice[i]] = -1;
+            if (rot_culled(S.evbin[i], ind1, ind2, ind3)) {
+                assign[S.choice[i]] = -1;
                 ++cull;
             }
         }
@@ -1679,8 +1677,7 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
         if ((tid & 63) == 0 && cull) atomicAdd(&S.vars[2], cull);
         __syncthreads();
     }
-    if (mode == 4) for (int i = tid; i < nq; i += T) out[i] = S.choice[i];   // per query, no slot exclusivity
-    else for (int c = tid; c < n; c += T) out[c] = assign[c];
+    for (int c = tid; c < n; c += T) out[c] = assign[c];
     if (tid == 0) *out_n = S.vars[1] - S.vars[2];
 }
 
@@ -1924,31 +1921,17 @@ __global__ __launch_bounds__(1024) void k_resolve_init(DevFrame F, const orbhip_
             }
         }
         if (i < nq) { S.q_cnt[i] = m; kept += m >= 0; }   // q_cnt is free now: vnMatches12
-        unsigned long long todo = __ballot(bin >= 0);
-        while (todo) {
-            const int first = __ffsll((long long)todo) - 1;
-            const int lead = __builtin_amdgcn_readlane(bin, first);
-            const unsigned long long same = __ballot(bin == lead);
-            if ((tid & 63) == first) atomicAdd(&S.hist[lead], __popcll(same));
-            todo &= ~same;
-        }
+        wave_hist_add(S.hist, bin);
     }
     kept = wave_reduce_add_i(kept);
     if ((tid & 63) == 0 && kept) atomicAdd(&S.vars[4], kept);
     __syncthreads();
     if (check_ori) {
-        if (tid < 64) {
-            int i1, i2, i3;
-            three_maxima(S.hist, i1, i2, i3);
-            if (tid == 0) { S.vars[8] = i1; S.vars[9] = i2; S.vars[10] = i3; }
-        }
-        __syncthreads();
+        rank_bins_once(S.hist, S.vars + 8);
         const int ind1 = S.vars[8], ind2 = S.vars[9], ind3 = S.vars[10];
         int cull = 0;
-        for (int i = tid; i < nq; i += T) {
-            const int b = S.evbin[i];
-            if (b != 0xff && b != ind1 && b != ind2 && b != ind3 && S.q_cnt[i] >= 0) { S.q_cnt[i] = -1; ++cull; }
-        }
+        for (int i = tid; i < nq; i += T)
+            if (rot_culled(S.evbin[i], ind1, ind2, ind3) && S.q_cnt[i] >= 0) { S.q_cnt[i] = -1; ++cull; }
         cull = wave_reduce_add_i(cull);
         if ((tid & 63) == 0 && cull) atomicAdd(&S.vars[5], cull);
         __syncthreads();
@@ -3470,37 +3453,32 @@ static int run_bow(orbhip_matcher *m, const orbhip_frame_view *f1, const uint32_
     Stage st;
     int rc;
     if ((rc = stage_begin(m, al256(n * sizeof(orbhip_keypoint)) + al256(n * 32) + al256((size_t)nt * 4) + al256((size_t)nt) +
-                                 al256((size_t)nq * 32) + al256((size_t)nq * 4) + al256((size_t)ng * sizeof(NodeGroup)) +
-                                 al256(HISTO_LENGTH * 4), &st))) return rc;
+                                 al256((size_t)nq * 32) + al256((size_t)nq * 4) + al256((size_t)ng * sizeof(NodeGroup)), &st)))
+        return rc;
     const orbhip_keypoint *d_tkeys = st.put(f2->keys, n);
     const uint8_t *d_tdesc = st.put(f2->desc, n * 32);
     const uint32_t *d_torder = st.put(reinterpret_cast<const uint32_t *>(torder.data()), (size_t)nt);
     const uint8_t *d_matched, *d_qdesc;
     const float *d_qangle;
-    const int *d_hist;
     uint8_t *hm = st.take((size_t)nt, &d_matched);
     uint8_t *hqd = st.take((size_t)nq * 32, &d_qdesc);
     float *hqa = st.take((size_t)nq, &d_qangle);
     const NodeGroup *d_groups = st.put(groups.data(), (size_t)ng);
-    int *hh = st.take((size_t)HISTO_LENGTH, &d_hist);
     if ((rc = st.status())) return rc;
     for (int c = 0; c < nt; ++c) hm[c] = (uint8_t)(blocked2 && blocked2[torder[c]]);
     for (int p = 0; p < nq; ++p) {
         memcpy(hqd + (size_t)p * 32, f1->desc + (size_t)order[p] * 32, 32);
         hqa[p] = f1->keys[order[p]].angle;
     }
-    memset(hh, 0, HISTO_LENGTH * 4);
     if ((rc = stage_commit(m, &st))) return rc;
     void *p;
     if ((rc = scratch(m, S_OUT, (size_t)(nq + 1) * sizeof(int), &p))) return rc;
     int *d_out = (int *)p;
-    if ((rc = scratch(m, S_CNT, (size_t)nq, &p))) return rc;
-    uint8_t *d_bin = (uint8_t *)p;
     // queries whose node does not occur in f2 belong to no group: they stay at -1
     ORBHIP_HIP_CHECK(hipMemsetAsync(d_out, 0xff, (size_t)nq * sizeof(int), m->stream));
-    hipLaunchKernelGGL(k_bow_groups, dim3((ng + 3) / 4), dim3(256), 0, m->stream, d_groups, ng, d_qdesc, d_qangle, d_torder,
-                       d_tdesc, d_tkeys, (uint8_t *)d_matched, max_dist, nnratio, check_ori, d_out, d_bin, (int *)d_hist);
-    hipLaunchKernelGGL(k_bow_cull, dim3(1), dim3(1024), 0, m->stream, nq, check_ori, d_hist, (const uint8_t *)d_bin, d_out,
+    hipLaunchKernelGGL(k_bow_groups, dim3((ng + 3) / 4), dim3(256), 0, m->stream, d_groups, ng, d_qdesc, d_torder, d_tdesc,
+                       (uint8_t *)d_matched, max_dist, nnratio, d_out);
+    hipLaunchKernelGGL(k_rot_cull, dim3(1), dim3(1024), 0, m->stream, d_out, nq, (const void *)d_qangle, 4, d_tkeys, check_ori,
                        d_out + nq);
     const uint8_t *h;
     if ((rc = read_back(m, d_out, (size_t)(nq + 1) * sizeof(int), &h))) return rc;
@@ -3511,7 +3489,8 @@ static int run_bow(orbhip_matcher *m, const orbhip_frame_view *f1, const uint32_
     return ORBHIP_OK;
 }
 
-// SearchForTriangulation
+// SearchForTriangulation.  The kResolveMax size limit is the one include/orbhip.h documents for the entry point (n1, n2 <=
+// 4096); nothing on this path sizes device state by it.
 static int run_tri(orbhip_matcher *m, const TriParams *tri, const orbhip_frame_view *f1, const uint32_t *node1,
                    const uint8_t *valid1, const orbhip_frame_view *f2, const uint32_t *node2, const uint8_t *valid2,
                    int only_stereo, int check_ori, int32_t *matches12, int *nmatches)
@@ -3569,20 +3548,12 @@ static int run_tri(orbhip_matcher *m, const TriParams *tri, const orbhip_frame_v
     }
     if ((rc = stage_commit(m, &st))) return rc;
     void *p;
-    const int stride = 2;
-    if ((rc = scratch(m, S_CAND, (size_t)nq * stride * sizeof(unsigned long long), &p))) return rc;
-    unsigned long long *d_cand = (unsigned long long *)p;
-    if ((rc = scratch(m, S_CNT, (size_t)nq * sizeof(int), &p))) return rc;
-    int *d_cnt = (int *)p;
     if ((rc = scratch(m, S_OUT, (size_t)(nq + 1) * sizeof(int), &p))) return rc;
     int *d_out = (int *)p;
-    const Batch B = {nullptr, nullptr, n2, nq};
-    if ((rc = ensure_resolve_attr(m))) return rc;
-    hipLaunchKernelGGL(k_tri_search, dim3((nq + 3) / 4), dim3(256), 0, m->stream, D, d_tnode, d_mask, d_q, d_qdesc, nq,
-                       d_cand, d_cnt, stride, *tri);
-    if ((rc = launch_resolve_par(m, 1, 4, D, d_q, d_cand, nullptr, d_cnt, stride, (const uint8_t *)nullptr, 0.f, check_ori,
-                                 d_out, d_out + nq, B, TH_LOW, 0)))
-        return rc;
+    hipLaunchKernelGGL(k_tri_search, dim3((nq + 3) / 4), dim3(256), 0, m->stream, D, d_tnode, d_mask, d_q, d_qdesc, nq, d_out,
+                       *tri);
+    hipLaunchKernelGGL(k_rot_cull, dim3(1), dim3(1024), 0, m->stream, d_out, nq, (const void *)&d_q->angle,
+                       (int)sizeof(orbhip_query), D.keys, check_ori, d_out + nq);
     const uint8_t *h;
     if ((rc = read_back(m, d_out, (size_t)(nq + 1) * sizeof(int), &h))) return rc;
     const int *res = reinterpret_cast<const int *>(h);
