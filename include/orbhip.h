@@ -561,7 +561,8 @@ int orbhip_keyframe_queries(orbhip_matcher *m, const orbhip_camera *cam, int mod
 /* ORBmatcher::Fuse up to the decision (src/ORBmatcher.cc:825-947 / :975-1075): prologue + best key point in the window
  * with the chi-square gate; best_idx[n] / best_dist[n] out (-1 / 256 when nothing passes).  The replace-or-add decision
  * (:949-971, :1077-1095: bestDist <= TH_LOW, pKF->GetMapPoint(bestIdx), Replace / AddObservation) touches the map
- * graph, depends on the order of the points and stays in the caller.  sim3_form != 0: the Scw overload (invz in double).
+ * graph, depends on the order of the points and stays in the caller.  sim3_form != 0: the Scw overload (invz in double,
+ * and no chi-square gate: its loop, :1062-1079, tests the level window only; inv_level_sigma2 is not read).
  * point_desc [n][32] = pMP->GetDescriptor(). */
 int orbhip_fuse(orbhip_matcher *m, const orbhip_frame_view *kf, const orbhip_camera *cam, const float *Tcw, int sim3_form,
                 int n, const float *world, const float *normal, const float *max_dist, const float *min_dist,

@@ -1721,7 +1721,9 @@ void oracle_project_last_frame(const oracle_camera *cam, const float *Tcw, const
         const int o = last_keys[i].octave;
         q[i].valid = 1;
         q[i].u = u; q[i].v = v;
-        q[i].radius = th * cam->scale_factors[o];
+        /* an octave outside the table is caller data (the reference reads out of bounds): the first entry below 0,
+         * a factor of 0 past the end */
+        q[i].radius = th * (o < 0 ? cam->scale_factors[0] : o >= cam->n_levels ? 0.0f : cam->scale_factors[o]);
         if (forward) { q[i].min_level = o; q[i].max_level = -1; }
         else if (backward) { q[i].min_level = 0; q[i].max_level = o; }
         else { q[i].min_level = o - 1; q[i].max_level = o + 1; }

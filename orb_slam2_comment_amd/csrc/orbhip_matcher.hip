@@ -2499,7 +2499,8 @@ struct FuseBatchArgs {
     const uint8_t *point_desc, *flags;      // [np][32], [K][pcap]
     int *best_idx, *best_dist;              // [K][pcap]
     orbhip_query *q;                        // [K][pcap] or null
-    int cap, np, pcap, double_invz;
+    int cap, np, pcap;
+    int sim3_form;                          // the Scw overload (src/ORBmatcher.cc:977-1100): invz = 1.0/z in double, no chi-square gate
     int csr_by_target;                      // CSR rows are indexed by k (built by this call), not by the frame row
     float min_x, min_y, inv_w, inv_h;
 };
@@ -2536,7 +2537,7 @@ __global__ __launch_bounds__(256) void k_fuse_batch(FuseBatchArgs A, orbhip_came
         KfQueryArgs P;
         P.T1 = A.Tcw + (size_t)k * 12; P.T2 = nullptr;
         P.world = A.world; P.normal = A.normal; P.max_dist = A.max_dist; P.min_dist = A.min_dist;
-        P.flags = A.flags + orow; P.q = nullptr; P.n = A.np; P.mode = 0; P.double_invz = A.double_invz;
+        P.flags = A.flags + orow; P.q = nullptr; P.n = A.np; P.mode = 0; P.double_invz = A.sim3_form;
         Q = keyframe_query(P, cam, th, i);
         if (A.q) A.q[orow + i] = Q;
         if (!Q.valid) { A.best_idx[orow + i] = -1; A.best_dist[orow + i] = 256; }
@@ -2594,13 +2595,15 @@ __global__ __launch_bounds__(256) void k_fuse_batch(FuseBatchArgs A, orbhip_came
                         if (kp.octave < min_level || kp.octave > min_level + 1) continue;   // kpLevel<pred-1 || kpLevel>pred
                         const float ex = __fsub_rn(x, kp.x), ey = __fsub_rn(y, kp.y);
                         float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-                        const float kpr = u_right ? u_right[j] : -1.0f;
-                        const float is2 = sig.inv_sigma2[kp.octave & (ORBHIP_MAX_LEVELS - 1)];
-                        if (kpr >= 0) {
-                            const float er = __fsub_rn(qur, kpr);
-                            e2 = __fadd_rn(e2, __fmul_rn(er, er));
-                            if ((double)__fmul_rn(e2, is2) > 7.8) continue;
-                        } else if ((double)__fmul_rn(e2, is2) > 5.99) continue;
+                        if (!A.sim3_form) {                 // the loop of the Scw overload (:1062-1079) has no chi-square gate
+                            const float kpr = u_right ? u_right[j] : -1.0f;
+                            const float is2 = sig.inv_sigma2[kp.octave & (ORBHIP_MAX_LEVELS - 1)];
+                            if (kpr >= 0) {
+                                const float er = __fsub_rn(qur, kpr);
+                                e2 = __fadd_rn(e2, __fmul_rn(er, er));
+                                if ((double)__fmul_rn(e2, is2) > 7.8) continue;
+                            } else if ((double)__fmul_rn(e2, is2) > 5.99) continue;
+                        }
                         const uint4 *tp = reinterpret_cast<const uint4 *>(desc + (size_t)j * 32);
                         const uint4 t0 = tp[0], t1 = tp[1];
                         const int d = __popc(qd[0] ^ t0.x) + __popc(qd[1] ^ t0.y) + __popc(qd[2] ^ t0.z) + __popc(qd[3] ^ t0.w) +
@@ -4428,7 +4431,8 @@ int orbhip_fuse(orbhip_matcher *m, const orbhip_frame_view *kf, const orbhip_cam
     q.resize((size_t)n);
     int rc = orbhip_keyframe_queries(m, cam, 0, sim3_form ? 1 : 0, Tcw, nullptr, n, world, normal, max_dist, min_dist, flags, th, q.data());
     if (rc) return rc;
-    return orbhip_search_best_in_window(m, kf, q.data(), point_desc, n, 1, inv_level_sigma2, best_idx, best_dist);
+    // the Scw overload (src/ORBmatcher.cc:1062-1079) has no chi-square gate
+    return orbhip_search_best_in_window(m, kf, q.data(), point_desc, n, sim3_form ? 0 : 1, inv_level_sigma2, best_idx, best_dist);
 }
 
 // lanes per query of k_fuse_batch: 8 is the mapping kept; development builds can select the
@@ -4468,7 +4472,7 @@ int orbhip_fuse_device(orbhip_matcher *m, int K, const void *d_kf_index, const o
     A.max_dist = (const float *)d_max_dist; A.min_dist = (const float *)d_min_dist;
     A.point_desc = (const uint8_t *)d_point_desc; A.flags = (const uint8_t *)d_flags;
     A.best_idx = (int *)d_best_idx; A.best_dist = (int *)d_best_dist; A.q = (orbhip_query *)d_q;
-    A.cap = cap; A.np = np; A.pcap = pcap; A.double_invz = sim3_form ? 1 : 0; A.csr_by_target = 0;
+    A.cap = cap; A.np = np; A.pcap = pcap; A.sim3_form = sim3_form ? 1 : 0; A.csr_by_target = 0;
     // Frame::ComputeImageBounds / mfGridElement{Width,Height}Inv (src/Frame.cc:99-100) from the camera's bounds
     A.min_x = cam->min_x; A.min_y = cam->min_y;
     A.inv_w = (float)GRID_COLS / (cam->max_x - cam->min_x); A.inv_h = (float)GRID_ROWS / (cam->max_y - cam->min_y);

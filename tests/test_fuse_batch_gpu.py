@@ -91,7 +91,8 @@ def oracle_rows(O, S, kf_index, flags, th, sim3_form, X=None, nrm=None, max_d=No
         keep = []
         u = None if ur is None else ur[f]
         ov = O.make_frame(k, d, u, (0.0, 0.0, float(W), float(H)), S["sf"], keep)
-        obi, obd = O.search_best_in_window(ov, oq, pdesc, S["inv_sigma2"])
+        # the Scw overload has no chi-square gate (src/ORBmatcher.cc:1062-1079)
+        obi, obd = O.search_best_in_window(ov, oq, pdesc, None if sim3_form else S["inv_sigma2"])
         rows.append((oq, obi, obd))
     return rows
 

@@ -320,7 +320,8 @@ def test_fuse_prologue_and_search(env, sim3_form, th):
     _assert_queries_equal(q, oq)
     assert 200 < q["valid"].sum() < len(q)
     bi, bd = m.Fuse(gv, cam, T, X, nrm, max_d, min_d, flags, pdesc, th, inv_sigma2, sim3_form)
-    obi, obd = O.search_best_in_window(ov, oq, pdesc, inv_sigma2)
+    # the Scw overload has no chi-square gate (src/ORBmatcher.cc:1062-1079)
+    obi, obd = O.search_best_in_window(ov, oq, pdesc, None if sim3_form else inv_sigma2)
     assert np.array_equal(bi, obi) and np.array_equal(bd, obd)
     assert (bd <= 50).sum() > 150
 
@@ -340,16 +341,30 @@ def test_search_by_sim3_complete(env):
     T1w = np.eye(4, dtype=np.float32)
     T2w = np.eye(4, dtype=np.float32)
     T2w[0, 3] = np.float32(4.0 * 12.0 / KITTI_FX); T2w[1, 3] = np.float32(2.0 * 12.0 / KITTI_FY)
-    s12 = np.float32(1.0)
-    R12, t12 = np.eye(3, dtype=np.float32), -T2w[:3, 3]              # camera 1 from camera 2
-    S12 = np.eye(4, dtype=np.float32); S12[:3, :3] = s12 * R12; S12[:3, 3] = t12
-    sR21 = (np.float32(1.0 / s12) * R12.T).astype(np.float32)
+    s12 = np.float32(1.05)
+    R12, t12 = _pose(rng)[:3, :3].copy(), -T2w[:3, 3]                # camera 1 from camera 2: a small rotation, scale 1.05
+    S12 = np.eye(4, dtype=np.float32); S12[:3, :3] = (np.float64(s12) * R12).astype(np.float32); S12[:3, 3] = t12
+    sR21 = ((1.0 / np.float64(s12)) * R12.T).astype(np.float32)
     S21 = np.eye(4, dtype=np.float32); S21[:3, :3] = sR21; S21[:3, 3] = -(sR21 @ t12)
+    assert not np.allclose(S21[:3, :3], S12[:3, :3].T, atol=0.05) and not np.allclose(R12, R12.T, atol=1e-3)
     z = np.float32(12.0)
-    X1 = _back_project(k1, np.full(len(k1), z, np.float32), cam, T1w)
-    X2 = _back_project(k2, np.full(len(k2), z, np.float32), cam, T2w)
-    mx1 = (z * np.float32(1.2) ** k1["octave"].astype(np.float32)).astype(np.float32)
-    mx2 = (z * np.float32(1.2) ** k2["octave"].astype(np.float32)).astype(np.float32)
+    eye = np.eye(4, dtype=np.float32)
+
+    def through(S, T, Pc):
+        """Camera coordinates Pc carried through the Sim3 S into the other camera, then into the world of its pose T."""
+        Pc = Pc.astype(np.float64) @ S[:3, :3].astype(np.float64).T + S[:3, 3].astype(np.float64)
+        return ((Pc - T[:3, 3].astype(np.float64)) @ T[:3, :3].astype(np.float64)).astype(np.float32)
+
+    # the map point in slot i of key frame 1 is the one S21 carries onto key point i shifted by the image shift, at depth
+    # 12 m in camera 2 (and the other way round), so each direction projects onto its counterpart; the matching distance
+    # is the one PredictScale measures there, |p3Dc|, half a level below the key point's octave
+    s1, s2 = k1.copy(), k2.copy()
+    s1["x"] += 4; s1["y"] += 2; s2["x"] -= 4; s2["y"] -= 2
+    P2 = _back_project(s1, np.full(len(k1), z, np.float32), cam, eye)
+    P1 = _back_project(s2, np.full(len(k2), z, np.float32), cam, eye)
+    X1, X2 = through(S12, T1w, P2), through(S21, T2w, P1)
+    mx1 = (np.linalg.norm(P2, axis=1) * 1.2 ** (k1["octave"] - 0.5)).astype(np.float32)
+    mx2 = (np.linalg.norm(P1, axis=1) * 1.2 ** (k2["octave"] - 0.5)).astype(np.float32)
     mn1, mn2 = (mx1 / np.float32(3.58)).astype(np.float32), (mx2 / np.float32(3.58)).astype(np.float32)
     f1 = (rng.random(len(k1)) < 0.9).astype(np.uint8)
     f2 = (rng.random(len(k2)) < 0.9).astype(np.uint8)
