@@ -35,6 +35,7 @@
  *   orbhip_compute_stereo_from_rgbd_raw  the same on the sensor's depth image: imDepth.convertTo(CV_32F, mDepthMapFactor)
  *                                     (src/Tracking.cc:227-228) applied to the samples the keypoints read
  *   orbhip_distinctive_descriptors    MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307), batched
+ *   orbhip_update_map_points*         the same and MapPoint::UpdateNormalAndDepth (:330-371) from an observation table
  *   orbhip_vocabulary_*               ORBVocabulary (DBoW2::TemplatedVocabulary<FORB>) loadFromTextFile + transform,
  *                                     i.e. Frame::ComputeBoW (src/Frame.cc:395-402)
  *   orbhip_search_by_bow              ORBmatcher::SearchByBoW(KeyFrame*,Frame&,..) (src/ORBmatcher.cc:159-288) and
@@ -698,6 +699,60 @@ int orbhip_count_close_points(orbhip_matcher *m, const float *depth, const uint8
  * output frame, like the other arrays); d_counts [frames][2] int32 = {nTrackedClose, nNonTrackedClose}.  Asynchronous. */
 int orbhip_count_close_points_device(orbhip_matcher *m, int frames, const void *d_depth, const void *d_flags, const void *d_n,
                                      int cap, float th_depth, void *d_counts);
+
+/* ---- refreshing map points: descriptor, normal and depth range ---------------------------------------------------
+ * MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307) and MapPoint::UpdateNormalAndDepth (:330-371) for np map
+ * points in one call, from an observation table over the key-frame bank the other _device entries read (d_Tcw [rows][12],
+ * d_kps [rows][cap] = mvKeysUn, d_desc [rows][cap][32], d_n [rows]).  It writes the four per-point arrays that
+ * orbhip_fuse_device, orbhip_frustum_queries_device, orbhip_keyframe_queries and orbhip_search_by_sim3 read, so that the
+ * steps the reference follows with both functions (src/LocalMapping.cc:152-153, :442-444, :526-527; src/Tracking.cc:532-533,
+ * :668-669, :1117-1118; src/LoopClosing.cc:500, :532; normal and depth only: src/Optimizer.cc:227, :776, :1042) need no host
+ * hop.  The map graph (AddObservation, Replace, the choice of mpRefKF, building the table) stays with the caller.
+ *   what: ORBHIP_UPDATE_DESCRIPTOR | ORBHIP_UPDATE_NORMAL_DEPTH, at least one of them (anything else: ORBHIP_E_ARG).
+ *   Table, CSR in the caller's order: d_obs_start [np+1] int32, non-decreasing; observation j of point p is key point
+ *   d_obs_idx[o] of bank row d_obs_kf[o], o = d_obs_start[p] + j.  A row may repeat inside a list.  d_ref_obs [np] int32: the
+ *   position j of mpRefKF's observation in the point's own list (what observations[pRefKF] finds).  The reference iterates a
+ *   map<KeyFrame*, size_t>, in heap-address order; here the order is the table's: it decides the float sum of the normal
+ *   and which of several equal medians wins (the first).
+ *   d_kf_bad [rows] uint8, nullable: pKF->isBad().  Such an observation is left out of the descriptor set (:265) but still
+ *   counts for the normal and for n (:350-357 has no such test).
+ *   d_flags [pcap] uint8: ORBHIP_POINT_PRESENT = !mbBad; d_world [pcap][3] = mWorldPos.
+ *   Outputs, written only where the reference writes (every other entry, and everything at np and above, keeps the caller's
+ *   bytes): d_point_desc [pcap][32] = mDescriptor, d_normal [pcap][3] = mNormalVector, d_max_dist / d_min_dist [pcap] = raw
+ *   mfMaxDistance / mfMinDistance (the consumers apply 1.2 / 0.8 themselves).  Reports, written for every p < np:
+ *   d_status [np] uint8 = one ORBHIP_MAPPOINT_* code; d_best_obs [np] int32 (nullable; written when ORBHIP_UPDATE_DESCRIPTOR
+ *   is selected) = position in the point's list of the chosen descriptor, -1 where none was chosen.
+ *   Arithmetic: DESIGN.md section 3.  A point on a camera centre divides by zero; the inf / NaN propagates as is.
+ *   The device form does not range-check rows, key-point indices or d_obs_start (like d_kf_index elsewhere); d_n is not read.
+ *   cap <= 4096 (ORBHIP_E_CAPACITY beyond); np == 0: success, nothing written; np < 0, np > pcap, a bad mask or a null
+ *   pointer that a selected bit needs (descriptor: d_desc, d_point_desc; normal / depth: cam, d_Tcw, d_kps, d_ref_obs,
+ *   d_world, d_normal, d_max_dist, d_min_dist; always: the table, d_flags, d_status): ORBHIP_E_ARG before any device work.
+ *   Asynchronous on the matcher's stream, no host synchronisation and no staging copy; the worklist of the points with more
+ *   than 16 observations lives in the handle. */
+#define ORBHIP_UPDATE_DESCRIPTOR   1   /* ComputeDistinctiveDescriptors */
+#define ORBHIP_UPDATE_NORMAL_DEPTH 2   /* UpdateNormalAndDepth */
+#define ORBHIP_MAPPOINT_UPDATED        0   /* refreshed as asked */
+#define ORBHIP_MAPPOINT_BAD            1   /* not ORBHIP_POINT_PRESENT (:251, :338): nothing written */
+#define ORBHIP_MAPPOINT_NO_OBSERVATION 2   /* empty list (:256, :345): nothing written */
+#define ORBHIP_MAPPOINT_NO_DESCRIPTOR  3   /* every observing key frame is bad (:269); normal and depth range are written */
+#define ORBHIP_MAPPOINT_BAD_REF        4   /* ref_obs outside [0, N): the descriptor is written, normal and depth range are
+                                              not; reported in preference to NO_DESCRIPTOR */
+#define ORBHIP_MAPPOINT_TOO_MANY       5   /* N > 2048, the limit of orbhip_distinctive_descriptors: nothing written */
+int orbhip_update_map_points_device(orbhip_matcher *m, const orbhip_camera *cam, int what, const void *d_Tcw, const void *d_kps,
+                                    const void *d_desc, const void *d_n, int cap, const void *d_kf_bad, int np, int pcap,
+                                    const void *d_obs_start, const void *d_obs_kf, const void *d_obs_idx, const void *d_ref_obs,
+                                    const void *d_world, const void *d_flags, void *d_point_desc, void *d_normal,
+                                    void *d_max_dist, void *d_min_dist, void *d_best_obs, void *d_status);
+/* Host buffers, synchronous: one staging copy, the device call above, one read-back.  The bank is K frame views (keys,
+ * desc, n; at most 4096 key points each), Tcw [K][12] and kf_bad [K] (nullable); obs_kf indexes the views.  The four
+ * arrays are in/out with np entries (entries the reference would not write keep the caller's values); best_obs (nullable)
+ * and status are outputs.  Rows outside [0, K), key-point indices outside [0, kfs[row]->n) and a decreasing obs_start are
+ * ORBHIP_E_ARG.  Arrays that the selected bits do not need may be null. */
+int orbhip_update_map_points(orbhip_matcher *m, const orbhip_camera *cam, int what, int K, const orbhip_frame_view *const *kfs,
+                             const float *Tcw, const uint8_t *kf_bad, int np, const int32_t *obs_start, const int32_t *obs_kf,
+                             const int32_t *obs_idx, const int32_t *ref_obs, const float *world, const uint8_t *flags,
+                             uint8_t *point_desc, float *normal, float *max_dist, float *min_dist, int32_t *best_obs,
+                             uint8_t *status);
 
 /* ---- creating new map points -------------------------------------------------------------------------------------
  * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) for the current key frame and K neighbours in one call, up

@@ -639,6 +639,47 @@ public:
               "orbhip_count_close_points_device");
     }
 
+    // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307; what & ORBHIP_UPDATE_DESCRIPTOR) and
+    // MapPoint::UpdateNormalAndDepth (:330-371; what & ORBHIP_UPDATE_NORMAL_DEPTH) for the obsStart.size() - 1 map points of an
+    // observation table in CSR form: observation j of point p is key point obsIdx[o] of KFs[obsKf[o]], o = obsStart[p] + j;
+    // refObs[p] is the position of mpRefKF's observation in the point's list.  Tcw: 12 floats per key frame; kfBad: one
+    // byte per key frame (pKF->isBad()) or empty; flags: ORBHIP_POINT_PRESENT = !mbBad.  pointDesc (32 bytes per point),
+    // normal (3 floats), maxDist and minDist are updated in place where the reference writes; bestObs = the position of
+    // the chosen descriptor in each list (-1: none), status = one ORBHIP_MAPPOINT_* code per point.
+    void UpdateMapPoints(const orbhip_camera &cam, int what, const std::vector<const orbhip_frame_view *> &KFs,
+                         const std::vector<float> &Tcw, const std::vector<uint8_t> &kfBad, const std::vector<int32_t> &obsStart,
+                         const std::vector<int32_t> &obsKf, const std::vector<int32_t> &obsIdx, const std::vector<int32_t> &refObs,
+                         const std::vector<float> &world, const std::vector<uint8_t> &flags, std::vector<uint8_t> &pointDesc,
+                         std::vector<float> &normal, std::vector<float> &maxDist, std::vector<float> &minDist,
+                         std::vector<int32_t> &bestObs, std::vector<uint8_t> &status)
+    {
+        if (obsStart.empty()) throw Error(ORBHIP_E_ARG, "UpdateMapPoints");
+        const size_t n = obsStart.size() - 1, K = KFs.size();
+        if (Tcw.size() != 12 * K || (!kfBad.empty() && kfBad.size() != K) || obsKf.size() != obsIdx.size() ||
+            (n > 0 && (obsStart[n] < 0 || obsKf.size() < (size_t)obsStart[n])) || refObs.size() != n || world.size() != 3 * n ||
+            flags.size() != n || pointDesc.size() != 32 * n || normal.size() != 3 * n || maxDist.size() != n || minDist.size() != n)
+            throw Error(ORBHIP_E_ARG, "UpdateMapPoints");
+        bestObs.assign(n ? n : 1, -1);
+        status.assign(n ? n : 1, 0);
+        check(orbhip_update_map_points(m_, &cam, what, (int)K, KFs.data(), Tcw.data(), kfBad.empty() ? nullptr : kfBad.data(), (int)n,
+                                       obsStart.data(), obsKf.data(), obsIdx.data(), refObs.data(), world.data(), flags.data(),
+                                       pointDesc.data(), normal.data(), maxDist.data(), minDist.data(), bestObs.data(),
+                                       status.data()), "orbhip_update_map_points");
+        bestObs.resize(n);
+        status.resize(n);
+    }
+    // device-resident, asynchronous on the matcher's stream: orbhip_update_map_points_device with the mirror's handle; the
+    // table indexes the rows of the bank the other *Device calls read, and the four arrays are the ones FuseDevice reads
+    void UpdateMapPointsDevice(const orbhip_camera &cam, int what, const void *dTcw, const void *dKps, const void *dDesc,
+                               const void *dN, int cap, const void *dKfBad, int np, int pcap, const void *dObsStart,
+                               const void *dObsKf, const void *dObsIdx, const void *dRefObs, const void *dWorld, const void *dFlags,
+                               void *dPointDesc, void *dNormal, void *dMaxDist, void *dMinDist, void *dBestObs, void *dStatus)
+    {
+        check(orbhip_update_map_points_device(m_, &cam, what, dTcw, dKps, dDesc, dN, cap, dKfBad, np, pcap, dObsStart, dObsKf,
+                                              dObsIdx, dRefObs, dWorld, dFlags, dPointDesc, dNormal, dMaxDist, dMinDist, dBestObs,
+                                              dStatus), "orbhip_update_map_points_device");
+    }
+
     // the Frame statics the prologues read (src/Frame.cc:97-112), as one record
     static orbhip_camera MakeCamera(float fx, float fy, float cx, float cy, float mbf, float mb, float minX, float maxX, float minY,
                                     float maxY, const std::vector<float> &scaleFactors, float logScaleFactor)

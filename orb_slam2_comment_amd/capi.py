@@ -47,6 +47,10 @@ SEED_ALL, SEED_CLOSEST = 0, 1
 # ORBHIP_NEWPOINT_*: d_status of orbhip_create_new_map_points*, one code per way out of the loop body
 (NEWPOINT_CREATED, NEWPOINT_NO_MATCH, NEWPOINT_LOW_PARALLAX, NEWPOINT_W_ZERO, NEWPOINT_BEHIND_1, NEWPOINT_BEHIND_2,
  NEWPOINT_REPROJ_1, NEWPOINT_REPROJ_2, NEWPOINT_ZERO_DIST, NEWPOINT_SCALE) = range(10)
+# ORBHIP_UPDATE_* (the `what` mask) and ORBHIP_MAPPOINT_* (d_status) of orbhip_update_map_points*
+UPDATE_DESCRIPTOR, UPDATE_NORMAL_DEPTH = 1, 2
+(MAPPOINT_UPDATED, MAPPOINT_BAD, MAPPOINT_NO_OBSERVATION, MAPPOINT_NO_DESCRIPTOR, MAPPOINT_BAD_REF,
+ MAPPOINT_TOO_MANY) = range(6)
 REMAP_TABLE_SIZE = 4096
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
@@ -151,6 +155,10 @@ SYMBOLS = [
                                               _vp, _vp, _vp]),
     ("orbhip_count_close_points", _i, [_vp, _vp, _vp, _i, _f, _pi, _pi]),
     ("orbhip_count_close_points_device", _i, [_vp, _i, _vp, _vp, _vp, _i, _f, _vp]),
+    ("orbhip_update_map_points_device", _i, [_vp, C.POINTER(Camera), _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp,
+                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("orbhip_update_map_points", _i, [_vp, C.POINTER(Camera), _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp]),
     ("orbhip_matcher_set_stream", _i, [_vp, _vp]),
     ("orbhip_matcher_sync", _i, [_vp]),
     ("orbhip_compute_stereo_matches_device", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,

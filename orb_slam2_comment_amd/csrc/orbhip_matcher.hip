@@ -1961,6 +1961,24 @@ __global__ void k_distance_matrix(const uint8_t *__restrict__ a, int na, const u
 // distances in LDS).  Smallest median wins, first index on ties (:296-300).
 constexpr int kDistinctMax = 2048;
 
+// The k-th smallest (k from 0) of one row of N distances, wave-uniform: lane j holds d0 = d(i, j) (any value above 256
+// where j >= N), entries 64 and up are in srow.  Bisection on the value range [0, 256], counting with ballot / popcount.
+__device__ __forceinline__ int row_kth_distance(int d0, const unsigned short *srow, int N, int k, int lane)
+{
+    int lo = 0, hi = 256;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        int cnt = __popcll(__ballot(d0 <= mid));
+        if (N > 64) {
+            int c = 0;
+            for (int j = lane + 64; j < N; j += 64) c += srow[j] <= mid;
+            cnt += wave_reduce_add_i(c);
+        }
+        if (cnt >= k + 1) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
 __global__ __launch_bounds__(256) void k_distinctive(const uint8_t *__restrict__ desc, const int *__restrict__ offsets,
                                                      int npoints, int *__restrict__ best)
 {
@@ -1995,21 +2013,291 @@ __global__ __launch_bounds__(256) void k_distinctive(const uint8_t *__restrict__
             }
             __builtin_amdgcn_wave_barrier();
         }
-        int lo = 0, hi = 256;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            int cnt = __popcll(__ballot(d0 <= mid));
-            if (N > 64) {
-                int c = 0;
-                for (int j = lane + 64; j < N; j += 64) c += srow[wv][j] <= mid;
-                cnt += wave_reduce_add_i(c);
-            }
-            if (cnt >= k + 1) hi = mid; else lo = mid + 1;
-        }
+        const int lo = row_kth_distance(d0, srow[wv], N, k, lane);
         if (lo < bestMedian) { bestMedian = lo; bestIdx = i; }
         if (N > 64) __builtin_amdgcn_wave_barrier();
     }
     if (lane == 0) best[p] = bestIdx;
+}
+
+// ---- MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307) and MapPoint::UpdateNormalAndDepth (:330-371) from an
+// observation table over the key-frame bank: observation j of point p is key point obs_idx[o] of bank row obs_kf[o],
+// o = obs_start[p] + j.  k_update_points gives a group of 16 lanes to a point with at most 16 observations, four points to
+// a wavefront; longer lists go to a worklist that k_update_points_long walks with one wavefront per point.  The sum of
+// the normal is taken in table order by one lane, and of several equal medians the first in table order wins.
+constexpr int kUpdGroup = 16;         // lanes, and observations, of a point in k_update_points
+constexpr int kUpdStage = 512;        // descriptors of a long point kept in LDS; the rest are read through their bank rows
+constexpr int kUpdLongBlocks = 1024;  // grid of k_update_points_long, which loops over the worklist
+
+struct UpdArgs {
+    const float *Tcw;               // [rows][12]
+    const orbhip_keypoint *keys;    // [rows][cap]
+    const uint8_t *desc;            // [rows][cap][32]
+    const uint8_t *kf_bad;          // [rows] or null
+    const int *obs_start, *obs_kf, *obs_idx, *ref_obs;
+    const float *world;             // [pcap][3]
+    const uint8_t *flags;           // [pcap]
+    uint8_t *point_desc;            // [pcap][32]
+    float *normal, *max_dist, *min_dist;
+    int *best_obs;                  // [np] or null
+    uint8_t *status;                // [np]
+    int *work;                      // [0] = number of long points, [1 + i] = their indices
+    int cap, np, what;
+};
+
+// an LDS hand-off between the lanes of one wavefront
+__device__ __forceinline__ void wave_lds_handoff()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// d = mWorldPos - Owi in float; v = normali / cv::norm(normali): the Mat times the double 1.0 / norm, element by element
+__device__ __forceinline__ void upd_view_dir(const float *T, const float *X, float *d, float *v)
+{
+    float Ow[3];
+    camera_centre(T, Ow);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d[c] = __fsub_rn(X[c], Ow[c]);
+    const double inv = 1.0 / norm3d(d[0], d[1], d[2]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = (float)(inv * (double)d[c]);
+}
+// mfMaxDistance / mfMinDistance (:359-368) from PC = Pos - Ow of the reference key frame and the octave of its observation
+__device__ __forceinline__ void upd_depth_range(const float *pc, int level, const orbhip_camera &cam, float *mx, float *mn)
+{
+    const float dist = (float)norm3d(pc[0], pc[1], pc[2]);
+    const float sf = level < 0 ? cam.scale_factors[0] : (level >= cam.n_levels ? 0.f : cam.scale_factors[level]);
+    *mx = __fmul_rn(dist, sf);
+    *mn = __fdiv_rn(*mx, cam.scale_factors[cam.n_levels - 1]);
+}
+// mNormalVector = normal / n (:369): the Mat times the double 1.0 / n
+__device__ __forceinline__ void upd_store_normal(float *out, const float *sum, int n)
+{
+    const double inv = 1.0 / (double)n;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[c] = (float)(inv * (double)sum[c]);
+}
+
+__global__ __launch_bounds__(256) void k_update_points(UpdArgs A, orbhip_camera cam)
+{
+    __shared__ uint32_t sdesc[16][kUpdGroup][8];
+    __shared__ float sdir[16][kUpdGroup][3];
+    const int lane = threadIdx.x & 63, gl = lane & 15, g = threadIdx.x >> 4, gshift = lane & 48;
+    const int p = blockIdx.x * 16 + g;
+    const bool want_desc = (A.what & ORBHIP_UPDATE_DESCRIPTOR) != 0, want_nd = (A.what & ORBHIP_UPDATE_NORMAL_DEPTH) != 0;
+    int N = 0, o0 = 0;
+    if (p < A.np) {
+        o0 = A.obs_start[p];
+        N = A.obs_start[p + 1] - o0;
+        int leave = -1;
+        if (!(A.flags[p] & ORBHIP_POINT_PRESENT)) leave = ORBHIP_MAPPOINT_BAD;
+        else if (N <= 0) leave = ORBHIP_MAPPOINT_NO_OBSERVATION;
+        else if (N > kDistinctMax) leave = ORBHIP_MAPPOINT_TOO_MANY;
+        if (leave >= 0) {
+            if (gl == 0) {
+                A.status[p] = (uint8_t)leave;
+                if (want_desc && A.best_obs) A.best_obs[p] = -1;
+            }
+            N = 0;
+        } else if (N > kUpdGroup) {
+            if (gl == 0) A.work[1 + atomicAdd(A.work, 1)] = p;
+            N = 0;
+        }
+    }
+    // from here on every lane of the wavefront runs the same steps; a group without a point has N = 0 and stores nothing
+    if (__ballot(N > 0) == 0) return;
+    const bool mine = gl < N;
+    int kf = 0, idx = 0;
+    bool ok = false;
+    if (mine) {
+        kf = A.obs_kf[o0 + gl];
+        idx = A.obs_idx[o0 + gl];
+        ok = !(A.kf_bad && A.kf_bad[kf]);   // :265
+    }
+    int status = ORBHIP_MAPPOINT_UPDATED;
+    if (want_desc) {
+        uint32_t t0[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (mine) {
+            const uint32_t *tp = reinterpret_cast<const uint32_t *>(A.desc + ((size_t)kf * A.cap + idx) * 32);
+#pragma unroll
+            for (int w = 0; w < 8; ++w) t0[w] = tp[w];
+        }
+#pragma unroll
+        for (int w = 0; w < 8; ++w) sdesc[g][gl][w] = t0[w];
+        wave_lds_handoff();
+        const uint32_t kept = (uint32_t)(__ballot(ok) >> gshift) & 0xffffu;   // vDescriptors, as a mask over the list
+        const int k = (__popc(kept) - 1) >> 1;                                // (int)(0.5*(N-1))
+        const int nmax = max(max(__builtin_amdgcn_readlane(N, 0), __builtin_amdgcn_readlane(N, 16)),
+                             max(__builtin_amdgcn_readlane(N, 32), __builtin_amdgcn_readlane(N, 48)));
+        int bestMedian = INT_MAX, bestIdx = -1;
+        for (int i = 0; i < nmax; ++i) {
+            uint32_t di[8];
+#pragma unroll
+            for (int w = 0; w < 8; ++w) di[w] = sdesc[g][i][w];
+            const int d = ok ? hamming256(di, t0) : 0x7fff;
+            // the k-th smallest of the group's row: nine halvings of [0, 256], counted in the group's slice of the ballot
+            int lo = 0, hi = 256;
+#pragma unroll
+            for (int s = 0; s < 9; ++s) {
+                const int mid = (lo + hi) >> 1;
+                const int cnt = __popc((uint32_t)(__ballot(d <= mid) >> gshift) & 0xffffu);
+                if (lo < hi) {
+                    if (cnt >= k + 1) hi = mid; else lo = mid + 1;
+                }
+            }
+            if (((kept >> i) & 1u) && lo < bestMedian) { bestMedian = lo; bestIdx = i; }   // :296-300
+        }
+        if (N > 0) {
+            if (bestIdx >= 0) {
+                if (gl < 8) reinterpret_cast<uint32_t *>(A.point_desc + (size_t)p * 32)[gl] = sdesc[g][bestIdx][gl];
+            } else status = ORBHIP_MAPPOINT_NO_DESCRIPTOR;   // :269
+            if (gl == 0 && A.best_obs) A.best_obs[p] = bestIdx;
+        }
+    }
+    if (want_nd) {
+        float d[3] = {0.f, 0.f, 0.f}, v[3] = {0.f, 0.f, 0.f};
+        if (mine) upd_view_dir(A.Tcw + (size_t)kf * 12, A.world + (size_t)p * 3, d, v);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) sdir[g][gl][c] = v[c];
+        wave_lds_handoff();
+        if (N > 0) {
+            const int r = A.ref_obs[p];
+            if (r < 0 || r >= N) status = ORBHIP_MAPPOINT_BAD_REF;
+            else {
+                if (gl == r) {   // this lane's d is Pos - pRefKF->GetCameraCenter()
+                    float mx, mn;
+                    upd_depth_range(d, A.keys[(size_t)kf * A.cap + idx].octave, cam, &mx, &mn);
+                    A.max_dist[p] = mx;
+                    A.min_dist[p] = mn;
+                }
+                if (gl == 0) {
+                    float sum[3] = {0.f, 0.f, 0.f};
+                    for (int j = 0; j < N; ++j)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) sum[c] = __fadd_rn(sum[c], sdir[g][j][c]);
+                    upd_store_normal(A.normal + (size_t)p * 3, sum, N);
+                }
+            }
+        }
+    }
+    if (N > 0 && gl == 0) A.status[p] = (uint8_t)status;
+}
+
+// descriptor j of the kept observations of a long point: from LDS, or past kUpdStage through its bank row
+__device__ __forceinline__ void upd_load_desc(const uint32_t (*sdesc)[8], const int *srow_of, const uint8_t *desc, int j,
+                                              uint32_t *out)
+{
+    if (j < kUpdStage) {
+#pragma unroll
+        for (int w = 0; w < 8; ++w) out[w] = sdesc[j][w];
+    } else {
+        const uint32_t *tp = reinterpret_cast<const uint32_t *>(desc) + (size_t)srow_of[j] * 8;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) out[w] = tp[w];
+    }
+}
+
+__global__ __launch_bounds__(64) void k_update_points_long(UpdArgs A, orbhip_camera cam)
+{
+    __shared__ uint32_t sdesc[kUpdStage][8];
+    __shared__ int srow_of[kDistinctMax];           // bank row * cap + key point of the kept observations
+    __shared__ unsigned short spos[kDistinctMax];   // their positions in the point's list
+    __shared__ unsigned short srow[kDistinctMax];   // distances of one row past lane 63
+    __shared__ float sdir[64][3];
+    const int lane = threadIdx.x;
+    const bool want_desc = (A.what & ORBHIP_UPDATE_DESCRIPTOR) != 0, want_nd = (A.what & ORBHIP_UPDATE_NORMAL_DEPTH) != 0;
+    const int count = A.work[0];
+    for (int wi = blockIdx.x; wi < count; wi += gridDim.x) {
+        const int p = A.work[1 + wi];
+        const int o0 = A.obs_start[p], N = A.obs_start[p + 1] - o0;   // 16 < N <= kDistinctMax
+        int status = ORBHIP_MAPPOINT_UPDATED;
+        if (want_desc) {
+            int M = 0;   // vDescriptors.size()
+            for (int base = 0; base < N; base += 64) {
+                const int j = base + lane;
+                bool ok = false;
+                int row = 0;
+                if (j < N) {
+                    const int kf = A.obs_kf[o0 + j];
+                    ok = !(A.kf_bad && A.kf_bad[kf]);
+                    row = kf * A.cap + A.obs_idx[o0 + j];
+                }
+                const unsigned long long mk = __ballot(ok);
+                if (ok) {
+                    const int pos = M + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0));
+                    srow_of[pos] = row;
+                    spos[pos] = (unsigned short)j;
+                }
+                M += __popcll(mk);
+            }
+            wave_lds_handoff();
+            const int staged = min(M, kUpdStage) * 8;
+            for (int e = lane; e < staged; e += 64)
+                (&sdesc[0][0])[e] = reinterpret_cast<const uint32_t *>(A.desc)[(size_t)srow_of[e >> 3] * 8 + (e & 7)];
+            wave_lds_handoff();
+            int bestIdx = -1;
+            if (M > 0) {
+                const int k = (M - 1) >> 1;
+                uint32_t t0[8];
+                upd_load_desc(sdesc, srow_of, A.desc, lane < M ? lane : 0, t0);
+                int bestMedian = INT_MAX;
+                for (int i = 0; i < M; ++i) {
+                    uint32_t di[8];
+                    upd_load_desc(sdesc, srow_of, A.desc, i, di);
+                    const int d0 = lane < M ? hamming256(di, t0) : 0x7fff;
+                    if (M > 64) {
+                        for (int j = lane + 64; j < M; j += 64) {
+                            uint32_t t[8];
+                            upd_load_desc(sdesc, srow_of, A.desc, j, t);
+                            srow[j] = (unsigned short)hamming256(di, t);
+                        }
+                        wave_lds_handoff();
+                    }
+                    const int lo = row_kth_distance(d0, srow, M, k, lane);
+                    if (lo < bestMedian) { bestMedian = lo; bestIdx = i; }
+                    if (M > 64) wave_lds_handoff();
+                }
+                if (lane < 8)
+                    reinterpret_cast<uint32_t *>(A.point_desc + (size_t)p * 32)[lane] =
+                        bestIdx < kUpdStage ? sdesc[bestIdx][lane]
+                                            : reinterpret_cast<const uint32_t *>(A.desc)[(size_t)srow_of[bestIdx] * 8 + lane];
+            } else status = ORBHIP_MAPPOINT_NO_DESCRIPTOR;
+            if (lane == 0 && A.best_obs) A.best_obs[p] = bestIdx >= 0 ? (int)spos[bestIdx] : -1;
+        }
+        if (want_nd) {
+            const int r = A.ref_obs[p];
+            if (r < 0 || r >= N) status = ORBHIP_MAPPOINT_BAD_REF;
+            else {
+                float sum[3] = {0.f, 0.f, 0.f};
+                for (int base = 0; base < N; base += 64) {
+                    const int j = base + lane;
+                    float d[3], v[3] = {0.f, 0.f, 0.f};
+                    if (j < N) {
+                        const int kf = A.obs_kf[o0 + j];
+                        upd_view_dir(A.Tcw + (size_t)kf * 12, A.world + (size_t)p * 3, d, v);
+                        if (j == r) {
+                            float mx, mn;
+                            upd_depth_range(d, A.keys[(size_t)kf * A.cap + A.obs_idx[o0 + j]].octave, cam, &mx, &mn);
+                            A.max_dist[p] = mx;
+                            A.min_dist[p] = mn;
+                        }
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) sdir[lane][c] = v[c];
+                    wave_lds_handoff();
+                    const int m = min(64, N - base);
+                    for (int jj = 0; jj < m; ++jj)   // every lane the same sum, in table order
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) sum[c] = __fadd_rn(sum[c], sdir[jj][c]);
+                    wave_lds_handoff();
+                }
+                if (lane == 0) upd_store_normal(A.normal + (size_t)p * 3, sum, N);
+            }
+        }
+        if (lane == 0) A.status[p] = (uint8_t)status;
+        wave_lds_handoff();   // the next point reuses the LDS arrays
+    }
 }
 
 // ---- Frame constructor glue on the device ------------------------------------------------
@@ -3151,8 +3439,8 @@ struct orbhip_matcher {
     hipStream_t stream = nullptr;       // stream every launch goes to
     hipStream_t own_stream = nullptr;   // created with the handle
     // grow-only device scratch
-    void *buf[16] = {};
-    size_t cap[16] = {};
+    void *buf[17] = {};
+    size_t cap[17] = {};
     bool lds_attr_set = false, bow_attr_set = false;
     // pinned host staging: all inputs of a call travel in one DMA, all outputs in one
     uint8_t *h_stage = nullptr; size_t h_stage_bytes = 0;
@@ -3207,7 +3495,7 @@ static int scratch(orbhip_matcher *m, int slot, size_t bytes, void **out)
     return ORBHIP_OK;
 }
 
-enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_NSLOTS };
+enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_NSLOTS };
 
 static int stage_begin(orbhip_matcher *m, size_t total, Stage *st)
 {
@@ -4373,6 +4661,146 @@ int orbhip_count_close_points(orbhip_matcher *m, const float *depth, const uint8
     if ((rc = read_back(m, p, 2 * sizeof(int), &h))) return rc;
     *tracked = reinterpret_cast<const int *>(h)[0];
     *non_tracked = reinterpret_cast<const int *>(h)[1];
+    return ORBHIP_OK;
+}
+
+static bool update_args_ok(const orbhip_camera *cam, int what)
+{
+    if (what == 0 || (what & ~(ORBHIP_UPDATE_DESCRIPTOR | ORBHIP_UPDATE_NORMAL_DEPTH))) return false;
+    if ((what & ORBHIP_UPDATE_NORMAL_DEPTH) && (!cam || cam->n_levels < 1 || cam->n_levels > ORBHIP_MAX_LEVELS)) return false;
+    return true;
+}
+
+int orbhip_update_map_points_device(orbhip_matcher *m, const orbhip_camera *cam, int what, const void *d_Tcw, const void *d_kps,
+                                    const void *d_desc, const void *d_n, int cap, const void *d_kf_bad, int np, int pcap,
+                                    const void *d_obs_start, const void *d_obs_kf, const void *d_obs_idx, const void *d_ref_obs,
+                                    const void *d_world, const void *d_flags, void *d_point_desc, void *d_normal,
+                                    void *d_max_dist, void *d_min_dist, void *d_best_obs, void *d_status)
+{
+    (void)d_n;
+    if (!m || !update_args_ok(cam, what) || np < 0 || np > pcap || cap < 1) return ORBHIP_E_ARG;
+    if (cap > kGridMax) { set_error("update_map_points: capacity %d exceeds %d", cap, kGridMax); return ORBHIP_E_CAPACITY; }
+    if (np == 0) return ORBHIP_OK;
+    if (!d_obs_start || !d_obs_kf || !d_obs_idx || !d_flags || !d_status) return ORBHIP_E_ARG;
+    if ((what & ORBHIP_UPDATE_DESCRIPTOR) && (!d_desc || !d_point_desc)) return ORBHIP_E_ARG;
+    if ((what & ORBHIP_UPDATE_NORMAL_DEPTH) &&
+        (!d_Tcw || !d_kps || !d_ref_obs || !d_world || !d_normal || !d_max_dist || !d_min_dist))
+        return ORBHIP_E_ARG;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    void *work;
+    if (int rc = scratch(m, S_UPD, ((size_t)np + 1) * sizeof(int), &work)) return rc;
+    UpdArgs A;
+    A.Tcw = (const float *)d_Tcw; A.keys = (const orbhip_keypoint *)d_kps; A.desc = (const uint8_t *)d_desc;
+    A.kf_bad = (const uint8_t *)d_kf_bad;
+    A.obs_start = (const int *)d_obs_start; A.obs_kf = (const int *)d_obs_kf; A.obs_idx = (const int *)d_obs_idx;
+    A.ref_obs = (const int *)d_ref_obs;
+    A.world = (const float *)d_world; A.flags = (const uint8_t *)d_flags;
+    A.point_desc = (uint8_t *)d_point_desc; A.normal = (float *)d_normal; A.max_dist = (float *)d_max_dist;
+    A.min_dist = (float *)d_min_dist; A.best_obs = (int *)d_best_obs; A.status = (uint8_t *)d_status;
+    A.work = (int *)work; A.cap = cap; A.np = np; A.what = what;
+    orbhip_camera c;
+    memset(&c, 0, sizeof(c));
+    if (cam) c = *cam;
+    ORBHIP_HIP_CHECK(hipMemsetAsync(work, 0, sizeof(int), m->stream));
+    hipLaunchKernelGGL(k_update_points, dim3((np + 15) / 16), dim3(256), 0, m->stream, A, c);
+    hipLaunchKernelGGL(k_update_points_long, dim3(std::min(np, kUpdLongBlocks)), dim3(64), 0, m->stream, A, c);
+    ORBHIP_HIP_CHECK(hipGetLastError());
+    return ORBHIP_OK;
+}
+
+int orbhip_update_map_points(orbhip_matcher *m, const orbhip_camera *cam, int what, int K, const orbhip_frame_view *const *kfs,
+                             const float *Tcw, const uint8_t *kf_bad, int np, const int32_t *obs_start, const int32_t *obs_kf,
+                             const int32_t *obs_idx, const int32_t *ref_obs, const float *world, const uint8_t *flags,
+                             uint8_t *point_desc, float *normal, float *max_dist, float *min_dist, int32_t *best_obs,
+                             uint8_t *status)
+{
+    if (!m || !update_args_ok(cam, what) || K < 0 || np < 0) return ORBHIP_E_ARG;
+    if (np == 0) return ORBHIP_OK;
+    const bool wd = (what & ORBHIP_UPDATE_DESCRIPTOR) != 0, wn = (what & ORBHIP_UPDATE_NORMAL_DEPTH) != 0;
+    if (!obs_start || !flags || !status || (K > 0 && !kfs) || (wd && !point_desc) ||
+        (wn && (!ref_obs || !world || !normal || !max_dist || !min_dist || (K > 0 && !Tcw))))
+        return ORBHIP_E_ARG;
+    int cap = 1;
+    for (int k = 0; k < K; ++k) {
+        if (!kfs[k] || kfs[k]->n < 0 || (kfs[k]->n > 0 && ((wn && !kfs[k]->keys) || (wd && !kfs[k]->desc)))) return ORBHIP_E_ARG;
+        cap = std::max(cap, kfs[k]->n);
+    }
+    if (cap > kGridMax) { set_error("update_map_points: a key frame has %d key points (limit %d)", cap, kGridMax); return ORBHIP_E_CAPACITY; }
+    if (obs_start[0] < 0) return ORBHIP_E_ARG;
+    for (int p = 0; p < np; ++p)
+        if (obs_start[p + 1] < obs_start[p]) {
+            set_error("update_map_points: obs_start must be non-decreasing (point %d)", p);
+            return ORBHIP_E_ARG;
+        }
+    const size_t o_first = (size_t)obs_start[0], nobs = (size_t)obs_start[np];
+    if (nobs > o_first && (!obs_kf || !obs_idx)) return ORBHIP_E_ARG;
+    for (size_t o = o_first; o < nobs; ++o)
+        if (obs_kf[o] < 0 || obs_kf[o] >= K || obs_idx[o] < 0 || obs_idx[o] >= kfs[obs_kf[o]]->n) {
+            set_error("update_map_points: observation %zu (row %d, key point %d) is outside the bank", o, obs_kf[o], obs_idx[o]);
+            return ORBHIP_E_ARG;
+        }
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    // inputs in one copy; the in/out arrays and the two reports are staged last and next to each other, so that
+    // everything the call returns comes back in one copy as well
+    const size_t kc = (size_t)std::max(K, 1) * cap, sn = (size_t)np, no = std::max(nobs, (size_t)1);
+    const size_t ob = al256(sn * 32) + 3 * al256(sn * 12) + al256(sn * 4) + al256(sn);
+    Stage st;
+    int rc;
+    if ((rc = stage_begin(m, al256((size_t)std::max(K, 1) * 48) + al256((size_t)std::max(K, 1)) + al256(kc * sizeof(orbhip_keypoint)) +
+                                 al256(kc * 32) + al256((sn + 1) * 4) + 2 * al256(no * 4) + al256(sn * 4) + al256(sn * 12) +
+                                 al256(sn) + ob, &st))) return rc;
+    const float *d_T = nullptr, *d_world = nullptr;
+    const uint8_t *d_bad = nullptr, *d_desc = nullptr;
+    const orbhip_keypoint *d_keys = nullptr;
+    const int *d_ref = nullptr;
+    if (wn) {
+        d_T = st.put(Tcw, (size_t)K * 12);
+        orbhip_keypoint *h_keys = st.take(kc, &d_keys);
+        if (h_keys)
+            for (int k = 0; k < K; ++k)
+                if (kfs[k]->n) memcpy(h_keys + (size_t)k * cap, kfs[k]->keys, (size_t)kfs[k]->n * sizeof(orbhip_keypoint));
+        d_ref = st.put(ref_obs, sn);
+        d_world = st.put(world, sn * 3);
+    }
+    if (wd) {
+        uint8_t *h_desc = st.take(kc * 32, &d_desc);
+        if (h_desc)
+            for (int k = 0; k < K; ++k)
+                if (kfs[k]->n) memcpy(h_desc + (size_t)k * cap * 32, kfs[k]->desc, (size_t)kfs[k]->n * 32);
+    }
+    if (kf_bad) d_bad = st.put(kf_bad, (size_t)K);
+    const int *d_start = st.put(obs_start, sn + 1);
+    const int *d_okf = st.put(obs_kf, nobs), *d_oidx = st.put(obs_idx, nobs);
+    const uint8_t *d_flags = st.put(flags, sn);
+    // outputs: point_desc | normal | max_dist | min_dist | best_obs | status
+    const uint8_t *d_pd = nullptr;
+    const float *d_nrm = nullptr, *d_mx = nullptr, *d_mn = nullptr;
+    const int *d_best;
+    const uint8_t *d_status;
+    const size_t out_off = st.off;
+    if (wd) d_pd = st.put(point_desc, sn * 32);
+    if (wn) { d_nrm = st.put(normal, sn * 3); d_mx = st.put(max_dist, sn); d_mn = st.put(min_dist, sn); }
+    int *h_best = st.take(sn, &d_best);
+    uint8_t *h_status = st.take(sn, &d_status);
+    if ((rc = st.status())) return rc;
+    for (size_t i = 0; i < sn; ++i) { h_best[i] = -1; h_status[i] = 0; }
+    const size_t out_bytes = st.off - out_off;
+    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = orbhip_update_map_points_device(m, cam, what, d_T, d_keys, d_desc, nullptr, cap, d_bad, np, np, d_start, d_okf, d_oidx,
+                                              d_ref, d_world, d_flags, const_cast<uint8_t *>(d_pd), const_cast<float *>(d_nrm),
+                                              const_cast<float *>(d_mx), const_cast<float *>(d_mn), const_cast<int *>(d_best),
+                                              const_cast<uint8_t *>(d_status)))) return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
+    const uint8_t *base = st.d + out_off;
+    if (wd) memcpy(point_desc, h + (d_pd - base), sn * 32);
+    if (wn) {
+        memcpy(normal, h + ((const uint8_t *)d_nrm - base), sn * 12);
+        memcpy(max_dist, h + ((const uint8_t *)d_mx - base), sn * 4);
+        memcpy(min_dist, h + ((const uint8_t *)d_mn - base), sn * 4);
+    }
+    if (best_obs && wd) memcpy(best_obs, h + ((const uint8_t *)d_best - base), sn * 4);
+    memcpy(status, h + (d_status - base), sn);
     return ORBHIP_OK;
 }
 

@@ -339,6 +339,55 @@ class ORBmatcher:
                                                          float(np.float32(th_depth)), d_counts),
               "orbhip_count_close_points_device")
 
+    # -- refreshing map points (src/MapPoint.cc:242-307, :330-371) ------------------------------------------------------
+    def UpdateMapPoints(self, cam, what, KFs, Tcw, kf_bad, obs_start, obs_kf, obs_idx, ref_obs, world, flags, point_desc,
+                        normal, max_dist, min_dist):
+        """MapPoint::ComputeDistinctiveDescriptors (what & capi.UPDATE_DESCRIPTOR) and MapPoint::UpdateNormalAndDepth
+        (what & capi.UPDATE_NORMAL_DEPTH) for the np = len(obs_start) - 1 map points of an observation table in CSR form:
+        observation j of point p is key point obs_idx[o] of KFs[obs_kf[o]], o = obs_start[p] + j, and ref_obs[p] is the
+        position of mpRefKF's observation in the point's list.  KFs: K FrameViews, Tcw [K] poses (4x4 or 3x4), kf_bad [K]
+        (None: no key frame is bad); flags [np]: POINT_PRESENT = !mbBad; world [np, 3].  One staged copy, one device call,
+        one read-back.  Returns (point_desc, normal, max_dist, min_dist, best_obs, status): updated copies of the four
+        arrays (an entry the reference would not write keeps the value passed in), the position of the chosen descriptor
+        in each list (-1: none) and one capi.MAPPOINT_* code per point."""
+        K = len(KFs)
+        start = np.ascontiguousarray(obs_start, np.int32)
+        n = len(start) - 1
+        if n < 0:
+            raise ValueError("obs_start needs np + 1 entries")
+        okf, oidx = np.ascontiguousarray(obs_kf, np.int32), np.ascontiguousarray(obs_idx, np.int32)
+        if len(okf) != len(oidx) or (n > 0 and len(okf) < start[-1]):
+            raise ValueError("obs_kf and obs_idx must hold obs_start[-1] entries")
+        Tc = np.ascontiguousarray(np.asarray(Tcw, np.float32).reshape(K, -1, 4)[:, :3, :]).reshape(K, 12)
+        bad = None if kf_bad is None else np.ascontiguousarray(kf_bad, np.uint8)
+        ref = np.ascontiguousarray(ref_obs, np.int32)
+        w = np.ascontiguousarray(world, np.float32).reshape(-1, 3)
+        fg = np.ascontiguousarray(flags, np.uint8)
+        pd = np.array(point_desc, np.uint8, order="C").reshape(-1, 32)
+        nn = np.array(normal, np.float32, order="C").reshape(-1, 3)
+        mx, mn = np.array(max_dist, np.float32, order="C"), np.array(min_dist, np.float32, order="C")
+        if (bad is not None and len(bad) != K) or any(len(a) < n for a in (ref, w, fg, pd, nn, mx, mn)):
+            raise ValueError("every per-point array needs one entry per map point, kf_bad one per key frame")
+        best, status = np.full(max(n, 1), -1, np.int32), np.zeros(max(n, 1), np.uint8)
+        views = [kf.c_view() for kf in KFs]
+        arr = (C.POINTER(capi.FrameView) * max(K, 1))(*[C.pointer(v) for v in views])
+        check(self._lib.orbhip_update_map_points(self._h, C.byref(cam), int(what), K, arr, ptr(Tc), ptr(bad), n, ptr(start),
+                                                 ptr(okf), ptr(oidx), ptr(ref), ptr(w), ptr(fg), ptr(pd), ptr(nn), ptr(mx),
+                                                 ptr(mn), ptr(best), ptr(status)), "orbhip_update_map_points")
+        return pd, nn, mx, mn, best[:n].copy(), status[:n].copy()
+
+    def UpdateMapPointsDevice(self, cam, what, d_Tcw, d_kps, d_desc, d_n, cap, np_, pcap, d_obs_start, d_obs_kf, d_obs_idx,
+                              d_ref_obs, d_world, d_flags, d_point_desc, d_normal, d_max_dist, d_min_dist, d_status,
+                              d_best_obs=0, d_kf_bad=0):
+        """Device-resident form (device pointers as ints; see orbhip_update_map_points_device in include/orbhip.h): the
+        table indexes the rows of the extractor-layout bank, and the four arrays are the ones FuseDevice,
+        FrustumQueriesDevice and KeyFrameQueries read.  Asynchronous on the matcher's stream."""
+        check(self._lib.orbhip_update_map_points_device(self._h, C.byref(cam), int(what), d_Tcw, d_kps, d_desc, d_n, int(cap),
+                                                        d_kf_bad, int(np_), int(pcap), d_obs_start, d_obs_kf, d_obs_idx,
+                                                        d_ref_obs, d_world, d_flags, d_point_desc, d_normal, d_max_dist,
+                                                        d_min_dist, d_best_obs, d_status),
+              "orbhip_update_map_points_device")
+
     # -- device-resident, batched SearchByProjection ---------------------------
     def set_stream(self, stream):
         check(self._lib.orbhip_matcher_set_stream(self._h, stream), "orbhip_matcher_set_stream")
