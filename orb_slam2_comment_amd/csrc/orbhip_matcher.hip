@@ -3,7 +3,7 @@
 // DescriptorDistance (src/ORBmatcher.cc) and Frame::ComputeStereoMatches
 // (src/Frame.cc:466-640).
 //
-// Structure: a fully parallel "window search" kernel (one wavefront per query:
+// Structure: a fully parallel "window search" kernel (16 or 64 lanes per query:
 // Frame::GetFeaturesInArea membership test + 256-bit XOR/popcount Hamming
 // distance, candidates compacted with wave ballots and sorted by
 // (distance, reference visiting order)), followed by a one-workgroup-per-pair
@@ -85,6 +85,31 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
 #undef ORBHIP_MIN64_STEP
     return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), 63) << 32) |
            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
+}
+
+// 64-bit minimum over LPQ consecutive lanes (8, 16 = one DPP row, 64 = the wavefront), in all of them: quad_perm [1,0,3,2],
+// quad_perm [2,3,0,1], row_half_mirror, and row_mirror for the row
+template <int LPQ> __device__ __forceinline__ unsigned long long group_min_u64(unsigned long long v)
+{
+    static_assert(LPQ == 8 || LPQ == 16 || LPQ == 64, "group sizes of k_fuse_batch and k_window_search");
+    if constexpr (LPQ == 64) {
+        return wave_min_u64(v);
+    } else {
+#define ORBHIP_GMIN_STEP(ctrl)                                                                                \
+    {                                                                                                         \
+        const uint32_t lo_ = (uint32_t)v, hi_ = (uint32_t)(v >> 32);                                          \
+        const uint32_t ol_ = (uint32_t)__builtin_amdgcn_update_dpp((int)lo_, (int)lo_, ctrl, 0xf, 0xf, false); \
+        const uint32_t oh_ = (uint32_t)__builtin_amdgcn_update_dpp((int)hi_, (int)hi_, ctrl, 0xf, 0xf, false); \
+        const unsigned long long o_ = ((unsigned long long)oh_ << 32) | ol_;                                  \
+        v = o_ < v ? o_ : v;                                                                                  \
+    }
+        ORBHIP_GMIN_STEP(0xB1)
+        ORBHIP_GMIN_STEP(0x4E)
+        ORBHIP_GMIN_STEP(0x141)
+        if constexpr (LPQ == 16) ORBHIP_GMIN_STEP(0x140)
+#undef ORBHIP_GMIN_STEP
+        return v;
+    }
 }
 
 // The smallest keys of a list whose entries are spread over the lanes, in ascending order, EXACTLY: every lane hands in
@@ -270,11 +295,44 @@ __device__ __forceinline__ void grid_build_body(DevFrame F, int *__restrict__ ce
     rec += rbase; rdesc += rbase * 2; rur += rbase;
     for (int c = tid; c < kGridCells; c += 256) s_cnt[c] = 0;
     __syncthreads();
-    for (int j = tid; j < F.n; j += 256) {
-        const orbhip_keypoint kp = F.keys[j];
-        const int px = (int)roundf(__fmul_rn(__fsub_rn(kp.x, F.min_x), F.inv_w));
-        const int py = (int)roundf(__fmul_rn(__fsub_rn(kp.y, F.min_y), F.inv_h));
-        if (!(px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS)) atomicAdd(&s_cnt[px * GRID_ROWS + py], 1);
+    // PosInGrid: the cell of a keypoint, -1 when it is rejected
+    const auto cell_of = [&](float x, float y) {
+        const int px = (int)roundf(__fmul_rn(__fsub_rn(x, F.min_x), F.inv_w));
+        const int py = (int)roundf(__fmul_rn(__fsub_rn(y, F.min_y), F.inv_h));
+        return (px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS) ? -1 : px * GRID_ROWS + py;
+    };
+    const auto emit = [&](int j, float x, float y, int octave, int cell) {
+        const int pos = atomicAdd(&s_cnt[cell], 1);
+        GridRec r; r.x = x; r.y = y; r.octave = octave; r.key = ((uint32_t)cell << 20) | (uint32_t)j;
+        rec[pos] = r;
+        const uint4 *d = reinterpret_cast<const uint4 *>(F.desc + (size_t)j * 32);
+        rdesc[2 * pos] = d[0]; rdesc[2 * pos + 1] = d[1];
+        rur[pos] = F.u_right ? F.u_right[j] : -1.0f;
+    };
+    // up to kGridKeep keypoints per thread stay in registers between the count pass and the scatter pass (one load of the
+    // 28-byte key, one PosInGrid); a larger frame reads its keys twice.  F.n is uniform: one scalar branch, no barrier inside
+    constexpr int kGridKeep = 4;
+    const bool keep = F.n <= 256 * kGridKeep;
+    float kx[kGridKeep], ky[kGridKeep];
+    int ko[kGridKeep], kc[kGridKeep];
+    if (keep) {
+#pragma unroll
+        for (int k = 0; k < kGridKeep; ++k) {
+            const int j = tid + 256 * k;
+            kx[k] = ky[k] = 0.0f; ko[k] = 0; kc[k] = -1;
+            if (j < F.n) {
+                const orbhip_keypoint kp = F.keys[j];
+                kx[k] = kp.x; ky[k] = kp.y; ko[k] = kp.octave; kc[k] = cell_of(kp.x, kp.y);
+                if (kc[k] >= 0) atomicAdd(&s_cnt[kc[k]], 1);
+            }
+        }
+    } else {
+        for (int j = tid; j < F.n; j += 256) {
+            const orbhip_keypoint kp = F.keys[j];
+            const int px = (int)roundf(__fmul_rn(__fsub_rn(kp.x, F.min_x), F.inv_w));
+            const int py = (int)roundf(__fmul_rn(__fsub_rn(kp.y, F.min_y), F.inv_h));
+            if (!(px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS)) atomicAdd(&s_cnt[px * GRID_ROWS + py], 1);
+        }
     }
     __syncthreads();
     // exclusive scan over the 3072 cells: 12 consecutive cells per thread
@@ -294,18 +352,24 @@ __device__ __forceinline__ void grid_build_body(DevFrame F, int *__restrict__ ce
     for (int k = 0; k < PER; ++k) { s_cnt[tid * PER + k] = base; cell_start[tid * PER + k] = base; base += local[k]; }
     if (tid == 255) cell_start[kGridCells] = base;
     __syncthreads();
-    for (int j = tid; j < F.n; j += 256) {
-        const orbhip_keypoint kp = F.keys[j];
-        const int px = (int)roundf(__fmul_rn(__fsub_rn(kp.x, F.min_x), F.inv_w));
-        const int py = (int)roundf(__fmul_rn(__fsub_rn(kp.y, F.min_y), F.inv_h));
-        if (!(px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS)) {
-            const int cell = px * GRID_ROWS + py;
-            const int pos = atomicAdd(&s_cnt[cell], 1);
-            GridRec r; r.x = kp.x; r.y = kp.y; r.octave = kp.octave; r.key = ((uint32_t)cell << 20) | (uint32_t)j;
-            rec[pos] = r;
-            const uint4 *d = reinterpret_cast<const uint4 *>(F.desc + (size_t)j * 32);
-            rdesc[2 * pos] = d[0]; rdesc[2 * pos + 1] = d[1];
-            rur[pos] = F.u_right ? F.u_right[j] : -1.0f;
+    if (keep) {
+#pragma unroll
+        for (int k = 0; k < kGridKeep; ++k)
+            if (kc[k] >= 0) emit(tid + 256 * k, kx[k], ky[k], ko[k], kc[k]);
+    } else {
+        for (int j = tid; j < F.n; j += 256) {
+            const orbhip_keypoint kp = F.keys[j];
+            const int px = (int)roundf(__fmul_rn(__fsub_rn(kp.x, F.min_x), F.inv_w));
+            const int py = (int)roundf(__fmul_rn(__fsub_rn(kp.y, F.min_y), F.inv_h));
+            if (!(px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS)) {
+                const int cell = px * GRID_ROWS + py;
+                const int pos = atomicAdd(&s_cnt[cell], 1);
+                GridRec r; r.x = kp.x; r.y = kp.y; r.octave = kp.octave; r.key = ((uint32_t)cell << 20) | (uint32_t)j;
+                rec[pos] = r;
+                const uint4 *d = reinterpret_cast<const uint4 *>(F.desc + (size_t)j * 32);
+                rdesc[2 * pos] = d[0]; rdesc[2 * pos + 1] = d[1];
+                rur[pos] = F.u_right ? F.u_right[j] : -1.0f;
+            }
         }
     }
 }
@@ -315,14 +379,237 @@ __global__ __launch_bounds__(256) void k_grid_build(DevFrame F, int *__restrict_
     grid_build_body(F, cell_start, rec, rdesc, rur, B, (int)blockIdx.x);
 }
 
-// One wavefront per query.  The cells of the query's window (Frame.cc:332-346) are dealt to the lanes; the records of
-// all those cells are then flattened over the lanes (wave prefix sum of the cell populations + an LDS scatter of the
-// record positions), so one pass tests 64 candidates: level window, |dx|,|dy| < r, stereo gate, Hamming distance.
-// Output: dist << 32 | (cell << 20 | index) keys; with <= 64 candidates the list is bitonic-sorted (= (distance,
-// reference visiting order)) into ccand[q*64 ..] and cnt[q] > 0, otherwise it stays unsorted in cand[q*stride ..] with
-// cnt[q] = -count.
+// L lanes per query (L = 16: one DPP row, four queries per wavefront; L = 64: the whole wavefront).  The columns of the
+// query's window (Frame.cc:332-346) are dealt to the lanes of its group; the records of those columns are then flattened
+// over the lanes (group prefix sum of the column populations + an LDS scatter of the record positions), so one pass tests
+// L candidates per query: level window, |dx|,|dy| < r, stereo gate, Hamming distance.  Every primitive is scoped to the
+// group -- scan, total, ballot prefix, minimum -- and the groups of a wavefront run in lockstep: loops go to the largest
+// trip count of the wavefront under per-group predicates, a group without a query or with an empty window idles.
+// Nothing is shared between wavefronts (stage / spos rows belong to one group), so there is no workgroup barrier.
+// Output: dist << 32 | (cell << 20 | index) keys; with <= 64 candidates the list is rank-sorted (= (distance, reference
+// visiting order)) into ccand[q*64 ..] and cnt[q] > 0 -- such a list lives in LDS only and never touches `cand` --
+// otherwise it stays unsorted in cand[q*stride ..] with cnt[q] = -count.
 constexpr int kCompact = 64;
+template <int L> __device__ __forceinline__ int group_incl_scan_add(int v)
+{
+    static_assert(L == 16, "a group is one DPP row");
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8
+    return v;
+}
+// total of a group whose inclusive scan is `incl` (of the values v), in every lane of the group
+template <int L> __device__ __forceinline__ int group_total(int incl, int v)
+{
+    static_assert(L == 16, "a group is one DPP row");
+    (void)incl;
+    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);    // quad_perm [1,0,3,2]
+    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);    // quad_perm [2,3,0,1]
+    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);   // row_half_mirror
+    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false);   // row_mirror
+    return v;
+}
+// the group's bits of a wavefront ballot, shifted down to bit 0
+template <int L> __device__ __forceinline__ unsigned long long group_bits(unsigned long long bal)
+{
+    return (bal >> (threadIdx.x & 63 & ~(L - 1))) & ((1ull << L) - 1ull);
+}
+// wave_sorted_head per group.  Called by the whole wavefront (the groups step together; one that has stopped, run dry or
+// has no long list hands in ~0 and ignores the minimum); every result is group-uniform.
+template <int L>
+__device__ __forceinline__ int group_sorted_head(unsigned long long a1, unsigned long long a2, bool more,
+                                                 unsigned long long (&head)[kHeadMax], bool *complete)
+{
+    int given = 0, hl = 0;
+    bool done = false;   // stopped or dry
+#pragma unroll
+    for (int k = 0; k < kHeadMax; ++k) {
+        head[k] = ~0ull;
+        if (!__any(!done)) continue;        // wave-uniform: every group has stopped or run dry
+        const unsigned long long c = done ? ~0ull : (given == 0 ? a1 : (given == 1 ? a2 : ~0ull));
+        const unsigned long long g = group_min_u64<L>(c);
+        const bool got = !done && g != ~0ull;
+        if (got) { head[k] = g; hl = k + 1; }
+        const bool mine = got && c == g;
+        if (mine) ++given;
+        const bool stop = group_bits<L>(__ballot(mine && given == 2 && more)) != 0;
+        done = done || !got || stop;
+    }
+    // a lane that still holds an unextracted tracked key, or more keys than it tracks, means the list goes on
+    const bool rest = (given == 0 && a1 != ~0ull) || (given <= 1 && a2 != ~0ull) || more;
+    *complete = group_bits<L>(__ballot(rest)) == 0;
+    return hl;
+}
+// Rank sort of a group's staged keys (total <= 64, distinct): a lane owns the M keys gl, gl + L, ... and counts for each
+// the keys below it -- key j comes to the group as a same-address LDS read -- then stores it at its rank.  Cheaper than a
+// bitonic network (12 instructions per stage, 10 .. 21 stages) at every length.  `total` is group-uniform; 0 = no list.
+template <int L, int M>
+__device__ __forceinline__ void group_rank_store(const unsigned long long *__restrict__ st, const int total, const int gl,
+                                                 unsigned long long *__restrict__ row)
+{
+    unsigned long long v[M];
+    int rank[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) { v[m] = gl + m * L < total ? st[gl + m * L] : ~0ull; rank[m] = 0; }
+#pragma unroll 4
+    for (int j = 0; j < total; ++j) {
+        const unsigned long long kj = st[j];
+#pragma unroll
+        for (int m = 0; m < M; ++m) rank[m] += kj < v[m] ? 1 : 0;
+    }
+#pragma unroll
+    for (int m = 0; m < M; ++m) if (gl + m * L < total) row[rank[m]] = v[m];
+}
+template <int L>
 __global__ __launch_bounds__(256) void k_window_search(DevFrame F, const int *__restrict__ cell_start,
+                                                       const GridRec *__restrict__ rec, const uint4 *__restrict__ rdesc,
+                                                       const float *__restrict__ rur,
+                                                       const orbhip_query *__restrict__ q,
+                                                       const uint8_t *__restrict__ qdesc,
+                                                       unsigned long long *__restrict__ cand,
+                                                       unsigned long long *__restrict__ ccand,
+                                                       int *__restrict__ cnt, int stride, int use_ur, Batch B,
+                                                       const uint8_t *__restrict__ taken, int max_dist)
+{
+    static_assert(L == 16, "a group is one DPP row; the wavefront form is the specialisation below");
+    constexpr int QW = 256 / L;                    // queries per workgroup
+    __shared__ unsigned long long stage[QW][kCompact];
+    __shared__ int spos[QW][L];
+    const int gl = threadIdx.x & (L - 1), qw = threadIdx.x / L;   // lane in the group, query in the workgroup
+    const int pair = blockIdx.y;
+    const bool has_ur = F.u_right != nullptr;
+    batch_frame(F, B, pair);
+    const size_t rbase = (size_t)pair * B.cap;
+    cell_start += (size_t)pair * (kGridCells + 1);
+    rec += rbase; rdesc += rbase * 2; rur += rbase;
+    q += (size_t)pair * B.qcap;
+    qdesc += (size_t)(B.qd0 + pair * B.qds) * B.qcap * 32;
+    cand += (size_t)pair * B.qcap * stride;
+    ccand += (size_t)pair * B.qcap * kCompact;
+    cnt += (size_t)pair * B.qcap;
+    if (taken) taken += (size_t)pair * B.cap;
+    const int nq = B.nq_dev ? min(B.nq_dev[pair], B.qcap) : B.qcap;
+    const int qi = blockIdx.x * QW + qw;
+    const bool inq = qi < nq;
+    orbhip_query Q = {};
+    if (inq) Q = q[qi];
+    const float x = Q.u, y = Q.v, r = Q.radius;
+    // Frame.cc:332-346
+    const int nMinCellX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, F.min_x), r), F.inv_w)));
+    const int nMaxCellX = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, F.min_x), r), F.inv_w)));
+    const int nMinCellY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, F.min_y), r), F.inv_h)));
+    const int nMaxCellY = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, F.min_y), r), F.inv_h)));
+    // a group without a valid query or with an empty window idles: no column, no record, no list
+    const bool live = inq && Q.valid &&
+                      !(nMinCellX >= GRID_COLS || nMaxCellX < 0 || nMinCellY >= GRID_ROWS || nMaxCellY < 0 ||
+                        nMaxCellX < nMinCellX || nMaxCellY < nMinCellY);
+    if (!__any(live)) {   // nothing to search in this wavefront
+        if (inq && gl == 0) cnt[qi] = 0;
+        return;
+    }
+    const bool bCheckLevels = (Q.min_level > 0) || (Q.max_level >= 0);
+    uint32_t qd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (live) {
+        const uint32_t *qp = reinterpret_cast<const uint32_t *>(qdesc + (size_t)qi * 32);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) qd[i] = qp[i];
+    }
+    unsigned long long *out = cand + (size_t)(inq ? qi : 0) * stride;
+    const int ncy = nMaxCellY - nMinCellY + 1;
+    int total = 0;
+    unsigned long long b1 = ~0ull, b2 = ~0ull;   // this lane's two smallest keys among candidates not taken on entry
+    int nb = 0;                                  // ... out of how many
+    // a column of the window is a contiguous run of cells (cell = ix * 48 + iy), so its records are one contiguous CSR
+    // range: lane = window column, range = [start[ix*48 + y0], start[ix*48 + y1 + 1]).  A window wider than L columns
+    // takes several trips; total, b1, b2 and nb carry over.
+    const int ncol = live ? nMaxCellX - nMinCellX + 1 : 0;
+    for (int c0 = 0; __any(c0 < ncol); c0 += L) {
+        const int c = c0 + gl;
+        int start = 0, ncand = 0;
+        if (c < ncol) {
+            const int cell0 = (nMinCellX + c) * GRID_ROWS + nMinCellY;
+            start = cell_start[cell0];
+            ncand = cell_start[cell0 + ncy] - start;
+        }
+        // exclusive prefix of the column populations over the group
+        const int incl = group_incl_scan_add<L>(ncand);
+        const int excl = incl - ncand, nrec = group_total<L>(incl, ncand);
+        for (int r0 = 0; __any(r0 < nrec); r0 += L) {
+            // scatter: flat record t of this chunk comes from CSR position spos[t - r0]
+            __builtin_amdgcn_wave_barrier();
+            for (int k = max(0, r0 - excl); k < ncand && excl + k < r0 + L; ++k) spos[qw][excl + k - r0] = start + k;
+            __builtin_amdgcn_wave_barrier();
+            bool ok = false;
+            unsigned long long key = 0;
+            if (r0 + gl < nrec) {
+                const int p = spos[qw][gl];
+                const GridRec R = rec[p];
+                const uint4 d0 = rdesc[2 * p], d1 = rdesc[2 * p + 1];
+                ok = true;
+                if (bCheckLevels) {
+                    if (R.octave < Q.min_level) ok = false;
+                    if (Q.max_level >= 0 && R.octave > Q.max_level) ok = false;
+                }
+                ok = ok && fabsf(__fsub_rn(R.x, x)) < r && fabsf(__fsub_rn(R.y, y)) < r;
+                if (ok && use_ur && has_ur) {
+                    const float ur = rur[p];
+                    if (ur > 0 && fabsf(__fsub_rn(Q.ur, ur)) > r) ok = false;
+                }
+                const int dist = __popc(qd[0] ^ d0.x) + __popc(qd[1] ^ d0.y) + __popc(qd[2] ^ d0.z) + __popc(qd[3] ^ d0.w) +
+                                 __popc(qd[4] ^ d1.x) + __popc(qd[5] ^ d1.y) + __popc(qd[6] ^ d1.z) + __popc(qd[7] ^ d1.w);
+                key = ((unsigned long long)dist << 32) | R.key;
+                // searches that take the best candidate alone (no second best, no ratio test) never look past the first
+                // free entry, and an entry beyond their acceptance threshold can only mean "no match": it need not be listed
+                ok = ok && dist <= max_dist;
+            }
+            const unsigned long long bal = group_bits<L>(__ballot(ok));
+            const int ntot = total + __popcll(bal);
+            // a list stays in LDS while it fits the compact row; the chunk that takes it past 64 entries moves the staged
+            // keys to `cand`, and from then on keys go there directly
+            if (ntot > kCompact && total <= kCompact)
+                for (int i = gl; i < total; i += L) out[i] = stage[qw][i];
+            if (ok) {
+                const int pos = total + __popcll(bal & ((1ull << gl) - 1ull));
+                if (ntot <= kCompact) stage[qw][pos] = key; else out[pos] = key;
+                if (!(taken && taken[key & 0xfffffu])) {
+                    if (key < b1) { b2 = b1; b1 = key; } else if (key < b2) b2 = key;
+                    ++nb;
+                }
+            }
+            total = ntot;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    // short lists: sorted into the compact row
+    const int ns = total <= kCompact ? total : 0;
+    unsigned long long *row = ccand + (size_t)(inq ? qi : 0) * kCompact;
+    if (__any(ns > L)) group_rank_store<L, kCompact / L>(stage[qw], ns, gl, row);
+    else group_rank_store<L, 1>(stage[qw], ns, gl, row);
+    // more than 64 candidates: the list stays unsorted in `cand`; the first (up to kHeadMax) keys of its sorted order
+    // among the candidates not taken on entry go to the head of the compact row -- {keys[8], count | complete << 8} --
+    // so the resolve walks a sorted head like it does for short lists and only scans the list when the head runs out
+    const bool lng = total > kCompact;
+    if (__any(lng)) {
+        unsigned long long head[kHeadMax];
+        bool complete;
+        const int hl = group_sorted_head<L>(lng ? b1 : ~0ull, lng ? b2 : ~0ull, lng && nb > 2, head, &complete);
+        if (lng && gl < kHeadMax) {
+            unsigned long long v = head[0];
+#pragma unroll
+            for (int k = 1; k < kHeadMax; ++k) if (gl == k) v = head[k];
+            row[gl] = v;
+        }
+        if (lng && gl == 0) row[kHeadMax] = (unsigned long long)hl | (complete ? 0x100ull : 0ull);
+    }
+    if (inq && gl == 0) cnt[qi] = lng ? -total : total;
+}
+
+// L = 64, one wavefront per query: the form SearchForInitialization and wide tracking searches run.  The cells of the
+// query's window are dealt to the lanes, one pass tests 64 candidates; every candidate goes to `cand`, the first 64 also to
+// the LDS stage that is rank-sorted through v_readlane when the list ends there.
+template <>
+__global__ __launch_bounds__(256) void k_window_search<64>(DevFrame F, const int *__restrict__ cell_start,
                                                        const GridRec *__restrict__ rec, const uint4 *__restrict__ rdesc,
                                                        const float *__restrict__ rur,
                                                        const orbhip_query *__restrict__ q,
@@ -1304,8 +1591,22 @@ __device__ __forceinline__ void resolve_par_carve(ResolveParState &S, unsigned c
 
 #ifdef ORBHIP_DEVTOOLS
 __device__ unsigned int g_resolve_stats[4];   // development builds: {launched workgroups, sum of rounds, max rounds, -}
+// Diagnostic build only (STAMPS = true is instantiated under -DORBHIP_DEVTOOLS alone): per-phase s_memtime sums of thread 0
+// of every workgroup (each phase ends at a barrier, so its stamps are the workgroup's) -- {state init + head loads, first
+// full step, event-driven rounds (mode 1: all rounds), unobserved pass, assign + histogram, cull, output, workgroups} --
+// read by tools/bench_track_th.py through orbhip_dev_resolve_stamps.  Shares, not lengths, are meaningful (the stamps fence).
+__device__ unsigned long long g_resolve_stamps[8];
 #endif
-template <bool GS>
+// time stamp of the stamped instantiation; the wait and the scheduling barriers fence it
+__device__ __forceinline__ unsigned long long resolve_stamp_now()
+{
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+template <bool GS, bool STAMPS = false>
 __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, const orbhip_query *__restrict__ q, int nq,
                                                       const unsigned long long *__restrict__ cand,
                                                       const unsigned long long *__restrict__ ccand,
@@ -1317,6 +1618,9 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
 {
     extern __shared__ unsigned char resolve_lds[];
     const int tid = threadIdx.x, T = blockDim.x;
+    unsigned long long tacc[7] = {0, 0, 0, 0, 0, 0, 0}, tprev = 0;
+#define RESOLVE_STAMP(i) do { if constexpr (STAMPS) { const unsigned long long t_ = resolve_stamp_now(); tacc[i] += t_ - tprev; tprev = t_; } } while (0)
+    if constexpr (STAMPS) tprev = resolve_stamp_now();
     {
         const int pair = blockIdx.x;
         batch_frame(F, B, pair);
@@ -1392,6 +1696,7 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
         }
     }
     __syncthreads();
+    RESOLVE_STAMP(0);   // state init + head loads
     // One deferred-acceptance step of query i against the holders as they are right now (any interleaving of proposals
     // is a valid execution, the atomics are the only synchronisation the matching needs).  Returns "the choice changed".
     auto held_by_smaller = [&](int idx, int i) -> bool {
@@ -1591,6 +1896,7 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
         wl_next = w_out; wl_count = &S.vars[c_out];
         for (int i0 = 0; i0 < nq; i0 += T) step_group(i0 + tid, i0 + tid < nq);
         __syncthreads();
+        RESOLVE_STAMP(1);   // first full step
         for (;; ++rounds) {
             { unsigned short *t_ = w_in; w_in = w_out; w_out = t_; }
             { const int t_ = c_in; c_in = c_out; c_out = c_clr; c_clr = t_; }
@@ -1602,6 +1908,7 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
             __syncthreads();
         }
         wl_next = nullptr;
+        RESOLVE_STAMP(2);   // event-driven rounds
         bool unobs = false;
         for (int i = tid; i < nq; i += T) unobs |= !S.q_obs[i];
         if (__syncthreads_or(unobs))
@@ -1640,6 +1947,7 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
         }
     }
     __syncthreads();
+    if (mode != 1) RESOLVE_STAMP(3); else RESOLVE_STAMP(2);   // unobserved pass; mode 1: its fixed-point rounds
     // ---- outputs: assign[slot] = last accepted query that picked it; rotation-histogram cull (mode 0) ----
     int *assign = S.owner[1];
     for (int c = tid; c < n; c += T) assign[c] = -1;
@@ -1663,6 +1971,7 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
     acc_local = wave_reduce_add_i(acc_local);
     if ((tid & 63) == 0 && acc_local) atomicAdd(&S.vars[1], acc_local);
     __syncthreads();
+    RESOLVE_STAMP(4);   // assign + histogram
     if (ori) {
         rank_bins_once(S.hist, S.vars + 8);
         const int ind1 = S.vars[8], ind2 = S.vars[9], ind3 = S.vars[10];
@@ -1677,8 +1986,20 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
         if ((tid & 63) == 0 && cull) atomicAdd(&S.vars[2], cull);
         __syncthreads();
     }
+    RESOLVE_STAMP(5);   // cull
     for (int c = tid; c < n; c += T) out[c] = assign[c];
     if (tid == 0) *out_n = S.vars[1] - S.vars[2];
+    RESOLVE_STAMP(6);   // output (thread 0's share of it: nothing waits for the stores)
+#ifdef ORBHIP_DEVTOOLS
+    if constexpr (STAMPS) {
+        if (tid == 0) {
+#pragma unroll
+            for (int i = 0; i < 7; ++i) atomicAdd(&g_resolve_stamps[i], tacc[i]);
+            atomicAdd(&g_resolve_stamps[7], 1ull);
+        }
+    }
+#endif
+#undef RESOLVE_STAMP
 }
 
 // ---- parallel resolve of SearchForInitialization (ORBmatcher.cc:405-520) -----------------------------------------
@@ -2793,26 +3114,6 @@ struct FuseBatchArgs {
     float min_x, min_y, inv_w, inv_h;
 };
 
-template <int LPQ> __device__ __forceinline__ unsigned long long group_min_u64(unsigned long long v);
-template <> __device__ __forceinline__ unsigned long long group_min_u64<64>(unsigned long long v) { return wave_min_u64(v); }
-// minimum over 8 consecutive lanes, in all of them: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror
-template <> __device__ __forceinline__ unsigned long long group_min_u64<8>(unsigned long long v)
-{
-#define ORBHIP_GMIN_STEP(ctrl)                                                                                \
-    {                                                                                                         \
-        const uint32_t lo_ = (uint32_t)v, hi_ = (uint32_t)(v >> 32);                                          \
-        const uint32_t ol_ = (uint32_t)__builtin_amdgcn_update_dpp((int)lo_, (int)lo_, ctrl, 0xf, 0xf, false); \
-        const uint32_t oh_ = (uint32_t)__builtin_amdgcn_update_dpp((int)hi_, (int)hi_, ctrl, 0xf, 0xf, false); \
-        const unsigned long long o_ = ((unsigned long long)oh_ << 32) | ol_;                                  \
-        v = o_ < v ? o_ : v;                                                                                  \
-    }
-    ORBHIP_GMIN_STEP(0xB1)
-    ORBHIP_GMIN_STEP(0x4E)
-    ORBHIP_GMIN_STEP(0x141)
-#undef ORBHIP_GMIN_STEP
-    return v;
-}
-
 template <int LPQ>
 __global__ __launch_bounds__(256) void k_fuse_batch(FuseBatchArgs A, orbhip_camera cam, float th, SigmaTab sig)
 {
@@ -3442,6 +3743,10 @@ struct orbhip_matcher {
     void *buf[17] = {};
     size_t cap[17] = {};
     bool lds_attr_set = false, bow_attr_set = false;
+#ifdef ORBHIP_DEVTOOLS
+    int window_lanes = 0;               // development build: lanes per query of k_window_search forced to 16 / 64 (0: the rule)
+    bool resolve_stamps = false;        // development build: k_resolve_par<false> runs its stamped instantiation
+#endif
     // pinned host staging: all inputs of a call travel in one DMA, all outputs in one
     uint8_t *h_stage = nullptr; size_t h_stage_bytes = 0;
     uint8_t *h_out = nullptr; size_t h_out_bytes = 0;
@@ -3542,6 +3847,10 @@ static int ensure_resolve_attr(orbhip_matcher *m)
                                              kResolveLdsBudget));
         ORBHIP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve_init), hipFuncAttributeMaxDynamicSharedMemorySize,
                                              kResolveLdsBudget));
+#ifdef ORBHIP_DEVTOOLS
+        ORBHIP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_resolve_par<false, true>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, kResolveLdsBudget));
+#endif
         m->lds_attr_set = true;
     }
     return ORBHIP_OK;
@@ -3560,6 +3869,15 @@ static int launch_resolve_par(orbhip_matcher *m, int pairs, int mode, const DevF
     if (B.cap <= kResolveMax && B.qcap <= kResolveMax) {
         // the list heads go to LDS when the budget allows
         const int lcn = resolve_par_bytes((size_t)B.cap, (size_t)B.qcap, kResolveHead) <= (size_t)kResolveLdsBudget ? kResolveHead : 0;
+#ifdef ORBHIP_DEVTOOLS
+        if (m->resolve_stamps) {
+            hipLaunchKernelGGL((k_resolve_par<false, true>), dim3(pairs), dim3(1024),
+                               resolve_par_bytes((size_t)B.cap, (size_t)B.qcap, (size_t)lcn), m->stream, mode, D, d_q, B.qcap, d_cand, d_ccand,
+                               d_cnt, stride, d_taken, nnratio, check_ori, d_out, d_out_n, B, th_accept, all_block,
+                               (unsigned char *)nullptr, (size_t)0, lcn);
+            return ORBHIP_OK;
+        }
+#endif
         hipLaunchKernelGGL(k_resolve_par<false>, dim3(pairs), dim3(1024), resolve_par_bytes((size_t)B.cap, (size_t)B.qcap, (size_t)lcn),
                            m->stream, mode, D, d_q, B.qcap, d_cand, d_ccand, d_cnt, stride, d_taken, nnratio, check_ori, d_out, d_out_n, B,
                            th_accept, all_block, (unsigned char *)nullptr, (size_t)0, lcn);
@@ -3579,9 +3897,25 @@ static int launch_resolve_par(orbhip_matcher *m, int pairs, int mode, const DevF
 // (SearchByProjection overloads), k_resolve_init for mode 2 (SearchForInitialization, query keypoints d_qkeys).
 // Modes 0 / 1 only: d_taken (slots blocked on entry, nullable), th_accept (acceptance distance of mode 0), all_block
 // (every accepted match blocks its slot, not only observed ones), use_ur (stereo gate).  Outputs d_out, d_out_n.
+//
+// Lanes per query of the window search: the SearchByProjection family (modes 0 / 1) has short lists
+// -- a 64-lane pass over one would be mostly idle -- and takes 16; SearchForInitialization's 100-px windows hold more than
+// 64 candidates as a rule and keep the whole wavefront.  The tracking step knows its radius factor on the host: the two
+// widths' times cross at th 19 (32 pairs) / 23 (85 pairs) -- 16 lanes win at 7 / 15 and lose at 30 / 60 / 100,
+// profiles/window_groups_track_th.json -- so a search wider than th 20 takes the wavefront form.  The other mode 0 / 1
+// entries get their radii in the query records and are not measured per radius: they take 16 lanes.
+constexpr float kWindowLanesTh = 20.0f;
+static int window_lanes(const orbhip_matcher *m, int mode, const ProjLaunch *proj = nullptr)
+{
+#ifdef ORBHIP_DEVTOOLS
+    if (m->window_lanes) return m->window_lanes;
+#endif
+    if (proj && proj->th > kWindowLanesTh) return 64;
+    return mode == 2 ? 64 : 16;
+}
 static int launch_search(orbhip_matcher *m, int mode, int pairs, const DevFrame &D, const Batch &B, const orbhip_query *d_q,
                          const uint8_t *d_qdesc, const orbhip_keypoint *d_qkeys, const uint8_t *d_taken, float nnratio,
-                         int check_ori, int th_accept, int all_block, int use_ur, int *d_out, int *d_out_n,
+                         int check_ori, int th_accept, int all_block, int use_ur, int *d_out, int *d_out_n, const int lanes,
                          const ProjLaunch *proj = nullptr)
 {
     void *p;
@@ -3613,8 +3947,13 @@ static int launch_search(orbhip_matcher *m, int mode, int pairs, const DevFrame 
         hipLaunchKernelGGL(k_grid_build, dim3(pairs), dim3(256), 0, m->stream, D, d_start, d_rec, d_rdesc, d_rur, B);
     }
     // searches that take the best candidate alone list nothing beyond their acceptance threshold
-    hipLaunchKernelGGL(k_window_search, dim3((B.qcap + 3) / 4, pairs), dim3(256), 0, m->stream, D, d_start, d_rec, d_rdesc, d_rur,
-                       d_q, d_qdesc, d_cand, d_ccand, d_cnt, stride, use_ur, B, d_taken, mode == 0 ? th_accept : 256);
+    const int max_dist = mode == 0 ? th_accept : 256;
+    if (lanes == 16)
+        hipLaunchKernelGGL(k_window_search<16>, dim3((B.qcap + 15) / 16, pairs), dim3(256), 0, m->stream, D, d_start, d_rec, d_rdesc,
+                           d_rur, d_q, d_qdesc, d_cand, d_ccand, d_cnt, stride, use_ur, B, d_taken, max_dist);
+    else
+        hipLaunchKernelGGL(k_window_search<64>, dim3((B.qcap + 3) / 4, pairs), dim3(256), 0, m->stream, D, d_start, d_rec, d_rdesc,
+                           d_rur, d_q, d_qdesc, d_cand, d_ccand, d_cnt, stride, use_ur, B, d_taken, max_dist);
     if (mode == 2) {   // match stealing depends on the running minimum distance per slot
         const int lcn = init_state_bytes((size_t)B.cap, (size_t)B.qcap, kResolveHead) <= (size_t)kResolveLdsBudget ? kResolveHead : 0;
         hipLaunchKernelGGL(k_resolve_init, dim3(pairs), dim3(1024), init_state_bytes((size_t)B.cap, (size_t)B.qcap, (size_t)lcn),
@@ -3687,7 +4026,7 @@ static int run_search(orbhip_matcher *m, int mode, const orbhip_frame_view *trai
     int *d_out = (int *)p;
     const Batch B = {nullptr, nullptr, train->n, nqv};
     if ((rc = launch_search(m, mode, 1, D, B, d_q, d_qdesc, d_qkeys, d_taken, nnratio, check_ori, th_accept, all_block, use_ur,
-                            d_out, d_out + nout)))
+                            d_out, d_out + nout, window_lanes(m, mode))))
         return rc;
     const uint8_t *h;
     if ((rc = read_back(m, d_out, (size_t)(nout + 1) * sizeof(int), &h))) return rc;
@@ -4362,7 +4701,7 @@ static int search_device(orbhip_matcher *m, int mode, int pairs, const void *d_k
     D.min_x = min_x; D.min_y = min_y; D.inv_w = grid_inv_w; D.inv_h = grid_inv_h;
     const Batch B = {(const int *)d_n, (const int *)d_nq, cap, qcap, t0, ts, qd0, qds};
     return launch_search(m, mode, pairs, D, B, (const orbhip_query *)d_q, (const uint8_t *)d_qdesc, nullptr, (const uint8_t *)d_taken,
-                         nnratio, check_ori, TH_HIGH, 0, 1, (int *)d_assign, (int *)d_nmatches, proj);
+                         nnratio, check_ori, TH_HIGH, 0, 1, (int *)d_assign, (int *)d_nmatches, window_lanes(m, mode, proj), proj);
 }
 
 int orbhip_search_by_projection_frame_device(orbhip_matcher *m, int pairs, const void *d_kps, const void *d_desc,
@@ -4437,7 +4776,7 @@ int orbhip_search_for_initialization_device(orbhip_matcher *m, int pairs, const 
     D.min_x = min_x; D.min_y = min_y; D.inv_w = grid_inv_w; D.inv_h = grid_inv_h;
     const Batch B = {(const int *)d_n, d_nq, cap, cap, f2_first, f2_step, f1_first, f1_step};
     if ((rc = launch_search(m, 2, pairs, D, B, d_q, (const uint8_t *)d_desc, keys, nullptr, nnratio, check_ori, TH_HIGH, 0, 0,
-                            (int *)d_matches12, (int *)d_nmatches)))
+                            (int *)d_matches12, (int *)d_nmatches, window_lanes(m, 2))))
         return rc;
     hipLaunchKernelGGL(k_init_update_prev, dim3((cap + 255) / 256, pairs), dim3(256), 0, m->stream, keys, cap, f2_first, f2_step,
                        d_nq, (const int *)d_matches12, (float *)d_prev_matched);
@@ -4813,6 +5152,35 @@ int orbhip_dev_resolve_stats(unsigned int out[4])
     if (hipMemcpyToSymbol(HIP_SYMBOL(orbhip::g_resolve_stats), z, sizeof(z)) != hipSuccess) return ORBHIP_E_HIP;
     return ORBHIP_OK;
 }
+// development builds: what the window search of this handle's last windowed search left for the resolve -- cnt[nlists] and
+// the compact rows ccand[nlists * 64] (nlists = pairs x query capacity of that call); synchronises the stream
+int orbhip_dev_window_lists(orbhip_matcher *m, int nlists, int *cnt, unsigned long long *ccand)
+{
+    if (!m || nlists < 1 || !cnt || !ccand) return ORBHIP_E_ARG;
+    const size_t n = (size_t)nlists;
+    if (m->cap[S_CNT] < n * sizeof(int) || m->cap[S_CCAND] < n * kCompact * sizeof(unsigned long long)) return ORBHIP_E_ARG;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
+    ORBHIP_HIP_CHECK(hipMemcpy(cnt, m->buf[S_CNT], n * sizeof(int), hipMemcpyDeviceToHost));
+    ORBHIP_HIP_CHECK(hipMemcpy(ccand, m->buf[S_CCAND], n * kCompact * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return ORBHIP_OK;
+}
+// development builds: the LDS-state parallel resolve of this handle runs its stamped instantiation (on != 0) ...
+int orbhip_dev_set_resolve_stamps(orbhip_matcher *m, int on)
+{
+    if (!m) return ORBHIP_E_ARG;
+    m->resolve_stamps = on != 0;
+    return ORBHIP_OK;
+}
+// ... and its per-phase clock sums since the last call: {state init + head loads, first full step, event-driven rounds,
+// unobserved pass, assign + histogram, cull, output, workgroups}.  The caller synchronises the stream first.
+int orbhip_dev_resolve_stamps(unsigned long long out[8])
+{
+    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(orbhip::g_resolve_stamps), sizeof(z)) != hipSuccess) return ORBHIP_E_HIP;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(orbhip::g_resolve_stamps), z, sizeof(z)) != hipSuccess) return ORBHIP_E_HIP;
+    return ORBHIP_OK;
+}
 #endif
 
 int orbhip_keyframe_queries(orbhip_matcher *m, const orbhip_camera *cam, int mode, int double_invz, const float *T1,
@@ -4867,6 +5235,13 @@ int orbhip_fuse(orbhip_matcher *m, const orbhip_frame_view *kf, const orbhip_cam
 // one-wavefront-per-query mapping for tools/bench_fuse.py
 static int g_fuse_lanes = 8;
 #ifdef ORBHIP_DEVTOOLS
+// lanes per query of k_window_search for every windowed search of this handle: 16 / 64, 0 = the product rule
+int orbhip_dev_set_window_lanes(orbhip_matcher *m, int lanes)
+{
+    if (!m || (lanes != 0 && lanes != 16 && lanes != 64)) return ORBHIP_E_ARG;
+    m->window_lanes = lanes;
+    return ORBHIP_OK;
+}
 int orbhip_dev_fuse_lanes(int lanes)
 {
     if (lanes != 8 && lanes != 64) return ORBHIP_E_ARG;

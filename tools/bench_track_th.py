@@ -3,11 +3,17 @@
 (last, cur) KITTI-shape pairs as a function of the search radius `th` (src/Tracking.cc:880-892 uses 7 / 15 and 2 x th on
 its retry; wider windows put more than 64 candidates on a query's list).  HIP events on the launch stream.
 
-  python tools/bench_track_th.py [--pairs 32] [--ths 7,15,30,60,100]
+  python tools/bench_track_th.py [--pairs 32[,85]] [--ths 7,15,30,60,100] [--widths 16,64] [--resolve-stamps] [--out FILE]
+
+--widths (development build, orbhip_dev_set_window_lanes): the table once per forced width of k_window_search (lanes per
+query), 0 = the product rule.  --resolve-stamps (development build, orbhip_dev_resolve_stamps): one stamped call per th
+after the timing, the shares of k_resolve_par's phases in its workgroups' clocks.
 """
 import argparse
+import ctypes as C
 import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -18,56 +24,109 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--pairs", type=int, default=32)
+    ap.add_argument("--pairs", default="32", help="pairs per call; a comma-separated list gives one table per value")
     ap.add_argument("--ths", default="7,15,30,60,100")
+    ap.add_argument("--widths", default="")
+    ap.add_argument("--resolve-stamps", action="store_true")
+    ap.add_argument("--out", default="")
     args = ap.parse_args()
+    widths = [int(v) for v in args.widths.split(",")] if args.widths else []
+    L = None
+    if widths or args.resolve_stamps:
+        from orb_slam2_comment_amd import capi
+        dev_lib = os.path.join(ROOT, "tools", "_dev", "liborbhip_dev.so")
+        if not os.path.exists(dev_lib):
+            subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "orb_slam2_comment_amd", "csrc"), "dev"], check=True)
+        capi.use_library(dev_lib)
+        L = capi.lib()
     import torch
     import bench as Bn
     from orb_slam2_comment_amd import ORBextractor, ORBmatcher
     from orb_slam2_comment_amd import matcher as M
     from orb_slam2_comment_amd.capi import POINT_OBSERVED, POINT_PRESENT
     from orb_slam2_comment_amd.synth import synth_frame
-    dev = torch.device("cuda", 0)
-    W, H, P = Bn.W, Bn.H, args.pairs
-    B = 2 * P
-    frames = np.stack([synth_frame(1 + (i // 2) % 8, W, H, shift_xy=(3 * (i % 2), 0)) for i in range(min(B, 16))])
-    d_img = torch.from_numpy(np.stack([frames[i % len(frames)] for i in range(B)])).to(dev)
-    st = torch.cuda.Stream(dev)
-    ext = ORBextractor(Bn.NFEAT, 1.2, Bn.NLEVELS, 20, 7)
-    mt = ORBmatcher(0.9, True)
-    ext.set_stream(st.cuda_stream); mt.set_stream(st.cuda_stream)
-    cap = ext.capacity(H, W)
-    k = torch.zeros((B, cap, 7), dtype=torch.int32, device=dev); d = torch.zeros((B, cap, 32), dtype=torch.uint8, device=dev)
-    n = torch.zeros(B, dtype=torch.int32, device=dev); s = torch.zeros(B, dtype=torch.int32, device=dev)
-    ext.extract_batch_device(d_img.data_ptr(), B, H, W, k.data_ptr(), d.data_ptr(), cap, n.data_ptr(), s.data_ptr())
-    torch.cuda.synchronize(dev)
-    cam = M.make_camera(Bn.KITTI_FX, Bn.KITTI_FY, Bn.KITTI_CX, Bn.KITTI_CY, (0.0, 0.0, float(W), float(H)), ext.GetScaleFactors(),
-                        mbf=Bn.KITTI_BF, mb=Bn.KITTI_BF / Bn.KITTI_FX)
-    Tlw = torch.eye(4)[:3, :].reshape(1, 12).repeat(P, 1).contiguous().to(dev)
-    Tc = torch.eye(4); Tc[0, 3] = float(np.float32(3.0) * np.float32(Bn.DEPTH) / np.float32(Bn.KITTI_FX))
-    Tcw = Tc[:3, :].reshape(1, 12).repeat(P, 1).contiguous().to(dev)
-    world = torch.zeros((B, cap, 3), dtype=torch.float32, device=dev)
-    kf = k[0::2].view(torch.float32)
-    world[0::2, :, 0] = (kf[..., 0] - Bn.KITTI_CX) * (Bn.DEPTH / Bn.KITTI_FX)
-    world[0::2, :, 1] = (kf[..., 1] - Bn.KITTI_CY) * (Bn.DEPTH / Bn.KITTI_FY)
-    world[0::2, :, 2] = Bn.DEPTH
-    flags = torch.full((B, cap), POINT_PRESENT | POINT_OBSERVED, dtype=torch.uint8, device=dev)
-    a = torch.zeros((P, cap), dtype=torch.int32, device=dev); m = torch.zeros(P, dtype=torch.int32, device=dev)
-    out = {}
-    for th in [float(v) for v in args.ths.split(",")]:
-        def run():
-            mt.TrackLastFrameDevice(P, cam, Tcw.data_ptr(), Tlw.data_ptr(), k.data_ptr(), d.data_ptr(), n.data_ptr(), cap, 1, 2, 0, 2,
-                                    world.data_ptr(), flags.data_ptr(), th, True, a.data_ptr(), m.data_ptr())
-        for _ in range(3):
-            run()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st)
-        for _ in range(20):
-            run()
-        e1.record(st)
+
+    def measure(P):
+        dev = torch.device("cuda", 0)
+        W, H = Bn.W, Bn.H
+        B = 2 * P
+        frames = np.stack([synth_frame(1 + (i // 2) % 8, W, H, shift_xy=(3 * (i % 2), 0)) for i in range(min(B, 16))])
+        d_img = torch.from_numpy(np.stack([frames[i % len(frames)] for i in range(B)])).to(dev)
+        st = torch.cuda.Stream(dev)
+        ext = ORBextractor(Bn.NFEAT, 1.2, Bn.NLEVELS, 20, 7)
+        mt = ORBmatcher(0.9, True)
+        ext.set_stream(st.cuda_stream); mt.set_stream(st.cuda_stream)
+        cap = ext.capacity(H, W)
+        k = torch.zeros((B, cap, 7), dtype=torch.int32, device=dev); d = torch.zeros((B, cap, 32), dtype=torch.uint8, device=dev)
+        n = torch.zeros(B, dtype=torch.int32, device=dev); s = torch.zeros(B, dtype=torch.int32, device=dev)
+        ext.extract_batch_device(d_img.data_ptr(), B, H, W, k.data_ptr(), d.data_ptr(), cap, n.data_ptr(), s.data_ptr())
         torch.cuda.synchronize(dev)
-        out["th_%g" % th] = {"us_per_call": round(e0.elapsed_time(e1) / 20 * 1e3, 1), "mean_matches": round(float(m.float().mean().item()), 1)}
-    print(json.dumps({"pairs": P, "track_last_frame_device": out}))
+        cam = M.make_camera(Bn.KITTI_FX, Bn.KITTI_FY, Bn.KITTI_CX, Bn.KITTI_CY, (0.0, 0.0, float(W), float(H)), ext.GetScaleFactors(),
+                            mbf=Bn.KITTI_BF, mb=Bn.KITTI_BF / Bn.KITTI_FX)
+        Tlw = torch.eye(4)[:3, :].reshape(1, 12).repeat(P, 1).contiguous().to(dev)
+        Tc = torch.eye(4); Tc[0, 3] = float(np.float32(3.0) * np.float32(Bn.DEPTH) / np.float32(Bn.KITTI_FX))
+        Tcw = Tc[:3, :].reshape(1, 12).repeat(P, 1).contiguous().to(dev)
+        world = torch.zeros((B, cap, 3), dtype=torch.float32, device=dev)
+        kf = k[0::2].view(torch.float32)
+        world[0::2, :, 0] = (kf[..., 0] - Bn.KITTI_CX) * (Bn.DEPTH / Bn.KITTI_FX)
+        world[0::2, :, 1] = (kf[..., 1] - Bn.KITTI_CY) * (Bn.DEPTH / Bn.KITTI_FY)
+        world[0::2, :, 2] = Bn.DEPTH
+        flags = torch.full((B, cap), POINT_PRESENT | POINT_OBSERVED, dtype=torch.uint8, device=dev)
+        a = torch.zeros((P, cap), dtype=torch.int32, device=dev); m = torch.zeros(P, dtype=torch.int32, device=dev)
+        phases = ("state_init_head_loads", "first_full_step", "event_driven_rounds", "unobserved_pass", "assign_histogram", "cull",
+                  "output")
+
+        def table():
+            out = {}
+            for th in [float(v) for v in args.ths.split(",")]:
+                def run():
+                    mt.TrackLastFrameDevice(P, cam, Tcw.data_ptr(), Tlw.data_ptr(), k.data_ptr(), d.data_ptr(), n.data_ptr(), cap, 1, 2, 0,
+                                            2, world.data_ptr(), flags.data_ptr(), th, True, a.data_ptr(), m.data_ptr())
+                for _ in range(3):
+                    run()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(20):
+                    run()
+                e1.record(st)
+                torch.cuda.synchronize(dev)
+                out["th_%g" % th] = {"us_per_call": round(e0.elapsed_time(e1) / 20 * 1e3, 1),
+                                     "mean_matches": round(float(m.float().mean().item()), 1)}
+                if args.resolve_stamps:
+                    z = (C.c_ulonglong * 8)()
+                    L.orbhip_dev_set_resolve_stamps(mt._h, 1)
+                    L.orbhip_dev_resolve_stamps(z)
+                    run()
+                    torch.cuda.synchronize(dev)
+                    L.orbhip_dev_resolve_stamps(z)
+                    L.orbhip_dev_set_resolve_stamps(mt._h, 0)
+                    tot = float(sum(z[:7])) or 1.0
+                    out["th_%g" % th]["resolve_phase_share"] = {p: round(z[i] / tot, 3) for i, p in enumerate(phases)}
+                    out["th_%g" % th]["resolve_clocks_per_workgroup"] = round(tot / max(int(z[7]), 1))
+            return out
+
+        if widths:
+            by = {}
+            for w in widths:
+                L.orbhip_dev_set_window_lanes(mt._h, w)
+                by["lanes_%d" % w] = table()
+            L.orbhip_dev_set_window_lanes(mt._h, 0)
+            return {"track_last_frame_device_by_width": by}
+        return {"track_last_frame_device": table()}
+
+    plist = [int(v) for v in args.pairs.split(",")]
+    if len(plist) == 1:
+        doc = {"pairs": plist[0]}
+        doc.update(measure(plist[0]))
+    else:
+        doc = {"pairs": plist}
+        for P in plist:
+            doc["pairs_%d" % P] = measure(P)
+    print(json.dumps(doc))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":
