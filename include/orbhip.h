@@ -36,6 +36,8 @@
  *                                     (src/Tracking.cc:227-228) applied to the samples the keypoints read
  *   orbhip_distinctive_descriptors    MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307), batched
  *   orbhip_update_map_points*         the same and MapPoint::UpdateNormalAndDepth (:330-371) from an observation table
+ *   orbhip_update_local_map*          Tracking::UpdateLocalKeyFrames / UpdateLocalPoints (src/Tracking.cc:1205-1339) over tables;
+ *   orbhip_track_local_map_device     the same + SearchLocalPoints' frustum test and search (:1143-1193)
  *   orbhip_vocabulary_*               ORBVocabulary (DBoW2::TemplatedVocabulary<FORB>) loadFromTextFile + transform,
  *                                     i.e. Frame::ComputeBoW (src/Frame.cc:395-402)
  *   orbhip_search_by_bow              ORBmatcher::SearchByBoW(KeyFrame*,Frame&,..) (src/ORBmatcher.cc:159-288) and
@@ -753,6 +755,90 @@ int orbhip_update_map_points(orbhip_matcher *m, const orbhip_camera *cam, int wh
                              const int32_t *obs_idx, const int32_t *ref_obs, const float *world, const uint8_t *flags,
                              uint8_t *point_desc, float *normal, float *max_dist, float *min_dist, int32_t *best_obs,
                              uint8_t *status);
+
+/* ---- local map: votes, local key frames, local points -----------------------------------------------------------------
+ * Tracking::UpdateLocalKeyFrames (src/Tracking.cc:1231-1339), UpdateLocalPoints (:1205-1228) and the two loops in front of
+ * SearchLocalPoints' search (:1146-1180) for `frames` current frames in one call, over tables.  The covisibility graph
+ * (AddConnection, UpdateConnections, the parent / child links) stays with the caller, who passes it as tables like the
+ * observation table.  Where the reference iterates a map<KeyFrame*, int> or a set<KeyFrame*> in heap-address order, the
+ * order here is the table's: ascending bank row for the vote map, the caller's order for the children.
+ *
+ * orbhip_local_map_tables (read only).  The key-frame bank has `rows` rows of `cap` slots, the map np points in arrays of pcap:
+ *   slot_point [rows][cap] int32 = mvpMapPoints of each bank row as point indices, -1 = none; n [rows] int32.
+ *   kf_bad [rows] uint8, nullable = pKF->isBad().
+ *   covis [rows][10] int32 = the head of mvpOrderedConnectedKeyFrames (GetBestCovisibilityKeyFrames(10)), -1 padded.
+ *   child_start [rows+1] / child [..] int32 = mspChildrens in CSR form; parent [rows] int32, -1 = none.
+ *   obs_start [np+1] / obs_kf [..] int32: the observation table of orbhip_update_map_points_device.
+ *   flags [pcap] uint8: ORBHIP_POINT_PRESENT = !isBad(), ORBHIP_POINT_OBSERVED = Observations() > 0.
+ *   world / normal [pcap][3], max_dist / min_dist [pcap] float, point_desc [pcap][32] (16-byte aligned): the arrays
+ *   orbhip_update_map_points_device maintains.
+ * orbhip_local_map_io.  In/out: frame_point [frames][cap] int32 = mCurrentFrame.mvpMapPoints (a bad point is set to -1,
+ *   :1248, :1153), frame_n [frames] int32 (read only); local_kf [frames][rows] int32 / n_local_kf [frames] int32 =
+ *   mvpLocalKeyFrames (in/out because :1253 returns early when nobody voted: the previous list then stays and the local
+ *   points are rebuilt from it).  Outputs:
+ *   votes [frames][rows] int32 = keyframeCounter, zeroed by the call (a row repeated in a list counts each time);
+ *   local_point [frames][pcap] int32 = mvpLocalMapPoints as point indices, in the reference's push_back order: list order,
+ *     then slot order, each good point at its first occurrence.  SearchByProjection gives a key point to the first point
+ *     in this order that wins it, so the order is part of the result;
+ *   world_l / normal_l [frames][pcap][3], max_dist_l / min_dist_l [frames][pcap], desc_l [frames][pcap][32] (16-byte
+ *     aligned), flags_l [frames][pcap] uint8, np_l [frames] int32: the same points gathered in that order, in the layout
+ *     orbhip_frustum_queries_device and orbhip_search_by_projection_points_device read.  flags_l is 0 for a point the frame
+ *     already holds (mnLastFrameSeen == mnId, :1170) and ORBHIP_POINT_PRESENT | (flags & ORBHIP_POINT_OBSERVED) otherwise;
+ *   taken [frames][cap] uint8 = frame_point[i] >= 0 && Observations() > 0 (src/ORBmatcher.cc:84-86), for i < frame_n;
+ *   report [frames][8] int32 = {status, n_voted (bad rows included), n_local_kf, ref_row = mpReferenceKF (-1: unchanged),
+ *     ref_votes, walk_end, n_local_points, n_to_match (0 here; orbhip_track_local_map_device fills it)}.
+ *     status: ORBHIP_LOCALMAP_OK; ORBHIP_LOCALMAP_NO_VOTES (list kept); ORBHIP_LOCALMAP_ALL_BAD (every voted row is bad: the
+ *     list is empty, the reference key frame unchanged).  walk_end (the loop :1282-1332): ORBHIP_LOCALMAP_WALK_EXHAUSTED,
+ *     ORBHIP_LOCALMAP_WALK_LIMIT (size() > 80 at the start of a visit), ORBHIP_LOCALMAP_WALK_PARENT (the break at :1328, which
+ *     leaves the whole walk).  The reference key frame is the first row, ascending, with the strictly largest vote count
+ *     among the rows that are not bad.
+ *   A row and a point appear at most once, so [rows] and [pcap] cannot overflow; entries past the counts (and taken past
+ *   frame_n) keep the caller's bytes.
+ * Asynchronous on the matcher's stream, no host synchronisation, no staging copy: two memsets and six kernel launches.  The
+ * workspace (first-occurrence keys, frame-held marks, per-row counts) lives in the handle, grows on demand and is reset by
+ * every call.  cap <= 4096, rows <= 65536 (ORBHIP_E_CAPACITY beyond); frames, rows or np negative, cap < 1, np > pcap or a
+ * null required pointer (everything but kf_bad): ORBHIP_E_ARG; all refused before any device work.  frames == 0: success,
+ * nothing written.  The device form does not range-check the tables' contents (rows, point indices, CSR arrays). */
+#define ORBHIP_LOCALMAP_OK       0
+#define ORBHIP_LOCALMAP_NO_VOTES 1
+#define ORBHIP_LOCALMAP_ALL_BAD  2
+#define ORBHIP_LOCALMAP_WALK_EXHAUSTED 0
+#define ORBHIP_LOCALMAP_WALK_LIMIT     1
+#define ORBHIP_LOCALMAP_WALK_PARENT    2
+typedef struct orbhip_local_map_tables {
+    const void *slot_point, *n, *kf_bad, *covis, *child_start, *child, *parent;
+    const void *obs_start, *obs_kf, *flags;
+    const void *world, *normal, *max_dist, *min_dist, *point_desc;
+} orbhip_local_map_tables;
+typedef struct orbhip_local_map_io {
+    void *frame_point;
+    const void *frame_n;
+    void *local_kf, *n_local_kf;
+    void *votes, *local_point, *world_l, *normal_l, *max_dist_l, *min_dist_l, *desc_l, *flags_l, *np_l, *taken, *report;
+} orbhip_local_map_io;
+int orbhip_update_local_map_device(orbhip_matcher *m, int frames, int rows, int cap, int np, int pcap,
+                                   const orbhip_local_map_tables *tables, const orbhip_local_map_io *io);
+/* The above, then Frame::isInFrustum for the gathered points (orbhip_frustum_queries_device's kernel) and
+ * SearchByProjection(F, vpMapPoints, th) (orbhip_search_by_projection_points_device's kernels) on the same stream: the
+ * matching step of Tracking::TrackLocalMap up to the pose optimisation.  Rows equal calling the three entries in sequence.
+ * track: Tcw [frames][12]; kps [frames][cap] orbhip_keypoint, desc [frames][cap][32], u_right [frames][cap] float (nullable)
+ * = the current frames in the extractor's layout (their counts are io->frame_n).  Outputs: q [frames][pcap] orbhip_query,
+ * assign [frames][cap] int32 (local entry held by each key point, or -1), nmatches [frames] int32; io->frame_point[i] =
+ * local_point[assign[i]] where a key point was assigned (src/ORBmatcher.cc:122) and report[f][7] = nToMatch, the valid query
+ * records.  Needs pcap >= 1 besides the limits above. */
+typedef struct orbhip_local_map_track {
+    const void *Tcw, *kps, *desc, *u_right;
+    void *q, *assign, *nmatches;
+} orbhip_local_map_track;
+int orbhip_track_local_map_device(orbhip_matcher *m, int frames, int rows, int cap, int np, int pcap,
+                                  const orbhip_local_map_tables *tables, const orbhip_local_map_io *io, const orbhip_camera *cam,
+                                  const orbhip_local_map_track *track, float viewing_cos_limit, float th, float nnratio);
+/* Host buffers, synchronous: one staging copy, orbhip_update_local_map_device, one read-back.  The same two records with
+ * host pointers; the in/out and output arrays come back whole (entries past the counts as they were passed in).  It
+ * range-checks what the device form does not: rows in [0, rows), point indices in [-1, np), non-decreasing CSR arrays
+ * starting at or above 0, frame_n and n in [0, cap], n_local_kf in [0, rows]: ORBHIP_E_ARG. */
+int orbhip_update_local_map(orbhip_matcher *m, int frames, int rows, int cap, int np, int pcap,
+                            const orbhip_local_map_tables *tables, const orbhip_local_map_io *io);
 
 /* ---- creating new map points -------------------------------------------------------------------------------------
  * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) for the current key frame and K neighbours in one call, up

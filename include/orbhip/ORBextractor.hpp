@@ -680,6 +680,31 @@ public:
                                               dStatus), "orbhip_update_map_points_device");
     }
 
+    // Tracking::UpdateLocalKeyFrames, UpdateLocalPoints and the bookkeeping in front of SearchLocalPoints' search
+    // (src/Tracking.cc:1146-1180, :1205-1339) for `frames` current frames over tables; the records and the report are
+    // described at orbhip_update_local_map_device in orbhip.h.  Host pointers, synchronous and range-checked: io's
+    // frame_point, local_kf and n_local_kf are updated in place, the outputs are written up to their counts.
+    void UpdateLocalMap(int frames, int rows, int cap, int np, int pcap, const orbhip_local_map_tables &tables,
+                        const orbhip_local_map_io &io)
+    {
+        check(orbhip_update_local_map(m_, frames, rows, cap, np, pcap, &tables, &io), "orbhip_update_local_map");
+    }
+    // device pointers, asynchronous on the matcher's stream, no range checks
+    void UpdateLocalMapDevice(int frames, int rows, int cap, int np, int pcap, const orbhip_local_map_tables &dTables,
+                              const orbhip_local_map_io &dIo)
+    {
+        check(orbhip_update_local_map_device(m_, frames, rows, cap, np, pcap, &dTables, &dIo), "orbhip_update_local_map_device");
+    }
+    // the same, then Frame::isInFrustum(pMP, viewingCosLimit) and SearchByProjection(F, vpMapPoints, th) with nnratio on the
+    // same stream: the matching step of Tracking::TrackLocalMap
+    void TrackLocalMapDevice(int frames, int rows, int cap, int np, int pcap, const orbhip_local_map_tables &dTables,
+                             const orbhip_local_map_io &dIo, const orbhip_camera &cam, const orbhip_local_map_track &dTrack,
+                             float viewingCosLimit, float th, float nnratio)
+    {
+        check(orbhip_track_local_map_device(m_, frames, rows, cap, np, pcap, &dTables, &dIo, &cam, &dTrack, viewingCosLimit, th,
+                                            nnratio), "orbhip_track_local_map_device");
+    }
+
     // the Frame statics the prologues read (src/Frame.cc:97-112), as one record
     static orbhip_camera MakeCamera(float fx, float fy, float cx, float cy, float mbf, float mb, float minX, float maxX, float minY,
                                     float maxY, const std::vector<float> &scaleFactors, float logScaleFactor)

@@ -40,6 +40,24 @@ class Camera(C.Structure):
                 ("scale_factors", C.c_float * MAX_LEVELS)]
 
 
+class LocalMapTables(C.Structure):
+    """orbhip_local_map_tables: the bank, graph and map-point tables of orbhip_update_local_map* (read only)."""
+    _fields_ = [(k, C.c_void_p) for k in ("slot_point", "n", "kf_bad", "covis", "child_start", "child", "parent", "obs_start",
+                                          "obs_kf", "flags", "world", "normal", "max_dist", "min_dist", "point_desc")]
+
+
+class LocalMapIO(C.Structure):
+    """orbhip_local_map_io: the in/out lists and the outputs of orbhip_update_local_map*."""
+    _fields_ = [(k, C.c_void_p) for k in ("frame_point", "frame_n", "local_kf", "n_local_kf", "votes", "local_point", "world_l",
+                                          "normal_l", "max_dist_l", "min_dist_l", "desc_l", "flags_l", "np_l", "taken",
+                                          "report")]
+
+
+class LocalMapTrack(C.Structure):
+    """orbhip_local_map_track: the current frames and the search outputs of orbhip_track_local_map_device."""
+    _fields_ = [(k, C.c_void_p) for k in ("Tcw", "kps", "desc", "u_right", "q", "assign", "nmatches")]
+
+
 POINT_PRESENT, POINT_OBSERVED = 1, 2
 COLOR_BGR, COLOR_RGB = 0, 1
 DEPTH_U16, DEPTH_F32 = 0, 1
@@ -51,6 +69,9 @@ SEED_ALL, SEED_CLOSEST = 0, 1
 UPDATE_DESCRIPTOR, UPDATE_NORMAL_DEPTH = 1, 2
 (MAPPOINT_UPDATED, MAPPOINT_BAD, MAPPOINT_NO_OBSERVATION, MAPPOINT_NO_DESCRIPTOR, MAPPOINT_BAD_REF,
  MAPPOINT_TOO_MANY) = range(6)
+# ORBHIP_LOCALMAP_*: report[0] (status) and report[5] (walk_end) of orbhip_update_local_map*
+LOCALMAP_OK, LOCALMAP_NO_VOTES, LOCALMAP_ALL_BAD = range(3)
+LOCALMAP_WALK_EXHAUSTED, LOCALMAP_WALK_LIMIT, LOCALMAP_WALK_PARENT = range(3)
 REMAP_TABLE_SIZE = 4096
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
@@ -159,6 +180,10 @@ SYMBOLS = [
                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("orbhip_update_map_points", _i, [_vp, C.POINTER(Camera), _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _vp]),
+    ("orbhip_update_local_map_device", _i, [_vp, _i, _i, _i, _i, _i, C.POINTER(LocalMapTables), C.POINTER(LocalMapIO)]),
+    ("orbhip_track_local_map_device", _i, [_vp, _i, _i, _i, _i, _i, C.POINTER(LocalMapTables), C.POINTER(LocalMapIO),
+                                           C.POINTER(Camera), C.POINTER(LocalMapTrack), _f, _f, _f]),
+    ("orbhip_update_local_map", _i, [_vp, _i, _i, _i, _i, _i, C.POINTER(LocalMapTables), C.POINTER(LocalMapIO)]),
     ("orbhip_matcher_set_stream", _i, [_vp, _vp]),
     ("orbhip_matcher_sync", _i, [_vp]),
     ("orbhip_compute_stereo_matches_device", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,

@@ -52,6 +52,38 @@ struct PyrLevelTab {
     unsigned src_off;        // source ROI inside the frame's pyramid block (levels >= 2)
 };
 int ensure_level0(orbhip_extractor *e, hipStream_t consumer);   // orbhip_extractor.hip
+
+// orbhip_localmap.hip: the tables, in/out lists and outputs of orbhip_update_local_map_device, and its workspace
+struct LocalMapArgs {
+    const int *slot_point, *n;          // [rows][cap], [rows]
+    const uint8_t *kf_bad;              // [rows] or null
+    const int *covis;                   // [rows][10]
+    const int *child_start, *child, *parent;
+    const int *obs_start, *obs_kf;
+    const uint8_t *flags;               // [pcap]
+    const float *world, *normal, *max_dist, *min_dist;
+    const uint8_t *point_desc;          // [pcap][32]
+    int *frame_point;                   // [frames][cap], in/out
+    const int *frame_n;
+    int *local_kf, *n_local_kf;         // [frames][rows], [frames], in/out
+    int *votes, *local_point;
+    float *world_l, *normal_l, *max_dist_l, *min_dist_l;
+    uint8_t *desc_l, *flags_l;
+    int *np_l;
+    uint8_t *taken;
+    int *report;                        // [frames][8]
+    // workspace: first [frames][pcap] (reset by the call), free_pt [frames][pcap] (0 = the frame holds the point, reset
+    // by the call), base [frames][rows] (winner counts, then their exclusive scan)
+    uint32_t *first;
+    uint8_t *free_pt;
+    int *base;
+    int frames, rows, cap, pcap;
+};
+size_t local_map_workspace_bytes(int frames, int rows, int pcap);
+int launch_local_map(hipStream_t stream, LocalMapArgs A, void *workspace);
+// n_to_match and F.mvpMapPoints[bestIdx] = pMP after the points search of orbhip_track_local_map_device
+int launch_local_map_apply(hipStream_t stream, int frames, int cap, int pcap, const void *q, const int *np_l, const int *frame_n,
+                           const int *assign, const int *local_point, int *frame_point, int *report);
 }  // namespace orbhip
 
 struct orbhip_extractor {

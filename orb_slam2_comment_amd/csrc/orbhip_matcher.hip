@@ -3740,8 +3740,8 @@ struct orbhip_matcher {
     hipStream_t stream = nullptr;       // stream every launch goes to
     hipStream_t own_stream = nullptr;   // created with the handle
     // grow-only device scratch
-    void *buf[17] = {};
-    size_t cap[17] = {};
+    void *buf[18] = {};
+    size_t cap[18] = {};
     bool lds_attr_set = false, bow_attr_set = false;
 #ifdef ORBHIP_DEVTOOLS
     int window_lanes = 0;               // development build: lanes per query of k_window_search forced to 16 / 64 (0: the rule)
@@ -3800,7 +3800,7 @@ static int scratch(orbhip_matcher *m, int slot, size_t bytes, void **out)
     return ORBHIP_OK;
 }
 
-enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_NSLOTS };
+enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_NSLOTS };
 
 static int stage_begin(orbhip_matcher *m, size_t total, Stage *st)
 {
@@ -5140,6 +5140,165 @@ int orbhip_update_map_points(orbhip_matcher *m, const orbhip_camera *cam, int wh
     }
     if (best_obs && wd) memcpy(best_obs, h + ((const uint8_t *)d_best - base), sn * 4);
     memcpy(status, h + (d_status - base), sn);
+    return ORBHIP_OK;
+}
+
+// ---- local map (kernels: orbhip_localmap.hip) -----------------------------------------------------------------------
+static int local_map_args(orbhip_matcher *m, int frames, int rows, int cap, int np, int pcap, const orbhip_local_map_tables *t,
+                          const orbhip_local_map_io *io)
+{
+    if (!m || !t || !io || frames < 0 || rows < 0 || np < 0 || pcap < 0 || np > pcap || cap < 1) return ORBHIP_E_ARG;
+    if (cap > kGridMax) { set_error("update_local_map: capacity %d exceeds %d", cap, kGridMax); return ORBHIP_E_CAPACITY; }
+    if (rows > 65536) { set_error("update_local_map: %d bank rows exceed 65536", rows); return ORBHIP_E_CAPACITY; }
+    if (!t->slot_point || !t->n || !t->covis || !t->child_start || !t->child || !t->parent || !t->obs_start || !t->obs_kf ||
+        !t->flags || !t->world || !t->normal || !t->max_dist || !t->min_dist || !t->point_desc || !io->frame_point ||
+        !io->frame_n || !io->local_kf || !io->n_local_kf || !io->votes || !io->local_point || !io->world_l || !io->normal_l ||
+        !io->max_dist_l || !io->min_dist_l || !io->desc_l || !io->flags_l || !io->np_l || !io->taken || !io->report)
+        return ORBHIP_E_ARG;
+    return ORBHIP_OK;
+}
+
+int orbhip_update_local_map_device(orbhip_matcher *m, int frames, int rows, int cap, int np, int pcap,
+                                   const orbhip_local_map_tables *t, const orbhip_local_map_io *io)
+{
+    if (int rc = local_map_args(m, frames, rows, cap, np, pcap, t, io)) return rc;
+    if (frames == 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    void *work;
+    if (int rc = scratch(m, S_LMAP, local_map_workspace_bytes(frames, rows, pcap), &work)) return rc;
+    LocalMapArgs A;
+    memset(&A, 0, sizeof(A));
+    A.slot_point = (const int *)t->slot_point; A.n = (const int *)t->n; A.kf_bad = (const uint8_t *)t->kf_bad;
+    A.covis = (const int *)t->covis; A.child_start = (const int *)t->child_start; A.child = (const int *)t->child;
+    A.parent = (const int *)t->parent; A.obs_start = (const int *)t->obs_start; A.obs_kf = (const int *)t->obs_kf;
+    A.flags = (const uint8_t *)t->flags; A.world = (const float *)t->world; A.normal = (const float *)t->normal;
+    A.max_dist = (const float *)t->max_dist; A.min_dist = (const float *)t->min_dist; A.point_desc = (const uint8_t *)t->point_desc;
+    A.frame_point = (int *)io->frame_point; A.frame_n = (const int *)io->frame_n; A.local_kf = (int *)io->local_kf;
+    A.n_local_kf = (int *)io->n_local_kf; A.votes = (int *)io->votes; A.local_point = (int *)io->local_point;
+    A.world_l = (float *)io->world_l; A.normal_l = (float *)io->normal_l; A.max_dist_l = (float *)io->max_dist_l;
+    A.min_dist_l = (float *)io->min_dist_l; A.desc_l = (uint8_t *)io->desc_l; A.flags_l = (uint8_t *)io->flags_l;
+    A.np_l = (int *)io->np_l; A.taken = (uint8_t *)io->taken; A.report = (int *)io->report;
+    A.frames = frames; A.rows = rows; A.cap = cap; A.pcap = pcap;
+    return launch_local_map(m->stream, A, work);
+}
+
+int orbhip_track_local_map_device(orbhip_matcher *m, int frames, int rows, int cap, int np, int pcap,
+                                  const orbhip_local_map_tables *t, const orbhip_local_map_io *io, const orbhip_camera *cam,
+                                  const orbhip_local_map_track *tr, float viewing_cos_limit, float th, float nnratio)
+{
+    if (int rc = local_map_args(m, frames, rows, cap, np, pcap, t, io)) return rc;
+    if (!cam || !tr || pcap < 1 || cam->n_levels < 1 || cam->n_levels > ORBHIP_MAX_LEVELS || !tr->Tcw || !tr->kps || !tr->desc ||
+        !tr->q || !tr->assign || !tr->nmatches)
+        return ORBHIP_E_ARG;
+    if (frames == 0) return ORBHIP_OK;
+    int rc;
+    if ((rc = orbhip_update_local_map_device(m, frames, rows, cap, np, pcap, t, io))) return rc;
+    if ((rc = orbhip_frustum_queries_device(m, frames, cam, tr->Tcw, pcap, io->np_l, io->world_l, io->normal_l, io->max_dist_l,
+                                            io->min_dist_l, io->flags_l, viewing_cos_limit, th, tr->q, nullptr))) return rc;
+    // Frame::ComputeImageBounds / mfGridElement{Width,Height}Inv (src/Frame.cc:99-100) from the camera's bounds
+    const float inv_w = (float)GRID_COLS / (cam->max_x - cam->min_x), inv_h = (float)GRID_ROWS / (cam->max_y - cam->min_y);
+    if ((rc = orbhip_search_by_projection_points_device(m, frames, tr->kps, tr->desc, io->frame_n, cap, tr->u_right, io->taken,
+                                                        cam->min_x, cam->min_y, inv_w, inv_h, tr->q, io->desc_l, io->np_l, pcap,
+                                                        nnratio, tr->assign, tr->nmatches))) return rc;
+    return launch_local_map_apply(m->stream, frames, cap, pcap, tr->q, (const int *)io->np_l, (const int *)io->frame_n,
+                                  (const int *)tr->assign, (const int *)io->local_point, (int *)io->frame_point, (int *)io->report);
+}
+
+// a CSR offsets array: starts at or above 0 and does not decrease
+static bool csr_ok(const int32_t *start, int count, const char *what)
+{
+    if (start[0] < 0) { set_error("update_local_map: %s starts below 0", what); return false; }
+    for (int i = 0; i < count; ++i)
+        if (start[i + 1] < start[i]) { set_error("update_local_map: %s must be non-decreasing (entry %d)", what, i); return false; }
+    return true;
+}
+
+int orbhip_update_local_map(orbhip_matcher *m, int frames, int rows, int cap, int np, int pcap,
+                            const orbhip_local_map_tables *t, const orbhip_local_map_io *io)
+{
+    if (int rc = local_map_args(m, frames, rows, cap, np, pcap, t, io)) return rc;
+    if (frames == 0) return ORBHIP_OK;
+    const int32_t *slot_point = (const int32_t *)t->slot_point, *n = (const int32_t *)t->n, *covis = (const int32_t *)t->covis;
+    const int32_t *child_start = (const int32_t *)t->child_start, *child = (const int32_t *)t->child, *parent = (const int32_t *)t->parent;
+    const int32_t *obs_start = (const int32_t *)t->obs_start, *obs_kf = (const int32_t *)t->obs_kf;
+    const int32_t *frame_point = (const int32_t *)io->frame_point, *frame_n = (const int32_t *)io->frame_n;
+    const int32_t *local_kf = (const int32_t *)io->local_kf, *n_local_kf = (const int32_t *)io->n_local_kf;
+    if (!csr_ok(child_start, rows, "child_start") || !csr_ok(obs_start, np, "obs_start")) return ORBHIP_E_ARG;
+    const size_t nchild = (size_t)child_start[rows], nobs = (size_t)obs_start[np];
+    auto row_ok = [rows](int r) { return r >= 0 && r < rows; };
+    for (int r = 0; r < rows; ++r) {
+        bool ok = n[r] >= 0 && n[r] <= cap && parent[r] >= -1 && parent[r] < rows;
+        for (int j = 0; ok && j < 10; ++j) ok = covis[(size_t)r * 10 + j] >= -1 && covis[(size_t)r * 10 + j] < rows;
+        for (int i = 0; ok && i < n[r]; ++i) ok = slot_point[(size_t)r * cap + i] >= -1 && slot_point[(size_t)r * cap + i] < np;
+        if (!ok) { set_error("update_local_map: bank row %d holds a count, row or point index out of range", r); return ORBHIP_E_ARG; }
+    }
+    for (size_t o = 0; o < nchild; ++o)
+        if (!row_ok(child[o])) { set_error("update_local_map: child %zu (row %d) is outside the bank", o, child[o]); return ORBHIP_E_ARG; }
+    for (size_t o = 0; o < nobs; ++o)
+        if (!row_ok(obs_kf[o])) { set_error("update_local_map: observation %zu (row %d) is outside the bank", o, obs_kf[o]); return ORBHIP_E_ARG; }
+    for (int f = 0; f < frames; ++f) {
+        bool ok = frame_n[f] >= 0 && frame_n[f] <= cap && n_local_kf[f] >= 0 && n_local_kf[f] <= rows;
+        for (int i = 0; ok && i < frame_n[f]; ++i) ok = frame_point[(size_t)f * cap + i] >= -1 && frame_point[(size_t)f * cap + i] < np;
+        for (int i = 0; ok && i < n_local_kf[f]; ++i) ok = row_ok(local_kf[(size_t)f * rows + i]);
+        if (!ok) { set_error("update_local_map: frame %d holds a count, row or point index out of range", f); return ORBHIP_E_ARG; }
+    }
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const size_t R = (size_t)rows, Cp = (size_t)cap, P = (size_t)pcap, Fr = (size_t)frames;
+    const size_t in_bytes = al256(R * Cp * 4) + 4 * al256(R * 4 + 4) + al256(R * 40) + al256(nchild * 4) + al256((size_t)np * 4 + 4) +
+                            al256(nobs * 4) + al256(P) + 2 * al256(P * 12) + 2 * al256(P * 4) + al256(P * 32) + al256(Fr * 4);
+    const size_t out_bytes_max = 2 * al256(Fr * Cp * 4) + 2 * al256(Fr * R * 4) + 2 * al256(Fr * 4) + al256(Fr * P * 4) +
+                                 2 * al256(Fr * P * 12) + 2 * al256(Fr * P * 4) + al256(Fr * P * 32) + al256(Fr * P) + al256(Fr * 32);
+    Stage st;
+    int rc;
+    if ((rc = stage_begin(m, in_bytes + out_bytes_max, &st))) return rc;
+    orbhip_local_map_tables dt;
+    orbhip_local_map_io dio;
+    dt.slot_point = st.put(slot_point, R * Cp);
+    dt.n = st.put(n, R);
+    dt.kf_bad = t->kf_bad ? st.put((const uint8_t *)t->kf_bad, R) : nullptr;
+    dt.covis = st.put(covis, R * 10);
+    dt.child_start = st.put(child_start, R + 1);
+    dt.child = st.put(child, nchild);
+    dt.parent = st.put(parent, R);
+    dt.obs_start = st.put(obs_start, (size_t)np + 1);
+    dt.obs_kf = st.put(obs_kf, nobs);
+    dt.flags = st.put((const uint8_t *)t->flags, P);
+    dt.world = st.put((const float *)t->world, P * 3);
+    dt.normal = st.put((const float *)t->normal, P * 3);
+    dt.max_dist = st.put((const float *)t->max_dist, P);
+    dt.min_dist = st.put((const float *)t->min_dist, P);
+    dt.point_desc = st.put((const uint8_t *)t->point_desc, P * 32);
+    dio.frame_n = st.put(frame_n, Fr);
+    // in/out and output arrays next to each other, as the caller passed them: one copy brings all of them back
+    const size_t out_off = st.off;
+    struct Out { void *host; const void *dev; size_t bytes; } outs[14];
+    int no = 0;
+    auto out = [&](void *host, size_t bytes) -> void * {
+        const uint8_t *d = st.put((const uint8_t *)host, bytes);
+        outs[no].host = host; outs[no].dev = d; outs[no].bytes = bytes; ++no;
+        return const_cast<uint8_t *>(d);
+    };
+    dio.frame_point = out(io->frame_point, Fr * Cp * 4);
+    dio.local_kf = out(io->local_kf, Fr * R * 4);
+    dio.n_local_kf = out(io->n_local_kf, Fr * 4);
+    dio.votes = out(io->votes, Fr * R * 4);
+    dio.local_point = out(io->local_point, Fr * P * 4);
+    dio.world_l = out(io->world_l, Fr * P * 12);
+    dio.normal_l = out(io->normal_l, Fr * P * 12);
+    dio.max_dist_l = out(io->max_dist_l, Fr * P * 4);
+    dio.min_dist_l = out(io->min_dist_l, Fr * P * 4);
+    dio.desc_l = out(io->desc_l, Fr * P * 32);
+    dio.flags_l = out(io->flags_l, Fr * P);
+    dio.np_l = out(io->np_l, Fr * 4);
+    dio.taken = out(io->taken, Fr * Cp);
+    dio.report = out(io->report, Fr * 32);
+    const size_t out_bytes = st.off - out_off;
+    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = orbhip_update_local_map_device(m, frames, rows, cap, np, pcap, &dt, &dio))) return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
+    for (int i = 0; i < no; ++i)
+        if (outs[i].bytes) memcpy(outs[i].host, h + ((const uint8_t *)outs[i].dev - (st.d + out_off)), outs[i].bytes);
     return ORBHIP_OK;
 }
 

@@ -388,6 +388,89 @@ class ORBmatcher:
                                                         d_min_dist, d_best_obs, d_status),
               "orbhip_update_map_points_device")
 
+    # -- local map (src/Tracking.cc:1146-1180, :1205-1339) ---------------------------------------------------------------
+    LOCAL_MAP_TABLES = tuple(k for k, _ in capi.LocalMapTables._fields_)
+    LOCAL_MAP_IO = tuple(k for k, _ in capi.LocalMapIO._fields_)
+    LOCAL_MAP_TRACK = tuple(k for k, _ in capi.LocalMapTrack._fields_)
+
+    @staticmethod
+    def _record(cls, values, optional=()):
+        """A ctypes record from a dict of addresses (ints, or objects with data_ptr()); keys in `optional` may be absent."""
+        rec = cls()
+        for k, _ in cls._fields_:
+            v = values.get(k)
+            if v is None:
+                if k not in optional:
+                    raise ValueError("%s: %r is missing" % (cls.__name__, k))
+                continue
+            setattr(rec, k, v.data_ptr() if hasattr(v, "data_ptr") else int(v))
+        return rec
+
+    def UpdateLocalMap(self, tables, frame_point, frame_n, local_kf, n_local_kf, fill=0):
+        """Tracking::UpdateLocalKeyFrames, UpdateLocalPoints and the bookkeeping in front of SearchLocalPoints' search for the
+        frames of frame_point [frames, cap], from host arrays: `tables` is a dict with the keys of LOCAL_MAP_TABLES
+        (slot_point [rows, cap], n [rows], kf_bad [rows] or None, covis [rows, 10], child_start [rows+1], child, parent
+        [rows], obs_start [np+1], obs_kf, flags [pcap], world / normal [pcap, 3], max_dist / min_dist [pcap], point_desc
+        [pcap, 32]); local_kf [frames, rows] / n_local_kf [frames] are the previous lists.  One staged copy, one device
+        call, one read-back; range-checked (OrbHipError with E_ARG).  Returns a dict with the keys of LOCAL_MAP_IO: updated
+        copies of frame_point, local_kf and n_local_kf, and the outputs, whose entries past the counts hold `fill`."""
+        i32, f32, u8 = np.int32, np.float32, np.uint8
+        fp = np.array(frame_point, i32, order="C", ndmin=2)
+        frames, cap = fp.shape
+        T = {k: tables.get(k) for k in self.LOCAL_MAP_TABLES}
+        for k, dt in (("slot_point", i32), ("n", i32), ("covis", i32), ("child_start", i32), ("child", i32), ("parent", i32),
+                      ("obs_start", i32), ("obs_kf", i32), ("flags", u8), ("world", f32), ("normal", f32), ("max_dist", f32),
+                      ("min_dist", f32), ("point_desc", u8)):
+            if T[k] is None:
+                raise ValueError("tables[%r] is missing" % k)
+            T[k] = np.ascontiguousarray(T[k], dt)
+        T["kf_bad"] = None if T["kf_bad"] is None else np.ascontiguousarray(T["kf_bad"], u8)
+        rows, pcap, n_pts = len(T["n"]), len(T["flags"]), len(T["obs_start"]) - 1
+        if (T["slot_point"].size != rows * cap or T["covis"].size != rows * 10 or len(T["child_start"]) != rows + 1 or
+                len(T["parent"]) != rows or n_pts < 0 or n_pts > pcap or (T["kf_bad"] is not None and len(T["kf_bad"]) != rows) or
+                T["world"].size != 3 * pcap or T["normal"].size != 3 * pcap or len(T["max_dist"]) != pcap or
+                len(T["min_dist"]) != pcap or T["point_desc"].size != 32 * pcap or
+                len(T["child"]) < max(int(T["child_start"][-1]), 0) or len(T["obs_kf"]) < max(int(T["obs_start"][-1]), 0)):
+            raise ValueError("the local-map tables do not agree on rows, cap or pcap")
+        for k in ("child", "obs_kf"):        # a required pointer even when the list is empty
+            if T[k].size == 0:
+                T[k] = np.zeros(1, i32)
+        io = dict(frame_point=fp, frame_n=np.ascontiguousarray(frame_n, i32),
+                  local_kf=np.array(local_kf, i32, order="C").reshape(frames, rows), n_local_kf=np.array(n_local_kf, i32, order="C"),
+                  votes=np.full((frames, rows), fill, i32), local_point=np.full((frames, pcap), fill, i32),
+                  world_l=np.full((frames, pcap, 3), fill, f32), normal_l=np.full((frames, pcap, 3), fill, f32),
+                  max_dist_l=np.full((frames, pcap), fill, f32), min_dist_l=np.full((frames, pcap), fill, f32),
+                  desc_l=np.full((frames, pcap, 32), fill, u8), flags_l=np.full((frames, pcap), fill, u8),
+                  np_l=np.full(frames, fill, i32), taken=np.full((frames, cap), fill, u8), report=np.full((frames, 8), fill, i32))
+        if len(io["frame_n"]) != frames or len(io["n_local_kf"]) != frames:
+            raise ValueError("frame_n and n_local_kf need one entry per frame")
+        keep = [np.zeros(1, u8) if a.size == 0 else a for a in io.values()]      # never pass a null required pointer
+        rt = self._record(capi.LocalMapTables, {k: (None if v is None else ptr(v).value) for k, v in T.items()}, ("kf_bad",))
+        rio = self._record(capi.LocalMapIO, {k: ptr(a).value for k, a in zip(io, keep)})
+        check(self._lib.orbhip_update_local_map(self._h, frames, rows, cap, n_pts, pcap, C.byref(rt), C.byref(rio)),
+              "orbhip_update_local_map")
+        return io
+
+    def UpdateLocalMapDevice(self, frames, rows, cap, np_, pcap, tables, io):
+        """Device-resident form (orbhip_update_local_map_device in include/orbhip.h): `tables` and `io` are dicts with the
+        keys of LOCAL_MAP_TABLES / LOCAL_MAP_IO holding device addresses (ints, or tensors); kf_bad may be absent.
+        Asynchronous on the matcher's stream."""
+        rt = self._record(capi.LocalMapTables, tables, ("kf_bad",))
+        rio = self._record(capi.LocalMapIO, io)
+        check(self._lib.orbhip_update_local_map_device(self._h, int(frames), int(rows), int(cap), int(np_), int(pcap), C.byref(rt),
+                                                       C.byref(rio)), "orbhip_update_local_map_device")
+
+    def TrackLocalMapDevice(self, frames, rows, cap, np_, pcap, tables, io, cam, track, viewing_cos_limit, th, nnratio):
+        """UpdateLocalMapDevice, then the frustum prologue and the points search on the same stream
+        (orbhip_track_local_map_device): `track` holds Tcw, kps, desc, u_right (may be absent), q, assign, nmatches."""
+        rt = self._record(capi.LocalMapTables, tables, ("kf_bad",))
+        rio = self._record(capi.LocalMapIO, io)
+        rtr = self._record(capi.LocalMapTrack, track, ("u_right",))
+        check(self._lib.orbhip_track_local_map_device(self._h, int(frames), int(rows), int(cap), int(np_), int(pcap), C.byref(rt),
+                                                      C.byref(rio), C.byref(cam), C.byref(rtr),
+                                                      float(np.float32(viewing_cos_limit)), float(np.float32(th)),
+                                                      float(np.float32(nnratio))), "orbhip_track_local_map_device")
+
     # -- device-resident, batched SearchByProjection ---------------------------
     def set_stream(self, stream):
         check(self._lib.orbhip_matcher_set_stream(self._h, stream), "orbhip_matcher_set_stream")
