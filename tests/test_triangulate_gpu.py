@@ -1,6 +1,7 @@
 """orbhip_create_new_map_points_device / orbhip_create_new_map_points (LocalMapping::CreateNewMapPoints for the current
-key frame and K neighbours in one call) against tests/seqref/triangulate.py and the oracle's search_for_triangulation run
-pair by pair: F12, epipole, gate, matches, status codes and 3-D points bit-identical, row by row.
+key frame and K neighbours in one call) against tests/seqref/triangulate.py with a search_for_triangulation run pair by
+pair, the oracle's or, in the *_with_the_sequential_search tests, that of tests/seqref/bow.py: F12, epipole, gate,
+matches, status codes and 3-D points bit-identical, row by row.
 
 The scene: one extraction batch of 7 frames at 376x240, 500 features.  A uniform image shift s is a fronto-parallel plane at
 depth Z seen from a camera translated sideways by s*Z/f, so with identity rotations the matched pairs really triangulate
@@ -25,6 +26,7 @@ import numpy as np
 import pytest
 
 from helpers import make_vocabulary, synth_frame, write_vocabulary
+from seqref import bow as SB
 from seqref import triangulate as R
 
 pytestmark = pytest.mark.gpu
@@ -133,8 +135,9 @@ class Run:
                            depth=None if mono else S["depth"][f][:n]))
         return fr
 
-    def expected(self, kf_index, mono, only_stereo, check_ori, median=None, n_cur=None):
-        """seqref rows; the search is the unchanged oracle's, called per pair with the seqref's F12 and epipole"""
+    def expected(self, kf_index, mono, only_stereo, check_ori, median=None, n_cur=None, search_from="oracle"):
+        """seqref rows; the search is the unchanged oracle's, or (search_from="seqref") tests/seqref/bow.py's, called per
+        pair with the seqref's F12 and epipole"""
         S, O = self.env["S"], self.env["O"]
         fr = self.frames(mono, n_cur)
         n1 = fr[CUR]["n"]
@@ -153,9 +156,20 @@ class Run:
                                                  1 - S["hp"][f][:n2], F12, float(ex), float(ey), S["sigma2"], only_stereo,
                                                  check_ori)
             return m12
-        key = (tuple(kf_index), mono, only_stereo, check_ori, n_cur)
+
+        def search_seqref(k, f, F12, ex, ey):
+            n2 = fr[f]["n"]
+            if n1 == 0 or n2 == 0:
+                return np.full(n1, -1, np.int32)
+            nm, m12 = SB.search_for_triangulation(
+                S["keys"][CUR][:n1], S["desc"][CUR][:n1], S["node"][CUR][:n1], 1 - S["hp"][CUR][:n1],
+                None if mono else S["ur"][CUR][:n1], S["keys"][f][:n2], S["desc"][f][:n2], S["node"][f][:n2], 1 - S["hp"][f][:n2],
+                None if mono else S["ur"][f][:n2], F12, ex, ey, S["sigma2"], S["sf"], only_stereo, check_ori)
+            return m12
+        key = (tuple(kf_index), mono, only_stereo, check_ori, n_cur, search_from)
         if key not in self.pair_cache:
-            self.pair_cache[key] = R.create_new_map_points(fr, CUR, kf_index, S["rcam"], S["sigma2"], S["sf"], search, median)
+            self.pair_cache[key] = R.create_new_map_points(fr, CUR, kf_index, S["rcam"], S["sigma2"], S["sf"],
+                                                           search if search_from == "oracle" else search_seqref, median)
         return self.pair_cache[key]
 
     def device(self, kf_index, mono, only_stereo, check_ori, median=None, n_cur=None, cap=None, cur=CUR, f12=True):
@@ -280,6 +294,26 @@ def test_stereo_rows_equal_the_sequential_reference(env, only_stereo, check_ori)
             assert exp["status"][KF_INDEX.index(HAND3), i] == code, (i, code)
         created = exp["status"] == R.CREATED
         assert created.sum() > 50 and np.median(np.abs(exp["x3d"][created][:, 2] - Z)) < 0.1 * Z   # onto the plane
+
+
+@pytest.mark.parametrize("only_stereo,check_ori", [(False, True), (True, False)])
+def test_stereo_rows_with_the_sequential_search(env, only_stereo, check_ori):
+    """The same rows with tests/seqref/bow.py's SearchForTriangulation in the oracle's place: nothing of the expected
+    values comes from the oracle."""
+    run, S = env["run"], env["S"]
+    exp = run.expected(KF_INDEX, False, only_stereo, check_ori, search_from="seqref")
+    got = run.device(KF_INDEX, False, only_stereo, check_ori)
+    compare(got, exp, S["n"][CUR], len(KF_INDEX))
+    assert exp["nmatches"].sum() > (150 if not only_stereo else 20)
+
+
+def test_monocular_rows_with_the_sequential_search(env):
+    run, S = env["run"], env["S"]
+    median = [Z] * len(KF_INDEX)
+    exp = run.expected(KF_INDEX, True, False, False, median, search_from="seqref")
+    got = run.device(KF_INDEX, True, False, False, median)
+    compare(got, exp, S["n"][CUR], len(KF_INDEX))
+    assert (exp["status"] == R.CREATED).sum() > 30
 
 
 def test_rows_equal_todays_single_pair_search(env):

@@ -1,8 +1,10 @@
 """Parity of the HIP vocabulary transform (Frame::ComputeBoW) against the oracle, through the C ABI.
 Words, weights, FeatureVector nodes and BowVector ids must be identical; BowVector values are doubles produced by
 the same operation order and must be BIT-identical (asserted with array_equal, tolerance 0).
-Parity unpinned: the reference ships no vocabulary file and no BoW fixtures, so the oracle itself is only checked
-against hand-worked cases (tests/test_oracle_known_answers.py)."""
+The oracle is not the only arbiter of this path: tests/seqref/bow.py restates the loader and both transform overloads from
+the reference text, tests/test_seqref_bow_cpu.py checks the oracle against it bit for bit and tests/test_seqref_bow_gpu.py
+the kernels.  What stays unpinned is a real ORBvoc.txt: the reference checkout ships no vocabulary file and no BoW
+fixtures, so every tree here is synthetic (helpers.make_vocabulary, written in the same text format)."""
 import numpy as np
 import pytest
 
