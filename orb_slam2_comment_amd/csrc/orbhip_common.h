@@ -106,6 +106,26 @@ __device__ __forceinline__ int wave_min(int v)
     return __builtin_amdgcn_readlane(v, 63);
 }
 
+// set bits of `mask` below this lane (position of the lane among the set lanes of a ballot)
+__device__ __forceinline__ int lane_prefix(unsigned long long mask)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+}
+
+// An LDS hand-off between the lanes of ONE wavefront: what a lane wrote to LDS before this point is what any lane of the
+// same wavefront reads after it, and what a lane read before it may be overwritten by another lane after it.  Two halves:
+//   - hardware: a wavefront issues in lockstep and its DS operations execute in order, so nothing is waited for -- no
+//     s_barrier, no s_waitcnt; the fences are wavefront-scope and emit no instruction.
+//   - compiler: wave_barrier alone is a scheduling barrier, not a memory fence (it is IntrNoMem in LLVM); the release /
+//     acquire pair is what forbids moving LDS accesses across this point.
+// Data that crosses wavefronts needs __syncthreads().
+__device__ __forceinline__ void wave_lds_handoff()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // XCD-aware work mapping (speed only, never correctness): workgroups are dealt round-robin over the
 // 8 XCDs in linear order, each XCD has a private 4 MB L2.  Re-index so that XCD k owns a contiguous
 // run of (frame, unit) pairs: with a batch that is a multiple of 8 every kernel of the pipeline

@@ -32,8 +32,6 @@ void set_error(const char *fmt, ...)
 // ---------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int wave_reduce_add(int v) { return wave_sum(v); }
-
 // Exclusive scan of one int per thread over a T-thread block (T = 256, 512 or 1024).  `sh` = T / 64 ints of LDS.
 // Returns the exclusive prefix; *total receives the block sum.  Ends with a barrier.
 template <int T>
@@ -576,10 +574,6 @@ constexpr int kFastLead = 1;             // k_fast_cells: LDS column of sub-imag
 
 __device__ __forceinline__ int min3i(int a, int b, int c) { return min(min(a, b), c); }
 __device__ __forceinline__ int max3i(int a, int b, int c) { return max(max(a, b), c); }
-__device__ __forceinline__ int lane_prefix(unsigned long long m)
-{
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-}
 
 // ---------------------------------------------------------------------------
 // K2+K3: FAST-9/16 + NMS, one WAVEFRONT per reference cell (= the reference's cv::FAST call(s) for
@@ -1299,7 +1293,7 @@ __device__ __forceinline__ void octree_body(OctShared<MAXN> &S, const PyrGeom &G
                     }
                 }
             }
-            __builtin_amdgcn_wave_barrier();
+            wave_lds_handoff();                            // S.rnk / S.ord: written by one lane, read by another
             // D: inclusive scan of the child counts in processing order; the break index J of the careful phase
             const int perm = (m + 63) >> 6;
             const int j_lo = lane * perm, j_hi = min(j_lo + perm, m);
@@ -1322,7 +1316,7 @@ __device__ __forceinline__ void octree_body(OctShared<MAXN> &S, const PyrGeom &G
                 jf = wave_min(jf);
                 J = jf == 0x7fffffff ? m - 1 : jf;
             }
-            __builtin_amdgcn_wave_barrier();
+            wave_lds_handoff();                            // S.cincl
             Gc = m > 0 ? S.cincl[J] : 0;   // children created this pass
             // E: the new table: children reversed in front, survivors behind in order
             int nToExpand = 0;
@@ -1799,14 +1793,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ORBHIP_DESC
                 __builtin_memcpy(&wvv[u], wb + (uint32_t)(u * kWinRpi * wpitch) + voff, 4);
         }
     }
-    __builtin_amdgcn_wave_barrier();                     // the previous keypoint's LDS reads are done
+    wave_lds_handoff();                                  // the previous keypoint's LDS reads come before the overwrite
     if (lane < kWinRpi * kWinDw) {
         uint32_t *dd = win + (srow * kWinDw + scol);
 #pragma unroll
         for (int u = 0; u < kWinLoads; ++u)
             if (u < kWinLoads - 1 || srow < kWinRows - (kWinLoads - 1) * kWinRpi) dd[u * kWinRpi * kWinDw] = wvv[u];
     }
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_handoff();                                  // the tile is read across lanes
     // ---- moments ----
     // sum u * I = sum u * (I - 128) because the weights of the disc sum to zero: the pixels become signed bytes (xor
     // 0x80) and a chunk costs two v_dot4c_i32_i8
@@ -1835,13 +1829,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ORBHIP_DESC
         hs[it] = make_uint4(__builtin_amdgcn_perm(s[1][0], s[0][0], 0x05040100u), __builtin_amdgcn_perm(s[1][1], s[0][1], 0x05040100u),
                             __builtin_amdgcn_perm(s[1][2], s[0][2], 0x05040100u), __builtin_amdgcn_perm(s[1][3], s[0][3], 0x05040100u));
     }
-    m10 = wave_reduce_add(m10);
-    m01 = wave_reduce_add(m01);
+    wave_lds_handoff();                                  // the column pass reads other lanes' row sums
+    m10 = wave_sum(m10);
+    m01 = wave_sum(m01);
     const float angle = fast_atan2_deg((float)m01, (float)m10);
     const float factorPI = (float)(3.14159265358979323846 / 180.f);
     float a, bsn;
     det_sincos(__fmul_rn(angle, factorPI), &a, &bsn);
-    __builtin_amdgcn_wave_barrier();                     // DS operations of a wavefront execute in order
     // ---- column pass on demand: a descriptor test needs the blurred patch at two points only, so the 7-tap column sum
     // is evaluated right at the 8 sample points of a lane (4 dwords of row sums -- two window rows each -- against the
     // tap pairs of the point's row parity) instead of over all 37 x 37 patch pixels first ----

@@ -25,18 +25,6 @@ constexpr int kLmCovis = 10;        // GetBestCovisibilityKeyFrames(10)
 constexpr int kLmPosBlocks = 1024;  // grid.x of the kernels that loop over list positions
 constexpr int kLmStampWords = 65536 / 32;
 
-// an LDS hand-off between the lanes of one wavefront
-__device__ __forceinline__ void lm_handoff()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// set bits of mk below this lane
-__device__ __forceinline__ int lm_prefix(unsigned long long mk)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0));
-}
 __device__ __forceinline__ int lm_list_len(const LocalMapArgs &A, int f) { return min(max(A.n_local_kf[f], 0), A.rows); }
 
 // :1235-1251 and :1146-1162.  A group of 16 lanes owns one slot of the current frame.
@@ -90,7 +78,7 @@ __global__ __launch_bounds__(256) void k_lm_keyframes(LocalMapArgs A)
         for (int w = 0; w < wv; ++w) off += s_wcnt[w];
         const int total = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
         if (good) {
-            const int pos = off + lm_prefix(mg);
+            const int pos = off + lane_prefix(mg);
             list[pos] = r;                                                 // :1276
             if (pos < kLmMaxKf) s_head[pos] = r;
             atomicOr(&s_stamp[r >> 5], 1u << (r & 31));                    // :1277
@@ -123,7 +111,7 @@ __global__ __launch_bounds__(256) void k_lm_keyframes(LocalMapArgs A)
     do {                                                                     \
         if (lane == 0) { list[size] = (x); s_stamp[(x) >> 5] |= 1u << ((x) & 31); } \
         ++size;                                                              \
-        lm_handoff();                                                        \
+        wave_lds_handoff();                                                  \
     } while (0)
     for (int v = 0; v < n_first; ++v) {
         if (size > kLmMaxKf) { walk_end = 1; break; }                      // :1285
@@ -210,7 +198,7 @@ template <bool EMIT> __global__ __launch_bounds__(256) void k_lm_points(LocalMap
             for (int w = 0; w < wv; ++w) off += s_w[w];
             run += s_w[0] + s_w[1] + s_w[2] + s_w[3];
             if (EMIT && win) {
-                const size_t e = (size_t)f * A.pcap + (size_t)(off + lm_prefix(mk));
+                const size_t e = (size_t)f * A.pcap + (size_t)(off + lane_prefix(mk));
                 A.local_point[e] = p;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {

@@ -59,11 +59,6 @@ __device__ __forceinline__ int hamming256(const uint32_t *a, const uint32_t *b)
     return d;
 }
 
-__device__ __forceinline__ int wave_reduce_add_i(int v)
-{
-    return wave_sum(v);
-}
-
 // 64-bit minimum over the wavefront (wave-uniform result): the same DPP butterfly + row broadcasts as wave_sum, both
 // halves of the key travelling together
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
@@ -537,9 +532,9 @@ __global__ __launch_bounds__(256) void k_window_search(DevFrame F, const int *__
         const int excl = incl - ncand, nrec = group_total<L>(incl, ncand);
         for (int r0 = 0; __any(r0 < nrec); r0 += L) {
             // scatter: flat record t of this chunk comes from CSR position spos[t - r0]
-            __builtin_amdgcn_wave_barrier();
+            wave_lds_handoff();   // the previous chunk's reads of spos are done; its staged keys may be copied out below
             for (int k = max(0, r0 - excl); k < ncand && excl + k < r0 + L; ++k) spos[qw][excl + k - r0] = start + k;
-            __builtin_amdgcn_wave_barrier();
+            wave_lds_handoff();
             bool ok = false;
             unsigned long long key = 0;
             if (r0 + gl < nrec) {
@@ -580,7 +575,7 @@ __global__ __launch_bounds__(256) void k_window_search(DevFrame F, const int *__
             total = ntot;
         }
     }
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_handoff();                                   // the staged keys are read across the group
     // short lists: sorted into the compact row
     const int ns = total <= kCompact ? total : 0;
     unsigned long long *row = ccand + (size_t)(inq ? qi : 0) * kCompact;
@@ -679,9 +674,9 @@ __global__ __launch_bounds__(256) void k_window_search<64>(DevFrame F, const int
         const int excl = incl - ncand;
         for (int r0 = 0; r0 < nrec; r0 += 64) {
             // scatter: flat record t of this chunk comes from CSR position spos[t - r0]
-            __builtin_amdgcn_wave_barrier();
+            wave_lds_handoff();                           // the previous chunk's reads of spos are done
             for (int k = max(0, r0 - excl); k < ncand && excl + k < r0 + 64; ++k) spos[wv][excl + k - r0] = start + k;
-            __builtin_amdgcn_wave_barrier();
+            wave_lds_handoff();
             bool ok = false;
             unsigned long long key = 0;
             if (r0 + lane < nrec) {
@@ -722,7 +717,7 @@ __global__ __launch_bounds__(256) void k_window_search<64>(DevFrame F, const int
         // rank sort of up to 64 distinct keys: lane i counts the keys below its own -- key j comes to all lanes through
         // v_readlane (j is wave-uniform), so a key costs two readlanes, one 64-bit compare and one add -- and stores its
         // key at its rank; cheaper than a bitonic network (12 instructions per stage, 10 .. 21 stages) at every length
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_handoff();                               // the staged keys were written by other lanes
         const unsigned long long v = lane < total ? stage[wv][lane] : ~0ull;
         const uint32_t vlo = (uint32_t)v, vhi = (uint32_t)(v >> 32);
         const int tu = __builtin_amdgcn_readfirstlane(total);
@@ -904,10 +899,10 @@ __global__ __launch_bounds__(1024) void k_bow_pairs(BowSide Q, BowSide T, int ca
             }
             // A thread's elements are tid, tid + 1024, ...: a wavefront owns aligned blocks of 64 elements.  While the
             // partner distance of this step and of the next one is below 64, every element a wavefront touches belongs to
-            // it: its DS operations execute in order and no workgroup barrier is needed (41 of the 55 steps of P = 1024).
+            // it: a wave-local hand-off (wave_lds_handoff) replaces the workgroup barrier (41 of the 55 steps of P = 1024).
             const int jn = j > 1 ? (j >> 1) : k;            // partner distance of the next step
             if (j >= 64 || jn >= 64) __syncthreads();
-            else __builtin_amdgcn_wave_barrier();
+            else wave_lds_handoff();
         }
     for (int i = tid; i < P; i += NT) {   // sizes of the valid prefixes; group heads of the query side
         if (S.qkey[i] != ~0ull) {
@@ -958,10 +953,10 @@ __global__ __launch_bounds__(1024) void k_bow_pairs(BowSide Q, BowSide T, int ca
             const int qo = (qi - q_begin) & (kBowStage - 1);
             if (qo == 0) {
                 const int nst = min(kBowStage, q_end - qi);
-                __builtin_amdgcn_wave_barrier();          // the previous chunk's reads are done (DS operations execute in order)
+                wave_lds_handoff();                       // the previous chunk's reads come before the refill
                 for (int e = lane; e < nst * 8; e += 64)
                     qs[e] = reinterpret_cast<const uint32_t *>(qd + (size_t)(uint32_t)S.qkey[qi + (e >> 3)] * 32)[e & 7];
-                __builtin_amdgcn_wave_barrier();
+                wave_lds_handoff();
             }
             uint32_t qdw[8];
 #pragma unroll
@@ -1840,7 +1835,7 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
         unsigned long long head[kHeadMax];
         bool complete;
         const int nh = wave_sorted_head(a1, a2, na > 2, head, &complete);
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_handoff();                               // every lane has read the old head
         if (lane < kHeadMax) {
             unsigned long long v = head[0];
 #pragma unroll
@@ -1848,7 +1843,7 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
             lrow[lane] = ((uint32_t)(v >> 32) << 20) | (uint32_t)(v & 0xfffffu);
         }
         if (lane == 0) lrow[S.lcn] = (uint32_t)nh | (complete ? 0x100u : 0u);
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_handoff();                               // the owner of query i walks the new head
     };
     // One deferred-acceptance / fixed-point step for the queries of a whole wavefront (lane: query i, `valid` false for
     // idle lanes; every lane of the wavefront must call).  What an unsorted list needs from the whole wavefront -- a
@@ -1968,7 +1963,7 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
         }
         wave_hist_add(S.hist, bin);
     }
-    acc_local = wave_reduce_add_i(acc_local);
+    acc_local = wave_sum(acc_local);
     if ((tid & 63) == 0 && acc_local) atomicAdd(&S.vars[1], acc_local);
     __syncthreads();
     RESOLVE_STAMP(4);   // assign + histogram
@@ -1982,7 +1977,7 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
                 ++cull;
             }
         }
-        cull = wave_reduce_add_i(cull);
+        cull = wave_sum(cull);
         if ((tid & 63) == 0 && cull) atomicAdd(&S.vars[2], cull);
         __syncthreads();
     }
@@ -2244,7 +2239,7 @@ __global__ __launch_bounds__(1024) void k_resolve_init(DevFrame F, const orbhip_
         if (i < nq) { S.q_cnt[i] = m; kept += m >= 0; }   // q_cnt is free now: vnMatches12
         wave_hist_add(S.hist, bin);
     }
-    kept = wave_reduce_add_i(kept);
+    kept = wave_sum(kept);
     if ((tid & 63) == 0 && kept) atomicAdd(&S.vars[4], kept);
     __syncthreads();
     if (check_ori) {
@@ -2253,7 +2248,7 @@ __global__ __launch_bounds__(1024) void k_resolve_init(DevFrame F, const orbhip_
         int cull = 0;
         for (int i = tid; i < nq; i += T)
             if (rot_culled(S.evbin[i], ind1, ind2, ind3) && S.q_cnt[i] >= 0) { S.q_cnt[i] = -1; ++cull; }
-        cull = wave_reduce_add_i(cull);
+        cull = wave_sum(cull);
         if ((tid & 63) == 0 && cull) atomicAdd(&S.vars[5], cull);
         __syncthreads();
     }
@@ -2293,7 +2288,7 @@ __device__ __forceinline__ int row_kth_distance(int d0, const unsigned short *sr
         if (N > 64) {
             int c = 0;
             for (int j = lane + 64; j < N; j += 64) c += srow[j] <= mid;
-            cnt += wave_reduce_add_i(c);
+            cnt += wave_sum(c);
         }
         if (cnt >= k + 1) hi = mid; else lo = mid + 1;
     }
@@ -2332,11 +2327,11 @@ __global__ __launch_bounds__(256) void k_distinctive(const uint8_t *__restrict__
                 for (int w = 0; w < 8; ++w) t[w] = tp[w];
                 srow[wv][j] = (unsigned short)hamming256(di, t);
             }
-            __builtin_amdgcn_wave_barrier();
+            wave_lds_handoff();
         }
         const int lo = row_kth_distance(d0, srow[wv], N, k, lane);
         if (lo < bestMedian) { bestMedian = lo; bestIdx = i; }
-        if (N > 64) __builtin_amdgcn_wave_barrier();
+        if (N > 64) wave_lds_handoff();   // the next row overwrites srow
     }
     if (lane == 0) best[p] = bestIdx;
 }
@@ -2366,13 +2361,6 @@ struct UpdArgs {
     int cap, np, what;
 };
 
-// an LDS hand-off between the lanes of one wavefront
-__device__ __forceinline__ void wave_lds_handoff()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // d = mWorldPos - Owi in float; v = normali / cv::norm(normali): the Mat times the double 1.0 / norm, element by element
 __device__ __forceinline__ void upd_view_dir(const float *T, const float *X, float *d, float *v)
 {
@@ -2546,7 +2534,7 @@ __global__ __launch_bounds__(64) void k_update_points_long(UpdArgs A, orbhip_cam
                 }
                 const unsigned long long mk = __ballot(ok);
                 if (ok) {
-                    const int pos = M + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0));
+                    const int pos = M + lane_prefix(mk);
                     srow_of[pos] = row;
                     spos[pos] = (unsigned short)j;
                 }
@@ -3415,7 +3403,7 @@ __global__ __launch_bounds__(256) void k_stereo_match(const orbhip_keypoint *__r
             sr[idx] = rw;
         }
     }
-    __builtin_amdgcn_wave_barrier();          // DS operations of a wavefront execute in order
+    wave_lds_handoff();                       // the two windows are read across lanes
     const uint8_t *bl = reinterpret_cast<const uint8_t *>(sl), *br = reinterpret_cast<const uint8_t *>(sr);
     const int cL = bl[5 * 12 + 5];
     int pl[2];
@@ -3441,10 +3429,10 @@ __global__ __launch_bounds__(256) void k_stereo_match(const orbhip_keypoint *__r
     int dists[11];
 #pragma unroll
     for (int s = 0; s < 10; s += 2) {
-        const uint32_t two = (uint32_t)wave_reduce_add_i(accs[s] | (accs[s + 1] << 16));
+        const uint32_t two = (uint32_t)wave_sum(accs[s] | (accs[s + 1] << 16));
         dists[s] = (int)(two & 0xffffu); dists[s + 1] = (int)(two >> 16);
     }
-    dists[10] = wave_reduce_add_i(accs[10]);
+    dists[10] = wave_sum(accs[10]);
     int bestD = INT_MAX, bestincR = 0;
 #pragma unroll
     for (int s = 0; s < 11; ++s) if (dists[s] < bestD) { bestD = dists[s]; bestincR = s - L; }
@@ -3654,9 +3642,7 @@ __global__ __launch_bounds__(1024) void k_seed_stereo_points(SeedBatch B, float 
                 const int t = c * 64 + lane;
                 for (int jj = j; jj > 0; jj >>= 1) {
                     if (t < half) seed_compare_exchange(key, t, jj, k);
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wave_lds_handoff();
                 }
             }
             __syncthreads();

@@ -40,12 +40,6 @@ struct VocBatch {
     int cap;            // feature stride per frame
 };
 
-__device__ __forceinline__ int group16_min(int v)
-{
-    // 16-lane groups are DPP rows: the butterfly never leaves the group and needs no LDS crossbar round trip
-    return orbhip::row16_min(v);
-}
-
 // One 16-lane group per feature.  key = distance * 32 + child position, so the group minimum is the reference's
 // first strict minimum (:1240-1249).
 __global__ __launch_bounds__(256) void k_voc_descend(VocDev V, const uint8_t *__restrict__ desc, int n, int levelsup,
@@ -85,7 +79,7 @@ __global__ __launch_bounds__(256) void k_voc_descend(VocDev V, const uint8_t *__
             for (int w = 0; w < 8; ++w) d += __popc(f[w] ^ cp[w]);
             best = min(best, d * 32 + c);
         }
-        best = group16_min(best);
+        best = orbhip::row16_min(best);   // a 16-lane group is a DPP row: the butterfly never leaves it
         if (!done) {
             node = V.child_id[off + (uint32_t)(best & 31)];
             ++level;
