@@ -58,6 +58,98 @@ __device__ __forceinline__ int hamming256(const uint32_t *a, const uint32_t *b)
     for (int i = 0; i < 8; ++i) d += __popc(a[i] ^ b[i]);
     return d;
 }
+// the same against a descriptor that arrived as two 16-byte loads
+__device__ __forceinline__ int hamming256(const uint32_t (&q)[8], uint4 d0, uint4 d1)
+{
+    return __popc(q[0] ^ d0.x) + __popc(q[1] ^ d0.y) + __popc(q[2] ^ d0.z) + __popc(q[3] ^ d0.w) +
+           __popc(q[4] ^ d1.x) + __popc(q[5] ^ d1.y) + __popc(q[6] ^ d1.z) + __popc(q[7] ^ d1.w);
+}
+
+// ---- the frame grid (Frame::PosInGrid, Frame::GetFeaturesInArea), the one home of its rules ------------------------
+// Bit-exactness against the reference hangs on these: `round` in PosInGrid, floor / ceil and the float operation order
+// ((x - min_x) - r) * inv_w in the cell window, the strict |dx| < r, Fuse's chi-square gate compared in double.
+//
+// Frame::PosInGrid (src/Frame.cc:382-392): the cell posX * 48 + posY of a key point, -1 when it is rejected.
+__device__ __forceinline__ int grid_cell(float x, float y, float min_x, float min_y, float inv_w, float inv_h)
+{
+    const int px = (int)roundf(__fmul_rn(__fsub_rn(x, min_x), inv_w));
+    const int py = (int)roundf(__fmul_rn(__fsub_rn(y, min_y), inv_h));
+    return (px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS) ? -1 : px * GRID_ROWS + py;
+}
+// The cells a window of radius r around (x, y) covers (src/Frame.cc:332-346), clamped to the grid.  empty() = either of the
+// reference's early exits (nMinCell >= 64 / 48, nMaxCell < 0) or a reversed range, over which its loops do not run.
+struct CellWindow {
+    int x0, x1, y0, y1;
+    __device__ __forceinline__ bool empty() const
+    {
+        // `|`, not `||`: one straight-line test, no branch around the y terms
+        return (x0 >= GRID_COLS) | (x1 < 0) | (y0 >= GRID_ROWS) | (y1 < 0) | (x1 < x0) | (y1 < y0);
+    }
+};
+__device__ __forceinline__ CellWindow cell_window(float x, float y, float r, float min_x, float min_y, float inv_w,
+                                                  float inv_h)
+{
+    CellWindow W;
+    W.x0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, min_x), r), inv_w)));
+    W.x1 = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, min_x), r), inv_w)));
+    W.y0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, min_y), r), inv_h)));
+    W.y1 = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, min_y), r), inv_h)));
+    return W;
+}
+constexpr int kGridCells = GRID_COLS * GRID_ROWS;
+struct GridRec { float x, y; int octave; uint32_t key; };   // a key point in the CSR grid of k_grid_build; key = cell << 20 | index
+struct SigmaTab { float inv_sigma2[ORBHIP_MAX_LEVELS]; };
+// The candidate test of the window search (the loop bodies of SearchByProjection / SearchForInitialization over
+// GetFeaturesInArea) for the record at CSR position p: level window, |dx|,|dy| < r, the stereo gate (rur[p] is loaded only
+// when it applies) and the acceptance cut.  key = dist << 32 | R.key whatever ok says.
+struct WindowHit { bool ok; unsigned long long key; };
+__device__ __forceinline__ WindowHit window_candidate(const GridRec *__restrict__ rec, const uint4 *__restrict__ rdesc,
+                                                      const float *__restrict__ rur, int p, const orbhip_query &Q,
+                                                      const uint32_t (&qd)[8], bool stereo_gate, int max_dist)
+{
+    const GridRec R = rec[p];
+    const uint4 d0 = rdesc[2 * p], d1 = rdesc[2 * p + 1];
+    bool ok = true;
+    if ((Q.min_level > 0) || (Q.max_level >= 0)) {   // bCheckLevels
+        if (R.octave < Q.min_level) ok = false;
+        if (Q.max_level >= 0 && R.octave > Q.max_level) ok = false;
+    }
+    ok = ok && fabsf(__fsub_rn(R.x, Q.u)) < Q.radius && fabsf(__fsub_rn(R.y, Q.v)) < Q.radius;
+    if (ok && stereo_gate) {
+        const float ur = rur[p];
+        if (ur > 0 && fabsf(__fsub_rn(Q.ur, ur)) > Q.radius) ok = false;
+    }
+    const int dist = hamming256(qd, d0, d1);
+    // searches that take the best candidate alone (no second best, no ratio test) never look past the first free entry,
+    // and an entry beyond their acceptance threshold can only mean "no match": it need not be listed
+    return {ok && dist <= max_dist, ((unsigned long long)dist << 32) | R.key};
+}
+// The candidate test of Fuse and SearchBySim3 (src/ORBmatcher.cc:893-950, :1045-1075, :1199-1219) for train key point j:
+// |dx|,|dy| < r, kpLevel in [min_level, max_level], with chi2_gate the reprojection error against 5.99 (mono) / 7.8
+// (stereo) scaled by mvInvLevelSigma2[level] and compared in double.  False = not a candidate; else *dist = Hamming distance.
+__device__ __forceinline__ bool fuse_candidate(const orbhip_keypoint *__restrict__ keys, const uint8_t *__restrict__ desc,
+                                               const float *__restrict__ u_right, int j, float x, float y, float r,
+                                               float qur, int min_level, int max_level, bool chi2_gate,
+                                               const SigmaTab &sig, const uint32_t (&qd)[8], int *dist)
+{
+    const orbhip_keypoint kp = keys[j];
+    if (!(fabsf(__fsub_rn(kp.x, x)) < r && fabsf(__fsub_rn(kp.y, y)) < r)) return false;
+    if (kp.octave < min_level || kp.octave > max_level) return false;   // kpLevel<pred-1 || kpLevel>pred
+    if (chi2_gate) {
+        const float ex = __fsub_rn(x, kp.x), ey = __fsub_rn(y, kp.y);
+        float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+        const float kpr = u_right ? u_right[j] : -1.0f;
+        const float is2 = sig.inv_sigma2[kp.octave & (ORBHIP_MAX_LEVELS - 1)];
+        if (kpr >= 0) {
+            const float er = __fsub_rn(qur, kpr);
+            e2 = __fadd_rn(e2, __fmul_rn(er, er));
+            if ((double)__fmul_rn(e2, is2) > 7.8) return false;
+        } else if ((double)__fmul_rn(e2, is2) > 5.99) return false;
+    }
+    const uint4 *tp = reinterpret_cast<const uint4 *>(desc + (size_t)j * 32);
+    *dist = hamming256(qd, tp[0], tp[1]);
+    return true;
+}
 
 // 64-bit minimum over the wavefront (wave-uniform result): the same DPP butterfly + row broadcasts as wave_sum, both
 // halves of the key travelling together
@@ -262,10 +354,8 @@ __global__ void k_grid_order(DevFrame F, uint32_t *__restrict__ ord, Batch B)
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= F.n) return;
     const orbhip_keypoint kp = F.keys[j];
-    int px = (int)roundf(__fmul_rn(__fsub_rn(kp.x, F.min_x), F.inv_w));
-    int py = (int)roundf(__fmul_rn(__fsub_rn(kp.y, F.min_y), F.inv_h));
-    bool in = !(px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS);
-    ord[j] = in ? (((uint32_t)(px * GRID_ROWS + py) << 20) | (uint32_t)j) : kNoCell;
+    const int cell = grid_cell(kp.x, kp.y, F.min_x, F.min_y, F.inv_w, F.inv_h);
+    ord[j] = cell >= 0 ? (((uint32_t)cell << 20) | (uint32_t)j) : kNoCell;
 }
 
 // mGrid of the train frame (Frame::AssignFeaturesToGrid, Frame.cc:230-245) as CSR, one workgroup per frame: cell
@@ -276,8 +366,6 @@ __global__ void k_grid_order(DevFrame F, uint32_t *__restrict__ ord, Batch B)
 // by the key (cell << 20 | index) = the visiting order of Frame::GetFeaturesInArea (cell-major ix outer / iy inner,
 // insertion order inside a cell; Frame.cc:350-358).  Keypoints that PosInGrid rejects (Frame.cc:382-392) are in no
 // cell and never candidates.
-constexpr int kGridCells = GRID_COLS * GRID_ROWS;
-struct GridRec { float x, y; int octave; uint32_t key; };   // key = cell << 20 | index
 __device__ __forceinline__ void grid_build_body(DevFrame F, int *__restrict__ cell_start, GridRec *__restrict__ rec,
                                                 uint4 *__restrict__ rdesc, float *__restrict__ rur, const Batch &B, const int pair)
 {
@@ -290,12 +378,7 @@ __device__ __forceinline__ void grid_build_body(DevFrame F, int *__restrict__ ce
     rec += rbase; rdesc += rbase * 2; rur += rbase;
     for (int c = tid; c < kGridCells; c += 256) s_cnt[c] = 0;
     __syncthreads();
-    // PosInGrid: the cell of a keypoint, -1 when it is rejected
-    const auto cell_of = [&](float x, float y) {
-        const int px = (int)roundf(__fmul_rn(__fsub_rn(x, F.min_x), F.inv_w));
-        const int py = (int)roundf(__fmul_rn(__fsub_rn(y, F.min_y), F.inv_h));
-        return (px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS) ? -1 : px * GRID_ROWS + py;
-    };
+    const auto cell_of = [&](float x, float y) { return grid_cell(x, y, F.min_x, F.min_y, F.inv_w, F.inv_h); };
     const auto emit = [&](int j, float x, float y, int octave, int cell) {
         const int pos = atomicAdd(&s_cnt[cell], 1);
         GridRec r; r.x = x; r.y = y; r.octave = octave; r.key = ((uint32_t)cell << 20) | (uint32_t)j;
@@ -324,9 +407,8 @@ __device__ __forceinline__ void grid_build_body(DevFrame F, int *__restrict__ ce
     } else {
         for (int j = tid; j < F.n; j += 256) {
             const orbhip_keypoint kp = F.keys[j];
-            const int px = (int)roundf(__fmul_rn(__fsub_rn(kp.x, F.min_x), F.inv_w));
-            const int py = (int)roundf(__fmul_rn(__fsub_rn(kp.y, F.min_y), F.inv_h));
-            if (!(px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS)) atomicAdd(&s_cnt[px * GRID_ROWS + py], 1);
+            const int cell = cell_of(kp.x, kp.y);
+            if (cell >= 0) atomicAdd(&s_cnt[cell], 1);
         }
     }
     __syncthreads();
@@ -354,17 +436,8 @@ __device__ __forceinline__ void grid_build_body(DevFrame F, int *__restrict__ ce
     } else {
         for (int j = tid; j < F.n; j += 256) {
             const orbhip_keypoint kp = F.keys[j];
-            const int px = (int)roundf(__fmul_rn(__fsub_rn(kp.x, F.min_x), F.inv_w));
-            const int py = (int)roundf(__fmul_rn(__fsub_rn(kp.y, F.min_y), F.inv_h));
-            if (!(px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS)) {
-                const int cell = px * GRID_ROWS + py;
-                const int pos = atomicAdd(&s_cnt[cell], 1);
-                GridRec r; r.x = kp.x; r.y = kp.y; r.octave = kp.octave; r.key = ((uint32_t)cell << 20) | (uint32_t)j;
-                rec[pos] = r;
-                const uint4 *d = reinterpret_cast<const uint4 *>(F.desc + (size_t)j * 32);
-                rdesc[2 * pos] = d[0]; rdesc[2 * pos + 1] = d[1];
-                rur[pos] = F.u_right ? F.u_right[j] : -1.0f;
-            }
+            const int cell = cell_of(kp.x, kp.y);
+            if (cell >= 0) emit(j, kp.x, kp.y, kp.octave, cell);
         }
     }
 }
@@ -394,11 +467,10 @@ template <int L> __device__ __forceinline__ int group_incl_scan_add(int v)
     v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8
     return v;
 }
-// total of a group whose inclusive scan is `incl` (of the values v), in every lane of the group
-template <int L> __device__ __forceinline__ int group_total(int incl, int v)
+// total of the values v of a group, in every lane of the group
+template <int L> __device__ __forceinline__ int group_total(int v)
 {
     static_assert(L == 16, "a group is one DPP row");
-    (void)incl;
     v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);    // quad_perm [1,0,3,2]
     v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);    // quad_perm [2,3,0,1]
     v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);   // row_half_mirror
@@ -489,21 +561,13 @@ __global__ __launch_bounds__(256) void k_window_search(DevFrame F, const int *__
     const bool inq = qi < nq;
     orbhip_query Q = {};
     if (inq) Q = q[qi];
-    const float x = Q.u, y = Q.v, r = Q.radius;
-    // Frame.cc:332-346
-    const int nMinCellX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, F.min_x), r), F.inv_w)));
-    const int nMaxCellX = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, F.min_x), r), F.inv_w)));
-    const int nMinCellY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, F.min_y), r), F.inv_h)));
-    const int nMaxCellY = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, F.min_y), r), F.inv_h)));
+    const CellWindow W = cell_window(Q.u, Q.v, Q.radius, F.min_x, F.min_y, F.inv_w, F.inv_h);
     // a group without a valid query or with an empty window idles: no column, no record, no list
-    const bool live = inq && Q.valid &&
-                      !(nMinCellX >= GRID_COLS || nMaxCellX < 0 || nMinCellY >= GRID_ROWS || nMaxCellY < 0 ||
-                        nMaxCellX < nMinCellX || nMaxCellY < nMinCellY);
+    const bool live = inq && Q.valid && !W.empty();
     if (!__any(live)) {   // nothing to search in this wavefront
         if (inq && gl == 0) cnt[qi] = 0;
         return;
     }
-    const bool bCheckLevels = (Q.min_level > 0) || (Q.max_level >= 0);
     uint32_t qd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (live) {
         const uint32_t *qp = reinterpret_cast<const uint32_t *>(qdesc + (size_t)qi * 32);
@@ -511,53 +575,34 @@ __global__ __launch_bounds__(256) void k_window_search(DevFrame F, const int *__
         for (int i = 0; i < 8; ++i) qd[i] = qp[i];
     }
     unsigned long long *out = cand + (size_t)(inq ? qi : 0) * stride;
-    const int ncy = nMaxCellY - nMinCellY + 1;
+    const int ncy = W.y1 - W.y0 + 1;
     int total = 0;
     unsigned long long b1 = ~0ull, b2 = ~0ull;   // this lane's two smallest keys among candidates not taken on entry
     int nb = 0;                                  // ... out of how many
     // a column of the window is a contiguous run of cells (cell = ix * 48 + iy), so its records are one contiguous CSR
     // range: lane = window column, range = [start[ix*48 + y0], start[ix*48 + y1 + 1]).  A window wider than L columns
     // takes several trips; total, b1, b2 and nb carry over.
-    const int ncol = live ? nMaxCellX - nMinCellX + 1 : 0;
+    const int ncol = live ? W.x1 - W.x0 + 1 : 0;
     for (int c0 = 0; __any(c0 < ncol); c0 += L) {
         const int c = c0 + gl;
         int start = 0, ncand = 0;
         if (c < ncol) {
-            const int cell0 = (nMinCellX + c) * GRID_ROWS + nMinCellY;
+            const int cell0 = (W.x0 + c) * GRID_ROWS + W.y0;
             start = cell_start[cell0];
             ncand = cell_start[cell0 + ncy] - start;
         }
         // exclusive prefix of the column populations over the group
         const int incl = group_incl_scan_add<L>(ncand);
-        const int excl = incl - ncand, nrec = group_total<L>(incl, ncand);
+        const int excl = incl - ncand, nrec = group_total<L>(ncand);
         for (int r0 = 0; __any(r0 < nrec); r0 += L) {
             // scatter: flat record t of this chunk comes from CSR position spos[t - r0]
             wave_lds_handoff();   // the previous chunk's reads of spos are done; its staged keys may be copied out below
             for (int k = max(0, r0 - excl); k < ncand && excl + k < r0 + L; ++k) spos[qw][excl + k - r0] = start + k;
             wave_lds_handoff();
-            bool ok = false;
-            unsigned long long key = 0;
-            if (r0 + gl < nrec) {
-                const int p = spos[qw][gl];
-                const GridRec R = rec[p];
-                const uint4 d0 = rdesc[2 * p], d1 = rdesc[2 * p + 1];
-                ok = true;
-                if (bCheckLevels) {
-                    if (R.octave < Q.min_level) ok = false;
-                    if (Q.max_level >= 0 && R.octave > Q.max_level) ok = false;
-                }
-                ok = ok && fabsf(__fsub_rn(R.x, x)) < r && fabsf(__fsub_rn(R.y, y)) < r;
-                if (ok && use_ur && has_ur) {
-                    const float ur = rur[p];
-                    if (ur > 0 && fabsf(__fsub_rn(Q.ur, ur)) > r) ok = false;
-                }
-                const int dist = __popc(qd[0] ^ d0.x) + __popc(qd[1] ^ d0.y) + __popc(qd[2] ^ d0.z) + __popc(qd[3] ^ d0.w) +
-                                 __popc(qd[4] ^ d1.x) + __popc(qd[5] ^ d1.y) + __popc(qd[6] ^ d1.z) + __popc(qd[7] ^ d1.w);
-                key = ((unsigned long long)dist << 32) | R.key;
-                // searches that take the best candidate alone (no second best, no ratio test) never look past the first
-                // free entry, and an entry beyond their acceptance threshold can only mean "no match": it need not be listed
-                ok = ok && dist <= max_dist;
-            }
+            WindowHit H = {false, 0};
+            if (r0 + gl < nrec) H = window_candidate(rec, rdesc, rur, spos[qw][gl], Q, qd, use_ur && has_ur, max_dist);
+            const bool ok = H.ok;
+            const unsigned long long key = H.key;
             const unsigned long long bal = group_bits<L>(__ballot(ok));
             const int ntot = total + __popcll(bal);
             // a list stays in LDS while it fits the compact row; the chunk that takes it past 64 entries moves the staged
@@ -634,36 +679,28 @@ __global__ __launch_bounds__(256) void k_window_search<64>(DevFrame F, const int
     if (qi >= nq) return;
     const orbhip_query Q = q[qi];
     if (!Q.valid) { if (lane == 0) cnt[qi] = 0; return; }
-    const float x = Q.u, y = Q.v, r = Q.radius;
-    // Frame.cc:332-346
-    const int nMinCellX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, F.min_x), r), F.inv_w)));
-    const int nMaxCellX = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, F.min_x), r), F.inv_w)));
-    const int nMinCellY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, F.min_y), r), F.inv_h)));
-    const int nMaxCellY = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, F.min_y), r), F.inv_h)));
-    if (nMinCellX >= GRID_COLS || nMaxCellX < 0 || nMinCellY >= GRID_ROWS || nMaxCellY < 0 || nMaxCellX < nMinCellX ||
-        nMaxCellY < nMinCellY) {
+    const CellWindow W = cell_window(Q.u, Q.v, Q.radius, F.min_x, F.min_y, F.inv_w, F.inv_h);
+    if (W.empty()) {
         if (lane == 0) cnt[qi] = 0;
         return;
     }
-    const bool bCheckLevels = (Q.min_level > 0) || (Q.max_level >= 0);
     uint32_t qd[8];
     const uint32_t *qp = reinterpret_cast<const uint32_t *>(qdesc + (size_t)qi * 32);
 #pragma unroll
     for (int i = 0; i < 8; ++i) qd[i] = qp[i];
     unsigned long long *out = cand + (size_t)qi * stride;
-    const int ncy = nMaxCellY - nMinCellY + 1, ncell = (nMaxCellX - nMinCellX + 1) * ncy;
+    const int ncy = W.y1 - W.y0 + 1;
     int total = 0;
     unsigned long long b1 = ~0ull, b2 = ~0ull;   // this lane's two smallest keys among candidates not taken on entry
     int nb = 0;                                  // ... out of how many
     // a column of the window is a contiguous run of cells (cell = ix * 48 + iy), so its records are one contiguous CSR
     // range: lane = window column, range = [start[ix*48 + y0], start[ix*48 + y1 + 1])
-    const int ncol = nMaxCellX - nMinCellX + 1;
-    (void)ncell;
+    const int ncol = W.x1 - W.x0 + 1;
     for (int c0 = 0; c0 < ncol; c0 += 64) {
         const int c = c0 + lane;
         int start = 0, ncand = 0;
         if (c < ncol) {
-            const int cell0 = (nMinCellX + c) * GRID_ROWS + nMinCellY;
+            const int cell0 = (W.x0 + c) * GRID_ROWS + W.y0;
             start = cell_start[cell0];
             ncand = cell_start[cell0 + ncy] - start;
         }
@@ -677,29 +714,10 @@ __global__ __launch_bounds__(256) void k_window_search<64>(DevFrame F, const int
             wave_lds_handoff();                           // the previous chunk's reads of spos are done
             for (int k = max(0, r0 - excl); k < ncand && excl + k < r0 + 64; ++k) spos[wv][excl + k - r0] = start + k;
             wave_lds_handoff();
-            bool ok = false;
-            unsigned long long key = 0;
-            if (r0 + lane < nrec) {
-                const int p = spos[wv][lane];
-                const GridRec R = rec[p];
-                const uint4 d0 = rdesc[2 * p], d1 = rdesc[2 * p + 1];
-                ok = true;
-                if (bCheckLevels) {
-                    if (R.octave < Q.min_level) ok = false;
-                    if (Q.max_level >= 0 && R.octave > Q.max_level) ok = false;
-                }
-                ok = ok && fabsf(__fsub_rn(R.x, x)) < r && fabsf(__fsub_rn(R.y, y)) < r;
-                if (ok && use_ur && has_ur) {
-                    const float ur = rur[p];
-                    if (ur > 0 && fabsf(__fsub_rn(Q.ur, ur)) > r) ok = false;
-                }
-                const int dist = __popc(qd[0] ^ d0.x) + __popc(qd[1] ^ d0.y) + __popc(qd[2] ^ d0.z) + __popc(qd[3] ^ d0.w) +
-                                 __popc(qd[4] ^ d1.x) + __popc(qd[5] ^ d1.y) + __popc(qd[6] ^ d1.z) + __popc(qd[7] ^ d1.w);
-                key = ((unsigned long long)dist << 32) | R.key;
-                // searches that take the best candidate alone (no second best, no ratio test) never look past the first
-                // free entry, and an entry beyond their acceptance threshold can only mean "no match": it need not be listed
-                ok = ok && dist <= max_dist;
-            }
+            WindowHit H = {false, 0};
+            if (r0 + lane < nrec) H = window_candidate(rec, rdesc, rur, spos[wv][lane], Q, qd, use_ur && has_ur, max_dist);
+            const bool ok = H.ok;
+            const unsigned long long key = H.key;
             const unsigned long long bal = __ballot(ok);
             if (ok) {
                 const int pos = total + __popcll(bal & ((1ull << lane) - 1ull));
@@ -1471,8 +1489,6 @@ __global__ __launch_bounds__(256) void k_cnmp_triangulate(CnmpArgs A, orbhip_cam
 // (:1199-1219, :1279-1299): GetFeaturesInArea window, level window, optional chi-square gate on the
 // reprojection error (Fuse: 5.99 mono / 7.8 stereo, scaled by mvInvLevelSigma2[level]), Hamming argmin with the
 // reference's first-minimum tie-break.  One wavefront per query.
-struct SigmaTab { float inv_sigma2[ORBHIP_MAX_LEVELS]; };
-
 __global__ __launch_bounds__(256) void k_best_in_window(DevFrame F, const uint32_t *__restrict__ ord,
                                                         const orbhip_query *__restrict__ q,
                                                         const uint8_t *__restrict__ qdesc, int nq, int chi2_gate,
@@ -1485,12 +1501,8 @@ __global__ __launch_bounds__(256) void k_best_in_window(DevFrame F, const uint32
     const orbhip_query Q = q[qi];
     unsigned long long best = ~0ull;
     if (Q.valid) {
-        const float x = Q.u, y = Q.v, r = Q.radius;
-        const int nMinCellX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, F.min_x), r), F.inv_w)));
-        const int nMaxCellX = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, F.min_x), r), F.inv_w)));
-        const int nMinCellY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, F.min_y), r), F.inv_h)));
-        const int nMaxCellY = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, F.min_y), r), F.inv_h)));
-        if (!(nMinCellX >= GRID_COLS || nMaxCellX < 0 || nMinCellY >= GRID_ROWS || nMaxCellY < 0)) {
+        const CellWindow W = cell_window(Q.u, Q.v, Q.radius, F.min_x, F.min_y, F.inv_w, F.inv_h);
+        if (!W.empty()) {
             uint32_t qd[8];
             const uint32_t *qp = reinterpret_cast<const uint32_t *>(qdesc + (size_t)qi * 32);
 #pragma unroll
@@ -1502,26 +1514,11 @@ __global__ __launch_bounds__(256) void k_best_in_window(DevFrame F, const uint32
                 if (o == kNoCell) continue;
                 const int cell = (int)(o >> 20);
                 const int px = cell / GRID_ROWS, py = cell - px * GRID_ROWS;
-                if (!(px >= nMinCellX && px <= nMaxCellX && py >= nMinCellY && py <= nMaxCellY)) continue;
-                const orbhip_keypoint kp = F.keys[j];
-                if (!(fabsf(__fsub_rn(kp.x, x)) < r && fabsf(__fsub_rn(kp.y, y)) < r)) continue;
-                if (kp.octave < Q.min_level || kp.octave > Q.max_level) continue;   // kpLevel<pred-1 || kpLevel>pred
-                if (chi2_gate) {
-                    const float ex = __fsub_rn(x, kp.x), ey = __fsub_rn(y, kp.y);
-                    float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-                    const float kpr = F.u_right ? F.u_right[j] : -1.0f;
-                    const float is2 = sig.inv_sigma2[kp.octave];
-                    if (kpr >= 0) {
-                        const float er = __fsub_rn(Q.ur, kpr);
-                        e2 = __fadd_rn(e2, __fmul_rn(er, er));
-                        if ((double)__fmul_rn(e2, is2) > 7.8) continue;
-                    } else if ((double)__fmul_rn(e2, is2) > 5.99) continue;
-                }
-                const uint32_t *tp = reinterpret_cast<const uint32_t *>(F.desc + (size_t)j * 32);
-                uint32_t td[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) td[i] = tp[i];
-                const unsigned long long key = ((unsigned long long)hamming256(qd, td) << 32) | o;
+                if (!(px >= W.x0 && px <= W.x1 && py >= W.y0 && py <= W.y1)) continue;
+                int d;
+                if (!fuse_candidate(F.keys, F.desc, F.u_right, j, Q.u, Q.v, Q.radius, Q.ur, Q.min_level, Q.max_level,
+                                    chi2_gate != 0, sig, qd, &d)) continue;
+                const unsigned long long key = ((unsigned long long)d << 32) | o;
                 best = key < best ? key : best;
             }
         }
@@ -1813,7 +1810,8 @@ __global__ __launch_bounds__(1024) void k_resolve_par(int mode, DevFrame F, cons
         uint32_t *lrow = S.lc + i * (S.lcn + 1);
         const int hl = (int)(lrow[S.lcn] & 0xffu);
         // the head's last key in full: the LDS copy holds (distance, slot); the cell bits of the key are the slot's grid
-        // cell (PosInGrid, src/Frame.cc:382-392, the expressions of the grid build)
+        // cell.  PosInGrid spelled out, without grid_cell's rejection select: a listed candidate is never a key point that
+        // PosInGrid rejects, and with the select this kernel measured slower than the parent (profiles/grid_rules.json)
         unsigned long long cursor = 0ull;
         if (hl > 0) {
             const uint32_t w = lrow[hl - 1];
@@ -2631,12 +2629,9 @@ __device__ __forceinline__ void grid_csr_body(const DevFrame &F, int *__restrict
         uint32_t k = 0xffffffffu;
         if (i < n) {
             const orbhip_keypoint kp = F.keys[i];
-            const int px = (int)roundf(__fmul_rn(__fsub_rn(kp.x, F.min_x), F.inv_w));
-            const int py = (int)roundf(__fmul_rn(__fsub_rn(kp.y, F.min_y), F.inv_h));
-            const bool in = !(px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS);
-            const int c = px * GRID_ROWS + py;
-            cell_of[i] = in ? c : -1;
-            if (in) { k = ((uint32_t)c << 12) | (uint32_t)i; atomicAdd(&cnt[c], 1); }
+            const int c = grid_cell(kp.x, kp.y, F.min_x, F.min_y, F.inv_w, F.inv_h);
+            cell_of[i] = c;
+            if (c >= 0) { k = ((uint32_t)c << 12) | (uint32_t)i; atomicAdd(&cnt[c], 1); }
         }
         key[i] = k;
     }
@@ -3081,7 +3076,8 @@ __global__ __launch_bounds__(256) void k_keyframe_queries(KfQueryArgs A, orbhip_
 //   3. LPQ lanes per query (64 / LPQ queries of the wavefront at a time) walk the window's cells in the order of
 //      Frame::GetFeaturesInArea (src/Frame.cc:332-378): for every column ix the cells (ix, nMinCellY..nMaxCellY) are
 //      consecutive in c = ix*48 + iy, so their key points are ONE run of cell_items.  Candidate p of the run goes to
-//      lane p % LPQ: |dx|,|dy| < r, level window, chi-square gate, 256-bit Hamming distance exactly as k_best_in_window.
+//      lane p % LPQ: |dx|,|dy| < r, level window, chi-square gate, 256-bit Hamming distance: the test of fuse_candidate,
+//      spelled out in the loop (through the helper this kernel measured 2 % slower than the parent).
 //      The key is distance << 32 | position in cell_items << 12 | index: cell_items is sorted by (cell, index), so the
 //      position orders candidates as cell << 20 | index does and the group minimum is the reference's first minimum.
 struct FuseBatchArgs {
@@ -3151,22 +3147,19 @@ __global__ __launch_bounds__(256) void k_fuse_batch(FuseBatchArgs A, orbhip_came
         const int min_level = __shfl(cml, src), qi = __shfl(cqi, src);
         unsigned long long best = ~0ull;
         if (active) {
-            const int nMinCellX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, A.min_x), r), A.inv_w)));
-            const int nMaxCellX = min(GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, A.min_x), r), A.inv_w)));
-            const int nMinCellY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, A.min_y), r), A.inv_h)));
-            const int nMaxCellY = min(GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, A.min_y), r), A.inv_h)));
-            if (!(nMinCellX >= GRID_COLS || nMaxCellX < 0 || nMinCellY >= GRID_ROWS || nMaxCellY < 0) &&
-                nMinCellY <= nMaxCellY) {
+            const CellWindow W = cell_window(x, y, r, A.min_x, A.min_y, A.inv_w, A.inv_h);
+            if (!W.empty()) {
                 uint32_t qd[8];
                 const uint4 *qp = reinterpret_cast<const uint4 *>(A.point_desc + (size_t)qi * 32);
                 const uint4 q0 = qp[0], q1 = qp[1];
                 qd[0] = q0.x; qd[1] = q0.y; qd[2] = q0.z; qd[3] = q0.w; qd[4] = q1.x; qd[5] = q1.y; qd[6] = q1.z; qd[7] = q1.w;
-                for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
+                for (int ix = W.x0; ix <= W.x1; ++ix) {
                     const int c0 = ix * GRID_ROWS;
-                    const int pb = max(cs[c0 + nMinCellY], 0), pe = min(cs[c0 + nMaxCellY + 1], A.cap);
+                    const int pb = max(cs[c0 + W.y0], 0), pe = min(cs[c0 + W.y1 + 1], A.cap);
                     for (int p = pb + sub; p < pe; p += LPQ) {
                         const int j = items[p];
                         if ((unsigned)j >= (unsigned)n) continue;   // never for a grid of these key points
+                        // fuse_candidate, kept inline here (see 3. above); change the two together
                         const orbhip_keypoint kp = keys[j];
                         if (!(fabsf(__fsub_rn(kp.x, x)) < r && fabsf(__fsub_rn(kp.y, y)) < r)) continue;
                         if (kp.octave < min_level || kp.octave > min_level + 1) continue;   // kpLevel<pred-1 || kpLevel>pred
@@ -3182,9 +3175,7 @@ __global__ __launch_bounds__(256) void k_fuse_batch(FuseBatchArgs A, orbhip_came
                             } else if ((double)__fmul_rn(e2, is2) > 5.99) continue;
                         }
                         const uint4 *tp = reinterpret_cast<const uint4 *>(desc + (size_t)j * 32);
-                        const uint4 t0 = tp[0], t1 = tp[1];
-                        const int d = __popc(qd[0] ^ t0.x) + __popc(qd[1] ^ t0.y) + __popc(qd[2] ^ t0.z) + __popc(qd[3] ^ t0.w) +
-                                      __popc(qd[4] ^ t1.x) + __popc(qd[5] ^ t1.y) + __popc(qd[6] ^ t1.z) + __popc(qd[7] ^ t1.w);
+                        const int d = hamming256(qd, tp[0], tp[1]);
                         const unsigned long long key = ((unsigned long long)d << 32) | ((uint32_t)p << 12) | (uint32_t)j;
                         best = key < best ? key : best;
                     }
@@ -3786,6 +3777,36 @@ static int scratch(orbhip_matcher *m, int slot, size_t bytes, void **out)
     return ORBHIP_OK;
 }
 
+// ---- the host side of the frame grid ---------------------------------------------------------------------------------
+// Frame::ComputeImageBounds / mfGridElement{Width,Height}Inv (src/Frame.cc:99-100) from a camera's bounds
+struct GridInv { float w, h; };
+static GridInv grid_inv(const orbhip_camera *cam)
+{
+    return {(float)GRID_COLS / (cam->max_x - cam->min_x), (float)GRID_ROWS / (cam->max_y - cam->min_y)};
+}
+// the train frame of a device call: n = capacity of a row (Batch::n_dev holds the counts), or 0 where only keys are read
+static DevFrame dev_frame(int n, const void *d_kps, const void *d_desc, const void *d_u_right, float min_x, float min_y,
+                          float inv_w, float inv_h)
+{
+    return {n, (const orbhip_keypoint *)d_kps, (const uint8_t *)d_desc, (const float *)d_u_right, min_x, min_y, inv_w, inv_h};
+}
+// the train frame of a host call: keys, descriptors and u_right go into the staging buffer, in this order
+static DevFrame dev_frame(const orbhip_frame_view *f, Stage &st)
+{
+    const size_t n = (size_t)f->n;
+    const orbhip_keypoint *keys = st.put(f->keys, n);
+    const uint8_t *desc = st.put(f->desc, n * 32);
+    return {f->n, keys, desc, f->u_right ? st.put(f->u_right, n) : nullptr, f->min_x, f->min_y, f->grid_inv_w, f->grid_inv_h};
+}
+// mvInvLevelSigma2 of the first n_levels levels (null: no table, every entry 0)
+static SigmaTab sigma_tab(const float *inv_level_sigma2, int n_levels)
+{
+    SigmaTab sig;
+    memset(&sig, 0, sizeof(sig));
+    if (inv_level_sigma2) for (int l = 0; l < std::min(n_levels, ORBHIP_MAX_LEVELS); ++l) sig.inv_sigma2[l] = inv_level_sigma2[l];
+    return sig;
+}
+
 enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_NSLOTS };
 
 static int stage_begin(orbhip_matcher *m, size_t total, Stage *st)
@@ -3985,11 +4006,7 @@ static int run_search(orbhip_matcher *m, int mode, const orbhip_frame_view *trai
     if ((rc = stage_begin(m, al256(n * sizeof(orbhip_keypoint)) + al256(n * 32) + al256(n * 4) + al256(n) +
                                  al256((size_t)nqv * sizeof(orbhip_query)) + al256((size_t)nqv * 32) +
                                  al256((size_t)nqv * sizeof(orbhip_keypoint)), &st))) return rc;
-    DevFrame D;
-    D.n = train->n; D.min_x = train->min_x; D.min_y = train->min_y; D.inv_w = train->grid_inv_w; D.inv_h = train->grid_inv_h;
-    D.keys = st.put(train->keys, n);
-    D.desc = st.put(train->desc, n * 32);
-    D.u_right = train->u_right ? st.put(train->u_right, n) : nullptr;
+    const DevFrame D = dev_frame(train, st);
     const uint8_t *d_taken = taken ? st.put(taken, n) : nullptr;
     const orbhip_query *d_q;
     const uint8_t *d_qdesc;
@@ -4330,9 +4347,7 @@ int orbhip_assign_features_to_grid_device(orbhip_matcher *m, int frames, const v
     if (cap > kGridMax) { set_error("assign_features_to_grid: capacity %d exceeds %d", cap, kGridMax); return ORBHIP_E_CAPACITY; }
     if (frames == 0) return ORBHIP_OK;
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
-    DevFrame D;
-    D.n = 0; D.keys = (const orbhip_keypoint *)d_kps; D.desc = nullptr; D.u_right = nullptr;
-    D.min_x = min_x; D.min_y = min_y; D.inv_w = grid_inv_w; D.inv_h = grid_inv_h;
+    const DevFrame D = dev_frame(0, d_kps, nullptr, nullptr, min_x, min_y, grid_inv_w, grid_inv_h);
     const Batch B = {(const int *)d_n, nullptr, cap, 0};
     hipLaunchKernelGGL(k_grid_csr, dim3(frames), dim3(1024), 0, m->stream, D, B, (int *)d_cell_of, (int *)d_cell_start,
                        (int *)d_cell_items);
@@ -4638,11 +4653,7 @@ int orbhip_search_best_in_window(orbhip_matcher *m, const orbhip_frame_view *kf,
     int rc;
     if ((rc = stage_begin(m, al256(n * sizeof(orbhip_keypoint)) + al256(n * 32) + al256(n * 4) +
                                  al256((size_t)nq * sizeof(orbhip_query)) + al256((size_t)nq * 32), &st))) return rc;
-    DevFrame D;
-    D.n = kf->n; D.min_x = kf->min_x; D.min_y = kf->min_y; D.inv_w = kf->grid_inv_w; D.inv_h = kf->grid_inv_h;
-    D.keys = st.put(kf->keys, n);
-    D.desc = st.put(kf->desc, n * 32);
-    D.u_right = kf->u_right ? st.put(kf->u_right, n) : nullptr;
+    const DevFrame D = dev_frame(kf, st);
     const orbhip_query *d_q = st.put(q, (size_t)nq);
     const uint8_t *d_qdesc = st.put(qdesc, (size_t)nq * 32);
     if ((rc = stage_commit(m, &st))) return rc;
@@ -4651,9 +4662,7 @@ int orbhip_search_best_in_window(orbhip_matcher *m, const orbhip_frame_view *kf,
     uint32_t *d_ord = (uint32_t *)p;
     if ((rc = scratch(m, S_OUT, (size_t)nq * 2 * sizeof(int), &p))) return rc;
     int *d_out = (int *)p;
-    SigmaTab sig;
-    memset(&sig, 0, sizeof(sig));
-    if (inv_level_sigma2) for (int l = 0; l < std::min(kf->n_levels, ORBHIP_MAX_LEVELS); ++l) sig.inv_sigma2[l] = inv_level_sigma2[l];
+    const SigmaTab sig = sigma_tab(inv_level_sigma2, kf->n_levels);
     const Batch B = {nullptr, nullptr, kf->n, nq};
     hipLaunchKernelGGL(k_grid_order, dim3((kf->n + 255) / 256), dim3(256), 0, m->stream, D, d_ord, B);
     hipLaunchKernelGGL(k_best_in_window, dim3((nq + 3) / 4), dim3(256), 0, m->stream, D, d_ord, d_q, d_qdesc, nq, chi2_gate,
@@ -4682,9 +4691,7 @@ static int search_device(orbhip_matcher *m, int mode, int pairs, const void *d_k
     if (!m || pairs <= 0 || !d_kps || !d_desc || !d_n || !d_q || !d_qdesc || !d_nq || !d_assign || !d_nmatches || cap <= 0 || qcap <= 0)
         return ORBHIP_E_ARG;
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
-    DevFrame D;
-    D.n = cap; D.keys = (const orbhip_keypoint *)d_kps; D.desc = (const uint8_t *)d_desc; D.u_right = (const float *)d_u_right;
-    D.min_x = min_x; D.min_y = min_y; D.inv_w = grid_inv_w; D.inv_h = grid_inv_h;
+    const DevFrame D = dev_frame(cap, d_kps, d_desc, d_u_right, min_x, min_y, grid_inv_w, grid_inv_h);
     const Batch B = {(const int *)d_n, (const int *)d_nq, cap, qcap, t0, ts, qd0, qds};
     return launch_search(m, mode, pairs, D, B, (const orbhip_query *)d_q, (const uint8_t *)d_qdesc, nullptr, (const uint8_t *)d_taken,
                          nnratio, check_ori, TH_HIGH, 0, 1, (int *)d_assign, (int *)d_nmatches, window_lanes(m, mode, proj), proj);
@@ -4757,9 +4764,7 @@ int orbhip_search_for_initialization_device(orbhip_matcher *m, int pairs, const 
     const orbhip_keypoint *keys = (const orbhip_keypoint *)d_kps;
     hipLaunchKernelGGL(k_init_queries, dim3((cap + 255) / 256, pairs), dim3(256), 0, m->stream, keys, (const int *)d_n, cap,
                        f1_first, f1_step, (float *)d_prev_matched, reset_prev, (float)window_size, d_q, d_nq);
-    DevFrame D;
-    D.n = cap; D.keys = keys; D.desc = (const uint8_t *)d_desc; D.u_right = nullptr;
-    D.min_x = min_x; D.min_y = min_y; D.inv_w = grid_inv_w; D.inv_h = grid_inv_h;
+    const DevFrame D = dev_frame(cap, keys, d_desc, nullptr, min_x, min_y, grid_inv_w, grid_inv_h);
     const Batch B = {(const int *)d_n, d_nq, cap, cap, f2_first, f2_step, f1_first, f1_step};
     if ((rc = launch_search(m, 2, pairs, D, B, d_q, (const uint8_t *)d_desc, keys, nullptr, nnratio, check_ori, TH_HIGH, 0, 0,
                             (int *)d_matches12, (int *)d_nmatches, window_lanes(m, 2))))
@@ -4806,9 +4811,8 @@ int orbhip_track_last_frame_device(orbhip_matcher *m, int pairs, const orbhip_ca
     proj.P = {(const float *)d_Tcw, (const float *)d_Tlw, (const orbhip_keypoint *)d_kps, (const int *)d_n,
               (const float *)d_world, (const uint8_t *)d_flags, d_q, d_nq, cap, last_first, last_step};
     proj.cam = *cam; proj.th = th; proj.mono = mono;
-    // Frame::ComputeImageBounds / mfGridElement{Width,Height}Inv (src/Frame.cc:99-100) from the camera's bounds
-    const float inv_w = (float)GRID_COLS / (cam->max_x - cam->min_x), inv_h = (float)GRID_ROWS / (cam->max_y - cam->min_y);
-    return search_device(m, 0, pairs, d_kps, d_desc, d_n, cap, d_u_right, d_taken, cam->min_x, cam->min_y, inv_w, inv_h, d_q,
+    const GridInv inv = grid_inv(cam);
+    return search_device(m, 0, pairs, d_kps, d_desc, d_n, cap, d_u_right, d_taken, cam->min_x, cam->min_y, inv.w, inv.h, d_q,
                          d_desc, d_nq, cap, 0.f, check_ori, d_assign, d_nmatches, cur_first, cur_step, last_first, last_step, &proj);
 }
 
@@ -5181,10 +5185,9 @@ int orbhip_track_local_map_device(orbhip_matcher *m, int frames, int rows, int c
     if ((rc = orbhip_update_local_map_device(m, frames, rows, cap, np, pcap, t, io))) return rc;
     if ((rc = orbhip_frustum_queries_device(m, frames, cam, tr->Tcw, pcap, io->np_l, io->world_l, io->normal_l, io->max_dist_l,
                                             io->min_dist_l, io->flags_l, viewing_cos_limit, th, tr->q, nullptr))) return rc;
-    // Frame::ComputeImageBounds / mfGridElement{Width,Height}Inv (src/Frame.cc:99-100) from the camera's bounds
-    const float inv_w = (float)GRID_COLS / (cam->max_x - cam->min_x), inv_h = (float)GRID_ROWS / (cam->max_y - cam->min_y);
+    const GridInv inv = grid_inv(cam);
     if ((rc = orbhip_search_by_projection_points_device(m, frames, tr->kps, tr->desc, io->frame_n, cap, tr->u_right, io->taken,
-                                                        cam->min_x, cam->min_y, inv_w, inv_h, tr->q, io->desc_l, io->np_l, pcap,
+                                                        cam->min_x, cam->min_y, inv.w, inv.h, tr->q, io->desc_l, io->np_l, pcap,
                                                         nnratio, tr->assign, tr->nmatches))) return rc;
     return launch_local_map_apply(m->stream, frames, cap, pcap, tr->q, (const int *)io->np_l, (const int *)io->frame_n,
                                   (const int *)tr->assign, (const int *)io->local_point, (int *)io->frame_point, (int *)io->report);
@@ -5421,24 +5424,19 @@ int orbhip_fuse_device(orbhip_matcher *m, int K, const void *d_kf_index, const o
     A.point_desc = (const uint8_t *)d_point_desc; A.flags = (const uint8_t *)d_flags;
     A.best_idx = (int *)d_best_idx; A.best_dist = (int *)d_best_dist; A.q = (orbhip_query *)d_q;
     A.cap = cap; A.np = np; A.pcap = pcap; A.sim3_form = sim3_form ? 1 : 0; A.csr_by_target = 0;
-    // Frame::ComputeImageBounds / mfGridElement{Width,Height}Inv (src/Frame.cc:99-100) from the camera's bounds
-    A.min_x = cam->min_x; A.min_y = cam->min_y;
-    A.inv_w = (float)GRID_COLS / (cam->max_x - cam->min_x); A.inv_h = (float)GRID_ROWS / (cam->max_y - cam->min_y);
+    const GridInv inv = grid_inv(cam);
+    A.min_x = cam->min_x; A.min_y = cam->min_y; A.inv_w = inv.w; A.inv_h = inv.h;
     if (!d_cell_start) {   // mGrid of the K targets into the handle's scratch: cell_of | cell_items | cell_start
         void *p;
         const size_t rows = al256((size_t)K * cap * sizeof(int));
         if (int rc = scratch(m, S_CSR, 2 * rows + (size_t)K * (kGridCells + 1) * sizeof(int), &p)) return rc;
         int *cell_of = (int *)p, *cell_items = (int *)((uint8_t *)p + rows), *cell_start = (int *)((uint8_t *)p + 2 * rows);
-        DevFrame D;
-        D.n = 0; D.keys = A.keys; D.desc = nullptr; D.u_right = nullptr;
-        D.min_x = A.min_x; D.min_y = A.min_y; D.inv_w = A.inv_w; D.inv_h = A.inv_h;
+        const DevFrame D = dev_frame(0, A.keys, nullptr, nullptr, A.min_x, A.min_y, A.inv_w, A.inv_h);
         hipLaunchKernelGGL(k_grid_csr_indexed, dim3(K), dim3(1024), 0, m->stream, D, A.kf_index, A.n_dev, cap, cell_of,
                            cell_start, cell_items);
         A.cell_start = cell_start; A.cell_items = cell_items; A.csr_by_target = 1;
     }
-    SigmaTab sig;
-    memset(&sig, 0, sizeof(sig));
-    for (int l = 0; l < cam->n_levels; ++l) sig.inv_sigma2[l] = inv_level_sigma2[l];
+    const SigmaTab sig = sigma_tab(inv_level_sigma2, cam->n_levels);
     const dim3 grid((np + 255) / 256, K);
     if (g_fuse_lanes == 64) hipLaunchKernelGGL(k_fuse_batch<64>, grid, dim3(256), 0, m->stream, A, *cam, th, sig);
     else hipLaunchKernelGGL(k_fuse_batch<8>, grid, dim3(256), 0, m->stream, A, *cam, th, sig);
@@ -5461,14 +5459,14 @@ int orbhip_fuse_batch(orbhip_matcher *m, int K, const orbhip_frame_view *const *
     for (size_t i = 0; i < (size_t)K * n; ++i) { best_idx[i] = -1; best_dist[i] = 256; }
     // A key frame goes with the batch when the one launch computes what orbhip_fuse would for it: at most 4096 key
     // points and the grid / level count of the shared camera.  Any other takes the single-frame path for its row.
-    const float inv_w = (float)GRID_COLS / (cam->max_x - cam->min_x), inv_h = (float)GRID_ROWS / (cam->max_y - cam->min_y);
+    const GridInv inv = grid_inv(cam);
     std::vector<int> rows, single;
     int cap = 1;
     bool any_ur = false;
     for (int k = 0; k < K; ++k) {
         const orbhip_frame_view *f = kfs[k];
-        if (f->n <= kGridMax && f->min_x == cam->min_x && f->min_y == cam->min_y && f->grid_inv_w == inv_w &&
-            f->grid_inv_h == inv_h && f->n_levels == cam->n_levels) {
+        if (f->n <= kGridMax && f->min_x == cam->min_x && f->min_y == cam->min_y && f->grid_inv_w == inv.w &&
+            f->grid_inv_h == inv.h && f->n_levels == cam->n_levels) {
             rows.push_back(k);
             cap = std::max(cap, f->n);
             any_ur = any_ur || (f->u_right && f->n > 0);
