@@ -38,6 +38,11 @@
  *   orbhip_update_map_points*         the same and MapPoint::UpdateNormalAndDepth (:330-371) from an observation table
  *   orbhip_update_local_map*          Tracking::UpdateLocalKeyFrames / UpdateLocalPoints (src/Tracking.cc:1205-1339) over tables;
  *   orbhip_track_local_map_device     the same + SearchLocalPoints' frustum test and search (:1143-1193)
+ *   orbhip_update_connections*        KeyFrame::UpdateConnections (src/KeyFrame.cc:289-379) with AddConnection and
+ *                                     UpdateBestCovisibles (:123-157) over tables
+ *   orbhip_covisible_targets*         KeyFrame::GetBestCovisibilityKeyFrames (:174-182) and the target list of
+ *                                     LocalMapping::SearchInNeighbors (src/LocalMapping.cc:457-479)
+ *   orbhip_children_from_parents_device  mspChildrens of every row from mpParent and isBad()
  *   orbhip_vocabulary_*               ORBVocabulary (DBoW2::TemplatedVocabulary<FORB>) loadFromTextFile + transform,
  *                                     i.e. Frame::ComputeBoW (src/Frame.cc:395-402)
  *   orbhip_search_by_bow              ORBmatcher::SearchByBoW(KeyFrame*,Frame&,..) (src/ORBmatcher.cc:159-288) and
@@ -759,8 +764,8 @@ int orbhip_update_map_points(orbhip_matcher *m, const orbhip_camera *cam, int wh
 /* ---- local map: votes, local key frames, local points -----------------------------------------------------------------
  * Tracking::UpdateLocalKeyFrames (src/Tracking.cc:1231-1339), UpdateLocalPoints (:1205-1228) and the two loops in front of
  * SearchLocalPoints' search (:1146-1180) for `frames` current frames in one call, over tables.  The covisibility graph
- * (AddConnection, UpdateConnections, the parent / child links) stays with the caller, who passes it as tables like the
- * observation table.  Where the reference iterates a map<KeyFrame*, int> or a set<KeyFrame*> in heap-address order, the
+ * (covis, parent, child) is passed as tables like the observation table: orbhip_update_connections_device and
+ * orbhip_children_from_parents_device below maintain them on the device.  Where the reference iterates a map<KeyFrame*, int> or a set<KeyFrame*> in heap-address order, the
  * order here is the table's: ascending bank row for the vote map, the caller's order for the children.
  *
  * orbhip_local_map_tables (read only).  The key-frame bank has `rows` rows of `cap` slots, the map np points in arrays of pcap:
@@ -839,6 +844,85 @@ int orbhip_track_local_map_device(orbhip_matcher *m, int frames, int rows, int c
  * starting at or above 0, frame_n and n in [0, cap], n_local_kf in [0, rows]: ORBHIP_E_ARG. */
 int orbhip_update_local_map(orbhip_matcher *m, int frames, int rows, int cap, int np, int pcap,
                             const orbhip_local_map_tables *tables, const orbhip_local_map_io *io);
+
+/* ---- covisibility graph -----------------------------------------------------------------------------------------------
+ * KeyFrame::UpdateConnections (src/KeyFrame.cc:289-379) for the U bank rows of d_update_rows, with AddConnection (:123-136)
+ * and UpdateBestCovisibles (:138-157) on the rows it connects.  The result equals running it for each entry in list order;
+ * a row may come more than once.  The bank has `rows` rows of `cap` slots.
+ *
+ * orbhip_covis_tables (read only): slot_point [rows][cap] / n [rows], obs_start [np+1] / obs_kf, flags [pcap] as in
+ *   orbhip_local_map_tables (ORBHIP_POINT_PRESENT = !isBad()).
+ * orbhip_covis_state (in/out, owned by the caller, maintained by the call):
+ *   conn_w [rows][rows] int32 = mConnectedKeyFrameWeights of every row, dense; 0 = no entry (the reference never stores a
+ *     weight below 1).  GetWeight(c) of row r is conn_w[r][c].
+ *   ord_kf / ord_w [rows][rows] int32, n_ord [rows] int32 = mvpOrderedConnectedKeyFrames / mvOrderedWeights; a rewrite of a
+ *     list stores its n_ord[r] entries and nothing behind them.  GetCovisiblesByWeight(w) is the prefix of ord_kf[r] whose ord_w[r] is above w.
+ *   covis [rows][10] int32 = the head of ord_kf, -1 padded: the array orbhip_local_map_tables.covis reads.  Rewritten for
+ *     every row whose ordered list is rewritten.
+ *   first_conn [rows] uint8 = mbFirstConnection; parent [rows] int32 = mpParent, written on a first connection.
+ * id0_row: the row whose mnId is 0 (it never gets a parent, :371), or -1.
+ *
+ * Per updated row r.  Counter (:302-320): every slot i < n[r] with a present point adds 1 to counter[obs_kf[o]] for each of
+ * its observations with obs_kf[o] != r; a row repeated in a list counts each time; bad key frames are not skipped.  An empty
+ * counter (:323) writes nothing, first_conn stays, status ORBHIP_CONNECTIONS_EMPTY.  The qualifying rows are those with
+ * counter >= 15, or, if there are none, the first row in ascending order with the strictly largest count (:334-352).
+ * AddConnection(r, counter[c]) runs on every qualifying c: if conn_w[c][r] already equals the weight row c is left alone
+ * (the early return, :131-132), otherwise conn_w[c][r] is written and ALL entries of conn_w[c][:] are re-sorted into
+ * ord_kf[c] / ord_w[c] / n_ord[c] / covis[c].  The own row (:367-369): conn_w[r][:] becomes the WHOLE counter, entries below
+ * 15 included and old entries dropped, while ord_kf[r] / ord_w[r] hold ONLY the qualifying rows; the reference has this
+ * asymmetry, and it shows when a later AddConnection re-sorts row r from the full map.  Order of a list: the reference sorts
+ * pair<int, KeyFrame*> ascending and reverses, so equal weights go by heap address; here address order is row order, as for
+ * the vote map of the local map: descending weight, then descending row.  First connection (:371-376): if first_conn[r] and
+ * r != id0_row, parent[r] = ord_kf[r][0] and first_conn[r] = 0.
+ * d_report [U][8] int32 = {status, distinct voted rows, n_ord[r], row of the maximum (-1: none), the maximum, parent set
+ * (-1: not set), other rows re-sorted, 1 if the fallback to the maximum was used}.
+ *
+ * Asynchronous on the matcher's stream, no host synchronisation: one memset, two launches for the counters of all entries
+ * and one launch per entry.  rows, cap <= 4096 (ORBHIP_E_CAPACITY beyond: the state is dense, 3 x 64 MB there); rows, np or U
+ * negative, cap < 1, np > pcap, id0_row outside [-1, rows) or a null pointer: ORBHIP_E_ARG; all refused before any device
+ * work.  U == 0: success, nothing written.  The device form does not range-check the tables' contents. */
+#define ORBHIP_CONNECTIONS_OK    0
+#define ORBHIP_CONNECTIONS_EMPTY 1
+typedef struct orbhip_covis_tables {
+    const void *slot_point, *n, *obs_start, *obs_kf, *flags;
+} orbhip_covis_tables;
+typedef struct orbhip_covis_state {
+    void *conn_w, *ord_kf, *ord_w, *n_ord, *covis, *first_conn, *parent;
+} orbhip_covis_state;
+int orbhip_update_connections_device(orbhip_matcher *m, int rows, int cap, int np, int pcap, const orbhip_covis_tables *tables,
+                                     const orbhip_covis_state *state, int id0_row, int U, const void *d_update_rows,
+                                     void *d_report);
+/* Host buffers, synchronous: one staging copy, orbhip_update_connections_device, one read-back.  The records hold host
+ * pointers to the whole arrays, but only the rows the call can reach travel: the updated rows and the rows their points'
+ * observations name; every other row keeps its bytes.  It range-checks what the device form does not: update_rows and
+ * obs_kf in [0, rows), n and n_ord in [0, cap] / [0, rows], the point indices of the updated rows in [-1, np), obs_start
+ * non-decreasing from 0 or above: ORBHIP_E_ARG, before the handle is looked at. */
+int orbhip_update_connections(orbhip_matcher *m, int rows, int cap, int np, int pcap, const orbhip_covis_tables *tables,
+                              const orbhip_covis_state *state, int id0_row, int U, const int32_t *update_rows, int32_t *report);
+/* Readers of the graph, for Q current rows d_cur [Q], one wavefront each.
+ *   nn2 == 0: GetBestCovisibilityKeyFrames(nn) verbatim (:174-182), the neighbour list of CreateNewMapPoints
+ *     (src/LocalMapping.cc:210-213); bad rows are NOT skipped there.
+ *   nn2 > 0: vpTargetKFs of SearchInNeighbors (src/LocalMapping.cc:457-479; nn = 10 or 20, nn2 = 5 there).  A first
+ *     neighbour is skipped if bad or stamped (mnFuseTargetForKF), otherwise appended and stamped; then each of its nn2 best
+ *     covisibles is appended unless it is bad, stamped or the current row.  Second neighbours are not stamped, so a row can
+ *     come again, which orbhip_fuse_device allows.
+ * d_ord_kf [rows][rows] / d_n_ord [rows]: the state above; d_kf_bad [rows] uint8, nullable.  Outputs: d_targets
+ * [Q][nn * (1 + nn2)] int32, -1 behind the count, and d_counts [Q] int32: the lists are d_kf_index of
+ * orbhip_create_new_map_points_device / orbhip_fuse_device, whose K is a host integer, so the caller reads d_counts.
+ * rows <= 4096 (ORBHIP_E_CAPACITY); rows or Q negative, nn < 1, nn2 < 0, nn or nn2 above 4096 or a null pointer:
+ * ORBHIP_E_ARG.  Q == 0: success, nothing written. */
+int orbhip_covisible_targets_device(orbhip_matcher *m, int rows, const void *d_ord_kf, const void *d_n_ord, const void *d_kf_bad,
+                                    int Q, const void *d_cur, int nn, int nn2, void *d_targets, void *d_counts);
+/* Host buffers, synchronous; only the heads of the lists it walks travel.  Range-checked: cur and the entries it reads in
+ * [0, rows), n_ord in [0, rows]: ORBHIP_E_ARG, before the handle is looked at. */
+int orbhip_covisible_targets(orbhip_matcher *m, int rows, const int32_t *ord_kf, const int32_t *n_ord, const uint8_t *kf_bad,
+                             int Q, const int32_t *cur, int nn, int nn2, int32_t *targets, int32_t *counts);
+/* d_child_start [rows+1] / d_child [rows] (the CSR orbhip_local_map_tables reads) from d_parent [rows] and d_kf_bad [rows]
+ * (nullable): row c is a child of parent[c] iff 0 <= parent[c] < rows and c is not bad, because SetBadFlag erases itself from
+ * its parent (src/KeyFrame.cc:453-545); ascending row inside a list.  A first connection then needs no host edit of the CSR.
+ * rows <= 4096 (ORBHIP_E_CAPACITY). */
+int orbhip_children_from_parents_device(orbhip_matcher *m, int rows, const void *d_parent, const void *d_kf_bad,
+                                        void *d_child_start, void *d_child);
 
 /* ---- creating new map points -------------------------------------------------------------------------------------
  * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) for the current key frame and K neighbours in one call, up

@@ -705,6 +705,43 @@ public:
                                             nnratio), "orbhip_track_local_map_device");
     }
 
+    // KeyFrame::UpdateConnections (src/KeyFrame.cc:289-379) with AddConnection / UpdateBestCovisibles (:123-157) for the U
+    // bank rows of updateRows, in list order; the records, the order rules and the report are described at
+    // orbhip_update_connections_device in orbhip.h.  Host pointers, synchronous and range-checked: the rows of `state` the
+    // call reaches are updated in place, report [U][8] is written.
+    void UpdateConnections(int rows, int cap, int np, int pcap, const orbhip_covis_tables &tables, const orbhip_covis_state &state,
+                           int id0Row, int U, const int32_t *updateRows, int32_t *report)
+    {
+        check(orbhip_update_connections(m_, rows, cap, np, pcap, &tables, &state, id0Row, U, updateRows, report),
+              "orbhip_update_connections");
+    }
+    // device pointers, asynchronous on the matcher's stream, no range checks
+    void UpdateConnectionsDevice(int rows, int cap, int np, int pcap, const orbhip_covis_tables &dTables,
+                                 const orbhip_covis_state &dState, int id0Row, int U, const void *dUpdateRows, void *dReport)
+    {
+        check(orbhip_update_connections_device(m_, rows, cap, np, pcap, &dTables, &dState, id0Row, U, dUpdateRows, dReport),
+              "orbhip_update_connections_device");
+    }
+    // GetBestCovisibilityKeyFrames(nn) (nn2 == 0, :174-182) or vpTargetKFs of LocalMapping::SearchInNeighbors (nn2 > 0,
+    // src/LocalMapping.cc:457-479) for Q current rows: targets [Q][nn * (1 + nn2)], -1 behind counts [Q]
+    void CovisibleTargets(int rows, const int32_t *ordKf, const int32_t *nOrd, const uint8_t *kfBad, int Q, const int32_t *cur,
+                          int nn, int nn2, int32_t *targets, int32_t *counts)
+    {
+        check(orbhip_covisible_targets(m_, rows, ordKf, nOrd, kfBad, Q, cur, nn, nn2, targets, counts), "orbhip_covisible_targets");
+    }
+    void CovisibleTargetsDevice(int rows, const void *dOrdKf, const void *dNOrd, const void *dKfBad, int Q, const void *dCur, int nn,
+                                int nn2, void *dTargets, void *dCounts)
+    {
+        check(orbhip_covisible_targets_device(m_, rows, dOrdKf, dNOrd, dKfBad, Q, dCur, nn, nn2, dTargets, dCounts),
+              "orbhip_covisible_targets_device");
+    }
+    // mspChildrens of every row as CSR from mpParent and isBad(), ascending row inside a list
+    void ChildrenFromParentsDevice(int rows, const void *dParent, const void *dKfBad, void *dChildStart, void *dChild)
+    {
+        check(orbhip_children_from_parents_device(m_, rows, dParent, dKfBad, dChildStart, dChild),
+              "orbhip_children_from_parents_device");
+    }
+
     // the Frame statics the prologues read (src/Frame.cc:97-112), as one record
     static orbhip_camera MakeCamera(float fx, float fy, float cx, float cy, float mbf, float mb, float minX, float maxX, float minY,
                                     float maxY, const std::vector<float> &scaleFactors, float logScaleFactor)

@@ -58,6 +58,16 @@ class LocalMapTrack(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("Tcw", "kps", "desc", "u_right", "q", "assign", "nmatches")]
 
 
+class CovisTables(C.Structure):
+    """orbhip_covis_tables: the bank and map-point tables orbhip_update_connections* reads."""
+    _fields_ = [(k, C.c_void_p) for k in ("slot_point", "n", "obs_start", "obs_kf", "flags")]
+
+
+class CovisState(C.Structure):
+    """orbhip_covis_state: the covisibility graph orbhip_update_connections* maintains (in/out)."""
+    _fields_ = [(k, C.c_void_p) for k in ("conn_w", "ord_kf", "ord_w", "n_ord", "covis", "first_conn", "parent")]
+
+
 POINT_PRESENT, POINT_OBSERVED = 1, 2
 COLOR_BGR, COLOR_RGB = 0, 1
 DEPTH_U16, DEPTH_F32 = 0, 1
@@ -72,6 +82,9 @@ UPDATE_DESCRIPTOR, UPDATE_NORMAL_DEPTH = 1, 2
 # ORBHIP_LOCALMAP_*: report[0] (status) and report[5] (walk_end) of orbhip_update_local_map*
 LOCALMAP_OK, LOCALMAP_NO_VOTES, LOCALMAP_ALL_BAD = range(3)
 LOCALMAP_WALK_EXHAUSTED, LOCALMAP_WALK_LIMIT, LOCALMAP_WALK_PARENT = range(3)
+# ORBHIP_CONNECTIONS_*: report[0] of orbhip_update_connections*
+CONNECTIONS_OK, CONNECTIONS_EMPTY = range(2)
+CONNECTIONS_REPORT = ("status", "n_voted", "n_ordered", "max_row", "max_votes", "parent_set", "n_resorted", "fallback")
 REMAP_TABLE_SIZE = 4096
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
@@ -184,6 +197,12 @@ SYMBOLS = [
     ("orbhip_track_local_map_device", _i, [_vp, _i, _i, _i, _i, _i, C.POINTER(LocalMapTables), C.POINTER(LocalMapIO),
                                            C.POINTER(Camera), C.POINTER(LocalMapTrack), _f, _f, _f]),
     ("orbhip_update_local_map", _i, [_vp, _i, _i, _i, _i, _i, C.POINTER(LocalMapTables), C.POINTER(LocalMapIO)]),
+    ("orbhip_update_connections_device", _i, [_vp, _i, _i, _i, _i, C.POINTER(CovisTables), C.POINTER(CovisState), _i, _i, _vp,
+                                              _vp]),
+    ("orbhip_update_connections", _i, [_vp, _i, _i, _i, _i, C.POINTER(CovisTables), C.POINTER(CovisState), _i, _i, _vp, _vp]),
+    ("orbhip_covisible_targets_device", _i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    ("orbhip_covisible_targets", _i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    ("orbhip_children_from_parents_device", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
     ("orbhip_matcher_set_stream", _i, [_vp, _vp]),
     ("orbhip_matcher_sync", _i, [_vp]),
     ("orbhip_compute_stereo_matches_device", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,

@@ -84,6 +84,37 @@ int launch_local_map(hipStream_t stream, LocalMapArgs A, void *workspace);
 // n_to_match and F.mvpMapPoints[bestIdx] = pMP after the points search of orbhip_track_local_map_device
 int launch_local_map_apply(hipStream_t stream, int frames, int cap, int pcap, const void *q, const int *np_l, const int *frame_n,
                            const int *assign, const int *local_point, int *frame_point, int *report);
+
+// orbhip_covisibility.hip: the tables, the graph state and the workspace of orbhip_update_connections_device
+struct CovisArgs {
+    const int *slot_point, *n;          // [rows][cap], [rows]
+    const int *obs_start, *obs_kf;
+    const uint8_t *flags;               // [pcap]
+    int *conn_w, *ord_kf, *ord_w;       // [rows][rows] each, in/out
+    int *n_ord, *covis;                 // [rows], [rows][10]
+    uint8_t *first_conn;
+    int *parent;
+    // null: bank row c is row c of every array above.  The host entry keeps only the rows a call can reach on the device,
+    // row_slot[c] = where row c is (-1: not resident); the columns of conn_w / ord_* stay bank rows.
+    const int *row_slot;
+    const int *update_rows;             // [U]
+    int *report;                        // [U][8]
+    // workspace: counter [U][rows] (reset by the call), summary [U][4] = {voted rows, maximum, its row, rows >= 15}
+    int *counter, *summary;
+    int rows, cap, np, id0_row, U;
+};
+struct CovisTargetArgs {
+    const int *ord_kf, *n_ord;          // [rows][stride] (the head of each list), [rows]
+    const int *row_slot;                // as in CovisArgs
+    const uint8_t *kf_bad;              // [rows] or null
+    const int *cur;                     // [Q]
+    int *targets, *counts;              // [Q][nn * (1 + nn2)], [Q]
+    int rows, stride, nn, nn2;
+};
+size_t covis_workspace_bytes(int U, int rows);
+int launch_update_connections(hipStream_t stream, CovisArgs A, void *workspace);
+int launch_covisible_targets(hipStream_t stream, CovisTargetArgs A, int Q);
+int launch_children_from_parents(hipStream_t stream, int rows, const int *parent, const uint8_t *kf_bad, int *child_start, int *child);
 }  // namespace orbhip
 
 struct orbhip_extractor {

@@ -3717,8 +3717,8 @@ struct orbhip_matcher {
     hipStream_t stream = nullptr;       // stream every launch goes to
     hipStream_t own_stream = nullptr;   // created with the handle
     // grow-only device scratch
-    void *buf[18] = {};
-    size_t cap[18] = {};
+    void *buf[19] = {};
+    size_t cap[19] = {};
     bool lds_attr_set = false, bow_attr_set = false;
 #ifdef ORBHIP_DEVTOOLS
     int window_lanes = 0;               // development build: lanes per query of k_window_search forced to 16 / 64 (0: the rule)
@@ -3807,7 +3807,8 @@ static SigmaTab sigma_tab(const float *inv_level_sigma2, int n_levels)
     return sig;
 }
 
-enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_NSLOTS };
+enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_COVIS, S_NSLOTS };
+static_assert(S_NSLOTS == sizeof(orbhip_matcher::buf) / sizeof(void *), "one scratch buffer per slot");
 
 static int stage_begin(orbhip_matcher *m, size_t total, Stage *st)
 {
@@ -5289,6 +5290,250 @@ int orbhip_update_local_map(orbhip_matcher *m, int frames, int rows, int cap, in
     for (int i = 0; i < no; ++i)
         if (outs[i].bytes) memcpy(outs[i].host, h + ((const uint8_t *)outs[i].dev - (st.d + out_off)), outs[i].bytes);
     return ORBHIP_OK;
+}
+
+// ---- covisibility graph (kernels: orbhip_covisibility.hip) ------------------------------------------------------------
+static constexpr int kCovisMaxRows = 4096;
+
+// what both forms of orbhip_update_connections check, the handle aside
+static int update_connections_args(int rows, int cap, int np, int pcap, const orbhip_covis_tables *t, const orbhip_covis_state *s,
+                                   int id0_row, int U, const void *update_rows, const void *report)
+{
+    if (!t || !s || rows < 0 || np < 0 || pcap < 0 || np > pcap || cap < 1 || U < 0 || id0_row < -1 || id0_row >= std::max(rows, 0))
+        return ORBHIP_E_ARG;
+    if (cap > kGridMax) { set_error("update_connections: capacity %d exceeds %d", cap, kGridMax); return ORBHIP_E_CAPACITY; }
+    if (rows > kCovisMaxRows) { set_error("update_connections: %d bank rows exceed %d", rows, kCovisMaxRows); return ORBHIP_E_CAPACITY; }
+    if (U > 65536) { set_error("update_connections: %d list entries exceed 65536", U); return ORBHIP_E_CAPACITY; }
+    if (!t->slot_point || !t->n || !t->obs_start || !t->obs_kf || !t->flags || !s->conn_w || !s->ord_kf || !s->ord_w || !s->n_ord ||
+        !s->covis || !s->first_conn || !s->parent || !update_rows || !report)
+        return ORBHIP_E_ARG;
+    return ORBHIP_OK;
+}
+
+static int update_connections_launch(orbhip_matcher *m, int rows, int cap, int np, const orbhip_covis_tables *t,
+                                     const orbhip_covis_state *s, const int *d_row_slot, int id0_row, int U, const void *d_update_rows,
+                                     void *d_report)
+{
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    void *work;
+    if (int rc = scratch(m, S_COVIS, covis_workspace_bytes(U, rows), &work)) return rc;
+    CovisArgs A;
+    memset(&A, 0, sizeof(A));
+    A.slot_point = (const int *)t->slot_point; A.n = (const int *)t->n; A.obs_start = (const int *)t->obs_start;
+    A.obs_kf = (const int *)t->obs_kf; A.flags = (const uint8_t *)t->flags;
+    A.conn_w = (int *)s->conn_w; A.ord_kf = (int *)s->ord_kf; A.ord_w = (int *)s->ord_w; A.n_ord = (int *)s->n_ord;
+    A.covis = (int *)s->covis; A.first_conn = (uint8_t *)s->first_conn; A.parent = (int *)s->parent;
+    A.row_slot = d_row_slot; A.update_rows = (const int *)d_update_rows; A.report = (int *)d_report;
+    A.rows = rows; A.cap = cap; A.np = np; A.id0_row = id0_row; A.U = U;
+    return launch_update_connections(m->stream, A, work);
+}
+
+int orbhip_update_connections_device(orbhip_matcher *m, int rows, int cap, int np, int pcap, const orbhip_covis_tables *t,
+                                     const orbhip_covis_state *s, int id0_row, int U, const void *d_update_rows, void *d_report)
+{
+    if (int rc = update_connections_args(rows, cap, np, pcap, t, s, id0_row, U, d_update_rows, d_report)) return rc;
+    if (!m) return ORBHIP_E_ARG;
+    if (U == 0 || rows == 0) return ORBHIP_OK;
+    return update_connections_launch(m, rows, cap, np, t, s, nullptr, id0_row, U, d_update_rows, d_report);
+}
+
+int orbhip_update_connections(orbhip_matcher *m, int rows, int cap, int np, int pcap, const orbhip_covis_tables *t,
+                              const orbhip_covis_state *s, int id0_row, int U, const int32_t *update_rows, int32_t *report)
+{
+    if (int rc = update_connections_args(rows, cap, np, pcap, t, s, id0_row, U, update_rows, report)) return rc;
+    const int32_t *slot_point = (const int32_t *)t->slot_point, *n = (const int32_t *)t->n;
+    const int32_t *obs_start = (const int32_t *)t->obs_start, *obs_kf = (const int32_t *)t->obs_kf;
+    const uint8_t *flags = (const uint8_t *)t->flags;
+    int32_t *conn_w = (int32_t *)s->conn_w, *ord_kf = (int32_t *)s->ord_kf, *ord_w = (int32_t *)s->ord_w, *n_ord = (int32_t *)s->n_ord;
+    int32_t *covis = (int32_t *)s->covis, *parent = (int32_t *)s->parent;
+    uint8_t *first_conn = (uint8_t *)s->first_conn;
+    if (obs_start[0] < 0) { set_error("update_connections: obs_start starts below 0"); return ORBHIP_E_ARG; }
+    for (int p = 0; p < np; ++p)
+        if (obs_start[p + 1] < obs_start[p]) { set_error("update_connections: obs_start must be non-decreasing (entry %d)", p); return ORBHIP_E_ARG; }
+    const size_t nobs = (size_t)obs_start[np];
+    for (size_t o = 0; o < nobs; ++o)
+        if (obs_kf[o] < 0 || obs_kf[o] >= rows) { set_error("update_connections: observation %zu (row %d) is outside the bank", o, obs_kf[o]); return ORBHIP_E_ARG; }
+    for (int r = 0; r < rows; ++r) {
+        if (n[r] < 0 || n[r] > cap) { set_error("update_connections: bank row %d holds a count outside [0, cap]", r); return ORBHIP_E_ARG; }
+        if (n_ord[r] < 0 || n_ord[r] > rows) { set_error("update_connections: n_ord of bank row %d is outside [0, rows]", r); return ORBHIP_E_ARG; }
+    }
+    // the rows the call can reach: the updated rows and the rows their points' observations name
+    std::vector<int32_t> row_slot((size_t)rows, -1), resident;
+    auto reach = [&](int r) { if (row_slot[r] < 0) { row_slot[r] = (int32_t)resident.size(); resident.push_back(r); } };
+    for (int u = 0; u < U; ++u) {
+        const int r = update_rows[u];
+        if (r < 0 || r >= rows) { set_error("update_connections: list entry %d (row %d) is outside the bank", u, r); return ORBHIP_E_ARG; }
+        if (row_slot[r] >= 0) continue;                           // a repeat, or a row a point of an earlier entry named
+        reach(r);
+    }
+    const size_t n_updated = resident.size();                     // the updated rows come first
+    for (size_t k = 0; k < n_updated; ++k) {
+        const int r = resident[k];
+        for (int i = 0; i < n[r]; ++i) {
+            const int p = slot_point[(size_t)r * cap + i];
+            if (p < -1 || p >= np) { set_error("update_connections: bank row %d holds a point index out of range", r); return ORBHIP_E_ARG; }
+            if (p < 0 || !(flags[p] & ORBHIP_POINT_PRESENT)) continue;
+            for (int o = obs_start[p]; o < obs_start[p + 1]; ++o) reach(obs_kf[o]);
+        }
+    }
+    if (!m) return ORBHIP_E_ARG;
+    if (U == 0 || rows == 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const size_t R = (size_t)rows, Cp = (size_t)cap, T = resident.size(), Un = (size_t)U;
+    const size_t total = al256(R * 4) + al256(n_updated * Cp * 4) + al256(T * 4) + al256((size_t)np * 4 + 4) + al256(nobs * 4) +
+                         al256((size_t)np) + al256(Un * 4) + 3 * al256(T * R * 4) + 2 * al256(T * 4) + al256(T * 40) + al256(T) +
+                         al256(Un * 32);
+    Stage st;
+    int rc;
+    if ((rc = stage_begin(m, total, &st))) return rc;
+    orbhip_covis_tables dt;
+    orbhip_covis_state ds;
+    const int32_t *d_row_slot = st.put(row_slot.data(), R);
+    {   // slot rows of the updated rows only: they hold the first slots
+        const int32_t *d;
+        int32_t *h = st.take(n_updated * Cp, &d);
+        for (size_t k = 0; h && k < n_updated; ++k) memcpy(h + k * Cp, slot_point + (size_t)resident[k] * Cp, Cp * 4);
+        dt.slot_point = d;
+        h = st.take(T, &d);
+        for (size_t k = 0; h && k < T; ++k) h[k] = n[resident[k]];
+        dt.n = d;
+    }
+    dt.obs_start = st.put(obs_start, (size_t)np + 1);
+    dt.obs_kf = st.put(obs_kf, nobs);
+    dt.flags = st.put(flags, (size_t)np);
+    const int32_t *d_update = st.put(update_rows, Un);
+    // the state rows and the report next to each other: one copy brings all of them back
+    const size_t out_off = st.off;
+    const int32_t *d_cw, *d_okf, *d_ow, *d_no, *d_cv, *d_par, *d_rep;
+    const uint8_t *d_fc;
+    int32_t *h_cw = st.take(T * R, &d_cw), *h_okf = st.take(T * R, &d_okf), *h_ow = st.take(T * R, &d_ow);
+    int32_t *h_no = st.take(T, &d_no), *h_cv = st.take(T * 10, &d_cv);
+    uint8_t *h_fc = st.take(T, &d_fc);
+    int32_t *h_par = st.take(T, &d_par);
+    st.take(Un * 8, &d_rep);
+    if ((rc = st.status())) return rc;
+    for (size_t k = 0; k < T; ++k) {
+        const size_t r = (size_t)resident[k];
+        memcpy(h_cw + k * R, conn_w + r * R, R * 4);
+        memcpy(h_okf + k * R, ord_kf + r * R, R * 4);
+        memcpy(h_ow + k * R, ord_w + r * R, R * 4);
+        memcpy(h_cv + k * 10, covis + r * 10, 40);
+        h_no[k] = n_ord[r]; h_fc[k] = first_conn[r]; h_par[k] = parent[r];
+    }
+    ds.conn_w = (void *)d_cw; ds.ord_kf = (void *)d_okf; ds.ord_w = (void *)d_ow; ds.n_ord = (void *)d_no; ds.covis = (void *)d_cv;
+    ds.first_conn = (void *)d_fc; ds.parent = (void *)d_par;
+    const size_t out_bytes = st.off - out_off;
+    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = update_connections_launch(m, rows, cap, np, &dt, &ds, d_row_slot, id0_row, U, d_update, (void *)d_rep))) return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
+    auto back = [&](const void *dev) { return h + ((const uint8_t *)dev - (st.d + out_off)); };
+    for (size_t k = 0; k < T; ++k) {
+        const size_t r = (size_t)resident[k];
+        memcpy(conn_w + r * R, back(d_cw) + k * R * 4, R * 4);
+        memcpy(ord_kf + r * R, back(d_okf) + k * R * 4, R * 4);
+        memcpy(ord_w + r * R, back(d_ow) + k * R * 4, R * 4);
+        memcpy(covis + r * 10, back(d_cv) + k * 40, 40);
+        n_ord[r] = ((const int32_t *)back(d_no))[k];
+        first_conn[r] = back(d_fc)[k];
+        parent[r] = ((const int32_t *)back(d_par))[k];
+    }
+    memcpy(report, back(d_rep), Un * 32);
+    return ORBHIP_OK;
+}
+
+static int covisible_targets_args(int rows, const void *ord_kf, const void *n_ord, int Q, const void *cur, int nn, int nn2,
+                                  const void *targets, const void *counts)
+{
+    if (rows < 0 || Q < 0 || nn < 1 || nn2 < 0 || nn > kCovisMaxRows || nn2 > kCovisMaxRows || !ord_kf || !n_ord || !cur || !targets ||
+        !counts)
+        return ORBHIP_E_ARG;
+    if (rows > kCovisMaxRows) { set_error("covisible_targets: %d bank rows exceed %d", rows, kCovisMaxRows); return ORBHIP_E_CAPACITY; }
+    return ORBHIP_OK;
+}
+
+int orbhip_covisible_targets_device(orbhip_matcher *m, int rows, const void *d_ord_kf, const void *d_n_ord, const void *d_kf_bad,
+                                    int Q, const void *d_cur, int nn, int nn2, void *d_targets, void *d_counts)
+{
+    if (int rc = covisible_targets_args(rows, d_ord_kf, d_n_ord, Q, d_cur, nn, nn2, d_targets, d_counts)) return rc;
+    if (!m) return ORBHIP_E_ARG;
+    if (Q == 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    CovisTargetArgs A;
+    A.ord_kf = (const int *)d_ord_kf; A.n_ord = (const int *)d_n_ord; A.row_slot = nullptr; A.kf_bad = (const uint8_t *)d_kf_bad;
+    A.cur = (const int *)d_cur; A.targets = (int *)d_targets; A.counts = (int *)d_counts;
+    A.rows = rows; A.stride = rows; A.nn = nn; A.nn2 = nn2;
+    return launch_covisible_targets(m->stream, A, Q);
+}
+
+int orbhip_covisible_targets(orbhip_matcher *m, int rows, const int32_t *ord_kf, const int32_t *n_ord, const uint8_t *kf_bad, int Q,
+                             const int32_t *cur, int nn, int nn2, int32_t *targets, int32_t *counts)
+{
+    if (int rc = covisible_targets_args(rows, ord_kf, n_ord, Q, cur, nn, nn2, targets, counts)) return rc;
+    // the lists it walks: those of the current rows and, for the fuse targets, of their first nn entries
+    std::vector<int32_t> row_slot((size_t)rows, -1), resident;
+    auto reach = [&](int r, const char *what) {
+        if (r < 0 || r >= rows) { set_error("covisible_targets: %s (row %d) is outside the bank", what, r); return false; }
+        if (n_ord[r] < 0 || n_ord[r] > rows) { set_error("covisible_targets: n_ord of bank row %d is outside [0, rows]", r); return false; }
+        if (row_slot[r] < 0) { row_slot[r] = (int32_t)resident.size(); resident.push_back(r); }
+        return true;
+    };
+    for (int q = 0; q < Q; ++q) {
+        if (!reach(cur[q], "a current row")) return ORBHIP_E_ARG;
+        const int c = cur[q];
+        for (int v = 0; v < std::min(n_ord[c], nn); ++v) {
+            const int a = ord_kf[(size_t)c * rows + v];
+            if (!reach(a, "a first neighbour")) return ORBHIP_E_ARG;
+            for (int v2 = 0; nn2 > 0 && v2 < std::min(n_ord[a], nn2); ++v2) {
+                const int k2 = ord_kf[(size_t)a * rows + v2];
+                if (k2 < 0 || k2 >= rows) { set_error("covisible_targets: a second neighbour (row %d) is outside the bank", k2); return ORBHIP_E_ARG; }
+            }
+        }
+    }
+    if (!m) return ORBHIP_E_ARG;
+    if (Q == 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const size_t R = (size_t)rows, T = resident.size(), W = (size_t)std::min(std::max(nn, nn2), rows), Qn = (size_t)Q;
+    const size_t out_cap = (size_t)nn * (1 + (size_t)nn2);
+    const size_t total = al256(R * 4) + al256(T * W * 4) + al256(T * 4) + al256(R) + al256(Qn * 4) + al256(Qn * out_cap * 4) + al256(Qn * 4);
+    Stage st;
+    int rc;
+    if ((rc = stage_begin(m, total, &st))) return rc;
+    CovisTargetArgs A;
+    A.row_slot = st.put(row_slot.data(), R);
+    int32_t *h_head = st.take(T * W, &A.ord_kf), *h_no = st.take(T, &A.n_ord);
+    if ((rc = st.status())) return rc;
+    for (size_t k = 0; k < T; ++k) {
+        memcpy(h_head + k * W, ord_kf + (size_t)resident[k] * R, W * 4);
+        h_no[k] = n_ord[resident[k]];
+    }
+    A.kf_bad = kf_bad ? st.put(kf_bad, R) : nullptr;
+    A.cur = st.put(cur, Qn);
+    const size_t out_off = st.off;
+    const int32_t *d_t, *d_c;
+    st.take(Qn * out_cap, &d_t);
+    st.take(Qn, &d_c);
+    const size_t out_bytes = st.off - out_off;
+    if ((rc = stage_commit(m, &st))) return rc;
+    A.targets = (int *)d_t; A.counts = (int *)d_c;
+    A.rows = rows; A.stride = (int)W; A.nn = nn; A.nn2 = nn2;
+    if ((rc = launch_covisible_targets(m->stream, A, Q))) return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
+    memcpy(targets, h, Qn * out_cap * 4);
+    memcpy(counts, h + ((const uint8_t *)d_c - (st.d + out_off)), Qn * 4);
+    return ORBHIP_OK;
+}
+
+int orbhip_children_from_parents_device(orbhip_matcher *m, int rows, const void *d_parent, const void *d_kf_bad, void *d_child_start,
+                                        void *d_child)
+{
+    if (rows < 0 || !d_parent || !d_child_start || !d_child) return ORBHIP_E_ARG;
+    if (rows > kCovisMaxRows) { set_error("children_from_parents: %d bank rows exceed %d", rows, kCovisMaxRows); return ORBHIP_E_CAPACITY; }
+    if (!m) return ORBHIP_E_ARG;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    return launch_children_from_parents(m->stream, rows, (const int *)d_parent, (const uint8_t *)d_kf_bad, (int *)d_child_start,
+                                        (int *)d_child);
 }
 
 #ifdef ORBHIP_DEVTOOLS

@@ -471,6 +471,89 @@ class ORBmatcher:
                                                       float(np.float32(viewing_cos_limit)), float(np.float32(th)),
                                                       float(np.float32(nnratio))), "orbhip_track_local_map_device")
 
+    # -- covisibility graph (src/KeyFrame.cc:123-182, :289-379; src/LocalMapping.cc:457-479) -----------------------------
+    COVIS_TABLES = tuple(k for k, _ in capi.CovisTables._fields_)
+    COVIS_STATE = tuple(k for k, _ in capi.CovisState._fields_)
+
+    def UpdateConnections(self, tables, state, update_rows, id0_row=-1):
+        """KeyFrame::UpdateConnections for the bank rows of update_rows, in list order, from host arrays: `tables` is a
+        dict with the keys of COVIS_TABLES (slot_point [rows, cap], n [rows], obs_start [np+1], obs_kf, flags [pcap]),
+        `state` a dict with the keys of COVIS_STATE (conn_w / ord_kf / ord_w [rows, rows], n_ord [rows], covis [rows, 10],
+        first_conn [rows] uint8, parent [rows]).  One staged copy of the rows the call can reach, one device call, one
+        read-back; range-checked (OrbHipError with E_ARG).  Returns (state, report): updated copies of the seven arrays
+        (rows the call does not reach, and list entries past n_ord, as passed in) and report [U, 8] int32 in the order of
+        capi.CONNECTIONS_REPORT."""
+        i32, u8 = np.int32, np.uint8
+        T = {}
+        for k, dt in (("slot_point", i32), ("n", i32), ("obs_start", i32), ("obs_kf", i32), ("flags", u8)):
+            if tables.get(k) is None:
+                raise ValueError("tables[%r] is missing" % k)
+            T[k] = np.ascontiguousarray(tables[k], dt)
+        rows, pcap, n_pts = len(T["n"]), len(T["flags"]), len(T["obs_start"]) - 1
+        if T["slot_point"].ndim != 2 or T["slot_point"].shape[0] != rows or n_pts < 0 or n_pts > pcap or \
+                len(T["obs_kf"]) < max(int(T["obs_start"][-1]), 0):
+            raise ValueError("the covisibility tables do not agree on rows or pcap")
+        cap = T["slot_point"].shape[1]
+        S = {}
+        for k, dt, shape in (("conn_w", i32, (rows, rows)), ("ord_kf", i32, (rows, rows)), ("ord_w", i32, (rows, rows)),
+                             ("n_ord", i32, (rows,)), ("covis", i32, (rows, 10)), ("first_conn", u8, (rows,)),
+                             ("parent", i32, (rows,))):
+            if state.get(k) is None:
+                raise ValueError("state[%r] is missing" % k)
+            S[k] = np.array(state[k], dt, order="C").reshape(shape)
+        upd = np.ascontiguousarray(update_rows, i32).reshape(-1)
+        U = len(upd)
+        report = np.zeros((U, 8), i32)
+        keep = {k: (np.zeros(1, a.dtype) if a.size == 0 else a) for k, a in list(T.items()) + list(S.items())}
+        rt = self._record(capi.CovisTables, {k: ptr(keep[k]).value for k in self.COVIS_TABLES})
+        rs = self._record(capi.CovisState, {k: ptr(keep[k]).value for k in self.COVIS_STATE})
+        pad = [np.zeros(1, i32) if a.size == 0 else a for a in (upd, report)]      # never pass a null required pointer
+        check(self._lib.orbhip_update_connections(self._h, rows, cap, n_pts, pcap, C.byref(rt), C.byref(rs), int(id0_row), U,
+                                                  ptr(pad[0]), ptr(pad[1])), "orbhip_update_connections")
+        return S, report
+
+    def UpdateConnectionsDevice(self, rows, cap, np_, pcap, tables, state, id0_row, U, d_update_rows, d_report):
+        """Device-resident form (orbhip_update_connections_device in include/orbhip.h): `tables` and `state` are dicts with
+        the keys of COVIS_TABLES / COVIS_STATE holding device addresses (ints, or tensors).  Asynchronous on the matcher's
+        stream."""
+        rt = self._record(capi.CovisTables, tables)
+        rs = self._record(capi.CovisState, state)
+        check(self._lib.orbhip_update_connections_device(self._h, int(rows), int(cap), int(np_), int(pcap), C.byref(rt),
+                                                         C.byref(rs), int(id0_row), int(U), d_update_rows, d_report),
+              "orbhip_update_connections_device")
+
+    def CovisibleTargets(self, ord_kf, n_ord, cur, nn, nn2=0, kf_bad=None):
+        """GetBestCovisibilityKeyFrames(nn) of each row of `cur` (nn2 == 0: the neighbours of CreateNewMapPoints) or the
+        target list of SearchInNeighbors (nn2 > 0) from the host arrays ord_kf [rows, rows] / n_ord [rows] / kf_bad [rows].
+        Returns a list of int32 arrays, one per current row."""
+        i32 = np.int32
+        no = np.ascontiguousarray(n_ord, i32)
+        rows = len(no)
+        ok = np.ascontiguousarray(ord_kf, i32).reshape(rows, rows)
+        bad = None if kf_bad is None else np.ascontiguousarray(kf_bad, np.uint8)
+        if bad is not None and len(bad) != rows:
+            raise ValueError("kf_bad needs one entry per bank row")
+        c = np.ascontiguousarray(cur, i32).reshape(-1)
+        Q, width = len(c), max(int(nn), 0) * (1 + max(int(nn2), 0))
+        targets, counts = np.full((max(Q, 1), max(width, 1)), -1, i32), np.zeros(max(Q, 1), i32)
+        pad = [np.zeros(1, i32) if a.size == 0 else a for a in (ok, no, c)]
+        check(self._lib.orbhip_covisible_targets(self._h, rows, ptr(pad[0]), ptr(pad[1]), ptr(bad), Q, ptr(pad[2]), int(nn),
+                                                 int(nn2), ptr(targets), ptr(counts)), "orbhip_covisible_targets")
+        return [targets[q, :counts[q]].copy() for q in range(Q)]
+
+    def CovisibleTargetsDevice(self, rows, d_ord_kf, d_n_ord, d_kf_bad, Q, d_cur, nn, nn2, d_targets, d_counts):
+        """Device-resident form (orbhip_covisible_targets_device): d_targets [Q, nn * (1 + nn2)] int32, -1 behind the
+        count, and d_counts [Q].  K of the following CreateNewMapPointsDevice / FuseDevice call is a host integer, so the
+        caller reads d_counts.  Asynchronous on the matcher's stream."""
+        check(self._lib.orbhip_covisible_targets_device(self._h, int(rows), d_ord_kf, d_n_ord, d_kf_bad, int(Q), d_cur, int(nn),
+                                                        int(nn2), d_targets, d_counts), "orbhip_covisible_targets_device")
+
+    def ChildrenFromParentsDevice(self, rows, d_parent, d_kf_bad, d_child_start, d_child):
+        """d_child_start [rows + 1] / d_child [rows] from d_parent [rows] and d_kf_bad [rows] (0: no row is bad)
+        (orbhip_children_from_parents_device).  Asynchronous on the matcher's stream."""
+        check(self._lib.orbhip_children_from_parents_device(self._h, int(rows), d_parent, d_kf_bad, d_child_start, d_child),
+              "orbhip_children_from_parents_device")
+
     # -- device-resident, batched SearchByProjection ---------------------------
     def set_stream(self, stream):
         check(self._lib.orbhip_matcher_set_stream(self._h, stream), "orbhip_matcher_set_stream")
