@@ -43,6 +43,9 @@
  *   orbhip_covisible_targets*         KeyFrame::GetBestCovisibilityKeyFrames (:174-182) and the target list of
  *                                     LocalMapping::SearchInNeighbors (src/LocalMapping.cc:457-479)
  *   orbhip_children_from_parents_device  mspChildrens of every row from mpParent and isBad()
+ *   orbhip_cull_map_points*           LocalMapping::MapPointCulling (src/LocalMapping.cc:170-205) with MapPoint::SetBadFlag
+ *   orbhip_cull_key_frames*           LocalMapping::KeyFrameCulling (:632-696) with KeyFrame::SetBadFlag, EraseConnection
+ *                                     and MapPoint::EraseObservation, over tables
  *   orbhip_vocabulary_*               ORBVocabulary (DBoW2::TemplatedVocabulary<FORB>) loadFromTextFile + transform,
  *                                     i.e. Frame::ComputeBoW (src/Frame.cc:395-402)
  *   orbhip_search_by_bow              ORBmatcher::SearchByBoW(KeyFrame*,Frame&,..) (src/ORBmatcher.cc:159-288) and
@@ -923,6 +926,124 @@ int orbhip_covisible_targets(orbhip_matcher *m, int rows, const int32_t *ord_kf,
  * rows <= 4096 (ORBHIP_E_CAPACITY). */
 int orbhip_children_from_parents_device(orbhip_matcher *m, int rows, const void *d_parent, const void *d_kf_bad,
                                         void *d_child_start, void *d_child);
+
+/* ---- culling: MapPointCulling, KeyFrameCulling, SetBadFlag ------------------------------------------------------------
+ * The two steps of LocalMapping::Run that shrink the map, over the tables the entries above read and maintain.
+ * mObservations of a point is its list in the observation table of orbhip_update_map_points_device; both calls read the
+ * table IN and write the table OUT, the same lists in table order without the erased entries, into buffers the caller
+ * provides and then swaps in.  Lists are maps here: mObservations holds a key frame once, so these entries need every list
+ * to name a bank row at most once (the other entries tolerate repeats).  The host forms check that; the device forms do not,
+ * and a repeated row then leaves its second entry in the list.
+ *
+ * orbhip_cull_tables (read only): kps [rows][cap] orbhip_keypoint (mvKeysUn; only octave is read), u_right [rows][cap] float
+ *   (mvuRight; NULL = monocular: every observation counts 1), depth [rows][cap] float (mvDepth; may be NULL only with
+ *   mono != 0), n [rows] int32, obs_start [np+1] / obs_kf / obs_idx / ref_obs [np] int32 as orbhip_update_map_points_device
+ *   defines them (ref_obs is a position inside the point's own list), not_erase [rows] uint8 (mbNotErase; NULL = none).
+ *   orbhip_cull_map_points* reads u_right and the table only.
+ * orbhip_cull_io.  In/out: slot_point [rows][cap] int32, flags [pcap] uint8, kf_bad [rows] uint8, to_be_erased [rows] uint8
+ *   (mbToBeErased; needed when not_erase is given), child_start [rows+1] / child [rows] int32 (rewritten at the end as
+ *   orbhip_children_from_parents_device does).  Out: obs_start_out [np+1], obs_kf_out / obs_idx_out [obs_cap], ref_obs_out
+ *   [np] = the new position of the reference observation, -1 for an empty list or a ref_obs outside its list.  The out
+ *   buffers must not be the in buffers (ORBHIP_E_ARG).  orbhip_cull_map_points* uses slot_point, flags and the table out.
+ * obs_cap: entries of obs_kf / obs_idx and of their out buffers, at least obs_start[np]; it sizes the workspace, because the
+ *   device forms never read obs_start on the host.
+ *
+ * Observations() is not a caller array: a call derives it at its start as the sum over the list of (u_right[kf][idx] >= 0 ?
+ * 2 : 1), which is what AddObservation / EraseObservation maintain for a good point (src/MapPoint.cc:98-137).  A point that
+ * is not ORBHIP_POINT_PRESENT when the call starts has no observations (SetBadFlag cleared them): its list is dropped from
+ * the table out.  Where a call changes a count it rewrites ORBHIP_POINT_OBSERVED as count > 0; a point that turns bad loses
+ * ORBHIP_POINT_PRESENT only (SetBadFlag does not reset nObs).  MapPoint::SetBadFlag (:151-168): every observation (kf, idx)
+ * of the point is erased and slot_point[kf][idx] = -1, whatever that slot holds (EraseMapPointMatch is by index).
+ *
+ * orbhip_cull_map_points_device: d_recent [R] int32 = mlpRecentAddedMapPoints as point indices in list order, d_found /
+ *   d_visible / d_first_kf_id [pcap] int32 (mnFound, mnVisible, mnFirstKFid), cur_kf_id, th_obs (2 monocular, 3 otherwise).
+ *   Per entry, in the order of the reference's if / else if, d_status [R] uint8:
+ *     ORBHIP_CULLPOINT_ALREADY_BAD  isBad(): dropped;
+ *     ORBHIP_CULLPOINT_BAD_RATIO    (float)found / visible < 0.25f, evaluated as 4 * found < visible (equal for counts below
+ *                                   2^24; x / 0 is false both ways): SetBadFlag, dropped;
+ *     ORBHIP_CULLPOINT_BAD_OBS      cur_kf_id - first_kf_id >= 2 and Observations() <= th_obs: SetBadFlag, dropped;
+ *     ORBHIP_CULLPOINT_DROPPED_OLD  cur_kf_id - first_kf_id >= 3: dropped, not bad;
+ *     ORBHIP_CULLPOINT_KEPT.
+ *   d_recent_out [R] = the kept entries in order (entries behind the count keep the caller's bytes), d_n_recent_out [1].
+ *   A point listed twice belongs to its first entry: if that one culls it the later ones report ALREADY_BAD, as the
+ *   sequential loop does.  No entry's decision reads what another entry's SetBadFlag writes, so the loop is parallel.
+ *   Seven launches.  R == 0 (four launches and a memset): the table is still copied through, so the caller can swap
+ *   unconditionally.
+ *
+ * orbhip_cull_key_frames_device: d_cand [U] int32 = the reference's copy vpLocalKeyFrames (:638); -1 entries are skipped, so
+ *   the output of orbhip_covisible_targets_device(nn, 0) can be passed as it is.  The call copies the list first: it may be
+ *   ord_kf[cur], which the call itself re-sorts.  state: orbhip_covis_state; conn_w, ord_kf, ord_w, n_ord, covis and parent
+ *   are maintained, first_conn is not touched.  id0_row as in orbhip_update_connections_device; mono, th_depth = mbMonocular,
+ *   mThDepth.  The result equals running the loop for each candidate in list order against the state the candidates before
+ *   it left.
+ *   Decision (:643-694): r == id0_row is skipped.  Over slots i < n[r] holding a present point: unless mono, a slot with
+ *   depth > th_depth || depth < 0 is skipped; nMPs++; if Observations() > 3, the observations in rows other than r whose key
+ *   point's octave is <= octave(r, i) + 1 are counted, and the point is redundant at 3.  Cull iff nRedundant > 0.9 * nMPs,
+ *   evaluated as 10 * nRedundant > 9 * nMPs.
+ *   KeyFrame::SetBadFlag of a culled r (src/KeyFrame.cc:453-545): not_erase[r] sets to_be_erased[r] and nothing else.
+ *   Connections: for every c with conn_w[r][c] != 0 and conn_w[c][r] != 0, conn_w[c][r] is cleared and ALL of conn_w[c][:]
+ *   is re-sorted into ord_kf[c] / ord_w[c] / n_ord[c] / covis[c] with the order and dense-list rules of
+ *   orbhip_update_connections_device; a row r names but that does not name r (the own-row asymmetry) is left alone.
+ *   conn_w[r][r] must be 0, as UpdateConnections leaves it.  Points: every slot of r with a point index runs
+ *   EraseObservation(r) (src/MapPoint.cc:111-137): r's entry leaves the list, the count drops by 2 or 1, a reference
+ *   observation that was r's moves to the first entry left in table order, and at a count <= 2 the point turns bad.  r's own
+ *   slots keep their point indices.  Own row: conn_w[r][:] = 0, n_ord[r] = 0, covis[r] = -1 (ord_kf[r] / ord_w[r] keep
+ *   their bytes).  Spanning tree (:479-535): the children are the rows c with parent[c] == r that are not bad, in ascending
+ *   row; the candidates start as {parent[r]}; each round goes over the children in order and over ord_kf[c] in list order,
+ *   and the first strictly largest conn_w[c][entry] to a candidate wins: that child gets that parent and becomes a
+ *   candidate.  The children left when no pair is found get parent[r].  parent[r] itself stays.  A culled row without a
+ *   parent dereferences null in the reference; here the candidates start empty and the children left get -1.  Then
+ *   kf_bad[r] = 1.  A candidate that is already bad goes through all of this again, as in the reference.  mTcp,
+ *   Map::EraseKeyFrame and KeyFrameDatabase::erase stay with the caller.
+ *   d_report [U][8] int32 = {ORBHIP_CULLKF_* status, nMPs, nRedundant, observations erased (EraseObservation calls that
+ *   found an entry), points turned bad, other rows re-sorted, children of r, 1 if a child fell back to parent[r] or r had no
+ *   parent}; SKIPPED rows report zeros behind the status.
+ *   One launch at the start, then in stream order one for the first verdict and two per candidate (connections and points;
+ *   the spanning tree together with the next candidate's verdict, which reads nothing the tree writes), three for the
+ *   table and k_cv_children: 2 U + 6 (5 for U == 0).  The launches of a candidate that is not culled leave at once.  The
+ *   spanning tree is one wavefront and serial in the children of r.
+ *
+ * Both: asynchronous on the matcher's stream, no host synchronisation, no staging copy; the alive marks and counts live in
+ * the handle, grow on demand and are reset by every call.  rows, cap <= 4096 (ORBHIP_E_CAPACITY beyond).  Negative counts,
+ * cap < 1, np > pcap, id0_row outside [-1, rows), th_obs < 0, aliasing in/out tables or a null required pointer:
+ * ORBHIP_E_ARG, before any device work.  The device forms do not range-check the tables' contents. */
+#define ORBHIP_CULLPOINT_KEPT        0
+#define ORBHIP_CULLPOINT_ALREADY_BAD 1
+#define ORBHIP_CULLPOINT_BAD_RATIO   2
+#define ORBHIP_CULLPOINT_BAD_OBS     3
+#define ORBHIP_CULLPOINT_DROPPED_OLD 4
+#define ORBHIP_CULLKF_NOT_CULLED    0
+#define ORBHIP_CULLKF_CULLED        1
+#define ORBHIP_CULLKF_SKIPPED_ID0   2
+#define ORBHIP_CULLKF_SKIPPED_ENTRY 3
+#define ORBHIP_CULLKF_NOT_ERASE     4
+typedef struct orbhip_cull_tables {
+    const void *kps, *u_right, *depth, *n, *obs_start, *obs_kf, *obs_idx, *ref_obs, *not_erase;
+} orbhip_cull_tables;
+typedef struct orbhip_cull_io {
+    void *slot_point, *flags, *kf_bad, *to_be_erased, *child_start, *child;
+    void *obs_start_out, *obs_kf_out, *obs_idx_out, *ref_obs_out;
+} orbhip_cull_io;
+int orbhip_cull_map_points_device(orbhip_matcher *m, int rows, int cap, int np, int pcap, int obs_cap,
+                                  const orbhip_cull_tables *tables, const orbhip_cull_io *io, int R, const void *d_recent,
+                                  const void *d_found, const void *d_visible, const void *d_first_kf_id, int cur_kf_id, int th_obs,
+                                  void *d_recent_out, void *d_n_recent_out, void *d_status);
+int orbhip_cull_key_frames_device(orbhip_matcher *m, int rows, int cap, int np, int pcap, int obs_cap,
+                                  const orbhip_cull_tables *tables, const orbhip_cull_io *io, const orbhip_covis_state *state,
+                                  int id0_row, int U, const void *d_cand, int mono, float th_depth, void *d_report);
+/* Host buffers, synchronous: one staging copy, the device call, one read-back.  The records hold host pointers; in/out and
+ * output arrays come back whole (entries behind the counts as they were passed in).  They range-check what the device forms
+ * do not: obs_kf in [0, rows), obs_idx in [0, cap), a row at most once per list, obs_start non-decreasing from 0 with
+ * obs_start[np] <= obs_cap, point indices in [-1, np), n in [0, cap], n_ord in [0, rows] and its entries and parent inside
+ * the bank, candidates in [-1, rows) with a row at most once, recent in [0, np): ORBHIP_E_ARG, before the handle is looked
+ * at. */
+int orbhip_cull_map_points(orbhip_matcher *m, int rows, int cap, int np, int pcap, int obs_cap, const orbhip_cull_tables *tables,
+                           const orbhip_cull_io *io, int R, const int32_t *recent, const int32_t *found, const int32_t *visible,
+                           const int32_t *first_kf_id, int cur_kf_id, int th_obs, int32_t *recent_out, int32_t *n_recent_out,
+                           uint8_t *status);
+int orbhip_cull_key_frames(orbhip_matcher *m, int rows, int cap, int np, int pcap, int obs_cap, const orbhip_cull_tables *tables,
+                           const orbhip_cull_io *io, const orbhip_covis_state *state, int id0_row, int U, const int32_t *cand,
+                           int mono, float th_depth, int32_t *report);
 
 /* ---- creating new map points -------------------------------------------------------------------------------------
  * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) for the current key frame and K neighbours in one call, up

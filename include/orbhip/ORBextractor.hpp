@@ -742,6 +742,43 @@ public:
               "orbhip_children_from_parents_device");
     }
 
+    // LocalMapping::MapPointCulling (src/LocalMapping.cc:170-205) with MapPoint::SetBadFlag over the entries of `recent`; the
+    // records, the table out and the status codes are described at orbhip_cull_map_points_device in orbhip.h.  Host pointers,
+    // synchronous and range-checked: slot_point, flags and the table out of `io` are written, recentOut / nRecentOut hold
+    // the list left, status [R] one ORBHIP_CULLPOINT_* code per entry.
+    void CullMapPoints(int rows, int cap, int np, int pcap, int obsCap, const orbhip_cull_tables &tables, const orbhip_cull_io &io,
+                       int R, const int32_t *recent, const int32_t *found, const int32_t *visible, const int32_t *firstKfId,
+                       int curKfId, int thObs, int32_t *recentOut, int32_t *nRecentOut, uint8_t *status)
+    {
+        check(orbhip_cull_map_points(m_, rows, cap, np, pcap, obsCap, &tables, &io, R, recent, found, visible, firstKfId, curKfId,
+                                     thObs, recentOut, nRecentOut, status), "orbhip_cull_map_points");
+    }
+    // device pointers, asynchronous on the matcher's stream, no range checks
+    void CullMapPointsDevice(int rows, int cap, int np, int pcap, int obsCap, const orbhip_cull_tables &dTables,
+                             const orbhip_cull_io &dIo, int R, const void *dRecent, const void *dFound, const void *dVisible,
+                             const void *dFirstKfId, int curKfId, int thObs, void *dRecentOut, void *dNRecentOut, void *dStatus)
+    {
+        check(orbhip_cull_map_points_device(m_, rows, cap, np, pcap, obsCap, &dTables, &dIo, R, dRecent, dFound, dVisible, dFirstKfId,
+                                            curKfId, thObs, dRecentOut, dNRecentOut, dStatus), "orbhip_cull_map_points_device");
+    }
+    // LocalMapping::KeyFrameCulling (:632-696) with KeyFrame::SetBadFlag, EraseConnection and MapPoint::EraseObservation over
+    // the candidate rows `cand` (-1 entries are skipped), each decided against the state the candidates before it left;
+    // report [U][8] as described at orbhip_cull_key_frames_device in orbhip.h.  Host pointers, synchronous, range-checked.
+    void CullKeyFrames(int rows, int cap, int np, int pcap, int obsCap, const orbhip_cull_tables &tables, const orbhip_cull_io &io,
+                       const orbhip_covis_state &state, int id0Row, int U, const int32_t *cand, bool mono, float thDepth,
+                       int32_t *report)
+    {
+        check(orbhip_cull_key_frames(m_, rows, cap, np, pcap, obsCap, &tables, &io, &state, id0Row, U, cand, mono ? 1 : 0, thDepth,
+                                     report), "orbhip_cull_key_frames");
+    }
+    void CullKeyFramesDevice(int rows, int cap, int np, int pcap, int obsCap, const orbhip_cull_tables &dTables,
+                             const orbhip_cull_io &dIo, const orbhip_covis_state &dState, int id0Row, int U, const void *dCand,
+                             bool mono, float thDepth, void *dReport)
+    {
+        check(orbhip_cull_key_frames_device(m_, rows, cap, np, pcap, obsCap, &dTables, &dIo, &dState, id0Row, U, dCand, mono ? 1 : 0,
+                                            thDepth, dReport), "orbhip_cull_key_frames_device");
+    }
+
     // the Frame statics the prologues read (src/Frame.cc:97-112), as one record
     static orbhip_camera MakeCamera(float fx, float fy, float cx, float cy, float mbf, float mb, float minX, float maxX, float minY,
                                     float maxY, const std::vector<float> &scaleFactors, float logScaleFactor)

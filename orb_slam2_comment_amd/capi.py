@@ -68,6 +68,18 @@ class CovisState(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("conn_w", "ord_kf", "ord_w", "n_ord", "covis", "first_conn", "parent")]
 
 
+class CullTables(C.Structure):
+    """orbhip_cull_tables: what orbhip_cull_map_points* / orbhip_cull_key_frames* read."""
+    _fields_ = [(k, C.c_void_p) for k in ("kps", "u_right", "depth", "n", "obs_start", "obs_kf", "obs_idx", "ref_obs",
+                                          "not_erase")]
+
+
+class CullIO(C.Structure):
+    """orbhip_cull_io: the tables the culling entries maintain (in/out) and the observation table out."""
+    _fields_ = [(k, C.c_void_p) for k in ("slot_point", "flags", "kf_bad", "to_be_erased", "child_start", "child",
+                                          "obs_start_out", "obs_kf_out", "obs_idx_out", "ref_obs_out")]
+
+
 POINT_PRESENT, POINT_OBSERVED = 1, 2
 COLOR_BGR, COLOR_RGB = 0, 1
 DEPTH_U16, DEPTH_F32 = 0, 1
@@ -85,6 +97,10 @@ LOCALMAP_WALK_EXHAUSTED, LOCALMAP_WALK_LIMIT, LOCALMAP_WALK_PARENT = range(3)
 # ORBHIP_CONNECTIONS_*: report[0] of orbhip_update_connections*
 CONNECTIONS_OK, CONNECTIONS_EMPTY = range(2)
 CONNECTIONS_REPORT = ("status", "n_voted", "n_ordered", "max_row", "max_votes", "parent_set", "n_resorted", "fallback")
+# ORBHIP_CULLPOINT_*: d_status of orbhip_cull_map_points*; ORBHIP_CULLKF_*: report[0] of orbhip_cull_key_frames*
+CULLPOINT_KEPT, CULLPOINT_ALREADY_BAD, CULLPOINT_BAD_RATIO, CULLPOINT_BAD_OBS, CULLPOINT_DROPPED_OLD = range(5)
+CULLKF_NOT_CULLED, CULLKF_CULLED, CULLKF_SKIPPED_ID0, CULLKF_SKIPPED_ENTRY, CULLKF_NOT_ERASE = range(5)
+CULLKF_REPORT = ("status", "n_mps", "n_redundant", "n_erased", "n_bad", "n_resorted", "n_children", "fallback")
 REMAP_TABLE_SIZE = 4096
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
@@ -203,6 +219,14 @@ SYMBOLS = [
     ("orbhip_covisible_targets_device", _i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     ("orbhip_covisible_targets", _i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     ("orbhip_children_from_parents_device", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    ("orbhip_cull_map_points_device", _i, [_vp, _i, _i, _i, _i, _i, C.POINTER(CullTables), C.POINTER(CullIO), _i, _vp, _vp, _vp,
+                                           _vp, _i, _i, _vp, _vp, _vp]),
+    ("orbhip_cull_map_points", _i, [_vp, _i, _i, _i, _i, _i, C.POINTER(CullTables), C.POINTER(CullIO), _i, _vp, _vp, _vp, _vp, _i,
+                                    _i, _vp, _vp, _vp]),
+    ("orbhip_cull_key_frames_device", _i, [_vp, _i, _i, _i, _i, _i, C.POINTER(CullTables), C.POINTER(CullIO),
+                                           C.POINTER(CovisState), _i, _i, _vp, _i, _f, _vp]),
+    ("orbhip_cull_key_frames", _i, [_vp, _i, _i, _i, _i, _i, C.POINTER(CullTables), C.POINTER(CullIO), C.POINTER(CovisState), _i,
+                                    _i, _vp, _i, _f, _vp]),
     ("orbhip_matcher_set_stream", _i, [_vp, _vp]),
     ("orbhip_matcher_sync", _i, [_vp]),
     ("orbhip_compute_stereo_matches_device", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,

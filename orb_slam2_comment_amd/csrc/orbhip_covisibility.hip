@@ -89,13 +89,12 @@ __global__ __launch_bounds__(256) void k_cv_summary(CovisArgs A)
 }
 
 // Entry u of the list.  Workgroup c: AddConnection(r, counter[c]) on a qualifying row c (:123-136, :344, :351) with the
-// re-sort of all its entries (:138-157), or the own row (:354-376).  The list is a bitonic sort of weight << 32 | row in
-// LDS, descending: larger weight first, the higher row first among equal weights.
+// re-sort of all its entries (:138-157, cv_resort_row), or the own row (:354-376).
 __global__ __launch_bounds__(256) void k_cv_apply(CovisArgs A, int u)
 {
     __shared__ unsigned long long s_key[kCvMaxRows];
     __shared__ int s_cnt[4];
-    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, rows = A.rows;
+    const int c = blockIdx.x, tid = threadIdx.x, rows = A.rows;
     const int r = A.update_rows[u];
     if ((unsigned)r >= (unsigned)rows) return;
     const int *S = A.summary + (size_t)u * 4;
@@ -144,30 +143,9 @@ __global__ __launch_bounds__(256) void k_cv_apply(CovisArgs A, int u)
         }
         s_key[i] = key;
     }
-    mine = wave_sum(mine);
-    if (lane == 0) s_cnt[wv] = mine;
-    __syncthreads();
-    const int n_out = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    for (int k = 2; k <= N; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < N; i += 256) {
-                const int x = i ^ j;
-                if (x > i) {
-                    const unsigned long long a = s_key[i], b = s_key[x];
-                    if ((i & k) == 0 ? a < b : a > b) { s_key[i] = b; s_key[x] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    int *okf = A.ord_kf + (size_t)sc * rows, *ow = A.ord_w + (size_t)sc * rows;
-    for (int i = tid; i < n_out; i += 256) {
-        const unsigned long long key = s_key[i];
-        okf[i] = (int)(unsigned)key;
-        ow[i] = (int)(key >> 32);
-    }
-    if (tid < kCvCovis) A.covis[(size_t)sc * kCvCovis + tid] = tid < n_out ? (int)(unsigned)s_key[tid] : -1;
+    const int n_out = cv_resort_row(s_key, s_cnt, mine, N, A.ord_kf + (size_t)sc * rows, A.ord_w + (size_t)sc * rows,
+                                    A.covis + (size_t)sc * kCvCovis, A.n_ord + sc);
     if (tid != 0) return;
-    A.n_ord[sc] = n_out;
     if (!own) { atomicAdd(rep + 6, 1); return; }
     int parent_set = -1;
     if (A.first_conn[sc] && r != A.id0_row) {                              // :371-376

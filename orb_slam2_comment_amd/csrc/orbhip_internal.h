@@ -115,6 +115,72 @@ size_t covis_workspace_bytes(int U, int rows);
 int launch_update_connections(hipStream_t stream, CovisArgs A, void *workspace);
 int launch_covisible_targets(hipStream_t stream, CovisTargetArgs A, int Q);
 int launch_children_from_parents(hipStream_t stream, int rows, const int *parent, const uint8_t *kf_bad, int *child_start, int *child);
+
+// UpdateBestCovisibles (src/KeyFrame.cc:138-157) of one bank row by one workgroup of 256 threads, shared by k_cv_apply and
+// k_cull_apply.  The caller has filled s_key[0 .. N) (N the power of two at or above rows, at least 2) with
+// weight << 32 | row for the entries of the list and 0 elsewhere, and counted its own entries in `mine`.  A bitonic sort
+// in LDS, descending: larger weight first, the higher row first among equal weights.  It stores the n_out entries to
+// okf / ow and nothing behind them, the head to covis10, and n_out to *n_ord.  Returns n_out in every thread; s_key then
+// holds the sorted keys.
+__device__ __forceinline__ int cv_resort_row(unsigned long long *s_key, int *s_cnt, int mine, int N, int *okf, int *ow, int *covis10,
+                                             int *n_ord)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    mine = wave_sum(mine);
+    if (lane == 0) s_cnt[wv] = mine;
+    __syncthreads();
+    const int n_out = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    for (int k = 2; k <= N; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < N; i += 256) {
+                const int x = i ^ j;
+                if (x > i) {
+                    const unsigned long long a = s_key[i], b = s_key[x];
+                    if ((i & k) == 0 ? a < b : a > b) { s_key[i] = b; s_key[x] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    for (int i = tid; i < n_out; i += 256) {
+        const unsigned long long key = s_key[i];
+        okf[i] = (int)(unsigned)key;
+        ow[i] = (int)(key >> 32);
+    }
+    if (tid < 10) covis10[tid] = tid < n_out ? (int)(unsigned)s_key[tid] : -1;
+    if (tid == 0) *n_ord = n_out;
+    return n_out;
+}
+
+// orbhip_culling.hip: the tables, the graph state and the workspace of orbhip_cull_map_points_device /
+// orbhip_cull_key_frames_device
+struct CullArgs {
+    const orbhip_keypoint *kps;         // [rows][cap]
+    const float *u_right, *depth;       // [rows][cap], nullable
+    const int *n;                       // [rows]
+    const int *obs_start, *obs_kf, *obs_idx, *ref_obs;
+    const uint8_t *not_erase;           // [rows] or null
+    int *slot_point;                    // [rows][cap], in/out
+    uint8_t *flags, *kf_bad, *to_be_erased;
+    int *conn_w, *ord_kf, *ord_w, *n_ord, *covis, *parent;
+    int *child_start, *child;
+    int *obs_start_out, *obs_kf_out, *obs_idx_out, *ref_obs_out;
+    // map points
+    const int *recent, *found, *visible, *first_kf_id;
+    int *recent_out, *n_recent_out;
+    uint8_t *status;
+    // key frames
+    const int *cand_in;                 // [U]
+    int *report;                        // [U][8]
+    // workspace, reset by every call: nobs [np] = Observations(), alive [obs_cap] (1 = the entry is in mObservations),
+    // ref_cur [np] = position of mpRefKF's entry in the list as passed in (-1: none), owner [np] = first list position of a
+    // recent point, cand [U] = the call's copy of the list, verdict [U]
+    int *nobs, *alive, *ref_cur, *owner, *cand, *verdict;
+    int rows, cap, np, obs_cap, id0_row, U, R, cur_kf_id, th_obs, mono;
+    float th_depth;
+};
+size_t cull_workspace_bytes(int np, int obs_cap, int U);
+int launch_cull_map_points(hipStream_t stream, CullArgs A, void *workspace);
+int launch_cull_key_frames(hipStream_t stream, CullArgs A, void *workspace);
 }  // namespace orbhip
 
 struct orbhip_extractor {

@@ -3717,8 +3717,8 @@ struct orbhip_matcher {
     hipStream_t stream = nullptr;       // stream every launch goes to
     hipStream_t own_stream = nullptr;   // created with the handle
     // grow-only device scratch
-    void *buf[19] = {};
-    size_t cap[19] = {};
+    void *buf[20] = {};
+    size_t cap[20] = {};
     bool lds_attr_set = false, bow_attr_set = false;
 #ifdef ORBHIP_DEVTOOLS
     int window_lanes = 0;               // development build: lanes per query of k_window_search forced to 16 / 64 (0: the rule)
@@ -3807,7 +3807,7 @@ static SigmaTab sigma_tab(const float *inv_level_sigma2, int n_levels)
     return sig;
 }
 
-enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_COVIS, S_NSLOTS };
+enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_COVIS, S_CULL, S_NSLOTS };
 static_assert(S_NSLOTS == sizeof(orbhip_matcher::buf) / sizeof(void *), "one scratch buffer per slot");
 
 static int stage_begin(orbhip_matcher *m, size_t total, Stage *st)
@@ -5534,6 +5534,299 @@ int orbhip_children_from_parents_device(orbhip_matcher *m, int rows, const void 
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     return launch_children_from_parents(m->stream, rows, (const int *)d_parent, (const uint8_t *)d_kf_bad, (int *)d_child_start,
                                         (int *)d_child);
+}
+
+// ---- culling (kernels: orbhip_culling.hip) ----------------------------------------------------------------------------
+// what every form of the two culling entries checks, the handle aside; kf: orbhip_cull_key_frames*
+static int cull_args(const char *who, bool kf, int rows, int cap, int np, int pcap, int obs_cap, const orbhip_cull_tables *t,
+                     const orbhip_cull_io *io)
+{
+    if (!t || !io || rows < 0 || np < 0 || pcap < 0 || np > pcap || cap < 1 || obs_cap < 0) return ORBHIP_E_ARG;
+    if (cap > kGridMax) { set_error("%s: capacity %d exceeds %d", who, cap, kGridMax); return ORBHIP_E_CAPACITY; }
+    if (rows > kCovisMaxRows) { set_error("%s: %d bank rows exceed %d", who, rows, kCovisMaxRows); return ORBHIP_E_CAPACITY; }
+    if (!t->obs_start || !t->obs_kf || !t->obs_idx || !t->ref_obs || !io->slot_point || !io->flags || !io->obs_start_out ||
+        !io->obs_kf_out || !io->obs_idx_out || !io->ref_obs_out)
+        return ORBHIP_E_ARG;
+    if (io->obs_start_out == t->obs_start || io->obs_kf_out == t->obs_kf || io->obs_idx_out == t->obs_idx || io->ref_obs_out == t->ref_obs) {
+        set_error("%s: the observation table out must not alias the table in", who);
+        return ORBHIP_E_ARG;
+    }
+    if (kf && (!t->kps || !t->n || !io->kf_bad || !io->child_start || !io->child || (t->not_erase && !io->to_be_erased)))
+        return ORBHIP_E_ARG;
+    return ORBHIP_OK;
+}
+
+static void cull_common(CullArgs &A, int rows, int cap, int np, int obs_cap, const orbhip_cull_tables *t, const orbhip_cull_io *io)
+{
+    memset(&A, 0, sizeof(A));
+    A.kps = (const orbhip_keypoint *)t->kps; A.u_right = (const float *)t->u_right; A.depth = (const float *)t->depth;
+    A.n = (const int *)t->n; A.obs_start = (const int *)t->obs_start; A.obs_kf = (const int *)t->obs_kf;
+    A.obs_idx = (const int *)t->obs_idx; A.ref_obs = (const int *)t->ref_obs; A.not_erase = (const uint8_t *)t->not_erase;
+    A.slot_point = (int *)io->slot_point; A.flags = (uint8_t *)io->flags; A.kf_bad = (uint8_t *)io->kf_bad;
+    A.to_be_erased = (uint8_t *)io->to_be_erased; A.child_start = (int *)io->child_start; A.child = (int *)io->child;
+    A.obs_start_out = (int *)io->obs_start_out; A.obs_kf_out = (int *)io->obs_kf_out; A.obs_idx_out = (int *)io->obs_idx_out;
+    A.ref_obs_out = (int *)io->ref_obs_out;
+    A.rows = rows; A.cap = cap; A.np = np; A.obs_cap = obs_cap; A.id0_row = -1;
+}
+
+static int cull_map_points_args(int rows, int cap, int np, int pcap, int obs_cap, const orbhip_cull_tables *t, const orbhip_cull_io *io,
+                                int R, const void *recent, const void *found, const void *visible, const void *first_kf_id, int th_obs,
+                                const void *recent_out, const void *n_recent_out, const void *status)
+{
+    if (int rc = cull_args("cull_map_points", false, rows, cap, np, pcap, obs_cap, t, io)) return rc;
+    if (R < 0 || th_obs < 0 || !recent || !found || !visible || !first_kf_id || !recent_out || !n_recent_out || !status) return ORBHIP_E_ARG;
+    return ORBHIP_OK;
+}
+
+static int cull_map_points_launch(orbhip_matcher *m, int rows, int cap, int np, int obs_cap, const orbhip_cull_tables *t,
+                                  const orbhip_cull_io *io, int R, const void *d_recent, const void *d_found, const void *d_visible,
+                                  const void *d_first_kf_id, int cur_kf_id, int th_obs, void *d_recent_out, void *d_n_recent_out,
+                                  void *d_status)
+{
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    void *work;
+    if (int rc = scratch(m, S_CULL, cull_workspace_bytes(np, obs_cap, 0), &work)) return rc;
+    CullArgs A;
+    cull_common(A, rows, cap, np, obs_cap, t, io);
+    A.recent = (const int *)d_recent; A.found = (const int *)d_found; A.visible = (const int *)d_visible;
+    A.first_kf_id = (const int *)d_first_kf_id; A.recent_out = (int *)d_recent_out; A.n_recent_out = (int *)d_n_recent_out;
+    A.status = (uint8_t *)d_status; A.R = R; A.cur_kf_id = cur_kf_id; A.th_obs = th_obs;
+    return launch_cull_map_points(m->stream, A, work);
+}
+
+int orbhip_cull_map_points_device(orbhip_matcher *m, int rows, int cap, int np, int pcap, int obs_cap, const orbhip_cull_tables *t,
+                                  const orbhip_cull_io *io, int R, const void *d_recent, const void *d_found, const void *d_visible,
+                                  const void *d_first_kf_id, int cur_kf_id, int th_obs, void *d_recent_out, void *d_n_recent_out,
+                                  void *d_status)
+{
+    if (int rc = cull_map_points_args(rows, cap, np, pcap, obs_cap, t, io, R, d_recent, d_found, d_visible, d_first_kf_id, th_obs,
+                                      d_recent_out, d_n_recent_out, d_status))
+        return rc;
+    if (!m) return ORBHIP_E_ARG;
+    return cull_map_points_launch(m, rows, cap, np, obs_cap, t, io, R, d_recent, d_found, d_visible, d_first_kf_id, cur_kf_id, th_obs,
+                                  d_recent_out, d_n_recent_out, d_status);
+}
+
+static int cull_key_frames_args(int rows, int cap, int np, int pcap, int obs_cap, const orbhip_cull_tables *t, const orbhip_cull_io *io,
+                                const orbhip_covis_state *s, int id0_row, int U, const void *cand, int mono, const void *report)
+{
+    if (int rc = cull_args("cull_key_frames", true, rows, cap, np, pcap, obs_cap, t, io)) return rc;
+    if (!s || U < 0 || id0_row < -1 || id0_row >= std::max(rows, 0) || !cand || !report || (!mono && !t->depth)) return ORBHIP_E_ARG;
+    if (U > 65536) { set_error("cull_key_frames: %d candidates exceed 65536", U); return ORBHIP_E_CAPACITY; }
+    if (!s->conn_w || !s->ord_kf || !s->ord_w || !s->n_ord || !s->covis || !s->parent) return ORBHIP_E_ARG;
+    return ORBHIP_OK;
+}
+
+static int cull_key_frames_launch(orbhip_matcher *m, int rows, int cap, int np, int obs_cap, const orbhip_cull_tables *t,
+                                  const orbhip_cull_io *io, const orbhip_covis_state *s, int id0_row, int U, const void *d_cand, int mono,
+                                  float th_depth, void *d_report)
+{
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    void *work;
+    if (int rc = scratch(m, S_CULL, cull_workspace_bytes(np, obs_cap, U), &work)) return rc;
+    CullArgs A;
+    cull_common(A, rows, cap, np, obs_cap, t, io);
+    A.conn_w = (int *)s->conn_w; A.ord_kf = (int *)s->ord_kf; A.ord_w = (int *)s->ord_w; A.n_ord = (int *)s->n_ord;
+    A.covis = (int *)s->covis; A.parent = (int *)s->parent;
+    A.cand_in = (const int *)d_cand; A.report = (int *)d_report; A.id0_row = id0_row; A.U = U; A.mono = mono != 0; A.th_depth = th_depth;
+    return launch_cull_key_frames(m->stream, A, work);
+}
+
+int orbhip_cull_key_frames_device(orbhip_matcher *m, int rows, int cap, int np, int pcap, int obs_cap, const orbhip_cull_tables *t,
+                                  const orbhip_cull_io *io, const orbhip_covis_state *s, int id0_row, int U, const void *d_cand, int mono,
+                                  float th_depth, void *d_report)
+{
+    if (int rc = cull_key_frames_args(rows, cap, np, pcap, obs_cap, t, io, s, id0_row, U, d_cand, mono, d_report)) return rc;
+    if (!m) return ORBHIP_E_ARG;
+    return cull_key_frames_launch(m, rows, cap, np, obs_cap, t, io, s, id0_row, U, d_cand, mono, th_depth, d_report);
+}
+
+// what the host forms range-check in the tables both calls share; *total = obs_start[np]
+static int cull_check_tables(const char *who, int rows, int cap, int np, int obs_cap, const orbhip_cull_tables *t, const orbhip_cull_io *io,
+                             size_t *total)
+{
+    const int32_t *obs_start = (const int32_t *)t->obs_start, *obs_kf = (const int32_t *)t->obs_kf, *obs_idx = (const int32_t *)t->obs_idx;
+    if (obs_start[0] != 0) { set_error("%s: obs_start must start at 0", who); return ORBHIP_E_ARG; }
+    for (int p = 0; p < np; ++p)
+        if (obs_start[p + 1] < obs_start[p]) { set_error("%s: obs_start must be non-decreasing (entry %d)", who, p); return ORBHIP_E_ARG; }
+    if (obs_start[np] > obs_cap) { set_error("%s: the table holds %d entries, obs_cap is %d", who, obs_start[np], obs_cap); return ORBHIP_E_ARG; }
+    *total = (size_t)obs_start[np];
+    std::vector<int32_t> seen((size_t)rows, -1);
+    for (int p = 0; p < np; ++p)
+        for (int o = obs_start[p]; o < obs_start[p + 1]; ++o) {
+            const int k = obs_kf[o];
+            if (k < 0 || k >= rows || obs_idx[o] < 0 || obs_idx[o] >= cap) { set_error("%s: observation %d (row %d, key point %d) is outside the bank", who, o, k, obs_idx[o]); return ORBHIP_E_ARG; }
+            if (seen[k] == p) { set_error("%s: the list of point %d names bank row %d twice", who, p, k); return ORBHIP_E_ARG; }
+            seen[k] = p;
+        }
+    const int32_t *slot_point = (const int32_t *)io->slot_point;
+    for (size_t i = 0; i < (size_t)rows * cap; ++i)
+        if (slot_point[i] < -1 || slot_point[i] >= np) { set_error("%s: bank row %zu holds a point index out of range", who, i / cap); return ORBHIP_E_ARG; }
+    return ORBHIP_OK;
+}
+
+// the tables both host forms stage; `outs` collects what travels back
+struct CullOut { void *host; const void *dev; size_t bytes; };
+static void cull_stage_tables(Stage &st, int rows, int cap, int np, int pcap, int obs_cap, size_t total, const orbhip_cull_tables *t,
+                              orbhip_cull_tables *dt)
+{
+    const size_t RC = (size_t)rows * cap;
+    memset(dt, 0, sizeof(*dt));
+    if (t->kps) dt->kps = st.put((const orbhip_keypoint *)t->kps, RC);
+    if (t->u_right) dt->u_right = st.put((const float *)t->u_right, RC);
+    if (t->depth) dt->depth = st.put((const float *)t->depth, RC);
+    if (t->n) dt->n = st.put((const int32_t *)t->n, (size_t)rows);
+    dt->obs_start = st.put((const int32_t *)t->obs_start, (size_t)np + 1);
+    dt->obs_kf = st.put((const int32_t *)t->obs_kf, total);
+    dt->obs_idx = st.put((const int32_t *)t->obs_idx, total);
+    dt->ref_obs = st.put((const int32_t *)t->ref_obs, (size_t)np);
+    if (t->not_erase) dt->not_erase = st.put((const uint8_t *)t->not_erase, (size_t)rows);
+    (void)pcap; (void)obs_cap;
+}
+static size_t cull_stage_bytes(int rows, int cap, int np, int obs_cap)
+{
+    const size_t RC = (size_t)rows * cap, R = (size_t)rows, P = (size_t)np, O = (size_t)obs_cap;
+    return al256(RC * sizeof(orbhip_keypoint)) + 3 * al256(RC * 4) + 8 * al256(R * 4 + 4) + 4 * al256(P * 4 + 4) + al256(P) + 4 * al256(O * 4) +
+           3 * al256(R * R * 4) + al256(R * 40);
+}
+
+int orbhip_cull_map_points(orbhip_matcher *m, int rows, int cap, int np, int pcap, int obs_cap, const orbhip_cull_tables *t,
+                           const orbhip_cull_io *io, int R, const int32_t *recent, const int32_t *found, const int32_t *visible,
+                           const int32_t *first_kf_id, int cur_kf_id, int th_obs, int32_t *recent_out, int32_t *n_recent_out,
+                           uint8_t *status)
+{
+    if (int rc = cull_map_points_args(rows, cap, np, pcap, obs_cap, t, io, R, recent, found, visible, first_kf_id, th_obs, recent_out,
+                                      n_recent_out, status))
+        return rc;
+    size_t total;
+    if (int rc = cull_check_tables("cull_map_points", rows, cap, np, obs_cap, t, io, &total)) return rc;
+    for (int e = 0; e < R; ++e)
+        if (recent[e] < 0 || recent[e] >= np) { set_error("cull_map_points: list entry %d (point %d) is outside the map", e, recent[e]); return ORBHIP_E_ARG; }
+    if (!m) return ORBHIP_E_ARG;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const size_t RC = (size_t)rows * cap, P = (size_t)np, Rn = (size_t)R;
+    Stage st;
+    int rc;
+    if ((rc = stage_begin(m, cull_stage_bytes(rows, cap, np, obs_cap) + 6 * al256(Rn * 4 + 4) + 3 * al256(P * 4), &st))) return rc;
+    orbhip_cull_tables dt;
+    orbhip_cull_io dio;
+    memset(&dio, 0, sizeof(dio));
+    orbhip_cull_tables th = *t;
+    th.kps = nullptr; th.depth = nullptr; th.n = nullptr; th.not_erase = nullptr;       // not read by this call
+    cull_stage_tables(st, rows, cap, np, pcap, obs_cap, total, &th, &dt);
+    const int32_t *d_recent = st.put(recent, Rn), *d_found = st.put(found, P), *d_visible = st.put(visible, P);
+    const int32_t *d_first = st.put(first_kf_id, P);
+    const size_t out_off = st.off;
+    CullOut outs[9];
+    int no = 0;
+    auto inout = [&](void *host, size_t bytes) {
+        const uint8_t *d = st.put((const uint8_t *)host, bytes);
+        outs[no++] = {host, d, bytes};
+        return (void *)d;
+    };
+    auto out = [&](void *host, size_t bytes) {
+        const uint8_t *d;
+        st.take(bytes, &d);
+        outs[no++] = {host, d, bytes};
+        return (void *)d;
+    };
+    dio.slot_point = inout(io->slot_point, RC * 4);
+    dio.flags = inout(io->flags, P);
+    dio.obs_start_out = out(io->obs_start_out, (P + 1) * 4);
+    dio.obs_kf_out = inout(io->obs_kf_out, total * 4);
+    dio.obs_idx_out = inout(io->obs_idx_out, total * 4);
+    dio.ref_obs_out = out(io->ref_obs_out, P * 4);
+    void *d_recent_out = inout(recent_out, Rn * 4), *d_n_out = out(n_recent_out, 4), *d_status = out(status, Rn);
+    const size_t out_bytes = st.off - out_off;
+    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = cull_map_points_launch(m, rows, cap, np, obs_cap, &dt, &dio, R, d_recent, d_found, d_visible, d_first, cur_kf_id, th_obs,
+                                     d_recent_out, d_n_out, d_status)))
+        return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
+    for (int i = 0; i < no; ++i)
+        if (outs[i].bytes) memcpy(outs[i].host, h + ((const uint8_t *)outs[i].dev - (st.d + out_off)), outs[i].bytes);
+    return ORBHIP_OK;
+}
+
+int orbhip_cull_key_frames(orbhip_matcher *m, int rows, int cap, int np, int pcap, int obs_cap, const orbhip_cull_tables *t,
+                           const orbhip_cull_io *io, const orbhip_covis_state *s, int id0_row, int U, const int32_t *cand, int mono,
+                           float th_depth, int32_t *report)
+{
+    if (int rc = cull_key_frames_args(rows, cap, np, pcap, obs_cap, t, io, s, id0_row, U, cand, mono, report)) return rc;
+    size_t total;
+    if (int rc = cull_check_tables("cull_key_frames", rows, cap, np, obs_cap, t, io, &total)) return rc;
+    const int32_t *n = (const int32_t *)t->n, *n_ord = (const int32_t *)s->n_ord, *ord_kf = (const int32_t *)s->ord_kf;
+    const int32_t *parent = (const int32_t *)s->parent;
+    for (int r = 0; r < rows; ++r) {
+        if (n[r] < 0 || n[r] > cap) { set_error("cull_key_frames: bank row %d holds a count outside [0, cap]", r); return ORBHIP_E_ARG; }
+        if (n_ord[r] < 0 || n_ord[r] > rows) { set_error("cull_key_frames: n_ord of bank row %d is outside [0, rows]", r); return ORBHIP_E_ARG; }
+        if (parent[r] < -1 || parent[r] >= rows) { set_error("cull_key_frames: the parent of bank row %d is outside the bank", r); return ORBHIP_E_ARG; }
+        for (int i = 0; i < n_ord[r]; ++i)
+            if (ord_kf[(size_t)r * rows + i] < 0 || ord_kf[(size_t)r * rows + i] >= rows) { set_error("cull_key_frames: the ordered list of bank row %d names a row outside the bank", r); return ORBHIP_E_ARG; }
+    }
+    {
+        std::vector<uint8_t> seen((size_t)rows, 0);
+        for (int u = 0; u < U; ++u) {
+            const int r = cand[u];
+            if (r < -1 || r >= rows) { set_error("cull_key_frames: candidate %d (row %d) is outside the bank", u, r); return ORBHIP_E_ARG; }
+            if (r < 0) continue;
+            if (seen[r]) { set_error("cull_key_frames: the candidate list names bank row %d twice", r); return ORBHIP_E_ARG; }
+            seen[r] = 1;
+        }
+    }
+    if (!m) return ORBHIP_E_ARG;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const size_t RC = (size_t)rows * cap, P = (size_t)np, Rw = (size_t)rows, Un = (size_t)U;
+    Stage st;
+    int rc;
+    if ((rc = stage_begin(m, cull_stage_bytes(rows, cap, np, obs_cap) + al256(Un * 4 + 4) + al256(Un * 32), &st))) return rc;
+    orbhip_cull_tables dt;
+    orbhip_cull_io dio;
+    orbhip_covis_state ds;
+    memset(&dio, 0, sizeof(dio));
+    memset(&ds, 0, sizeof(ds));
+    cull_stage_tables(st, rows, cap, np, pcap, obs_cap, total, t, &dt);
+    const int32_t *d_cand = st.put(cand, Un);
+    const size_t out_off = st.off;
+    CullOut outs[20];
+    int no = 0;
+    auto inout = [&](void *host, size_t bytes) {
+        const uint8_t *d = st.put((const uint8_t *)host, bytes);
+        outs[no++] = {host, d, bytes};
+        return (void *)d;
+    };
+    auto out = [&](void *host, size_t bytes) {
+        const uint8_t *d;
+        st.take(bytes, &d);
+        outs[no++] = {host, d, bytes};
+        return (void *)d;
+    };
+    dio.slot_point = inout(io->slot_point, RC * 4);
+    dio.flags = inout(io->flags, P);
+    dio.kf_bad = inout(io->kf_bad, Rw);
+    if (io->to_be_erased) dio.to_be_erased = inout(io->to_be_erased, Rw);
+    dio.child_start = out(io->child_start, (Rw + 1) * 4);
+    dio.child = inout(io->child, Rw * 4);
+    dio.obs_start_out = out(io->obs_start_out, (P + 1) * 4);
+    dio.obs_kf_out = inout(io->obs_kf_out, total * 4);
+    dio.obs_idx_out = inout(io->obs_idx_out, total * 4);
+    dio.ref_obs_out = out(io->ref_obs_out, P * 4);
+    ds.conn_w = inout(s->conn_w, Rw * Rw * 4);
+    ds.ord_kf = inout(s->ord_kf, Rw * Rw * 4);
+    ds.ord_w = inout(s->ord_w, Rw * Rw * 4);
+    ds.n_ord = inout(s->n_ord, Rw * 4);
+    ds.covis = inout(s->covis, Rw * 40);
+    ds.parent = inout(s->parent, Rw * 4);
+    void *d_report = out(report, Un * 32);
+    const size_t out_bytes = st.off - out_off;
+    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = cull_key_frames_launch(m, rows, cap, np, obs_cap, &dt, &dio, &ds, id0_row, U, d_cand, mono, th_depth, d_report))) return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
+    for (int i = 0; i < no; ++i)
+        if (outs[i].bytes) memcpy(outs[i].host, h + ((const uint8_t *)outs[i].dev - (st.d + out_off)), outs[i].bytes);
+    return ORBHIP_OK;
 }
 
 #ifdef ORBHIP_DEVTOOLS

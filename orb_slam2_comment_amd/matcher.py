@@ -554,6 +554,113 @@ class ORBmatcher:
         check(self._lib.orbhip_children_from_parents_device(self._h, int(rows), d_parent, d_kf_bad, d_child_start, d_child),
               "orbhip_children_from_parents_device")
 
+    # -- culling (src/LocalMapping.cc:170-205, :632-696; src/KeyFrame.cc:453-567; src/MapPoint.cc:111-168) ----------------
+    CULL_TABLES = tuple(k for k, _ in capi.CullTables._fields_)
+    CULL_IO = tuple(k for k, _ in capi.CullIO._fields_)
+    _CULL_DTYPES = dict(kps=capi.KP_DTYPE, u_right=np.float32, depth=np.float32, n=np.int32, obs_start=np.int32, obs_kf=np.int32,
+                        obs_idx=np.int32, ref_obs=np.int32, not_erase=np.uint8, slot_point=np.int32, flags=np.uint8,
+                        kf_bad=np.uint8, to_be_erased=np.uint8, child_start=np.int32, child=np.int32)
+
+    def _cull_host(self, tables, io, key_frames, fill):
+        """The records of the host culling entries from dicts of host arrays, with fresh in/out copies and the table out."""
+        T = {k: (None if tables.get(k) is None else np.ascontiguousarray(tables[k], self._CULL_DTYPES[k])) for k in self.CULL_TABLES}
+        for k in ("obs_start", "obs_kf", "obs_idx", "ref_obs") + (("kps", "n") if key_frames else ()):
+            if T[k] is None:
+                raise ValueError("tables[%r] is missing" % k)
+        IO = {}
+        need = ("slot_point", "flags") + (("kf_bad", "child_start", "child") if key_frames else ())
+        for k in ("slot_point", "flags", "kf_bad", "to_be_erased", "child_start", "child"):
+            if io.get(k) is None:
+                if k in need:
+                    raise ValueError("io[%r] is missing" % k)
+                IO[k] = None
+            else:
+                IO[k] = np.array(io[k], self._CULL_DTYPES[k], order="C")
+        if IO["slot_point"].ndim != 2:
+            raise ValueError("slot_point is [rows, cap]")
+        rows, cap = IO["slot_point"].shape
+        n_pts, pcap = len(T["obs_start"]) - 1, len(IO["flags"])
+        obs_cap = len(T["obs_kf"])
+        if n_pts < 0 or len(T["obs_idx"]) != obs_cap or len(T["ref_obs"]) < n_pts:
+            raise ValueError("the observation table does not agree with itself")
+        IO["obs_start_out"] = np.full(n_pts + 1, fill, np.int32)
+        IO["obs_kf_out"] = np.full(max(obs_cap, 1), fill, np.int32)
+        IO["obs_idx_out"] = np.full(max(obs_cap, 1), fill, np.int32)
+        IO["ref_obs_out"] = np.full(max(n_pts, 1), fill, np.int32)
+        keep = [np.zeros(1, a.dtype) if a is not None and a.size == 0 else a for a in list(T.values()) + list(IO.values())]
+        rt = self._record(capi.CullTables, {k: ptr(a).value for k, a in zip(T, keep) if a is not None},
+                          ("kps", "u_right", "depth", "n", "not_erase"))
+        rio = self._record(capi.CullIO, {k: ptr(a).value for k, a in zip(IO, keep[len(T):]) if a is not None},
+                           ("kf_bad", "to_be_erased", "child_start", "child"))
+        return rt, rio, IO, keep, (rows, cap, n_pts, pcap, obs_cap)
+
+    def CullMapPoints(self, tables, io, recent, found, visible, first_kf_id, cur_kf_id, th_obs, fill=0):
+        """LocalMapping::MapPointCulling from host arrays (orbhip_cull_map_points): `tables` holds obs_start, obs_kf, obs_idx,
+        ref_obs and optionally u_right [rows, cap]; `io` holds slot_point [rows, cap] and flags [pcap].  Returns (io, kept,
+        status): copies of slot_point and flags as the call left them plus the table out (obs_start_out, obs_kf_out,
+        obs_idx_out, ref_obs_out; entries the call does not write hold `fill`), the kept entries of `recent` in order and one capi.CULLPOINT_* code per entry."""
+        i32 = np.int32
+        rt, rio, IO, keep, (rows, cap, n_pts, pcap, obs_cap) = self._cull_host(tables, io, False, fill)
+        rec = np.ascontiguousarray(recent, i32).reshape(-1)
+        R = len(rec)
+        per_point = [np.ascontiguousarray(a, i32) for a in (found, visible, first_kf_id)]
+        if any(len(a) < n_pts for a in per_point):
+            raise ValueError("found, visible and first_kf_id need one entry per point")
+        out, n_out, status = np.zeros(max(R, 1), i32), np.zeros(1, i32), np.zeros(max(R, 1), np.uint8)
+        pad = [np.zeros(1, i32) if a.size == 0 else a for a in [rec] + per_point]
+        check(self._lib.orbhip_cull_map_points(self._h, rows, cap, n_pts, pcap, obs_cap, C.byref(rt), C.byref(rio), R, ptr(pad[0]),
+                                               ptr(pad[1]), ptr(pad[2]), ptr(pad[3]), int(cur_kf_id), int(th_obs), ptr(out),
+                                               ptr(n_out), ptr(status)), "orbhip_cull_map_points")
+        return IO, out[:int(n_out[0])].copy(), status[:R].copy()
+
+    def CullMapPointsDevice(self, rows, cap, np_, pcap, obs_cap, tables, io, R, d_recent, d_found, d_visible, d_first_kf_id,
+                            cur_kf_id, th_obs, d_recent_out, d_n_recent_out, d_status):
+        """Device-resident form (orbhip_cull_map_points_device in include/orbhip.h): `tables` and `io` are dicts with the keys
+        of CULL_TABLES / CULL_IO holding device addresses (ints, or tensors); what the call does not read may be absent.
+        Asynchronous on the matcher's stream."""
+        rt = self._record(capi.CullTables, tables, ("kps", "u_right", "depth", "n", "not_erase"))
+        rio = self._record(capi.CullIO, io, ("kf_bad", "to_be_erased", "child_start", "child"))
+        check(self._lib.orbhip_cull_map_points_device(self._h, int(rows), int(cap), int(np_), int(pcap), int(obs_cap), C.byref(rt),
+                                                      C.byref(rio), int(R), d_recent, d_found, d_visible, d_first_kf_id,
+                                                      int(cur_kf_id), int(th_obs), d_recent_out, d_n_recent_out, d_status),
+              "orbhip_cull_map_points_device")
+
+    def CullKeyFrames(self, tables, io, state, cand, id0_row=-1, mono=False, th_depth=0.0, fill=0):
+        """LocalMapping::KeyFrameCulling over the candidate rows `cand` (-1 entries are skipped) from host arrays
+        (orbhip_cull_key_frames): `tables` with the keys of CULL_TABLES (u_right, depth, not_erase may be absent), `io` with
+        slot_point, flags, kf_bad, child_start [rows + 1], child [rows] and optionally to_be_erased, `state` with the keys of
+        COVIS_STATE.  Returns (io, state, report): copies as the call left them, the table out among io, and report [U, 8]
+        int32 in the order of capi.CULLKF_REPORT."""
+        i32, u8 = np.int32, np.uint8
+        rt, rio, IO, keep, (rows, cap, n_pts, pcap, obs_cap) = self._cull_host(tables, io, True, fill)
+        S = {}
+        for k, dt, shape in (("conn_w", i32, (rows, rows)), ("ord_kf", i32, (rows, rows)), ("ord_w", i32, (rows, rows)),
+                             ("n_ord", i32, (rows,)), ("covis", i32, (rows, 10)), ("first_conn", u8, (rows,)),
+                             ("parent", i32, (rows,))):
+            if state.get(k) is None:
+                raise ValueError("state[%r] is missing" % k)
+            S[k] = np.array(state[k], dt, order="C").reshape(shape)
+        skeep = {k: (np.zeros(1, a.dtype) if a.size == 0 else a) for k, a in S.items()}
+        rs = self._record(capi.CovisState, {k: ptr(skeep[k]).value for k in self.COVIS_STATE})
+        c = np.ascontiguousarray(cand, i32).reshape(-1)
+        U = len(c)
+        report = np.zeros((max(U, 1), 8), i32)
+        check(self._lib.orbhip_cull_key_frames(self._h, rows, cap, n_pts, pcap, obs_cap, C.byref(rt), C.byref(rio), C.byref(rs),
+                                               int(id0_row), U, ptr(c if U else np.zeros(1, i32)), int(bool(mono)),
+                                               float(np.float32(th_depth)), ptr(report)), "orbhip_cull_key_frames")
+        return IO, S, report[:U].copy()
+
+    def CullKeyFramesDevice(self, rows, cap, np_, pcap, obs_cap, tables, io, state, id0_row, U, d_cand, mono, th_depth, d_report):
+        """Device-resident form (orbhip_cull_key_frames_device): `tables`, `io` and `state` are dicts with the keys of
+        CULL_TABLES / CULL_IO / COVIS_STATE holding device addresses; u_right, depth (with mono), not_erase and to_be_erased
+        may be absent, first_conn is not read.  Asynchronous on the matcher's stream."""
+        rt = self._record(capi.CullTables, tables, ("u_right", "depth", "not_erase"))
+        rio = self._record(capi.CullIO, io, ("to_be_erased",))
+        rs = self._record(capi.CovisState, state, ("first_conn",))
+        check(self._lib.orbhip_cull_key_frames_device(self._h, int(rows), int(cap), int(np_), int(pcap), int(obs_cap), C.byref(rt),
+                                                      C.byref(rio), C.byref(rs), int(id0_row), int(U), d_cand, int(bool(mono)),
+                                                      float(np.float32(th_depth)), d_report), "orbhip_cull_key_frames_device")
+
     # -- device-resident, batched SearchByProjection ---------------------------
     def set_stream(self, stream):
         check(self._lib.orbhip_matcher_set_stream(self._h, stream), "orbhip_matcher_set_stream")
