@@ -1045,6 +1045,97 @@ int orbhip_cull_key_frames(orbhip_matcher *m, int rows, int cap, int np, int pca
                            const orbhip_cull_io *io, const orbhip_covis_state *state, int id0_row, int U, const int32_t *cand,
                            int mono, float th_depth, int32_t *report);
 
+/* ---- Sim3 RANSAC ----------------------------------------------------------------------------------------------------------
+ * Sim3Solver (src/Sim3Solver.cc) for the current key frame and C loop candidates in one call each: the step of
+ * LoopClosing::ComputeSim3 (src/LoopClosing.cc:238-342) between orbhip_search_by_bow_device and orbhip_search_by_sim3.
+ * orbhip_sim3_setup_device is the constructor (:37-112) with SetRansacParameters (:114-138); orbhip_sim3_iterate_device is
+ * iterate (:140-207) for every candidate at once.  The arithmetic, operation by operation, is tests/seqref/sim3.py and
+ * DESIGN.md section 3 (a two-sided Jacobi method in fp32 stands in for cv::eigen, the rotation comes straight from the
+ * normalised quaternion).  The reference draws with rand(); here the draws are caller data.
+ *
+ * orbhip_sim3_tables (read only).  The key-frame bank has `rows` rows of `cap` slots, the map np points in arrays of pcap:
+ *   slot_point [rows][cap] int32 = mvpMapPoints as point indices, -1 = none; n [rows] int32;
+ *   obs_start [np+1] / obs_kf / obs_idx int32: the observation table of orbhip_update_map_points_device.
+ *     MapPoint::GetIndexInKeyFrame(row) is obs_idx of the first entry of the point's list whose obs_kf is the row, -1 if none;
+ *   flags [pcap] uint8 (ORBHIP_POINT_PRESENT = !isBad()), world [pcap][3] float = mWorldPos;
+ *   Tcw [rows][12] float = [Rcw | tcw]; kps [rows][cap] orbhip_keypoint = mvKeysUn (only octave is read).
+ * orbhip_sim3_solvers (device state the caller owns, one row per candidate; written by setup, read and advanced by iterate):
+ *   x1 / x2 [C][cap][3] float = mvX3Dc1 / mvX3Dc2, p1 / p2 [C][cap][2] float = mvP1im1 / mvP2im2,
+ *   max_err1 / max_err2 [C][cap] uint32 = mvnMaxError1 / 2: the reference keeps them in a vector<size_t>, so the threshold is
+ *     the TRUNCATED integer of 9.210 * (double)sigma2 (9 at level 0, not 9.21; saturated at 2^32 - 1), compared as a float;
+ *   slot1 [C][cap] int32 = mvnIndices1; n_corr [C] int32 = N; n1 [C] int32 = mN1 = n[cur] when setup ran;
+ *   limit [C] int32 = mRansacMaxIts after SetRansacParameters, 0 where N < min_inliers;
+ *   state [C][2] int32 = {mnIterations, mnBestInliers}.
+ *   Entries behind n_corr keep the caller's bytes.
+ *
+ * orbhip_sim3_setup_device: candidate c is bank row d_kf_index[c], the current key frame row `cur`.  d_matched12 [C][cap]
+ * int32 = vpMatched12 per slot of `cur`, negative = none: point indices (ORBHIP_SIM3_MATCH_POINTS) or key-point slots of the
+ * candidate row as orbhip_search_by_bow_device writes them (ORBHIP_SIM3_MATCH_SLOTS; mapped through slot_point, a slot
+ * without a point is no match).  A slot i1 < n[cur] is kept unless it has no match, slot i1 of `cur` has no point, either
+ * point is not ORBHIP_POINT_PRESENT, or either point has no observation in its key frame; the kept ones are compacted in
+ * slot order.  level_sigma2 [cam->n_levels] = mvLevelSigma2 (host).  The iteration limit depends on N only: 1 for
+ * N == min_inliers, otherwise ceil(log(1 - prob) / log(1 - pow((float)min_inliers / N, 3))) clamped to [1, max_its]; the
+ * library computes the cap + 1 values on the host, keeps them in the handle and rebuilds them only when (prob,
+ * min_inliers, max_its, cap) change (that one call waits for the stream and uploads the table; no other call
+ * synchronises).  state is zeroed.  One launch, one workgroup per candidate.
+ * min_inliers >= 3 (a sample is three correspondences), max_its >= 1, 0 < prob < 1.
+ *
+ * orbhip_sim3_iterate_device advances every candidate by at most n_iterations (the reference passes 5; a device caller
+ * passes max_its).  d_draws [C][max_its][3] int32: row `it` serves iteration number `it`, so a later call continues in the
+ * same array; draw k lies in [0, N-1-k] and stands for DUtils::Random::RandomInt(0, vAvailableIndices.size()-1) (:168).
+ * All hypotheses of the call are computed and scored at once, then the state machine of :183-204 runs as a prefix maximum
+ * over the iteration numbers, which gives what the sequential loop gives: the first iteration whose inlier count is
+ * >= the best so far and > min_inliers returns.
+ *   d_report [C][8] int32 = {status, N, limit, mnIterations after, mnBestInliers after, returned iteration or -1, nInliers,
+ *     0}.  status: ORBHIP_SIM3_RETURNED; ORBHIP_SIM3_CONTINUE (bNoMore false, nothing returned); ORBHIP_SIM3_NO_MORE
+ *     (mnIterations >= limit when the loop ended without a return; a return on the last allowed iteration reports
+ *     RETURNED and the NEXT call reports NO_MORE without running anything); ORBHIP_SIM3_TOO_FEW (N < min_inliers, :146).
+ *   d_sim3 [C][16] float = mBestRotation (9, row-major), mBestTranslation (3), mBestScale, three zeros: written only on
+ *     a return.
+ *   d_inliers [C][cap] uint8 = vbInliers over the slots of `cur`: zeroed for i1 < n1 on every call (:143), then set at
+ *     slot1 of the returned hypothesis's inliers.
+ * min_inliers, max_its and cap must be the values setup was given; cam supplies fx, fy, cx, cy for both key frames.
+ * fix_scale = mbFixScale (stereo / RGB-D).  Three launches; the hypotheses, counts and inlier masks of a call live in the
+ * handle.  A zero depth or a degenerate sample propagates inf / NaN as is: every comparison is false, 0 inliers.
+ *
+ * Both: asynchronous on the matcher's stream, no host synchronisation, no staging copy.  cap <= 4096 (ORBHIP_E_CAPACITY
+ * beyond); C, rows or np negative, np > pcap, cap < 1, cur outside [0, rows), a bad match_form, parameters outside the
+ * ranges above or a null pointer: ORBHIP_E_ARG; all refused before any device work.  C == 0: success, nothing written.
+ * The device forms do not range-check the tables' contents, the candidate rows or the draws (a draw outside its range is
+ * clamped into the arrays and gives an unspecified sample). */
+#define ORBHIP_SIM3_MATCH_POINTS 0
+#define ORBHIP_SIM3_MATCH_SLOTS  1
+#define ORBHIP_SIM3_RETURNED 0
+#define ORBHIP_SIM3_CONTINUE 1
+#define ORBHIP_SIM3_NO_MORE  2
+#define ORBHIP_SIM3_TOO_FEW  3
+typedef struct orbhip_sim3_tables {
+    const void *slot_point, *obs_start, *obs_kf, *obs_idx, *flags, *world, *Tcw, *kps, *n;
+} orbhip_sim3_tables;
+typedef struct orbhip_sim3_solvers {
+    void *x1, *x2, *p1, *p2, *max_err1, *max_err2, *slot1, *n_corr, *n1, *limit, *state;
+} orbhip_sim3_solvers;
+int orbhip_sim3_setup_device(orbhip_matcher *m, int C, int cur, const void *d_kf_index, const orbhip_camera *cam, int rows, int cap,
+                             int np, int pcap, const orbhip_sim3_tables *tables, const void *d_matched12, int match_form,
+                             const float *level_sigma2, double prob, int min_inliers, int max_its,
+                             const orbhip_sim3_solvers *solvers);
+int orbhip_sim3_iterate_device(orbhip_matcher *m, int C, int cap, const orbhip_camera *cam, const orbhip_sim3_solvers *solvers,
+                               const void *d_draws, int max_its, int n_iterations, int min_inliers, int fix_scale, void *d_sim3,
+                               void *d_inliers, void *d_report);
+/* Host buffers, synchronous: one staging copy, setup + iterate(n_iterations), one read-back.  The same table record with
+ * host pointers; kf_index [C], matched12 [C][cap], draws [C][max_its][3].  state [C][2] int32, nullable, in/out: NULL (or
+ * zeros) is a fresh solver; passing back what an earlier call left resumes that solver, which is how the reference's
+ * five-iterations-at-a-time loop runs over this form (the setup is recomputed, it is a function of the tables).  sim3
+ * [C][16], inliers [C][cap] and report [C][8] as above (entries the call does not write keep the caller's values).  It
+ * range-checks what the device forms do not: kf_index in [0, rows), n in [0, cap], slot_point in [-1, np), matches below np
+ * (points) or cap (slots), obs_start non-decreasing from 0, obs_kf in [0, rows), obs_idx in [0, cap), octaves in
+ * [0, cam->n_levels), state[c][0] in [0, max_its] and every draw the call can reach in [0, N-1-k] (checked against the N
+ * of the tables on the host): ORBHIP_E_ARG, before the handle is looked at. */
+int orbhip_sim3_ransac(orbhip_matcher *m, int C, int cur, const int32_t *kf_index, const orbhip_camera *cam, int rows, int cap, int np,
+                       int pcap, const orbhip_sim3_tables *tables, const int32_t *matched12, int match_form,
+                       const float *level_sigma2, double prob, int min_inliers, int max_its, int fix_scale, const int32_t *draws,
+                       int n_iterations, int32_t *state, float *sim3, uint8_t *inliers, int32_t *report);
+
 /* ---- creating new map points -------------------------------------------------------------------------------------
  * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) for the current key frame and K neighbours in one call, up
  * to the point where the map graph is touched: `new MapPoint`, AddObservation and everything after :434 stay with the

@@ -250,6 +250,7 @@ public:
     ~ORBmatcher() { orbhip_matcher_destroy(m_); }
     ORBmatcher(const ORBmatcher &) = delete;
     ORBmatcher &operator=(const ORBmatcher &) = delete;
+    orbhip_matcher *handle() { return m_; }   // for the classes that work over the same handle (orbhip/Sim3Solver.hpp)
 
     // static int DescriptorDistance(const cv::Mat &a, const cv::Mat &b): host popcount, same result
     static int DescriptorDistance(const uint8_t *a, const uint8_t *b)

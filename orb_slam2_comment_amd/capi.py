@@ -80,6 +80,17 @@ class CullIO(C.Structure):
                                           "obs_start_out", "obs_kf_out", "obs_idx_out", "ref_obs_out")]
 
 
+class Sim3Tables(C.Structure):
+    """orbhip_sim3_tables: the bank and map-point tables orbhip_sim3_setup_device / orbhip_sim3_ransac read."""
+    _fields_ = [(k, C.c_void_p) for k in ("slot_point", "obs_start", "obs_kf", "obs_idx", "flags", "world", "Tcw", "kps", "n")]
+
+
+class Sim3Solvers(C.Structure):
+    """orbhip_sim3_solvers: the per-candidate solver state on the device (written by setup, advanced by iterate)."""
+    _fields_ = [(k, C.c_void_p) for k in ("x1", "x2", "p1", "p2", "max_err1", "max_err2", "slot1", "n_corr", "n1", "limit",
+                                          "state")]
+
+
 POINT_PRESENT, POINT_OBSERVED = 1, 2
 COLOR_BGR, COLOR_RGB = 0, 1
 DEPTH_U16, DEPTH_F32 = 0, 1
@@ -101,11 +112,16 @@ CONNECTIONS_REPORT = ("status", "n_voted", "n_ordered", "max_row", "max_votes", 
 CULLPOINT_KEPT, CULLPOINT_ALREADY_BAD, CULLPOINT_BAD_RATIO, CULLPOINT_BAD_OBS, CULLPOINT_DROPPED_OLD = range(5)
 CULLKF_NOT_CULLED, CULLKF_CULLED, CULLKF_SKIPPED_ID0, CULLKF_SKIPPED_ENTRY, CULLKF_NOT_ERASE = range(5)
 CULLKF_REPORT = ("status", "n_mps", "n_redundant", "n_erased", "n_bad", "n_resorted", "n_children", "fallback")
+# ORBHIP_SIM3_MATCH_*: what d_matched12 of orbhip_sim3_setup_device holds; ORBHIP_SIM3_*: report[0] of orbhip_sim3_iterate_device
+SIM3_MATCH_POINTS, SIM3_MATCH_SLOTS = range(2)
+SIM3_RETURNED, SIM3_CONTINUE, SIM3_NO_MORE, SIM3_TOO_FEW = range(4)
+SIM3_REPORT = ("status", "n_corr", "limit", "iterations", "best_inliers", "returned_iteration", "n_inliers", "reserved")
 REMAP_TABLE_SIZE = 4096
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _pi = C.POINTER(C.c_int)
+_d = C.c_double
 SYMBOLS = [
     ("orbhip_last_error", C.c_char_p, []),
     ("orbhip_device_count", _i, [_pi]),
@@ -227,6 +243,12 @@ SYMBOLS = [
                                            C.POINTER(CovisState), _i, _i, _vp, _i, _f, _vp]),
     ("orbhip_cull_key_frames", _i, [_vp, _i, _i, _i, _i, _i, C.POINTER(CullTables), C.POINTER(CullIO), C.POINTER(CovisState), _i,
                                     _i, _vp, _i, _f, _vp]),
+    ("orbhip_sim3_setup_device", _i, [_vp, _i, _i, _vp, C.POINTER(Camera), _i, _i, _i, _i, C.POINTER(Sim3Tables), _vp, _i, _vp, _d,
+                                      _i, _i, C.POINTER(Sim3Solvers)]),
+    ("orbhip_sim3_iterate_device", _i, [_vp, _i, _i, C.POINTER(Camera), C.POINTER(Sim3Solvers), _vp, _i, _i, _i, _i, _vp, _vp,
+                                        _vp]),
+    ("orbhip_sim3_ransac", _i, [_vp, _i, _i, _vp, C.POINTER(Camera), _i, _i, _i, _i, C.POINTER(Sim3Tables), _vp, _i, _vp, _d, _i,
+                                _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     ("orbhip_matcher_set_stream", _i, [_vp, _vp]),
     ("orbhip_matcher_sync", _i, [_vp]),
     ("orbhip_compute_stereo_matches_device", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,

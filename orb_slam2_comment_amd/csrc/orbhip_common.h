@@ -126,6 +126,10 @@ __device__ __forceinline__ void wave_lds_handoff()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Correctly rounded fp32 square root.  NOT __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define that
+// one as the native approximation (a bare v_sqrt_f32, 1 ulp); the builtin gets the compiler's correctly rounded expansion.
+__device__ __forceinline__ float sqrt_rn(float x) { return __builtin_sqrtf(x); }
+
 // XCD-aware work mapping (speed only, never correctness): workgroups are dealt round-robin over the
 // 8 XCDs in linear order, each XCD has a private 4 MB L2.  Re-index so that XCD k owns a contiguous
 // run of (frame, unit) pairs: with a batch that is a multiple of 8 every kernel of the pipeline

@@ -181,6 +181,36 @@ struct CullArgs {
 size_t cull_workspace_bytes(int np, int obs_cap, int U);
 int launch_cull_map_points(hipStream_t stream, CullArgs A, void *workspace);
 int launch_cull_key_frames(hipStream_t stream, CullArgs A, void *workspace);
+
+// orbhip_sim3.hip: the tables, the solver state and the workspace of orbhip_sim3_setup_device / orbhip_sim3_iterate_device
+constexpr int kSim3HypFloats = 40;      // T12 [12], T21 [12], R12 [9], t12 [3], s12, padding
+struct Sim3Args {
+    const int *slot_point, *n;          // [rows][cap], [rows]
+    const int *obs_start, *obs_kf, *obs_idx;
+    const uint8_t *flags;               // [pcap]
+    const float *world, *Tcw;           // [pcap][3], [rows][12]
+    const orbhip_keypoint *kps;         // [rows][cap]
+    const int *kf_index, *matched12;    // [C], [C][cap]
+    const int *limit_tab;               // [cap + 1], built on the host
+    float *x1, *x2, *p1, *p2;           // [C][cap][3], [C][cap][2]
+    uint32_t *max_err1, *max_err2;      // [C][cap]
+    int *slot1, *n_corr, *n1, *limit, *state;
+    const int *draws;                   // [C][max_its][3]
+    float *sim3;                        // [C][16]
+    uint8_t *inliers;                   // [C][cap]
+    int *report;                        // [C][8]
+    // workspace of one iterate call, j = iteration number - mnIterations at the start of the call:
+    // hyp [C][n_iter][kSim3HypFloats], count [C][n_iter], mask [C][n_iter][cap16] (bit i & 15 of unit i >> 4 = correspondence i)
+    float *hyp;
+    int *count;
+    uint16_t *mask;
+    uint32_t thr[ORBHIP_MAX_LEVELS];    // the truncated thresholds per pyramid level
+    float fx, fy, cx, cy;
+    int C, cur, rows, cap, np, match_form, n_levels, max_its, n_iter, min_inliers, fix_scale, cap16;
+};
+size_t sim3_workspace_bytes(int C, int n_iter, int cap);
+int launch_sim3_setup(hipStream_t stream, Sim3Args A);
+int launch_sim3_iterate(hipStream_t stream, Sim3Args A, void *workspace);
 }  // namespace orbhip
 
 struct orbhip_extractor {

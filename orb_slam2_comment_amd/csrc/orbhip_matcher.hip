@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <new>
 #include <vector>
 
@@ -1294,9 +1295,6 @@ __global__ __launch_bounds__(1024) void k_cnmp_cull(CnmpArgs A)
                   A.keys + f * A.cap, 1, nullptr);
 }
 
-// Correctly rounded fp32 square root.  NOT __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define that
-// one as the native approximation (a bare v_sqrt_f32, 1 ulp); the builtin gets the compiler's correctly rounded expansion.
-__device__ __forceinline__ float sqrt_rn(float x) { return __builtin_sqrtf(x); }
 __device__ __forceinline__ float dot4f(const float (&a)[4], const float (&b)[4])
 {
     return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(a[0], b[0]), __fmul_rn(a[1], b[1])), __fmul_rn(a[2], b[2])),
@@ -3717,8 +3715,8 @@ struct orbhip_matcher {
     hipStream_t stream = nullptr;       // stream every launch goes to
     hipStream_t own_stream = nullptr;   // created with the handle
     // grow-only device scratch
-    void *buf[20] = {};
-    size_t cap[20] = {};
+    void *buf[23] = {};
+    size_t cap[23] = {};
     bool lds_attr_set = false, bow_attr_set = false;
 #ifdef ORBHIP_DEVTOOLS
     int window_lanes = 0;               // development build: lanes per query of k_window_search forced to 16 / 64 (0: the rule)
@@ -3727,6 +3725,10 @@ struct orbhip_matcher {
     // pinned host staging: all inputs of a call travel in one DMA, all outputs in one
     uint8_t *h_stage = nullptr; size_t h_stage_bytes = 0;
     uint8_t *h_out = nullptr; size_t h_out_bytes = 0;
+    // Sim3 RANSAC: the iteration limit per correspondence count, [sim3_cap + 1], rebuilt when a parameter changes
+    std::vector<int> sim3_limit;
+    double sim3_prob = 0.0;
+    int sim3_min_inliers = 0, sim3_max_its = 0, sim3_cap = -1;
 };
 
 static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -3807,7 +3809,7 @@ static SigmaTab sigma_tab(const float *inv_level_sigma2, int n_levels)
     return sig;
 }
 
-enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_COVIS, S_CULL, S_NSLOTS };
+enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_COVIS, S_CULL, S_SIM3, S_SIM3LIM, S_SIM3SOLV, S_NSLOTS };
 static_assert(S_NSLOTS == sizeof(orbhip_matcher::buf) / sizeof(void *), "one scratch buffer per slot");
 
 static int stage_begin(orbhip_matcher *m, size_t total, Stage *st)
@@ -5826,6 +5828,241 @@ int orbhip_cull_key_frames(orbhip_matcher *m, int rows, int cap, int np, int pca
     if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
     for (int i = 0; i < no; ++i)
         if (outs[i].bytes) memcpy(outs[i].host, h + ((const uint8_t *)outs[i].dev - (st.d + out_off)), outs[i].bytes);
+    return ORBHIP_OK;
+}
+
+// ---- Sim3 RANSAC (kernels: orbhip_sim3.hip) ---------------------------------------------------------------------------
+// SetRansacParameters (src/Sim3Solver.cc:114-138) as a function of N.  epsilon is a float before pow, as in the text; the
+// quotient is clamped while still a double (the text converts it to int first, which overflows for small epsilon).
+static int sim3_limit_of(int N, double prob, int min_inliers, int max_its)
+{
+    if (N < min_inliers) return 0;          // iterate never runs (:146)
+    if (N == min_inliers) return 1;
+    const float epsilon = (float)min_inliers / N;
+    const double d = std::ceil(std::log(1 - prob) / std::log(1 - std::pow((double)epsilon, 3)));
+    if (!(d >= 1.0)) return 1;
+    return d > (double)max_its ? max_its : (int)d;
+}
+
+static int sim3_params(const char *who, int C, int cap, const orbhip_camera *cam, int min_inliers, int max_its)
+{
+    if (C < 0 || cap < 1 || !cam || min_inliers < 3 || max_its < 1) return ORBHIP_E_ARG;
+    if (cap > kGridMax) { set_error("%s: capacity %d exceeds %d", who, cap, kGridMax); return ORBHIP_E_CAPACITY; }
+    if (max_its > 65536) { set_error("%s: %d iterations exceed 65536", who, max_its); return ORBHIP_E_CAPACITY; }
+    return ORBHIP_OK;
+}
+static bool sim3_solvers_ok(const orbhip_sim3_solvers *s)
+{
+    return s && s->x1 && s->x2 && s->p1 && s->p2 && s->max_err1 && s->max_err2 && s->slot1 && s->n_corr && s->n1 && s->limit && s->state;
+}
+static int sim3_setup_args(int C, int cur, const void *kf_index, const orbhip_camera *cam, int rows, int cap, int np, int pcap,
+                           const orbhip_sim3_tables *t, const void *matched12, int match_form, const float *level_sigma2, double prob,
+                           int min_inliers, int max_its)
+{
+    if (int rc = sim3_params("sim3_setup", C, cap, cam, min_inliers, max_its)) return rc;
+    if (rows < 0 || np < 0 || pcap < 0 || np > pcap || cur < 0 || cur >= rows || !(prob > 0.0 && prob < 1.0) || !level_sigma2 ||
+        cam->n_levels < 1 || cam->n_levels > ORBHIP_MAX_LEVELS || !kf_index || !matched12 ||
+        (match_form != ORBHIP_SIM3_MATCH_POINTS && match_form != ORBHIP_SIM3_MATCH_SLOTS))
+        return ORBHIP_E_ARG;
+    if (!t || !t->slot_point || !t->obs_start || !t->obs_kf || !t->obs_idx || !t->flags || !t->world || !t->Tcw || !t->kps || !t->n)
+        return ORBHIP_E_ARG;
+    return ORBHIP_OK;
+}
+static void sim3_solvers(Sim3Args &A, const orbhip_sim3_solvers *s)
+{
+    A.x1 = (float *)s->x1; A.x2 = (float *)s->x2; A.p1 = (float *)s->p1; A.p2 = (float *)s->p2;
+    A.max_err1 = (uint32_t *)s->max_err1; A.max_err2 = (uint32_t *)s->max_err2; A.slot1 = (int *)s->slot1;
+    A.n_corr = (int *)s->n_corr; A.n1 = (int *)s->n1; A.limit = (int *)s->limit; A.state = (int *)s->state;
+}
+static void sim3_camera(Sim3Args &A, const orbhip_camera *cam)
+{
+    A.fx = cam->fx; A.fy = cam->fy; A.cx = cam->cx; A.cy = cam->cy; A.n_levels = cam->n_levels;
+}
+// mvnMaxError* is a vector<size_t> (include/Sim3Solver.h:78-79): the product is truncated
+static uint32_t sim3_threshold(float sigma2)
+{
+    const double v = 9.210 * (double)sigma2;
+    if (!(v >= 0.0)) return 0;
+    return v >= 4294967295.0 ? 0xffffffffu : (uint32_t)v;
+}
+
+static int sim3_setup_launch(orbhip_matcher *m, int C, int cur, const void *d_kf_index, const orbhip_camera *cam, int rows, int cap, int np,
+                             const orbhip_sim3_tables *t, const void *d_matched12, int match_form, const float *level_sigma2, double prob,
+                             int min_inliers, int max_its, const orbhip_sim3_solvers *s)
+{
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    void *d_tab;
+    if (int rc = scratch(m, S_SIM3LIM, ((size_t)cap + 1) * sizeof(int), &d_tab)) return rc;
+    if (m->sim3_cap != cap || m->sim3_prob != prob || m->sim3_min_inliers != min_inliers || m->sim3_max_its != max_its) {
+        ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));   // the table a previous call may still read is about to change
+        m->sim3_limit.resize((size_t)cap + 1);
+        for (int N = 0; N <= cap; ++N) m->sim3_limit[N] = sim3_limit_of(N, prob, min_inliers, max_its);
+        ORBHIP_HIP_CHECK(hipMemcpy(d_tab, m->sim3_limit.data(), ((size_t)cap + 1) * sizeof(int), hipMemcpyHostToDevice));
+        m->sim3_cap = cap; m->sim3_prob = prob; m->sim3_min_inliers = min_inliers; m->sim3_max_its = max_its;
+    }
+    Sim3Args A;
+    memset(&A, 0, sizeof(A));
+    A.slot_point = (const int *)t->slot_point; A.n = (const int *)t->n; A.obs_start = (const int *)t->obs_start;
+    A.obs_kf = (const int *)t->obs_kf; A.obs_idx = (const int *)t->obs_idx; A.flags = (const uint8_t *)t->flags;
+    A.world = (const float *)t->world; A.Tcw = (const float *)t->Tcw; A.kps = (const orbhip_keypoint *)t->kps;
+    A.kf_index = (const int *)d_kf_index; A.matched12 = (const int *)d_matched12; A.limit_tab = (const int *)d_tab;
+    sim3_solvers(A, s);
+    sim3_camera(A, cam);
+    for (int l = 0; l < ORBHIP_MAX_LEVELS; ++l) A.thr[l] = l < cam->n_levels ? sim3_threshold(level_sigma2[l]) : 0;
+    A.C = C; A.cur = cur; A.rows = rows; A.cap = cap; A.np = np; A.match_form = match_form; A.min_inliers = min_inliers; A.max_its = max_its;
+    return launch_sim3_setup(m->stream, A);
+}
+
+int orbhip_sim3_setup_device(orbhip_matcher *m, int C, int cur, const void *d_kf_index, const orbhip_camera *cam, int rows, int cap, int np,
+                             int pcap, const orbhip_sim3_tables *t, const void *d_matched12, int match_form, const float *level_sigma2,
+                             double prob, int min_inliers, int max_its, const orbhip_sim3_solvers *s)
+{
+    if (int rc = sim3_setup_args(C, cur, d_kf_index, cam, rows, cap, np, pcap, t, d_matched12, match_form, level_sigma2, prob, min_inliers,
+                                 max_its))
+        return rc;
+    if (!sim3_solvers_ok(s) || !m) return ORBHIP_E_ARG;
+    if (C == 0) return ORBHIP_OK;
+    return sim3_setup_launch(m, C, cur, d_kf_index, cam, rows, cap, np, t, d_matched12, match_form, level_sigma2, prob, min_inliers, max_its, s);
+}
+
+static int sim3_iterate_launch(orbhip_matcher *m, int C, int cap, const orbhip_camera *cam, const orbhip_sim3_solvers *s, const void *d_draws,
+                               int max_its, int n_iterations, int min_inliers, int fix_scale, void *d_sim3, void *d_inliers, void *d_report)
+{
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const int n_iter = std::min(n_iterations, max_its);
+    void *work;
+    if (int rc = scratch(m, S_SIM3, sim3_workspace_bytes(C, n_iter, cap), &work)) return rc;
+    Sim3Args A;
+    memset(&A, 0, sizeof(A));
+    sim3_solvers(A, s);
+    sim3_camera(A, cam);
+    A.draws = (const int *)d_draws; A.sim3 = (float *)d_sim3; A.inliers = (uint8_t *)d_inliers; A.report = (int *)d_report;
+    A.C = C; A.cap = cap; A.max_its = max_its; A.n_iter = n_iter; A.min_inliers = min_inliers; A.fix_scale = fix_scale != 0;
+    return launch_sim3_iterate(m->stream, A, work);
+}
+
+int orbhip_sim3_iterate_device(orbhip_matcher *m, int C, int cap, const orbhip_camera *cam, const orbhip_sim3_solvers *s, const void *d_draws,
+                               int max_its, int n_iterations, int min_inliers, int fix_scale, void *d_sim3, void *d_inliers, void *d_report)
+{
+    if (int rc = sim3_params("sim3_iterate", C, cap, cam, min_inliers, max_its)) return rc;
+    if (!sim3_solvers_ok(s) || n_iterations < 0 || !d_draws || !d_sim3 || !d_inliers || !d_report || !m) return ORBHIP_E_ARG;
+    if (C == 0) return ORBHIP_OK;
+    return sim3_iterate_launch(m, C, cap, cam, s, d_draws, max_its, n_iterations, min_inliers, fix_scale, d_sim3, d_inliers, d_report);
+}
+
+// N of candidate row kf as k_sim3_setup counts it, for the draw check of the host form
+static int sim3_host_count(int cur, int kf, int cap, const orbhip_sim3_tables *t, const int32_t *matched, int match_form)
+{
+    const int32_t *slot_point = (const int32_t *)t->slot_point, *n = (const int32_t *)t->n, *obs_start = (const int32_t *)t->obs_start;
+    const int32_t *obs_kf = (const int32_t *)t->obs_kf;
+    const uint8_t *flags = (const uint8_t *)t->flags;
+    auto observed = [&](int p, int row) {
+        for (int o = obs_start[p]; o < obs_start[p + 1]; ++o)
+            if (obs_kf[o] == row) return true;
+        return false;
+    };
+    int N = 0;
+    for (int i1 = 0; i1 < n[cur]; ++i1) {
+        const int mt = matched[i1];
+        if (mt < 0) continue;
+        const int p2 = match_form == ORBHIP_SIM3_MATCH_SLOTS ? slot_point[(size_t)kf * cap + mt] : mt;
+        const int p1 = slot_point[(size_t)cur * cap + i1];
+        if (p1 < 0 || p2 < 0 || !(flags[p1] & ORBHIP_POINT_PRESENT) || !(flags[p2] & ORBHIP_POINT_PRESENT)) continue;
+        if (observed(p1, cur) && observed(p2, kf)) ++N;
+    }
+    return N;
+}
+
+int orbhip_sim3_ransac(orbhip_matcher *m, int C, int cur, const int32_t *kf_index, const orbhip_camera *cam, int rows, int cap, int np,
+                       int pcap, const orbhip_sim3_tables *t, const int32_t *matched12, int match_form, const float *level_sigma2,
+                       double prob, int min_inliers, int max_its, int fix_scale, const int32_t *draws, int n_iterations, int32_t *state,
+                       float *sim3, uint8_t *inliers, int32_t *report)
+{
+    if (int rc = sim3_setup_args(C, cur, kf_index, cam, rows, cap, np, pcap, t, matched12, match_form, level_sigma2, prob, min_inliers,
+                                 max_its))
+        return rc;
+    if (n_iterations < 0 || !draws || !sim3 || !inliers || !report) return ORBHIP_E_ARG;
+    const int32_t *slot_point = (const int32_t *)t->slot_point, *n = (const int32_t *)t->n, *obs_start = (const int32_t *)t->obs_start;
+    const int32_t *obs_kf = (const int32_t *)t->obs_kf, *obs_idx = (const int32_t *)t->obs_idx;
+    const orbhip_keypoint *kps = (const orbhip_keypoint *)t->kps;
+    const size_t RC = (size_t)rows * cap, P = (size_t)np, Cn = (size_t)C;
+    for (int r = 0; r < rows; ++r)
+        if (n[r] < 0 || n[r] > cap) { set_error("sim3_ransac: bank row %d holds a count outside [0, cap]", r); return ORBHIP_E_ARG; }
+    for (size_t i = 0; i < RC; ++i)
+        if (slot_point[i] < -1 || slot_point[i] >= np) { set_error("sim3_ransac: bank row %zu holds a point index out of range", i / cap); return ORBHIP_E_ARG; }
+    if (obs_start[0] != 0) { set_error("sim3_ransac: obs_start must start at 0"); return ORBHIP_E_ARG; }
+    for (int p = 0; p < np; ++p)
+        if (obs_start[p + 1] < obs_start[p]) { set_error("sim3_ransac: obs_start must be non-decreasing (entry %d)", p); return ORBHIP_E_ARG; }
+    const size_t total = (size_t)obs_start[np];
+    for (size_t o = 0; o < total; ++o) {
+        if (obs_kf[o] < 0 || obs_kf[o] >= rows || obs_idx[o] < 0 || obs_idx[o] >= cap) { set_error("sim3_ransac: observation %zu is outside the bank", o); return ORBHIP_E_ARG; }
+        const int oct = kps[(size_t)obs_kf[o] * cap + obs_idx[o]].octave;
+        if (oct < 0 || oct >= cam->n_levels) { set_error("sim3_ransac: observation %zu names a key point of octave %d", o, oct); return ORBHIP_E_ARG; }
+    }
+    const int n_iter = std::min(n_iterations, max_its);
+    for (int c = 0; c < C; ++c) {
+        const int kf = kf_index[c];
+        if (kf < 0 || kf >= rows) { set_error("sim3_ransac: candidate %d (row %d) is outside the bank", c, kf); return ORBHIP_E_ARG; }
+        const int32_t *mt = matched12 + (size_t)c * cap;
+        for (int i1 = 0; i1 < n[cur]; ++i1)
+            if (mt[i1] >= (match_form == ORBHIP_SIM3_MATCH_SLOTS ? cap : np)) { set_error("sim3_ransac: match %d of candidate %d is out of range", i1, c); return ORBHIP_E_ARG; }
+        const int it0 = state ? state[2 * c] : 0;
+        if (it0 < 0 || it0 > max_its || (state && state[2 * c + 1] < 0)) { set_error("sim3_ransac: the state of candidate %d is out of range", c); return ORBHIP_E_ARG; }
+        const int N = sim3_host_count(cur, kf, cap, t, mt, match_form);
+        const int last = std::min(sim3_limit_of(N, prob, min_inliers, max_its), it0 + n_iter);
+        for (int it = it0; it < last; ++it)
+            for (int k = 0; k < 3; ++k) {
+                const int d = draws[((size_t)c * max_its + it) * 3 + k];
+                if (d < 0 || d > N - 1 - k) { set_error("sim3_ransac: draw %d of iteration %d of candidate %d is %d, outside [0, %d]", k, it, c, d, N - 1 - k); return ORBHIP_E_ARG; }
+            }
+    }
+    if (!m) return ORBHIP_E_ARG;
+    if (C == 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const size_t CC = Cn * cap;
+    Stage st;
+    int rc;
+    const size_t in_bytes = 2 * al256(RC * 4) + al256(RC * sizeof(orbhip_keypoint)) + al256(P * 4 + 4) + 2 * al256(total * 4) + al256(P) +
+                            al256(P * 12) + al256((size_t)rows * 48) + al256((size_t)rows * 4) + al256(Cn * 4) + al256(CC * 4) +
+                            al256(Cn * max_its * 12);
+    const size_t out_size = al256(Cn * 64) + al256(CC) + al256(Cn * 32) + al256(Cn * 8);
+    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
+    orbhip_sim3_tables dt;
+    dt.slot_point = st.put(slot_point, RC); dt.obs_start = st.put(obs_start, P + 1); dt.obs_kf = st.put(obs_kf, total);
+    dt.obs_idx = st.put(obs_idx, total); dt.flags = st.put((const uint8_t *)t->flags, P); dt.world = st.put((const float *)t->world, P * 3);
+    dt.Tcw = st.put((const float *)t->Tcw, (size_t)rows * 12); dt.kps = st.put(kps, RC); dt.n = st.put(n, (size_t)rows);
+    const int32_t *d_kf = st.put(kf_index, Cn), *d_matched = st.put(matched12, CC), *d_draws = st.put(draws, Cn * max_its * 3);
+    const size_t out_off = st.off;
+    const float *d_sim3 = st.put(sim3, Cn * 16);
+    const uint8_t *d_inl = st.put(inliers, CC);
+    const int32_t *d_rep = st.put(report, Cn * 8), *d_state;
+    int32_t *h_state = st.take(Cn * 2, &d_state);
+    if (h_state) {
+        if (state) memcpy(h_state, state, Cn * 8); else memset(h_state, 0, Cn * 8);
+    }
+    const size_t out_bytes = st.off - out_off;
+    // the solvers live in the handle for the length of the call
+    void *sv;
+    if ((rc = scratch(m, S_SIM3SOLV, 11 * al256(CC * 12), &sv))) return rc;
+    uint8_t *w = (uint8_t *)sv;
+    auto carve = [&](size_t bytes) { void *p = w; w += al256(bytes); return p; };
+    orbhip_sim3_solvers ds;
+    ds.x1 = carve(CC * 12); ds.x2 = carve(CC * 12); ds.p1 = carve(CC * 8); ds.p2 = carve(CC * 8); ds.max_err1 = carve(CC * 4);
+    ds.max_err2 = carve(CC * 4); ds.slot1 = carve(CC * 4); ds.n_corr = carve(Cn * 4); ds.n1 = carve(Cn * 4); ds.limit = carve(Cn * 4);
+    ds.state = carve(Cn * 8);
+    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = sim3_setup_launch(m, C, cur, d_kf, cam, rows, cap, np, &dt, d_matched, match_form, level_sigma2, prob, min_inliers, max_its, &ds)))
+        return rc;
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(ds.state, d_state, Cn * 8, hipMemcpyDeviceToDevice, m->stream));
+    if ((rc = sim3_iterate_launch(m, C, cap, cam, &ds, d_draws, max_its, n_iterations, min_inliers, fix_scale, (void *)d_sim3, (void *)d_inl,
+                                  (void *)d_rep)))
+        return rc;
+    ORBHIP_HIP_CHECK(hipMemcpyAsync((void *)d_state, ds.state, Cn * 8, hipMemcpyDeviceToDevice, m->stream));
+    const uint8_t *h;
+    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
+    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
+    back(sim3, d_sim3, Cn * 64); back(inliers, d_inl, CC); back(report, d_rep, Cn * 32);
+    if (state) back(state, d_state, Cn * 8);
     return ORBHIP_OK;
 }
 

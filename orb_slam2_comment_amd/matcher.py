@@ -661,6 +661,132 @@ class ORBmatcher:
                                                       C.byref(rio), C.byref(rs), int(id0_row), int(U), d_cand, int(bool(mono)),
                                                       float(np.float32(th_depth)), d_report), "orbhip_cull_key_frames_device")
 
+    # -- Sim3 RANSAC (src/Sim3Solver.cc) ---------------------------------------
+    SIM3_TABLES = tuple(k for k, _ in capi.Sim3Tables._fields_)
+    SIM3_SOLVERS = tuple(k for k, _ in capi.Sim3Solvers._fields_)
+    _SIM3_DTYPES = dict(slot_point=np.int32, obs_start=np.int32, obs_kf=np.int32, obs_idx=np.int32, flags=np.uint8,
+                        world=np.float32, Tcw=np.float32, kps=capi.KP_DTYPE, n=np.int32)
+
+    @staticmethod
+    def _sigma2(level_sigma2, cam):
+        sig = np.ascontiguousarray(level_sigma2, np.float32)
+        if len(sig) < cam.n_levels:
+            raise ValueError("level_sigma2 needs one entry per pyramid level")
+        return sig
+
+    def Sim3SetupDevice(self, C_, cur, d_kf_index, cam, rows, cap, np_, pcap, tables, d_matched12, match_form, level_sigma2,
+                        solvers, prob=0.99, min_inliers=20, max_its=300):
+        """The Sim3Solver constructor and SetRansacParameters for C_ candidates (orbhip_sim3_setup_device in
+        include/orbhip.h): `tables` and `solvers` are dicts with the keys of SIM3_TABLES / SIM3_SOLVERS holding device
+        addresses (ints, or tensors).  Asynchronous on the matcher's stream."""
+        sig = self._sigma2(level_sigma2, cam)
+        rt, rs = self._record(capi.Sim3Tables, tables), self._record(capi.Sim3Solvers, solvers)
+        dp = lambda a: a.data_ptr() if hasattr(a, "data_ptr") else a  # noqa: E731
+        check(self._lib.orbhip_sim3_setup_device(self._h, int(C_), int(cur), dp(d_kf_index), C.byref(cam), int(rows), int(cap),
+                                                 int(np_), int(pcap), C.byref(rt), dp(d_matched12), int(match_form), ptr(sig),
+                                                 float(prob), int(min_inliers), int(max_its), C.byref(rs)),
+              "orbhip_sim3_setup_device")
+
+    def Sim3IterateDevice(self, C_, cap, cam, solvers, d_draws, max_its, n_iterations, min_inliers, fix_scale, d_sim3,
+                          d_inliers, d_report):
+        """Sim3Solver::iterate for every candidate at once (orbhip_sim3_iterate_device): at most n_iterations more
+        iterations each, draws[c][it] serving iteration number it.  Asynchronous on the matcher's stream."""
+        rs = self._record(capi.Sim3Solvers, solvers)
+        dp = lambda a: a.data_ptr() if hasattr(a, "data_ptr") else a  # noqa: E731
+        check(self._lib.orbhip_sim3_iterate_device(self._h, int(C_), int(cap), C.byref(cam), C.byref(rs), dp(d_draws),
+                                                   int(max_its), int(n_iterations), int(min_inliers), int(bool(fix_scale)),
+                                                   dp(d_sim3), dp(d_inliers), dp(d_report)), "orbhip_sim3_iterate_device")
+
+    def _sim3_tables(self, tables):
+        T = {}
+        for k in self.SIM3_TABLES:
+            if tables.get(k) is None:
+                raise ValueError("tables[%r] is missing" % k)
+            T[k] = np.ascontiguousarray(tables[k], self._SIM3_DTYPES[k])
+        if T["slot_point"].ndim != 2:
+            raise ValueError("slot_point is [rows, cap]")
+        rows, cap = T["slot_point"].shape
+        T["Tcw"] = np.ascontiguousarray(T["Tcw"].reshape(rows, -1, 4)[:, :3, :]).reshape(rows, 12)
+        return T, rows, cap, len(T["obs_start"]) - 1, len(T["flags"])
+
+    def Sim3Setup(self, tables, cur, kf_index, cam, matched12, match_form, level_sigma2, prob=0.99, min_inliers=20,
+                  max_its=300, fill=0):
+        """Sim3SetupDevice from host arrays: `tables` is a dict with the keys of SIM3_TABLES (slot_point [rows, cap], n
+        [rows], obs_start [np+1], obs_kf, obs_idx, flags [pcap], world [pcap, 3], Tcw [rows, 12 or 4x4], kps [rows, cap]
+        KP_DTYPE), matched12 [C, cap].  The arrays are uploaded as torch tensors; the returned solver record keeps them and
+        the solver state on the device for Sim3Iterate, and holds host copies of the solver arrays under "host" (entries
+        the call does not write hold `fill` bytes)."""
+        import torch
+        T, rows, cap, n_pts, pcap = self._sim3_tables(tables)
+        kf = np.ascontiguousarray(kf_index, np.int32).reshape(-1)
+        Cn = len(kf)
+        m12 = np.ascontiguousarray(matched12, np.int32).reshape(Cn, cap)
+        dev = torch.device("cuda")
+        up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(4, np.uint8)).to(dev)  # noqa: E731
+        dT = {k: up(v) for k, v in T.items()}
+        shapes = dict(x1=(cap, 3), x2=(cap, 3), p1=(cap, 2), p2=(cap, 2), max_err1=(cap,), max_err2=(cap,), slot1=(cap,),
+                      n_corr=(), n1=(), limit=(), state=(2,))
+        dS = {k: torch.full((max(Cn, 1) * int(np.prod(shapes[k], dtype=np.int64)) * 4,), fill, dtype=torch.uint8, device=dev)
+              for k in self.SIM3_SOLVERS}
+        d_kf, d_m12 = up(kf), up(m12)
+        torch.cuda.synchronize()
+        self.Sim3SetupDevice(Cn, cur, d_kf, cam, rows, cap, n_pts, pcap, dT, d_m12, match_form, level_sigma2, dS, prob,
+                             min_inliers, max_its)
+        self.sync()
+        dts = dict(x1=np.float32, x2=np.float32, p1=np.float32, p2=np.float32, max_err1=np.uint32, max_err2=np.uint32)
+        host = {k: dS[k].cpu().numpy().view(dts.get(k, np.int32))[:Cn * int(np.prod(shapes[k], dtype=np.int64))]
+                .reshape((Cn,) + shapes[k]).copy() for k in self.SIM3_SOLVERS}
+        return dict(C=Cn, cap=cap, cam=cam, tables=dT, solvers=dS, keep=(d_kf, d_m12), host=host, min_inliers=int(min_inliers),
+                    max_its=int(max_its))
+
+    def Sim3Iterate(self, solver, draws, n_iterations, fix_scale=False, fill=0):
+        """Sim3IterateDevice on the record Sim3Setup returned; draws [C, max_its, 3] int32.  Returns (report [C, 8] int32
+        in the order of capi.SIM3_REPORT, sim3 [C, 16] float32, inliers [C, cap] uint8); sim3 rows of candidates that did
+        not return, and inliers behind n1, hold `fill` bytes.  The solver's state advances on the device."""
+        import torch
+        Cn, cap, max_its = solver["C"], solver["cap"], solver["max_its"]
+        d = np.ascontiguousarray(draws, np.int32).reshape(Cn, max_its, 3)
+        dev = torch.device("cuda")
+        d_draws = torch.from_numpy(d.reshape(-1).copy() if d.size else np.zeros(3, np.int32)).to(dev)
+        d_sim3 = torch.full((max(Cn, 1) * 64,), fill, dtype=torch.uint8, device=dev)
+        d_inl = torch.full((max(Cn, 1) * cap,), fill, dtype=torch.uint8, device=dev)
+        d_rep = torch.full((max(Cn, 1) * 32,), fill, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        self.Sim3IterateDevice(Cn, cap, solver["cam"], solver["solvers"], d_draws, max_its, n_iterations, solver["min_inliers"],
+                               fix_scale, d_sim3, d_inl, d_rep)
+        self.sync()
+        solver["host"]["state"] = solver["solvers"]["state"].cpu().numpy().view(np.int32)[:Cn * 2].reshape(Cn, 2).copy()
+        return (d_rep.cpu().numpy().view(np.int32)[:Cn * 8].reshape(Cn, 8).copy(),
+                d_sim3.cpu().numpy().view(np.float32)[:Cn * 16].reshape(Cn, 16).copy(),
+                d_inl.cpu().numpy()[:Cn * cap].reshape(Cn, cap).copy())
+
+    def Sim3Ransac(self, tables, cur, kf_index, cam, matched12, match_form, level_sigma2, draws, fix_scale=False, prob=0.99,
+                   min_inliers=20, max_its=300, n_iterations=None, state=None, fill=0):
+        """Setup and iterate from host arrays in one staged copy, one device sequence and one read-back
+        (orbhip_sim3_ransac), range-checked (OrbHipError with E_ARG), draws included.  n_iterations None = max_its, i.e.
+        Sim3Solver::find; `state` [C, 2] resumes solvers an earlier call left.  Returns dict(report [C, 8], sim3 [C, 16],
+        inliers [C, cap], state [C, 2]); what the call does not write holds `fill` bytes."""
+        T, rows, cap, n_pts, pcap = self._sim3_tables(tables)
+        kf = np.ascontiguousarray(kf_index, np.int32).reshape(-1)
+        Cn = len(kf)
+        m12 = np.ascontiguousarray(matched12, np.int32).reshape(Cn, cap)
+        d = np.ascontiguousarray(draws, np.int32).reshape(Cn, max_its, 3)
+        sig = self._sigma2(level_sigma2, cam)
+        st = np.zeros((max(Cn, 1), 2), np.int32)
+        if state is not None:
+            st[:Cn] = np.asarray(state, np.int32).reshape(Cn, 2)
+        sim3 = np.full(max(Cn, 1) * 64, fill, np.uint8).view(np.float32).reshape(-1, 16)
+        inl = np.full((max(Cn, 1), cap), fill, np.uint8)
+        rep = np.full(max(Cn, 1) * 32, fill, np.uint8).view(np.int32).reshape(-1, 8)
+        keep = {k: (np.zeros(1, a.dtype) if a.size == 0 else a) for k, a in T.items()}
+        rt = self._record(capi.Sim3Tables, {k: ptr(a).value for k, a in keep.items()})
+        pad = [np.zeros(3, np.int32) if a.size == 0 else a for a in (kf, m12, d)]
+        check(self._lib.orbhip_sim3_ransac(self._h, Cn, int(cur), ptr(pad[0]), C.byref(cam), rows, cap, n_pts, pcap, C.byref(rt),
+                                           ptr(pad[1]), int(match_form), ptr(sig), float(prob), int(min_inliers), int(max_its),
+                                           int(bool(fix_scale)), ptr(pad[2]), int(max_its if n_iterations is None else n_iterations),
+                                           ptr(st), ptr(sim3), ptr(inl), ptr(rep)), "orbhip_sim3_ransac")
+        return dict(report=rep[:Cn].copy(), sim3=sim3[:Cn].copy(), inliers=inl[:Cn].copy(), state=st[:Cn].copy())
+
     # -- device-resident, batched SearchByProjection ---------------------------
     def set_stream(self, stream):
         check(self._lib.orbhip_matcher_set_stream(self._h, stream), "orbhip_matcher_set_stream")
@@ -963,6 +1089,20 @@ class SeedReplay:
 
     def summary(self):
         return "mean close points per frame: %.2f" % (sum(self.close) / len(self.close) if self.close else 0.0)
+
+
+def sim3_draws(C_, max_its, n_corr, seed):
+    """Valid draws for Sim3Iterate / Sim3Ransac: [C, max_its, 3] int32 from numpy.random.default_rng(seed), draw k of
+    candidate c uniform in [0, n_corr[c] - 1 - k], which is what DUtils::Random::RandomInt(0, size - 1) returns for the
+    shrinking list (src/Sim3Solver.cc:168).  Candidates with fewer than three correspondences get zeros (never read)."""
+    rng = np.random.default_rng(seed)
+    n = np.broadcast_to(np.asarray(n_corr, np.int64).reshape(-1), (int(C_),))
+    out = np.zeros((int(C_), int(max_its), 3), np.int32)
+    for c in range(int(C_)):
+        if n[c] >= 3:
+            for k in range(3):
+                out[c, :, k] = rng.integers(0, n[c] - k, int(max_its))
+    return out
 
 
 def RadiusByViewingCos(viewCos):
