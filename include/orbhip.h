@@ -241,7 +241,15 @@ int orbhip_extractor_set_stream(orbhip_extractor *e, void *stream);
 /* mvImagePyramid[level] of frame `frame` of the last extract call: size and device pointer of
  * the level ROI (valid until the next extract on this handle); row stride in bytes.  The ROI is
  * surrounded by the 19-px BORDER_REFLECT_101 frame the reference allocates
- * (src/ORBextractor.cc:1113-1128), so d_roi[-19*stride-19] is addressable. */
+ * (src/ORBextractor.cc:1113-1128), so d_roi[-19*stride-19] is addressable.
+ * Frame rule: an extraction writes a level's interior and only the inner 8 px of its frame (level 0 of a handle with
+ * orbhip_extractor_set_lazy_level0: nothing).  The rest of the frames is written by the first call after the extraction
+ * that can read it -- this one when d_roi is asked for (enqueued on the handle's stream), orbhip_pyramid_level_download
+ * with_border, orbhip_blurred_level_download -- so the ROI's surrounding frame is valid from this call on, for every
+ * frame and level of the batch, until the next extraction.  A pointer kept from before that extraction addresses the
+ * same plane, whose frame is then stale until one of these calls is made again.  orbhip_compute_stereo_matches* does
+ * not need the frames of the levels >= 1 for keypoints the handles' extraction produced (16 px inside their level), and
+ * does not ask for them. */
 int orbhip_pyramid_level(orbhip_extractor *e, int frame, int level, int *rows, int *cols,
                          int *stride, const void **d_roi);
 /* Copy a level to host.  with_border != 0 copies the (rows+38)x(cols+38) padded plane. */

@@ -140,6 +140,19 @@ __device__ __forceinline__ uint32_t resize_px(const uint8_t *S0, const uint8_t *
 }
 
 constexpr int kPyrRows = 4;   // destination rows per thread (independent loads in flight)
+// Eager frame depth of the levels >= 1 (pyr_span.h): how much of a level's 19-px REFLECT_101 frame the table-driven
+// pyramid kernels write during an extraction; the accessors get the rest from ensure_frames.  The next level resizes
+// the interior and FAST cells start 13 px inside, so the only reader inside an extraction is the descriptor kernel: a
+// border keypoint's window overshoots the level by <= 6 px.  0: nothing of the frame is written and that kernel reflects
+// the overshoot by index (a byte gather for 4-14 % of the keypoints); >= 6: its windows stay inside what is written;
+// kEdge: the full frame, as before there was a choice.  Measured: 8 beats 0 on the headline -- the
+// gather costs the descriptor kernel more issue slots than 8 px of frame cost the pyramid -- and both beat 19.
+// `make frame0` builds the F = 0 variant (tests/test_pyramid_frames_gpu.py runs it in a child process).
+#ifndef ORBHIP_PYR_FRAME
+#define ORBHIP_PYR_FRAME 8
+#endif
+constexpr int kPyrFrame = ORBHIP_PYR_FRAME;
+static_assert(kPyrFrame >= 0 && kPyrFrame <= kEdge, "the eager frame is part of the 19-px frame");
 
 // OpenCV's fixed-point bilinear coefficients of one destination coordinate d (resize INTER_LINEAR, 8U):
 // f = (float)((d + 0.5) * scale - 0.5) in double, s = floor(f), f -= s, clamped at the ends; coefficients
@@ -260,7 +273,8 @@ __global__ __launch_bounds__(256) void k_pyr_resize(uint8_t *__restrict__ pyr, P
 // row addresses) is wave-uniform and lives on the scalar unit; everything that depends on the column comes from a
 // per-lane table record that is the same for every row and every frame.  The REFLECT_101 frame is part of the
 // tables (a border lane gathers the reflected interior columns through the same instructions), so no wavefront
-// ever runs a second code path.
+// ever runs a second code path -- all 19 px of it for level 0, the inner kPyrFrame px for the levels >= 1, whose
+// tables start at the first row and dword of that span (PyrLevelTab::plane_off) and count from there.
 //  * level 0 (copyMakeBorder of the input image): per lane one unaligned 16-byte load + six v_perm_b32 + one
 //    16-byte store per row;
 //  * level l >= 1 (resize INTER_LINEAR 8U + copyMakeBorder): per lane two unaligned 8-byte loads per row, and per
@@ -401,6 +415,31 @@ __global__ __launch_bounds__(256) void k_pyr_rows(uint8_t *__restrict__ pyr, uin
     if (unit >= T.units) return;
     uint8_t *frame = pyr + (size_t)fr * frame_bytes;
     pyr_resize_rows(T, unit, frame + T.src_off, T.src_pitch, frame + T.plane_off);
+}
+
+// The REFLECT_101 frames of the levels >= 1 (the levels of `levels`, a bit mask), for the accessors: every byte of a
+// padded plane that the full-frame tables used to write and that is not interior -- dwords [0, (kPadL + w + kEdge + 3) / 4)
+// of every padded row -- as the reflection of the level's own interior, 0 outside the 19-px frame.  Not a hot path: a
+// workgroup per padded row, a thread per byte.  Interior bytes are only read, frame bytes only written.
+__global__ __launch_bounds__(256) void k_pyr_frames(uint8_t *__restrict__ pyr, PyrGeom G, unsigned levels)
+{
+    int l = 1, py = (int)blockIdx.x;
+    for (; l < G.nlevels; ++l) {   // wave-uniform: the level and padded row of this workgroup
+        if (!((levels >> l) & 1u)) continue;
+        if (py < G.lv[l].prows) break;
+        py -= G.lv[l].prows;
+    }
+    if (l >= G.nlevels) return;
+    const int w = G.lv[l].w, h = G.lv[l].h, pitch = G.lv[l].pitch;
+    uint8_t *plane = pyr + (size_t)blockIdx.y * G.frame_bytes + G.lv[l].plane_off;
+    const int nbytes = ((kPadL + w + kEdge + 3) >> 2) * 4;
+    const bool irow = py >= kEdge && py < kEdge + h;   // an interior row keeps bytes [kPadL, kPadL + w)
+    const uint8_t *srow = plane + (size_t)(kEdge + reflect101(py - kEdge, h)) * pitch + kPadL;
+    uint8_t *drow = plane + (size_t)py * pitch;
+    for (int i = (int)threadIdx.x; i < (irow ? nbytes - w : nbytes); i += 256) {
+        const int c = irow && i >= kPadL ? i + w : i, x = c - kPadL;
+        drow[c] = x >= -kEdge && x < w + kEdge ? srow[reflect101(x, w)] : (uint8_t)0;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -708,6 +747,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORBHIP_FAST_
     // LDS column of sub-image x: col = x + a + 4 (a = misalignment of x0; the dword on the left holds real pixels).
     // Lane = (row mod RPI, dword column); a batch is U row groups, all loads issued before the first LDS store.  Row
     // groups past the sub-image re-read its last rows (scalar clamp) into LDS rows that nothing looks at.
+    // A staged row is SW dwords from column x0 - 5 whatever the cell's width: at a narrow last cell of a row of cells it
+    // runs past the level's right edge, into frame bytes that an extraction does not write.  Those are LDS columns
+    // >= sw + 5; the compares read LDS columns [5, sw + 5) only (detection columns [8, 8 + dw) and their radius-3 ring),
+    // and the pixels of a row's last group beyond the detection rectangle are masked (en[]): no such byte reaches a compare.
     {
         const int c = lane & (LPR - 1), r = lane / LPR;
         // level-0 cells of a handle that does not materialise mvImagePyramid[0] read the caller's image itself (a FAST
@@ -1734,7 +1777,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ORBHIP_DESC
     const uint32_t hitems = hitem_tab[lane];
     uint32_t *win = swin[wv];
     uint4 *hs = shsum[wv];
-  int level = 0, before = 0, mine = 0, kp_base = 0, kp_end = -1, pitch = 0;
+  int level = 0, before = 0, mine = 0, kp_base = 0, kp_end = -1, pitch = 0, lw = 0, lh = 0;
   for (int kk = 0; kk < per_wave; ++kk) {
     const int slot = (bx * 4 + wv) * per_wave + kk;  // wave-uniform: everything up to the pixel loads is scalar work
     if (slot >= G.kp_cap_total) break;
@@ -1753,6 +1796,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ORBHIP_DESC
             if (l == level) mine = c;
         }
         kp_base = G.lv[level].kp_base; kp_end = kp_base + G.lv[level].kp_cap; pitch = G.lv[level].pitch;
+        lw = G.lv[level].w; lh = G.lv[level].h;
     }
     const int i = slot - kp_base;
     if (i >= mine) continue;
@@ -1763,28 +1807,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ORBHIP_DESC
     const int kx = (int)(kv & 0xfff) + 16, ky = (int)((kv >> 12) & 0xfff) + 16;  // + minBorder (:843-844)
     const int resp = (int)(kv >> 24);
     uint32_t wvv[kWinLoads];
-    // level 0 of a handle that does not materialise mvImagePyramid[0]: the window comes from the caller's image; the up
-    // to 5 px it overshoots the image near the border are REFLECT_101 by index (what copyMakeBorder would have written)
+    // The window overshoots the level by up to 5 px (6 on the right) for a keypoint of the outer strip of the keypoint
+    // area.  What lies there depends on the source: level 0 of a handle that does not materialise mvImagePyramid[0] comes
+    // from the caller's image, which has no frame; a materialised level 0 has its full 19-px frame; a level >= 1 has the
+    // kPyrFrame px of frame that the pyramid kernels write eagerly.  A window that leaves what is there is gathered byte
+    // by byte with REFLECT_101 by index (what copyMakeBorder would have written); `inside` is stated with the keypoint's
+    // own level size.
     const bool from_img = images != nullptr && level == 0;
-    const bool inside = kx >= 21 && kx + 22 < G.lv[0].w && ky >= 21 && ky + 21 < G.lv[0].h;
-    if (from_img && !inside) {   // wave-uniform: a border keypoint gathers its window byte by byte
-        const uint8_t *ib = images + (size_t)b * img_frame_stride;
+    const int fd = from_img ? 0 : level == 0 ? kEdge : kPyrFrame;   // frame depth of the source, wave-uniform
+    const bool inside = kx - 21 >= -fd && kx + 22 < lw + fd && ky - 21 >= -fd && ky + 21 < lh + fd;
+    const int wpitch = from_img ? img_stride : pitch;
+    const uint8_t *roi = from_img   // pixel (0, 0) of the level, uniform
+        ? images + (size_t)b * img_frame_stride
+        : pyr + (size_t)b * G.frame_bytes + G.lv[level].plane_off + (size_t)kEdge * pitch + kPadL;
+    if (!inside) {   // wave-uniform: a border keypoint gathers its window byte by byte
         uint32_t cx[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) cx[k] = (uint32_t)reflect101(kx - 21 + 4 * scol + k, G.lv[0].w);
+        for (int k = 0; k < 4; ++k) cx[k] = (uint32_t)reflect101(kx - 21 + 4 * scol + k, lw);
 #pragma unroll
         for (int u = 0; u < kWinLoads; ++u) {
             wvv[u] = 0u;
             if (lane < kWinRpi * kWinDw && (u < kWinLoads - 1 || srow < kWinRows - (kWinLoads - 1) * kWinRpi)) {
-                const uint8_t *rp = ib + (size_t)((uint32_t)reflect101(ky - 21 + srow + u * kWinRpi, G.lv[0].h) * (uint32_t)img_stride);
+                const uint8_t *rp = roi + (size_t)((uint32_t)reflect101(ky - 21 + srow + u * kWinRpi, lh) * (uint32_t)wpitch);
                 wvv[u] = (uint32_t)rp[cx[0]] | ((uint32_t)rp[cx[1]] << 8) | ((uint32_t)rp[cx[2]] << 16) | ((uint32_t)rp[cx[3]] << 24);
             }
         }
     } else {
-        const int wpitch = from_img ? img_stride : pitch;
-        const uint8_t *wb = from_img
-            ? images + (size_t)b * img_frame_stride + (size_t)(ky - 21) * img_stride + (kx - 21)
-            : pyr + (size_t)b * G.frame_bytes + G.lv[level].plane_off + (size_t)kEdge * pitch + kPadL + (size_t)(ky - 21) * pitch + (kx - 21);   // window byte (0, 0), uniform
+        const uint8_t *wb = roi + (ptrdiff_t)(ky - 21) * wpitch + (kx - 21);   // window byte (0, 0), uniform
         const uint32_t voff = (uint32_t)(__mul24(srow, wpitch) + 4 * scol);
 #pragma unroll
         for (int u = 0; u < kWinLoads; ++u) {
@@ -2024,7 +2073,10 @@ static int build_pyr_tables(orbhip_extractor *e)
         }
         const LevelGeom &P = G.lv[l - 1];
         const double sx = 1. / ((double)L.w / P.w), sy = 1. / ((double)L.h / P.h);   // OpenCV: scale = 1. / ((double)dst / src)
-        T.words = (kPadL + L.w + kEdge + 3) >> 2;
+        // the level's eager span: interior + kPyrFrame px of frame (pyr_span.h); table row 0 / dword 0 are its first ones
+        const PyrSpan S = pyr_span(L.w, L.h, kPyrFrame, kEdge, kPadL);
+        T.words = S.words; T.prows = S.rows;
+        T.plane_off = L.plane_off + (unsigned)(S.row0 * L.pitch + S.col0 * 4);
         T.src_h = P.h; T.src_pitch = P.pitch;
         T.src_off = P.plane_off + (unsigned)(kEdge * P.pitch + kPadL);
         std::vector<PyrCol> col(T.words);
@@ -2034,8 +2086,8 @@ static int build_pyr_tables(orbhip_extractor *e)
             int sxk[4], a0[4], a1[4], lo_ = 1 << 30, hi_ = -1;
             bool valid[4];
             for (int k = 0; k < 4; ++k) {
-                const int x = pw * 4 - kPadL + k;
-                valid[k] = x >= -kEdge && x < L.w + kEdge;
+                const int x = (S.col0 + pw) * 4 - kPadL + k;
+                valid[k] = x >= -kPyrFrame && x < L.w + kPyrFrame;
                 sxk[k] = 0; a0[k] = a1[k] = 0;
                 if (!valid[k]) continue;
                 int s1;
@@ -2044,8 +2096,8 @@ static int build_pyr_tables(orbhip_extractor *e)
             }
             if (hi_ < 0) { lo_ = 0; hi_ = 0; }
             if (hi_ - lo_ > 6) { ok = false; break; }
-            lo_ = std::min(lo_, P.w - 8);
-            lo[pw] = (uint32_t)lo_;
+            lo_ = std::min(lo_, P.w - 8);   // the 8-byte window [lo, lo + 8) lies inside the source's interior columns [0, P.w):
+            lo[pw] = (uint32_t)lo_;         // no tap comes from level l-1's frame, which an extraction does not write
             for (int k = 0; k < 4; ++k) {
                 if (!valid[k]) { col[pw].sel[k] = 0x0c0c0c0cu; col[pw].alv[k] = 0; continue; }
                 const int rel = sxk[k] - lo_;
@@ -2057,10 +2109,10 @@ static int build_pyr_tables(orbhip_extractor *e)
             }
         }
         if (!ok) continue;   // this level keeps the general kernel
-        std::vector<PyrRow> row(L.prows);
-        for (int py = 0; py < L.prows; ++py) {
-            int s0, s1, b0, b1;
-            host_resize_coef(host_reflect101(py - kEdge, L.h), sy, P.h, true, s0, s1, b0, b1);
+        std::vector<PyrRow> row(S.rows);
+        for (int py = 0; py < S.rows; ++py) {
+            int s0, s1, b0, b1;   // both source rows are clamped to [0, P.h): interior rows of level l-1
+            host_resize_coef(host_reflect101(S.row0 + py - kEdge, L.h), sy, P.h, true, s0, s1, b0, b1);
             row[py].s0 = s0; row[py].s1 = s1; row[py].B0 = (uint32_t)b0 << 12; row[py].B1 = (uint32_t)b1 << 12;
         }
         pyr_chunks(T, kPyrRows);
@@ -2315,6 +2367,7 @@ static int begin_extraction(orbhip_extractor *e, const uint8_t *d_images, int st
     e->cells_stride = want;
     e->l0_in_image = lazy;
     e->l0_valid = !lazy;
+    e->frames_valid = kPyrFrame == kEdge;   // the pyramid kernels write kPyrFrame px of the levels' frames (ensure_frames)
     e->src_images = d_images; e->src_stride = stride; e->src_frame_stride = frame_stride;
     return ORBHIP_OK;
 }
@@ -2322,6 +2375,16 @@ static int begin_extraction(orbhip_extractor *e, const uint8_t *d_images, int st
 // The padded level-0 planes of the last batch, for the accessors that read them (orbhip_pyramid_level*, the blurred
 // planes, ComputeStereoMatches): written now, from the image buffer of the last extraction, if that extraction skipped
 // them.  `consumer`: a stream that will read the planes (ordered behind the copy), or null.
+static int order_behind(orbhip_extractor *e, hipStream_t consumer)
+{
+    if (consumer && consumer != e->stream) {
+        if (!e->ev_l0) ORBHIP_HIP_CHECK(hipEventCreateWithFlags(&e->ev_l0, hipEventDisableTiming));
+        ORBHIP_HIP_CHECK(hipEventRecord(e->ev_l0, e->stream));
+        ORBHIP_HIP_CHECK(hipStreamWaitEvent(consumer, e->ev_l0, 0));
+    }
+    return ORBHIP_OK;
+}
+
 int orbhip::ensure_level0(orbhip_extractor *e, hipStream_t consumer)
 {
     if (!e || !e->bound || e->last_batch <= 0) return ORBHIP_OK;
@@ -2334,12 +2397,30 @@ int orbhip::ensure_level0(orbhip_extractor *e, hipStream_t consumer)
         ORBHIP_HIP_CHECK(hipGetLastError());
         e->l0_valid = true;
     }
-    if (consumer && consumer != e->stream) {
-        if (!e->ev_l0) ORBHIP_HIP_CHECK(hipEventCreateWithFlags(&e->ev_l0, hipEventDisableTiming));
-        ORBHIP_HIP_CHECK(hipEventRecord(e->ev_l0, e->stream));
-        ORBHIP_HIP_CHECK(hipStreamWaitEvent(consumer, e->ev_l0, 0));
+    return order_behind(e, consumer);
+}
+
+// The REFLECT_101 frames of levels 1 .. n-1 of the last batch (every slot of it: the chunked host path keeps all
+// chunks' planes resident), for the accessors that can read a frame byte: an extraction writes only kPyrFrame px of
+// them, the rest is the reflection of each level's own interior and is written now, once per extraction.  Levels
+// that go through the general kernel (k_pyr_resize) have their full frames already.  Enqueued on the handle's stream
+// like ensure_level0's copy, also inside a stream capture.
+int orbhip::ensure_frames(orbhip_extractor *e, hipStream_t consumer)
+{
+    if (!e || !e->bound || e->last_batch <= 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(e->device));
+    if (!e->frames_valid) {
+        unsigned levels = 0;
+        int rows = 0;
+        for (int l = 1; l < e->G.nlevels; ++l)
+            if (e->ptab_rows[l]) { levels |= 1u << l; rows += e->G.lv[l].prows; }
+        if (rows > 0) {
+            hipLaunchKernelGGL(k_pyr_frames, dim3(rows, e->last_batch), dim3(256), 0, e->stream, e->d_pyr, e->G, levels);
+            ORBHIP_HIP_CHECK(hipGetLastError());
+        }
+        e->frames_valid = true;
     }
-    return ORBHIP_OK;
+    return order_behind(e, consumer);
 }
 
 // `frame0`: first internal frame slot of this launch (the host path runs a batch as several chunks, each in its own
@@ -3271,7 +3352,8 @@ int orbhip_pyramid_level(orbhip_extractor *e, int frame, int level, int *rows, i
 {
     if (!e || !e->bound || frame < 0 || frame >= e->last_batch || level < 0 || level >= e->nlevels) return ORBHIP_E_ARG;
     const LevelGeom &L = e->G.lv[level];
-    if (level == 0 && d_roi) { if (int rc = ensure_level0(e, nullptr)) return rc; }
+    // the ROI's surrounding frame is valid from this call on
+    if (d_roi) { if (int rc = level == 0 ? ensure_level0(e, nullptr) : ensure_frames(e, nullptr)) return rc; }
     if (rows) *rows = L.h;
     if (cols) *cols = L.w;
     if (stride) *stride = L.pitch;
@@ -3315,6 +3397,7 @@ static int download_plane(orbhip_extractor *e, const uint8_t *base, int frame, i
 int orbhip_pyramid_level_download(orbhip_extractor *e, int frame, int level, int with_border, uint8_t *dst, int dst_stride)
 {
     if (level == 0) { if (int rc = ensure_level0(e, nullptr)) return rc; }
+    else if (with_border) { if (int rc = ensure_frames(e, nullptr)) return rc; }
     return download_plane(e, e ? e->d_pyr : nullptr, frame, level, with_border, dst, dst_stride);
 }
 
@@ -3324,6 +3407,7 @@ int orbhip_blurred_level_download(orbhip_extractor *e, int frame, int level, uin
         // the pipeline blurs patches inside the descriptor kernel; the full blurred planes (and their buffer) are
         // produced on request
         if (int rc = ensure_level0(e, nullptr)) return rc;
+        if (int rc = ensure_frames(e, nullptr)) return rc;   // k_blur's taps reach into every level's frame
         if (!e->d_blur) ORBHIP_HIP_CHECK(hipMalloc(&e->d_blur, (size_t)e->batch_cap * e->G.frame_bytes));
         hipLaunchKernelGGL(k_blur, dim3((unsigned)e->tiles.size(), e->last_batch), dim3(256), 0, e->stream, e->d_pyr, e->d_blur, e->G,
                            e->d_tiles, e->blurw);

@@ -1,6 +1,7 @@
 // Internal (non-ABI) definitions shared by the extractor and matcher translation units.
 #pragma once
 #include "orbhip_common.h"
+#include "pyr_span.h"
 
 #include <vector>
 
@@ -42,16 +43,18 @@ struct PyrLevelTab {
     const PyrRow *row;       // [prows]                      (resize only)
     const void *col;         // [words] PyrCol / PyrCopyCol
     const uint32_t *lo;      // [words] first source byte of the lane's window
-    int words;               // lanes per padded row: dwords (resize) or 16-byte groups (copy)
+    int words;               // lanes per destination row: dwords (resize) or 16-byte groups (copy)
     int nchunks, chunk_w;    // a row is split into nchunks runs of chunk_w <= 64 lanes
     uint32_t rcp_chunks;     // ceil(2^32 / nchunks)
     int units;               // wavefront work items = row groups x nchunks
-    int prows, pitch;        // destination plane
-    unsigned plane_off;
+    int prows, pitch;        // destination rows the tables cover, row pitch of the plane
+    unsigned plane_off;      // destination byte of table row 0, lane 0, inside a frame's pyramid block: the padded plane for
+                             // level 0; for a level >= 1 the first dword of its eager span (pyr_span.h: row0, col0)
     int src_h, src_pitch;    // source: rows (level-0 copy: REFLECT_101 of the row index), pitch for levels >= 2
     unsigned src_off;        // source ROI inside the frame's pyramid block (levels >= 2)
 };
 int ensure_level0(orbhip_extractor *e, hipStream_t consumer);   // orbhip_extractor.hip
+int ensure_frames(orbhip_extractor *e, hipStream_t consumer);   // orbhip_extractor.hip
 
 // orbhip_localmap.hip: the tables, in/out lists and outputs of orbhip_update_local_map_device, and its workspace
 struct LocalMapArgs {
@@ -259,6 +262,8 @@ struct orbhip_extractor {
     int cells_stride = 0;           // image row stride the level-0 entries of d_cells2 are built for (0: the padded plane)
     const uint8_t *src_images = nullptr; int src_stride = 0; size_t src_frame_stride = 0;   // image buffer of the last extraction
     hipEvent_t ev_l0 = nullptr;
+    // the REFLECT_101 frames of levels >= 1 on demand (ensure_frames): an extraction writes each level's eager span only
+    bool frames_valid = true;       // d_pyr holds the full frames of levels >= 1 of the last batch
     // stage gates (orbhip_extractor_set_stage_gate): events other pipelines' handles record / wait for
     hipEvent_t gate_wait[4] = {nullptr, nullptr, nullptr, nullptr}, gate_rec[4] = {nullptr, nullptr, nullptr, nullptr};
     float4 *d_patternf = nullptr;   // rBRIEF pattern as floats: (x0, y0, x1, y1) per test

@@ -4739,6 +4739,13 @@ int orbhip_compute_stereo_matches_device(orbhip_matcher *m, orbhip_extractor *le
     // mvImagePyramid[0] of handles that produce it on demand; this launch is ordered behind the copy
     if (int rc = ensure_level0(left, m->stream)) return rc;
     if (right != left) { if (int rc = ensure_level0(right, m->stream)) return rc; }
+    // The REFLECT_101 frames of the levels >= 1, which an extraction does not write in full, are NOT asked for
+    // (ensure_frames): no byte of them reaches a result.  k_stereo_match stages rows cv-5 .. cv+5, bytes cu-5 .. cu+6 (left)
+    // and cr-10 .. cr+13 (right), and reads cr-10 .. cr+10 of the latter.  The keypoints are those of the handles'
+    // extraction: 16 px inside their own level (cu in [16, w-17], cv in [16, h-17]), the right one at most one level from
+    // the left one's, i.e. at 16 / 1.2 = 13.3 <= x <= w - 13.2 of the left one's level after scaling: cr in [13, w-13].
+    // Every byte that is read lies in columns [3, w-3] and rows [11, h-12] of the interior; of the staged bytes only
+    // cr+11 .. cr+13, which nothing reads, can reach column w, the first frame byte
     const StereoBatch B = {(const int *)d_n_l, (const int *)d_n_r, l0, ls, r0, rs, cap, 0, 0};
     return launch_stereo(m, left, 0, right, 0, pairs, B, (const orbhip_keypoint *)d_kps_l, (const uint8_t *)d_desc_l,
                          (const orbhip_keypoint *)d_kps_r, (const uint8_t *)d_desc_r, mbf, mb, (float *)d_u_right, (float *)d_depth,
@@ -6525,6 +6532,7 @@ int orbhip_compute_stereo_matches(orbhip_matcher *m, orbhip_extractor *left, int
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     if (int rc = ensure_level0(left, nullptr)) return rc;     // mvImagePyramid[0] of handles that produce it on demand
     if (int rc = ensure_level0(right, nullptr)) return rc;
+    // (the frames of the levels >= 1 are not needed: orbhip_compute_stereo_matches_device)
     // the pyramids were produced on the extractors' streams
     ORBHIP_HIP_CHECK(hipStreamSynchronize(left->stream));
     ORBHIP_HIP_CHECK(hipStreamSynchronize(right->stream));
