@@ -1144,6 +1144,115 @@ int orbhip_sim3_ransac(orbhip_matcher *m, int C, int cur, const int32_t *kf_inde
                        const float *level_sigma2, double prob, int min_inliers, int max_its, int fix_scale, const int32_t *draws,
                        int n_iterations, int32_t *state, float *sim3, uint8_t *inliers, int32_t *report);
 
+/* ---- PnP RANSAC -----------------------------------------------------------------------------------------------------------
+ * PnPsolver (src/PnPsolver.cc) for the current frame and C relocalisation candidates in one call each: the step of
+ * Tracking::Relocalization (src/Tracking.cc:1341-1500) between orbhip_search_by_bow_device and
+ * orbhip_search_by_projection_keyframe.  orbhip_pnp_setup_device is the constructor (:67-110) with SetRansacParameters
+ * (:121-157); orbhip_pnp_iterate_device is iterate (:165-258) for every candidate at once; PnPsolver::find (:159-163) is
+ * iterate(mRansacMaxIts) and has no entry of its own.  The arithmetic, operation by operation, is tests/seqref/pnp.py and
+ * DESIGN.md section 3 (Jacobi methods in fp64 stand in for cvSVD, cvInvert(CV_SVD) and cvSolve(CV_SVD)).  The reference
+ * draws with DUtils::Random; here the draws are caller data.
+ *
+ * orbhip_pnp_params = the arguments of SetRansacParameters: prob, min_inliers, max_its, min_set, epsilon, th2 (the
+ * reference's relocalisation passes 0.99, 10, 300, 4, 0.5, 5.991).  min_set must be 4 (the sample of :191 is what EPnP
+ * here is built for), min_inliers >= 1, max_its in [1, 65536], 0 < prob < 1, epsilon and th2 finite and >= 0.
+ * orbhip_pnp_map (read only): flags [pcap] uint8 (ORBHIP_POINT_PRESENT = !isBad()), world [pcap][3] float = mWorldPos,
+ *   slot_point [rows][cap] int32 = mvpMapPoints of the candidate key frames as point indices, -1 = none (read only with
+ *   ORBHIP_PNP_MATCH_SLOTS; may be NULL otherwise).
+ * orbhip_pnp_solvers (device state the caller owns, one row per candidate; written by setup, read and advanced by iterate):
+ *   p2d [C][cap][2] float = mvP2D, p3d [C][cap][3] float = mvP3Dw,
+ *   max_err [C][cap] float = mvMaxError = mvSigma2[i] * th2 as a float product (a vector<float>, :156),
+ *   kp_index [C][cap] int32 = mvKeyPointIndices, n_corr [C] int32 = N,
+ *   min_inliers [C] int32 = mRansacMinInliers after the adjustment, limit [C] int32 = mRansacMaxIts after it (0 where
+ *     N is below the adjusted minimum: iterate never runs then, :173),
+ *   state [C][2] int32 = {mnIterations, mnBestInliers},
+ *   best_inliers [C][cap] uint8 = mvbBestInliers over the correspondences, best_Tcw [C][12] float = mBestTcw: written by
+ *     iterate when an iteration sets a new best (:212-224), meaningful while state[c][1] > 0; setup leaves them alone.
+ *   Entries behind n_corr keep the caller's bytes.
+ *
+ * orbhip_pnp_setup_device: d_kps [n] orbhip_keypoint = mvKeysUn of the current frame (x, y and octave are read), n <= cap
+ * slots.  d_matches [C][cap] int32 = vpMapPointMatches per slot, negative = none: point indices (ORBHIP_PNP_MATCH_POINTS)
+ * or key-point slots of bank row d_kf_index[c] as orbhip_search_by_bow_device writes them (ORBHIP_PNP_MATCH_SLOTS; mapped
+ * through slot_point, whose rows have the same `cap`; a slot without a point is no match; rows may repeat).  A slot i < n is
+ * kept iff it has a match and the point is ORBHIP_POINT_PRESENT (:83-85); the kept ones are compacted in slot order.
+ * level_sigma2 [cam->n_levels] = mvLevelSigma2 (host).  The adjustment of :134-152 depends on N and the parameters only:
+ *   nMinInliers = (int)((float)N * epsilon), raised to min_inliers, then to min_set; epsilon raised to
+ *   (float)nMinInliers / N; the limit is 1 when nMinInliers == N, otherwise
+ *   ceil(log(1 - prob) / log(1 - pow(epsilon, 3))) -- exponent 3 although the sample is 4 -- clamped to [1, max_its] (the
+ *   quotient is clamped while still a double; the text converts to int first).
+ * The library computes the cap + 1 pairs on the host, keeps them in the handle and rebuilds them only when the parameters
+ * or cap change (that one call waits for the stream and uploads the table; no other call synchronises).  state is zeroed.
+ *
+ * orbhip_pnp_iterate_device: d_draws [C][draw_rows][4] int32: row `it` serves iteration number `it`, so a later call
+ * continues in the same array; draw k lies in [0, N-1-k] and stands for RandomInt(0, vAvailableIndices.size()-1) (:193).
+ * The loop condition of :182 is an OR: a call runs the iterations mnIterations ... max(limit, mnIterations +
+ * n_iterations) - 1 unless it returns earlier -- a first call with n_iterations = 5 runs to the limit, a call on a solver
+ * at its limit runs n_iterations more.  draw_rows >= max(max_its, n_iterations) is required (ORBHIP_E_ARG otherwise: a
+ * fresh solver can reach that many); the limit and the state live on the device, so iterations a resumed solver would
+ * run at or behind draw_rows are not run (the host form refuses such a call instead).
+ * All hypotheses of the call are computed and scored at once.  Refine() (:260-305) refines mvbBestInliers, not the
+ * current hypothesis, and is deterministic, so it runs once per best set: for the set the record holds and for every
+ * iteration whose count passes the gate (>= the adjusted minimum, :209) and is strictly above the running best (:212).
+ * The iteration that returns is the first one that passes the gate while the refinement of the best set so far has more
+ * inliers than the adjusted minimum (:292, strict).
+ *   d_report [C][8] int32 = {status, N, limit, mnIterations after, mnBestInliers after, returned iteration or -1,
+ *     nInliers, adjusted min inliers}.  status, one per way out of the function:
+ *     ORBHIP_PNP_REFINED (:235, bNoMore false; mnIterations stops behind the returned iteration),
+ *     ORBHIP_PNP_BEST (:253, bNoMore true: the unrefined mBestTcw / mvbBestInliers, possibly left by an earlier call),
+ *     ORBHIP_PNP_NO_MORE (:257 with bNoMore true: the loop only ends with mnIterations >= limit),
+ *     ORBHIP_PNP_TOO_FEW (:173; the state is left alone).
+ *   d_Tcw [C][12] float = [Rcw | tcw]: written only on REFINED and BEST.
+ *   d_inliers [C][cap] uint8 = vbInliers over the key-point slots of the frame (vbInliers[mvKeyPointIndices[i]]): on REFINED
+ *     and BEST entries i < n are zeroed, then set; otherwise untouched.
+ * n, cap and the parameters must be the values setup was given.  Five launches; the hypotheses, counts, masks and
+ * refinements of a call live in the handle.  A NaN or inf from a degenerate sample (coplanar or repeated points, zero
+ * depth) propagates: every comparison is false, 0 inliers, nothing faults.
+ *
+ * Both: asynchronous on the matcher's stream, no host synchronisation, no staging copy.  cap <= 4096 (ORBHIP_E_CAPACITY
+ * beyond); C, n, rows or np negative, n > cap, np > pcap, cap < 1, a bad match_form, min_set != 4, parameters outside the
+ * ranges above or a null pointer: ORBHIP_E_ARG; all refused before any device work.  C == 0: success, nothing written.
+ * The device forms do not range-check the matches, the candidate rows, the state or the draws (a draw outside its range
+ * is clamped into the list). */
+#define ORBHIP_PNP_MATCH_POINTS 0
+#define ORBHIP_PNP_MATCH_SLOTS  1
+#define ORBHIP_PNP_REFINED 0
+#define ORBHIP_PNP_BEST    1
+#define ORBHIP_PNP_NO_MORE 2
+#define ORBHIP_PNP_TOO_FEW 3
+typedef struct orbhip_pnp_params {
+    double prob;
+    int32_t min_inliers, max_its, min_set;
+    float epsilon, th2;
+} orbhip_pnp_params;
+typedef struct orbhip_pnp_map {
+    const void *flags, *world, *slot_point;
+} orbhip_pnp_map;
+typedef struct orbhip_pnp_solvers {
+    void *p2d, *p3d, *max_err, *kp_index, *n_corr, *min_inliers, *limit, *state, *best_inliers, *best_Tcw;
+} orbhip_pnp_solvers;
+int orbhip_pnp_setup_device(orbhip_matcher *m, int C, const void *d_kps, int n, int cap, const void *d_matches, int match_form,
+                            const void *d_kf_index, int rows, int np, int pcap, const orbhip_pnp_map *map,
+                            const orbhip_camera *cam, const float *level_sigma2, const orbhip_pnp_params *params,
+                            const orbhip_pnp_solvers *solvers);
+int orbhip_pnp_iterate_device(orbhip_matcher *m, int C, int n, int cap, const orbhip_camera *cam, const orbhip_pnp_params *params,
+                              const orbhip_pnp_solvers *solvers, const void *d_draws, int draw_rows, int n_iterations,
+                              void *d_Tcw, void *d_inliers, void *d_report);
+/* Host buffers, synchronous: one staging copy, setup + iterate(n_iterations), one read-back.  kps [n], matches [C][cap],
+ * kf_index [C] (NULL allowed with ORBHIP_PNP_MATCH_POINTS), the map record with host pointers, draws [C][draw_rows][4].
+ * state [C][2], best_inliers [C][cap] and best_Tcw [C][12] are in/out and nullable together: NULL (or a zero state) is a
+ * fresh solver; passing back what an earlier call left resumes it, which is how the reference's five-iterations-at-a-time
+ * loop runs over this form (the setup is recomputed, it is a function of the inputs).  Tcw [C][12], inliers [C][cap] and
+ * report [C][8] as above (what the call does not write keeps the caller's values).  It range-checks what the device forms
+ * do not: matches below np (points) or cap (slots), kf_index in [0, rows), slot_point in [-1, np), octaves in
+ * [0, cam->n_levels), state[c][0] >= 0, state[c][1] either 0 or in [adjusted minimum, N] and equal to the number of set
+ * entries of best_inliers[c], draw_rows large enough for every iteration the call runs, and every such draw in
+ * [0, N-1-k]: ORBHIP_E_ARG, before the handle is looked at, nothing written. */
+int orbhip_pnp_ransac(orbhip_matcher *m, int C, const orbhip_keypoint *kps, int n, int cap, const int32_t *matches, int match_form,
+                      const int32_t *kf_index, int rows, int np, int pcap, const orbhip_pnp_map *map, const orbhip_camera *cam,
+                      const float *level_sigma2, const orbhip_pnp_params *params, const int32_t *draws, int draw_rows,
+                      int n_iterations, int32_t *state, uint8_t *best_inliers, float *best_Tcw, float *Tcw, uint8_t *inliers,
+                      int32_t *report);
+
 /* ---- creating new map points -------------------------------------------------------------------------------------
  * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) for the current key frame and K neighbours in one call, up
  * to the point where the map graph is touched: `new MapPoint`, AddObservation and everything after :434 stay with the

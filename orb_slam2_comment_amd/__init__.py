@@ -8,5 +8,5 @@ the compute entry points raise if the HIP library is missing.
 from . import capi  # noqa: F401
 from .capi import KP_DTYPE, QUERY_DTYPE, OrbHipError  # noqa: F401
 from .extractor import ORBextractor, init_undistort_rectify_map  # noqa: F401
-from .matcher import FrameView, ORBmatcher, sim3_draws  # noqa: F401
+from .matcher import FrameView, ORBmatcher, pnp_draws, sim3_draws  # noqa: F401
 from .vocabulary import ORBVocabulary  # noqa: F401

@@ -91,6 +91,23 @@ class Sim3Solvers(C.Structure):
                                           "state")]
 
 
+class PnpParams(C.Structure):
+    """orbhip_pnp_params: the arguments of PnPsolver::SetRansacParameters."""
+    _fields_ = [("prob", C.c_double), ("min_inliers", C.c_int32), ("max_its", C.c_int32), ("min_set", C.c_int32),
+                ("epsilon", C.c_float), ("th2", C.c_float)]
+
+
+class PnpMap(C.Structure):
+    """orbhip_pnp_map: the map-point tables (and, for slot matches, the bank's slot_point) the PnP setup reads."""
+    _fields_ = [(k, C.c_void_p) for k in ("flags", "world", "slot_point")]
+
+
+class PnpSolvers(C.Structure):
+    """orbhip_pnp_solvers: the per-candidate solver record on the device (written by setup, advanced by iterate)."""
+    _fields_ = [(k, C.c_void_p) for k in ("p2d", "p3d", "max_err", "kp_index", "n_corr", "min_inliers", "limit", "state",
+                                          "best_inliers", "best_Tcw")]
+
+
 POINT_PRESENT, POINT_OBSERVED = 1, 2
 COLOR_BGR, COLOR_RGB = 0, 1
 DEPTH_U16, DEPTH_F32 = 0, 1
@@ -116,6 +133,10 @@ CULLKF_REPORT = ("status", "n_mps", "n_redundant", "n_erased", "n_bad", "n_resor
 SIM3_MATCH_POINTS, SIM3_MATCH_SLOTS = range(2)
 SIM3_RETURNED, SIM3_CONTINUE, SIM3_NO_MORE, SIM3_TOO_FEW = range(4)
 SIM3_REPORT = ("status", "n_corr", "limit", "iterations", "best_inliers", "returned_iteration", "n_inliers", "reserved")
+# ORBHIP_PNP_MATCH_*: what d_matches of orbhip_pnp_setup_device holds; ORBHIP_PNP_*: report[0] of orbhip_pnp_iterate_device
+PNP_MATCH_POINTS, PNP_MATCH_SLOTS = range(2)
+PNP_REFINED, PNP_BEST, PNP_NO_MORE, PNP_TOO_FEW = range(4)
+PNP_REPORT = ("status", "n_corr", "limit", "iterations", "best_inliers", "returned_iteration", "n_inliers", "min_inliers")
 REMAP_TABLE_SIZE = 4096
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
@@ -249,6 +270,12 @@ SYMBOLS = [
                                         _vp]),
     ("orbhip_sim3_ransac", _i, [_vp, _i, _i, _vp, C.POINTER(Camera), _i, _i, _i, _i, C.POINTER(Sim3Tables), _vp, _i, _vp, _d, _i,
                                 _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("orbhip_pnp_setup_device", _i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, C.POINTER(PnpMap), C.POINTER(Camera), _vp,
+                                     C.POINTER(PnpParams), C.POINTER(PnpSolvers)]),
+    ("orbhip_pnp_iterate_device", _i, [_vp, _i, _i, _i, C.POINTER(Camera), C.POINTER(PnpParams), C.POINTER(PnpSolvers), _vp, _i,
+                                       _i, _vp, _vp, _vp]),
+    ("orbhip_pnp_ransac", _i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, C.POINTER(PnpMap), C.POINTER(Camera), _vp,
+                               C.POINTER(PnpParams), _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("orbhip_matcher_set_stream", _i, [_vp, _vp]),
     ("orbhip_matcher_sync", _i, [_vp]),
     ("orbhip_compute_stereo_matches_device", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,

@@ -214,6 +214,37 @@ struct Sim3Args {
 size_t sim3_workspace_bytes(int C, int n_iter, int cap);
 int launch_sim3_setup(hipStream_t stream, Sim3Args A);
 int launch_sim3_iterate(hipStream_t stream, Sim3Args A, void *workspace);
+
+// orbhip_pnp.hip: the inputs, the solver record and the workspace of orbhip_pnp_setup_device / orbhip_pnp_iterate_device
+struct PnpArgs {
+    const orbhip_keypoint *kps;         // [n]
+    const int *matches, *kf_index;      // [C][cap], [C]
+    const int *slot_point;              // [rows][cap]
+    const uint8_t *flags;               // [pcap]
+    const float *world;                 // [pcap][3]
+    const int *tab;                     // [cap + 1][2]: adjusted (min inliers, limit) per correspondence count
+    float max_err_lv[ORBHIP_MAX_LEVELS];   // mvLevelSigma2[l] * th2, a float product
+    float *p2d, *p3d, *max_err;         // [C][cap][2], [C][cap][3], [C][cap]
+    int *kp_index, *n_corr, *min_inliers, *limit, *state;
+    uint8_t *best_inliers;              // [C][cap]
+    float *best_Tcw;                    // [C][12]
+    const int *draws;                   // [C][draw_rows][4]
+    float *Tcw;                         // [C][12]
+    uint8_t *inliers;                   // [C][cap]
+    int *report;                        // [C][8]
+    // workspace of one iterate call, j = iteration number - mnIterations at the start of the call, e = refinement entry:
+    // hyp [C][W][12] (R, t in double), count / is_rec [C][W], mask [C][W][cap], ref_T [C][W+1][12], ref_cnt [C][W+1],
+    // ref_mask [C][W+1][cap]
+    double *hyp;
+    int *count, *is_rec, *ref_cnt;
+    uint8_t *mask, *ref_mask;
+    float *ref_T;
+    double fu, fv, uc, vc;
+    int C, n, cap, rows, np, match_form, n_levels, n_iter, draw_rows, W;
+};
+size_t pnp_workspace_bytes(int C, int W, int cap);
+int launch_pnp_setup(hipStream_t stream, PnpArgs A);
+int launch_pnp_iterate(hipStream_t stream, PnpArgs A, void *workspace);
 }  // namespace orbhip
 
 struct orbhip_extractor {

@@ -3715,8 +3715,8 @@ struct orbhip_matcher {
     hipStream_t stream = nullptr;       // stream every launch goes to
     hipStream_t own_stream = nullptr;   // created with the handle
     // grow-only device scratch
-    void *buf[23] = {};
-    size_t cap[23] = {};
+    void *buf[26] = {};
+    size_t cap[26] = {};
     bool lds_attr_set = false, bow_attr_set = false;
 #ifdef ORBHIP_DEVTOOLS
     int window_lanes = 0;               // development build: lanes per query of k_window_search forced to 16 / 64 (0: the rule)
@@ -3729,6 +3729,10 @@ struct orbhip_matcher {
     std::vector<int> sim3_limit;
     double sim3_prob = 0.0;
     int sim3_min_inliers = 0, sim3_max_its = 0, sim3_cap = -1;
+    // PnP RANSAC: the adjusted (min inliers, limit) per correspondence count, [pnp_cap + 1][2], rebuilt when a parameter changes
+    std::vector<int> pnp_tab;
+    orbhip_pnp_params pnp_params = {0.0, 0, 0, 0, 0.f, 0.f};
+    int pnp_cap = -1;
 };
 
 static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -3809,7 +3813,7 @@ static SigmaTab sigma_tab(const float *inv_level_sigma2, int n_levels)
     return sig;
 }
 
-enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_COVIS, S_CULL, S_SIM3, S_SIM3LIM, S_SIM3SOLV, S_NSLOTS };
+enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_COVIS, S_CULL, S_SIM3, S_SIM3LIM, S_SIM3SOLV, S_PNP, S_PNPTAB, S_PNPSOLV, S_NSLOTS };
 static_assert(S_NSLOTS == sizeof(orbhip_matcher::buf) / sizeof(void *), "one scratch buffer per slot");
 
 static int stage_begin(orbhip_matcher *m, size_t total, Stage *st)
@@ -6070,6 +6074,244 @@ int orbhip_sim3_ransac(orbhip_matcher *m, int C, int cur, const int32_t *kf_inde
     auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
     back(sim3, d_sim3, Cn * 64); back(inliers, d_inl, CC); back(report, d_rep, Cn * 32);
     if (state) back(state, d_state, Cn * 8);
+    return ORBHIP_OK;
+}
+
+// ---- PnP RANSAC (kernels: orbhip_pnp.hip) ------------------------------------------------------------------------------
+// SetRansacParameters (src/PnPsolver.cc:134-152) as a function of N: the adjusted mRansacMinInliers and mRansacMaxIts, with
+// the reference's types.  The quotient is clamped while still a double (the text converts it to int first).
+static void pnp_parameters_of(int N, const orbhip_pnp_params *p, int *n_min_out, int *limit_out)
+{
+    float eps = p->epsilon;
+    int n_min = (int)((float)N * eps);                   // :134, a float product
+    if (n_min < p->min_inliers) n_min = p->min_inliers;
+    if (n_min < p->min_set) n_min = p->min_set;
+    *n_min_out = n_min;
+    if (N < n_min) { *limit_out = 0; return; }          // iterate never runs (:173)
+    const float q = (float)n_min / (float)N;
+    if (eps < q) eps = q;
+    if (n_min == N) { *limit_out = 1; return; }
+    const double d = std::ceil(std::log(1 - p->prob) / std::log(1 - std::pow((double)eps, 3)));
+    *limit_out = !(d >= 1.0) ? 1 : (d > (double)p->max_its ? p->max_its : (int)d);
+}
+
+static bool pnp_params_equal(const orbhip_pnp_params &a, const orbhip_pnp_params &b)
+{
+    return a.prob == b.prob && a.min_inliers == b.min_inliers && a.max_its == b.max_its && a.min_set == b.min_set &&
+           a.epsilon == b.epsilon && a.th2 == b.th2;
+}
+static int pnp_common_args(const char *who, int C, int n, int cap, const orbhip_camera *cam, const orbhip_pnp_params *p)
+{
+    if (C < 0 || n < 0 || cap < 1 || n > cap || !cam || !p) return ORBHIP_E_ARG;
+    if (p->min_set != 4) { set_error("%s: min_set must be 4", who); return ORBHIP_E_ARG; }
+    if (p->min_inliers < 1 || p->max_its < 1 || !(p->prob > 0.0 && p->prob < 1.0) || !(p->epsilon >= 0.f) || !(p->th2 >= 0.f) ||
+        !std::isfinite(p->epsilon) || !std::isfinite(p->th2))
+        return ORBHIP_E_ARG;
+    if (cap > kGridMax) { set_error("%s: capacity %d exceeds %d", who, cap, kGridMax); return ORBHIP_E_CAPACITY; }
+    if (p->max_its > 65536) { set_error("%s: %d iterations exceed 65536", who, p->max_its); return ORBHIP_E_CAPACITY; }
+    return ORBHIP_OK;
+}
+static bool pnp_solvers_ok(const orbhip_pnp_solvers *s)
+{
+    return s && s->p2d && s->p3d && s->max_err && s->kp_index && s->n_corr && s->min_inliers && s->limit && s->state &&
+           s->best_inliers && s->best_Tcw;
+}
+static int pnp_setup_args(int C, const void *kps, int n, int cap, const void *matches, int match_form, const void *kf_index, int rows,
+                          int np, int pcap, const orbhip_pnp_map *map, const orbhip_camera *cam, const float *level_sigma2,
+                          const orbhip_pnp_params *p)
+{
+    if (int rc = pnp_common_args("pnp_setup", C, n, cap, cam, p)) return rc;
+    if (rows < 0 || np < 0 || pcap < 0 || np > pcap || !kps || !matches || !level_sigma2 || cam->n_levels < 1 ||
+        cam->n_levels > ORBHIP_MAX_LEVELS || !map || !map->flags || !map->world ||
+        (match_form != ORBHIP_PNP_MATCH_POINTS && match_form != ORBHIP_PNP_MATCH_SLOTS))
+        return ORBHIP_E_ARG;
+    if (match_form == ORBHIP_PNP_MATCH_SLOTS && (!kf_index || !map->slot_point)) return ORBHIP_E_ARG;
+    return ORBHIP_OK;
+}
+static void pnp_solvers(PnpArgs &A, const orbhip_pnp_solvers *s)
+{
+    A.p2d = (float *)s->p2d; A.p3d = (float *)s->p3d; A.max_err = (float *)s->max_err; A.kp_index = (int *)s->kp_index;
+    A.n_corr = (int *)s->n_corr; A.min_inliers = (int *)s->min_inliers; A.limit = (int *)s->limit; A.state = (int *)s->state;
+    A.best_inliers = (uint8_t *)s->best_inliers; A.best_Tcw = (float *)s->best_Tcw;
+}
+static void pnp_camera(PnpArgs &A, const orbhip_camera *cam)
+{
+    A.fu = (double)cam->fx; A.fv = (double)cam->fy; A.uc = (double)cam->cx; A.vc = (double)cam->cy; A.n_levels = cam->n_levels;
+}
+
+static int pnp_setup_launch(orbhip_matcher *m, int C, const void *d_kps, int n, int cap, const void *d_matches, int match_form,
+                            const void *d_kf_index, int rows, int np, const orbhip_pnp_map *map, const orbhip_camera *cam,
+                            const float *level_sigma2, const orbhip_pnp_params *p, const orbhip_pnp_solvers *s)
+{
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    void *d_tab;
+    const size_t tab_bytes = ((size_t)cap + 1) * 2 * sizeof(int);
+    if (int rc = scratch(m, S_PNPTAB, tab_bytes, &d_tab)) return rc;
+    if (m->pnp_cap != cap || !pnp_params_equal(m->pnp_params, *p)) {
+        ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));   // the table a previous call may still read is about to change
+        m->pnp_tab.resize(((size_t)cap + 1) * 2);
+        for (int N = 0; N <= cap; ++N) pnp_parameters_of(N, p, &m->pnp_tab[2 * (size_t)N], &m->pnp_tab[2 * (size_t)N + 1]);
+        ORBHIP_HIP_CHECK(hipMemcpy(d_tab, m->pnp_tab.data(), tab_bytes, hipMemcpyHostToDevice));
+        m->pnp_cap = cap; m->pnp_params = *p;
+    }
+    PnpArgs A;
+    memset(&A, 0, sizeof(A));
+    A.kps = (const orbhip_keypoint *)d_kps; A.matches = (const int *)d_matches; A.kf_index = (const int *)d_kf_index;
+    A.slot_point = (const int *)map->slot_point; A.flags = (const uint8_t *)map->flags; A.world = (const float *)map->world;
+    A.tab = (const int *)d_tab;
+    pnp_solvers(A, s);
+    pnp_camera(A, cam);
+    for (int l = 0; l < ORBHIP_MAX_LEVELS; ++l) A.max_err_lv[l] = l < cam->n_levels ? level_sigma2[l] * p->th2 : 0.f;   // :156
+    A.C = C; A.n = n; A.cap = cap; A.rows = rows; A.np = np; A.match_form = match_form;
+    return launch_pnp_setup(m->stream, A);
+}
+
+int orbhip_pnp_setup_device(orbhip_matcher *m, int C, const void *d_kps, int n, int cap, const void *d_matches, int match_form,
+                            const void *d_kf_index, int rows, int np, int pcap, const orbhip_pnp_map *map, const orbhip_camera *cam,
+                            const float *level_sigma2, const orbhip_pnp_params *params, const orbhip_pnp_solvers *s)
+{
+    if (int rc = pnp_setup_args(C, d_kps, n, cap, d_matches, match_form, d_kf_index, rows, np, pcap, map, cam, level_sigma2, params))
+        return rc;
+    if (!pnp_solvers_ok(s) || !m) return ORBHIP_E_ARG;
+    if (C == 0) return ORBHIP_OK;
+    return pnp_setup_launch(m, C, d_kps, n, cap, d_matches, match_form, d_kf_index, rows, np, map, cam, level_sigma2, params, s);
+}
+
+static int pnp_iterate_launch(orbhip_matcher *m, int C, int n, int cap, const orbhip_camera *cam, const orbhip_pnp_params *p,
+                              const orbhip_pnp_solvers *s, const void *d_draws, int draw_rows, int n_iterations, void *d_Tcw,
+                              void *d_inliers, void *d_report)
+{
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const int W = std::min(std::max(p->max_its, n_iterations), draw_rows);   // no call runs more iterations than this
+    void *work;
+    if (int rc = scratch(m, S_PNP, pnp_workspace_bytes(C, W, cap), &work)) return rc;
+    PnpArgs A;
+    memset(&A, 0, sizeof(A));
+    pnp_solvers(A, s);
+    pnp_camera(A, cam);
+    A.draws = (const int *)d_draws; A.Tcw = (float *)d_Tcw; A.inliers = (uint8_t *)d_inliers; A.report = (int *)d_report;
+    A.C = C; A.n = n; A.cap = cap; A.n_iter = n_iterations; A.draw_rows = draw_rows; A.W = W;
+    return launch_pnp_iterate(m->stream, A, work);
+}
+
+int orbhip_pnp_iterate_device(orbhip_matcher *m, int C, int n, int cap, const orbhip_camera *cam, const orbhip_pnp_params *params,
+                              const orbhip_pnp_solvers *s, const void *d_draws, int draw_rows, int n_iterations, void *d_Tcw,
+                              void *d_inliers, void *d_report)
+{
+    if (int rc = pnp_common_args("pnp_iterate", C, n, cap, cam, params)) return rc;
+    if (!pnp_solvers_ok(s) || n_iterations < 0 || n_iterations > 65536 || !d_draws || !d_Tcw || !d_inliers || !d_report || !m)
+        return ORBHIP_E_ARG;
+    if (draw_rows < std::max(params->max_its, n_iterations)) {
+        set_error("pnp_iterate: %d draw rows, a fresh solver can reach %d", draw_rows, std::max(params->max_its, n_iterations));
+        return ORBHIP_E_ARG;
+    }
+    if (C == 0) return ORBHIP_OK;
+    return pnp_iterate_launch(m, C, n, cap, cam, params, s, d_draws, draw_rows, n_iterations, d_Tcw, d_inliers, d_report);
+}
+
+int orbhip_pnp_ransac(orbhip_matcher *m, int C, const orbhip_keypoint *kps, int n, int cap, const int32_t *matches, int match_form,
+                      const int32_t *kf_index, int rows, int np, int pcap, const orbhip_pnp_map *map, const orbhip_camera *cam,
+                      const float *level_sigma2, const orbhip_pnp_params *params, const int32_t *draws, int draw_rows, int n_iterations,
+                      int32_t *state, uint8_t *best_inliers, float *best_Tcw, float *Tcw, uint8_t *inliers, int32_t *report)
+{
+    if (int rc = pnp_setup_args(C, kps, n, cap, matches, match_form, kf_index, rows, np, pcap, map, cam, level_sigma2, params)) return rc;
+    if (n_iterations < 0 || n_iterations > 65536 || draw_rows < 0 || !draws || !Tcw || !inliers || !report) return ORBHIP_E_ARG;
+    if ((state != nullptr) != (best_inliers != nullptr) || (state != nullptr) != (best_Tcw != nullptr)) {
+        set_error("pnp_ransac: state, best_inliers and best_Tcw go together");
+        return ORBHIP_E_ARG;
+    }
+    const bool slots = match_form == ORBHIP_PNP_MATCH_SLOTS;
+    const int32_t *slot_point = (const int32_t *)map->slot_point;
+    const uint8_t *flags = (const uint8_t *)map->flags;
+    const size_t RC = slots ? (size_t)rows * cap : 0, P = (size_t)np, Cn = (size_t)C, CC = Cn * cap;
+    for (size_t i = 0; i < RC; ++i)
+        if (slot_point[i] < -1 || slot_point[i] >= np) { set_error("pnp_ransac: bank row %zu holds a point index out of range", i / cap); return ORBHIP_E_ARG; }
+    for (int i = 0; i < n; ++i)
+        if (kps[i].octave < 0 || kps[i].octave >= cam->n_levels) { set_error("pnp_ransac: key point %d has octave %d", i, kps[i].octave); return ORBHIP_E_ARG; }
+    for (int c = 0; c < C; ++c) {
+        const int kf = slots ? kf_index[c] : 0;
+        if (slots && (kf < 0 || kf >= rows)) { set_error("pnp_ransac: candidate %d (row %d) is outside the bank", c, kf); return ORBHIP_E_ARG; }
+        const int32_t *mt = matches + (size_t)c * cap;
+        int N = 0;
+        for (int i = 0; i < n; ++i) {
+            if (mt[i] >= (slots ? cap : np)) { set_error("pnp_ransac: match %d of candidate %d is out of range", i, c); return ORBHIP_E_ARG; }
+            if (mt[i] < 0) continue;
+            const int p = slots ? slot_point[(size_t)kf * cap + mt[i]] : mt[i];
+            if (p >= 0 && (flags[p] & ORBHIP_POINT_PRESENT)) ++N;
+        }
+        int n_min, limit;
+        pnp_parameters_of(N, params, &n_min, &limit);
+        const int it0 = state ? state[2 * c] : 0, best = state ? state[2 * c + 1] : 0;
+        if (it0 < 0 || it0 > 65536 || (best != 0 && (best < n_min || best > N))) { set_error("pnp_ransac: the state of candidate %d is out of range", c); return ORBHIP_E_ARG; }
+        if (best > 0) {
+            int set = 0;
+            for (int i = 0; i < N; ++i) set += best_inliers[(size_t)c * cap + i] ? 1 : 0;
+            if (set != best) { set_error("pnp_ransac: best_inliers of candidate %d holds %d entries, the state says %d", c, set, best); return ORBHIP_E_ARG; }
+        }
+        if (N < n_min) continue;
+        const int last = std::max(limit, it0 + n_iterations);
+        if (last > draw_rows) { set_error("pnp_ransac: candidate %d runs to iteration %d, draws has %d rows", c, last, draw_rows); return ORBHIP_E_ARG; }
+        for (int it = it0; it < last; ++it)
+            for (int k = 0; k < 4; ++k) {
+                const int d = draws[((size_t)c * draw_rows + it) * 4 + k];
+                if (d < 0 || d > N - 1 - k) { set_error("pnp_ransac: draw %d of iteration %d of candidate %d is %d, outside [0, %d]", k, it, c, d, N - 1 - k); return ORBHIP_E_ARG; }
+            }
+    }
+    if (!m) return ORBHIP_E_ARG;
+    if (C == 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    Stage st;
+    int rc;
+    const size_t in_bytes = al256((size_t)n * sizeof(orbhip_keypoint)) + al256(CC * 4) + al256(Cn * 4) + al256(RC * 4) + al256(P) +
+                            al256(P * 12) + al256(Cn * draw_rows * 16);
+    const size_t out_size = al256(Cn * 48) + al256(CC) + al256(Cn * 32) + al256(Cn * 8) + al256(CC) + al256(Cn * 48);
+    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
+    const orbhip_keypoint *d_kps = st.put(kps, (size_t)n);
+    const int32_t *d_matches = st.put(matches, CC), *d_kf = slots ? st.put(kf_index, Cn) : nullptr;
+    orbhip_pnp_map dm;
+    dm.slot_point = slots ? st.put(slot_point, RC) : nullptr;
+    dm.flags = st.put(flags, P); dm.world = st.put((const float *)map->world, P * 3);
+    const int32_t *d_draws = st.put(draws, Cn * draw_rows * 4);
+    const size_t out_off = st.off;
+    const float *d_Tcw = st.put(Tcw, Cn * 12);
+    const uint8_t *d_inl = st.put(inliers, CC);
+    const int32_t *d_rep = st.put(report, Cn * 8), *d_state;
+    int32_t *h_state = st.take(Cn * 2, &d_state);
+    if (h_state) {
+        if (state) memcpy(h_state, state, Cn * 8); else memset(h_state, 0, Cn * 8);
+    }
+    const uint8_t *d_bi;
+    uint8_t *h_bi = st.take(CC, &d_bi);
+    if (h_bi) {
+        if (best_inliers) memcpy(h_bi, best_inliers, CC); else memset(h_bi, 0, CC);
+    }
+    const float *d_bt;
+    float *h_bt = st.take(Cn * 12, &d_bt);
+    if (h_bt) {
+        if (best_Tcw) memcpy(h_bt, best_Tcw, Cn * 48); else memset(h_bt, 0, Cn * 48);
+    }
+    const size_t out_bytes = st.off - out_off;
+    // the rest of the solver record lives in the handle for the length of the call
+    void *sv;
+    if ((rc = scratch(m, S_PNPSOLV, al256(CC * 8) + al256(CC * 12) + 2 * al256(CC * 4) + 4 * al256(Cn * 8), &sv))) return rc;
+    uint8_t *w = (uint8_t *)sv;
+    auto carve = [&](size_t bytes) { void *p = w; w += al256(bytes); return p; };
+    orbhip_pnp_solvers ds;
+    ds.p2d = carve(CC * 8); ds.p3d = carve(CC * 12); ds.max_err = carve(CC * 4); ds.kp_index = carve(CC * 4); ds.n_corr = carve(Cn * 4);
+    ds.min_inliers = carve(Cn * 4); ds.limit = carve(Cn * 4); ds.state = carve(Cn * 8);
+    ds.best_inliers = (void *)d_bi; ds.best_Tcw = (void *)d_bt;
+    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = pnp_setup_launch(m, C, d_kps, n, cap, d_matches, match_form, d_kf, rows, np, &dm, cam, level_sigma2, params, &ds))) return rc;
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(ds.state, d_state, Cn * 8, hipMemcpyDeviceToDevice, m->stream));
+    if ((rc = pnp_iterate_launch(m, C, n, cap, cam, params, &ds, d_draws, draw_rows, n_iterations, (void *)d_Tcw,
+                                 (void *)d_inl, (void *)d_rep)))
+        return rc;
+    ORBHIP_HIP_CHECK(hipMemcpyAsync((void *)d_state, ds.state, Cn * 8, hipMemcpyDeviceToDevice, m->stream));
+    const uint8_t *h;
+    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
+    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
+    back(Tcw, d_Tcw, Cn * 48); back(inliers, d_inl, CC); back(report, d_rep, Cn * 32);
+    if (state) { back(state, d_state, Cn * 8); back(best_inliers, d_bi, CC); back(best_Tcw, d_bt, Cn * 48); }
     return ORBHIP_OK;
 }
 

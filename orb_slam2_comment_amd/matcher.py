@@ -787,6 +787,142 @@ class ORBmatcher:
                                            ptr(st), ptr(sim3), ptr(inl), ptr(rep)), "orbhip_sim3_ransac")
         return dict(report=rep[:Cn].copy(), sim3=sim3[:Cn].copy(), inliers=inl[:Cn].copy(), state=st[:Cn].copy())
 
+    # -- PnP RANSAC (src/PnPsolver.cc) -----------------------------------------
+    PNP_SOLVERS = tuple(k for k, _ in capi.PnpSolvers._fields_)
+    _PNP_SHAPES = dict(p2d=("cap", 2, np.float32), p3d=("cap", 3, np.float32), max_err=("cap", 1, np.float32),
+                       kp_index=("cap", 1, np.int32), n_corr=(1, 1, np.int32), min_inliers=(1, 1, np.int32),
+                       limit=(1, 1, np.int32), state=(1, 2, np.int32), best_inliers=("cap", 1, np.uint8),
+                       best_Tcw=(1, 12, np.float32))
+
+    @staticmethod
+    def pnp_params(prob=0.99, min_inliers=10, max_its=300, min_set=4, epsilon=0.5, th2=5.991):
+        """The arguments of PnPsolver::SetRansacParameters as an orbhip_pnp_params record."""
+        return capi.PnpParams(float(prob), int(min_inliers), int(max_its), int(min_set), float(epsilon), float(th2))
+
+    def PnpSetupDevice(self, C_, d_kps, n, cap, d_matches, match_form, d_kf_index, rows, np_, pcap, pmap, cam, level_sigma2,
+                       params, solvers):
+        """The PnPsolver constructor and SetRansacParameters for C_ candidates (orbhip_pnp_setup_device in
+        include/orbhip.h): `pmap` and `solvers` are dicts with the fields of capi.PnpMap / PNP_SOLVERS holding device
+        addresses (ints, or tensors).  Asynchronous on the matcher's stream."""
+        sig = self._sigma2(level_sigma2, cam)
+        rm, rs = self._record(capi.PnpMap, pmap, optional=("slot_point",)), self._record(capi.PnpSolvers, solvers)
+        dp = lambda a: 0 if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a)  # noqa: E731
+        check(self._lib.orbhip_pnp_setup_device(self._h, int(C_), dp(d_kps), int(n), int(cap), dp(d_matches), int(match_form),
+                                                dp(d_kf_index), int(rows), int(np_), int(pcap), C.byref(rm), C.byref(cam), ptr(sig),
+                                                C.byref(params), C.byref(rs)), "orbhip_pnp_setup_device")
+
+    def PnpIterateDevice(self, C_, n, cap, cam, params, solvers, d_draws, draw_rows, n_iterations, d_Tcw, d_inliers, d_report):
+        """PnPsolver::iterate for every candidate at once (orbhip_pnp_iterate_device): iterations mnIterations ...
+        max(limit, mnIterations + n_iterations) - 1, draws[c][it] serving iteration number it.  Asynchronous."""
+        rs = self._record(capi.PnpSolvers, solvers)
+        dp = lambda a: a.data_ptr() if hasattr(a, "data_ptr") else a  # noqa: E731
+        check(self._lib.orbhip_pnp_iterate_device(self._h, int(C_), int(n), int(cap), C.byref(cam), C.byref(params), C.byref(rs),
+                                                  dp(d_draws), int(draw_rows), int(n_iterations), dp(d_Tcw), dp(d_inliers),
+                                                  dp(d_report)), "orbhip_pnp_iterate_device")
+
+    @staticmethod
+    def _pnp_inputs(kps, matches, kf_index, pmap):
+        k = np.ascontiguousarray(kps, KP_DTYPE).reshape(-1)
+        m = np.ascontiguousarray(matches, np.int32)
+        if m.ndim != 2:
+            raise ValueError("matches is [C, cap]")
+        Cn, cap = m.shape
+        kf = None if kf_index is None else np.ascontiguousarray(kf_index, np.int32).reshape(Cn)
+        M = dict(flags=np.ascontiguousarray(pmap["flags"], np.uint8).reshape(-1),
+                 world=np.ascontiguousarray(pmap["world"], np.float32).reshape(-1, 3))
+        rows = 0
+        if pmap.get("slot_point") is not None:
+            M["slot_point"] = np.ascontiguousarray(pmap["slot_point"], np.int32)
+            if M["slot_point"].ndim != 2 or M["slot_point"].shape[1] != cap:
+                raise ValueError("slot_point is [rows, cap]")
+            rows = M["slot_point"].shape[0]
+        return k, m, kf, M, Cn, cap, rows, int(pmap.get("np", len(M["flags"]))), len(M["flags"])
+
+    def PnpSetup(self, kps, matches, match_form, kf_index, pmap, cam, level_sigma2, params=None, fill=0):
+        """PnpSetupDevice from host arrays: kps [n] KP_DTYPE (mvKeysUn), matches [C, cap] int32, kf_index [C] (None with
+        point matches), pmap = dict(flags [pcap], world [pcap, 3], slot_point [rows, cap] for slot matches, optional np).
+        The arrays are uploaded as torch tensors; the returned record keeps them and the solver record on the device for
+        PnpIterate, and holds host copies of the solver arrays under "host" (what the call does not write holds `fill`)."""
+        import torch
+        params = params or self.pnp_params()
+        k, m, kf, M, Cn, cap, rows, n_pts, pcap = self._pnp_inputs(kps, matches, kf_index, pmap)
+        dev = torch.device("cuda")
+        up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(4, np.uint8)).to(dev)  # noqa: E731
+        dM = {key: up(v) for key, v in M.items()}
+        size = lambda key: (cap if self._PNP_SHAPES[key][0] == "cap" else 1) * self._PNP_SHAPES[key][1]  # noqa: E731
+        dS = {key: torch.full((max(Cn, 1) * size(key) * np.dtype(self._PNP_SHAPES[key][2]).itemsize,), fill, dtype=torch.uint8,
+                              device=dev) for key in self.PNP_SOLVERS}
+        d_k, d_m, d_kf = up(k), up(m), (None if kf is None else up(kf))
+        torch.cuda.synchronize()
+        self.PnpSetupDevice(Cn, d_k, len(k), cap, d_m, match_form, d_kf, rows, n_pts, pcap, dM, cam, level_sigma2, params, dS)
+        self.sync()
+        rec = dict(C=Cn, n=len(k), cap=cap, cam=cam, params=params, map=dM, solvers=dS, keep=(d_k, d_m, d_kf))
+        rec["host"] = self._pnp_host(rec)
+        return rec
+
+    def _pnp_host(self, rec):
+        Cn, cap, out = rec["C"], rec["cap"], {}
+        for key in self.PNP_SOLVERS:
+            per, width, dt = self._PNP_SHAPES[key]
+            cnt = (cap if per == "cap" else 1) * width
+            a = rec["solvers"][key].cpu().numpy().view(dt)[:Cn * cnt]
+            out[key] = a.reshape((Cn,) + ((cap,) if per == "cap" else ()) + ((width,) if width > 1 else ())).copy()
+        return out
+
+    def PnpIterate(self, solver, draws, n_iterations, fill=0):
+        """PnpIterateDevice on the record PnpSetup returned; draws [C, draw_rows, 4] int32.  Returns (report [C, 8] int32 in
+        the order of capi.PNP_REPORT, Tcw [C, 12] float32, inliers [C, cap] uint8); what the call does not write holds `fill`
+        bytes.  The solver record advances on the device; solver["host"] is refreshed."""
+        import torch
+        Cn, cap = solver["C"], solver["cap"]
+        d = np.ascontiguousarray(draws, np.int32)
+        d = d.reshape(Cn, -1, 4)
+        dev = torch.device("cuda")
+        d_draws = torch.from_numpy(d.reshape(-1).copy() if d.size else np.zeros(4, np.int32)).to(dev)
+        d_T = torch.full((max(Cn, 1) * 48,), fill, dtype=torch.uint8, device=dev)
+        d_inl = torch.full((max(Cn, 1) * cap,), fill, dtype=torch.uint8, device=dev)
+        d_rep = torch.full((max(Cn, 1) * 32,), fill, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        self.PnpIterateDevice(Cn, solver["n"], cap, solver["cam"], solver["params"], solver["solvers"], d_draws, d.shape[1],
+                              n_iterations, d_T, d_inl, d_rep)
+        self.sync()
+        solver["host"] = self._pnp_host(solver)
+        return (d_rep.cpu().numpy().view(np.int32)[:Cn * 8].reshape(Cn, 8).copy(),
+                d_T.cpu().numpy().view(np.float32)[:Cn * 12].reshape(Cn, 12).copy(),
+                d_inl.cpu().numpy()[:Cn * cap].reshape(Cn, cap).copy())
+
+    def PnpRansac(self, kps, matches, match_form, kf_index, pmap, cam, level_sigma2, draws, params=None, n_iterations=None,
+                  state=None, best_inliers=None, best_Tcw=None, fill=0):
+        """Setup and iterate from host arrays in one staged copy, one device sequence and one read-back
+        (orbhip_pnp_ransac), range-checked (OrbHipError with E_ARG), draws included.  n_iterations None = max_its, i.e.
+        PnPsolver::find; state [C, 2], best_inliers [C, cap] and best_Tcw [C, 12] resume solvers an earlier call left.
+        Returns dict(report, Tcw, inliers, state, best_inliers, best_Tcw); what the call does not write holds `fill`."""
+        params = params or self.pnp_params()
+        k, m, kf, M, Cn, cap, rows, n_pts, pcap = self._pnp_inputs(kps, matches, kf_index, pmap)
+        d = np.ascontiguousarray(draws, np.int32).reshape(Cn, -1, 4) if Cn else np.zeros((0, int(params.max_its), 4), np.int32)
+        sig = self._sigma2(level_sigma2, cam)
+        c1 = max(Cn, 1)
+        st = np.zeros((c1, 2), np.int32)
+        bi = np.full((c1, cap), fill, np.uint8)
+        bt = np.full(c1 * 48, fill, np.uint8).view(np.float32).reshape(c1, 12)
+        if state is not None:
+            st[:Cn] = np.asarray(state, np.int32).reshape(Cn, 2)
+            bi[:Cn] = np.asarray(best_inliers, np.uint8).reshape(Cn, cap)
+            bt[:Cn] = np.asarray(best_Tcw, np.float32).reshape(Cn, 12)
+        T = np.full(c1 * 48, fill, np.uint8).view(np.float32).reshape(c1, 12)
+        inl = np.full((c1, cap), fill, np.uint8)
+        rep = np.full(c1 * 32, fill, np.uint8).view(np.int32).reshape(c1, 8)
+        pad = lambda a: None if a is None else (np.zeros(4, a.dtype) if a.size == 0 else a)  # noqa: E731
+        keep = {key: pad(v) for key, v in M.items()}
+        rm = self._record(capi.PnpMap, {key: ptr(a).value for key, a in keep.items()}, optional=("slot_point",))
+        args = [pad(k), pad(m), pad(kf), pad(d)]
+        check(self._lib.orbhip_pnp_ransac(self._h, Cn, ptr(args[0]), len(k), cap, ptr(args[1]), int(match_form),
+                                          None if kf is None else ptr(args[2]), rows, n_pts, pcap, C.byref(rm), C.byref(cam), ptr(sig),
+                                          C.byref(params), ptr(args[3]), d.shape[1], int(params.max_its if n_iterations is None else n_iterations),
+                                          ptr(st), ptr(bi), ptr(bt), ptr(T), ptr(inl), ptr(rep)), "orbhip_pnp_ransac")
+        return dict(report=rep[:Cn].copy(), Tcw=T[:Cn].copy(), inliers=inl[:Cn].copy(), state=st[:Cn].copy(),
+                    best_inliers=bi[:Cn].copy(), best_Tcw=bt[:Cn].copy())
+
     # -- device-resident, batched SearchByProjection ---------------------------
     def set_stream(self, stream):
         check(self._lib.orbhip_matcher_set_stream(self._h, stream), "orbhip_matcher_set_stream")
@@ -1166,3 +1302,16 @@ def project_last_frame(Tcw, K, bounds, world_pts, last_octaves, last_angles, val
         q[i]["angle"] = last_angles[i]
         q[i]["observed"] = int(observed[i])
     return q
+
+
+def pnp_draws(n_corr, draw_rows, seed):
+    """Valid draws for PnpIterate / PnpRansac: [C, draw_rows, 4] int32 from numpy.random.default_rng(seed), draw k of
+    candidate c uniform in [0, n_corr[c] - 1 - k], which is what DUtils::Random::RandomInt(0, size - 1) ranges over for the
+    shrinking list (src/PnPsolver.cc:193).  Candidates with fewer than four correspondences get zeros (never read)."""
+    rng = np.random.default_rng(seed)
+    out = np.zeros((len(n_corr), draw_rows, 4), np.int32)
+    for c, N in enumerate(n_corr):
+        if N >= 4:
+            for k in range(4):
+                out[c, :, k] = rng.integers(0, N - k, draw_rows)
+    return out
