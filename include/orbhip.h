@@ -1253,6 +1253,69 @@ int orbhip_pnp_ransac(orbhip_matcher *m, int C, const orbhip_keypoint *kps, int 
                       int n_iterations, int32_t *state, uint8_t *best_inliers, float *best_Tcw, float *Tcw, uint8_t *inliers,
                       int32_t *report);
 
+/* ---- pose optimisation --------------------------------------------------------------------------------------------------
+ * Optimizer::PoseOptimization (src/Optimizer.cc:239-451) for `frames` frames in one call, one workgroup each: the step of
+ * Tracking between orbhip_track_last_frame_device and orbhip_track_local_map_device (src/Tracking.cc:898, :775), the one
+ * after SearchLocalPoints (:940) and the one relocalisation runs on every pose orbhip_pnp_iterate_device returns
+ * (:1440-1471).  One 6-DoF vertex, unary monocular and stereo edges, four rounds of g2o's Levenberg-Marquardt with the
+ * outlier classification between them.  The arithmetic, operation by operation, is tests/seqref/poseopt.py and DESIGN.md
+ * section 3 (the order of the sums over edges, det_sincos64, the pivoted LDLt and Eigen's quaternion formulas are stated
+ * there).
+ *
+ * Read only: d_kps [frames][cap] orbhip_keypoint = mvKeysUn (x, y and octave are read), d_n [frames] int32 = N,
+ * d_u_right [frames][cap] float = mvuRight (NULL: every edge is monocular; otherwise u_right[i] < 0 is monocular, :286),
+ * d_world [wrows][pcap][3] float = mWorldPos, d_point_flags [wrows][pcap] uint8 (ORBHIP_POINT_OBSERVED is read by the two
+ * epilogue modes; NULL allowed with ORBHIP_POSEOPT_PLAIN), d_world_row [frames] int32 = the row of d_world / d_point_flags a
+ * frame's point indices refer to (NULL: row 0 for every frame, the shared map arrays of orbhip_local_map_tables; with
+ * pcap == cap and world_row[p] = the last frame of pair p it is the per-frame layout of orbhip_track_last_frame_device),
+ * inv_level_sigma2 [cam->n_levels] = mvInvLevelSigma2 (host), cam: fx, fy, cx, cy, mbf.
+ * In/out: d_Tcw [frames][12] float = [Rcw | tcw]; d_frame_point [frames][cap] int32 = mvpMapPoints as indices into the
+ * frame's world row, -1 = none (written only by the two epilogue modes).
+ * Out: d_outlier [frames][cap] uint8 = mvbOutlier: only slots i < n with a point are written (:289 and :323 clear them
+ * even when the function returns at :365); d_discarded [frames][cap] int32, nullable: for i < n the point an epilogue took
+ * out of slot i, else -1 (not written with ORBHIP_POSEOPT_PLAIN); d_report [frames][8] int32 = {status,
+ * nInitialCorrespondences, nBad, return value, rounds run, optimize() iterations run in total, count A, count B}.
+ * status: ORBHIP_POSEOPT_OK; ORBHIP_POSEOPT_TOO_FEW (:364, fewer than three edges: return value 0, the pose is untouched);
+ * ORBHIP_POSEOPT_ONE_ROUND (the break of :440: optimizer.edges() counts all edges, so it happens after round 0 and exactly
+ * when 3 <= nInitialCorrespondences < 10).
+ * mode: ORBHIP_POSEOPT_PLAIN: the function alone (counts A and B are 0).
+ *   ORBHIP_POSEOPT_DISCARD: plus the loop of src/Tracking.cc:900-919 (the same text as :778-795): an outlier slot has its
+ *     point moved to d_discarded, frame_point = -1 and the outlier byte cleared; count A = the slots that keep a point
+ *     (nmatches left), count B = nmatchesMap, the inlier slots whose point is ORBHIP_POINT_OBSERVED.
+ *   ORBHIP_POSEOPT_LOCAL_MAP: plus :941-963: count A = mnMatchesInliers (inlier slots whose point is OBSERVED, or all
+ *     inlier slots with the flag ORBHIP_POSEOPT_ONLY_TRACKING), count B = the inlier slots (the IncreaseFound count); with
+ *     the flag ORBHIP_POSEOPT_STEREO outlier slots lose their point (:959-960) and their outlier byte stays set, as in
+ *     the reference.
+ * Every round restarts from the input pose (:377), only the outlier set carries over, and the pose returned is the last
+ * round's.  A NaN or inf from a point at zero depth propagates; nothing faults.
+ *
+ * Asynchronous on the matcher's stream, no host synchronisation, no staging copy, one launch.  cap <= 4096
+ * (ORBHIP_E_CAPACITY beyond); frames, wrows or pcap negative, cap < 1, wrows or pcap < 1 with frames > 0, cam->n_levels
+ * outside [1, ORBHIP_MAX_LEVELS], a bad mode, flag bits other than the two above or a null required pointer:
+ * ORBHIP_E_ARG; all refused before any device work.  frames == 0: success, nothing written.  The device form does not
+ * range-check its arrays: n is clamped to [0, cap], an octave into the level table, and a point index outside [0, pcap)
+ * or a frame whose world_row is outside [0, wrows) counts as "no point". */
+#define ORBHIP_POSEOPT_PLAIN     0
+#define ORBHIP_POSEOPT_DISCARD   1
+#define ORBHIP_POSEOPT_LOCAL_MAP 2
+#define ORBHIP_POSEOPT_ONLY_TRACKING 1
+#define ORBHIP_POSEOPT_STEREO        2
+#define ORBHIP_POSEOPT_OK        0
+#define ORBHIP_POSEOPT_TOO_FEW   1
+#define ORBHIP_POSEOPT_ONE_ROUND 2
+int orbhip_pose_optimization_device(orbhip_matcher *m, int frames, const void *d_kps, const void *d_n, int cap, const void *d_u_right,
+                                    const void *d_world, const void *d_point_flags, int wrows, int pcap, const void *d_world_row,
+                                    const orbhip_camera *cam, const float *inv_level_sigma2, int mode, int flags, void *d_Tcw,
+                                    void *d_frame_point, void *d_outlier, void *d_discarded, void *d_report);
+/* Host buffers, synchronous: one staging copy, the launch, one read-back; what the call does not write keeps the caller's
+ * values.  It range-checks what the device form does not: n in [0, cap], world_row in [0, wrows), and for the slots i < n
+ * point indices in [-1, pcap) and, where a slot has a point, octaves in [0, cam->n_levels): ORBHIP_E_ARG, before the handle
+ * is looked at, nothing written. */
+int orbhip_pose_optimization(orbhip_matcher *m, int frames, const orbhip_keypoint *kps, const int32_t *n, int cap, const float *u_right,
+                             const float *world, const uint8_t *point_flags, int wrows, int pcap, const int32_t *world_row,
+                             const orbhip_camera *cam, const float *inv_level_sigma2, int mode, int flags, float *Tcw,
+                             int32_t *frame_point, uint8_t *outlier, int32_t *discarded, int32_t *report);
+
 /* ---- creating new map points -------------------------------------------------------------------------------------
  * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) for the current key frame and K neighbours in one call, up
  * to the point where the map graph is touched: `new MapPoint`, AddObservation and everything after :434 stay with the

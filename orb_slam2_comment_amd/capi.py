@@ -137,6 +137,11 @@ SIM3_REPORT = ("status", "n_corr", "limit", "iterations", "best_inliers", "retur
 PNP_MATCH_POINTS, PNP_MATCH_SLOTS = range(2)
 PNP_REFINED, PNP_BEST, PNP_NO_MORE, PNP_TOO_FEW = range(4)
 PNP_REPORT = ("status", "n_corr", "limit", "iterations", "best_inliers", "returned_iteration", "n_inliers", "min_inliers")
+# ORBHIP_POSEOPT_*: mode and flags of orbhip_pose_optimization_device, report[0]
+POSEOPT_PLAIN, POSEOPT_DISCARD, POSEOPT_LOCAL_MAP = range(3)
+POSEOPT_ONLY_TRACKING, POSEOPT_STEREO = 1, 2
+POSEOPT_OK, POSEOPT_TOO_FEW, POSEOPT_ONE_ROUND = range(3)
+POSEOPT_REPORT = ("status", "n_initial", "n_bad", "returned", "rounds", "iterations", "count_a", "count_b")
 REMAP_TABLE_SIZE = 4096
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
@@ -276,6 +281,10 @@ SYMBOLS = [
                                        _i, _vp, _vp, _vp]),
     ("orbhip_pnp_ransac", _i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, C.POINTER(PnpMap), C.POINTER(Camera), _vp,
                                C.POINTER(PnpParams), _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("orbhip_pose_optimization_device", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, C.POINTER(Camera), _vp, _i, _i,
+                                             _vp, _vp, _vp, _vp, _vp]),
+    ("orbhip_pose_optimization", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, C.POINTER(Camera), _vp, _i, _i,
+                                      _vp, _vp, _vp, _vp, _vp]),
     ("orbhip_matcher_set_stream", _i, [_vp, _vp]),
     ("orbhip_matcher_sync", _i, [_vp]),
     ("orbhip_compute_stereo_matches_device", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,

@@ -247,6 +247,30 @@ int launch_pnp_setup(hipStream_t stream, PnpArgs A);
 int launch_pnp_iterate(hipStream_t stream, PnpArgs A, void *workspace);
 }  // namespace orbhip
 
+#include "orbhip_poseopt_core.h"
+
+namespace orbhip {
+// orbhip_poseopt.hip: the arguments of orbhip_pose_optimization_device
+constexpr int kPoCapMax = 4096;
+struct PoArgs {
+    const orbhip_keypoint *kps;         // [frames][cap]
+    const int *n;                       // [frames]
+    const float *u_right;               // [frames][cap] or nullptr
+    const float *world;                 // [wrows][pcap][3]
+    const uint8_t *point_flags;         // [wrows][pcap] or nullptr
+    const int *world_row;               // [frames] or nullptr
+    float *Tcw;                         // [frames][12]
+    int *frame_point;                   // [frames][cap]
+    uint8_t *outlier;                   // [frames][cap]
+    int *discarded;                     // [frames][cap] or nullptr
+    int *report;                        // [frames][8]
+    float inv[ORBHIP_MAX_LEVELS];       // mvInvLevelSigma2
+    PoCam cam;
+    int frames, cap, wrows, pcap, n_levels, mode, flags;
+};
+int launch_pose_optimization(hipStream_t stream, PoArgs A);
+}  // namespace orbhip
+
 struct orbhip_extractor {
     int nfeatures = 0;
     double scaleFactor = 1.2;

@@ -6315,6 +6315,120 @@ int orbhip_pnp_ransac(orbhip_matcher *m, int C, const orbhip_keypoint *kps, int 
     return ORBHIP_OK;
 }
 
+// ---- pose optimisation (kernel: orbhip_poseopt.hip) ----------------------------------------------------------------------
+static int poseopt_args(int frames, const void *kps, const void *n, int cap, const void *world, const void *point_flags, int wrows,
+                        int pcap, const orbhip_camera *cam, const float *inv_level_sigma2, int mode, int flags, const void *Tcw,
+                        const void *frame_point, const void *outlier, const void *report)
+{
+    if (frames < 0 || cap < 1 || wrows < 0 || pcap < 0 || !cam || !inv_level_sigma2 || !kps || !n || !world || !Tcw || !frame_point ||
+        !outlier || !report)
+        return ORBHIP_E_ARG;
+    if (mode != ORBHIP_POSEOPT_PLAIN && mode != ORBHIP_POSEOPT_DISCARD && mode != ORBHIP_POSEOPT_LOCAL_MAP) {
+        set_error("pose_optimization: mode %d", mode);
+        return ORBHIP_E_ARG;
+    }
+    if ((flags & ~(ORBHIP_POSEOPT_ONLY_TRACKING | ORBHIP_POSEOPT_STEREO)) || (mode != ORBHIP_POSEOPT_PLAIN && !point_flags) ||
+        cam->n_levels < 1 || cam->n_levels > ORBHIP_MAX_LEVELS || (frames > 0 && (wrows < 1 || pcap < 1)))
+        return ORBHIP_E_ARG;
+    if (cap > kPoCapMax) { set_error("pose_optimization: capacity %d exceeds %d", cap, kPoCapMax); return ORBHIP_E_CAPACITY; }
+    return ORBHIP_OK;
+}
+
+static int poseopt_launch(orbhip_matcher *m, int frames, const void *d_kps, const void *d_n, int cap, const void *d_u_right,
+                          const void *d_world, const void *d_point_flags, int wrows, int pcap, const void *d_world_row,
+                          const orbhip_camera *cam, const float *inv_level_sigma2, int mode, int flags, void *d_Tcw,
+                          void *d_frame_point, void *d_outlier, void *d_discarded, void *d_report)
+{
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    PoArgs A;
+    memset(&A, 0, sizeof(A));
+    A.kps = (const orbhip_keypoint *)d_kps; A.n = (const int *)d_n; A.u_right = (const float *)d_u_right;
+    A.world = (const float *)d_world; A.point_flags = (const uint8_t *)d_point_flags; A.world_row = (const int *)d_world_row;
+    A.Tcw = (float *)d_Tcw; A.frame_point = (int *)d_frame_point; A.outlier = (uint8_t *)d_outlier; A.discarded = (int *)d_discarded;
+    A.report = (int *)d_report;
+    for (int l = 0; l < ORBHIP_MAX_LEVELS; ++l) A.inv[l] = l < cam->n_levels ? inv_level_sigma2[l] : 0.f;
+    A.cam.fx = (double)cam->fx; A.cam.fy = (double)cam->fy; A.cam.cx = (double)cam->cx; A.cam.cy = (double)cam->cy;
+    A.cam.bf = (double)cam->mbf;
+    A.cam.delta_mono = (double)(float)std::sqrt(5.991);                       // src/Optimizer.cc:273-274
+    A.cam.delta_stereo = (double)(float)std::sqrt(7.815);
+    A.frames = frames; A.cap = cap; A.wrows = wrows; A.pcap = pcap; A.n_levels = cam->n_levels; A.mode = mode; A.flags = flags;
+    return launch_pose_optimization(m->stream, A);
+}
+
+int orbhip_pose_optimization_device(orbhip_matcher *m, int frames, const void *d_kps, const void *d_n, int cap, const void *d_u_right,
+                                    const void *d_world, const void *d_point_flags, int wrows, int pcap, const void *d_world_row,
+                                    const orbhip_camera *cam, const float *inv_level_sigma2, int mode, int flags, void *d_Tcw,
+                                    void *d_frame_point, void *d_outlier, void *d_discarded, void *d_report)
+{
+    if (int rc = poseopt_args(frames, d_kps, d_n, cap, d_world, d_point_flags, wrows, pcap, cam, inv_level_sigma2, mode, flags, d_Tcw,
+                              d_frame_point, d_outlier, d_report))
+        return rc;
+    if (!m) return ORBHIP_E_ARG;
+    if (frames == 0) return ORBHIP_OK;
+    return poseopt_launch(m, frames, d_kps, d_n, cap, d_u_right, d_world, d_point_flags, wrows, pcap, d_world_row, cam,
+                          inv_level_sigma2, mode, flags, d_Tcw, d_frame_point, d_outlier, d_discarded, d_report);
+}
+
+int orbhip_pose_optimization(orbhip_matcher *m, int frames, const orbhip_keypoint *kps, const int32_t *n, int cap, const float *u_right,
+                             const float *world, const uint8_t *point_flags, int wrows, int pcap, const int32_t *world_row,
+                             const orbhip_camera *cam, const float *inv_level_sigma2, int mode, int flags, float *Tcw,
+                             int32_t *frame_point, uint8_t *outlier, int32_t *discarded, int32_t *report)
+{
+    if (int rc = poseopt_args(frames, kps, n, cap, world, point_flags, wrows, pcap, cam, inv_level_sigma2, mode, flags, Tcw, frame_point,
+                              outlier, report))
+        return rc;
+    for (int f = 0; f < frames; ++f) {
+        if (n[f] < 0 || n[f] > cap) { set_error("pose_optimization: frame %d has n = %d, cap = %d", f, n[f], cap); return ORBHIP_E_ARG; }
+        if (world_row && (world_row[f] < 0 || world_row[f] >= wrows)) {
+            set_error("pose_optimization: frame %d refers to world row %d of %d", f, world_row[f], wrows);
+            return ORBHIP_E_ARG;
+        }
+        for (int i = 0; i < n[f]; ++i) {
+            const size_t k = (size_t)f * cap + i;
+            if (frame_point[k] < -1 || frame_point[k] >= pcap) {
+                set_error("pose_optimization: slot %d of frame %d holds point %d, outside [-1, %d)", i, f, frame_point[k], pcap);
+                return ORBHIP_E_ARG;
+            }
+            if (frame_point[k] >= 0 && (kps[k].octave < 0 || kps[k].octave >= cam->n_levels)) {
+                set_error("pose_optimization: key point %d of frame %d has octave %d", i, f, kps[k].octave);
+                return ORBHIP_E_ARG;
+            }
+        }
+    }
+    if (!m) return ORBHIP_E_ARG;
+    if (frames == 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    Stage st;
+    int rc;
+    const size_t Fn = (size_t)frames, FC = Fn * cap, WP = (size_t)wrows * pcap;
+    const size_t in_bytes = al256(FC * sizeof(orbhip_keypoint)) + al256(Fn * 4) + al256(FC * 4) + al256(WP * 12) + al256(WP) + al256(Fn * 4);
+    const size_t out_size = al256(Fn * 48) + al256(FC * 4) + al256(FC) + al256(FC * 4) + al256(Fn * 32);
+    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
+    const orbhip_keypoint *d_kps = st.put(kps, FC);
+    const int32_t *d_n = st.put(n, Fn);
+    const float *d_ur = u_right ? st.put(u_right, FC) : nullptr;
+    const float *d_world = st.put(world, WP * 3);
+    const uint8_t *d_pf = point_flags ? st.put(point_flags, WP) : nullptr;
+    const int32_t *d_row = world_row ? st.put(world_row, Fn) : nullptr;
+    const size_t out_off = st.off;
+    const float *d_Tcw = st.put(Tcw, Fn * 12);
+    const int32_t *d_fp = st.put(frame_point, FC);
+    const uint8_t *d_out = st.put(outlier, FC);
+    const int32_t *d_dis = discarded ? st.put(discarded, FC) : nullptr;
+    const int32_t *d_rep = st.put(report, Fn * 8);
+    const size_t out_bytes = st.off - out_off;
+    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = poseopt_launch(m, frames, d_kps, d_n, cap, d_ur, d_world, d_pf, wrows, pcap, d_row, cam, inv_level_sigma2, mode, flags,
+                             (void *)d_Tcw, (void *)d_fp, (void *)d_out, (void *)d_dis, (void *)d_rep)))
+        return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
+    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
+    back(Tcw, d_Tcw, Fn * 48); back(frame_point, d_fp, FC * 4); back(outlier, d_out, FC); back(report, d_rep, Fn * 32);
+    if (discarded) back(discarded, d_dis, FC * 4);
+    return ORBHIP_OK;
+}
+
 #ifdef ORBHIP_DEVTOOLS
 // development builds: {workgroups, sum of rounds, max rounds} of the parallel resolve since the last call
 int orbhip_dev_resolve_stats(unsigned int out[4])

@@ -923,6 +923,55 @@ class ORBmatcher:
         return dict(report=rep[:Cn].copy(), Tcw=T[:Cn].copy(), inliers=inl[:Cn].copy(), state=st[:Cn].copy(),
                     best_inliers=bi[:Cn].copy(), best_Tcw=bt[:Cn].copy())
 
+    # -- pose optimisation (src/Optimizer.cc:239-451) ---------------------------
+    def PoseOptimizationDevice(self, frames, d_kps, d_n, cap, d_u_right, d_world, d_point_flags, wrows, pcap, d_world_row, cam,
+                               inv_level_sigma2, d_Tcw, d_frame_point, d_outlier, d_discarded, d_report,
+                               mode=capi.POSEOPT_PLAIN, flags=0):
+        """Optimizer::PoseOptimization for `frames` frames, one workgroup each, and with mode DISCARD / LOCAL_MAP the loop of
+        Tracking that follows it (orbhip_pose_optimization_device in include/orbhip.h).  The d_* are device addresses (ints,
+        or tensors); d_u_right, d_point_flags (PLAIN only), d_world_row and d_discarded may be None.  Asynchronous on the
+        matcher's stream."""
+        sig = self._sigma2(inv_level_sigma2, cam)
+        dp = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a)  # noqa: E731
+        check(self._lib.orbhip_pose_optimization_device(self._h, int(frames), dp(d_kps), dp(d_n), int(cap), dp(d_u_right), dp(d_world),
+                                                        dp(d_point_flags), int(wrows), int(pcap), dp(d_world_row), C.byref(cam),
+                                                        ptr(sig), int(mode), int(flags), dp(d_Tcw), dp(d_frame_point), dp(d_outlier),
+                                                        dp(d_discarded), dp(d_report)), "orbhip_pose_optimization_device")
+
+    def PoseOptimization(self, kps, n, u_right, world, point_flags, world_row, cam, inv_level_sigma2, Tcw, frame_point,
+                         outlier=None, mode=capi.POSEOPT_PLAIN, flags=0, fill=0):
+        """The same from host arrays in one staged copy, one launch and one read-back (orbhip_pose_optimization),
+        range-checked (OrbHipError with E_ARG).  kps [frames, cap] KP_DTYPE, n [frames], u_right [frames, cap] or None,
+        world [wrows, pcap, 3], point_flags [wrows, pcap] or None, world_row [frames] or None, Tcw [frames, 12],
+        frame_point [frames, cap]; `outlier` [frames, cap] is the caller's mvbOutlier (default: `fill` bytes).  Returns
+        dict(Tcw, frame_point, outlier, discarded, report): copies, what the call does not write holds the input / `fill`."""
+        fp = np.array(frame_point, np.int32, order="C", ndmin=2)
+        frames, cap = fp.shape
+        k = np.ascontiguousarray(kps, KP_DTYPE).reshape(frames, cap)
+        nn = np.ascontiguousarray(n, np.int32).reshape(frames)
+        ur = None if u_right is None else np.ascontiguousarray(u_right, np.float32).reshape(frames, cap)
+        w = np.ascontiguousarray(world, np.float32)
+        w = w.reshape((1,) + w.shape) if w.ndim == 2 else w
+        wrows, pcap = w.shape[0], w.shape[1]
+        pf = None if point_flags is None else np.ascontiguousarray(point_flags, np.uint8).reshape(wrows, pcap)
+        row = None if world_row is None else np.ascontiguousarray(world_row, np.int32).reshape(frames)
+        sig = self._sigma2(inv_level_sigma2, cam)
+        f1 = max(frames, 1)
+        T = np.zeros((f1, 12), np.float32)
+        T[:frames] = np.asarray(Tcw, np.float32).reshape(frames, 12)
+        out = np.full((f1, cap), fill, np.uint8)
+        if outlier is not None:
+            out[:frames] = np.asarray(outlier, np.uint8).reshape(frames, cap)
+        dis = np.full(f1 * cap * 4, fill, np.uint8).view(np.int32).reshape(f1, cap)
+        rep = np.full(f1 * 32, fill, np.uint8).view(np.int32).reshape(f1, 8)
+        pad = lambda a: None if a is None else (np.zeros(8, a.dtype) if a.size == 0 else a)  # noqa: E731
+        args = [pad(a) for a in (k, nn, ur, w, pf, row, fp)]
+        check(self._lib.orbhip_pose_optimization(self._h, frames, ptr(args[0]), ptr(args[1]), cap, ptr(args[2]), ptr(args[3]),
+                                                 ptr(args[4]), wrows, pcap, ptr(args[5]), C.byref(cam), ptr(sig), int(mode), int(flags),
+                                                 ptr(T), ptr(args[6]), ptr(out), ptr(dis), ptr(rep)), "orbhip_pose_optimization")
+        return dict(Tcw=T[:frames].copy(), frame_point=fp.copy(), outlier=out[:frames].copy(),
+                    discarded=dis[:frames].copy(), report=rep[:frames].copy())
+
     # -- device-resident, batched SearchByProjection ---------------------------
     def set_stream(self, stream):
         check(self._lib.orbhip_matcher_set_stream(self._h, stream), "orbhip_matcher_set_stream")

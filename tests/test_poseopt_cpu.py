@@ -1,0 +1,808 @@
+"""The sequential reference of Optimizer::PoseOptimization (tests/seqref/poseopt.py) on its own: hand-worked cases for the
+rules it pins, det_sincos64 against libm, the distance to a textbook restatement (rotation matrices, math.sin / cos,
+numpy.linalg.solve, sequential sums), a host build of orbhip_poseopt_core.h that must match it bit for bit, and the cases
+the GPU tests replay (test_poseopt_gpu.py imports them from here; the reference answers are computed once per process).
+
+Rule 4 (an inlier edge is classified with the error at the last TRIED estimate) is pinned by a hand-worked call of the
+classification with two poses that differ by a visible step: of the seqref's classify, and of po_classify, the function
+po_run calls after every round, through the host program (test_host_classification_...); the host build must also leave
+the seqref's estimate and last tried estimate bit for bit (test_host_build_writes_...).  No frame makes the rule visible in
+the outputs: a round's last trial is rejected only after ten growths of lambda (a step below an ulp of the float chi2), on
+rho == 0, or on a NaN chi2 at the trial estimate, which needs a point at exactly zero depth there.
+
+Measured on the CPU (the asserted tolerances are four times these):
+  det_sincos64 against math.sin / math.cos, 10^5 log-spaced angles in [1e-8, 100] and their negatives     1 ulp
+  pose against the textbook restatement, R (max entry) and t (max entry, m), both poses in double:
+    scene A 6.5e-14, 3.8e-14; scene B 1.8e-12, 2.8e-12; seed 31 3.3e-13, 1.4e-12; seed 32 4.1e-11, 1.8e-10
+  (Levenberg-Marquardt stops on a relative gain of 1e-3, so a rounding difference early in a round is carried, not damped)
+"""
+import functools
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from seqref import poseopt as Q
+
+f32, f64, i32, u8 = np.float32, np.float64, np.int32, np.uint8
+KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"),
+                     ("class_id", "<i4")])
+CAM = (718.856, 718.856, 607.19, 185.2, 386.1)                                # KITTI: fx, fy, cx, cy, bf
+INV_SIGMA2 = np.array([1.0 / 1.2 ** (2 * l) for l in range(8)], f32)
+SENTINEL = 0xA5
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MEASURED = dict(R=4.2e-11, t=1.9e-10)                                          # what test_textbook_distance prints, see above
+TOL = {k: 4 * v for k, v in MEASURED.items()}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# scenes
+def _rot(a):
+    a = np.asarray(a, float)
+    th = np.linalg.norm(a)
+    k = a / th
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
+
+
+R_TRUE, T_TRUE = _rot([0.1, -0.2, 0.05]), np.array([0.3, -0.1, 0.5])
+
+
+def make_frame(seed, n_pts, n_bad, stereo, cap, observed=0.7, gaps=True, n=None):
+    """One frame: n_pts matched slots (spread over the first n slots when `gaps`), n_bad of them displaced by 12-30 px * sigma,
+    the fraction `stereo` with a right coordinate.  Points at x +-15 m, y +-3 m, depth 5-40 m, octaves 0-7, noise 0.3 px *
+    sigma; the input pose is the true one perturbed by (0.02, 0.015, -0.01) rad and (0.1, -0.05, 0.15) m."""
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy, bf = CAM
+    n = min(cap, n_pts + (n_pts // 3 if gaps else 0) + (1 if gaps else 0)) if n is None else n
+    slots = np.sort(rng.choice(n, n_pts, replace=False)) if n_pts else np.zeros(0, int)
+    Xc = np.c_[rng.uniform(-15, 15, n_pts), rng.uniform(-3, 3, n_pts), rng.uniform(5, 40, n_pts)]
+    octv = rng.integers(0, 8, n_pts)
+    sig = 1.2 ** octv
+    u = fx * Xc[:, 0] / Xc[:, 2] + cx + rng.normal(0, 0.3, n_pts) * sig
+    v = fy * Xc[:, 1] / Xc[:, 2] + cy + rng.normal(0, 0.3, n_pts) * sig
+    ur = u - bf / Xc[:, 2]
+    bad = np.sort(rng.choice(n_pts, n_bad, replace=False)) if n_bad else np.zeros(0, int)
+    ang, mag = rng.uniform(0, 2 * np.pi, n_bad), rng.uniform(12, 30, n_bad) * sig[bad]
+    u[bad] += mag * np.cos(ang)
+    v[bad] += mag * np.sin(ang)
+    ur[bad] += mag * np.cos(ang)
+    mono = rng.permutation(n_pts)[:n_pts - int(round(n_pts * stereo))]
+    ur[mono] = -1.0
+    kps = np.zeros(cap, KP_DTYPE)
+    kps["x"], kps["y"] = rng.uniform(0, 1200, cap), rng.uniform(0, 370, cap)
+    kps["octave"] = rng.integers(0, 8, cap)
+    u_right = np.full(cap, -1.0, f32)
+    kps["x"][slots], kps["y"][slots], kps["octave"][slots], u_right[slots] = u, v, octv, ur
+    perm = rng.permutation(n_pts)                                              # the point index is not the slot order
+    world = np.zeros((n_pts + 1, 3), f32)
+    world[perm] = (Xc - T_TRUE) @ R_TRUE
+    frame_point = np.full(cap, -1, i32)
+    frame_point[slots] = perm
+    flags = np.where(rng.uniform(size=n_pts + 1) < observed, 3, 1).astype(u8)
+    dR, dt = _rot([0.02, 0.015, -0.01]), np.array([0.1, -0.05, 0.15])
+    Tcw = np.c_[dR @ R_TRUE, dR @ T_TRUE + dt].astype(f32).ravel()
+    return dict(kps=kps, n=n, u_right=u_right, world=world, flags=flags, Tcw=Tcw, frame_point=frame_point,
+                displaced=slots[bad], slots=slots)
+
+
+def batch_of(frames, cap, shared=False, mono_null=False, mode=Q.PLAIN, flags=0, rows_extra=0):
+    """The C ABI's arrays for a list of make_frame results.  shared: every frame indexes world row 0 (world_row NULL; only
+    for a single frame or frames of one map); otherwise one row per frame, addressed through world_row in reversed order."""
+    F = len(frames)
+    pcap = cap if not shared else max(len(f["world"]) for f in frames)
+    pcap = max(pcap, max(len(f["world"]) for f in frames))
+    wrows = 1 if shared else F + rows_extra
+    world = np.zeros((wrows, pcap, 3), f32)
+    pflags = np.zeros((wrows, pcap), u8)
+    row = None if shared else np.arange(F, dtype=i32)[::-1].copy() + rows_extra
+    for k, f in enumerate(frames):
+        r = 0 if shared else int(row[k])
+        world[r, :len(f["world"])] = f["world"]
+        pflags[r, :len(f["flags"])] = f["flags"]
+    return dict(frames=F, cap=cap, wrows=wrows, pcap=pcap, kps=np.stack([f["kps"] for f in frames]),
+                n=np.array([f["n"] for f in frames], i32),
+                u_right=None if mono_null else np.stack([f["u_right"] for f in frames]),
+                world=world, point_flags=pflags, world_row=row, Tcw=np.stack([f["Tcw"] for f in frames]),
+                frame_point=np.stack([f["frame_point"] for f in frames]), mode=mode, flags=flags)
+
+
+def _zero_depth_frame(cap):
+    """Identity input pose; one point at the camera centre (0 / 0: every comparison false, an inlier for ever) and one in the
+    plane z = 0 (an infinite chi2: an outlier), among 14 ordinary ones."""
+    f = make_frame(21, 16, 0, 0.5, cap, gaps=False)
+    Xc = f["world"].astype(f64) @ R_TRUE.T + T_TRUE
+    f["world"] = Xc.astype(f32)
+    f["Tcw"] = np.c_[np.eye(3), np.zeros(3)].astype(f32).ravel()
+    f["world"][f["frame_point"][3]] = 0.0
+    f["world"][f["frame_point"][7]] = (1.0, 0.5, 0.0)
+    return f
+
+
+def _stale_step_frame(cap, seed=300):
+    """The input pose is the identity, the true one 0.3 x the usual perturbation, the noise 0.02 px * sigma.  Point 40 lies
+    in the plane z = 0 of the INPUT camera and is seen where the true pose puts it: while it is active every factorisation
+    of a round fails (infinite chi2, weight 0 times an infinite Jacobian), it is an outlier at the input pose and an inlier
+    at a converged one.  Rounds 0 and 3 fail, rounds 1 and 2 converge without it, it comes back after round 2; round 3
+    then applies the stale x of round 2 in each of its ten trials, pops it, and returns the input pose."""
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy, bf = CAM
+    dR, dt = _rot(0.3 * np.array([0.02, 0.015, -0.01])), 0.3 * np.array([0.1, -0.05, 0.15])
+    n_pts = 40
+    Xc = np.c_[rng.uniform(-15, 15, n_pts), rng.uniform(-3, 3, n_pts), rng.uniform(5, 40, n_pts)]
+    octv = rng.integers(0, 8, n_pts)
+    sig = 1.2 ** octv
+    u = fx * Xc[:, 0] / Xc[:, 2] + cx + rng.normal(0, 0.02, n_pts) * sig
+    v = fy * Xc[:, 1] / Xc[:, 2] + cy + rng.normal(0, 0.02, n_pts) * sig
+    bad = np.sort(rng.choice(n_pts, 6, replace=False))
+    ang, mag = rng.uniform(0, 2 * np.pi, 6), rng.uniform(12, 30, 6) * sig[bad]
+    u[bad] += mag * np.cos(ang)
+    v[bad] += mag * np.sin(ang)
+    world = np.zeros((n_pts + 1, 3), f32)
+    world[:n_pts] = (Xc - dt) @ dR
+    world[n_pts] = (0.0005, 0.00025, 0.0)
+    Sc = dR @ world[n_pts].astype(f64) + dt
+    kps = np.zeros(cap, KP_DTYPE)
+    kps["x"][:n_pts], kps["y"][:n_pts], kps["octave"][:n_pts] = u, v, octv
+    kps["x"][n_pts], kps["y"][n_pts], kps["octave"][n_pts] = fx * Sc[0] / Sc[2] + cx, fy * Sc[1] / Sc[2] + cy, 7
+    fp = np.full(cap, -1, i32)
+    fp[:n_pts + 1] = np.arange(n_pts + 1)
+    return dict(kps=kps, n=n_pts + 1, u_right=np.full(cap, -1.0, f32), world=world, flags=np.full(n_pts + 1, 3, u8),
+                Tcw=np.c_[np.eye(3), np.zeros(3)].astype(f32).ravel(), frame_point=fp, displaced=bad, slots=np.arange(n_pts + 1))
+
+
+def _comeback_frame(cap, seed=212):
+    """40 points, 6 displaced, and five clean observations moved to 2.2-2.7 sigma from where they were: chi2 near the
+    threshold, so the flag of such an edge depends on the pose of the round."""
+    f = make_frame(seed, 40, 6, 0.5, cap)
+    rng = np.random.default_rng(seed)
+    gone = set(f["displaced"].tolist())
+    clean = [s for s in f["slots"] if s not in gone]
+    for s in rng.choice(clean, 5, replace=False):
+        sig = 1.2 ** int(f["kps"]["octave"][s])
+        ang, k = rng.uniform(0, 2 * np.pi), rng.uniform(2.2, 2.7)
+        f["kps"]["x"][s] += k * sig * np.cos(ang)
+        f["kps"]["y"][s] += k * sig * np.sin(ang)
+        if f["u_right"][s] >= 0:
+            f["u_right"][s] += k * sig * np.cos(ang)
+    return f
+
+
+def _case(name):
+    A = lambda **kw: make_frame(1, 60, 12, 2 / 3, 128, **kw)                    # noqa: E731  scene A
+    B = lambda **kw: make_frame(2, 60, 12, 0.0, 128, **kw)                      # noqa: E731  scene B
+    empty = make_frame(5, 0, 0, 0, 128)
+    n0 = dict(make_frame(6, 20, 2, 0.5, 128), n=0)
+    if name == "A":
+        return batch_of([A()], 128, shared=True)
+    if name == "B":
+        return batch_of([B()], 128, shared=True, mono_null=True)
+    if name == "B_rows":
+        return batch_of([B()], 128)
+    if name == "batch3":                                                        # different edge counts, n = 0, no point at all
+        return batch_of([make_frame(3, 40, 8, 0.5, 128), n0, empty, A()], 128, rows_extra=1)
+    if name == "A_alone":                                                       # the frame that is row 3 of batch3
+        return batch_of([A()], 128)
+    if name == "e65":
+        return batch_of([make_frame(7, 65, 10, 0.5, 128, gaps=False)], 128, shared=True)
+    if name == "e300":
+        return batch_of([make_frame(8, 300, 60, 0.5, 512)], 512, shared=True)
+    if name == "nine":
+        return batch_of([make_frame(9, 9, 1, 0.5, 128), make_frame(10, 10, 1, 0.5, 128)], 128)
+    if name == "two":
+        return batch_of([make_frame(11, 2, 0, 0.5, 128)], 128)
+    if name == "zero_depth":
+        return batch_of([_zero_depth_frame(128)], 128, shared=True)
+    if name == "comeback":
+        return batch_of([_comeback_frame(128)], 128, shared=True)
+    if name == "stale_step":
+        return batch_of([_stale_step_frame(128)], 128, shared=True)
+    mode = dict(discard=Q.DISCARD, localmap=Q.LOCAL_MAP)[name.split("_")[0]]
+    flags = dict(f0=0, f1=Q.ONLY_TRACKING, f2=Q.STEREO, f3=Q.ONLY_TRACKING | Q.STEREO)[name.split("_")[1]]
+    if name.endswith("rows"):
+        return batch_of([A(), make_frame(11, 2, 0, 0.5, 128)], 128, mode=mode, flags=flags)
+    return batch_of([A()], 128, shared=True, mode=mode, flags=flags)
+
+
+CASES = ("A", "B", "B_rows", "batch3", "A_alone", "e65", "e300", "nine", "two", "zero_depth", "comeback", "stale_step", "discard_f0", "discard_f0_rows",
+         "localmap_f0", "localmap_f1", "localmap_f2", "localmap_f3_rows")
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    b = _case(name)
+    for v in b.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return b
+
+
+def prefilled(b):
+    """The in/out and out arrays as a caller passes them: outputs hold a sentinel."""
+    F, cap = b["frames"], b["cap"]
+    return dict(Tcw=b["Tcw"].copy(), frame_point=b["frame_point"].copy(), outlier=np.full((F, cap), SENTINEL, u8),
+                discarded=np.full(F * cap * 4, SENTINEL, u8).view(i32).reshape(F, cap),
+                report=np.full(F * 32, SENTINEL, u8).view(i32).reshape(F, 8))
+
+
+def run_seqref(b, traces=None, poses=None):
+    o = prefilled(b)
+    for f in range(b["frames"]):
+        r = 0 if b["world_row"] is None else int(b["world_row"][f])
+        tr = [] if traces is not None else None
+        o["report"][f] = Q.pose_optimization(b["kps"][f]["x"], b["kps"][f]["y"], b["kps"][f]["octave"], int(b["n"][f]),
+                                             None if b["u_right"] is None else b["u_right"][f], b["world"][r],
+                                             b["point_flags"][r], INV_SIGMA2, CAM, o["Tcw"][f], o["frame_point"][f],
+                                             o["outlier"][f], o["discarded"][f], b["mode"], b["flags"], trace=tr,
+                                             pose64=poses)
+        if traces is not None:
+            traces.append(tr)
+    return o
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    o = run_seqref(case(name))
+    for v in o.values():
+        v.setflags(write=False)
+    return o
+
+
+def assert_same(got, want, what):
+    for k in ("report", "outlier", "frame_point", "discarded", "Tcw"):
+        assert got[k].tobytes() == want[k].tobytes(), (what, k, got[k][got[k] != want[k]][:8], want[k][got[k] != want[k]][:8])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# hand-worked cases
+def test_two_edges_too_few():
+    b, o = case("two"), reference("two")
+    assert o["report"][0].tolist() == [Q.TOO_FEW, 2, 0, 0, 0, 0, 0, 0]
+    assert o["Tcw"].tobytes() == b["Tcw"].tobytes()                            # the pose is untouched
+    has = b["frame_point"][0] >= 0
+    assert has.sum() == 2 and (o["outlier"][0][has] == 0).all() and (o["outlier"][0][~has] == SENTINEL).all()
+    assert (o["discarded"] == prefilled(b)["discarded"]).all()                  # PLAIN writes no discarded
+
+
+def test_nine_edges_one_round_ten_edges_four():
+    o = reference("nine")
+    assert o["report"][0][[0, 1, 4]].tolist() == [Q.ONE_ROUND, 9, 1]            # rule 5: all edges count, outliers too
+    assert o["report"][1][[0, 1, 4]].tolist() == [Q.OK, 10, 4]
+    assert o["report"][0][2] == 1 and o["report"][0][3] == 8                    # the displaced one is found in that round
+
+
+def test_rule1_edges_in_slot_order_interleaved():
+    b = case("A")
+    f = dict(kx=b["kps"][0]["x"], n=int(b["n"][0]))
+    slots = np.flatnonzero(b["frame_point"][0][:f["n"]] >= 0)
+    stereo = b["u_right"][0][slots] >= 0
+    assert stereo.any() and (~stereo).any() and (stereo[:-1] != stereo[1:]).sum() > 10
+    # swapping the contents of two slots changes the order of the sums: the flags stay, the low bits of the pose move
+    k2 = b["kps"].copy(); u2 = b["u_right"].copy(); p2 = b["frame_point"].copy()
+    s0, s1 = slots[0], slots[5]
+    for a in (k2[0], u2[0], p2[0]):
+        a[[s0, s1]] = a[[s1, s0]]
+    p_sw, p_ref = [], []
+    o = run_seqref(dict(b, kps=k2, u_right=u2, frame_point=p2), poses=p_sw)
+    run_seqref(b, poses=p_ref)
+    ref = reference("A")
+    sw = o["outlier"][0].copy(); sw[[s0, s1]] = sw[[s1, s0]]
+    assert (sw == ref["outlier"][0]).all()
+    d = np.abs(np.array(p_sw) - np.array(p_ref)).max()
+    assert 0 < d < 1e-9, d                                                      # the order of the sums is part of the result
+
+
+def test_rule2_every_round_restarts_from_the_input_pose():
+    clean = batch_of([make_frame(12, 30, 0, 0.5, 128)], 128, shared=True)
+    tr = []
+    o = run_seqref(clean, tr)
+    assert o["report"][0][2] == 0
+    per = [[t[1:] for t in tr[0] if t[0] == r] for r in range(4)]
+    assert per[0] == per[1] == per[2] and len(per[0]) > 3                       # the same start, the same set, the same steps
+    assert o["report"][0][5] == sum(len({t[0] for t in p}) for p in per)
+
+
+def test_outlier_after_round_0_inlier_again_after_round_2():
+    """Only the outlier set carries over, and it is not monotone: an edge left out of a round is judged at that round's
+    estimate (:390) and comes back when it fits."""
+    b = case("comeback")
+    o, h = prefilled(b), []
+    Q.pose_optimization(b["kps"][0]["x"], b["kps"][0]["y"], b["kps"][0]["octave"], int(b["n"][0]), b["u_right"][0], b["world"][0],
+                        b["point_flags"][0], INV_SIGMA2, CAM, o["Tcw"][0], o["frame_point"][0], o["outlier"][0], None, history=h)
+    h = np.array(h)
+    assert h.shape == (4, 40)
+    back = np.flatnonzero(h[0] & ~h[2])
+    assert back.tolist() == [0] and h[:, 0].tolist() == [True, False, False, False]
+    slot = np.flatnonzero(b["frame_point"][0] >= 0)[0]
+    assert reference("comeback")["outlier"][0][slot] == 0 and reference("comeback")["report"][0][2] == h[3].sum()
+
+
+def test_failed_factorisation_applies_the_stale_step_and_pops_it():
+    """Rule 6's last clause, and the closest a frame comes to rule 4: in the last round every trial is exp(stale x) * input."""
+    b = case("stale_step")
+    o, h, tr, last = prefilled(b), [], [], []
+    rep = Q.pose_optimization(b["kps"][0]["x"], b["kps"][0]["y"], b["kps"][0]["octave"], int(b["n"][0]), b["u_right"][0], b["world"][0],
+                              b["point_flags"][0], INV_SIGMA2, CAM, o["Tcw"][0], o["frame_point"][0], o["outlier"][0], None, history=h,
+                              trace=tr, last64=last)
+    h = np.array(h)
+    assert h[:, 40].tolist() == [True, True, False, True]                       # the point in the plane z = 0
+    assert h.sum(1).tolist() == [34, 7, 6, 34] and rep[:5] == [Q.OK, 41, 34, 7, 4]
+    # the infinite chi2 makes b NaN, so rho is NaN: the trial loop ends after one failed trial (rho < 0 is false), neither
+    # stop rule fires (NaN compares false), and optimize() runs its ten iterations of one trial each
+    for r in (0, 3):
+        assert [t[1:] for t in tr if t[0] == r] == [(it, 0, False) for it in range(10)]
+    assert o["Tcw"][0].tobytes() == b["Tcw"][0].tobytes()                        # the input pose comes back
+    est, tried = np.array(last[:7]), np.array(last[7:])
+    assert 0 < np.abs(est - tried).max() < 1e-6                                 # the stale x is round 2's last, converged step
+
+
+def test_rule3_huber():
+    e = Q.Edge()
+    e.delta = Q.f32(math.sqrt(5.991)); e.dsqr = e.delta * e.delta
+    assert e.delta == 2.4476518630981445 and e.dsqr != 5.991
+    assert Q.robustify(e, e.dsqr, True) == (e.dsqr, 1.0)                        # e <= dsqr
+    up = math.nextafter(e.dsqr, 10)
+    r0, r1 = Q.robustify(e, up, True)
+    assert r1 == e.delta / math.sqrt(up) and r0 == 2 * math.sqrt(up) * e.delta - e.dsqr
+    assert Q.robustify(e, 16.0, True) == (8 * e.delta - e.dsqr, e.delta / 4)
+    assert Q.robustify(e, 16.0, False) == (16.0, 1.0)                           # round 3
+    assert Q.f32(7.815) == 7.815000057220459 and Q.f32(5.991) == 5.99100017547607422
+
+
+def test_rule4_inlier_keeps_the_error_of_the_last_tried_estimate():
+    b = case("A")
+    edges = Q.build_edges(b["kps"][0]["x"], b["kps"][0]["y"], b["kps"][0]["octave"], int(b["n"][0]), b["u_right"][0], b["world"][0],
+                          INV_SIGMA2, b["frame_point"][0])
+    cam = tuple(float(f32(v)) for v in CAM)
+    good = Q.pose_from_Tcw(reference("A")["Tcw"][0])
+    far = Q.pose_from_Tcw(b["Tcw"][0])                                           # the perturbed input: most edges fail there
+    inl = [False] * len(edges)
+    outl = [True] * len(edges)
+    # est = good, tried = far: inliers are judged at `far`, outliers at `good`
+    a = Q.classify(edges, list(inl), good, far, cam)
+    c = Q.classify(edges, list(outl), good, far, cam)
+    at_far = [Q.f32(Q.edge_error(e, far, cam)[1]) > e.thr for e in edges]
+    at_good = [Q.f32(Q.edge_error(e, good, cam)[1]) > e.thr for e in edges]
+    assert a[0] == at_far and c[0] == at_good and at_far != at_good
+    # and the scenes do end iterations on a rejected trial
+    tr = []
+    run_seqref(b, tr)
+    last = {}
+    for r, it, q, ok in tr[0]:
+        last[(r, it)] = ok
+    assert any(not ok for ok in last.values())                                  # existence is the property
+
+
+def test_rule7_float_invz_and_jacobian():
+    cam = tuple(float(f32(v)) for v in CAM)
+    e = Q.Edge()
+    e.X, e.stereo, e.inv, e.obs = [1.0, 2.0, 3.0], True, 1.0, [0.0, 0.0, 0.0]
+    ident = ([0.0, 0.0, 0.0, 1.0], [0.0, 0.0, 0.0])
+    err = Q.edge_error(e, ident, cam)[0]
+    invz = 0.3333333432674408                                                    # (float)(1.0 / 3.0)
+    p0 = 1.0 * invz * cam[0] + cam[2]
+    assert err == [0.0 - p0, 0.0 - (2.0 * invz * cam[1] + cam[3]), 0.0 - (p0 - cam[4] * invz)]
+    assert err[0] != -(1.0 / 3.0 * cam[0] + cam[2])
+    e.stereo = False
+    assert Q.edge_error(e, ident, cam)[0] == [-(1.0 / 3.0 * cam[0] + cam[2]), -(2.0 / 3.0 * cam[1] + cam[3])]
+    # b = -J^t W e against a central difference of chi2 / 2 along exp(h e_k) * pose
+    for stereo in (False, True):
+        e.stereo, e.obs, e.inv = stereo, [850.0, 660.0, 720.0][:3 if stereo else 2], 0.5
+        e.delta = e.dsqr = 1e30
+        pose = Q.pose_from_Tcw(case("A")["Tcw"][0])
+        bvec = Q.edge_terms(e, pose, cam, False, True)[21:27]
+        chi2 = Q.edge_error(e, pose, cam)[1]
+        # the float invz puts a relative noise of 2^-24 on the stereo projection, 2 * 2^-24 * chi2 on chi2: the step is chosen
+        # so that this noise and the h^2 truncation both stay below 1e-3 of the gradient's scale
+        step = 1e-4 if stereo else 1e-6
+        noise = (2 * 2.0 ** -24 * chi2 / (2 * step) if stereo else 0.0)
+        scale = max(abs(v) for v in bvec)
+        for k in range(6):
+            h = [0.0] * 6
+            h[k] = step
+            up = Q.edge_error(e, Q.se3_mul(Q.se3_exp(h), pose), cam)[1]
+            h[k] = -step
+            dn = Q.edge_error(e, Q.se3_mul(Q.se3_exp(h), pose), cam)[1]
+            assert abs(-(up - dn) / (4 * step) - bvec[k]) <= 1e-5 * scale + noise, (stereo, k)
+    assert Q.edge_terms(e, pose, cam, False, False)[:27] == [0.0] * 27
+
+
+def test_rule6_ldlt():
+    rng = np.random.default_rng(3)
+    M = rng.normal(size=(6, 6))
+    H = M @ M.T + np.eye(6)
+    bb = rng.normal(size=6)
+    ok, x = Q.ldlt_solve(H.tolist(), bb.tolist())
+    assert ok and np.abs(np.array(x) - np.linalg.solve(H, bb)).max() < 1e-12
+    ok, x = Q.ldlt_solve(np.diag([2.0, 4.0, 4.0, 1.0, 3.0, 4.0]).tolist(), [2.0, 4.0, 8.0, 1.0, 3.0, 12.0])
+    assert ok and x == [1.0, 1.0, 2.0, 1.0, 1.0, 3.0]
+    assert Q.ldlt_solve(np.zeros((6, 6)).tolist(), [0.0] * 6) == (False, None)
+    assert Q.ldlt_solve(np.diag([1.0, 1, 1, 1, 1, -1e-9]).tolist(), [0.0] * 6) == (False, None)
+    nan = np.eye(6)
+    nan[2, 2] = float("nan")
+    assert Q.ldlt_solve(nan.tolist(), [0.0] * 6) == (False, None)
+
+
+def test_rule8_zero_depth():
+    b, o = case("zero_depth"), reference("zero_depth")
+    rep = o["report"][0]
+    assert rep[0] == Q.OK and rep[1] == 16 and rep[4] == 4
+    assert o["outlier"][0][3] == 0                                              # NaN: every comparison is false
+    assert o["outlier"][0][7] == 1                                              # inf > threshold
+    assert np.isfinite(o["Tcw"]).all()
+
+
+def _expected_epilogue(b, plain, mode, flags):
+    fp, out = b["frame_point"][0].copy(), plain["outlier"][0].copy()
+    n = int(b["n"][0])
+    dis = np.full(b["cap"], -1, i32)
+    dis[n:] = prefilled(b)["discarded"][0][n:]
+    has = np.zeros(b["cap"], bool)
+    has[:n] = fp[:n] >= 0
+    obs = np.zeros(b["cap"], bool)
+    obs[has] = (b["point_flags"][0][fp[has]] & 2) != 0
+    isout = has & (out == 1)
+    if mode == Q.DISCARD:
+        dis[isout] = fp[isout]; fp[isout] = -1; out[isout] = 0
+        return fp, out, dis, int((has & ~isout).sum()), int((has & ~isout & obs).sum())
+    inl = has & ~isout
+    ca = int(inl.sum()) if flags & Q.ONLY_TRACKING else int((inl & obs).sum())
+    if flags & Q.STEREO:
+        dis[isout] = fp[isout]; fp[isout] = -1
+    return fp, out, dis, ca, int(inl.sum())
+
+
+@pytest.mark.parametrize("name", ["discard_f0", "localmap_f0", "localmap_f1", "localmap_f2"])
+def test_modes(name):
+    b, o, plain = case(name), reference(name), reference("A")
+    fp, out, dis, ca, cb = _expected_epilogue(b, plain, b["mode"], b["flags"])
+    assert (o["frame_point"][0] == fp).all() and (o["outlier"][0] == out).all() and (o["discarded"][0] == dis).all()
+    assert o["report"][0][6:].tolist() == [ca, cb] and o["report"][0][:6].tolist() == plain["report"][0][:6].tolist()
+    assert o["Tcw"].tobytes() == plain["Tcw"].tobytes()
+    if name == "localmap_f2":                                                   # the stereo outlier: no point, byte still set
+        gone = np.flatnonzero(o["discarded"][0][:int(b["n"][0])] >= 0)
+        assert len(gone) == 12 and (o["outlier"][0][gone] == 1).all() and (o["frame_point"][0][gone] == -1).all()
+    if name == "localmap_f0":
+        assert (o["frame_point"][0] == b["frame_point"][0]).all() and ca < cb
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# scenes
+@pytest.mark.parametrize("name", ["A", "B"])
+def test_scene_flags_the_displaced_set(name):
+    b, o = case(name), reference(name)
+    f = make_frame(1 if name == "A" else 2, 60, 12, 2 / 3 if name == "A" else 0.0, 128)
+    assert sorted(np.flatnonzero(o["outlier"][0] == 1).tolist()) == sorted(f["displaced"].tolist())
+    rep = o["report"][0]
+    assert rep[:5].tolist() == [Q.OK, 60, 12, 48, 4] and 12 <= rep[5] <= 40
+    free = np.ones(b["cap"], bool)
+    free[f["slots"]] = False
+    assert (o["outlier"][0][free] == SENTINEL).all()
+    Rt = o["Tcw"][0].reshape(3, 4)
+    assert np.abs(Rt[:, :3] - R_TRUE).max() < 2e-3 and np.abs(Rt[:, 3] - T_TRUE).max() < 0.05
+
+
+def test_batch_row_equals_frame_alone():
+    a, bt = reference("A_alone"), reference("batch3")
+    for k in ("report", "outlier", "frame_point", "Tcw"):
+        assert a[k][0].tobytes() == bt[k][3].tobytes()
+    assert bt["report"][1].tolist() == [Q.TOO_FEW, 0, 0, 0, 0, 0, 0, 0] == bt["report"][2].tolist()
+    assert reference("A")["Tcw"].tobytes() == a["Tcw"].tobytes()                  # the layout does not enter either
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the textbook restatement
+def textbook(b, f):
+    """The same rules with rotation matrices, math.sin / cos, numpy.linalg.solve and sequential sums."""
+    fx, fy, cx, cy, bf = (float(f32(v)) for v in CAM)
+    n = int(b["n"][f])
+    fp = b["frame_point"][f]
+    r = 0 if b["world_row"] is None else int(b["world_row"][f])
+    idx = [i for i in range(n) if fp[i] >= 0]
+    X = b["world"][r][fp[idx]].astype(f64)
+    ur = np.full(len(idx), -1.0) if b["u_right"] is None else b["u_right"][f][idx].astype(f64)
+    st = ~(ur < 0)
+    obs = np.c_[b["kps"][f]["x"][idx], b["kps"][f]["y"][idx], ur].astype(f64)
+    inv = INV_SIGMA2[b["kps"][f]["octave"][idx]].astype(f64)
+    delta = np.where(st, Q.f32(math.sqrt(7.815)), Q.f32(math.sqrt(5.991)))
+    thr = np.where(st, f32(7.815), f32(5.991))
+    T0 = b["Tcw"][f].astype(f64).reshape(3, 4)
+    # the input rotation is what SE3Quat(R, t) makes of the float matrix (a unit quaternion; the trace is positive here): without
+    # this the two start 3e-8 apart, and Levenberg-Marquardt, which stops on a 1e-3 relative gain, keeps them that far apart
+    tr_ = np.trace(T0[:, :3])
+    assert tr_ > 0
+    qw = math.sqrt(1 + tr_) / 2
+    qv = np.array([T0[2, 1] - T0[1, 2], T0[0, 2] - T0[2, 0], T0[1, 0] - T0[0, 1]]) / (4 * qw)
+    nq = math.sqrt(qw * qw + qv @ qv)
+    qw, qv = qw / nq, qv / nq
+    Kq = np.array([[0, -qv[2], qv[1]], [qv[2], 0, -qv[0]], [-qv[1], qv[0], 0]])
+    T0 = np.c_[np.eye(3) + 2 * qw * Kq + 2 * Kq @ Kq, T0[:, 3]]
+
+    def errs(R, t):
+        P = X @ R.T + t
+        invz = np.where(st, (1.0 / P[:, 2]).astype(f32).astype(f64), 1.0 / P[:, 2])
+        p0, p1 = P[:, 0] * invz * fx + cx, P[:, 1] * invz * fy + cy
+        e = np.c_[obs[:, 0] - p0, obs[:, 1] - p1, np.where(st, obs[:, 2] - (p0 - bf * invz), 0.0)]
+        return e, (e * e).sum(1) * inv, P
+
+    def exp(u):
+        om, up = u[:3], u[3:]
+        th = math.sqrt(om @ om)
+        O = np.array([[0, -om[2], om[1]], [om[2], 0, -om[0]], [-om[1], om[0], 0]])
+        if th < 1e-5:
+            R = np.eye(3) + O + O @ O
+            return R, R @ up
+        R = np.eye(3) + math.sin(th) / th * O + (1 - math.cos(th)) / th ** 2 * O @ O
+        V = np.eye(3) + (1 - math.cos(th)) / th ** 2 * O + (th - math.sin(th)) / th ** 3 * O @ O
+        return R, V @ up
+
+    def rob(c, kernel):
+        if not kernel:
+            return c, np.ones_like(c)
+        s = np.sqrt(np.maximum(c, 1e-300))
+        big = c > delta * delta
+        return np.where(big, 2 * s * delta - delta * delta, c), np.where(big, delta / s, 1.0)
+
+    def system(R, t, act, kernel):
+        e, c, P = errs(R, t)
+        rho0, rho1 = rob(c, kernel)
+        H, g, chi = np.zeros((6, 6)), np.zeros(6), 0.0
+        for j in np.flatnonzero(act):
+            x, y, iz = P[j, 0], P[j, 1], 1.0 / P[j, 2]
+            J = np.array([[x * y * iz * iz * fx, -(1 + x * x * iz * iz) * fx, y * iz * fx, -iz * fx, 0, x * iz * iz * fx],
+                          [(1 + y * y * iz * iz) * fy, -x * y * iz * iz * fy, -x * iz * fy, 0, -iz * fy, y * iz * iz * fy]])
+            if st[j]:
+                J = np.vstack([J, [J[0, 0] - bf * y * iz * iz, J[0, 1] + bf * x * iz * iz, J[0, 2], J[0, 3], 0, J[0, 5] - bf * iz * iz]])
+            w = rho1[j] * inv[j]
+            k = len(J)
+            H += J.T @ J * w
+            g -= J.T @ e[j, :k] * w
+            chi += rho0[j]
+        return H, g, chi
+
+    def chi_of(R, t, act, kernel):
+        c = errs(R, t)[1]
+        s = 0.0
+        for v in rob(c, kernel)[0][act]:
+            s += v
+        return s
+
+    out = np.zeros(len(idx), bool)
+    margin = np.inf
+    x = np.zeros(6)
+    for rnd in range(4):
+        R, t = T0[:, :3].copy(), T0[:, 3].copy()
+        Rt, tt = R, t
+        kernel, act = rnd < 3, ~out
+        lam = ni = 0.0
+        nbad = 0
+        for it in range(10):
+            H, g, cur = system(R, t, act, kernel)
+            ini = cur
+            if it == 0:
+                lam, ni, nbad = 1e-5 * np.abs(np.diag(H)).max(), 2.0, 0
+            q = 0
+            while True:
+                try:
+                    xs = np.linalg.solve(H + lam * np.eye(6), g)
+                    ok = bool(np.all(np.linalg.eigvalsh(H + lam * np.eye(6)) > 0))
+                except np.linalg.LinAlgError:
+                    ok = False
+                if ok:
+                    x = xs
+                dR, dtv = exp(x)
+                Rt, tt = dR @ R, dR @ t + dtv
+                tmp = chi_of(Rt, tt, act, kernel) if ok else Q.DBL_MAX
+                rho = (cur - tmp) / (x @ (lam * x + g) + 1e-3)
+                if rho > 0 and math.isfinite(tmp):
+                    lam *= max(1 / 3, min(1 - (2 * rho - 1) ** 3, 2 / 3))
+                    ni, cur, R, t = 2.0, tmp, Rt, tt
+                else:
+                    lam *= ni
+                    ni *= 2
+                q += 1
+                if not (rho < 0 and q < 10):
+                    break
+            if q == 10 or rho == 0:
+                break
+            nbad = nbad + 1 if (ini - cur) * 1e3 < ini else 0
+            if nbad >= 3:
+                break
+        c_est, c_try = errs(R, t)[1], errs(Rt, tt)[1]
+        c = np.where(out, c_est, c_try)
+        margin = min(margin, np.abs(c / thr - 1).min())
+        out = c.astype(f32) > thr
+        if len(idx) < 10:
+            break
+    return R, t, out, idx, margin
+
+
+def test_textbook_distance():
+    worst = dict(R=0.0, t=0.0)
+    for name, b in (("A", case("A")), ("B", case("B")), ("s31", batch_of([make_frame(31, 60, 12, 0.5, 128)], 128, shared=True)),
+                    ("s32", batch_of([make_frame(32, 60, 12, 0.5, 128)], 128, shared=True))):
+        R, t, out, idx, margin = textbook(b, 0)
+        assert margin > 1e-6, (name, margin)                                    # the precondition: no chi2 at its threshold
+        p64 = []
+        o = run_seqref(b, poses=p64)
+        pose = np.array(p64).reshape(3, 4)                                      # the seqref's pose before its rounding to float
+        assert (o["outlier"][0][idx] == out).all(), name
+        dR, dt = np.abs(pose[:, :3] - R).max(), np.abs(pose[:, 3] - t).max()
+        print("%s: |dR| %.3g  |dt| %.3g  margin %.3g" % (name, dR, dt, margin))
+        worst["R"], worst["t"] = max(worst["R"], dR), max(worst["t"], dt)
+    print("worst", worst)
+    assert worst["R"] <= TOL["R"] and worst["t"] <= TOL["t"], worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# det_sincos64
+def _grid():
+    x = np.exp(np.linspace(math.log(1e-8), math.log(100.0), 100000))
+    return np.r_[x, -x]
+
+
+def test_det_sincos64_within_one_ulp():
+    worst = 0.0
+    for x in _grid().tolist():
+        s, c = Q.det_sincos64(x)
+        ms, mc = math.sin(x), math.cos(x)
+        worst = max(worst, abs(s - ms) / math.ulp(ms), abs(c - mc) / math.ulp(mc))
+    print("det_sincos64: worst %.3g ulp" % worst)
+    assert worst <= 1.0
+    assert Q.det_sincos64(0.0) == (0.0, 1.0)
+    for x in (1e7, float("inf"), float("nan")):                                 # outside the stated range: deterministic
+        s, c = Q.det_sincos64(x)
+        assert s != s and c != c
+    s, c = Q.det_sincos64(1.6e6)                                                # still inside
+    assert abs(s - math.sin(1.6e6)) < 1e-9 and abs(c - math.cos(1.6e6)) < 1e-9
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the host build of orbhip_poseopt_core.h
+@functools.lru_cache(maxsize=None)
+def host_program():
+    import tempfile
+    d = tempfile.mkdtemp(prefix="poseopt_host_")
+    exe = os.path.join(d, "poseopt_host")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I",
+                    os.path.join(ROOT, "orb_slam2_comment_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "poseopt_host.cpp"),
+                    "-o", exe], check=True)
+    return exe
+
+
+def pack(b, o):
+    head = [b["frames"], b["cap"], b["wrows"], b["pcap"], int(b["u_right"] is not None), int(b["world_row"] is not None), 1, 1,
+            len(INV_SIGMA2), b["mode"], b["flags"]]
+    parts = [np.array(head, i32), np.array(CAM, f32), INV_SIGMA2, b["kps"], b["n"]]
+    parts += [b["u_right"]] if b["u_right"] is not None else []
+    parts += [b["world"], b["point_flags"]]
+    parts += [b["world_row"]] if b["world_row"] is not None else []
+    parts += [o["Tcw"], o["frame_point"], o["outlier"], o["discarded"]]
+    return b"".join(np.ascontiguousarray(p).tobytes() for p in parts)
+
+
+def run_host(name, tmp_path):
+    b = case(name)
+    o = prefilled(b)
+    fin, fout = tmp_path / (name + ".in"), tmp_path / (name + ".out")
+    fin.write_bytes(pack(b, o))
+    subprocess.run([host_program(), "run", str(fin), str(fout)], check=True)
+    raw = fout.read_bytes()
+    off = 0
+    for k in ("Tcw", "frame_point", "outlier", "discarded", "report"):
+        cnt = o[k].nbytes
+        o[k] = np.frombuffer(raw[off:off + cnt], o[k].dtype).reshape(o[k].shape)
+        off += cnt
+    o["last64"] = np.frombuffer(raw[off:], f64)                                  # est (7), tried (7) of the last frame's last round
+    assert o["last64"].size == 14
+    return o
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_host_build_matches_seqref(name, tmp_path):
+    assert_same(run_host(name, tmp_path), reference(name), name)
+
+
+def test_host_build_writes_the_last_tried_estimate(tmp_path):
+    """The state rule 4 reads: after the last round the core's estimate and its last TRIED estimate are the seqref's, bit
+    for bit; in scene A they differ (the round ends on a rejected trial), so a core that never wrote the tried one shows."""
+    for name in ("A", "B", "comeback"):
+        b, last = case(name), []
+        o = prefilled(b)
+        Q.pose_optimization(b["kps"][0]["x"], b["kps"][0]["y"], b["kps"][0]["octave"], int(b["n"][0]),
+                            None if b["u_right"] is None else b["u_right"][0], b["world"][0], b["point_flags"][0], INV_SIGMA2, CAM,
+                            o["Tcw"][0], o["frame_point"][0], o["outlier"][0], None, last64=last)
+        got = run_host(name, tmp_path)["last64"]
+        assert got.tobytes() == np.array(last, f64).tobytes(), name
+        if name == "A":                                                         # its last round ends on a rejected trial
+            assert got[:7].tobytes() != got[7:].tobytes()
+
+
+def test_host_classification_reads_the_tried_estimate_for_inliers(tmp_path):
+    """Rule 4 in the shared C++ text: po_classify, the classification po_run runs after every round, on the two-pose input
+    of test_rule4_...: est = the optimised pose, tried = the perturbed input, where most edges fail.  With all edges
+    inliers the flags are those at `tried`, with all outliers those at `est`, with a mixed set each edge follows its own
+    flag; the three differ, so reading the wrong pose for either kind of edge shows."""
+    b = case("A")
+    edges = Q.build_edges(b["kps"][0]["x"], b["kps"][0]["y"], b["kps"][0]["octave"], int(b["n"][0]), b["u_right"][0], b["world"][0],
+                          INV_SIGMA2, b["frame_point"][0])
+    cam = tuple(float(f32(v)) for v in CAM)
+    good, far = Q.pose_from_Tcw(reference("A")["Tcw"][0]), Q.pose_from_Tcw(b["Tcw"][0])
+    ne = len(edges)
+    seen = []
+    for k, flags in enumerate(([False] * ne, [True] * ne, [j % 3 == 0 for j in range(ne)])):
+        want, n_bad = Q.classify(edges, list(flags), good, far, cam)
+        e_out = np.zeros(b["cap"], u8)
+        e_out[:ne] = flags
+        fin, fout = tmp_path / ("c%d.in" % k), tmp_path / ("c%d.out" % k)
+        fin.write_bytes(pack(b, prefilled(b)) + np.array(good[0] + good[1] + far[0] + far[1], f64).tobytes() + e_out.tobytes())
+        subprocess.run([host_program(), "classify", str(fin), str(fout)], check=True)
+        raw = fout.read_bytes()
+        got, counts = np.frombuffer(raw[:b["cap"]], u8), np.frombuffer(raw[b["cap"]:], i32)
+        assert counts.tolist() == [n_bad, ne] and got[:ne].astype(bool).tolist() == want, k
+        seen.append(tuple(want))
+    assert len(set(seen)) == 3
+
+
+def test_host_sincos_matches_seqref(tmp_path):
+    x = np.r_[_grid()[::50], 0.0, 1e7, 1.6e6, -1.6e6, math.pi / 4, 0.7853981633974484]
+    fin, fout = tmp_path / "x.in", tmp_path / "x.out"
+    fin.write_bytes(x.astype(f64).tobytes())
+    subprocess.run([host_program(), "sincos", str(fin), str(fout)], check=True)
+    got = np.frombuffer(fout.read_bytes(), f64).reshape(-1, 2)
+    want = np.array([Q.det_sincos64(v) for v in x.tolist()])
+    ok = (got.view(np.uint64) == want.view(np.uint64)) | (np.isnan(got) & np.isnan(want))
+    assert ok.all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# argument checks: refused before the handle is looked at, so a null handle and no GPU will do
+def test_argument_checks():
+    import ctypes as C
+    from orb_slam2_comment_amd import capi
+    from orb_slam2_comment_amd.matcher import make_camera
+    L = capi.lib()
+    b = case("discard_f0")
+    cam = make_camera(*CAM[:4], (0, 0, 1241, 376), [1.2 ** l for l in range(8)], mbf=CAM[4])
+    p = capi.ptr
+
+    def call(entry, **kw):
+        a = dict(b, **{k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in prefilled(b).items()})
+        a.update(cam=cam, inv=INV_SIGMA2)
+        a.update(kw)
+        keep = [np.ascontiguousarray(a[k]) if a[k] is not None else None
+                for k in ("kps", "n", "u_right", "world", "point_flags", "world_row", "Tcw", "frame_point", "outlier", "discarded",
+                          "report", "inv")]
+        before = [None if k is None else k.tobytes() for k in keep]
+        rc = entry(None, a["frames"], p(keep[0]), p(keep[1]), a["cap"], p(keep[2]), p(keep[3]), p(keep[4]), a["wrows"], a["pcap"],
+                   p(keep[5]), C.byref(a["cam"]) if a["cam"] is not None else None, p(keep[11]), a["mode"], a["flags"], p(keep[6]),
+                   p(keep[7]), p(keep[8]), p(keep[9]), p(keep[10]))
+        assert before == [None if k is None else k.tobytes() for k in keep]      # nothing written
+        return rc
+
+    cam0 = make_camera(*CAM[:4], (0, 0, 1241, 376), [1.2 ** l for l in range(8)], mbf=CAM[4])
+    cam0.n_levels = 0
+    for entry in (L.orbhip_pose_optimization_device, L.orbhip_pose_optimization):
+        assert call(entry) == capi.E_ARG                                        # everything fine but the null handle
+        assert call(entry, cap=4097) == capi.E_CAPACITY
+        for bad in (dict(frames=-1), dict(cap=0), dict(wrows=-1), dict(pcap=-1), dict(mode=3), dict(mode=-1), dict(flags=4),
+                    dict(kps=None), dict(n=None), dict(world=None), dict(Tcw=None), dict(frame_point=None), dict(outlier=None),
+                    dict(report=None), dict(cam=None), dict(inv=None), dict(point_flags=None), dict(cam=cam0), dict(wrows=0)):
+            assert call(entry, **bad) == capi.E_ARG, bad
+        assert call(entry, mode=capi.POSEOPT_PLAIN, point_flags=None, discarded=None, u_right=None, world_row=None) == capi.E_ARG
+    host = L.orbhip_pose_optimization
+    assert call(host, frames=0) == capi.E_ARG                                   # valid, so only the handle is missing
+    fp = b["frame_point"].copy(); fp[0, 0] = b["pcap"]
+    assert call(host, frame_point=fp) == capi.E_ARG
+    fp = b["frame_point"].copy(); fp[0, 1] = -2
+    assert call(host, frame_point=fp) == capi.E_ARG
+    k = b["kps"].copy(); k["octave"][0, int(np.flatnonzero(b["frame_point"][0] >= 0)[0])] = 8
+    assert call(host, kps=k) == capi.E_ARG
+    assert call(host, n=np.array([b["cap"] + 1], i32)) == capi.E_ARG
+    assert call(host, n=np.array([-1], i32)) == capi.E_ARG
+    assert call(host, world_row=np.array([1], i32)) == capi.E_ARG
+    assert (capi.POSEOPT_PLAIN, capi.POSEOPT_DISCARD, capi.POSEOPT_LOCAL_MAP) == (Q.PLAIN, Q.DISCARD, Q.LOCAL_MAP)
+    assert (capi.POSEOPT_ONLY_TRACKING, capi.POSEOPT_STEREO) == (Q.ONLY_TRACKING, Q.STEREO)
+    assert (capi.POSEOPT_OK, capi.POSEOPT_TOO_FEW, capi.POSEOPT_ONE_ROUND) == (Q.OK, Q.TOO_FEW, Q.ONE_ROUND)
