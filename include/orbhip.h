@@ -1316,6 +1316,60 @@ int orbhip_pose_optimization(orbhip_matcher *m, int frames, const orbhip_keypoin
                              const orbhip_camera *cam, const float *inv_level_sigma2, int mode, int flags, float *Tcw,
                              int32_t *frame_point, uint8_t *outlier, int32_t *discarded, int32_t *report);
 
+/* ---- Sim3 optimisation ----------------------------------------------------------------------------------------------------
+ * Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241) for the current key frame and C loop candidates in one call, one
+ * workgroup each: the step of LoopClosing::ComputeSim3 (src/LoopClosing.cc:326) after orbhip_search_by_sim3.  One Sim3
+ * vertex, fixed points, the pairs of EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ with g2o's numeric Jacobian
+ * (delta = 1e-9), Huber in both rounds: optimize(5), the check, optimize(nBad > 0 ? 10 : 5), the check.  The arithmetic,
+ * operation by operation, is tests/seqref/sim3opt.py and DESIGN.md section 3 (the order of the sums over pairs, det_exp64,
+ * det_sincos64, the pivoted LDLt at 7 and Eigen's quaternion formulas are stated there).
+ *
+ * C, cur, d_kf_index [C], rows, cap, np, pcap, tables and match_form are those of orbhip_sim3_setup_device; of the tables'
+ * kps x, y and octave are read.  inv_level_sigma2 [cam->n_levels] = mvInvLevelSigma2 (host); cam supplies fx, fy, cx, cy for
+ * both key frames.  th2 is 10 in the reference (> 0); deltaHuber is sqrtf(th2).  fix_scale = bFixScale: the scale leaves
+ * the call with the bits it came with.
+ * d_select [C] uint8, nullable: a candidate with 0 is skipped, nothing of its rows is written except report[0] =
+ * ORBHIP_SIM3OPT_SKIPPED; a caller passes the batch of orbhip_sim3_iterate_device as it stands and selects the candidates
+ * that reported ORBHIP_SIM3_RETURNED.
+ * In/out: d_matched12 [C][cap] int32 = vpMatches1 per slot of `cur`, as point indices or as slots of the candidate row
+ * (resolved as setup resolves them).  A slot i < n[cur] makes a pair unless it has no match, slot i of `cur` has no point,
+ * either point is not ORBHIP_POINT_PRESENT or the candidate's point has no observation in the candidate row (i2 =
+ * GetIndexInKeyFrame; the index of the first point in `cur` is not asked for: obs1 is key point i).  An entry becomes -1
+ * where the reference nulls vpMatches1[idx] (after either round); every other entry keeps its bytes.
+ * In: d_sim3 [C][16] float as orbhip_sim3_iterate_device writes it: R (9), t (3), s; it enters as
+ * g2o::Sim3(toMatrix3d(R), toVector3d(t), s).
+ * Out: d_S12 [C][8] double = g2oS12 after the call: quaternion x, y, z, w (not normalised, as g2o keeps it), t, s; on the
+ * early return (nCorrespondences - nBad < 10) the input Sim3 converted as above.  d_Scw [C][12] float, nullable =
+ * Converter::toCvMat(gScm * gSmw) with gSmw = Sim3(R2w, t2w, 1) (src/LoopClosing.cc:333-335): rows of s R | t; written for
+ * every candidate that did not return early, the caller uses the rows whose nIn >= 20.  d_report [C][8] int32 = {status,
+ * nCorrespondences, nBad (of the first check), nIn (the return value; 0 on the early return), LM iterations of round 1, of
+ * round 2, 0, 0}; status: ORBHIP_SIM3OPT_OK, ORBHIP_SIM3OPT_TOO_FEW (the early return; with no pair at all nothing is
+ * optimised) or ORBHIP_SIM3OPT_SKIPPED.
+ * chi2 is compared as a double against (double)th2, strictly, at the last TRIED estimate of the round; a NaN from a point at
+ * zero depth is not greater and its pair stays.
+ *
+ * Asynchronous on the matcher's stream, no host synchronisation, no staging copy, one launch.  cap <= 4096
+ * (ORBHIP_E_CAPACITY beyond); C, rows, np or pcap negative, np > pcap, cap < 1, cur outside [0, rows), a bad match_form,
+ * cam->n_levels outside [1, ORBHIP_MAX_LEVELS], th2 not > 0 or a null required pointer: ORBHIP_E_ARG; all refused before any
+ * device work.  C == 0: success, nothing written.  The device form does not range-check the tables' contents or the
+ * candidate rows. */
+#define ORBHIP_SIM3OPT_OK      0
+#define ORBHIP_SIM3OPT_TOO_FEW 1
+#define ORBHIP_SIM3OPT_SKIPPED 2
+int orbhip_optimize_sim3_device(orbhip_matcher *m, int C, int cur, const void *d_kf_index, const orbhip_camera *cam, int rows, int cap,
+                                int np, int pcap, const orbhip_sim3_tables *tables, int match_form, const float *inv_level_sigma2,
+                                float th2, int fix_scale, const void *d_select, void *d_matched12, const void *d_sim3, void *d_S12,
+                                void *d_Scw, void *d_report);
+/* Host buffers, synchronous: one staging copy, the launch, one read-back; what the call does not write keeps the caller's
+ * values.  The same table record with host pointers; kf_index [C], select [C] or NULL, matched12 [C][cap], sim3 [C][16],
+ * S12 [C][8], Scw [C][12] or NULL, report [C][8].  It range-checks what orbhip_sim3_ransac range-checks of the tables, the
+ * candidate rows and the matches, and the octaves of the slots of `cur` that hold a point: ORBHIP_E_ARG, before the handle
+ * is looked at. */
+int orbhip_optimize_sim3(orbhip_matcher *m, int C, int cur, const int32_t *kf_index, const orbhip_camera *cam, int rows, int cap, int np,
+                         int pcap, const orbhip_sim3_tables *tables, int match_form, const float *inv_level_sigma2, float th2,
+                         int fix_scale, const uint8_t *select, int32_t *matched12, const float *sim3, double *S12, float *Scw,
+                         int32_t *report);
+
 /* ---- creating new map points -------------------------------------------------------------------------------------
  * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) for the current key frame and K neighbours in one call, up
  * to the point where the map graph is touched: `new MapPoint`, AddObservation and everything after :434 stay with the

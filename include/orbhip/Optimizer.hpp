@@ -1,6 +1,7 @@
-// C++ host-side mirror of ORB_SLAM2::Optimizer (include/Optimizer.h) above orbhip_pose_optimization of orbhip.h: the one
-// function of it the library has, PoseOptimization.  Header-only, no OpenCV and no g2o: a frame is the arrays the
-// reference's Frame holds (mvKeysUn, mvuRight, mvpMapPoints as indices into the map arrays, mvbOutlier, mTcw).
+// C++ host-side mirror of ORB_SLAM2::Optimizer (include/Optimizer.h) above orbhip_pose_optimization and
+// orbhip_optimize_sim3 of orbhip.h: the two functions of it the library has, PoseOptimization and OptimizeSim3.  Header-only,
+// no OpenCV and no g2o: a frame is the arrays the reference's Frame holds (mvKeysUn, mvuRight, mvpMapPoints as indices
+// into the map arrays, mvbOutlier, mTcw); key frames and map points of OptimizeSim3 are the tables of orbhip_sim3_tables.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -16,6 +17,11 @@ struct PoseFrame {
     std::vector<int32_t> mvpMapPoints;
     std::vector<uint8_t> mvbOutlier;
     float mTcw[12];                         // [Rcw | tcw], row-major
+};
+
+// g2o::Sim3 as OptimizeSim3 takes and leaves it: the quaternion as g2o keeps it (x, y, z, w; not normalised), t, s.
+struct Sim3 {
+    double r[4], t[3], s;
 };
 
 class Optimizer {
@@ -68,6 +74,45 @@ public:
         check(orbhip_pose_optimization_device(matcher.handle(), frames, d_kps, d_n, cap, d_u_right, d_world, d_point_flags, wrows, pcap,
                                               d_world_row, &cam, invLevelSigma2.data(), mode, flags, d_Tcw, d_frame_point, d_outlier,
                                               d_discarded, d_report), "orbhip_pose_optimization_device");
+    }
+
+    // int Optimizer::OptimizeSim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches1, g2o::Sim3 &g2oS12, const float
+    // th2, const bool bFixScale): pKF1 is bank row `cur`, pKF2 bank row `kf` of the tables (host pointers), vpMatches1 one
+    // entry per slot of pKF1 (point indices or slots of pKF2, see matchForm; negative = none), nulled entries become -1.
+    // sim3 [16] is what Sim3Solver leaves (GetEstimatedRotation is its start: R (9), t (3), s): the start, as
+    // g2o::Sim3(toMatrix3d(R), toVector3d(t), s).  g2oS12 receives the estimate (the start on the early return).  Scw [12],
+    // if given, receives Converter::toCvMat(g2oS12 * Sim3(R2w, t2w, 1)) unless the function returned early.  report [8] as
+    // orbhip_optimize_sim3_device lists it.  Returns nIn.
+    static int OptimizeSim3(ORBmatcher &matcher, const orbhip_camera &cam, int rows, int cap, int np, int pcap,
+                            const orbhip_sim3_tables &tables, int cur, int kf, std::vector<int32_t> &vpMatches1, int matchForm,
+                            const std::vector<float> &invLevelSigma2, const float *sim3, Sim3 &g2oS12, float th2, bool bFixScale,
+                            float *Scw = nullptr, int32_t *report = nullptr)
+    {
+        std::vector<int32_t> matched((size_t)(cap > 0 ? cap : 1), -1);
+        for (size_t i = 0; i < vpMatches1.size() && i < matched.size(); ++i) matched[i] = vpMatches1[i];
+        const int32_t row = kf;
+        double S12[8] = {0, 0, 0, 1, 0, 0, 0, 1};
+        int32_t rep[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        check(orbhip_optimize_sim3(matcher.handle(), 1, cur, &row, &cam, rows, cap, np, pcap, &tables, matchForm, invLevelSigma2.data(),
+                                   th2, bFixScale ? 1 : 0, nullptr, matched.data(), sim3, S12, Scw, rep), "orbhip_optimize_sim3");
+        for (size_t i = 0; i < vpMatches1.size() && i < matched.size(); ++i) vpMatches1[i] = matched[i];
+        for (int i = 0; i < 4; ++i) g2oS12.r[i] = S12[i];
+        for (int i = 0; i < 3; ++i) g2oS12.t[i] = S12[4 + i];
+        g2oS12.s = S12[7];
+        if (report) for (int i = 0; i < 8; ++i) report[i] = rep[i];
+        return rep[3];
+    }
+
+    // The same over device arrays for C candidates at once, asynchronous on the matcher's stream: the arguments of
+    // orbhip_optimize_sim3_device, which see.
+    static void OptimizeSim3Device(ORBmatcher &matcher, int C, int cur, const void *d_kf_index, const orbhip_camera &cam, int rows, int cap,
+                                   int np, int pcap, const orbhip_sim3_tables &tables, int matchForm,
+                                   const std::vector<float> &invLevelSigma2, float th2, bool bFixScale, const void *d_select,
+                                   void *d_matched12, const void *d_sim3, void *d_S12, void *d_Scw, void *d_report)
+    {
+        check(orbhip_optimize_sim3_device(matcher.handle(), C, cur, d_kf_index, &cam, rows, cap, np, pcap, &tables, matchForm,
+                                          invLevelSigma2.data(), th2, bFixScale ? 1 : 0, d_select, d_matched12, d_sim3, d_S12, d_Scw,
+                                          d_report), "orbhip_optimize_sim3_device");
     }
 };
 

@@ -142,6 +142,9 @@ POSEOPT_PLAIN, POSEOPT_DISCARD, POSEOPT_LOCAL_MAP = range(3)
 POSEOPT_ONLY_TRACKING, POSEOPT_STEREO = 1, 2
 POSEOPT_OK, POSEOPT_TOO_FEW, POSEOPT_ONE_ROUND = range(3)
 POSEOPT_REPORT = ("status", "n_initial", "n_bad", "returned", "rounds", "iterations", "count_a", "count_b")
+# ORBHIP_SIM3OPT_*: report[0] of orbhip_optimize_sim3_device
+SIM3OPT_OK, SIM3OPT_TOO_FEW, SIM3OPT_SKIPPED = range(3)
+SIM3OPT_REPORT = ("status", "n_correspondences", "n_bad", "n_in", "iterations_1", "iterations_2", "reserved_0", "reserved_1")
 REMAP_TABLE_SIZE = 4096
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
@@ -285,6 +288,10 @@ SYMBOLS = [
                                              _vp, _vp, _vp, _vp, _vp]),
     ("orbhip_pose_optimization", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, C.POINTER(Camera), _vp, _i, _i,
                                       _vp, _vp, _vp, _vp, _vp]),
+    ("orbhip_optimize_sim3_device", _i, [_vp, _i, _i, _vp, C.POINTER(Camera), _i, _i, _i, _i, C.POINTER(Sim3Tables), _i, _vp, _f, _i,
+                                         _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("orbhip_optimize_sim3", _i, [_vp, _i, _i, _vp, C.POINTER(Camera), _i, _i, _i, _i, C.POINTER(Sim3Tables), _i, _vp, _f, _i,
+                                  _vp, _vp, _vp, _vp, _vp, _vp]),
     ("orbhip_matcher_set_stream", _i, [_vp, _vp]),
     ("orbhip_matcher_sync", _i, [_vp]),
     ("orbhip_compute_stereo_matches_device", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,

@@ -271,6 +271,29 @@ struct PoArgs {
 int launch_pose_optimization(hipStream_t stream, PoArgs A);
 }  // namespace orbhip
 
+#include "orbhip_sim3opt_core.h"
+
+namespace orbhip {
+// orbhip_sim3opt.hip: the arguments of orbhip_optimize_sim3_device
+struct S3oArgs {
+    S3oTables T;                        // slot_point, n, the observation table, flags
+    const orbhip_keypoint *kps;         // [rows][cap]
+    const float *world, *Tcw;           // [pcap][3], [rows][12]
+    const int *kf_index;                // [C]
+    const uint8_t *select;              // [C] or nullptr
+    const float *sim3;                  // [C][16]
+    int *matched12;                     // [C][cap]
+    double *S12;                        // [C][8]
+    float *Scw;                         // [C][12] or nullptr
+    int *report;                        // [C][8]
+    float inv[ORBHIP_MAX_LEVELS];       // mvInvLevelSigma2
+    S3oCam cam;
+    double delta, th2;                  // (float)sqrt(th2) and th2, widened
+    int C, n_levels, fix_scale;
+};
+int launch_optimize_sim3(hipStream_t stream, S3oArgs A);
+}  // namespace orbhip
+
 struct orbhip_extractor {
     int nfeatures = 0;
     double scaleFactor = 1.2;

@@ -5984,6 +5984,29 @@ static int sim3_host_count(int cur, int kf, int cap, const orbhip_sim3_tables *t
     return N;
 }
 
+// what the host forms over orbhip_sim3_tables check of the tables' contents
+static int sim3_check_tables(const char *who, const orbhip_camera *cam, int rows, int cap, int np, const orbhip_sim3_tables *t)
+{
+    const int32_t *slot_point = (const int32_t *)t->slot_point, *n = (const int32_t *)t->n, *obs_start = (const int32_t *)t->obs_start;
+    const int32_t *obs_kf = (const int32_t *)t->obs_kf, *obs_idx = (const int32_t *)t->obs_idx;
+    const orbhip_keypoint *kps = (const orbhip_keypoint *)t->kps;
+    const size_t RC = (size_t)rows * cap;
+    for (int r = 0; r < rows; ++r)
+        if (n[r] < 0 || n[r] > cap) { set_error("%s: bank row %d holds a count outside [0, cap]", who, r); return ORBHIP_E_ARG; }
+    for (size_t i = 0; i < RC; ++i)
+        if (slot_point[i] < -1 || slot_point[i] >= np) { set_error("%s: bank row %zu holds a point index out of range", who, i / cap); return ORBHIP_E_ARG; }
+    if (obs_start[0] != 0) { set_error("%s: obs_start must start at 0", who); return ORBHIP_E_ARG; }
+    for (int p = 0; p < np; ++p)
+        if (obs_start[p + 1] < obs_start[p]) { set_error("%s: obs_start must be non-decreasing (entry %d)", who, p); return ORBHIP_E_ARG; }
+    const size_t total = (size_t)obs_start[np];
+    for (size_t o = 0; o < total; ++o) {
+        if (obs_kf[o] < 0 || obs_kf[o] >= rows || obs_idx[o] < 0 || obs_idx[o] >= cap) { set_error("%s: observation %zu is outside the bank", who, o); return ORBHIP_E_ARG; }
+        const int oct = kps[(size_t)obs_kf[o] * cap + obs_idx[o]].octave;
+        if (oct < 0 || oct >= cam->n_levels) { set_error("%s: observation %zu names a key point of octave %d", who, o, oct); return ORBHIP_E_ARG; }
+    }
+    return ORBHIP_OK;
+}
+
 int orbhip_sim3_ransac(orbhip_matcher *m, int C, int cur, const int32_t *kf_index, const orbhip_camera *cam, int rows, int cap, int np,
                        int pcap, const orbhip_sim3_tables *t, const int32_t *matched12, int match_form, const float *level_sigma2,
                        double prob, int min_inliers, int max_its, int fix_scale, const int32_t *draws, int n_iterations, int32_t *state,
@@ -5997,19 +6020,8 @@ int orbhip_sim3_ransac(orbhip_matcher *m, int C, int cur, const int32_t *kf_inde
     const int32_t *obs_kf = (const int32_t *)t->obs_kf, *obs_idx = (const int32_t *)t->obs_idx;
     const orbhip_keypoint *kps = (const orbhip_keypoint *)t->kps;
     const size_t RC = (size_t)rows * cap, P = (size_t)np, Cn = (size_t)C;
-    for (int r = 0; r < rows; ++r)
-        if (n[r] < 0 || n[r] > cap) { set_error("sim3_ransac: bank row %d holds a count outside [0, cap]", r); return ORBHIP_E_ARG; }
-    for (size_t i = 0; i < RC; ++i)
-        if (slot_point[i] < -1 || slot_point[i] >= np) { set_error("sim3_ransac: bank row %zu holds a point index out of range", i / cap); return ORBHIP_E_ARG; }
-    if (obs_start[0] != 0) { set_error("sim3_ransac: obs_start must start at 0"); return ORBHIP_E_ARG; }
-    for (int p = 0; p < np; ++p)
-        if (obs_start[p + 1] < obs_start[p]) { set_error("sim3_ransac: obs_start must be non-decreasing (entry %d)", p); return ORBHIP_E_ARG; }
+    if (int rc = sim3_check_tables("sim3_ransac", cam, rows, cap, np, t)) return rc;
     const size_t total = (size_t)obs_start[np];
-    for (size_t o = 0; o < total; ++o) {
-        if (obs_kf[o] < 0 || obs_kf[o] >= rows || obs_idx[o] < 0 || obs_idx[o] >= cap) { set_error("sim3_ransac: observation %zu is outside the bank", o); return ORBHIP_E_ARG; }
-        const int oct = kps[(size_t)obs_kf[o] * cap + obs_idx[o]].octave;
-        if (oct < 0 || oct >= cam->n_levels) { set_error("sim3_ransac: observation %zu names a key point of octave %d", o, oct); return ORBHIP_E_ARG; }
-    }
     const int n_iter = std::min(n_iterations, max_its);
     for (int c = 0; c < C; ++c) {
         const int kf = kf_index[c];
@@ -6426,6 +6438,116 @@ int orbhip_pose_optimization(orbhip_matcher *m, int frames, const orbhip_keypoin
     auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
     back(Tcw, d_Tcw, Fn * 48); back(frame_point, d_fp, FC * 4); back(outlier, d_out, FC); back(report, d_rep, Fn * 32);
     if (discarded) back(discarded, d_dis, FC * 4);
+    return ORBHIP_OK;
+}
+
+// ---- Sim3 optimisation (kernel: orbhip_sim3opt.hip) ----------------------------------------------------------------------
+static int sim3opt_args(int C, int cur, const void *kf_index, const orbhip_camera *cam, int rows, int cap, int np, int pcap,
+                        const orbhip_sim3_tables *t, int match_form, const float *inv_level_sigma2, float th2, const void *matched12,
+                        const void *sim3, const void *S12, const void *report)
+{
+    if (C < 0 || cap < 1 || !cam || rows < 0 || np < 0 || pcap < 0 || np > pcap || cur < 0 || cur >= rows || !inv_level_sigma2 ||
+        cam->n_levels < 1 || cam->n_levels > ORBHIP_MAX_LEVELS || !(th2 > 0.f) || !kf_index || !matched12 || !sim3 || !S12 || !report ||
+        (match_form != ORBHIP_SIM3_MATCH_POINTS && match_form != ORBHIP_SIM3_MATCH_SLOTS))
+        return ORBHIP_E_ARG;
+    if (!t || !t->slot_point || !t->obs_start || !t->obs_kf || !t->obs_idx || !t->flags || !t->world || !t->Tcw || !t->kps || !t->n)
+        return ORBHIP_E_ARG;
+    if (cap > kS3oCapMax) { set_error("optimize_sim3: capacity %d exceeds %d", cap, kS3oCapMax); return ORBHIP_E_CAPACITY; }
+    return ORBHIP_OK;
+}
+
+static int sim3opt_launch(orbhip_matcher *m, int C, int cur, const void *d_kf_index, const orbhip_camera *cam, int rows, int cap, int np,
+                          const orbhip_sim3_tables *t, int match_form, const float *inv_level_sigma2, float th2, int fix_scale,
+                          const void *d_select, void *d_matched12, const void *d_sim3, void *d_S12, void *d_Scw, void *d_report)
+{
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    S3oArgs A;
+    memset(&A, 0, sizeof(A));
+    A.T.slot_point = (const int *)t->slot_point; A.T.n = (const int *)t->n; A.T.obs_start = (const int *)t->obs_start;
+    A.T.obs_kf = (const int *)t->obs_kf; A.T.obs_idx = (const int *)t->obs_idx; A.T.flags = (const uint8_t *)t->flags;
+    A.T.rows = rows; A.T.cap = cap; A.T.np = np; A.T.cur = cur; A.T.match_form = match_form;
+    A.kps = (const orbhip_keypoint *)t->kps; A.world = (const float *)t->world; A.Tcw = (const float *)t->Tcw;
+    A.kf_index = (const int *)d_kf_index; A.select = (const uint8_t *)d_select; A.sim3 = (const float *)d_sim3;
+    A.matched12 = (int *)d_matched12; A.S12 = (double *)d_S12; A.Scw = (float *)d_Scw; A.report = (int *)d_report;
+    for (int l = 0; l < ORBHIP_MAX_LEVELS; ++l) A.inv[l] = l < cam->n_levels ? inv_level_sigma2[l] : 0.f;
+    A.cam.fx = (double)cam->fx; A.cam.fy = (double)cam->fy; A.cam.cx = (double)cam->cx; A.cam.cy = (double)cam->cy;
+    A.delta = (double)std::sqrt(th2);                                          // src/Optimizer.cc:1095: a float
+    A.th2 = (double)th2;
+    A.C = C; A.n_levels = cam->n_levels; A.fix_scale = fix_scale != 0;
+    return launch_optimize_sim3(m->stream, A);
+}
+
+int orbhip_optimize_sim3_device(orbhip_matcher *m, int C, int cur, const void *d_kf_index, const orbhip_camera *cam, int rows, int cap,
+                                int np, int pcap, const orbhip_sim3_tables *t, int match_form, const float *inv_level_sigma2, float th2,
+                                int fix_scale, const void *d_select, void *d_matched12, const void *d_sim3, void *d_S12, void *d_Scw,
+                                void *d_report)
+{
+    if (int rc = sim3opt_args(C, cur, d_kf_index, cam, rows, cap, np, pcap, t, match_form, inv_level_sigma2, th2, d_matched12, d_sim3,
+                              d_S12, d_report))
+        return rc;
+    if (!m) return ORBHIP_E_ARG;
+    if (C == 0) return ORBHIP_OK;
+    return sim3opt_launch(m, C, cur, d_kf_index, cam, rows, cap, np, t, match_form, inv_level_sigma2, th2, fix_scale, d_select,
+                          d_matched12, d_sim3, d_S12, d_Scw, d_report);
+}
+
+int orbhip_optimize_sim3(orbhip_matcher *m, int C, int cur, const int32_t *kf_index, const orbhip_camera *cam, int rows, int cap, int np,
+                         int pcap, const orbhip_sim3_tables *t, int match_form, const float *inv_level_sigma2, float th2, int fix_scale,
+                         const uint8_t *select, int32_t *matched12, const float *sim3, double *S12, float *Scw, int32_t *report)
+{
+    if (int rc = sim3opt_args(C, cur, kf_index, cam, rows, cap, np, pcap, t, match_form, inv_level_sigma2, th2, matched12, sim3, S12,
+                              report))
+        return rc;
+    if (int rc = sim3_check_tables("optimize_sim3", cam, rows, cap, np, t)) return rc;
+    const int32_t *slot_point = (const int32_t *)t->slot_point, *n = (const int32_t *)t->n, *obs_start = (const int32_t *)t->obs_start;
+    const orbhip_keypoint *kps = (const orbhip_keypoint *)t->kps;
+    for (int i = 0; i < n[cur]; ++i) {
+        const size_t k = (size_t)cur * cap + i;
+        if (slot_point[k] >= 0 && (kps[k].octave < 0 || kps[k].octave >= cam->n_levels)) {
+            set_error("optimize_sim3: key point %d of the current key frame has octave %d", i, kps[k].octave);
+            return ORBHIP_E_ARG;
+        }
+    }
+    for (int c = 0; c < C; ++c) {
+        const int kf = kf_index[c];
+        if (kf < 0 || kf >= rows) { set_error("optimize_sim3: candidate %d (row %d) is outside the bank", c, kf); return ORBHIP_E_ARG; }
+        const int32_t *mt = matched12 + (size_t)c * cap;
+        for (int i1 = 0; i1 < n[cur]; ++i1)
+            if (mt[i1] >= (match_form == ORBHIP_SIM3_MATCH_SLOTS ? cap : np)) { set_error("optimize_sim3: match %d of candidate %d is out of range", i1, c); return ORBHIP_E_ARG; }
+    }
+    if (!m) return ORBHIP_E_ARG;
+    if (C == 0) return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const size_t RC = (size_t)rows * cap, P = (size_t)np, Cn = (size_t)C, CC = Cn * cap, total = (size_t)obs_start[np];
+    Stage st;
+    int rc;
+    const size_t in_bytes = 2 * al256(RC * 4) + al256(RC * sizeof(orbhip_keypoint)) + al256(P * 4 + 4) + 2 * al256(total * 4) + al256(P) +
+                            al256(P * 12) + al256((size_t)rows * 48) + al256((size_t)rows * 4) + al256(Cn * 4) + al256(Cn) + al256(Cn * 64);
+    const size_t out_size = al256(CC * 4) + al256(Cn * 64) + al256(Cn * 48) + al256(Cn * 32);
+    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
+    orbhip_sim3_tables dt;
+    dt.slot_point = st.put(slot_point, RC); dt.obs_start = st.put(obs_start, P + 1);
+    dt.obs_kf = st.put((const int32_t *)t->obs_kf, total); dt.obs_idx = st.put((const int32_t *)t->obs_idx, total);
+    dt.flags = st.put((const uint8_t *)t->flags, P); dt.world = st.put((const float *)t->world, P * 3);
+    dt.Tcw = st.put((const float *)t->Tcw, (size_t)rows * 12); dt.kps = st.put(kps, RC); dt.n = st.put(n, (size_t)rows);
+    const int32_t *d_kf = st.put(kf_index, Cn);
+    const uint8_t *d_sel = select ? st.put(select, Cn) : nullptr;
+    const float *d_sim3 = st.put(sim3, Cn * 16);
+    const size_t out_off = st.off;
+    const int32_t *d_matched = st.put(matched12, CC);
+    const double *d_S12 = st.put(S12, Cn * 8);
+    const float *d_Scw = Scw ? st.put(Scw, Cn * 12) : nullptr;
+    const int32_t *d_rep = st.put(report, Cn * 8);
+    const size_t out_bytes = st.off - out_off;
+    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = sim3opt_launch(m, C, cur, d_kf, cam, rows, cap, np, &dt, match_form, inv_level_sigma2, th2, fix_scale, d_sel,
+                             (void *)d_matched, d_sim3, (void *)d_S12, (void *)d_Scw, (void *)d_rep)))
+        return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
+    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
+    back(matched12, d_matched, CC * 4); back(S12, d_S12, Cn * 64); back(report, d_rep, Cn * 32);
+    if (Scw) back(Scw, d_Scw, Cn * 48);
     return ORBHIP_OK;
 }
 

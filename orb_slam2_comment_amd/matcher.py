@@ -972,6 +972,49 @@ class ORBmatcher:
         return dict(Tcw=T[:frames].copy(), frame_point=fp.copy(), outlier=out[:frames].copy(),
                     discarded=dis[:frames].copy(), report=rep[:frames].copy())
 
+    # -- Sim3 optimisation (src/Optimizer.cc:1046-1241) --------------------------
+    def OptimizeSim3Device(self, C_, cur, d_kf_index, cam, rows, cap, np_, pcap, tables, match_form, inv_level_sigma2,
+                           d_matched12, d_sim3, d_S12, d_Scw, d_report, th2=10.0, fix_scale=False, d_select=None):
+        """Optimizer::OptimizeSim3 for the current key frame and C_ loop candidates, one workgroup each
+        (orbhip_optimize_sim3_device in include/orbhip.h).  `tables` is a dict with the keys of SIM3_TABLES holding device
+        addresses (ints, or tensors), the d_* are device addresses; d_Scw and d_select may be None.  Asynchronous on the
+        matcher's stream."""
+        sig = self._sigma2(inv_level_sigma2, cam)
+        rt = self._record(capi.Sim3Tables, tables)
+        dp = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a)  # noqa: E731
+        check(self._lib.orbhip_optimize_sim3_device(self._h, int(C_), int(cur), dp(d_kf_index), C.byref(cam), int(rows), int(cap),
+                                                    int(np_), int(pcap), C.byref(rt), int(match_form), ptr(sig), float(th2),
+                                                    int(bool(fix_scale)), dp(d_select), dp(d_matched12), dp(d_sim3), dp(d_S12),
+                                                    dp(d_Scw), dp(d_report)), "orbhip_optimize_sim3_device")
+
+    def OptimizeSim3(self, tables, cur, kf_index, cam, matched12, match_form, inv_level_sigma2, sim3, th2=10.0, fix_scale=False,
+                     select=None, want_scw=True, fill=0):
+        """The same from host arrays in one staged copy, one launch and one read-back (orbhip_optimize_sim3), range-checked
+        (OrbHipError with E_ARG).  `tables` as for Sim3Setup, matched12 [C, cap], sim3 [C, 16] as Sim3Iterate returns it,
+        select [C] or None.  Returns dict(matched12 [C, cap], S12 [C, 8] float64, Scw [C, 12] float32 or None, report [C, 8] in
+        the order of capi.SIM3OPT_REPORT): copies, what the call does not write holds the input / `fill` bytes."""
+        T, rows, cap, n_pts, pcap = self._sim3_tables(tables)
+        kf = np.ascontiguousarray(kf_index, np.int32).reshape(-1)
+        Cn = len(kf)
+        c1 = max(Cn, 1)
+        m12 = np.zeros((c1, cap), np.int32)
+        m12[:Cn] = np.asarray(matched12, np.int32).reshape(Cn, cap)
+        rec = np.zeros((c1, 16), np.float32)
+        rec[:Cn] = np.asarray(sim3, np.float32).reshape(Cn, 16)
+        sel = None if select is None else np.ascontiguousarray(select, np.uint8).reshape(Cn)
+        sig = self._sigma2(inv_level_sigma2, cam)
+        S12 = np.full(c1 * 64, fill, np.uint8).view(np.float64).reshape(c1, 8)
+        Scw = np.full(c1 * 48, fill, np.uint8).view(np.float32).reshape(c1, 12) if want_scw else None
+        rep = np.full(c1 * 32, fill, np.uint8).view(np.int32).reshape(c1, 8)
+        keep = {k: (np.zeros(1, a.dtype) if a.size == 0 else a) for k, a in T.items()}
+        rt = self._record(capi.Sim3Tables, {k: ptr(a).value for k, a in keep.items()})
+        pad = [None if a is None else (np.zeros(4, a.dtype) if a.size == 0 else a) for a in (kf, sel)]
+        check(self._lib.orbhip_optimize_sim3(self._h, Cn, int(cur), ptr(pad[0]), C.byref(cam), rows, cap, n_pts, pcap, C.byref(rt),
+                                             int(match_form), ptr(sig), float(th2), int(bool(fix_scale)), ptr(pad[1]), ptr(m12),
+                                             ptr(rec), ptr(S12), ptr(Scw), ptr(rep)), "orbhip_optimize_sim3")
+        return dict(matched12=m12[:Cn].copy(), S12=S12[:Cn].copy(), Scw=None if Scw is None else Scw[:Cn].copy(),
+                    report=rep[:Cn].copy())
+
     # -- device-resident, batched SearchByProjection ---------------------------
     def set_stream(self, stream):
         check(self._lib.orbhip_matcher_set_stream(self._h, stream), "orbhip_matcher_set_stream")
