@@ -1370,6 +1370,70 @@ int orbhip_optimize_sim3(orbhip_matcher *m, int C, int cur, const int32_t *kf_in
                          int fix_scale, const uint8_t *select, int32_t *matched12, const float *sim3, double *S12, float *Scw,
                          int32_t *report);
 
+/* ---- local bundle adjustment --------------------------------------------------------------------------------------------
+ * Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778) for one current key frame, device resident: the link of a
+ * local-mapping step between orbhip_update_connections_device and orbhip_cull_key_frames_device.  The three lists
+ * (:456-504), one SE3 vertex per listed key frame, one point vertex per local point, one EdgeSE3ProjectXYZ /
+ * EdgeStereoSE3ProjectXYZ per observation whose key frame is not bad (:589), g2o's Levenberg-Marquardt over
+ * BlockSolver_6_3 (the Schur complement over points, a dense system over the free poses), optimize(5) with Huber, the
+ * level-1 rule (:672-702), optimize(10) without kernel, the final check (:715-743) and the write-back (:762-776).  The
+ * arithmetic, operation by operation, is tests/seqref/lba.py and DESIGN.md section 3: everything is fp64 with one rounding
+ * per operation, the orders of all sums, the 3x3 inverse, the order of the poses in the Schur system (list order) and its
+ * unpivoted LDLt are stated there.
+ *
+ * cur: the row of the current key frame; id0_row: the row whose mnId is 0 (setFixed although local), or -1.
+ * orbhip_lba_tables: slot_point [rows][cap] int32, n [rows] int32, kf_bad [rows] uint8 (nullable: none is bad) as in the
+ * culling entries; obs_start [np+1], obs_kf, obs_idx int32: the observation table; flags [pcap] uint8, ORBHIP_POINT_PRESENT
+ * = !isBad(); kps [rows][cap] (x, y and octave are read); u_right [rows][cap] float, nullable (every observation is
+ * monocular), monocular iff u_right < 0 (:594); ord_kf [rows][rows], n_ord [rows] int32 of orbhip_covis_state
+ * (GetVectorCovisibleKeyFrames); in/out: Tcw [rows][12] float, world [pcap][3] float.  Where the reference iterates a
+ * std::map<KeyFrame*, size_t> the order is the table's order.
+ * orbhip_lba_out: local_kf [rows], fixed_kf [rows] int32 = lLocalKeyFrames, lFixedCameras in push_back order; local_point
+ * [max_points] int32 = lLocalMapPoints likewise, the point list orbhip_update_map_points_device takes (chain it with
+ * ORBHIP_UPDATE_NORMAL_DEPTH for :776); erase [max_edges][3] int32 = (key-frame row, key-point index, point) of vToErase in
+ * the reference's order, all monocular edges in creation order, then all stereo edges: applying them (:748-757) stays with
+ * the caller; report [16] int32 = {status, local key frames, fixed key frames, local points, monocular edges, stereo
+ * edges, edges at level 1 after round 1, erase rows, outer iterations and trials of round 1, of round 2, poses in the
+ * system of round 1, of round 2, 0, samples of the stop byte}.
+ * status: ORBHIP_LBA_OK; ORBHIP_LBA_STOPPED (the stop byte was set at :655-657: only the report is written);
+ * ORBHIP_LBA_ONE_ROUND (bDoMore false: the final check and the write-back still happen); ORBHIP_LBA_CAPACITY (more than
+ * ORBHIP_LBA_MAX_LOCAL non-fixed local key frames, more than max_points points or max_edges edges: only the report is
+ * written, the caller falls back).  Every local key frame and every local point is written back, as toCvMat(SE3Quat) and
+ * as float, the fixed id0_row included; fixed cameras are not.
+ * d_stop: nullable device byte = *pbStopFlag, sampled where the reference samples it (:655, :664, terminate() at the top of
+ * every outer iteration and at the end of a rejected trial).  Only "set before the call" and "null" are deterministic.
+ *
+ * Asynchronous on the matcher's stream, no host synchronisation: a fixed sequence of small launches (5 and 10 outer
+ * iterations of at most 10 trials) is enqueued, every kernel reads the state record first and leaves when its step is not
+ * due; no workgroup waits for another.  The workspace belongs to the handle and is sized from rows, pcap, max_points and
+ * max_edges; growing it is the only thing that synchronises.  rows, cap <= 4096 (ORBHIP_E_CAPACITY beyond); negative counts,
+ * cap < 1, np > pcap, cur outside [0, rows), id0_row outside [-1, rows), max_points or max_edges < 1, cam->n_levels outside
+ * [1, ORBHIP_MAX_LEVELS] or a null required pointer: ORBHIP_E_ARG; all refused before any device work.  The device form
+ * does not range-check the tables' contents. */
+#define ORBHIP_LBA_MAX_LOCAL 128
+#define ORBHIP_LBA_OK        0
+#define ORBHIP_LBA_STOPPED   1
+#define ORBHIP_LBA_ONE_ROUND 2
+#define ORBHIP_LBA_CAPACITY  3
+typedef struct orbhip_lba_tables {
+    const void *slot_point, *n, *kf_bad, *obs_start, *obs_kf, *obs_idx, *flags, *kps, *u_right, *ord_kf, *n_ord;
+    void *Tcw, *world;
+} orbhip_lba_tables;
+typedef struct orbhip_lba_out {
+    void *local_kf, *fixed_kf, *local_point, *erase, *report;
+} orbhip_lba_out;
+int orbhip_local_bundle_adjustment_device(orbhip_matcher *m, int cur, int id0_row, const orbhip_camera *cam, int rows, int cap, int np,
+                                          int pcap, const orbhip_lba_tables *tables, const float *inv_level_sigma2, int max_points,
+                                          int max_edges, const void *d_stop, const orbhip_lba_out *out);
+/* Host buffers, synchronous: one staging copy, the call, one read-back; what the call does not write keeps the caller's
+ * values.  The same records with host pointers; stop points to a host byte or is NULL.  It range-checks what the device
+ * form does not: n in [0, cap], slot points in [-1, np), obs_start non-decreasing from 0 or above, obs_kf in [0, rows),
+ * obs_idx in [0, cap), n_ord in [0, rows], the head of ord_kf[cur] in [0, rows), and the octaves of observed key points in
+ * [0, cam->n_levels): ORBHIP_E_ARG, before the handle is looked at. */
+int orbhip_local_bundle_adjustment(orbhip_matcher *m, int cur, int id0_row, const orbhip_camera *cam, int rows, int cap, int np,
+                                   int pcap, const orbhip_lba_tables *tables, const float *inv_level_sigma2, int max_points,
+                                   int max_edges, const uint8_t *stop, const orbhip_lba_out *out);
+
 /* ---- creating new map points -------------------------------------------------------------------------------------
  * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) for the current key frame and K neighbours in one call, up
  * to the point where the map graph is touched: `new MapPoint`, AddObservation and everything after :434 stay with the

@@ -1,5 +1,6 @@
-// C++ host-side mirror of ORB_SLAM2::Optimizer (include/Optimizer.h) above orbhip_pose_optimization and
-// orbhip_optimize_sim3 of orbhip.h: the two functions of it the library has, PoseOptimization and OptimizeSim3.  Header-only,
+// C++ host-side mirror of ORB_SLAM2::Optimizer (include/Optimizer.h) above orbhip_pose_optimization, orbhip_optimize_sim3
+// and orbhip_local_bundle_adjustment of orbhip.h: the three functions of it the library has, PoseOptimization, OptimizeSim3
+// and LocalBundleAdjustment (whose key frames and map points are the tables of orbhip_lba_tables).  Header-only,
 // no OpenCV and no g2o: a frame is the arrays the reference's Frame holds (mvKeysUn, mvuRight, mvpMapPoints as indices
 // into the map arrays, mvbOutlier, mTcw); key frames and map points of OptimizeSim3 are the tables of orbhip_sim3_tables.
 #pragma once
@@ -22,6 +23,14 @@ struct PoseFrame {
 // g2o::Sim3 as OptimizeSim3 takes and leaves it: the quaternion as g2o keeps it (x, y, z, w; not normalised), t, s.
 struct Sim3 {
     double r[4], t[3], s;
+};
+
+// What LocalBundleAdjustment leaves besides the poses and points it writes into the tables: the three lists in push_back
+// order (key-frame rows, point indices), vToErase as (key-frame row, key-point index, point) triples in the reference's
+// order, and the report of orbhip_local_bundle_adjustment_device.
+struct LocalBA {
+    std::vector<int32_t> lLocalKeyFrames, lFixedCameras, lLocalMapPoints, vToErase;
+    int32_t report[16];
 };
 
 class Optimizer {
@@ -113,6 +122,42 @@ public:
         check(orbhip_optimize_sim3_device(matcher.handle(), C, cur, d_kf_index, &cam, rows, cap, np, pcap, &tables, matchForm,
                                           invLevelSigma2.data(), th2, bFixScale ? 1 : 0, d_select, d_matched12, d_sim3, d_S12, d_Scw,
                                           d_report), "orbhip_optimize_sim3_device");
+    }
+
+    // void Optimizer::LocalBundleAdjustment(KeyFrame *pKF, bool *pbStopFlag, Map *pMap): pKF is bank row `cur` of the tables
+    // (host pointers; Tcw and world are updated in place), id0Row the row whose mnId is 0 (or -1), pbStopFlag may be null.
+    // `out` receives lLocalKeyFrames, lFixedCameras, lLocalMapPoints and vToErase; applying vToErase (:748-757) and
+    // UpdateNormalAndDepth of the local points (:776) stay with the caller.  Returns the status (ORBHIP_LBA_*): on
+    // ORBHIP_LBA_STOPPED and ORBHIP_LBA_CAPACITY nothing but out.report is written and the lists are empty.
+    static int LocalBundleAdjustment(ORBmatcher &matcher, const orbhip_camera &cam, int rows, int cap, int np, int pcap,
+                                     const orbhip_lba_tables &tables, int cur, int id0Row, const std::vector<float> &invLevelSigma2,
+                                     int maxPoints, int maxEdges, const bool *pbStopFlag, LocalBA &out)
+    {
+        std::vector<int32_t> lkf((size_t)(rows > 0 ? rows : 1), -1), fkf(lkf), lpt((size_t)(maxPoints > 0 ? maxPoints : 1), -1),
+            er((size_t)(maxEdges > 0 ? maxEdges : 1) * 3, -1);
+        for (int i = 0; i < 16; ++i) out.report[i] = 0;
+        const uint8_t stop = pbStopFlag && *pbStopFlag ? 1 : 0;
+        orbhip_lba_out o;
+        o.local_kf = lkf.data(); o.fixed_kf = fkf.data(); o.local_point = lpt.data(); o.erase = er.data(); o.report = out.report;
+        check(orbhip_local_bundle_adjustment(matcher.handle(), cur, id0Row, &cam, rows, cap, np, pcap, &tables, invLevelSigma2.data(),
+                                             maxPoints, maxEdges, pbStopFlag ? &stop : nullptr, &o), "orbhip_local_bundle_adjustment");
+        const bool wrote = out.report[0] == ORBHIP_LBA_OK || out.report[0] == ORBHIP_LBA_ONE_ROUND;
+        out.lLocalKeyFrames.assign(lkf.begin(), lkf.begin() + (wrote ? out.report[1] : 0));
+        out.lFixedCameras.assign(fkf.begin(), fkf.begin() + (wrote ? out.report[2] : 0));
+        out.lLocalMapPoints.assign(lpt.begin(), lpt.begin() + (wrote ? out.report[3] : 0));
+        out.vToErase.assign(er.begin(), er.begin() + (wrote ? 3 * (size_t)out.report[7] : 0));
+        return out.report[0];
+    }
+
+    // The same over device arrays, asynchronous on the matcher's stream, no host synchronisation: the arguments of
+    // orbhip_local_bundle_adjustment_device, which see.
+    static void LocalBundleAdjustmentDevice(ORBmatcher &matcher, int cur, int id0Row, const orbhip_camera &cam, int rows, int cap, int np,
+                                            int pcap, const orbhip_lba_tables &tables, const std::vector<float> &invLevelSigma2,
+                                            int maxPoints, int maxEdges, const void *d_stop, const orbhip_lba_out &out)
+    {
+        check(orbhip_local_bundle_adjustment_device(matcher.handle(), cur, id0Row, &cam, rows, cap, np, pcap, &tables,
+                                                    invLevelSigma2.data(), maxPoints, maxEdges, d_stop, &out),
+              "orbhip_local_bundle_adjustment_device");
     }
 };
 

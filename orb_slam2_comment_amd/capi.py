@@ -91,6 +91,17 @@ class Sim3Solvers(C.Structure):
                                           "state")]
 
 
+class LbaTables(C.Structure):
+    """orbhip_lba_tables: what orbhip_local_bundle_adjustment* reads; Tcw and world are in/out."""
+    _fields_ = [(k, C.c_void_p) for k in ("slot_point", "n", "kf_bad", "obs_start", "obs_kf", "obs_idx", "flags", "kps", "u_right",
+                                          "ord_kf", "n_ord", "Tcw", "world")]
+
+
+class LbaOut(C.Structure):
+    """orbhip_lba_out: the three lists, the erase rows and the report of orbhip_local_bundle_adjustment*."""
+    _fields_ = [(k, C.c_void_p) for k in ("local_kf", "fixed_kf", "local_point", "erase", "report")]
+
+
 class PnpParams(C.Structure):
     """orbhip_pnp_params: the arguments of PnPsolver::SetRansacParameters."""
     _fields_ = [("prob", C.c_double), ("min_inliers", C.c_int32), ("max_its", C.c_int32), ("min_set", C.c_int32),
@@ -145,6 +156,11 @@ POSEOPT_REPORT = ("status", "n_initial", "n_bad", "returned", "rounds", "iterati
 # ORBHIP_SIM3OPT_*: report[0] of orbhip_optimize_sim3_device
 SIM3OPT_OK, SIM3OPT_TOO_FEW, SIM3OPT_SKIPPED = range(3)
 SIM3OPT_REPORT = ("status", "n_correspondences", "n_bad", "n_in", "iterations_1", "iterations_2", "reserved_0", "reserved_1")
+# ORBHIP_LBA_*: report[0] of orbhip_local_bundle_adjustment_device
+LBA_OK, LBA_STOPPED, LBA_ONE_ROUND, LBA_CAPACITY = range(4)
+LBA_MAX_LOCAL = 128
+LBA_REPORT = ("status", "n_local_kf", "n_fixed_kf", "n_local_points", "n_mono", "n_stereo", "n_level1", "n_erase", "iterations_1",
+              "trials_1", "iterations_2", "trials_2", "poses_1", "poses_2", "reserved_0", "stop_samples")
 REMAP_TABLE_SIZE = 4096
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
@@ -292,6 +308,10 @@ SYMBOLS = [
                                          _vp, _vp, _vp, _vp, _vp, _vp]),
     ("orbhip_optimize_sim3", _i, [_vp, _i, _i, _vp, C.POINTER(Camera), _i, _i, _i, _i, C.POINTER(Sim3Tables), _i, _vp, _f, _i,
                                   _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("orbhip_local_bundle_adjustment_device", _i, [_vp, _i, _i, C.POINTER(Camera), _i, _i, _i, _i, C.POINTER(LbaTables), _vp, _i, _i,
+                                                   _vp, C.POINTER(LbaOut)]),
+    ("orbhip_local_bundle_adjustment", _i, [_vp, _i, _i, C.POINTER(Camera), _i, _i, _i, _i, C.POINTER(LbaTables), _vp, _i, _i, _vp,
+                                            C.POINTER(LbaOut)]),
     ("orbhip_matcher_set_stream", _i, [_vp, _vp]),
     ("orbhip_matcher_sync", _i, [_vp]),
     ("orbhip_compute_stereo_matches_device", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,

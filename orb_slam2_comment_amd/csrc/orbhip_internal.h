@@ -294,6 +294,14 @@ struct S3oArgs {
 int launch_optimize_sim3(hipStream_t stream, S3oArgs A);
 }  // namespace orbhip
 
+#include "orbhip_lba_core.h"
+
+namespace orbhip {
+// orbhip_lba.hip: the tables, the outputs and the scalars travel in LbaWs; the workspace pointers are carved by the launch
+size_t lba_workspace_bytes(LbaWs W);
+int launch_local_bundle_adjustment(hipStream_t stream, LbaWs W, void *workspace);
+}  // namespace orbhip
+
 struct orbhip_extractor {
     int nfeatures = 0;
     double scaleFactor = 1.2;

@@ -3715,8 +3715,8 @@ struct orbhip_matcher {
     hipStream_t stream = nullptr;       // stream every launch goes to
     hipStream_t own_stream = nullptr;   // created with the handle
     // grow-only device scratch
-    void *buf[26] = {};
-    size_t cap[26] = {};
+    void *buf[27] = {};
+    size_t cap[27] = {};
     bool lds_attr_set = false, bow_attr_set = false;
 #ifdef ORBHIP_DEVTOOLS
     int window_lanes = 0;               // development build: lanes per query of k_window_search forced to 16 / 64 (0: the rule)
@@ -3813,7 +3813,7 @@ static SigmaTab sigma_tab(const float *inv_level_sigma2, int n_levels)
     return sig;
 }
 
-enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_COVIS, S_CULL, S_SIM3, S_SIM3LIM, S_SIM3SOLV, S_PNP, S_PNPTAB, S_PNPSOLV, S_NSLOTS };
+enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_COVIS, S_CULL, S_SIM3, S_SIM3LIM, S_SIM3SOLV, S_PNP, S_PNPTAB, S_PNPSOLV, S_LBA, S_NSLOTS };
 static_assert(S_NSLOTS == sizeof(orbhip_matcher::buf) / sizeof(void *), "one scratch buffer per slot");
 
 static int stage_begin(orbhip_matcher *m, size_t total, Stage *st)
@@ -6548,6 +6548,120 @@ int orbhip_optimize_sim3(orbhip_matcher *m, int C, int cur, const int32_t *kf_in
     auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
     back(matched12, d_matched, CC * 4); back(S12, d_S12, Cn * 64); back(report, d_rep, Cn * 32);
     if (Scw) back(Scw, d_Scw, Cn * 48);
+    return ORBHIP_OK;
+}
+
+// ---- local bundle adjustment (kernels: orbhip_lba.hip) ---------------------------------------------------------------------
+static int lba_args(int cur, int id0_row, const orbhip_camera *cam, int rows, int cap, int np, int pcap, const orbhip_lba_tables *t,
+                    const float *inv_level_sigma2, int max_points, int max_edges, const orbhip_lba_out *out)
+{
+    if (!cam || rows < 0 || cap < 1 || np < 0 || pcap < 0 || np > pcap || cur < 0 || cur >= rows || id0_row < -1 || id0_row >= rows ||
+        max_points < 1 || max_edges < 1 || !inv_level_sigma2 || cam->n_levels < 1 || cam->n_levels > ORBHIP_MAX_LEVELS)
+        return ORBHIP_E_ARG;
+    if (!t || !t->slot_point || !t->n || !t->obs_start || !t->obs_kf || !t->obs_idx || !t->flags || !t->kps || !t->ord_kf || !t->n_ord ||
+        !t->Tcw || !t->world || !out || !out->local_kf || !out->fixed_kf || !out->local_point || !out->erase || !out->report)
+        return ORBHIP_E_ARG;
+    if (cap > 4096 || rows > 4096) { set_error("local_bundle_adjustment: rows %d or capacity %d exceeds 4096", rows, cap); return ORBHIP_E_CAPACITY; }
+    return ORBHIP_OK;
+}
+
+static int lba_launch(orbhip_matcher *m, int cur, int id0_row, const orbhip_camera *cam, int rows, int cap, int np, int pcap,
+                      const orbhip_lba_tables *t, const float *inv_level_sigma2, int max_points, int max_edges, const void *d_stop,
+                      const orbhip_lba_out *out)
+{
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    LbaWs W;
+    memset(&W, 0, sizeof(W));
+    W.slot_point = (const int *)t->slot_point; W.n = (const int *)t->n; W.kf_bad = (const uint8_t *)t->kf_bad;
+    W.obs_start = (const int *)t->obs_start; W.obs_kf = (const int *)t->obs_kf; W.obs_idx = (const int *)t->obs_idx;
+    W.flags = (const uint8_t *)t->flags; W.kps = (const orbhip_keypoint *)t->kps; W.u_right = (const float *)t->u_right;
+    W.ord_kf = (const int *)t->ord_kf; W.n_ord = (const int *)t->n_ord; W.Tcw = (float *)t->Tcw; W.world = (float *)t->world;
+    W.o_local_kf = (int *)out->local_kf; W.o_fixed_kf = (int *)out->fixed_kf; W.o_local_point = (int *)out->local_point;
+    W.o_erase = (int *)out->erase; W.o_report = (int *)out->report;
+    W.stop = (const uint8_t *)d_stop;
+    for (int l = 0; l < ORBHIP_MAX_LEVELS; ++l) W.inv[l] = l < cam->n_levels ? inv_level_sigma2[l] : 0.f;
+    W.cam.fx = (double)cam->fx; W.cam.fy = (double)cam->fy; W.cam.cx = (double)cam->cx; W.cam.cy = (double)cam->cy;
+    W.cam.bf = (double)cam->mbf;
+    W.cam.delta_mono = (double)(float)std::sqrt(5.991);                       // src/Optimizer.cc:569-570
+    W.cam.delta_stereo = (double)(float)std::sqrt(7.815);
+    W.cur = cur; W.id0_row = id0_row; W.rows = rows; W.cap = cap; W.np = np; W.pcap = pcap; W.n_levels = cam->n_levels;
+    W.max_points = max_points; W.max_edges = max_edges;
+    void *ws;
+    if (int rc = scratch(m, S_LBA, lba_workspace_bytes(W), &ws)) return rc;
+    return launch_local_bundle_adjustment(m->stream, W, ws);
+}
+
+int orbhip_local_bundle_adjustment_device(orbhip_matcher *m, int cur, int id0_row, const orbhip_camera *cam, int rows, int cap, int np,
+                                          int pcap, const orbhip_lba_tables *tables, const float *inv_level_sigma2, int max_points,
+                                          int max_edges, const void *d_stop, const orbhip_lba_out *out)
+{
+    if (int rc = lba_args(cur, id0_row, cam, rows, cap, np, pcap, tables, inv_level_sigma2, max_points, max_edges, out)) return rc;
+    if (!m) return ORBHIP_E_ARG;
+    return lba_launch(m, cur, id0_row, cam, rows, cap, np, pcap, tables, inv_level_sigma2, max_points, max_edges, d_stop, out);
+}
+
+int orbhip_local_bundle_adjustment(orbhip_matcher *m, int cur, int id0_row, const orbhip_camera *cam, int rows, int cap, int np,
+                                   int pcap, const orbhip_lba_tables *t, const float *inv_level_sigma2, int max_points, int max_edges,
+                                   const uint8_t *stop, const orbhip_lba_out *out)
+{
+    if (int rc = lba_args(cur, id0_row, cam, rows, cap, np, pcap, t, inv_level_sigma2, max_points, max_edges, out)) return rc;
+    const int32_t *slot_point = (const int32_t *)t->slot_point, *n = (const int32_t *)t->n, *obs_start = (const int32_t *)t->obs_start;
+    const int32_t *obs_kf = (const int32_t *)t->obs_kf, *obs_idx = (const int32_t *)t->obs_idx;
+    const int32_t *ord_kf = (const int32_t *)t->ord_kf, *n_ord = (const int32_t *)t->n_ord;
+    const orbhip_keypoint *kps = (const orbhip_keypoint *)t->kps;
+    const size_t R = (size_t)rows, RC = R * cap, P = (size_t)pcap;
+    for (int r = 0; r < rows; ++r) {
+        if (n[r] < 0 || n[r] > cap) { set_error("local_bundle_adjustment: bank row %d holds a count outside [0, cap]", r); return ORBHIP_E_ARG; }
+        if (n_ord[r] < 0 || n_ord[r] > rows) { set_error("local_bundle_adjustment: n_ord[%d] is outside [0, rows]", r); return ORBHIP_E_ARG; }
+    }
+    for (size_t i = 0; i < RC; ++i)
+        if (slot_point[i] < -1 || slot_point[i] >= np) { set_error("local_bundle_adjustment: bank row %zu holds a point index out of range", i / cap); return ORBHIP_E_ARG; }
+    for (int i = 0; i < n_ord[cur]; ++i)
+        if (ord_kf[(size_t)cur * rows + i] < 0 || ord_kf[(size_t)cur * rows + i] >= rows) { set_error("local_bundle_adjustment: covisible entry %d is outside the bank", i); return ORBHIP_E_ARG; }
+    if (obs_start[0] < 0) { set_error("local_bundle_adjustment: obs_start must start at 0 or above"); return ORBHIP_E_ARG; }
+    for (int p = 0; p < np; ++p)
+        if (obs_start[p + 1] < obs_start[p]) { set_error("local_bundle_adjustment: obs_start must be non-decreasing (entry %d)", p); return ORBHIP_E_ARG; }
+    const size_t total = (size_t)obs_start[np];
+    for (size_t o = (size_t)obs_start[0]; o < total; ++o) {
+        if (obs_kf[o] < 0 || obs_kf[o] >= rows || obs_idx[o] < 0 || obs_idx[o] >= cap) { set_error("local_bundle_adjustment: observation %zu is outside the bank", o); return ORBHIP_E_ARG; }
+        const int oct = kps[(size_t)obs_kf[o] * cap + obs_idx[o]].octave;
+        if (oct < 0 || oct >= cam->n_levels) { set_error("local_bundle_adjustment: observation %zu names a key point of octave %d", o, oct); return ORBHIP_E_ARG; }
+    }
+    if (!m) return ORBHIP_E_ARG;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const size_t MP = (size_t)max_points, ME = (size_t)max_edges;
+    Stage st;
+    int rc;
+    const size_t in_bytes = al256(RC * 4) + al256(R * 4) + al256(R) + al256(((size_t)np + 1) * 4) + 2 * al256(total * 4) + al256(P) +
+                            al256(RC * sizeof(orbhip_keypoint)) + al256(RC * 4) + al256(R * R * 4) + al256(R * 4) + 256;
+    const size_t out_size = al256(R * 48) + al256(P * 12) + 2 * al256(R * 4) + al256(MP * 4) + al256(ME * 12) + al256(64);
+    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
+    orbhip_lba_tables dt;
+    dt.slot_point = st.put(slot_point, RC); dt.n = st.put(n, R);
+    dt.kf_bad = t->kf_bad ? st.put((const uint8_t *)t->kf_bad, R) : nullptr;
+    dt.obs_start = st.put(obs_start, (size_t)np + 1); dt.obs_kf = st.put(obs_kf, total); dt.obs_idx = st.put(obs_idx, total);
+    dt.flags = st.put((const uint8_t *)t->flags, P); dt.kps = st.put(kps, RC);
+    dt.u_right = t->u_right ? st.put((const float *)t->u_right, RC) : nullptr;
+    dt.ord_kf = st.put(ord_kf, R * R); dt.n_ord = st.put(n_ord, R);
+    const uint8_t *d_stop = stop ? st.put(stop, 1) : nullptr;
+    const size_t out_off = st.off;
+    const float *d_Tcw = st.put((const float *)t->Tcw, R * 12);
+    const float *d_world = st.put((const float *)t->world, P * 3);
+    orbhip_lba_out dout;
+    const int32_t *d_lkf = st.put((const int32_t *)out->local_kf, R), *d_fkf = st.put((const int32_t *)out->fixed_kf, R);
+    const int32_t *d_lpt = st.put((const int32_t *)out->local_point, MP), *d_er = st.put((const int32_t *)out->erase, ME * 3);
+    const int32_t *d_rep = st.put((const int32_t *)out->report, 16);
+    const size_t out_bytes = st.off - out_off;
+    dt.Tcw = (void *)d_Tcw; dt.world = (void *)d_world;
+    dout.local_kf = (void *)d_lkf; dout.fixed_kf = (void *)d_fkf; dout.local_point = (void *)d_lpt; dout.erase = (void *)d_er;
+    dout.report = (void *)d_rep;
+    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = lba_launch(m, cur, id0_row, cam, rows, cap, np, pcap, &dt, inv_level_sigma2, max_points, max_edges, d_stop, &dout))) return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
+    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
+    back(t->Tcw, d_Tcw, R * 48); back(t->world, d_world, P * 12); back(out->local_kf, d_lkf, R * 4); back(out->fixed_kf, d_fkf, R * 4);
+    back(out->local_point, d_lpt, MP * 4); back(out->erase, d_er, ME * 12); back(out->report, d_rep, 64);
     return ORBHIP_OK;
 }
 

@@ -1015,6 +1015,60 @@ class ORBmatcher:
         return dict(matched12=m12[:Cn].copy(), S12=S12[:Cn].copy(), Scw=None if Scw is None else Scw[:Cn].copy(),
                     report=rep[:Cn].copy())
 
+    # -- local bundle adjustment (src/Optimizer.cc:453-778) ----------------------
+    LBA_TABLES = tuple(k for k, _ in capi.LbaTables._fields_)
+    LBA_OUT = tuple(k for k, _ in capi.LbaOut._fields_)
+    _LBA_DTYPES = dict(slot_point=np.int32, n=np.int32, kf_bad=np.uint8, obs_start=np.int32, obs_kf=np.int32, obs_idx=np.int32,
+                       flags=np.uint8, kps=capi.KP_DTYPE, u_right=np.float32, ord_kf=np.int32, n_ord=np.int32, Tcw=np.float32,
+                       world=np.float32)
+
+    def LocalBundleAdjustmentDevice(self, cur, id0_row, cam, rows, cap, np_, pcap, tables, inv_level_sigma2, max_points, max_edges,
+                                    out, d_stop=None):
+        """Optimizer::LocalBundleAdjustment for the key frame in row `cur` (orbhip_local_bundle_adjustment_device in
+        include/orbhip.h).  `tables` and `out` are dicts with the keys of LBA_TABLES / LBA_OUT holding device addresses (ints,
+        or tensors); kf_bad and u_right may be None; Tcw and world are updated in place.  d_stop: a device byte or None.
+        Asynchronous on the matcher's stream: a fixed sequence of small launches, no host synchronisation."""
+        sig = self._sigma2(inv_level_sigma2, cam)
+        rt, ro = self._record(capi.LbaTables, tables, optional=("kf_bad", "u_right")), self._record(capi.LbaOut, out)
+        dp = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a)  # noqa: E731
+        check(self._lib.orbhip_local_bundle_adjustment_device(self._h, int(cur), int(id0_row), C.byref(cam), int(rows), int(cap),
+                                                              int(np_), int(pcap), C.byref(rt), ptr(sig), int(max_points),
+                                                              int(max_edges), dp(d_stop), C.byref(ro)),
+              "orbhip_local_bundle_adjustment_device")
+
+    def LocalBundleAdjustment(self, tables, cur, id0_row, cam, inv_level_sigma2, max_points, max_edges, stop=None, fill=0):
+        """The same from host arrays in one staged copy, the call and one read-back (orbhip_local_bundle_adjustment),
+        range-checked (OrbHipError with E_ARG).  `tables`: dict with the keys of LBA_TABLES (slot_point [rows, cap], n [rows],
+        kf_bad [rows] or None, obs_start [np+1], obs_kf, obs_idx, flags [pcap], kps [rows, cap] KP_DTYPE, u_right [rows, cap]
+        or None, ord_kf [rows, rows], n_ord [rows], Tcw [rows, 12], world [pcap, 3]); stop: None or the value of the stop byte.
+        Returns dict(Tcw, world, local_kf [rows], fixed_kf [rows], local_point [max_points], erase [max_edges, 3], report [16]
+        in the order of capi.LBA_REPORT): copies, what the call does not write holds the input / `fill` bytes."""
+        T = {}
+        for k in self.LBA_TABLES:
+            if tables.get(k) is None:
+                if k in ("kf_bad", "u_right"):
+                    T[k] = None
+                    continue
+                raise ValueError("tables[%r] is missing" % k)
+            T[k] = np.array(tables[k], self._LBA_DTYPES[k], order="C") if k in ("Tcw", "world") else \
+                np.ascontiguousarray(tables[k], self._LBA_DTYPES[k])
+        rows, cap = T["slot_point"].shape
+        n_pts, pcap = len(T["obs_start"]) - 1, len(T["flags"])
+        T["Tcw"], T["world"] = T["Tcw"].reshape(rows, 12), T["world"].reshape(pcap, 3)
+        sig = self._sigma2(inv_level_sigma2, cam)
+        ints = lambda count: np.full(max(count, 1) * 4, fill, np.uint8).view(np.int32)  # noqa: E731
+        O = dict(local_kf=ints(rows), fixed_kf=ints(rows), local_point=ints(max_points), erase=ints(max_edges * 3), report=ints(16))
+        keep = {k: (None if a is None else (np.zeros(4, a.dtype) if a.size == 0 else a)) for k, a in T.items()}
+        rt = self._record(capi.LbaTables, {k: (None if a is None else ptr(a).value) for k, a in keep.items()}, optional=("kf_bad", "u_right"))
+        ro = self._record(capi.LbaOut, {k: ptr(a).value for k, a in O.items()})
+        sb = None if stop is None else np.array([stop], np.uint8)
+        check(self._lib.orbhip_local_bundle_adjustment(self._h, int(cur), int(id0_row), C.byref(cam), rows, cap, n_pts, pcap,
+                                                       C.byref(rt), ptr(sig), int(max_points), int(max_edges), ptr(sb), C.byref(ro)),
+              "orbhip_local_bundle_adjustment")
+        return dict(Tcw=keep["Tcw"].copy(), world=keep["world"].copy(), local_kf=O["local_kf"][:rows].copy(),
+                    fixed_kf=O["fixed_kf"][:rows].copy(), local_point=O["local_point"][:max_points].copy(),
+                    erase=O["erase"][:max_edges * 3].reshape(max_edges, 3).copy(), report=O["report"].copy())
+
     # -- device-resident, batched SearchByProjection ---------------------------
     def set_stream(self, stream):
         check(self._lib.orbhip_matcher_set_stream(self._h, stream), "orbhip_matcher_set_stream")
