@@ -1434,6 +1434,76 @@ int orbhip_local_bundle_adjustment(orbhip_matcher *m, int cur, int id0_row, cons
                                    int pcap, const orbhip_lba_tables *tables, const float *inv_level_sigma2, int max_points,
                                    int max_edges, const uint8_t *stop, const orbhip_lba_out *out);
 
+/* ---- essential-graph optimisation ----------------------------------------------------------------------------------------
+ * Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044, called at src/LoopClosing.cc:567), device resident: the
+ * step of CorrectLoop that moves the map.  One VertexSim3Expmap per bank row that is not bad, in row order (the row
+ * loop_row is fixed); EdgeSim3 with the identity as information in the reference's creation order: the loop connections
+ * (weight gate conn_w[i][j] < 100, the pair (cur, loop_row) exempt; they form sInsertedEdges), then per row the
+ * spanning-tree edge, the old loop edges to a smaller mnId, and the covisibility edges of weight >= 100 to a smaller mnId
+ * that are not the parent, a child, a loop-edge partner, bad or already inserted; g2o's numeric Jacobians through
+ * oplusImpl, Levenberg-Marquardt from setUserLambdaInit(1e-16) for 20 outer iterations of at most 10 trials, no robust
+ * kernel; the SE3 write-back (:991-1010) and the correction of every present point (:1012-1041).  The arithmetic,
+ * operation by operation, is tests/seqref/essgraph.py and DESIGN.md section 3: everything is fp64 with one rounding per
+ * operation; det_log64 / det_acos64 stand for std::log / acos, a stated 3x3 LU for W.lu().solve(t), and a dense unpivoted
+ * LDLt over 7 unknowns per free vertex in row order for LinearSolverEigen's sparse Cholesky.  Where the reference iterates a
+ * std::set or std::map of key frames the order is ascending bank row: loop_kf and lc_kf list each row's entries ascending.
+ *
+ * orbhip_eg_tables: kf_bad [rows] uint8 (nullable: none is bad; a bad row is not in the map and is skipped everywhere),
+ * kf_id [rows] int32 = mnId, parent [rows] int32 (-1: none), conn_w / ord_kf / ord_w [rows][rows], n_ord [rows] int32 of
+ * orbhip_covis_state (GetCovisiblesByWeight(100) is the prefix of ord_kf whose ord_w is at least 100 -- and, as
+ * src/KeyFrame.cc:191-193 has it, nothing when no entry of the row is below 100; hasChild(n) is parent[n] == r && !kf_bad[n]),
+ * loop_start [rows+1] / loop_kf int32 = mspLoopEdges, lc_start [rows+1] / lc_kf int32 = LoopConnections, corrected /
+ * non_corrected [rows][8] double = CorrectedSim3 / NonCorrectedSim3 in the S12 layout of orbhip_optimize_sim3 (quaternion x,
+ * y, z, w, t, s) with in_corrected / in_non_corrected [rows] uint8 saying which rows they hold, flags [pcap] uint8
+ * (ORBHIP_POINT_PRESENT = !isBad()), ref_kf [pcap] int32 = the row of GetReferenceKeyFrame(), corrected_by_kf /
+ * corrected_ref [pcap] int32 = mnCorrectedByKF / mnCorrectedReference as rows (-1: none); in/out: Tcw [rows][12] float,
+ * world [pcap][3] float.
+ * orbhip_eg_out: point_list [pcap] int32 = the present points in index order, the list orbhip_update_map_points_device
+ * takes (chain it with ORBHIP_UPDATE_NORMAL_DEPTH for :1042); Scw / Swc [rows][8] double = vScw / vCorrectedSwc of the rows
+ * that are not bad; report [16] int32 = {status, vertices, loop-connection edges, spanning-tree edges, old-loop edges,
+ * covisibility edges, edges skipped by the sInsertedEdges rule, by the weight gate, outer iterations, trials, unknowns,
+ * points listed, edges skipped because an end is a bad row (a null vertex in the reference), 0, 0, 0}.
+ * Every row that is not bad has its Tcw written as [R | t/s] in float, loop_row included; every present point whose
+ * reference row is in the map has its position written; a point whose reference row is bad or -1 keeps its position (the
+ * reference reads default-constructed Sim3s there) and is still listed.
+ * status: ORBHIP_EG_OK; ORBHIP_EG_CAPACITY (more than ORBHIP_EG_MAX_KF rows that are not bad, or more than max_edges edges:
+ * only the report is written, the caller falls back); ORBHIP_EG_SINGULAR (a pivot was <= 0 on every trial of the first
+ * iteration: the estimates are unchanged and the write-back still happens with them, as g2o does).
+ *
+ * This entry synchronises: the number of trials depends on the data, so the call reads the state record back once after
+ * the setup and once per trial (one small pinned copy, one stream synchronisation) and enqueues the next step from it; when
+ * it returns, the work is done.  The launches per trial depend on rows only.  The factorisation is blocked over panels of
+ * whole poses and runs from global memory; the workspace (about 100 MB at 512 key frames, plus 3 KB per edge) belongs to
+ * the handle.  rows <= 4096 (ORBHIP_E_CAPACITY beyond); rows < 1, pcap < 0, cur or loop_row outside [0, rows), max_edges <
+ * 1 or a null required pointer: ORBHIP_E_ARG; all refused before any device work.  The device form does not range-check
+ * the tables' contents; an edge whose other end is a bad row is skipped and counted. */
+#ifndef ORBHIP_EG_MAX_KF
+#define ORBHIP_EG_MAX_KF 512
+#endif
+#define ORBHIP_EG_OK       0
+#define ORBHIP_EG_CAPACITY 1
+#define ORBHIP_EG_SINGULAR 2
+typedef struct orbhip_eg_tables {
+    const void *kf_bad, *kf_id, *parent, *conn_w, *ord_kf, *ord_w, *n_ord, *loop_start, *loop_kf, *lc_start, *lc_kf, *corrected,
+        *non_corrected, *in_corrected, *in_non_corrected, *flags, *ref_kf, *corrected_by_kf, *corrected_ref;
+    void *Tcw, *world;
+} orbhip_eg_tables;
+typedef struct orbhip_eg_out {
+    void *point_list, *Scw, *Swc, *report;
+} orbhip_eg_out;
+int orbhip_optimize_essential_graph_device(orbhip_matcher *m, int cur, int loop_row, int rows, int pcap,
+                                           const orbhip_eg_tables *tables, int fix_scale, int max_edges, const orbhip_eg_out *out);
+/* Host buffers, synchronous: one staging copy, the call, one read-back; what the call does not write keeps the caller's
+ * values.  The same records with host pointers.  It range-checks what the device form does not: parent in [-1, rows), n_ord
+ * in [0, rows], the entries of ord_kf behind n_ord in [0, rows), loop_start / lc_start non-decreasing from 0, loop_kf /
+ * lc_kf in [0, rows) and ascending within a row, ref_kf / corrected_ref in [-1, rows); and it refuses the tables the
+ * reference would dereference a null vertex on: a row that is not bad whose parent, loop_kf entry or lc_kf entry is a bad
+ * row, and a bad row with lc_kf entries: ORBHIP_E_ARG, before the handle is looked at. */
+int orbhip_optimize_essential_graph(orbhip_matcher *m, int cur, int loop_row, int rows, int pcap, const orbhip_eg_tables *tables,
+                                    int fix_scale, int max_edges, const orbhip_eg_out *out);
+/* counters [2] = {stream synchronisations, kernel launches} of this handle's last essential-graph call. */
+int orbhip_optimize_essential_graph_counters(orbhip_matcher *m, int32_t counters[2]);
+
 /* ---- creating new map points -------------------------------------------------------------------------------------
  * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) for the current key frame and K neighbours in one call, up
  * to the point where the map graph is touched: `new MapPoint`, AddObservation and everything after :434 stay with the

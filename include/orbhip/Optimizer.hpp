@@ -1,6 +1,7 @@
-// C++ host-side mirror of ORB_SLAM2::Optimizer (include/Optimizer.h) above orbhip_pose_optimization, orbhip_optimize_sim3
-// and orbhip_local_bundle_adjustment of orbhip.h: the three functions of it the library has, PoseOptimization, OptimizeSim3
-// and LocalBundleAdjustment (whose key frames and map points are the tables of orbhip_lba_tables).  Header-only,
+// C++ host-side mirror of ORB_SLAM2::Optimizer (include/Optimizer.h) above orbhip_pose_optimization, orbhip_optimize_sim3,
+// orbhip_local_bundle_adjustment and orbhip_optimize_essential_graph of orbhip.h: the four functions of it the library has,
+// PoseOptimization, OptimizeSim3, LocalBundleAdjustment (whose key frames and map points are the tables of orbhip_lba_tables)
+// and OptimizeEssentialGraph (the tables of orbhip_eg_tables).  Header-only,
 // no OpenCV and no g2o: a frame is the arrays the reference's Frame holds (mvKeysUn, mvuRight, mvpMapPoints as indices
 // into the map arrays, mvbOutlier, mTcw); key frames and map points of OptimizeSim3 are the tables of orbhip_sim3_tables.
 #pragma once
@@ -30,6 +31,15 @@ struct Sim3 {
 // order, and the report of orbhip_local_bundle_adjustment_device.
 struct LocalBA {
     std::vector<int32_t> lLocalKeyFrames, lFixedCameras, lLocalMapPoints, vToErase;
+    int32_t report[16];
+};
+
+// What OptimizeEssentialGraph leaves besides the poses and points it writes into the tables: the present points in index
+// order (the list UpdateNormalAndDepth is then run over), vScw and vCorrectedSwc per bank row as Sim3 records (rows that are
+// bad keep Sim3{{0, 0, 0, 1}, {0, 0, 0}, 1}), and the report of orbhip_optimize_essential_graph_device.
+struct EssentialGraph {
+    std::vector<int32_t> vpCorrectedPoints;
+    std::vector<Sim3> vScw, vCorrectedSwc;
     int32_t report[16];
 };
 
@@ -158,6 +168,48 @@ public:
         check(orbhip_local_bundle_adjustment_device(matcher.handle(), cur, id0Row, &cam, rows, cap, np, pcap, &tables,
                                                     invLevelSigma2.data(), maxPoints, maxEdges, d_stop, &out),
               "orbhip_local_bundle_adjustment_device");
+    }
+
+    // void Optimizer::OptimizeEssentialGraph(Map *pMap, KeyFrame *pLoopKF, KeyFrame *pCurKF, const KeyFrameAndPose &NonCorrectedSim3,
+    // const KeyFrameAndPose &CorrectedSim3, const map<KeyFrame*, set<KeyFrame*>> &LoopConnections, const bool &bFixScale): the map
+    // is the tables (host pointers; Tcw and world are updated in place), pLoopKF / pCurKF are bank rows loopRow / cur, the two
+    // KeyFrameAndPose maps are tables.corrected / non_corrected with their marks, LoopConnections is tables.lc_start / lc_kf.
+    // UpdateNormalAndDepth of out.vpCorrectedPoints (:1042) stays with the caller.  Returns the status (ORBHIP_EG_*): on
+    // ORBHIP_EG_CAPACITY nothing but out.report is written and the lists are empty.
+    static int OptimizeEssentialGraph(ORBmatcher &matcher, int rows, int pcap, const orbhip_eg_tables &tables, int loopRow, int cur,
+                                      bool bFixScale, int maxEdges, EssentialGraph &out)
+    {
+        const size_t R = (size_t)(rows > 0 ? rows : 1), P = (size_t)(pcap > 0 ? pcap : 1);
+        std::vector<int32_t> pl(P, -1);
+        std::vector<double> scw(R * 8, 0.0), swc(R * 8, 0.0);
+        for (size_t r = 0; r < R; ++r) scw[r * 8 + 3] = scw[r * 8 + 7] = swc[r * 8 + 3] = swc[r * 8 + 7] = 1.0;
+        for (int i = 0; i < 16; ++i) out.report[i] = 0;
+        orbhip_eg_out o;
+        o.point_list = pl.data(); o.Scw = scw.data(); o.Swc = swc.data(); o.report = out.report;
+        check(orbhip_optimize_essential_graph(matcher.handle(), cur, loopRow, rows, pcap, &tables, bFixScale ? 1 : 0, maxEdges, &o),
+              "orbhip_optimize_essential_graph");
+        const bool wrote = out.report[0] != ORBHIP_EG_CAPACITY;
+        out.vpCorrectedPoints.assign(pl.begin(), pl.begin() + (wrote ? out.report[11] : 0));
+        out.vScw.assign((size_t)(rows > 0 ? rows : 0), Sim3());
+        out.vCorrectedSwc = out.vScw;
+        for (size_t r = 0; r < out.vScw.size(); ++r)
+            for (int k = 0; k < 2; ++k) {
+                const double *src = (k ? swc.data() : scw.data()) + r * 8;
+                Sim3 &dst = k ? out.vCorrectedSwc[r] : out.vScw[r];
+                for (int i = 0; i < 4; ++i) dst.r[i] = src[i];
+                for (int i = 0; i < 3; ++i) dst.t[i] = src[4 + i];
+                dst.s = src[7];
+            }
+        return out.report[0];
+    }
+
+    // The same over device arrays: the arguments of orbhip_optimize_essential_graph_device, which see.  The call synchronises the
+    // matcher's stream once per Levenberg-Marquardt trial.
+    static void OptimizeEssentialGraphDevice(ORBmatcher &matcher, int cur, int loopRow, int rows, int pcap, const orbhip_eg_tables &tables,
+                                             bool bFixScale, int maxEdges, const orbhip_eg_out &out)
+    {
+        check(orbhip_optimize_essential_graph_device(matcher.handle(), cur, loopRow, rows, pcap, &tables, bFixScale ? 1 : 0, maxEdges,
+                                                     &out), "orbhip_optimize_essential_graph_device");
     }
 };
 

@@ -102,6 +102,18 @@ class LbaOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("local_kf", "fixed_kf", "local_point", "erase", "report")]
 
 
+class EgTables(C.Structure):
+    """orbhip_eg_tables: what orbhip_optimize_essential_graph* reads; Tcw and world are in/out."""
+    _fields_ = [(k, C.c_void_p) for k in ("kf_bad", "kf_id", "parent", "conn_w", "ord_kf", "ord_w", "n_ord", "loop_start", "loop_kf",
+                                          "lc_start", "lc_kf", "corrected", "non_corrected", "in_corrected", "in_non_corrected", "flags",
+                                          "ref_kf", "corrected_by_kf", "corrected_ref", "Tcw", "world")]
+
+
+class EgOut(C.Structure):
+    """orbhip_eg_out: the point list, vScw, vCorrectedSwc and the report of orbhip_optimize_essential_graph*."""
+    _fields_ = [(k, C.c_void_p) for k in ("point_list", "Scw", "Swc", "report")]
+
+
 class PnpParams(C.Structure):
     """orbhip_pnp_params: the arguments of PnPsolver::SetRansacParameters."""
     _fields_ = [("prob", C.c_double), ("min_inliers", C.c_int32), ("max_its", C.c_int32), ("min_set", C.c_int32),
@@ -161,6 +173,11 @@ LBA_OK, LBA_STOPPED, LBA_ONE_ROUND, LBA_CAPACITY = range(4)
 LBA_MAX_LOCAL = 128
 LBA_REPORT = ("status", "n_local_kf", "n_fixed_kf", "n_local_points", "n_mono", "n_stereo", "n_level1", "n_erase", "iterations_1",
               "trials_1", "iterations_2", "trials_2", "poses_1", "poses_2", "reserved_0", "stop_samples")
+# ORBHIP_EG_*: report[0] of orbhip_optimize_essential_graph_device
+EG_OK, EG_CAPACITY, EG_SINGULAR = range(3)
+EG_MAX_KF = 512
+EG_REPORT = ("status", "n_vertices", "n_loop_connection", "n_spanning_tree", "n_old_loop", "n_covisibility", "skipped_inserted",
+             "skipped_weight", "iterations", "trials", "unknowns", "n_points", "skipped_null", "reserved_0", "reserved_1", "reserved_2")
 REMAP_TABLE_SIZE = 4096
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
@@ -312,6 +329,9 @@ SYMBOLS = [
                                                    _vp, C.POINTER(LbaOut)]),
     ("orbhip_local_bundle_adjustment", _i, [_vp, _i, _i, C.POINTER(Camera), _i, _i, _i, _i, C.POINTER(LbaTables), _vp, _i, _i, _vp,
                                             C.POINTER(LbaOut)]),
+    ("orbhip_optimize_essential_graph_device", _i, [_vp, _i, _i, _i, _i, C.POINTER(EgTables), _i, _i, C.POINTER(EgOut)]),
+    ("orbhip_optimize_essential_graph", _i, [_vp, _i, _i, _i, _i, C.POINTER(EgTables), _i, _i, C.POINTER(EgOut)]),
+    ("orbhip_optimize_essential_graph_counters", _i, [_vp, _vp]),
     ("orbhip_matcher_set_stream", _i, [_vp, _vp]),
     ("orbhip_matcher_sync", _i, [_vp]),
     ("orbhip_compute_stereo_matches_device", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,

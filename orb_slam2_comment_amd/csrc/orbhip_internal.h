@@ -302,6 +302,16 @@ size_t lba_workspace_bytes(LbaWs W);
 int launch_local_bundle_adjustment(hipStream_t stream, LbaWs W, void *workspace);
 }  // namespace orbhip
 
+#include "orbhip_essgraph_core.h"
+
+namespace orbhip {
+// orbhip_essgraph.hip: the tables, the outputs and the scalars travel in EgWs; the workspace pointers are carved by the launch.
+// h_state is pinned host memory the call reads the state record into once per trial; counters [2] (nullable) receives the
+// synchronisations and the launches of the call.
+size_t eg_workspace_bytes(EgWs W);
+int launch_optimize_essential_graph(hipStream_t stream, EgWs W, void *workspace, EgState *h_state, int *counters);
+}  // namespace orbhip
+
 struct orbhip_extractor {
     int nfeatures = 0;
     double scaleFactor = 1.2;

@@ -3715,8 +3715,8 @@ struct orbhip_matcher {
     hipStream_t stream = nullptr;       // stream every launch goes to
     hipStream_t own_stream = nullptr;   // created with the handle
     // grow-only device scratch
-    void *buf[27] = {};
-    size_t cap[27] = {};
+    void *buf[28] = {};
+    size_t cap[28] = {};
     bool lds_attr_set = false, bow_attr_set = false;
 #ifdef ORBHIP_DEVTOOLS
     int window_lanes = 0;               // development build: lanes per query of k_window_search forced to 16 / 64 (0: the rule)
@@ -3725,6 +3725,8 @@ struct orbhip_matcher {
     // pinned host staging: all inputs of a call travel in one DMA, all outputs in one
     uint8_t *h_stage = nullptr; size_t h_stage_bytes = 0;
     uint8_t *h_out = nullptr; size_t h_out_bytes = 0;
+    void *h_eg = nullptr;               // pinned: the state record of the essential-graph optimisation, read once per trial
+    int eg_counters[2] = {0, 0};        // synchronisations and launches of the last essential-graph call
     // Sim3 RANSAC: the iteration limit per correspondence count, [sim3_cap + 1], rebuilt when a parameter changes
     std::vector<int> sim3_limit;
     double sim3_prob = 0.0;
@@ -3813,7 +3815,7 @@ static SigmaTab sigma_tab(const float *inv_level_sigma2, int n_levels)
     return sig;
 }
 
-enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_COVIS, S_CULL, S_SIM3, S_SIM3LIM, S_SIM3SOLV, S_PNP, S_PNPTAB, S_PNPSOLV, S_LBA, S_NSLOTS };
+enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_COVIS, S_CULL, S_SIM3, S_SIM3LIM, S_SIM3SOLV, S_PNP, S_PNPTAB, S_PNPSOLV, S_LBA, S_EG, S_NSLOTS };
 static_assert(S_NSLOTS == sizeof(orbhip_matcher::buf) / sizeof(void *), "one scratch buffer per slot");
 
 static int stage_begin(orbhip_matcher *m, size_t total, Stage *st)
@@ -4271,6 +4273,7 @@ void orbhip_matcher_destroy(orbhip_matcher *m)
     for (int i = 0; i < S_NSLOTS; ++i) (void)hipFree(m->buf[i]);
     if (m->h_stage) (void)hipHostFree(m->h_stage);
     if (m->h_out) (void)hipHostFree(m->h_out);
+    if (m->h_eg) (void)hipHostFree(m->h_eg);
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
     delete m;
 }
@@ -6662,6 +6665,131 @@ int orbhip_local_bundle_adjustment(orbhip_matcher *m, int cur, int id0_row, cons
     auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
     back(t->Tcw, d_Tcw, R * 48); back(t->world, d_world, P * 12); back(out->local_kf, d_lkf, R * 4); back(out->fixed_kf, d_fkf, R * 4);
     back(out->local_point, d_lpt, MP * 4); back(out->erase, d_er, ME * 12); back(out->report, d_rep, 64);
+    return ORBHIP_OK;
+}
+
+// ---- essential-graph optimisation (kernels: orbhip_essgraph.hip) -------------------------------------------------------------
+static int eg_args(int cur, int loop_row, int rows, int pcap, const orbhip_eg_tables *t, int max_edges, const orbhip_eg_out *out)
+{
+    if (rows < 1 || pcap < 0 || cur < 0 || cur >= rows || loop_row < 0 || loop_row >= rows || max_edges < 1) return ORBHIP_E_ARG;
+    if (!t || !t->kf_id || !t->parent || !t->conn_w || !t->ord_kf || !t->ord_w || !t->n_ord || !t->loop_start || !t->loop_kf ||
+        !t->lc_start || !t->lc_kf || !t->corrected || !t->non_corrected || !t->in_corrected || !t->in_non_corrected || !t->Tcw ||
+        (pcap > 0 && (!t->flags || !t->ref_kf || !t->corrected_by_kf || !t->corrected_ref || !t->world)) || !out ||
+        (pcap > 0 && !out->point_list) || !out->Scw || !out->Swc || !out->report)
+        return ORBHIP_E_ARG;
+    if (rows > 4096) { set_error("optimize_essential_graph: rows %d exceeds 4096", rows); return ORBHIP_E_CAPACITY; }
+    return ORBHIP_OK;
+}
+
+static int eg_launch(orbhip_matcher *m, int cur, int loop_row, int rows, int pcap, const orbhip_eg_tables *t, int fix_scale, int max_edges,
+                     const orbhip_eg_out *out)
+{
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    EgWs W;
+    memset(&W, 0, sizeof(W));
+    W.kf_bad = (const uint8_t *)t->kf_bad; W.kf_id = (const int *)t->kf_id; W.parent = (const int *)t->parent;
+    W.conn_w = (const int *)t->conn_w; W.ord_kf = (const int *)t->ord_kf; W.ord_w = (const int *)t->ord_w; W.n_ord = (const int *)t->n_ord;
+    W.loop_start = (const int *)t->loop_start; W.loop_kf = (const int *)t->loop_kf; W.lc_start = (const int *)t->lc_start;
+    W.lc_kf = (const int *)t->lc_kf; W.corrected = (const double *)t->corrected; W.non_corrected = (const double *)t->non_corrected;
+    W.in_c = (const uint8_t *)t->in_corrected; W.in_nc = (const uint8_t *)t->in_non_corrected; W.flags = (const uint8_t *)t->flags;
+    W.ref_kf = (const int *)t->ref_kf; W.cby = (const int *)t->corrected_by_kf; W.cref = (const int *)t->corrected_ref;
+    W.Tcw = (float *)t->Tcw; W.world = (float *)t->world;
+    W.o_point_list = (int *)out->point_list; W.o_Scw = (double *)out->Scw; W.o_Swc = (double *)out->Swc; W.o_report = (int *)out->report;
+    W.rows = rows; W.pcap = pcap; W.cur = cur; W.loop_row = loop_row; W.fix_scale = fix_scale ? 1 : 0; W.max_edges = max_edges;
+    void *ws;
+    if (int rc = scratch(m, S_EG, eg_workspace_bytes(W), &ws)) return rc;
+    if (!m->h_eg) ORBHIP_HIP_CHECK(hipHostMalloc(&m->h_eg, sizeof(EgState), hipHostMallocDefault));
+    return launch_optimize_essential_graph(m->stream, W, ws, (EgState *)m->h_eg, m->eg_counters);
+}
+
+int orbhip_optimize_essential_graph_device(orbhip_matcher *m, int cur, int loop_row, int rows, int pcap, const orbhip_eg_tables *tables,
+                                           int fix_scale, int max_edges, const orbhip_eg_out *out)
+{
+    if (int rc = eg_args(cur, loop_row, rows, pcap, tables, max_edges, out)) return rc;
+    if (!m) return ORBHIP_E_ARG;
+    return eg_launch(m, cur, loop_row, rows, pcap, tables, fix_scale, max_edges, out);
+}
+
+int orbhip_optimize_essential_graph(orbhip_matcher *m, int cur, int loop_row, int rows, int pcap, const orbhip_eg_tables *t,
+                                    int fix_scale, int max_edges, const orbhip_eg_out *out)
+{
+    if (int rc = eg_args(cur, loop_row, rows, pcap, t, max_edges, out)) return rc;
+    const uint8_t *kf_bad = (const uint8_t *)t->kf_bad;
+    const int32_t *parent = (const int32_t *)t->parent, *ord_kf = (const int32_t *)t->ord_kf, *n_ord = (const int32_t *)t->n_ord;
+    const int32_t *starts[2] = {(const int32_t *)t->loop_start, (const int32_t *)t->lc_start};
+    const int32_t *lists[2] = {(const int32_t *)t->loop_kf, (const int32_t *)t->lc_kf};
+    const int32_t *ref_kf = (const int32_t *)t->ref_kf, *cref = (const int32_t *)t->corrected_ref;
+    const char *names[2] = {"loop_kf", "lc_kf"};
+    auto bad = [&](int r) { return kf_bad && kf_bad[r]; };
+    for (int r = 0; r < rows; ++r) {
+        if (parent[r] < -1 || parent[r] >= rows) { set_error("optimize_essential_graph: parent[%d] is outside [-1, rows)", r); return ORBHIP_E_ARG; }
+        if (n_ord[r] < 0 || n_ord[r] > rows) { set_error("optimize_essential_graph: n_ord[%d] is outside [0, rows]", r); return ORBHIP_E_ARG; }
+        for (int i = 0; i < n_ord[r]; ++i)
+            if (ord_kf[(size_t)r * rows + i] < 0 || ord_kf[(size_t)r * rows + i] >= rows) { set_error("optimize_essential_graph: covisible entry %d of row %d is outside the bank", i, r); return ORBHIP_E_ARG; }
+        if (!bad(r) && parent[r] >= 0 && bad(parent[r])) { set_error("optimize_essential_graph: the parent of row %d is a bad row", r); return ORBHIP_E_ARG; }
+    }
+    for (int k = 0; k < 2; ++k) {
+        if (starts[k][0] != 0) { set_error("optimize_essential_graph: %s's start table must begin at 0", names[k]); return ORBHIP_E_ARG; }
+        for (int r = 0; r < rows; ++r) {
+            if (starts[k][r + 1] < starts[k][r]) { set_error("optimize_essential_graph: %s's start table must be non-decreasing (row %d)", names[k], r); return ORBHIP_E_ARG; }
+            for (int o = starts[k][r]; o < starts[k][r + 1]; ++o) {
+                const int j = lists[k][o];
+                if (j < 0 || j >= rows || (o > starts[k][r] && j <= lists[k][o - 1])) { set_error("optimize_essential_graph: %s of row %d must hold ascending rows of the bank", names[k], r); return ORBHIP_E_ARG; }
+                if ((k == 1 || !bad(r)) && (bad(j) || bad(r))) { set_error("optimize_essential_graph: %s of row %d joins a bad row (a null vertex)", names[k], r); return ORBHIP_E_ARG; }
+            }
+        }
+    }
+    for (int p = 0; p < pcap; ++p)
+        if (ref_kf[p] < -1 || ref_kf[p] >= rows || cref[p] < -1 || cref[p] >= rows) { set_error("optimize_essential_graph: point %d names a reference row outside [-1, rows)", p); return ORBHIP_E_ARG; }
+    if (!m) return ORBHIP_E_ARG;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const size_t R = (size_t)rows, P = (size_t)pcap, NL = (size_t)starts[0][rows], NC = (size_t)starts[1][rows];
+    Stage st;
+    int rc;
+    const size_t in_bytes = 4 * al256(R) + 3 * al256(R * 4) + 3 * al256(R * R * 4) + 2 * al256((R + 1) * 4) + al256((NL + 1) * 4) + al256((NC + 1) * 4) +
+                            2 * al256(R * 64) + al256(P + 1) + 3 * al256((P + 1) * 4) + 256;
+    const size_t out_size = al256(R * 48) + al256((P + 1) * 12) + al256((P + 1) * 4) + 2 * al256(R * 64) + al256(64);
+    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
+    const int32_t zero = 0;
+    orbhip_eg_tables dt;
+    dt.kf_bad = kf_bad ? st.put(kf_bad, R) : nullptr;
+    dt.kf_id = st.put((const int32_t *)t->kf_id, R); dt.parent = st.put(parent, R);
+    dt.conn_w = st.put((const int32_t *)t->conn_w, R * R); dt.ord_kf = st.put(ord_kf, R * R); dt.ord_w = st.put((const int32_t *)t->ord_w, R * R);
+    dt.n_ord = st.put(n_ord, R);
+    dt.loop_start = st.put(starts[0], R + 1); dt.loop_kf = NL ? st.put(lists[0], NL) : st.put(&zero, 1);
+    dt.lc_start = st.put(starts[1], R + 1); dt.lc_kf = NC ? st.put(lists[1], NC) : st.put(&zero, 1);
+    dt.corrected = st.put((const double *)t->corrected, R * 8); dt.non_corrected = st.put((const double *)t->non_corrected, R * 8);
+    dt.in_corrected = st.put((const uint8_t *)t->in_corrected, R); dt.in_non_corrected = st.put((const uint8_t *)t->in_non_corrected, R);
+    const uint8_t zb = 0;
+    dt.flags = P ? st.put((const uint8_t *)t->flags, P) : st.put(&zb, 1);
+    dt.ref_kf = P ? st.put(ref_kf, P) : st.put(&zero, 1);
+    dt.corrected_by_kf = P ? st.put((const int32_t *)t->corrected_by_kf, P) : st.put(&zero, 1);
+    dt.corrected_ref = P ? st.put(cref, P) : st.put(&zero, 1);
+    const size_t out_off = st.off;
+    const float fz[3] = {0.f, 0.f, 0.f};
+    const float *d_Tcw = st.put((const float *)t->Tcw, R * 12);
+    const float *d_world = P ? st.put((const float *)t->world, P * 3) : st.put(fz, 3);
+    const int32_t *d_pl = P ? st.put((const int32_t *)out->point_list, P) : st.put(&zero, 1);
+    const double *d_Scw = st.put((const double *)out->Scw, R * 8), *d_Swc = st.put((const double *)out->Swc, R * 8);
+    const int32_t *d_rep = st.put((const int32_t *)out->report, 16);
+    const size_t out_bytes = st.off - out_off;
+    dt.Tcw = (void *)d_Tcw; dt.world = (void *)d_world;
+    orbhip_eg_out dout;
+    dout.point_list = (void *)d_pl; dout.Scw = (void *)d_Scw; dout.Swc = (void *)d_Swc; dout.report = (void *)d_rep;
+    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = eg_launch(m, cur, loop_row, rows, pcap, &dt, fix_scale, max_edges, &dout))) return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
+    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
+    back(t->Tcw, d_Tcw, R * 48); back(out->Scw, d_Scw, R * 64); back(out->Swc, d_Swc, R * 64); back(out->report, d_rep, 64);
+    if (P) { back(t->world, d_world, P * 12); back(out->point_list, d_pl, P * 4); }
+    return ORBHIP_OK;
+}
+
+int orbhip_optimize_essential_graph_counters(orbhip_matcher *m, int32_t counters[2])
+{
+    if (!m || !counters) return ORBHIP_E_ARG;
+    counters[0] = m->eg_counters[0]; counters[1] = m->eg_counters[1];
     return ORBHIP_OK;
 }
 

@@ -1069,6 +1069,64 @@ class ORBmatcher:
                     fixed_kf=O["fixed_kf"][:rows].copy(), local_point=O["local_point"][:max_points].copy(),
                     erase=O["erase"][:max_edges * 3].reshape(max_edges, 3).copy(), report=O["report"].copy())
 
+    # -- essential-graph optimisation (src/Optimizer.cc:781-1044) -----------------
+    EG_TABLES = tuple(k for k, _ in capi.EgTables._fields_)
+    EG_OUT = tuple(k for k, _ in capi.EgOut._fields_)
+    _EG_DTYPES = dict(kf_bad=np.uint8, kf_id=np.int32, parent=np.int32, conn_w=np.int32, ord_kf=np.int32, ord_w=np.int32, n_ord=np.int32,
+                      loop_start=np.int32, loop_kf=np.int32, lc_start=np.int32, lc_kf=np.int32, corrected=np.float64,
+                      non_corrected=np.float64, in_corrected=np.uint8, in_non_corrected=np.uint8, flags=np.uint8, ref_kf=np.int32,
+                      corrected_by_kf=np.int32, corrected_ref=np.int32, Tcw=np.float32, world=np.float32)
+    _EG_POINT_KEYS = ("flags", "ref_kf", "corrected_by_kf", "corrected_ref", "world")
+
+    def OptimizeEssentialGraphDevice(self, cur, loop_row, rows, pcap, tables, fix_scale, max_edges, out):
+        """Optimizer::OptimizeEssentialGraph between the key frames in rows `cur` and `loop_row`
+        (orbhip_optimize_essential_graph_device in include/orbhip.h).  `tables` and `out` are dicts with the keys of EG_TABLES /
+        EG_OUT holding device addresses (ints, or tensors); kf_bad may be None, and with pcap == 0 so may the point arrays; Tcw
+        and world are updated in place.  The call synchronises the matcher's stream once per Levenberg-Marquardt trial; when it
+        returns the outputs are written."""
+        optional = ("kf_bad",) + (self._EG_POINT_KEYS if pcap == 0 else ())
+        rt = self._record(capi.EgTables, tables, optional=optional)
+        ro = self._record(capi.EgOut, out, optional=("point_list",) if pcap == 0 else ())
+        check(self._lib.orbhip_optimize_essential_graph_device(self._h, int(cur), int(loop_row), int(rows), int(pcap), C.byref(rt),
+                                                               int(bool(fix_scale)), int(max_edges), C.byref(ro)),
+              "orbhip_optimize_essential_graph_device")
+
+    def OptimizeEssentialGraph(self, tables, cur, loop_row, fix_scale, max_edges, fill=0):
+        """The same from host arrays in one staged copy, the call and one read-back (orbhip_optimize_essential_graph), range-checked
+        (OrbHipError with E_ARG; also for a parent, loop_kf entry or lc_kf entry that is a bad row).  `tables`: dict with the keys
+        of EG_TABLES (kf_bad [rows] or None, kf_id, parent, n_ord [rows], conn_w, ord_kf, ord_w [rows, rows], loop_start / lc_start
+        [rows + 1], loop_kf, lc_kf, corrected / non_corrected [rows, 8] float64, in_corrected / in_non_corrected [rows], flags,
+        ref_kf, corrected_by_kf, corrected_ref [pcap], Tcw [rows, 12], world [pcap, 3]).  Returns dict(Tcw, world, point_list
+        [pcap], Scw [rows, 8], Swc [rows, 8], report [16] in the order of capi.EG_REPORT): copies, what the call does not write
+        holds the input / `fill` bytes."""
+        T = {}
+        for k in self.EG_TABLES:
+            if tables.get(k) is None:
+                if k == "kf_bad":
+                    T[k] = None
+                    continue
+                raise ValueError("tables[%r] is missing" % k)
+            T[k] = np.array(tables[k], self._EG_DTYPES[k], order="C") if k in ("Tcw", "world") else \
+                np.ascontiguousarray(tables[k], self._EG_DTYPES[k])
+        rows, pcap = len(T["kf_id"]), len(T["flags"])
+        T["Tcw"], T["world"] = T["Tcw"].reshape(rows, 12), T["world"].reshape(pcap, 3)
+        raw = lambda count, dt: np.full(max(count, 1) * np.dtype(dt).itemsize, fill, np.uint8).view(dt)  # noqa: E731
+        O = dict(point_list=raw(pcap, np.int32), Scw=raw(rows * 8, np.float64), Swc=raw(rows * 8, np.float64), report=raw(16, np.int32))
+        keep = {k: (None if a is None else (np.zeros(4, a.dtype) if a.size == 0 else a)) for k, a in T.items()}
+        rt = self._record(capi.EgTables, {k: (None if a is None else ptr(a).value) for k, a in keep.items()}, optional=("kf_bad",))
+        ro = self._record(capi.EgOut, {k: ptr(a).value for k, a in O.items()})
+        check(self._lib.orbhip_optimize_essential_graph(self._h, int(cur), int(loop_row), rows, pcap, C.byref(rt), int(bool(fix_scale)),
+                                                        int(max_edges), C.byref(ro)), "orbhip_optimize_essential_graph")
+        return dict(Tcw=T["Tcw"].copy(), world=T["world"].copy(), point_list=O["point_list"][:pcap].copy(),
+                    Scw=O["Scw"][:rows * 8].reshape(rows, 8).copy(), Swc=O["Swc"][:rows * 8].reshape(rows, 8).copy(),
+                    report=O["report"].copy())
+
+    def EssentialGraphCounters(self):
+        """(stream synchronisations, kernel launches) of this matcher's last OptimizeEssentialGraph* call."""
+        c = np.zeros(2, np.int32)
+        check(self._lib.orbhip_optimize_essential_graph_counters(self._h, ptr(c)), "orbhip_optimize_essential_graph_counters")
+        return int(c[0]), int(c[1])
+
     # -- device-resident, batched SearchByProjection ---------------------------
     def set_stream(self, stream):
         check(self._lib.orbhip_matcher_set_stream(self._h, stream), "orbhip_matcher_set_stream")
