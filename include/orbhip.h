@@ -1504,6 +1504,105 @@ int orbhip_optimize_essential_graph(orbhip_matcher *m, int cur, int loop_row, in
 /* counters [2] = {stream synchronisations, kernel launches} of this handle's last essential-graph call. */
 int orbhip_optimize_essential_graph_counters(orbhip_matcher *m, int32_t counters[2]);
 
+/* ---- global bundle adjustment ---------------------------------------------------------------------------------------------
+ * Optimizer::BundleAdjustment (src/Optimizer.cc:49-237; GlobalBundleAdjustemnt :41-46 is the call with null lists), device
+ * resident: the end of a loop closure (LoopClosing::RunGlobalBundleAdjustment, src/LoopClosing.cc:645-749) and of monocular
+ * initialisation (Tracking::CreateInitialMapMonocular).  One SE3 vertex per listed key frame that is not bad (:71-83; the rows
+ * whose kf_id is 0 are fixed, maxKFid is the largest kf_id among the vertices), one point vertex per listed point that is
+ * PRESENT, one EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ per observation in table order whose row is not bad and has kf_id
+ * <= maxKFid (:109), monocular iff u_right < 0, information mvInvLevelSigma2[octave]; a point without an edge is removed
+ * (:175-179) and neither written nor marked; one optimize(iterations) of g2o's Levenberg-Marquardt over BlockSolver_6_3, at most
+ * 10 trials per iteration, with Huber kernels of (float)sqrt(5.99) and (float)sqrt(7.815) when robust, none otherwise; no
+ * level-1 rule, no chi2 check, no erase list; the write-back (:193-235).  The arithmetic, operation by operation, is
+ * tests/seqref/gba.py and DESIGN.md section 3: the edges, the blocks, the Schur complement, the state machine and every sum
+ * order are those of the local bundle adjustment; the free poses of the reduced system are the vertices in list order with
+ * the fixed rows left out; its unpivoted LDLt is blocked (the kernels the essential-graph optimisation uses) and equals the
+ * sequential one bit for bit.
+ *
+ * orbhip_gba_tables: kf_bad [rows] uint8 (nullable: none is bad), kf_id [rows] int32 = mnId, obs_start [np+1], obs_kf, obs_idx
+ * int32, flags [pcap] uint8, kps [rows][cap], u_right [rows][cap] float (nullable: every observation is monocular) as in
+ * orbhip_lba_tables; in/out: Tcw [rows][12] float, world [pcap][3] float.
+ * d_kf_list [nkf] / d_pt_list [npt] int32 = vpKFs / vpMP, each nullable: every row / every point index below np in ascending
+ * order (nkf / npt are ignored then).  A list entry outside the tables is skipped.  iterations >= 1.
+ * mode ORBHIP_GBA_IN_PLACE (nLoopKF == 0): Tcw and world are written, and out->point_list [max_points] int32 receives the
+ * written points in list order: the list orbhip_update_map_points_device takes (chain it with ORBHIP_UPDATE_NORMAL_DEPTH for
+ * :227).  mode ORBHIP_GBA_STAGED (nLoopKF != 0): out->TcwGBA [rows][12] and out->posGBA [pcap][3] float are written and
+ * out->kf_mark [rows] / out->pt_mark [pcap] uint8 are set to 1 for exactly the entries written (mnBAGlobalForKF == nLoopKF; the
+ * caller clears the marks beforehand); Tcw and world are untouched.  The arrays of the other mode may be null.
+ * Every vertex is written back as toCvMat(SE3Quat), the fixed rows too, and every included point as float -- also when the stop
+ * byte was set on entry: ORBHIP_GBA_STOPPED, zero iterations, the poses are the inputs after the quaternion round trip.  When
+ * no listed row has kf_id 0 nothing is fixed and the system stands on the damping alone, as in g2o.
+ * An observation whose row is in the map and old enough but is not listed is a null vertex in the reference: the device form
+ * skips it (it is no edge of its point) and counts it; the host form refuses such tables.
+ * out->report [16] int32 = {status, key-frame vertices, free poses, included points, points removed for lack of edges, monocular
+ * edges, stereo edges, observations skipped by the bad / maxKFid rule, null-vertex skips, outer iterations, trials, unknowns of
+ * the reduced system, points listed for UpdateNormalAndDepth, 0, 0, samples of the stop byte}.
+ * status: ORBHIP_GBA_OK; ORBHIP_GBA_STOPPED; ORBHIP_GBA_CAPACITY (more than ORBHIP_GBA_MAX_KF vertices, more than max_points
+ * included points or max_edges edges: only the report is written, the caller falls back).
+ * d_stop: nullable device byte = *pbStopFlag, sampled where g2o samples terminate(): at the top of every outer iteration and
+ * in the condition of the trial loop after a rejected trial.  Only "set before the call" and "null" are deterministic.
+ *
+ * This entry synchronises: the call reads the state record back once after the setup and once per trial (one small pinned
+ * copy, one stream synchronisation) and enqueues the next step from it; when it returns, the work is done.  One stream, no
+ * cooperative launch.  The workspace belongs to the handle and is sized from rows, pcap, max_points and max_edges (the reduced
+ * system takes 75 MB at 512 key frames).  rows, cap <= 4096 (ORBHIP_E_CAPACITY beyond); negative counts, cap < 1, np > pcap, a
+ * list longer than its table, iterations < 1, a bad mode, max_points or max_edges < 1, cam->n_levels outside [1,
+ * ORBHIP_MAX_LEVELS] or a null required pointer: ORBHIP_E_ARG; all refused before any device work.  The device form does not
+ * range-check the tables' contents.  The entries read no environment variable. */
+#define ORBHIP_GBA_MAX_KF   512
+#define ORBHIP_GBA_IN_PLACE 0
+#define ORBHIP_GBA_STAGED   1
+#define ORBHIP_GBA_OK       0
+#define ORBHIP_GBA_STOPPED  1
+#define ORBHIP_GBA_CAPACITY 2
+typedef struct orbhip_gba_tables {
+    const void *kf_bad, *kf_id, *obs_start, *obs_kf, *obs_idx, *flags, *kps, *u_right;
+    void *Tcw, *world;
+} orbhip_gba_tables;
+typedef struct orbhip_gba_out {
+    void *TcwGBA, *posGBA, *kf_mark, *pt_mark, *point_list, *report;
+} orbhip_gba_out;
+int orbhip_global_bundle_adjustment_device(orbhip_matcher *m, const orbhip_camera *cam, int rows, int cap, int np, int pcap,
+                                           const orbhip_gba_tables *tables, const float *inv_level_sigma2, const void *d_kf_list,
+                                           int nkf, const void *d_pt_list, int npt, int iterations, int robust, int mode,
+                                           int max_points, int max_edges, const void *d_stop, const orbhip_gba_out *out);
+/* Host buffers, synchronous: one staging copy, the call, one read-back; what the call does not write keeps the caller's
+ * values.  The same records with host pointers; stop points to a host byte or is NULL.  It range-checks what the device form
+ * does not: list entries in [0, rows) / [0, np) and no row listed twice, obs_start non-decreasing from 0 or above, obs_kf in
+ * [0, rows), obs_idx in [0, cap), the octaves of observed key points in [0, cam->n_levels), and it refuses a null vertex:
+ * ORBHIP_E_ARG, before the handle is looked at. */
+int orbhip_global_bundle_adjustment(orbhip_matcher *m, const orbhip_camera *cam, int rows, int cap, int np, int pcap,
+                                    const orbhip_gba_tables *tables, const float *inv_level_sigma2, const int32_t *kf_list, int nkf,
+                                    const int32_t *pt_list, int npt, int iterations, int robust, int mode, int max_points,
+                                    int max_edges, const uint8_t *stop, const orbhip_gba_out *out);
+/* counters [2] = {stream synchronisations, kernel launches} of this handle's last global-bundle-adjustment call. */
+int orbhip_global_bundle_adjustment_counters(orbhip_matcher *m, int32_t counters[2]);
+
+/* The map update after a staged global bundle adjustment (src/LoopClosing.cc:676-737).  d_origins [n_origins] int32 =
+ * mvpKeyFrameOrigins as rows; parent [rows] int32 and kf_bad [rows] uint8 (nullable): the children of a row are the rows that
+ * are not bad whose parent it is, in ascending row where the reference iterates a std::set<KeyFrame*>; kf_mark, TcwGBA, Tcw
+ * in/out; pt_mark, posGBA, flags, ref_kf [pcap] in; world in/out; TcwBefGBA [rows][12] float out.
+ * The walk is breadth first from the origins in lpKFtoCheck order: a child whose mark is clear gets TcwGBA = (Tcw_child *
+ * Twc_parent) * TcwGBA_parent and its mark; every child is queued; the popped row then gets TcwBefGBA = Tcw and Tcw = TcwGBA.
+ * Twc_parent is formed from the parent's Tcw before that assignment (Rwc = Rcw^T, Ow = -Rwc tcw, KeyFrame::SetPose), a child's
+ * Tcw is still its old pose.  At most `rows` rows are popped; an origin that is bad, outside the table or unmarked (it has no
+ * TcwGBA) is not queued by the device form and refused by the host form.  Then every present point: marked, world = posGBA;
+ * otherwise, if its reference row is marked and was popped, Xc = Rcw_bef Xw + tcw_bef and world = Rwc Xc + twc with the
+ * inverse of the row's new pose; otherwise it is left (reference row unmarked, never reached, or -1).  Float arithmetic is
+ * fp32, per row, left to right, the 4x4 products element by element over k = 0..3.
+ * report [8] int32 = {rows popped, rows whose TcwGBA was propagated, points set from posGBA, points moved through their
+ * reference row, points left, present points, 0, 0}.
+ * Asynchronous on the matcher's stream, no host synchronisation, two launches.  rows <= 4096 (ORBHIP_E_CAPACITY beyond);
+ * rows < 1, pcap < 0, n_origins < 0 or a null required pointer: ORBHIP_E_ARG, before any device work. */
+typedef struct orbhip_gba_apply {
+    const void *origins, *parent, *kf_bad, *pt_mark, *posGBA, *flags, *ref_kf;
+    void *kf_mark, *TcwGBA, *Tcw, *world, *TcwBefGBA, *report;
+} orbhip_gba_apply;
+int orbhip_apply_global_ba_device(orbhip_matcher *m, int n_origins, int rows, int pcap, const orbhip_gba_apply *a);
+/* Host buffers, synchronous; additionally range-checks origins (in [0, rows), not bad, marked), parent in [-1, rows) and
+ * ref_kf in [-1, rows): ORBHIP_E_ARG, before the handle is looked at. */
+int orbhip_apply_global_ba(orbhip_matcher *m, int n_origins, int rows, int pcap, const orbhip_gba_apply *a);
+
 /* ---- creating new map points -------------------------------------------------------------------------------------
  * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452) for the current key frame and K neighbours in one call, up
  * to the point where the map graph is touched: `new MapPoint`, AddObservation and everything after :434 stay with the

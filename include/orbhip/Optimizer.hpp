@@ -1,7 +1,8 @@
 // C++ host-side mirror of ORB_SLAM2::Optimizer (include/Optimizer.h) above orbhip_pose_optimization, orbhip_optimize_sim3,
-// orbhip_local_bundle_adjustment and orbhip_optimize_essential_graph of orbhip.h: the four functions of it the library has,
-// PoseOptimization, OptimizeSim3, LocalBundleAdjustment (whose key frames and map points are the tables of orbhip_lba_tables)
-// and OptimizeEssentialGraph (the tables of orbhip_eg_tables).  Header-only,
+// orbhip_local_bundle_adjustment, orbhip_optimize_essential_graph and orbhip_global_bundle_adjustment of orbhip.h: all of its
+// functions, PoseOptimization, OptimizeSim3, LocalBundleAdjustment (whose key frames and map points are the tables of
+// orbhip_lba_tables), OptimizeEssentialGraph (the tables of orbhip_eg_tables), BundleAdjustment and GlobalBundleAdjustemnt (the
+// tables of orbhip_gba_tables), and ApplyGlobalBA, the map update LoopClosing runs after the last.  Header-only,
 // no OpenCV and no g2o: a frame is the arrays the reference's Frame holds (mvKeysUn, mvuRight, mvpMapPoints as indices
 // into the map arrays, mvbOutlier, mTcw); key frames and map points of OptimizeSim3 are the tables of orbhip_sim3_tables.
 #pragma once
@@ -40,6 +41,16 @@ struct LocalBA {
 struct EssentialGraph {
     std::vector<int32_t> vpCorrectedPoints;
     std::vector<Sim3> vScw, vCorrectedSwc;
+    int32_t report[16];
+};
+
+// What BundleAdjustment leaves besides the poses and points it writes into the tables when nLoopKF == 0: the written points
+// in list order (vpUpdatedPoints); when nLoopKF != 0: mTcwGBA / mPosGBA per bank row / point with their marks
+// (mnBAGlobalForKF == nLoopKF); and the report of orbhip_global_bundle_adjustment_device.
+struct GlobalBA {
+    std::vector<float> TcwGBA, posGBA;      // [rows][12], [pcap][3]
+    std::vector<uint8_t> kfMark, ptMark;    // [rows], [pcap]
+    std::vector<int32_t> vpUpdatedPoints;
     int32_t report[16];
 };
 
@@ -210,6 +221,78 @@ public:
     {
         check(orbhip_optimize_essential_graph_device(matcher.handle(), cur, loopRow, rows, pcap, &tables, bFixScale ? 1 : 0, maxEdges,
                                                      &out), "orbhip_optimize_essential_graph_device");
+    }
+
+    // void Optimizer::BundleAdjustment(const vector<KeyFrame*> &vpKFs, const vector<MapPoint*> &vpMP, int nIterations, bool
+    // *pbStopFlag, const unsigned long nLoopKF, const bool bRobust): the map is the tables (host pointers), vpKFs / vpMP are bank
+    // rows / point indices (a null pointer: all of them, ascending), pbStopFlag may be null.  nLoopKF == 0 writes tables.Tcw and
+    // tables.world and fills out.vpUpdatedPoints (UpdateNormalAndDepth of them, :227, stays with the caller); nLoopKF != 0 fills
+    // out.TcwGBA / posGBA and the marks (mnBAGlobalForKF == nLoopKF), which ApplyGlobalBA takes.  Returns the status
+    // (ORBHIP_GBA_*): on ORBHIP_GBA_CAPACITY nothing but out.report is written.
+    static int BundleAdjustment(ORBmatcher &matcher, const orbhip_camera &cam, int rows, int cap, int np, int pcap,
+                                const orbhip_gba_tables &tables, const std::vector<int32_t> *vpKFs, const std::vector<int32_t> *vpMP,
+                                const std::vector<float> &invLevelSigma2, int nIterations, const bool *pbStopFlag, unsigned long nLoopKF,
+                                bool bRobust, int maxPoints, int maxEdges, GlobalBA &out)
+    {
+        const size_t R = (size_t)(rows > 0 ? rows : 1), P = (size_t)(pcap > 0 ? pcap : 1);
+        out.TcwGBA.assign(R * 12, 0.f); out.posGBA.assign(P * 3, 0.f); out.kfMark.assign(R, 0); out.ptMark.assign(P, 0);
+        std::vector<int32_t> pl((size_t)(maxPoints > 0 ? maxPoints : 1), -1);
+        for (int i = 0; i < 16; ++i) out.report[i] = 0;
+        const uint8_t stop = pbStopFlag && *pbStopFlag ? 1 : 0;
+        const int32_t none = 0;
+        orbhip_gba_out o;
+        o.TcwGBA = out.TcwGBA.data(); o.posGBA = out.posGBA.data(); o.kf_mark = out.kfMark.data(); o.pt_mark = out.ptMark.data();
+        o.point_list = pl.data(); o.report = out.report;
+        check(orbhip_global_bundle_adjustment(matcher.handle(), &cam, rows, cap, np, pcap, &tables, invLevelSigma2.data(),
+                                              vpKFs ? (vpKFs->empty() ? &none : vpKFs->data()) : nullptr, vpKFs ? (int)vpKFs->size() : 0,
+                                              vpMP ? (vpMP->empty() ? &none : vpMP->data()) : nullptr, vpMP ? (int)vpMP->size() : 0,
+                                              nIterations, bRobust ? 1 : 0, nLoopKF == 0 ? ORBHIP_GBA_IN_PLACE : ORBHIP_GBA_STAGED,
+                                              maxPoints, maxEdges, pbStopFlag ? &stop : nullptr, &o), "orbhip_global_bundle_adjustment");
+        out.vpUpdatedPoints.assign(pl.begin(), pl.begin() + (out.report[0] != ORBHIP_GBA_CAPACITY ? out.report[12] : 0));
+        return out.report[0];
+    }
+
+    // void Optimizer::GlobalBundleAdjustemnt(Map *pMap, int nIterations, bool *pbStopFlag, const unsigned long nLoopKF, const bool
+    // bRobust) -- the reference's spelling: BundleAdjustment over every key frame and every map point of the tables.
+    static int GlobalBundleAdjustemnt(ORBmatcher &matcher, const orbhip_camera &cam, int rows, int cap, int np, int pcap,
+                                      const orbhip_gba_tables &tables, const std::vector<float> &invLevelSigma2, int nIterations,
+                                      const bool *pbStopFlag, unsigned long nLoopKF, bool bRobust, int maxPoints, int maxEdges,
+                                      GlobalBA &out)
+    {
+        return BundleAdjustment(matcher, cam, rows, cap, np, pcap, tables, nullptr, nullptr, invLevelSigma2, nIterations, pbStopFlag,
+                                nLoopKF, bRobust, maxPoints, maxEdges, out);
+    }
+
+    // The same over device arrays: the arguments of orbhip_global_bundle_adjustment_device, which see.  The call synchronises the
+    // matcher's stream once per Levenberg-Marquardt trial.
+    static void BundleAdjustmentDevice(ORBmatcher &matcher, const orbhip_camera &cam, int rows, int cap, int np, int pcap,
+                                       const orbhip_gba_tables &tables, const std::vector<float> &invLevelSigma2, const void *d_kf_list,
+                                       int nkf, const void *d_pt_list, int npt, int nIterations, bool bRobust, int mode, int maxPoints,
+                                       int maxEdges, const void *d_stop, const orbhip_gba_out &out)
+    {
+        check(orbhip_global_bundle_adjustment_device(matcher.handle(), &cam, rows, cap, np, pcap, &tables, invLevelSigma2.data(), d_kf_list,
+                                                     nkf, d_pt_list, npt, nIterations, bRobust ? 1 : 0, mode, maxPoints, maxEdges, d_stop,
+                                                     &out), "orbhip_global_bundle_adjustment_device");
+    }
+    static void GlobalBundleAdjustemntDevice(ORBmatcher &matcher, const orbhip_camera &cam, int rows, int cap, int np, int pcap,
+                                             const orbhip_gba_tables &tables, const std::vector<float> &invLevelSigma2, int nIterations,
+                                             bool bRobust, int mode, int maxPoints, int maxEdges, const void *d_stop,
+                                             const orbhip_gba_out &out)
+    {
+        BundleAdjustmentDevice(matcher, cam, rows, cap, np, pcap, tables, invLevelSigma2, nullptr, 0, nullptr, 0, nIterations, bRobust, mode,
+                               maxPoints, maxEdges, d_stop, out);
+    }
+
+    // The map update of LoopClosing::RunGlobalBundleAdjustment (src/LoopClosing.cc:676-737) over host arrays: the arguments of
+    // orbhip_apply_global_ba, which see; a.report receives the eight counts.
+    static void ApplyGlobalBA(ORBmatcher &matcher, int nOrigins, int rows, int pcap, const orbhip_gba_apply &a)
+    {
+        check(orbhip_apply_global_ba(matcher.handle(), nOrigins, rows, pcap, &a), "orbhip_apply_global_ba");
+    }
+    // The same over device arrays, asynchronous on the matcher's stream, two launches.
+    static void ApplyGlobalBADevice(ORBmatcher &matcher, int nOrigins, int rows, int pcap, const orbhip_gba_apply &a)
+    {
+        check(orbhip_apply_global_ba_device(matcher.handle(), nOrigins, rows, pcap, &a), "orbhip_apply_global_ba_device");
     }
 };
 

@@ -114,6 +114,22 @@ class EgOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("point_list", "Scw", "Swc", "report")]
 
 
+class GbaTables(C.Structure):
+    """orbhip_gba_tables: what orbhip_global_bundle_adjustment* reads; Tcw and world are in/out (ORBHIP_GBA_IN_PLACE)."""
+    _fields_ = [(k, C.c_void_p) for k in ("kf_bad", "kf_id", "obs_start", "obs_kf", "obs_idx", "flags", "kps", "u_right", "Tcw", "world")]
+
+
+class GbaOut(C.Structure):
+    """orbhip_gba_out: the staged poses and points with their marks, the point list and the report."""
+    _fields_ = [(k, C.c_void_p) for k in ("TcwGBA", "posGBA", "kf_mark", "pt_mark", "point_list", "report")]
+
+
+class GbaApply(C.Structure):
+    """orbhip_gba_apply: the arrays of orbhip_apply_global_ba*."""
+    _fields_ = [(k, C.c_void_p) for k in ("origins", "parent", "kf_bad", "pt_mark", "posGBA", "flags", "ref_kf", "kf_mark", "TcwGBA",
+                                          "Tcw", "world", "TcwBefGBA", "report")]
+
+
 class PnpParams(C.Structure):
     """orbhip_pnp_params: the arguments of PnPsolver::SetRansacParameters."""
     _fields_ = [("prob", C.c_double), ("min_inliers", C.c_int32), ("max_its", C.c_int32), ("min_set", C.c_int32),
@@ -178,6 +194,13 @@ EG_OK, EG_CAPACITY, EG_SINGULAR = range(3)
 EG_MAX_KF = 512
 EG_REPORT = ("status", "n_vertices", "n_loop_connection", "n_spanning_tree", "n_old_loop", "n_covisibility", "skipped_inserted",
              "skipped_weight", "iterations", "trials", "unknowns", "n_points", "skipped_null", "reserved_0", "reserved_1", "reserved_2")
+# ORBHIP_GBA_*: mode and report[0] of orbhip_global_bundle_adjustment_device
+GBA_IN_PLACE, GBA_STAGED = range(2)
+GBA_OK, GBA_STOPPED, GBA_CAPACITY = range(3)
+GBA_MAX_KF = 512
+GBA_REPORT = ("status", "n_vertices", "n_free", "n_points", "n_removed", "n_mono", "n_stereo", "skipped_bad_or_new", "skipped_null",
+              "iterations", "trials", "unknowns", "n_listed", "reserved_0", "reserved_1", "stop_samples")
+GBA_APPLY_REPORT = ("n_visited", "n_propagated", "n_from_gba", "n_moved", "n_left", "n_present", "reserved_0", "reserved_1")
 REMAP_TABLE_SIZE = 4096
 
 # every symbol include/orbhip.h declares: (name, restype, argtypes)
@@ -332,6 +355,13 @@ SYMBOLS = [
     ("orbhip_optimize_essential_graph_device", _i, [_vp, _i, _i, _i, _i, C.POINTER(EgTables), _i, _i, C.POINTER(EgOut)]),
     ("orbhip_optimize_essential_graph", _i, [_vp, _i, _i, _i, _i, C.POINTER(EgTables), _i, _i, C.POINTER(EgOut)]),
     ("orbhip_optimize_essential_graph_counters", _i, [_vp, _vp]),
+    ("orbhip_global_bundle_adjustment_device", _i, [_vp, C.POINTER(Camera), _i, _i, _i, _i, C.POINTER(GbaTables), _vp, _vp, _i, _vp, _i,
+                                                    _i, _i, _i, _i, _i, _vp, C.POINTER(GbaOut)]),
+    ("orbhip_global_bundle_adjustment", _i, [_vp, C.POINTER(Camera), _i, _i, _i, _i, C.POINTER(GbaTables), _vp, _vp, _i, _vp, _i, _i,
+                                             _i, _i, _i, _i, _vp, C.POINTER(GbaOut)]),
+    ("orbhip_global_bundle_adjustment_counters", _i, [_vp, _vp]),
+    ("orbhip_apply_global_ba_device", _i, [_vp, _i, _i, _i, C.POINTER(GbaApply)]),
+    ("orbhip_apply_global_ba", _i, [_vp, _i, _i, _i, C.POINTER(GbaApply)]),
     ("orbhip_matcher_set_stream", _i, [_vp, _vp]),
     ("orbhip_matcher_sync", _i, [_vp]),
     ("orbhip_compute_stereo_matches_device", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,

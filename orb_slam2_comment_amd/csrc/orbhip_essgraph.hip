@@ -15,23 +15,19 @@
 //   k_eg_vertex        one team per free vertex: its diagonal block and b over its edges in creation order, no float atomics
 //   k_eg_lm_begin      256 lanes: chi2, lambda
 //   k_eg_zero, k_eg_scatter   the dense system at the current lambda: zeroed, then one team per free vertex writes its rows
-//   k_eg_factor_diag / _panel / _trail, per panel of kEgPanel poses (kEgNb = 7 kEgPanel columns): one workgroup factorises
-//                      the diagonal block in LDS; workgroups of 16 rows scale the panel below it; 64 x 64 tiles of the trailing
-//                      matrix take the panel's update from two LDS tiles.  The lower triangle receives L, the upper triangle
-//                      the unscaled columns c_jk = l_jk d_k as they were before the division (both are needed: l_ik * c_jk).
-//                      Every element (i, j) still sees a - l_ik * c_jk for k ascending -- across panels, and inside a tile --
-//                      one multiply and one subtract each (eg_fnma), so the result does not depend on the panel width or on how
-//                      tiles are dealt out and is byte-identical to the one-thread host build.  That rules out FMA and the fp64
-//                      MFMA instructions (v_mfma_f64_*): both round once where the reference order rounds twice.
-//   k_eg_fwd_diag / _upd, k_eg_dscale, k_eg_bwd_diag / _upd   the two substitutions of lba_solve, blocked the same way
+//   ldlt::k_factor_diag / _panel / _trail, k_fwd_diag / _upd, k_dscale, k_bwd_diag / _upd (orbhip_ldlt.h, shared with global
+//                      bundle adjustment): the unpivoted LDLt of lba_solve and its two substitutions, blocked in panels of
+//                      kEgPanel poses (kEgNb = 7 kEgPanel columns) out of global memory, byte-identical to the one-thread host
+//                      build whatever the panel width
 //   k_eg_update, k_eg_trial, k_eg_judge   the tried estimates, chi2 at them, the Levenberg-Marquardt decision
 //   k_eg_finish        one workgroup of 1024: the poses, the list of present points (a scan) and their correction, the report
 #include "orbhip_internal.h"
+#include "orbhip_ldlt.h"
 
 namespace orbhip {
 namespace {
 
-constexpr int kBig = 1024, kItem = 256, kItemBlocks = 240, kNb = kEgNb, kLd = kEgNb + 1, kTile = 64, kPanelRows = 16;
+constexpr int kBig = 1024, kItem = 256, kItemBlocks = 240, kNb = kEgNb;
 
 // exclusive scan of v over the 1024 lanes of the workgroup; *total = the sum.  s_w [16].
 __device__ __forceinline__ int eg_block_scan(int v, int *s_w, int *total)
@@ -206,216 +202,15 @@ __global__ __launch_bounds__(kItem) void k_eg_scatter(EgWs W)
     for (int f = blockIdx.x * (kItem / 64) + (threadIdx.x >> 6); f < nf; f += teams) eg_vertex_scatter(W, f, eg_free_vtx(*W.S, f), lane);
 }
 
-// ---- the factorisation, panel p: columns c0 .. c0 + w ------------------------------------------------------------------------------
-struct Panel { int n, c0, w; size_t ld; bool due; };
-__device__ __forceinline__ Panel eg_panel(const EgWs &W, int p)
-{
-    Panel P;
-    P.n = W.S->n; P.ld = (size_t)P.n; P.c0 = p * kNb;
-    P.w = P.n - P.c0 < kNb ? P.n - P.c0 : kNb;
-    P.due = W.S->phase == kEgTrial && !W.S->fail && P.c0 < P.n;
-    return P;
-}
-
-__global__ __launch_bounds__(kItem) void k_eg_factor_diag(EgWs W, int p)
-{
-    __shared__ double sA[kNb][kLd], sL[kNb][kLd];
-    const Panel P = eg_panel(W, p);
-    if (!P.due) return;
-    const int tid = threadIdx.x, w = P.w;
-    double *A = W.A;
-    for (int idx = tid; idx < w * w; idx += kItem) {
-        const int i = idx / w, j = idx - i * w;
-        if (j <= i) sA[i][j] = A[(size_t)(P.c0 + i) * P.ld + P.c0 + j];
-    }
-    __syncthreads();
-    for (int k = 0; k < w; ++k) {
-        const double d = sA[k][k];
-        if (!(d > 0)) {                                                        // uniform: every lane reads the same pivot
-            if (tid == 0) W.S->fail = 1;
-            return;
-        }
-        for (int i = k + 1 + tid; i < w; i += kItem) sL[i][k] = sA[i][k] / d;
-        __syncthreads();
-        const int m = w - k - 1;
-        for (int idx = tid; idx < m * m; idx += kItem) {
-            const int i = k + 1 + idx / m, j = k + 1 + idx % m;
-            if (j <= i) sA[i][j] = eg_fnma(sA[i][j], sL[i][k], sA[j][k]);
-        }
-        __syncthreads();
-    }
-    for (int idx = tid; idx < w * w; idx += kItem) {
-        const int i = idx / w, j = idx - i * w;
-        if (j == i) A[(size_t)(P.c0 + i) * P.ld + P.c0 + i] = sA[i][i];
-        else if (j < i) {
-            A[(size_t)(P.c0 + i) * P.ld + P.c0 + j] = sL[i][j];
-            A[(size_t)(P.c0 + j) * P.ld + P.c0 + i] = sA[i][j];
-        }
-    }
-}
-
-// 16 rows below the diagonal block per workgroup, 16 lanes per row: column k' is divided, then the columns right of it updated
-__global__ __launch_bounds__(kItem) void k_eg_factor_panel(EgWs W, int p)
-{
-    __shared__ double sC[kNb][kLd], sR[kPanelRows][kLd], sLr[kPanelRows][kLd], sd[kNb];
-    const Panel P = eg_panel(W, p);
-    const int r0 = P.c0 + P.w + blockIdx.x * kPanelRows;
-    if (!P.due || r0 >= P.n) return;
-    const int tid = threadIdx.x, w = P.w, tr = tid >> 4, tl = tid & 15;
-    double *A = W.A;
-    for (int idx = tid; idx < w * w; idx += kItem) {
-        const int kp = idx / w, k = idx - kp * w;                              // c_k,k' sits in the upper triangle at (k', k)
-        if (kp < k) sC[k][kp] = A[(size_t)(P.c0 + kp) * P.ld + P.c0 + k];
-    }
-    for (int k = tid; k < w; k += kItem) sd[k] = A[(size_t)(P.c0 + k) * P.ld + P.c0 + k];
-    for (int idx = tid; idx < kPanelRows * w; idx += kItem) {
-        const int r = idx / w, k = idx - r * w;
-        sR[r][k] = r0 + r < P.n ? A[(size_t)(r0 + r) * P.ld + P.c0 + k] : 0.0;
-    }
-    __syncthreads();
-    for (int kp = 0; kp < w; ++kp) {
-        const double l = sR[tr][kp] / sd[kp];
-        if (tl == 0) sLr[tr][kp] = l;
-        for (int k = kp + 1 + tl; k < w; k += 16) sR[tr][k] = eg_fnma(sR[tr][k], l, sC[k][kp]);
-        __syncthreads();
-    }
-    for (int idx = tid; idx < kPanelRows * w; idx += kItem) {
-        const int r = idx / w, k = idx - r * w;
-        if (r0 + r < P.n) A[(size_t)(r0 + r) * P.ld + P.c0 + k] = sLr[r][k];
-    }
-    for (int idx = tid; idx < kPanelRows * w; idx += kItem) {
-        const int k = idx / kPanelRows, r = idx - k * kPanelRows;
-        if (r0 + r < P.n) A[(size_t)(P.c0 + k) * P.ld + r0 + r] = sR[r][k];
-    }
-}
-
-// a 64 x 64 tile (bi, bj), bj <= bi, of the trailing matrix: 256 lanes, 4 x 4 elements each, strided by 16 so that the LDS
-// rows a wavefront reads fall on different banks
-__global__ __launch_bounds__(kItem) void k_eg_factor_trail(EgWs W, int p)
-{
-    __shared__ double sL[kTile][kLd], sC[kTile][kLd];
-    const Panel P = eg_panel(W, p);
-    const int c1 = P.c0 + P.w, i0 = c1 + blockIdx.y * kTile, j0 = c1 + blockIdx.x * kTile;
-    if (!P.due || blockIdx.x > blockIdx.y || i0 >= P.n) return;
-    const int tid = threadIdx.x, w = P.w, tx = tid & 15, ty = tid >> 4;
-    double *A = W.A;
-    for (int idx = tid; idx < kTile * w; idx += kItem) {
-        const int r = idx / w, k = idx - r * w;
-        sL[r][k] = i0 + r < P.n ? A[(size_t)(i0 + r) * P.ld + P.c0 + k] : 0.0;
-    }
-    for (int idx = tid; idx < kTile * w; idx += kItem) {
-        const int k = idx / kTile, r = idx - k * kTile;
-        sC[r][k] = j0 + r < P.n ? A[(size_t)(P.c0 + k) * P.ld + j0 + r] : 0.0;
-    }
-    __syncthreads();
-    double acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int i = i0 + ty + 16 * a, j = j0 + tx + 16 * b;
-            acc[a][b] = (i < P.n && j <= i) ? A[(size_t)i * P.ld + j] : 0.0;
-        }
-#pragma unroll 2
-    for (int k = 0; k < w; ++k) {
-        double l[4], c[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) { l[a] = sL[ty + 16 * a][k]; c[a] = sC[tx + 16 * a][k]; }
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) acc[a][b] = eg_fnma(acc[a][b], l[a], c[b]);
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int i = i0 + ty + 16 * a, j = j0 + tx + 16 * b;
-            if (i < P.n && j <= i) A[(size_t)i * P.ld + j] = acc[a][b];
-        }
-}
-
-// ---- the substitutions ---------------------------------------------------------------------------------------------------------
-// L y = b: the panel's own rows, column by column
-__global__ __launch_bounds__(64) void k_eg_fwd_diag(EgWs W, int p)
-{
-    __shared__ double sLd[kNb][kLd], sy[kNb];
-    const Panel P = eg_panel(W, p);
-    if (!P.due) return;
-    const int tid = threadIdx.x, w = P.w;
-    for (int idx = tid; idx < w * w; idx += 64) {
-        const int i = idx / w, j = idx - i * w;
-        if (j < i) sLd[i][j] = W.A[(size_t)(P.c0 + i) * P.ld + P.c0 + j];
-    }
-    if (tid < w) sy[tid] = W.y[P.c0 + tid];
-    __syncthreads();
-    for (int k = 0; k < w; ++k) {
-        const double yk = sy[k];
-        __syncthreads();
-        if (tid > k && tid < w) sy[tid] = eg_fnma(sy[tid], sLd[tid][k], yk);
-        __syncthreads();
-    }
-    if (tid < w) W.y[P.c0 + tid] = sy[tid];
-}
-// the rows below the panel: one lane per row over the panel's columns in order, the tile staged through LDS
-__global__ __launch_bounds__(64) void k_eg_fwd_upd(EgWs W, int p)
-{
-    __shared__ double sT[kTile][kLd], sy[kNb];
-    const Panel P = eg_panel(W, p);
-    const int r0 = P.c0 + P.w + blockIdx.x * kTile;
-    if (!P.due || r0 >= P.n) return;
-    const int tid = threadIdx.x, w = P.w;
-    for (int idx = tid; idx < kTile * w; idx += 64) {
-        const int r = idx / w, k = idx - r * w;
-        sT[r][k] = r0 + r < P.n ? W.A[(size_t)(r0 + r) * P.ld + P.c0 + k] : 0.0;
-    }
-    if (tid < w) sy[tid] = W.y[P.c0 + tid];
-    __syncthreads();
-    if (r0 + tid >= P.n) return;
-    double v = W.y[r0 + tid];
-    for (int k = 0; k < w; ++k) v = eg_fnma(v, sT[tid][k], sy[k]);
-    W.y[r0 + tid] = v;
-}
-__global__ __launch_bounds__(kItem) void k_eg_dscale(EgWs W)
-{
-    if (W.S->phase != kEgTrial || W.S->fail) return;
-    const int n = W.S->n;
-    for (int i = blockIdx.x * kItem + threadIdx.x; i < n; i += gridDim.x * kItem) W.y[i] = W.y[i] / W.A[(size_t)i * n + i];
-}
-// L^T x = y: the panel's own rows from its last column, then the rows above it
-__global__ __launch_bounds__(64) void k_eg_bwd_diag(EgWs W, int p)
-{
-    __shared__ double sLd[kNb][kLd], sy[kNb];
-    const Panel P = eg_panel(W, p);
-    if (!P.due) return;
-    const int tid = threadIdx.x, w = P.w;
-    for (int idx = tid; idx < w * w; idx += 64) {
-        const int i = idx / w, j = idx - i * w;
-        if (j < i) sLd[i][j] = W.A[(size_t)(P.c0 + i) * P.ld + P.c0 + j];
-    }
-    if (tid < w) sy[tid] = W.y[P.c0 + tid];
-    __syncthreads();
-    for (int j = w - 1; j > 0; --j) {
-        const double yj = sy[j];
-        __syncthreads();
-        if (tid < j) sy[tid] = eg_fnma(sy[tid], sLd[j][tid], yj);
-        __syncthreads();
-    }
-    if (tid < w) W.y[P.c0 + tid] = sy[tid];
-}
-__global__ __launch_bounds__(kItem) void k_eg_bwd_upd(EgWs W, int p)
-{
-    __shared__ double sy[kNb];
-    const Panel P = eg_panel(W, p);
-    const int i = blockIdx.x * kItem + threadIdx.x;
-    if (!P.due || blockIdx.x * kItem >= P.c0) return;
-    if (threadIdx.x < P.w) sy[threadIdx.x] = W.y[P.c0 + threadIdx.x];
-    __syncthreads();
-    if (i >= P.c0) return;
-    double v = W.y[i];
-    for (int j = P.w - 1; j >= 0; --j) v = eg_fnma(v, W.A[(size_t)(P.c0 + j) * P.ld + i], sy[j]);
-    W.y[i] = v;
-}
+// ---- the factorisation and the substitutions: orbhip_ldlt.h over this view of the system -------------------------------------------
+struct EgView {
+    EgWs W;
+    __device__ __forceinline__ double *A() const { return W.A; }
+    __device__ __forceinline__ double *y() const { return W.y; }
+    __device__ __forceinline__ int n() const { return W.S->n; }
+    __device__ __forceinline__ bool due() const { return W.S->phase == kEgTrial && !W.S->fail; }
+    __device__ __forceinline__ void fail() const { W.S->fail = 1; }
+};
 
 // ---- the rest of a trial ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kItem) void k_eg_update(EgWs W)
@@ -486,8 +281,8 @@ size_t eg_workspace_bytes(EgWs W) { return eg_carve(W, nullptr); }
 int launch_optimize_essential_graph(hipStream_t stream, EgWs W, void *workspace, EgState *h_state, int *counters)
 {
     eg_carve(W, (uint8_t *)workspace);
-    const dim3 one(1), items(kItemBlocks), it(kItem), big(kBig), team(kEgTeam), w64(64);
-    const int nmax = 7 * eg_mk(W), panels = (nmax + kNb - 1) / kNb;
+    const dim3 one(1), items(kItemBlocks), it(kItem), big(kBig), team(kEgTeam);
+    const int nmax = 7 * eg_mk(W);
     int syncs = 0, launches = 0;
     auto read_state = [&]() -> int {
         ORBHIP_HIP_CHECK(hipGetLastError());
@@ -511,36 +306,11 @@ int launch_optimize_essential_graph(hipStream_t stream, EgWs W, void *workspace,
         if (h_state->phase == kEgBuild || h_state->phase == kEgTrial) {
             hipLaunchKernelGGL(k_eg_zero, dim3(1024), it, 0, stream, W);
             hipLaunchKernelGGL(k_eg_scatter, dim3((eg_mk(W) + 3) / 4), it, 0, stream, W);
-            for (int p = 0; p < panels; ++p) {
-                const int below = nmax - (p + 1) * kNb;
-                hipLaunchKernelGGL(k_eg_factor_diag, one, it, 0, stream, W, p);
-                ++launches;
-                if (below <= 0) continue;
-                const int tiles = (below + kTile - 1) / kTile;
-                hipLaunchKernelGGL(k_eg_factor_panel, dim3((below + kPanelRows - 1) / kPanelRows), it, 0, stream, W, p);
-                hipLaunchKernelGGL(k_eg_factor_trail, dim3(tiles, tiles), it, 0, stream, W, p);
-                launches += 2;
-            }
-            for (int p = 0; p < panels; ++p) {
-                const int below = nmax - (p + 1) * kNb;
-                hipLaunchKernelGGL(k_eg_fwd_diag, one, w64, 0, stream, W, p);
-                ++launches;
-                if (below <= 0) continue;
-                hipLaunchKernelGGL(k_eg_fwd_upd, dim3((below + kTile - 1) / kTile), w64, 0, stream, W, p);
-                ++launches;
-            }
-            hipLaunchKernelGGL(k_eg_dscale, dim3(16), it, 0, stream, W);
-            for (int p = panels - 1; p >= 0; --p) {
-                hipLaunchKernelGGL(k_eg_bwd_diag, one, w64, 0, stream, W, p);
-                ++launches;
-                if (p == 0) continue;
-                hipLaunchKernelGGL(k_eg_bwd_upd, dim3((p * kNb + kItem - 1) / kItem), it, 0, stream, W, p);
-                ++launches;
-            }
+            launches += ldlt::enqueue_solve<EgView, kNb>(stream, EgView{W}, nmax);
             hipLaunchKernelGGL(k_eg_update, dim3(4), it, 0, stream, W);
             hipLaunchKernelGGL(k_eg_trial, items, it, 0, stream, W);
             hipLaunchKernelGGL(k_eg_judge, one, team, 0, stream, W);
-            launches += 6;
+            launches += 5;
         } else {                                                               // kEgFinal
             hipLaunchKernelGGL(k_eg_finish, one, big, 0, stream, W);
             ++launches;

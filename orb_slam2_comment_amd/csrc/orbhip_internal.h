@@ -312,6 +312,16 @@ size_t eg_workspace_bytes(EgWs W);
 int launch_optimize_essential_graph(hipStream_t stream, EgWs W, void *workspace, EgState *h_state, int *counters);
 }  // namespace orbhip
 
+#include "orbhip_gba_core.h"
+
+namespace orbhip {
+// orbhip_gba.hip: as above; h_state is a pinned LbaState, read once after the setup and once per trial
+size_t gba_workspace_bytes(GbaWs G);
+int launch_global_bundle_adjustment(hipStream_t stream, GbaWs G, void *workspace, LbaState *h_state, int *counters);
+size_t gba_apply_workspace_bytes(GbaApply A);
+int launch_apply_global_ba(hipStream_t stream, GbaApply A, void *workspace);
+}  // namespace orbhip
+
 struct orbhip_extractor {
     int nfeatures = 0;
     double scaleFactor = 1.2;

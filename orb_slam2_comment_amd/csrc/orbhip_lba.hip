@@ -22,9 +22,11 @@
 //   k_lba_classify, k_lba_round2, k_lba_final_edges, k_lba_finish: the level-1 rule, the second round's system, the
 //                      erase rows (monocular, then stereo, by two scans), the write-back and the report
 #include "orbhip_internal.h"
+#include "orbhip_lba_dev.h"
 
 namespace orbhip {
 namespace {
+using namespace lbadev;
 
 constexpr int kSetupThreads = 1024, kItemThreads = 256, kItemBlocks = 120, kPoseBlocks = kLbaMaxLocal / 4, kSchurBlocks = 256;
 constexpr int kIntMax = 0x7fffffff;
@@ -245,16 +247,6 @@ __global__ __launch_bounds__(kItemThreads) void k_lba_linearize(LbaWs W)
     for (int j = blockIdx.x * kItemThreads + threadIdx.x; j < ne; j += gridDim.x * kItemThreads) lba_edge_linearize(W, j);
 }
 
-// the xor butterfly of N sums over a wavefront
-template <int N> __device__ __forceinline__ void wave_butterfly(double *s)
-{
-#pragma unroll
-    for (int off = 1; off < kLbaWave; off <<= 1) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) s[k] = s[k] + __shfl_xor(s[k], off);
-    }
-}
-
 __global__ __launch_bounds__(kItemThreads) void k_lba_blocks(LbaWs W)
 {
     if (W.S->phase != kLbaBuild) return;
@@ -277,21 +269,6 @@ __global__ __launch_bounds__(kItemThreads) void k_lba_blocks(LbaWs W)
     }
     const int np = W.S->n_pts, nb = gridDim.x - kPoseBlocks;
     for (int i = (blockIdx.x - kPoseBlocks) * kItemThreads + tid; i < np; i += nb * kItemThreads) lba_point_block(W, i);
-}
-
-__device__ __forceinline__ double team_sum(const LbaWs &W, int kind, double *s_part)
-{
-    const int tid = threadIdx.x;
-    double v = lba_sum_lane(W, kind, tid);
-#pragma unroll
-    for (int off = 1; off < kLbaWave; off <<= 1) v = lba_sum_op(kind, v, __shfl_xor(v, off));
-    __syncthreads();
-    if ((tid & 63) == 0) s_part[tid >> 6] = v;
-    __syncthreads();
-    double t = s_part[0];
-#pragma unroll
-    for (int w = 1; w < kLbaTeam / kLbaWave; ++w) t = lba_sum_op(kind, t, s_part[w]);
-    return t;
 }
 
 __global__ __launch_bounds__(kLbaTeam) void k_lba_begin(LbaWs W)
@@ -319,43 +296,7 @@ __global__ __launch_bounds__(kItemThreads) void k_lba_schur(LbaWs W)
     for (int t = blockIdx.x * (kItemThreads / 64) + (tid >> 6); t < nfree * nfree; t += waves) {
         const int i1 = t / nfree, i2 = t - i1 * nfree;
         if (i2 < i1) continue;
-        double acc[42];
-#pragma unroll
-        for (int k = 0; k < 42; ++k) acc[k] = 0.0;
-        lba_schur_lane(W, i1, i2, lane, acc);
-        wave_butterfly<42>(acc);
-        // the store, dealt over the lanes: every lane holds the sums
-        const int ld = 6 * nfree;
-        const double lam = W.S->lam;
-        if (i1 == i2) {
-            const bool act = W.pose_active[i1] != 0;
-            if (lane < 36) {
-                const int a = lane / 6, b = lane - a * 6;
-                if (b <= a) {
-                    double v = a == b ? 1.0 : 0.0, sm = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 36; ++k) if (k == b * 6 + a) sm = acc[k];
-                    if (act) {
-                        double h = W.Hpp[i1 * 21 + lba_upper(b, a)];
-                        if (a == b) h = h + lam;
-                        v = h - sm;
-                    }
-                    W.A[(size_t)(6 * i1 + a) * ld + 6 * i1 + b] = v;
-                }
-            } else if (lane < 42) {
-                const int a = lane - 36;
-                double sm = 0.0;
-#pragma unroll
-                for (int k = 0; k < 6; ++k) if (k == a) sm = acc[36 + k];
-                W.bs[6 * i1 + a] = act ? W.bp[i1 * 6 + a] - sm : 0.0;
-            }
-        } else if (lane < 36) {
-            const int a = lane / 6, b = lane - a * 6;
-            double sm = 0.0;
-#pragma unroll
-            for (int k = 0; k < 36; ++k) if (k == lane) sm = acc[k];
-            W.A[(size_t)(6 * i2 + b) * ld + 6 * i1 + a] = 0.0 - sm;
-        }
+        schur_pair(W, i1, i2, lane, true);
     }
 }
 

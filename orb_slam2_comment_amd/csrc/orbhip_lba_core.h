@@ -54,6 +54,10 @@ struct LbaWs {
     float inv[ORBHIP_MAX_LEVELS];
     PoCam cam;
     int cur, id0_row, rows, cap, np, pcap, n_levels, max_points, max_edges;
+    // what global bundle adjustment (orbhip_gba_core.h) sets; all zero is LocalBundleAdjustment
+    int single_its;                         // > 0: one round of optimize(single_its), no level-1 rule
+    int robust;                             // that round's edges carry Huber kernels
+    int max_free;                           // free poses the dense system is sized for (0: kLbaMaxLocal)
     // the workspace
     LbaState *S;
     int *lkf, *fkf, *lpt;                   // [rows], [rows], [max_points]: the three lists
@@ -64,12 +68,12 @@ struct LbaWs {
     int *e_vtx, *e_idx, *e_pt;              // [max_edges]: the edges in creation order
     uint8_t *e_fl, *e_erase;
     int *pt_e0;                             // [max_points + 1]: a point's edges
-    int *kf_e0, *kf_edges;                  // [kLbaMaxLocal + 1], [max_edges]: a free pose's edges, ascending
-    uint8_t *pt_active, *pose_active;       // [max_points], [kLbaMaxLocal]
+    int *kf_e0, *kf_edges;                  // [max_free + 1], [max_edges]: a free pose's edges, ascending
+    uint8_t *pt_active, *pose_active;       // [max_points], [max_free]
     double *pose, *pt;                      // [2][rows][7], [2][max_points][3]: the accepted estimate is buffer S->cur
     double *eb;                             // [max_edges][kLbaRec]
     double *Hll, *bl, *Dinv, *db, *xl;      // [max_points][6 | 3 | 6 | 3 | 3]
-    double *Hpp, *bp;                       // [kLbaMaxLocal][21 | 6]
+    double *Hpp, *bp;                       // [max_free][21 | 6]
     double *A, *bs, *xp, *L, *y;            // the Schur system [n][n], [n] each, n = 6 * n_free
 };
 
@@ -91,10 +95,13 @@ PO_HD bool lba_sample(LbaWs &W)
 }
 
 // ---- the serial state machine ---------------------------------------------------------------------------------------
+PO_HD int lba_max_free(const LbaWs &W) { return W.max_free ? W.max_free : kLbaMaxLocal; }
+PO_HD bool lba_robust(const LbaWs &W) { return W.single_its ? W.robust != 0 : W.S->round == 0; }
 PO_HD void lba_round_end(LbaWs &W)
 {
     LbaState &S = *W.S;
-    if (S.round == 0) {
+    if (W.single_its) S.phase = kLbaFinal;
+    else if (S.round == 0) {
         if (lba_sample(W)) { S.status = ORBHIP_LBA_ONE_ROUND; S.phase = kLbaFinal; }   // :664
         else S.phase = kLbaClassify;
     } else {
@@ -105,7 +112,7 @@ PO_HD void lba_round_end(LbaWs &W)
 PO_HD void lba_iter_top(LbaWs &W, bool ok)
 {
     LbaState &S = *W.S;
-    if (S.it >= (S.round == 0 ? 5 : 10)) { lba_round_end(W); return; }
+    if (S.it >= (W.single_its ? W.single_its : (S.round == 0 ? 5 : 10))) { lba_round_end(W); return; }
     const bool t = lba_sample(W);
     if (t || !ok) { lba_round_end(W); return; }
     S.phase = kLbaBuild;
@@ -203,7 +210,7 @@ PO_HD void lba_edge_error(const LbaWs &W, int j, int buf)
     lba_load_edge(W, j, buf, e, pose, fr);
     const double chi2 = po_edge_error(e, pose, W.cam, err, P);
     double rho0 = chi2;
-    if (W.S->round == 0 && !(chi2 <= e.dsqr)) rho0 = 2 * sqrt(chi2) * e.delta - e.dsqr;
+    if (lba_robust(W) && !(chi2 <= e.dsqr)) rho0 = 2 * sqrt(chi2) * e.delta - e.dsqr;
     double *r = W.eb + (size_t)j * kLbaRec;
     r[kLbaRho] = rho0; r[kLbaChi2] = chi2;
 }
@@ -219,7 +226,7 @@ PO_HD void lba_edge_linearize(const LbaWs &W, int j)
     lba_load_edge(W, j, W.S->cur, e, pose, fr);
     const double chi2 = po_edge_error(e, pose, W.cam, err, P);
     double rho0 = chi2, rho1 = 1.0;
-    if (W.S->round == 0 && !(chi2 <= e.dsqr)) {                                   // RobustKernelHuber::robustify
+    if (lba_robust(W) && !(chi2 <= e.dsqr)) {                                     // RobustKernelHuber::robustify
         const double s = sqrt(chi2);
         rho0 = 2 * s * e.delta - e.dsqr;
         rho1 = e.delta / s;
@@ -590,7 +597,7 @@ inline size_t lba_carve(LbaWs &W, uint8_t *base)
 {
     size_t off = 0;
     auto take = [&](size_t bytes) { uint8_t *p = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
-    const size_t R = (size_t)W.rows, P = (size_t)W.max_points, E = (size_t)W.max_edges, n = 6 * (size_t)kLbaMaxLocal;
+    const size_t R = (size_t)W.rows, P = (size_t)W.max_points, E = (size_t)W.max_edges, F = (size_t)lba_max_free(W), n = 6 * F;
     W.S = (LbaState *)take(sizeof(LbaState));
     W.lkf = (int *)take(R * 4); W.fkf = (int *)take(R * 4); W.lpt = (int *)take(P * 4);
     W.kf_vtx = (int *)take(R * 4); W.vtx_row = (int *)take(R * 4); W.vtx_free = (int *)take(R * 4);
@@ -599,13 +606,13 @@ inline size_t lba_carve(LbaWs &W, uint8_t *base)
     W.e_vtx = (int *)take(E * 4); W.e_idx = (int *)take(E * 4); W.e_pt = (int *)take(E * 4);
     W.e_fl = take(E); W.e_erase = take(E);
     W.pt_e0 = (int *)take((P + 1) * 4);
-    W.kf_e0 = (int *)take((kLbaMaxLocal + 1) * 4); W.kf_edges = (int *)take(E * 4);
-    W.pt_active = take(P); W.pose_active = take(kLbaMaxLocal);
+    W.kf_e0 = (int *)take((F + 1) * 4); W.kf_edges = (int *)take(E * 4);
+    W.pt_active = take(P); W.pose_active = take(F);
     W.pose = (double *)take(2 * R * 7 * 8); W.pt = (double *)take(2 * P * 3 * 8);
     W.eb = (double *)take(E * kLbaRec * 8);
     W.Hll = (double *)take(P * 6 * 8); W.bl = (double *)take(P * 3 * 8); W.Dinv = (double *)take(P * 6 * 8);
     W.db = (double *)take(P * 3 * 8); W.xl = (double *)take(P * 3 * 8);
-    W.Hpp = (double *)take((size_t)kLbaMaxLocal * 21 * 8); W.bp = (double *)take((size_t)kLbaMaxLocal * 6 * 8);
+    W.Hpp = (double *)take(F * 21 * 8); W.bp = (double *)take(F * 6 * 8);
     W.A = (double *)take(n * n * 8); W.bs = (double *)take(n * 8); W.xp = (double *)take(n * 8);
     W.L = (double *)take(n * 8); W.y = (double *)take(n * 8);
     return off;
@@ -767,11 +774,45 @@ inline void lba_host_snapshot(const LbaWs &W, int buf, double *dst)
         for (int k = 0; k < 3; ++k) dst[(size_t)W.rows * 7 + i * 3 + k] = W.pt[lba_pt_at(W, buf, i) + k];
 }
 
+// one linearisation (phase kLbaBuild) and one trial (phase kLbaTrial) on one thread, step by step as the device enqueues them
+inline void lba_host_build(LbaWs &W)
+{
+    LbaState &S = *W.S;
+    for (int j = 0; j < S.n_edges; ++j) lba_edge_linearize(W, j);
+    for (int i = 0; i < S.n_pts; ++i) lba_point_block(W, i);
+    for (int f = 0; f < S.n_free; ++f) {
+        double lanes[kLbaWave][42];
+        for (int l = 0; l < kLbaWave; ++l) { for (int k = 0; k < 27; ++k) lanes[l][k] = 0.0; lba_pose_block_lane(W, f, l, lanes[l]); }
+        lba_host_butterfly(lanes, 27, kLbaSumChi);
+        lba_pose_block_store(W, f, lanes[0]);
+    }
+    const double chi = lba_host_team_sum(W, kLbaSumChi), mx = S.it == 0 ? lba_host_team_sum(W, kLbaSumMax) : 0.0;
+    lba_lm_begin(W, chi, mx);
+}
+inline void lba_host_trial(LbaWs &W)
+{
+    LbaState &S = *W.S;
+    LbaHostTeam tm;
+    for (int i = 0; i < S.n_pts; ++i) lba_point_dinv(W, i);
+    for (int i1 = 0; i1 < S.n_free; ++i1)
+        for (int i2 = i1; i2 < S.n_free; ++i2) {
+            double lanes[kLbaWave][42];
+            for (int l = 0; l < kLbaWave; ++l) { for (int k = 0; k < 42; ++k) lanes[l][k] = 0.0; lba_schur_lane(W, i1, i2, l, lanes[l]); }
+            lba_host_butterfly(lanes, 42, kLbaSumChi);
+            lba_schur_store(W, i1, i2, lanes[0]);
+        }
+    S.ok2 = lba_solve(tm, W) ? 1 : 0;
+    for (int i = 0; i < S.n_pts; ++i) lba_point_update(W, i);
+    for (int v = 0; v < S.n_lkf + S.n_fkf; ++v) lba_vertex_update(W, v);
+    for (int j = 0; j < S.n_edges; ++j) lba_edge_error(W, j, 1 - S.cur);
+    const double chi = lba_host_team_sum(W, kLbaSumChi), scale = lba_host_team_sum(W, kLbaSumScale);
+    lba_lm_judge(W, chi, scale);
+}
+
 // the whole function on one thread, phase by phase as the device enqueues it
 inline void lba_host_run(LbaWs &W, LbaHostTrace *trace = nullptr)
 {
     LbaState &S = *W.S;
-    LbaHostTeam tm;
     lba_host_setup(W);
     if (S.status != ORBHIP_LBA_CAPACITY) lba_host_activity(W, 0);
     lba_begin(W);
@@ -781,32 +822,10 @@ inline void lba_host_run(LbaWs &W, LbaHostTrace *trace = nullptr)
     };
     while (S.phase != kLbaDone) {
         if (S.phase == kLbaBuild) {
-            for (int j = 0; j < S.n_edges; ++j) lba_edge_linearize(W, j);
-            for (int i = 0; i < S.n_pts; ++i) lba_point_block(W, i);
-            for (int f = 0; f < S.n_free; ++f) {
-                double lanes[kLbaWave][42];
-                for (int l = 0; l < kLbaWave; ++l) { for (int k = 0; k < 27; ++k) lanes[l][k] = 0.0; lba_pose_block_lane(W, f, l, lanes[l]); }
-                lba_host_butterfly(lanes, 27, kLbaSumChi);
-                lba_pose_block_store(W, f, lanes[0]);
-            }
-            const double chi = lba_host_team_sum(W, kLbaSumChi), mx = S.it == 0 ? lba_host_team_sum(W, kLbaSumMax) : 0.0;
-            lba_lm_begin(W, chi, mx);
+            lba_host_build(W);
         } else if (S.phase == kLbaTrial) {
-            for (int i = 0; i < S.n_pts; ++i) lba_point_dinv(W, i);
-            for (int i1 = 0; i1 < S.n_free; ++i1)
-                for (int i2 = i1; i2 < S.n_free; ++i2) {
-                    double lanes[kLbaWave][42];
-                    for (int l = 0; l < kLbaWave; ++l) { for (int k = 0; k < 42; ++k) lanes[l][k] = 0.0; lba_schur_lane(W, i1, i2, l, lanes[l]); }
-                    lba_host_butterfly(lanes, 42, kLbaSumChi);
-                    lba_schur_store(W, i1, i2, lanes[0]);
-                }
-            S.ok2 = lba_solve(tm, W) ? 1 : 0;
-            for (int i = 0; i < S.n_pts; ++i) lba_point_update(W, i);
-            for (int v = 0; v < S.n_lkf + S.n_fkf; ++v) lba_vertex_update(W, v);
-            for (int j = 0; j < S.n_edges; ++j) lba_edge_error(W, j, 1 - S.cur);
-            const double chi = lba_host_team_sum(W, kLbaSumChi), scale = lba_host_team_sum(W, kLbaSumScale);
             const int round = S.round;
-            lba_lm_judge(W, chi, scale);
+            lba_host_trial(W);
             if (S.phase == kLbaClassify || S.phase == kLbaFinal) snap(round);
         } else if (S.phase == kLbaClassify) {
             snap(0);

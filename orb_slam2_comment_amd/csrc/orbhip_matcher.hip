@@ -3715,8 +3715,8 @@ struct orbhip_matcher {
     hipStream_t stream = nullptr;       // stream every launch goes to
     hipStream_t own_stream = nullptr;   // created with the handle
     // grow-only device scratch
-    void *buf[28] = {};
-    size_t cap[28] = {};
+    void *buf[30] = {};
+    size_t cap[30] = {};
     bool lds_attr_set = false, bow_attr_set = false;
 #ifdef ORBHIP_DEVTOOLS
     int window_lanes = 0;               // development build: lanes per query of k_window_search forced to 16 / 64 (0: the rule)
@@ -3727,6 +3727,8 @@ struct orbhip_matcher {
     uint8_t *h_out = nullptr; size_t h_out_bytes = 0;
     void *h_eg = nullptr;               // pinned: the state record of the essential-graph optimisation, read once per trial
     int eg_counters[2] = {0, 0};        // synchronisations and launches of the last essential-graph call
+    void *h_gba = nullptr;              // pinned: the state record of global bundle adjustment, read once per trial
+    int gba_counters[2] = {0, 0};       // synchronisations and launches of the last global-bundle-adjustment call
     // Sim3 RANSAC: the iteration limit per correspondence count, [sim3_cap + 1], rebuilt when a parameter changes
     std::vector<int> sim3_limit;
     double sim3_prob = 0.0;
@@ -3815,7 +3817,7 @@ static SigmaTab sigma_tab(const float *inv_level_sigma2, int n_levels)
     return sig;
 }
 
-enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_COVIS, S_CULL, S_SIM3, S_SIM3LIM, S_SIM3SOLV, S_PNP, S_PNPTAB, S_PNPSOLV, S_LBA, S_EG, S_NSLOTS };
+enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_COVIS, S_CULL, S_SIM3, S_SIM3LIM, S_SIM3SOLV, S_PNP, S_PNPTAB, S_PNPSOLV, S_LBA, S_EG, S_GBA, S_GBAAPPLY, S_NSLOTS };
 static_assert(S_NSLOTS == sizeof(orbhip_matcher::buf) / sizeof(void *), "one scratch buffer per slot");
 
 static int stage_begin(orbhip_matcher *m, size_t total, Stage *st)
@@ -4274,6 +4276,7 @@ void orbhip_matcher_destroy(orbhip_matcher *m)
     if (m->h_stage) (void)hipHostFree(m->h_stage);
     if (m->h_out) (void)hipHostFree(m->h_out);
     if (m->h_eg) (void)hipHostFree(m->h_eg);
+    if (m->h_gba) (void)hipHostFree(m->h_gba);
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
     delete m;
 }
@@ -6790,6 +6793,257 @@ int orbhip_optimize_essential_graph_counters(orbhip_matcher *m, int32_t counters
 {
     if (!m || !counters) return ORBHIP_E_ARG;
     counters[0] = m->eg_counters[0]; counters[1] = m->eg_counters[1];
+    return ORBHIP_OK;
+}
+
+// ---- global bundle adjustment (kernels: orbhip_gba.hip) ----------------------------------------------------------------------
+static int gba_args(const orbhip_camera *cam, int rows, int cap, int np, int pcap, const orbhip_gba_tables *t, const float *inv_level_sigma2,
+                    const void *kf_list, int nkf, const void *pt_list, int npt, int iterations, int mode, int max_points, int max_edges,
+                    const orbhip_gba_out *out)
+{
+    if (!cam || rows < 0 || cap < 1 || np < 0 || pcap < 0 || np > pcap || max_points < 1 || max_edges < 1 || !inv_level_sigma2 ||
+        cam->n_levels < 1 || cam->n_levels > ORBHIP_MAX_LEVELS || iterations < 1 || (mode != ORBHIP_GBA_IN_PLACE && mode != ORBHIP_GBA_STAGED) ||
+        (kf_list && (nkf < 0 || nkf > rows)) || (pt_list && (npt < 0 || npt > pcap)))
+        return ORBHIP_E_ARG;
+    if (!t || !t->kf_id || !t->obs_start || !t->obs_kf || !t->obs_idx || !t->flags || !t->kps || !t->Tcw || !t->world || !out || !out->report)
+        return ORBHIP_E_ARG;
+    if (mode == ORBHIP_GBA_IN_PLACE ? !out->point_list : (!out->TcwGBA || !out->posGBA || !out->kf_mark || !out->pt_mark)) return ORBHIP_E_ARG;
+    if (cap > 4096 || rows > 4096) { set_error("global_bundle_adjustment: rows %d or capacity %d exceeds 4096", rows, cap); return ORBHIP_E_CAPACITY; }
+    return ORBHIP_OK;
+}
+
+static int gba_launch(orbhip_matcher *m, const orbhip_camera *cam, int rows, int cap, int np, int pcap, const orbhip_gba_tables *t,
+                      const float *inv_level_sigma2, const void *d_kf_list, int nkf, const void *d_pt_list, int npt, int iterations,
+                      int robust, int mode, int max_points, int max_edges, const void *d_stop, const orbhip_gba_out *out)
+{
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    GbaWs G;
+    memset(&G, 0, sizeof(G));
+    LbaWs &W = G.L;
+    W.kf_bad = (const uint8_t *)t->kf_bad; W.obs_start = (const int *)t->obs_start; W.obs_kf = (const int *)t->obs_kf;
+    W.obs_idx = (const int *)t->obs_idx; W.flags = (const uint8_t *)t->flags; W.kps = (const orbhip_keypoint *)t->kps;
+    W.u_right = (const float *)t->u_right; W.Tcw = (float *)t->Tcw; W.world = (float *)t->world;
+    W.stop = (const uint8_t *)d_stop;
+    for (int l = 0; l < ORBHIP_MAX_LEVELS; ++l) W.inv[l] = l < cam->n_levels ? inv_level_sigma2[l] : 0.f;
+    W.cam.fx = (double)cam->fx; W.cam.fy = (double)cam->fy; W.cam.cx = (double)cam->cx; W.cam.cy = (double)cam->cy;
+    W.cam.bf = (double)cam->mbf;
+    W.cam.delta_mono = (double)(float)std::sqrt(5.99);                        // src/Optimizer.cc:85-86
+    W.cam.delta_stereo = (double)(float)std::sqrt(7.815);
+    W.cur = 0; W.id0_row = -1; W.rows = rows; W.cap = cap; W.np = np; W.pcap = pcap; W.n_levels = cam->n_levels;
+    W.max_points = max_points; W.max_edges = max_edges;
+    W.single_its = iterations; W.robust = robust ? 1 : 0;
+    G.kf_id = (const int *)t->kf_id; G.kf_list = (const int *)d_kf_list; G.pt_list = (const int *)d_pt_list; G.nkf = nkf; G.npt = npt;
+    G.mode = mode;
+    G.TcwGBA = (float *)out->TcwGBA; G.posGBA = (float *)out->posGBA; G.kf_mark = (uint8_t *)out->kf_mark; G.pt_mark = (uint8_t *)out->pt_mark;
+    G.o_point_list = (int *)out->point_list; G.o_report = (int *)out->report;
+    void *ws;
+    if (int rc = scratch(m, S_GBA, gba_workspace_bytes(G), &ws)) return rc;
+    if (!m->h_gba) ORBHIP_HIP_CHECK(hipHostMalloc(&m->h_gba, sizeof(LbaState), hipHostMallocDefault));
+    return launch_global_bundle_adjustment(m->stream, G, ws, (LbaState *)m->h_gba, m->gba_counters);
+}
+
+int orbhip_global_bundle_adjustment_device(orbhip_matcher *m, const orbhip_camera *cam, int rows, int cap, int np, int pcap,
+                                           const orbhip_gba_tables *tables, const float *inv_level_sigma2, const void *d_kf_list,
+                                           int nkf, const void *d_pt_list, int npt, int iterations, int robust, int mode,
+                                           int max_points, int max_edges, const void *d_stop, const orbhip_gba_out *out)
+{
+    if (int rc = gba_args(cam, rows, cap, np, pcap, tables, inv_level_sigma2, d_kf_list, nkf, d_pt_list, npt, iterations, mode, max_points,
+                          max_edges, out))
+        return rc;
+    if (!m) return ORBHIP_E_ARG;
+    return gba_launch(m, cam, rows, cap, np, pcap, tables, inv_level_sigma2, d_kf_list, nkf, d_pt_list, npt, iterations, robust, mode,
+                      max_points, max_edges, d_stop, out);
+}
+
+int orbhip_global_bundle_adjustment(orbhip_matcher *m, const orbhip_camera *cam, int rows, int cap, int np, int pcap,
+                                    const orbhip_gba_tables *t, const float *inv_level_sigma2, const int32_t *kf_list, int nkf,
+                                    const int32_t *pt_list, int npt, int iterations, int robust, int mode, int max_points,
+                                    int max_edges, const uint8_t *stop, const orbhip_gba_out *out)
+{
+    if (int rc = gba_args(cam, rows, cap, np, pcap, t, inv_level_sigma2, kf_list, nkf, pt_list, npt, iterations, mode, max_points, max_edges, out))
+        return rc;
+    const uint8_t *kf_bad = (const uint8_t *)t->kf_bad;
+    const int32_t *kf_id = (const int32_t *)t->kf_id, *obs_start = (const int32_t *)t->obs_start;
+    const int32_t *obs_kf = (const int32_t *)t->obs_kf, *obs_idx = (const int32_t *)t->obs_idx;
+    const orbhip_keypoint *kps = (const orbhip_keypoint *)t->kps;
+    const uint8_t *flags = (const uint8_t *)t->flags;
+    const size_t R = (size_t)rows, RC = R * cap, P = (size_t)pcap;
+    auto bad = [&](int r) { return kf_bad && kf_bad[r]; };
+    std::vector<uint8_t> listed(R, kf_list ? 0 : 1);
+    int max_kfid = 0;
+    if (kf_list)
+        for (int i = 0; i < nkf; ++i) {
+            const int r = kf_list[i];
+            if (r < 0 || r >= rows || listed[r]) { set_error("global_bundle_adjustment: kf_list[%d] is outside the bank or repeats a row", i); return ORBHIP_E_ARG; }
+            listed[r] = 1;
+        }
+    for (int r = 0; r < rows; ++r)
+        if (listed[r] && !bad(r) && kf_id[r] > max_kfid) max_kfid = kf_id[r];
+    if (pt_list)
+        for (int i = 0; i < npt; ++i)
+            if (pt_list[i] < 0 || pt_list[i] >= np) { set_error("global_bundle_adjustment: pt_list[%d] is outside [0, np)", i); return ORBHIP_E_ARG; }
+    if (obs_start[0] < 0) { set_error("global_bundle_adjustment: obs_start must start at 0 or above"); return ORBHIP_E_ARG; }
+    for (int p = 0; p < np; ++p)
+        if (obs_start[p + 1] < obs_start[p]) { set_error("global_bundle_adjustment: obs_start must be non-decreasing (entry %d)", p); return ORBHIP_E_ARG; }
+    const size_t total = (size_t)obs_start[np];
+    for (size_t o = (size_t)obs_start[0]; o < total; ++o) {
+        if (obs_kf[o] < 0 || obs_kf[o] >= rows || obs_idx[o] < 0 || obs_idx[o] >= cap) { set_error("global_bundle_adjustment: observation %zu is outside the bank", o); return ORBHIP_E_ARG; }
+        const int oct = kps[(size_t)obs_kf[o] * cap + obs_idx[o]].octave;
+        if (oct < 0 || oct >= cam->n_levels) { set_error("global_bundle_adjustment: observation %zu names a key point of octave %d", o, oct); return ORBHIP_E_ARG; }
+    }
+    for (int i = 0; i < (pt_list ? npt : np); ++i) {                         // a null vertex: optimizer.vertex(pKF->mnId) of a row not listed
+        const int p = pt_list ? pt_list[i] : i;
+        if (!(flags[p] & ORBHIP_POINT_PRESENT)) continue;
+        for (int o = obs_start[p]; o < obs_start[p + 1]; ++o) {
+            const int r = obs_kf[o];
+            if (!bad(r) && kf_id[r] <= max_kfid && !listed[r]) { set_error("global_bundle_adjustment: point %d is observed by row %d, which is not listed (a null vertex)", p, r); return ORBHIP_E_ARG; }
+        }
+    }
+    if (!m) return ORBHIP_E_ARG;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const size_t MP = (size_t)max_points, NK = kf_list ? (size_t)nkf : 0, NP = pt_list ? (size_t)npt : 0;
+    const bool staged = mode == ORBHIP_GBA_STAGED;
+    Stage st;
+    int rc;
+    const size_t in_bytes = al256(R) + al256(R * 4) + al256(((size_t)np + 1) * 4) + 2 * al256(total * 4 + 4) + al256(P + 1) +
+                            al256(RC * sizeof(orbhip_keypoint)) + al256(RC * 4) + al256(NK * 4 + 4) + al256(NP * 4 + 4) + 256;
+    const size_t out_size = 2 * al256(R * 48) + 2 * al256(P * 12 + 12) + al256(R) + al256(P + 1) + al256(MP * 4) + al256(64);
+    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
+    const int32_t zero = 0;
+    const uint8_t zb = 0;
+    const float fz[3] = {0.f, 0.f, 0.f};
+    orbhip_gba_tables dt;
+    dt.kf_bad = kf_bad ? st.put(kf_bad, R) : nullptr; dt.kf_id = st.put(kf_id, R);
+    dt.obs_start = st.put(obs_start, (size_t)np + 1);
+    dt.obs_kf = total ? st.put(obs_kf, total) : st.put(&zero, 1); dt.obs_idx = total ? st.put(obs_idx, total) : st.put(&zero, 1);
+    dt.flags = P ? st.put(flags, P) : st.put(&zb, 1); dt.kps = st.put(kps, RC);
+    dt.u_right = t->u_right ? st.put((const float *)t->u_right, RC) : nullptr;
+    const int32_t *d_kfl = kf_list ? (NK ? st.put(kf_list, NK) : st.put(&zero, 1)) : nullptr;
+    const int32_t *d_ptl = pt_list ? (NP ? st.put(pt_list, NP) : st.put(&zero, 1)) : nullptr;
+    const uint8_t *d_stop = stop ? st.put(stop, 1) : nullptr;
+    const size_t out_off = st.off;
+    const float *d_Tcw = st.put((const float *)t->Tcw, R * 12);
+    const float *d_world = P ? st.put((const float *)t->world, P * 3) : st.put(fz, 3);
+    const float *d_TG = nullptr, *d_pG = nullptr;
+    const uint8_t *d_km = nullptr, *d_pm = nullptr;
+    const int32_t *d_pl = nullptr;
+    if (staged) {
+        d_TG = st.put((const float *)out->TcwGBA, R * 12); d_pG = P ? st.put((const float *)out->posGBA, P * 3) : st.put(fz, 3);
+        d_km = st.put((const uint8_t *)out->kf_mark, R); d_pm = P ? st.put((const uint8_t *)out->pt_mark, P) : st.put(&zb, 1);
+    } else {
+        d_pl = st.put((const int32_t *)out->point_list, MP);
+    }
+    const int32_t *d_rep = st.put((const int32_t *)out->report, 16);
+    const size_t out_bytes = st.off - out_off;
+    dt.Tcw = (void *)d_Tcw; dt.world = (void *)d_world;
+    orbhip_gba_out dout;
+    dout.TcwGBA = (void *)d_TG; dout.posGBA = (void *)d_pG; dout.kf_mark = (void *)d_km; dout.pt_mark = (void *)d_pm;
+    dout.point_list = (void *)d_pl; dout.report = (void *)d_rep;
+    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = gba_launch(m, cam, rows, cap, np, pcap, &dt, inv_level_sigma2, d_kfl, nkf, d_ptl, npt, iterations, robust, mode, max_points,
+                         max_edges, d_stop, &dout)))
+        return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
+    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
+    back(out->report, d_rep, 64);
+    if (staged) {
+        back(out->TcwGBA, d_TG, R * 48); back(out->kf_mark, d_km, R);
+        if (P) { back(out->posGBA, d_pG, P * 12); back(out->pt_mark, d_pm, P); }
+    } else {
+        back(t->Tcw, d_Tcw, R * 48); back(out->point_list, d_pl, MP * 4);
+        if (P) back(t->world, d_world, P * 12);
+    }
+    return ORBHIP_OK;
+}
+
+int orbhip_global_bundle_adjustment_counters(orbhip_matcher *m, int32_t counters[2])
+{
+    if (!m || !counters) return ORBHIP_E_ARG;
+    counters[0] = m->gba_counters[0]; counters[1] = m->gba_counters[1];
+    return ORBHIP_OK;
+}
+
+static int gba_apply_args(int n_origins, int rows, int pcap, const orbhip_gba_apply *a)
+{
+    if (rows < 1 || pcap < 0 || n_origins < 0) return ORBHIP_E_ARG;
+    if (!a || (n_origins > 0 && !a->origins) || !a->parent || !a->kf_mark || !a->TcwGBA || !a->Tcw || !a->TcwBefGBA || !a->report ||
+        (pcap > 0 && (!a->pt_mark || !a->posGBA || !a->flags || !a->ref_kf || !a->world)))
+        return ORBHIP_E_ARG;
+    if (rows > 4096) { set_error("apply_global_ba: rows %d exceeds 4096", rows); return ORBHIP_E_CAPACITY; }
+    return ORBHIP_OK;
+}
+
+static int gba_apply_launch(orbhip_matcher *m, int n_origins, int rows, int pcap, const orbhip_gba_apply *a)
+{
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    GbaApply A;
+    memset(&A, 0, sizeof(A));
+    A.origins = (const int *)a->origins; A.parent = (const int *)a->parent; A.kf_bad = (const uint8_t *)a->kf_bad;
+    A.kf_mark = (uint8_t *)a->kf_mark; A.TcwGBA = (float *)a->TcwGBA; A.Tcw = (float *)a->Tcw; A.TcwBef = (float *)a->TcwBefGBA;
+    A.pt_mark = (const uint8_t *)a->pt_mark; A.flags = (const uint8_t *)a->flags; A.posGBA = (const float *)a->posGBA;
+    A.ref_kf = (const int *)a->ref_kf; A.world = (float *)a->world; A.o_report = (int *)a->report;
+    A.n_origins = n_origins; A.rows = rows; A.pcap = pcap;
+    void *ws;
+    if (int rc = scratch(m, S_GBAAPPLY, gba_apply_workspace_bytes(A), &ws)) return rc;
+    return launch_apply_global_ba(m->stream, A, ws);
+}
+
+int orbhip_apply_global_ba_device(orbhip_matcher *m, int n_origins, int rows, int pcap, const orbhip_gba_apply *a)
+{
+    if (int rc = gba_apply_args(n_origins, rows, pcap, a)) return rc;
+    if (!m) return ORBHIP_E_ARG;
+    return gba_apply_launch(m, n_origins, rows, pcap, a);
+}
+
+int orbhip_apply_global_ba(orbhip_matcher *m, int n_origins, int rows, int pcap, const orbhip_gba_apply *a)
+{
+    if (int rc = gba_apply_args(n_origins, rows, pcap, a)) return rc;
+    const int32_t *origins = (const int32_t *)a->origins, *parent = (const int32_t *)a->parent, *ref_kf = (const int32_t *)a->ref_kf;
+    const uint8_t *kf_bad = (const uint8_t *)a->kf_bad, *kf_mark = (const uint8_t *)a->kf_mark;
+    for (int i = 0; i < n_origins; ++i) {
+        const int r = origins[i];
+        if (r < 0 || r >= rows || (kf_bad && kf_bad[r]) || !kf_mark[r]) { set_error("apply_global_ba: origin %d must be a marked row of the map", i); return ORBHIP_E_ARG; }
+    }
+    for (int r = 0; r < rows; ++r)
+        if (parent[r] < -1 || parent[r] >= rows) { set_error("apply_global_ba: parent[%d] is outside [-1, rows)", r); return ORBHIP_E_ARG; }
+    for (int p = 0; p < pcap; ++p)
+        if (ref_kf[p] < -1 || ref_kf[p] >= rows) { set_error("apply_global_ba: point %d names a reference row outside [-1, rows)", p); return ORBHIP_E_ARG; }
+    if (!m) return ORBHIP_E_ARG;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    const size_t R = (size_t)rows, P = (size_t)pcap, NO = (size_t)n_origins;
+    Stage st;
+    int rc;
+    const size_t in_bytes = al256(NO * 4 + 4) + al256(R * 4) + al256(R) + 2 * al256(P + 1) + al256(P * 12 + 12) + al256(P * 4 + 4) + 256;
+    const size_t out_size = al256(R) + 3 * al256(R * 48) + al256(P * 12 + 12) + al256(32);
+    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
+    const int32_t zero = 0;
+    const uint8_t zb = 0;
+    const float fz[3] = {0.f, 0.f, 0.f};
+    orbhip_gba_apply d;
+    d.origins = NO ? st.put(origins, NO) : st.put(&zero, 1); d.parent = st.put(parent, R);
+    d.kf_bad = kf_bad ? st.put(kf_bad, R) : nullptr;
+    d.pt_mark = P ? st.put((const uint8_t *)a->pt_mark, P) : st.put(&zb, 1);
+    d.posGBA = P ? st.put((const float *)a->posGBA, P * 3) : st.put(fz, 3);
+    d.flags = P ? st.put((const uint8_t *)a->flags, P) : st.put(&zb, 1);
+    d.ref_kf = P ? st.put(ref_kf, P) : st.put(&zero, 1);
+    const size_t out_off = st.off;
+    const uint8_t *d_km = st.put(kf_mark, R);
+    const float *d_TG = st.put((const float *)a->TcwGBA, R * 12), *d_T = st.put((const float *)a->Tcw, R * 12);
+    const float *d_TB = st.put((const float *)a->TcwBefGBA, R * 12);
+    const float *d_world = P ? st.put((const float *)a->world, P * 3) : st.put(fz, 3);
+    const int32_t *d_rep = st.put((const int32_t *)a->report, 8);
+    const size_t out_bytes = st.off - out_off;
+    d.kf_mark = (void *)d_km; d.TcwGBA = (void *)d_TG; d.Tcw = (void *)d_T; d.TcwBefGBA = (void *)d_TB; d.world = (void *)d_world;
+    d.report = (void *)d_rep;
+    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = gba_apply_launch(m, n_origins, rows, pcap, &d))) return rc;
+    const uint8_t *h;
+    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
+    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
+    back(a->kf_mark, d_km, R); back(a->TcwGBA, d_TG, R * 48); back(a->Tcw, d_T, R * 48); back(a->TcwBefGBA, d_TB, R * 48);
+    back(a->report, d_rep, 32);
+    if (P) back(a->world, d_world, P * 12);
     return ORBHIP_OK;
 }
 

@@ -1127,6 +1127,116 @@ class ORBmatcher:
         check(self._lib.orbhip_optimize_essential_graph_counters(self._h, ptr(c)), "orbhip_optimize_essential_graph_counters")
         return int(c[0]), int(c[1])
 
+    # -- global bundle adjustment (src/Optimizer.cc:41-237, src/LoopClosing.cc:676-737) ----
+    GBA_TABLES = tuple(k for k, _ in capi.GbaTables._fields_)
+    GBA_OUT = tuple(k for k, _ in capi.GbaOut._fields_)
+    GBA_APPLY = tuple(k for k, _ in capi.GbaApply._fields_)
+    _GBA_DTYPES = dict(kf_bad=np.uint8, kf_id=np.int32, obs_start=np.int32, obs_kf=np.int32, obs_idx=np.int32, flags=np.uint8,
+                       kps=capi.KP_DTYPE, u_right=np.float32, Tcw=np.float32, world=np.float32)
+    _GBA_APPLY_DTYPES = dict(origins=np.int32, parent=np.int32, kf_bad=np.uint8, pt_mark=np.uint8, posGBA=np.float32, flags=np.uint8,
+                             ref_kf=np.int32, kf_mark=np.uint8, TcwGBA=np.float32, Tcw=np.float32, world=np.float32,
+                             TcwBefGBA=np.float32, report=np.int32)
+
+    def GlobalBundleAdjustmentDevice(self, cam, rows, cap, np_, pcap, tables, inv_level_sigma2, iterations, robust, mode, max_points,
+                                     max_edges, out, d_kf_list=None, nkf=0, d_pt_list=None, npt=0, d_stop=None):
+        """Optimizer::BundleAdjustment over device arrays (orbhip_global_bundle_adjustment_device in include/orbhip.h); with both
+        lists None it is GlobalBundleAdjustemnt.  `tables` and `out` are dicts with the keys of GBA_TABLES / GBA_OUT holding
+        device addresses (ints, or tensors); kf_bad and u_right may be None, and so may the outputs of the other mode
+        (capi.GBA_IN_PLACE writes Tcw, world and point_list; capi.GBA_STAGED writes TcwGBA, posGBA and the marks).  The call
+        synchronises the matcher's stream once per Levenberg-Marquardt trial; when it returns the outputs are written."""
+        sig = self._sigma2(inv_level_sigma2, cam)
+        rt = self._record(capi.GbaTables, tables, optional=("kf_bad", "u_right"))
+        ro = self._record(capi.GbaOut, out, optional=("TcwGBA", "posGBA", "kf_mark", "pt_mark", "point_list"))
+        dp = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a)  # noqa: E731
+        check(self._lib.orbhip_global_bundle_adjustment_device(self._h, C.byref(cam), int(rows), int(cap), int(np_), int(pcap),
+                                                               C.byref(rt), ptr(sig), dp(d_kf_list), int(nkf), dp(d_pt_list), int(npt),
+                                                               int(iterations), int(bool(robust)), int(mode), int(max_points),
+                                                               int(max_edges), dp(d_stop), C.byref(ro)),
+              "orbhip_global_bundle_adjustment_device")
+
+    def GlobalBundleAdjustment(self, tables, cam, inv_level_sigma2, iterations, robust, mode, max_points, max_edges, kf_list=None,
+                               pt_list=None, stop=None, out=None, fill=0):
+        """The same from host arrays in one staged copy, the call and one read-back (orbhip_global_bundle_adjustment), range-checked
+        (OrbHipError with E_ARG; also for a null vertex).  `tables`: dict with the keys of GBA_TABLES (kf_bad [rows] or None, kf_id
+        [rows], obs_start [np+1], obs_kf, obs_idx, flags [pcap], kps [rows, cap] KP_DTYPE, u_right [rows, cap] or None, Tcw
+        [rows, 12], world [pcap, 3]); kf_list / pt_list: None or the lists; stop: None or the value of the stop byte; out: None or
+        a dict with the caller's TcwGBA, posGBA, kf_mark, pt_mark to start from (STAGED).  Returns dict(Tcw, world, TcwGBA, posGBA,
+        kf_mark, pt_mark, point_list [max_points], report [16] in the order of capi.GBA_REPORT): copies, what the call does not
+        write holds the input / `fill` bytes."""
+        T = {}
+        for k in self.GBA_TABLES:
+            if tables.get(k) is None:
+                if k in ("kf_bad", "u_right"):
+                    T[k] = None
+                    continue
+                raise ValueError("tables[%r] is missing" % k)
+            T[k] = np.array(tables[k], self._GBA_DTYPES[k], order="C") if k in ("Tcw", "world") else \
+                np.ascontiguousarray(tables[k], self._GBA_DTYPES[k])
+        rows, cap = T["kps"].shape
+        n_pts, pcap = len(T["obs_start"]) - 1, len(T["flags"])
+        T["Tcw"], T["world"] = T["Tcw"].reshape(rows, 12), T["world"].reshape(pcap, 3)
+        sig = self._sigma2(inv_level_sigma2, cam)
+        raw = lambda count, dt: np.full(max(count, 1) * np.dtype(dt).itemsize, fill, np.uint8).view(dt)  # noqa: E731
+        O = dict(TcwGBA=raw(rows * 12, np.float32), posGBA=raw(pcap * 3, np.float32), kf_mark=raw(rows, np.uint8),
+                 pt_mark=raw(pcap, np.uint8), point_list=raw(max_points, np.int32), report=raw(16, np.int32))
+        for k in ("TcwGBA", "posGBA", "kf_mark", "pt_mark"):
+            if out is not None and out.get(k) is not None:
+                src = np.ascontiguousarray(out[k], O[k].dtype).reshape(-1)
+                O[k][:len(src)] = src
+        keep = {k: (None if a is None else (np.zeros(4, a.dtype) if a.size == 0 else a)) for k, a in T.items()}
+        rt = self._record(capi.GbaTables, {k: (None if a is None else ptr(a).value) for k, a in keep.items()}, optional=("kf_bad", "u_right"))
+        ro = self._record(capi.GbaOut, {k: ptr(a).value for k, a in O.items()})
+        kl = None if kf_list is None else np.ascontiguousarray(kf_list, np.int32).reshape(-1)
+        pl = None if pt_list is None else np.ascontiguousarray(pt_list, np.int32).reshape(-1)
+        pad = [None if a is None else (np.zeros(4, np.int32) if a.size == 0 else a) for a in (kl, pl)]
+        sb = None if stop is None else np.array([stop], np.uint8)
+        check(self._lib.orbhip_global_bundle_adjustment(self._h, C.byref(cam), rows, cap, n_pts, pcap, C.byref(rt), ptr(sig), ptr(pad[0]),
+                                                        0 if kl is None else len(kl), ptr(pad[1]), 0 if pl is None else len(pl),
+                                                        int(iterations), int(bool(robust)), int(mode), int(max_points), int(max_edges),
+                                                        ptr(sb), C.byref(ro)), "orbhip_global_bundle_adjustment")
+        return dict(Tcw=keep["Tcw"].copy(), world=T["world"].copy(), TcwGBA=O["TcwGBA"][:rows * 12].reshape(rows, 12).copy(),
+                    posGBA=O["posGBA"][:pcap * 3].reshape(pcap, 3).copy(), kf_mark=O["kf_mark"][:rows].copy(),
+                    pt_mark=O["pt_mark"][:pcap].copy(), point_list=O["point_list"][:max_points].copy(), report=O["report"].copy())
+
+    def GlobalBACounters(self):
+        """(stream synchronisations, kernel launches) of this matcher's last GlobalBundleAdjustment* call."""
+        c = np.zeros(2, np.int32)
+        check(self._lib.orbhip_global_bundle_adjustment_counters(self._h, ptr(c)), "orbhip_global_bundle_adjustment_counters")
+        return int(c[0]), int(c[1])
+
+    def ApplyGlobalBADevice(self, n_origins, rows, pcap, arrays):
+        """The map update after a staged global bundle adjustment (orbhip_apply_global_ba_device in include/orbhip.h): `arrays` is a
+        dict with the keys of GBA_APPLY holding device addresses (ints, or tensors); kf_bad may be None, and with pcap == 0 so may
+        the point arrays.  Asynchronous on the matcher's stream, two launches."""
+        optional = ("kf_bad",) + (("pt_mark", "posGBA", "flags", "ref_kf", "world") if pcap == 0 else ()) + (("origins",) if n_origins == 0 else ())
+        rec = self._record(capi.GbaApply, arrays, optional=optional)
+        check(self._lib.orbhip_apply_global_ba_device(self._h, int(n_origins), int(rows), int(pcap), C.byref(rec)),
+              "orbhip_apply_global_ba_device")
+
+    def ApplyGlobalBA(self, arrays, fill=0):
+        """The same from host arrays (orbhip_apply_global_ba), range-checked (OrbHipError with E_ARG).  `arrays`: dict with origins
+        [n_origins], parent [rows], kf_bad [rows] or None, kf_mark [rows], TcwGBA / Tcw [rows, 12], pt_mark, flags, ref_kf [pcap],
+        posGBA / world [pcap, 3].  Returns dict(kf_mark, TcwGBA, Tcw, world, TcwBefGBA [rows, 12], report [8] in the order of
+        capi.GBA_APPLY_REPORT): copies, what the call does not write holds the input / `fill` bytes."""
+        A = {}
+        for k in self.GBA_APPLY:
+            if k in ("TcwBefGBA", "report"):
+                continue
+            if arrays.get(k) is None:
+                if k == "kf_bad":
+                    A[k] = None
+                    continue
+                raise ValueError("arrays[%r] is missing" % k)
+            A[k] = np.array(arrays[k], self._GBA_APPLY_DTYPES[k], order="C").reshape(-1)
+        rows, pcap, n_origins = len(A["parent"]), len(A["flags"]), len(A["origins"])
+        A["TcwBefGBA"] = np.full(rows * 48, fill, np.uint8).view(np.float32)
+        A["report"] = np.full(32, fill, np.uint8).view(np.int32)
+        keep = {k: (None if a is None else (np.zeros(4, a.dtype) if a.size == 0 else a)) for k, a in A.items()}
+        rec = self._record(capi.GbaApply, {k: (None if a is None else ptr(a).value) for k, a in keep.items()}, optional=("kf_bad",))
+        check(self._lib.orbhip_apply_global_ba(self._h, n_origins, rows, pcap, C.byref(rec)), "orbhip_apply_global_ba")
+        return dict(kf_mark=A["kf_mark"].copy(), TcwGBA=A["TcwGBA"].reshape(rows, 12).copy(), Tcw=A["Tcw"].reshape(rows, 12).copy(),
+                    world=A["world"].reshape(pcap, 3).copy(), TcwBefGBA=A["TcwBefGBA"].reshape(rows, 12).copy(), report=A["report"].copy())
+
     # -- device-resident, batched SearchByProjection ---------------------------
     def set_stream(self, stream):
         check(self._lib.orbhip_matcher_set_stream(self._h, stream), "orbhip_matcher_set_stream")

@@ -48,8 +48,8 @@ def scene():
 
 def kernel_split(path):
     groups = dict(linearisation=("k_eg_eval", "k_eg_blocks", "k_eg_vertex", "k_eg_lm_begin"), system=("k_eg_zero", "k_eg_scatter"),
-                  factorisation=("k_eg_factor_diag", "k_eg_factor_panel", "k_eg_factor_trail"),
-                  substitution=("k_eg_fwd_diag", "k_eg_fwd_upd", "k_eg_dscale", "k_eg_bwd_diag", "k_eg_bwd_upd"),
+                  factorisation=("k_factor_diag", "k_factor_panel", "k_factor_trail"),          # orbhip_ldlt.h, instantiated over EgView
+                  substitution=("k_fwd_diag", "k_fwd_upd", "k_dscale", "k_bwd_diag", "k_bwd_upd"),
                   rest=("k_eg_setup", "k_eg_update", "k_eg_trial", "k_eg_judge", "k_eg_finish"))
     per = {}
     for row in csv.DictReader(open(path)):
@@ -57,7 +57,7 @@ def kernel_split(path):
         total = row.get("TotalDurationNs") or row.get("TotalDuration(ns)") or row.get("TotalDurationNS")
         calls = row.get("Calls") or row.get("Count")
         for k in sum(groups.values(), ()):
-            if k + "E" in name or k + "(" in name or name.endswith(k):
+            if k + "E" in name or k + "(" in name or k + "<" in name or k + "I" in name or name.endswith(k):
                 per[k] = {"calls": int(calls), "us": float(total) / 1e3}
     out = {g: {"us": sum(per[k]["us"] for k in ks if k in per), "launches": sum(per[k]["calls"] for k in ks if k in per)} for g, ks in groups.items()}
     return {"per_kernel": per, "groups": out, "from": "rocprofv3 --kernel-trace --stats of one call in a run of its own (tracing slows the host; "
