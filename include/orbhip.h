@@ -1666,6 +1666,13 @@ int orbhip_create_new_map_points(orbhip_matcher *m, const orbhip_frame_view *cur
 /* Launch on a caller-owned hipStream_t (NULL: the handle's own stream); wait for the handle's stream. */
 int orbhip_matcher_set_stream(orbhip_matcher *m, void *stream);
 int orbhip_matcher_sync(orbhip_matcher *m);
+/* Test hook: overwrite the handle's workspaces with `byte` (0 .. 255).  Every allocated device scratch slot is filled on the
+ * handle's stream, ordered after earlier calls and before later ones; then, after a stream synchronise, the pinned staging
+ * and read-back buffers and the pinned state records of the essential-graph and global-bundle-adjustment calls.  The two
+ * slots that cache a host-built table (the RANSAC iteration tables of the Sim3 and PnP setup calls) are invalidated, so the
+ * next setup call uploads its table again.  No slot carries state from one public call to the next, so none is excluded.
+ * bytes_filled (nullable): the number of bytes written.  Every call of this header must give the same results after it. */
+int orbhip_matcher_fill_scratch(orbhip_matcher *m, int byte, unsigned long long *bytes_filled);
 
 /* Frame::ComputeStereoMatches.  The image pyramids are the ones left in the two extractor
  * handles by their last extract call (frame indices frame_l / frame_r of those batches), i.e.

@@ -3787,6 +3787,30 @@ static int scratch(orbhip_matcher *m, int slot, size_t bytes, void **out)
     return ORBHIP_OK;
 }
 
+// Test hook (include/orbhip.h): every byte a later call could find in the handle's workspaces becomes `byte`.  The device
+// slots are filled on the handle's stream, the pinned buffers once it drained.  The two slots that cache a host-built table
+// (S_SIM3LIM, S_PNPTAB) lose their keys, so the next setup call uploads the table again.
+int orbhip_matcher_fill_scratch(orbhip_matcher *m, int byte, unsigned long long *bytes_filled)
+{
+    if (!m || byte < 0 || byte > 255) return ORBHIP_E_ARG;
+    ORBHIP_HIP_CHECK(hipSetDevice(m->device));
+    unsigned long long total = 0;
+    for (size_t i = 0; i < sizeof(m->buf) / sizeof(m->buf[0]); ++i) {
+        if (!m->buf[i]) continue;
+        ORBHIP_HIP_CHECK(hipMemsetAsync(m->buf[i], byte, m->cap[i], m->stream));
+        total += m->cap[i];
+    }
+    ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
+    if (m->h_stage) { memset(m->h_stage, byte, m->h_stage_bytes); total += m->h_stage_bytes; }
+    if (m->h_out) { memset(m->h_out, byte, m->h_out_bytes); total += m->h_out_bytes; }
+    if (m->h_eg) { memset(m->h_eg, byte, sizeof(EgState)); total += sizeof(EgState); }
+    if (m->h_gba) { memset(m->h_gba, byte, sizeof(LbaState)); total += sizeof(LbaState); }
+    m->sim3_cap = -1;
+    m->pnp_cap = -1;
+    if (bytes_filled) *bytes_filled = total;
+    return ORBHIP_OK;
+}
+
 // ---- the host side of the frame grid ---------------------------------------------------------------------------------
 // Frame::ComputeImageBounds / mfGridElement{Width,Height}Inv (src/Frame.cc:99-100) from a camera's bounds
 struct GridInv { float w, h; };

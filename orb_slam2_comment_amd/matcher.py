@@ -1244,6 +1244,13 @@ class ORBmatcher:
     def sync(self):
         check(self._lib.orbhip_matcher_sync(self._h), "orbhip_matcher_sync")
 
+    def FillScratch(self, byte):
+        """Test hook (orbhip_matcher_fill_scratch in include/orbhip.h): every workspace of the handle is overwritten with `byte`;
+        returns the number of bytes filled.  No call's result may depend on it."""
+        n = C.c_ulonglong(0)
+        check(self._lib.orbhip_matcher_fill_scratch(self._h, int(byte), C.byref(n)), "orbhip_matcher_fill_scratch")
+        return int(n.value)
+
     def SearchByProjectionFrameDevice(self, pairs, d_kps, d_desc, d_n, cap, bounds, d_q, d_qdesc, d_nq, qcap, d_assign,
                                       d_nmatches, d_u_right=0, d_taken=0):
         """All d_* are device pointers (ints).  bounds = (mnMinX, mnMinY, mnMaxX, mnMaxY)."""

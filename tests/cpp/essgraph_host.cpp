@@ -1,7 +1,8 @@
 // Host build of orbhip_essgraph_core.h: one thread replays what the kernels do, so its outputs must equal those of
 // tests/seqref/essgraph.py bit for bit (tests/test_essgraph_cpu.py builds this with g++ -ffp-contract=off and runs it, also
 // under -fsanitize=address,undefined).
-//   essgraph_host <in> <out>   in:  int32 header[16] = {rows, pcap, cur, loop_row, fix_scale, max_edges, entries of loop_kf,
+//   essgraph_host <in> <out> [fill]   the optional trailing argument is the byte (0 .. 255, default 0) the workspace holds before the run
+//                              in:   int32 header[16] = {rows, pcap, cur, loop_row, fix_scale, max_edges, entries of loop_kf,
 //                                   entries of lc_kf, max trials to dump, 0 ...}, then kf_bad, kf_id, parent, conn_w, ord_kf,
 //                                   ord_w, n_ord, loop_start, loop_kf, lc_start, lc_kf, corrected, non_corrected,
 //                                   in_corrected, in_non_corrected, flags, ref_kf, corrected_by_kf, corrected_ref, Tcw, world
@@ -51,7 +52,8 @@ template <class T> static void emit(FILE *f, const T *p, size_t count)
 
 int main(int argc, char **argv)
 {
-    if (argc != 3) { fprintf(stderr, "usage: essgraph_host <in> <out>\n"); return 2; }
+    if (argc != 3 && argc != 4) { fprintf(stderr, "usage: essgraph_host <in> <out> [fill]\n"); return 2; }
+    const uint8_t fill = argc == 4 ? (uint8_t)strtol(argv[3], nullptr, 0) : 0;
     std::vector<unsigned char> in = slurp(argv[1]);
     Cursor c{in, 0};
     const std::vector<int32_t> h = c.take<int32_t>(16);
@@ -83,7 +85,7 @@ int main(int argc, char **argv)
     W.cref = cref.data(); W.Tcw = Tcw.data(); W.world = world.data(); W.o_point_list = point_list.data();
     W.o_Scw = Scw.data(); W.o_Swc = Swc.data(); W.o_report = report.data();
     W.rows = rows; W.pcap = pcap; W.cur = h[2]; W.loop_row = h[3]; W.fix_scale = h[4]; W.max_edges = max_edges;
-    std::vector<uint8_t> ws(eg_carve(W, nullptr) + 256);
+    std::vector<uint8_t> ws(eg_carve(W, nullptr) + 256, fill);
     eg_carve(W, ws.data() + (256 - (size_t)ws.data() % 256) % 256);
     std::vector<double> tried((size_t)max_trials * eg_mk(W) * 8 + 1, 0.0);
     EgHostTrace trace;

@@ -1,5 +1,6 @@
 // Host build of orbhip_gba_core.h: one thread replays what the kernels do, so its outputs must equal those of
 // tests/seqref/gba.py bit for bit (tests/test_gba_cpu.py builds this with g++ -ffp-contract=off and runs it).
+//   gba_host ba|apply <in> <out> [fill]   the optional trailing argument is the byte (0 .. 255, default 0) the workspace holds before the run
 //   gba_host ba <in> <out>      in:  int32 header[24] = {rows, cap, np, pcap, n_levels, max_points, max_edges, has kf_bad,
 //                                    has u_right, has stop, script length, has kf_list, nkf, has pt_list, npt, iterations, robust,
 //                                    mode, 0...}, float cam[5] = fx, fy, cx, cy, bf, float inv_level_sigma2[n_levels], then
@@ -52,7 +53,7 @@ template <class T> static void emit(FILE *f, const std::vector<T> &v)
 
 static uint8_t *aligned(std::vector<uint8_t> &ws) { return ws.data() + (256 - (size_t)ws.data() % 256) % 256; }
 
-static int run_ba(Cursor &c, FILE *out)
+static int run_ba(Cursor &c, FILE *out, uint8_t fill)
 {
     const std::vector<int32_t> h = c.take<int32_t>(24);
     const int rows = h[0], cap = h[1], np = h[2], pcap = h[3], n_levels = h[4], max_points = h[5], max_edges = h[6];
@@ -95,7 +96,7 @@ static int run_ba(Cursor &c, FILE *out)
     G.mode = h[17];
     G.TcwGBA = TcwGBA.data(); G.posGBA = posGBA.data(); G.kf_mark = kf_mark.data(); G.pt_mark = pt_mark.data();
     G.o_point_list = point_list.data(); G.o_report = report.data();
-    std::vector<uint8_t> ws(gba_carve(G, nullptr) + 256);
+    std::vector<uint8_t> ws(gba_carve(G, nullptr) + 256, fill);
     gba_carve(G, aligned(ws));
     gba_host_run(G);
     emit(out, Tcw); emit(out, world); emit(out, TcwGBA); emit(out, posGBA); emit(out, kf_mark); emit(out, pt_mark); emit(out, point_list);
@@ -103,7 +104,7 @@ static int run_ba(Cursor &c, FILE *out)
     return 0;
 }
 
-static int run_apply(Cursor &c, FILE *out)
+static int run_apply(Cursor &c, FILE *out, uint8_t fill)
 {
     const std::vector<int32_t> h = c.take<int32_t>(8);
     const int rows = h[0], pcap = h[1], n_origins = h[2];
@@ -125,7 +126,7 @@ static int run_apply(Cursor &c, FILE *out)
     A.TcwGBA = TcwGBA.data(); A.Tcw = Tcw.data(); A.TcwBef = bef.data(); A.pt_mark = pt_mark.data(); A.flags = flags.data();
     A.posGBA = posGBA.data(); A.ref_kf = ref_kf.data(); A.world = world.data(); A.o_report = report.data();
     A.n_origins = n_origins; A.rows = rows; A.pcap = pcap;
-    std::vector<uint8_t> ws(gba_apply_carve(A, nullptr) + 256);
+    std::vector<uint8_t> ws(gba_apply_carve(A, nullptr) + 256, fill);
     gba_apply_carve(A, aligned(ws));
     gba_apply_host(A);
     emit(out, kf_mark); emit(out, TcwGBA); emit(out, Tcw); emit(out, world); emit(out, bef); emit(out, report);
@@ -134,12 +135,16 @@ static int run_apply(Cursor &c, FILE *out)
 
 int main(int argc, char **argv)
 {
-    if (argc != 4 || (strcmp(argv[1], "ba") && strcmp(argv[1], "apply"))) { fprintf(stderr, "usage: gba_host ba|apply <in> <out>\n"); return 2; }
+    if ((argc != 4 && argc != 5) || (strcmp(argv[1], "ba") && strcmp(argv[1], "apply"))) {
+        fprintf(stderr, "usage: gba_host ba|apply <in> <out> [fill]\n");
+        return 2;
+    }
+    const uint8_t fill = argc == 5 ? (uint8_t)strtol(argv[4], nullptr, 0) : 0;
     std::vector<unsigned char> in = slurp(argv[2]);
     Cursor c{in, 0};
     FILE *out = fopen(argv[3], "wb");
     if (!out) { perror(argv[3]); return 2; }
-    const int rc = strcmp(argv[1], "ba") ? run_apply(c, out) : run_ba(c, out);
+    const int rc = strcmp(argv[1], "ba") ? run_apply(c, out, fill) : run_ba(c, out, fill);
     fclose(out);
     return rc;
 }

@@ -1,6 +1,7 @@
 // Host build of orbhip_lba_core.h: one thread replays what the phase kernels do, so its outputs must equal those of
 // tests/seqref/lba.py bit for bit (tests/test_lba_cpu.py builds this with g++ -ffp-contract=off and runs it).
-//   lba_host <in> <out>   in:  int32 header[16] = {cur, id0_row, rows, cap, np, pcap, n_levels, max_points, max_edges,
+//   lba_host <in> <out> [fill]   the optional trailing argument is the byte (0 .. 255, default 0) the workspace holds before the run
+//                         in:   int32 header[16] = {cur, id0_row, rows, cap, np, pcap, n_levels, max_points, max_edges,
 //                              has kf_bad, has u_right, has stop, script length, 0, 0, 0}, float cam[5] = fx, fy, cx, cy, bf,
 //                              float inv_level_sigma2[n_levels], then slot_point, n, [kf_bad], obs_start, obs_kf, obs_idx,
 //                              flags, kps, [u_right], ord_kf, n_ord, Tcw, world as the C ABI lays them out, uint8
@@ -51,7 +52,8 @@ template <class T> static void emit(FILE *f, const T *p, size_t count)
 
 int main(int argc, char **argv)
 {
-    if (argc != 3) { fprintf(stderr, "usage: lba_host <in> <out>\n"); return 2; }
+    if (argc != 3 && argc != 4) { fprintf(stderr, "usage: lba_host <in> <out> [fill]\n"); return 2; }
+    const uint8_t fill = argc == 4 ? (uint8_t)strtol(argv[3], nullptr, 0) : 0;
     std::vector<unsigned char> in = slurp(argv[1]);
     Cursor c{in, 0};
     const std::vector<int32_t> h = c.take<int32_t>(16);
@@ -90,7 +92,7 @@ int main(int argc, char **argv)
     W.cam.delta_stereo = (double)(float)std::sqrt(7.815);
     W.cur = h[0]; W.id0_row = h[1]; W.rows = rows; W.cap = cap; W.np = np; W.pcap = pcap; W.n_levels = n_levels;
     W.max_points = max_points; W.max_edges = max_edges;
-    std::vector<uint8_t> ws(lba_carve(W, nullptr) + 256);
+    std::vector<uint8_t> ws(lba_carve(W, nullptr) + 256, fill);
     lba_carve(W, ws.data() + (256 - (size_t)ws.data() % 256) % 256);
     const size_t snap = R * 7 + (size_t)max_points * 3;
     std::vector<double> tr(4 * snap, 0.0);

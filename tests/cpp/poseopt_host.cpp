@@ -1,5 +1,7 @@
 // Host build of orbhip_poseopt_core.h: one thread replays what a device team does, so its outputs must equal those of
 // tests/seqref/poseopt.py bit for bit (tests/test_poseopt_cpu.py builds this with g++ -ffp-contract=off and runs it).
+//   poseopt_host run|classify <in> <out> [fill]   the optional trailing argument is the byte (0 .. 255, default 0) the workspace holds before the run: the team's record PoWs (its two
+//                                    emitted estimates start at zero all the same) and the edge lists e_slot, e_pt, e_out
 //   poseopt_host run <in> <out>      in:  int32 header {frames, cap, wrows, pcap, has u_right, has world_row, has point_flags,
 //                                         has discarded, n_levels, mode, flags}, float cam[5] = fx, fy, cx, cy, bf,
 //                                         float inv_level_sigma2[n_levels], then kps, n, [u_right], world, [point_flags],
@@ -53,7 +55,8 @@ template <class T> static void emit(FILE *f, const T *p, size_t count)
 
 int main(int argc, char **argv)
 {
-    if (argc != 4) { fprintf(stderr, "usage: poseopt_host run|classify|sincos <in> <out>\n"); return 2; }
+    if (argc != 4 && argc != 5) { fprintf(stderr, "usage: poseopt_host run|classify|sincos <in> <out> [fill]\n"); return 2; }
+    const uint8_t fill = argc == 5 ? (uint8_t)strtol(argv[4], nullptr, 0) : 0;
     std::vector<unsigned char> in = slurp(argv[2]);
     FILE *out = fopen(argv[3], "wb");
     if (!out) { perror(argv[3]); return 2; }
@@ -92,8 +95,12 @@ int main(int argc, char **argv)
     std::vector<int32_t> report(Fn * 8, 0);
     std::vector<uint16_t> e_slot(cap);
     std::vector<int> e_pt(cap);
-    std::vector<uint8_t> e_out(cap);
+    std::vector<uint8_t> e_out(cap, fill);
+    memset(e_slot.data(), fill, e_slot.size() * sizeof(uint16_t));
+    memset(e_pt.data(), fill, e_pt.size() * sizeof(int));
     static PoWs W;
+    memset(&W, fill, sizeof(W));
+    for (int k = 0; k < 7; ++k) W.est[k] = W.tried[k] = 0.0;
     for (int f = 0; f < frames; ++f) {
         const int r = row ? row[f] : 0;
         if (r < 0 || r >= wrows || n[f] < 0 || n[f] > cap) return 2;

@@ -11,6 +11,8 @@
 //                                         round (s3o_classify) of candidate 0 with that state
 //                                    out: uint8 e_out[cap], int32 matched12[cap], int32 removed, int32 pairs
 //   sim3opt_host exp <in> <out>      in: doubles; out: det_exp64 of each
+//   run and classify take an optional trailing argument: the byte (0 .. 255, default 0) that the team's record S3oWs (its two
+//   emitted estimates start at zero all the same) and the pair lists e_slot, e_i2, e_p2, e_out hold before the run
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -54,7 +56,8 @@ template <class T> static void emit(FILE *f, const T *p, size_t count)
 
 int main(int argc, char **argv)
 {
-    if (argc != 4) { fprintf(stderr, "usage: sim3opt_host run|classify|exp <in> <out>\n"); return 2; }
+    if (argc != 4 && argc != 5) { fprintf(stderr, "usage: sim3opt_host run|classify|exp <in> <out> [fill]\n"); return 2; }
+    const uint8_t fill = argc == 5 ? (uint8_t)strtol(argv[4], nullptr, 0) : 0;
     std::vector<unsigned char> in = slurp(argv[2]);
     FILE *out = fopen(argv[3], "wb");
     if (!out) { perror(argv[3]); return 2; }
@@ -98,8 +101,12 @@ int main(int argc, char **argv)
     T.rows = rows; T.cap = cap; T.np = np; T.cur = cur; T.match_form = match_form;
     std::vector<uint16_t> e_slot(cap), e_i2(cap);
     std::vector<int> e_p2(cap);
-    std::vector<uint8_t> e_out(cap);
+    std::vector<uint8_t> e_out(cap, fill);
+    memset(e_slot.data(), fill, e_slot.size() * sizeof(uint16_t));
+    memset(e_i2.data(), fill, e_i2.size() * sizeof(uint16_t));
+    memset(e_p2.data(), fill, e_p2.size() * sizeof(int));
     static S3oWs W;
+    memset(&W, fill, sizeof(W));
     for (int k = 0; k < 8; ++k) W.est[k] = W.tried[k] = 0.0;
     for (int cd = 0; cd < C; ++cd) {
         if (h[9] && !select[cd]) { report[(size_t)cd * 8] = ORBHIP_SIM3OPT_SKIPPED; continue; }

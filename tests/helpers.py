@@ -4,6 +4,16 @@ import numpy as np
 from orb_slam2_comment_amd.synth import synth_frame, synth_stereo  # noqa: F401
 
 
+FILLS = (0x00, 0xA5, 0xFF)        # what a workspace holds before a run: zeros, large negative ints / finite garbage, -1 / NaN
+
+
+def with_fills(names):
+    """(name, fill) parameters for the host builds of the shared cores: every case with every byte of FILLS in its
+    workspace.  The zero fill keeps the case's plain id."""
+    import pytest
+    return [pytest.param(n, f, id=str(n) if f == 0 else "%s-fill%02X" % (n, f)) for n in names for f in FILLS]
+
+
 def has_gpu():
     try:
         import torch

@@ -31,6 +31,7 @@ import tempfile
 import numpy as np
 import pytest
 
+from helpers import FILLS, with_fills
 from seqref import essgraph as E
 from seqref.poseopt import quat_from_R, to_R
 from seqref.sim3opt import sim3_exp, sim3_inverse, sim3_mul
@@ -486,10 +487,10 @@ def unpack(b, raw):
     return got, off
 
 
-def run_host(b, tmp_path, tag, sanitize=False):
+def run_host(b, tmp_path, tag, sanitize=False, fill=0):
     fin, fout = tmp_path / (tag + ".in"), tmp_path / (tag + ".out")
     fin.write_bytes(pack(b, prefilled(b), max_trials=200))
-    subprocess.run([host_program(sanitize), str(fin), str(fout)], check=True)
+    subprocess.run([host_program(sanitize), str(fin), str(fout), str(fill)], check=True)
     raw = fout.read_bytes()
     got, off = unpack(b, raw)
     nt = int(np.frombuffer(raw, i32, 1, off)[0])
@@ -497,10 +498,11 @@ def run_host(b, tmp_path, tag, sanitize=False):
     return got
 
 
-@pytest.mark.parametrize("name", CASES + ["singular"])
-def test_host_build_matches_seqref(name, tmp_path):
+@pytest.mark.parametrize("name,fill", with_fills(CASES + ["singular"]))
+def test_host_build_matches_seqref(name, fill, tmp_path):
+    """`fill`: the byte the workspace holds before the run (the device's slot is never cleared)."""
     b, ref = case(name), reference(name)
-    got = run_host(b, tmp_path, name)
+    got = run_host(b, tmp_path, name, fill=fill)
     assert_same(got, ref, name, nan_ok=name == "singular")
     tried = ref["info"].get("tried", [])
     want = np.array(tried, f64).reshape(len(tried), -1, 8) if tried else np.zeros((0, 0, 8))
@@ -515,8 +517,9 @@ def test_host_program_runs_clean_under_asan_and_ubsan(tmp_path):
     for name in CASES + ["singular"]:
         if name in SLOW:
             continue
-        got = run_host(case(name), tmp_path, "san_" + name, sanitize=True)
-        assert_same(got, reference(name), name, nan_ok=name == "singular")
+        for fill in FILLS:
+            got = run_host(case(name), tmp_path, "san_" + name, sanitize=True, fill=fill)
+            assert_same(got, reference(name), (name, fill), nan_ok=name == "singular")
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 
 import test_lba_cpu as K
+from helpers import with_fills
 from seqref import gba as G
 from seqref import lba as L
 from seqref import poseopt as Q
@@ -518,18 +519,19 @@ def unpack(b, raw):
     return got
 
 
-def run_host(b, tmp_path, tag, script="case"):
+def run_host(b, tmp_path, tag, script="case", fill=0):
     if script == "case":
         script = None if b["stop"] is None else [b["stop"]]
     fin, fout = tmp_path / (tag + ".in"), tmp_path / (tag + ".out")
     fin.write_bytes(pack(b, prefilled(b), script))
-    subprocess.run([host_program(), "ba", str(fin), str(fout)], check=True)
+    subprocess.run([host_program(), "ba", str(fin), str(fout), str(fill)], check=True)
     return unpack(b, fout.read_bytes())
 
 
-@pytest.mark.parametrize("name", CASES)
-def test_host_build_matches_seqref(name, tmp_path):
-    assert_same(run_host(case(name), tmp_path, name), reference(name), name)
+@pytest.mark.parametrize("name,fill", with_fills(CASES))
+def test_host_build_matches_seqref(name, fill, tmp_path):
+    """`fill`: the byte the workspace holds before the run (the device's slot is never cleared)."""
+    assert_same(run_host(case(name), tmp_path, name, fill=fill), reference(name), name)
 
 
 @pytest.mark.parametrize("script", [[0, 1], [0, 0, 1, 0], [0, 0, 0, 1], [0] * 6 + [1], [1], [0]])
@@ -643,13 +645,13 @@ def pack_apply(a, o):
     return b"".join(np.ascontiguousarray(p).tobytes() for p in parts)
 
 
-@pytest.mark.parametrize("name", ["tree", "no_bad"])
-def test_host_build_of_the_apply_step_matches_seqref(name, tmp_path):
+@pytest.mark.parametrize("name,fill", with_fills(["tree", "no_bad"]))
+def test_host_build_of_the_apply_step_matches_seqref(name, fill, tmp_path):
     a = apply_case(name)
     rows, pcap = len(a["parent"]), len(a["flags"])
     fin, fout = tmp_path / "a.in", tmp_path / "a.out"
     fin.write_bytes(pack_apply(a, apply_prefilled(a)))
-    subprocess.run([host_program(), "apply", str(fin), str(fout)], check=True)
+    subprocess.run([host_program(), "apply", str(fin), str(fout), str(fill)], check=True)
     raw, off, got = fout.read_bytes(), 0, {}
     for k, dt, cnt in (("kf_mark", u8, rows), ("TcwGBA", f32, rows * 12), ("Tcw", f32, rows * 12), ("world", f32, pcap * 3),
                        ("TcwBefGBA", f32, rows * 12), ("report", i32, 8)):

@@ -19,6 +19,7 @@ import tempfile
 import numpy as np
 import pytest
 
+from helpers import with_fills
 from seqref import lba as L
 from seqref import poseopt as Q
 
@@ -694,13 +695,13 @@ def pack(b, o, script):
     return b"".join(np.ascontiguousarray(p).tobytes() for p in parts)
 
 
-def run_host(b, tmp_path, tag, script="case"):
+def run_host(b, tmp_path, tag, script="case", fill=0):
     if script == "case":
         script = None if b["stop"] is None else [b["stop"]]
     o = prefilled(b)
     fin, fout = tmp_path / (tag + ".in"), tmp_path / (tag + ".out")
     fin.write_bytes(pack(b, o, script))
-    subprocess.run([host_program(), str(fin), str(fout)], check=True)
+    subprocess.run([host_program(), str(fin), str(fout), str(fill)], check=True)
     raw = fout.read_bytes()
     off = 0
     got = {}
@@ -726,10 +727,11 @@ def _trace_rows(b, r, tr, what, rnd):
     return out
 
 
-@pytest.mark.parametrize("name", CASES)
-def test_host_build_matches_seqref(name, tmp_path):
+@pytest.mark.parametrize("name,fill", with_fills(CASES))
+def test_host_build_matches_seqref(name, fill, tmp_path):
+    """`fill`: the byte the workspace holds before the run (the device's slot is never cleared)."""
     b = case(name)
-    got = run_host(b, tmp_path, name)
+    got = run_host(b, tmp_path, name, fill=fill)
     assert_same(got, reference(name), name)
     tr = {}
     r = run_seqref(b, trace=tr)

@@ -24,6 +24,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import with_fills
 from seqref import poseopt as Q
 
 f32, f64, i32, u8 = np.float32, np.float64, np.int32, np.uint8
@@ -683,12 +684,12 @@ def pack(b, o):
     return b"".join(np.ascontiguousarray(p).tobytes() for p in parts)
 
 
-def run_host(name, tmp_path):
+def run_host(name, tmp_path, fill=0):
     b = case(name)
     o = prefilled(b)
     fin, fout = tmp_path / (name + ".in"), tmp_path / (name + ".out")
     fin.write_bytes(pack(b, o))
-    subprocess.run([host_program(), "run", str(fin), str(fout)], check=True)
+    subprocess.run([host_program(), "run", str(fin), str(fout), str(fill)], check=True)
     raw = fout.read_bytes()
     off = 0
     for k in ("Tcw", "frame_point", "outlier", "discarded", "report"):
@@ -700,9 +701,10 @@ def run_host(name, tmp_path):
     return o
 
 
-@pytest.mark.parametrize("name", CASES)
-def test_host_build_matches_seqref(name, tmp_path):
-    assert_same(run_host(name, tmp_path), reference(name), name)
+@pytest.mark.parametrize("name,fill", with_fills(CASES))
+def test_host_build_matches_seqref(name, fill, tmp_path):
+    """`fill`: the byte the team's record and the compacted lists hold before the run (on the device they are LDS and registers)."""
+    assert_same(run_host(name, tmp_path, fill), reference(name), name)
 
 
 def test_host_build_writes_the_last_tried_estimate(tmp_path):

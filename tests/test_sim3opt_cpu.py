@@ -24,6 +24,7 @@ import pytest
 
 import test_sim3_cpu as K
 from orb_slam2_comment_amd import capi
+from helpers import with_fills
 from seqref import sim3 as S3
 from seqref import sim3opt as Q
 
@@ -658,11 +659,11 @@ def prefilled(sc, form):
                 report=np.full(Cn * 32, SENTINEL, u8).view(i32).reshape(Cn, 8).copy())
 
 
-def run_host(sc, sim3, form, fix_scale, select, tmp_path, tag):
+def run_host(sc, sim3, form, fix_scale, select, tmp_path, tag, fill=0):
     o = prefilled(sc, form)
     fin, fout = tmp_path / (tag + ".in"), tmp_path / (tag + ".out")
     fin.write_bytes(pack(sc, sim3, form, fix_scale, select, o))
-    subprocess.run([host_program(), "run", str(fin), str(fout)], check=True)
+    subprocess.run([host_program(), "run", str(fin), str(fout), str(fill)], check=True)
     raw = fout.read_bytes()
     off = 0
     for k in ("matched12", "S12", "Scw", "report"):
@@ -678,11 +679,12 @@ HOST_CASES = [("A", S3.MATCH_POINTS, False, None), ("A", S3.MATCH_SLOTS, True, N
               ("B", S3.MATCH_POINTS, False, None), ("B", S3.MATCH_POINTS, True, None), ("A_alone", S3.MATCH_POINTS, False, None)]
 
 
-@pytest.mark.parametrize("k", range(len(HOST_CASES)))
-def test_host_build_matches_seqref(k, tmp_path):
+@pytest.mark.parametrize("k,fill", with_fills(range(len(HOST_CASES))))
+def test_host_build_matches_seqref(k, fill, tmp_path):
+    """`fill`: the byte the team's record and the compacted lists hold before the run (on the device they are LDS and registers)."""
     name, form, fix, select = HOST_CASES[k]
     sc, sim3 = case(name)
-    assert_same(run_host(sc, sim3, form, fix, select, tmp_path, "c%d" % k), reference(name, form, fix, select), HOST_CASES[k])
+    assert_same(run_host(sc, sim3, form, fix, select, tmp_path, "c%d" % k, fill), reference(name, form, fix, select), HOST_CASES[k])
 
 
 def test_host_build_on_the_hand_cases(tmp_path):
