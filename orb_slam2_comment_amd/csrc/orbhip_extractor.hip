@@ -606,7 +606,10 @@ __global__ __launch_bounds__(256) void k_remap(const uint8_t *__restrict__ src, 
 }
 
 constexpr int kSubMax = 72;              // max (wCell+6), (hCell+6)
-constexpr int kFastStageU = 12;         // k_fast_cells: row groups per staging batch (48 rows of a stride <= 16 dwords)
+#ifdef ORBHIP_DEVTOOLS
+constexpr int kFastStageU = 12;          // kFastStageBatch: row groups per staging batch (48 rows of a stride <= 16 dwords)
+#endif
+constexpr int kFastDenseU = 8;           // kFastStageDense: row groups in flight per lane
 constexpr int kFastLdsPerCu = 160 * 1024;  // gfx950
 constexpr int kFastLdsGranule = 1280;      // LDS is handed out in 1280-byte granules on gfx950 (tools/micro/lds_oob.hip: a 4 KB request owns 5 KB)
 constexpr int kFastLead = 1;             // k_fast_cells: LDS column of sub-image x is x + kFastLead + 4
@@ -617,9 +620,13 @@ __device__ __forceinline__ int max3i(int a, int b, int c) { return max(max(a, b)
 // ---------------------------------------------------------------------------
 // K2+K3: FAST-9/16 + NMS, one WAVEFRONT per reference cell (= the reference's cv::FAST call(s) for
 // that cell, ORBextractor.cc:789-829); 64-thread workgroups, every hand-off is wave-local.
-//  1. staging: the (wCell+6)x(hCell+6) sub-image goes to LDS as aligned dwords; lane = (row mod RPI,
-//     dword column), the row advance is scalar.  The LDS row stride SW is a template parameter, so
-//     every LDS access of the hot loops is "one base register + immediate offset".
+//  1. staging: the (wCell+6)x(hCell+6) sub-image goes to LDS as aligned dwords, SW per row, by LDS-DMA
+//     (global_load_lds_dword): lane = row * SW + dword column, so the 64 / SW rows of one instruction
+//     are one contiguous run of LDS dwords behind a scalar base (M0); ceil(rows / (64 / SW))
+//     instructions, the last one based at rows - 64 / SW (it restages the rows it shares with the
+//     one before it with the same bytes), no data register and no LDS store.  The wave's own
+//     vmcnt(0) orders the first LDS read behind them.  The LDS row stride SW is a template
+//     parameter, so every LDS access of the hot loops is "one base register + immediate offset".
 //  2. dense compass pre-test at the pass threshold (ring pixels 0,4,8,12: an arc of 9 holds one pixel
 //     of every opposite pair), 4 px per lane, on packed uint16 WITHOUT unpacking: a dword of four
 //     pixels is read as two uint16 lanes whose high bytes are pixels 1 and 3 -- the low byte only
@@ -698,7 +705,7 @@ __device__ __forceinline__ unsigned long long stamp_now()
 #ifndef ORBHIP_FAST_WAVES
 #define ORBHIP_FAST_WAVES 8   // resident waves per SIMD = what the LDS share of bind_geometry admits (32 workgroups per CU)
 #endif
-template <int SW, bool STAMPS = false>
+template <int SW, bool STAMPS = false, int STAGE = kFastStage>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORBHIP_FAST_WAVES, ORBHIP_FAST_WAVES))) void k_fast_cells(const uint8_t *__restrict__ pyr, const FastCell *__restrict__ cells,
                                                     int *__restrict__ cell_cnt, uint32_t *__restrict__ cell_kp,
                                                     FastParams P, const uint8_t *__restrict__ images, size_t frame_stride)
@@ -706,9 +713,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORBHIP_FAST_
     extern __shared__ uint32_t lds[];
     constexpr int SB = SW * 4;                 // bytes per staged row
     constexpr int SS = SB - 8;                 // bytes per score-map row (detection width + 2 halo bytes fit: dw + 2 <= sw - 4)
-    constexpr int LPR = SW <= 16 ? 16 : 32;    // lanes per staged row
-    constexpr int RPI = 64 / LPR;              // rows per staging instruction
-    constexpr int U = kFastStageU;             // staging loads in flight per lane
+    constexpr int RPI = 64 / SW;               // rows per staging instruction; lanes >= RPI * SW stage nothing
     uint32_t *simg = lds;                                   // staged sub-image, LDS col 0 = global column gxb - 4
     uint32_t *sscore = simg + P.img_words;                   // score map with a 1-px zero halo
     typedef __attribute__((address_space(3))) unsigned short lds_u16;
@@ -745,39 +750,93 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORBHIP_FAST_
     if (P.dev == 3) { if (lane == 0) cell_cnt[out_cell] = 0; return; }   // timing floor: launch + prologue only
 #endif
     // LDS column of sub-image x: col = x + a + 4 (a = misalignment of x0; the dword on the left holds real pixels).
-    // Lane = (row mod RPI, dword column); a batch is U row groups, all loads issued before the first LDS store.  Row
-    // groups past the sub-image re-read its last rows (scalar clamp) into LDS rows that nothing looks at.
+    // Lane = row * SW + dword column: a row group is RPI whole rows = one contiguous run of RPI * SW LDS dwords.  The
+    // sub-image takes ceil(sh / RPI) groups; the last one starts at row sh - RPI (scalar clamp; sh >= 7 > RPI) and
+    // restages the rows it shares with the group before it with the same bytes.  No row past the cell is read and no
+    // LDS row past sh is written.
     // A staged row is SW dwords from column x0 - 5 whatever the cell's width: at a narrow last cell of a row of cells it
     // runs past the level's right edge, into frame bytes that an extraction does not write.  Those are LDS columns
     // >= sw + 5; the compares read LDS columns [5, sw + 5) only (detection columns [8, 8 + dw) and their radius-3 ring),
     // and the pixels of a row's last group beyond the detection rectangle are masked (en[]): no such byte reaches a compare.
     {
-        const int c = lane & (LPR - 1), r = lane / LPR;
         // level-0 cells of a handle that does not materialise mvImagePyramid[0] read the caller's image itself (a FAST
-        // sub-image never reaches the REFLECT_101 frame: the cell grid starts 13 px inside the level)
+        // sub-image never reaches the REFLECT_101 frame: the cell grid starts 13 px inside the level); its rows start at
+        // any byte offset, which the DMA serves exactly like an ordinary dword load (tools/micro/glds_unaligned.hip)
         const uint8_t *sb = cd.img ? images + (size_t)fr * frame_stride + cd.src_off : pyr + (size_t)fr * P.frame_bytes + cd.src_off;
-        const uint32_t voff = (uint32_t)(__mul24(r, pitch) + 4 * c);
-        uint32_t *sdst = simg + (r * SW + c);
-        if (c < SW) {
-            for (int r0 = 0; r0 < sh; r0 += RPI * U) {
-                uint32_t v[U];
+#ifdef ORBHIP_DEVTOOLS
+        if constexpr (STAGE == kFastStageBatch) {
+            // lane = (row mod RPB, dword column), 16 or 32 lanes per row; whole batches of U row groups, the groups past
+            // the sub-image re-read its last row into LDS rows that nothing looks at (bind_geometry makes room for them)
+            constexpr int LPR = SW <= 16 ? 16 : 32, RPB = 64 / LPR, U = kFastStageU;
+            const int c = lane & (LPR - 1), r = lane / LPR;
+            const uint32_t voff = (uint32_t)(__mul24(r, pitch) + 4 * c);
+            uint32_t *sdst = simg + (r * SW + c);
+            if (c < SW) {
+                for (int r0 = 0; r0 < sh; r0 += RPB * U) {
+                    uint32_t v[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u)
-                    v[u] = *reinterpret_cast<const uint32_t *>(sb + (uint32_t)(min(r0 + u * RPI, sh - 1) * pitch) + voff);
+                    for (int u = 0; u < U; ++u)
+                        v[u] = *reinterpret_cast<const uint32_t *>(sb + (uint32_t)(min(r0 + u * RPB, sh - 1) * pitch) + voff);
 #pragma unroll
-                for (int u = 0; u < U; ++u) sdst[(r0 + u * RPI) * SW] = v[u];
+                    for (int u = 0; u < U; ++u) sdst[(r0 + u * RPB) * SW] = v[u];
+                }
+            }
+        } else
+#endif
+        {
+            const int r = lane / SW, c = lane - r * SW;
+            const uint32_t voff = (uint32_t)(__mul24(r, pitch) + 4 * c);
+            const int ngroups = (sh + RPI - 1) / RPI, last = sh - RPI;
+            if (lane < RPI * SW) {
+                if constexpr (STAGE == kFastStageDma) {
+                    // the global address is a scalar base plus the lane's 32-bit offset, the LDS address a scalar (M0);
+                    // masked-off lanes leave their LDS dwords alone (tools/micro/glds_unaligned.hip).
+                    // Written as an instruction: __builtin_amdgcn_global_load_lds never takes the scalar-base form here (it
+                    // adds base and offset with a 64-bit vector add per DMA and addresses through the VGPR pair).  M0 belongs to
+                    // the compiler, so the statement that writes it reads it and puts the old value back.  The compiler does
+                    // not count these loads: the s_waitcnt below is theirs.
+                    const uint32_t img_lds = (uint32_t)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint32_t *)simg);
+                    for (int g = 0; g < ngroups; ++g) {
+                        const int row = min(g * RPI, last);
+                        const uintptr_t rowp = reinterpret_cast<uintptr_t>(sb) + (uint32_t)(row * pitch);
+                        uint32_t keep;
+                        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
+                                     : "=&s"(keep) : "v"(voff), "s"(rowp), "s"(img_lds + (uint32_t)(row * SB)) : "memory");
+                    }
+                } else {
+                    // batches of U groups, all loads issued before the first LDS store; only a sub-image's last group
+                    // can need the clamp, and the last batch may be short (wave-uniform guards)
+                    constexpr int U = kFastDenseU;
+                    uint32_t *sdst = simg + lane;
+                    int g0 = 0;
+                    for (; g0 + U <= ngroups; g0 += U) {
+                        uint32_t v[U];
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const int row = u == U - 1 ? min((g0 + u) * RPI, last) : (g0 + u) * RPI;
+                            v[u] = *reinterpret_cast<const uint32_t *>(sb + (uint32_t)(row * pitch) + voff);
+                        }
+#pragma unroll
+                        for (int u = 0; u < U; ++u) sdst[(u == U - 1 ? min((g0 + u) * RPI, last) : (g0 + u) * RPI) * SW] = v[u];
+                    }
+                    if (g0 < ngroups) {
+                        uint32_t v[U - 1];
+#pragma unroll
+                        for (int u = 0; u < U - 1; ++u)
+                            if (g0 + u < ngroups) v[u] = *reinterpret_cast<const uint32_t *>(sb + (uint32_t)(min((g0 + u) * RPI, last) * pitch) + voff);
+#pragma unroll
+                        for (int u = 0; u < U - 1; ++u)
+                            if (g0 + u < ngroups) sdst[min((g0 + u) * RPI, last) * SW] = v[u];
+                    }
+                }
             }
         }
     }
     // score-map clear, 16 bytes per lane (the map starts on a 16-byte boundary: img_words is a multiple of 4; the last
     // store may run a few bytes into the survivor list, which nothing has written yet)
     for (int i = lane; i < ((dh + 2) * SS + 15) / 16; i += 64) reinterpret_cast<uint4 *>(sscore)[i] = make_uint4(0, 0, 0, 0);
-    __syncthreads();
-    FAST_STAMP(1);   // staging (global -> LDS) + score-map clear
-#ifdef ORBHIP_DEVTOOLS
-    if (P.dev == 4) { if (lane == 0) cell_cnt[out_cell] = (int)simg[lane] & 0; return; }   // timing floor: + staging
-#endif
 
+    // The loop constants come here, between the last DMA and the wait for it.
     // column groups: group g' covers LDS cols 8 + 4g' .. 8 + 4g' + 3; the detection columns are LDS cols [8, 8 + dw)
     // (every cell is staged with the same lead, bind_geometry: the first centre column sits on a dword boundary)
     static_assert(kFastLead + 4 + 3 == 8, "the first detection column is LDS column 8");
@@ -803,6 +862,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORBHIP_FAST_
         asm("s_ashr_i32 %0, %1, 31" : "=s"(half) : "s"(lj - j) : "scc");      // j > lj ? ~0 : 0
         en[j] = ((unsigned long long)half << 32) | half;
     }
+    // An LDS-DMA is ordered for this wave's LDS reads by nothing but its own vmcnt: a read issued early returns old LDS
+    // bytes without stalling.  The wait is written out, not left to the compiler's placement.
+    if constexpr (STAGE == kFastStageDma) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    FAST_STAMP(1);   // staging (global -> LDS) + score-map clear
+#ifdef ORBHIP_DEVTOOLS
+    if (P.dev == 4) { if (lane == 0) cell_cnt[out_cell] = (int)simg[lane] & 0; return; }   // timing floor: + staging
+#endif
     // The survivor list holds P.list_cap entries -- far fewer than the cell has pixels, so that 8 wavefronts per SIMD fit
     // the LDS.  It is the LAST array of the workgroup's LDS: entries past the end fall outside the allocation and are
     // dropped by the hardware's LDS range check (DS addresses are checked against the wavefront's LDS_SIZE: out-of-range
@@ -2161,6 +2228,53 @@ static FastCell make_fast_cell(const PyrGeom &G, const CellDesc &c, int img_stri
     return f;
 }
 
+// Dynamic LDS carve-up of k_fast_cells from the largest cell of the bound geometry: staged image, score map, survivor list
+static int fast_lds_layout(orbhip_extractor *e)
+{
+    int msh = 7, mdh = 1, mdw = 1, mndw = 2;
+    for (const CellDesc &c : e->cells) {
+        msh = std::max(msh, c.y1 - c.y0);
+        mdh = std::max(mdh, c.y1 - c.y0 - 6);
+        mdw = std::max(mdw, c.x1 - c.x0 - 6);
+        mndw = std::max(mndw, (kFastLead + (c.x1 - c.x0) + 3) >> 2);
+    }
+    FastLds &F2 = e->fast_lds;
+    // compile-time row stride (odd: rows rotate over the LDS banks): staged dwords + one real dword on the left
+    const int need = mndw + 1;
+    F2.strideW = need <= 11 ? 11 : need <= 13 ? 13 : need <= 15 ? 15 : need <= 17 ? 17 : 21;
+    if (need > 21) { set_error("cell geometry exceeds the FAST kernel limits"); return ORBHIP_E_SIZE; }
+    F2.scoreW = F2.strideW - 2;
+    F2.score_words = (mdh + 2) * F2.scoreW;
+    // the staging writes exactly the rows a cell has: the tallest cell's, rounded up to 16 bytes (the score map behind it is
+    // cleared 16 bytes at a time)
+    F2.img_words = (msh * F2.strideW + 3) & ~3;
+#ifdef ORBHIP_DEVTOOLS
+    if (e->fast_stage == kFastStageBatch) {   // that staging writes whole batches of row groups
+        const int lpr = F2.strideW <= 16 ? 16 : 32, rpi = 64 / lpr, rows_batch = rpi * kFastStageU;
+        F2.img_words = ((msh + rows_batch - 1) / rows_batch) * rows_batch * F2.strideW;
+    }
+#endif
+    // uint16 survivor list.  Every pixel of a cell may pass the pre-test, but few do: the list gets what is left of the
+    // LDS share that lets 32 workgroups (8 wavefronts per SIMD) live on a CU -- or of the next larger share that holds
+    // 128 entries and a whole row of the widest cell -- and the kernel repeats a round that overflows in row bands.
+    // It stays the last array of the allocation (k_fast_cells).
+    {
+        const int full = mdw * mdh, row_px = 4 * ((mdw + 3) >> 2), fixed = (F2.img_words + F2.score_words) * 4;
+        int cap = full;
+        for (int wgs = 32; wgs >= 4; wgs -= 4) {
+            const int share = kFastLdsPerCu / wgs / kFastLdsGranule * kFastLdsGranule;
+            const int room = (share - fixed) / 2 - 2;
+            if (room >= std::max(128, row_px)) { cap = std::min(full, room); break; }
+        }
+        F2.list_cap = cap;
+        F2.list_words = (cap + 1) / 2 + 1;
+    }
+    e->fast_lds_bytes = (F2.img_words + F2.score_words + F2.list_words) * 4;
+    FastParams &FP = e->fast_params;
+    FP.img_words = F2.img_words; FP.score_words = F2.score_words; FP.list_cap = F2.list_cap;
+    return ORBHIP_OK;
+}
+
 // Bind the handle to an image size: level geometry (:1111-1113), cell table (:769-829),
 // OpenCV resize tables, blur tiles.
 static int bind_geometry(orbhip_extractor *e, int rows, int cols)
@@ -2238,50 +2352,12 @@ static int bind_geometry(orbhip_extractor *e, int rows, int cols)
                 e->tiles.push_back(t);
             }
     }
-    {   // dynamic LDS carve-up of k_fast_cells from the largest cell of this geometry
-        int msh = 7, mdh = 1, mdw = 1, mndw = 2;
-        for (const CellDesc &c : e->cells) {
-            msh = std::max(msh, c.y1 - c.y0);
-            mdh = std::max(mdh, c.y1 - c.y0 - 6);
-            mdw = std::max(mdw, c.x1 - c.x0 - 6);
-            mndw = std::max(mndw, (kFastLead + (c.x1 - c.x0) + 3) >> 2);
-        }
-        FastLds &F2 = e->fast_lds;
-        // compile-time row stride (odd: rows rotate over the LDS banks): staged dwords + one real dword on the left
-        const int need = mndw + 1;
-        F2.strideW = need <= 11 ? 11 : need <= 13 ? 13 : need <= 15 ? 15 : need <= 17 ? 17 : 21;
-        if (need > 21) { set_error("cell geometry exceeds the FAST kernel limits"); return ORBHIP_E_SIZE; }
-        F2.scoreW = F2.strideW - 2;
-        F2.score_words = (mdh + 2) * F2.scoreW;
-        // staging batches write whole row groups: round the image rows up to what they touch
-        {
-            const int lpr = F2.strideW <= 16 ? 16 : 32, rpi = 64 / lpr, rows_batch = rpi * kFastStageU;
-            const int rows = ((msh + rows_batch - 1) / rows_batch) * rows_batch;
-            F2.img_words = rows * F2.strideW;
-        }
-        // uint16 survivor list.  Every pixel of a cell may pass the pre-test, but few do: the list gets what is left of the
-        // LDS share that lets 32 workgroups (8 wavefronts per SIMD) live on a CU -- or of the next larger share that holds
-        // 128 entries and a whole row of the widest cell -- and the kernel repeats a round that overflows in row bands
-        {
-            const int full = mdw * mdh, row_px = 4 * ((mdw + 3) >> 2), fixed = (F2.img_words + F2.score_words) * 4;
-            int cap = full;
-            for (int wgs = 32; wgs >= 4; wgs -= 4) {
-                const int share = kFastLdsPerCu / wgs / kFastLdsGranule * kFastLdsGranule;
-                const int room = (share - fixed) / 2 - 2;
-                if (room >= std::max(128, row_px)) { cap = std::min(full, room); break; }
-            }
-            F2.list_cap = cap;
-            F2.list_words = (cap + 1) / 2 + 1;
-        }
-        e->fast_lds_bytes = (F2.img_words + F2.score_words + F2.list_words) * 4;
-        e->cells2.clear();
-        for (const CellDesc &c : e->cells) e->cells2.push_back(make_fast_cell(G, c, 0));
-        e->cells_stride = 0;
-        FastParams &FP = e->fast_params;
-        memset(&FP, 0, sizeof(FP));
-        FP.img_words = F2.img_words; FP.score_words = F2.score_words; FP.list_cap = F2.list_cap;
-        FP.ini_th = G.ini_th; FP.min_th = G.min_th;
-    }
+    memset(&e->fast_params, 0, sizeof(e->fast_params));
+    if (int rc = fast_lds_layout(e)) return rc;
+    e->cells2.clear();
+    for (const CellDesc &c : e->cells) e->cells2.push_back(make_fast_cell(G, c, 0));
+    e->cells_stride = 0;
+    e->fast_params.ini_th = G.ini_th; e->fast_params.min_th = G.min_th;
     G.frame_bytes = off;
     G.ncells_total = (int)e->cells.size();
     G.slot_cap = slot_cap;
@@ -2513,21 +2589,28 @@ static int launch_pipeline(orbhip_extractor *e, const uint8_t *d_images, int bat
         if ((unsigned long long)G.ncells_total * G.ncells_total * (unsigned long long)batch >= (1ull << 32)) {
             set_error("batch too large for the FAST kernel's work mapping"); return ORBHIP_E_SIZE;
         }
-#define ORBHIP_FAST2(SWv) hipLaunchKernelGGL(k_fast_cells<SWv>, grid, dim3(64), lb, s, b_pyr, e->d_cells2, b_cell_cnt, b_cell_kp, P, d_images, frame_stride)
-#ifdef ORBHIP_DEVTOOLS
-        P.dev = e->fast_variant;
-        if (e->fast_variant == 2 && e->fast_lds.strideW == 11)   // stamped diagnostic build (tools/fast_ab.py)
-            hipLaunchKernelGGL((k_fast_cells<11, true>), grid, dim3(64), lb, s, b_pyr, e->d_cells2, b_cell_cnt, b_cell_kp, P, d_images, frame_stride);
-        else
-#endif
-        switch (e->fast_lds.strideW) {
-        case 11: ORBHIP_FAST2(11); break;
-        case 13: ORBHIP_FAST2(13); break;
-        case 15: ORBHIP_FAST2(15); break;
-        case 17: ORBHIP_FAST2(17); break;
-        default: ORBHIP_FAST2(21); break;
+#define ORBHIP_FAST3(SWv, STv, MDv) hipLaunchKernelGGL((k_fast_cells<SWv, STv, MDv>), grid, dim3(64), lb, s, b_pyr, e->d_cells2, b_cell_cnt, b_cell_kp, P, d_images, frame_stride)
+#define ORBHIP_FAST2(MDv) switch (e->fast_lds.strideW) { \
+        case 11: ORBHIP_FAST3(11, false, MDv); break; \
+        case 13: ORBHIP_FAST3(13, false, MDv); break; \
+        case 15: ORBHIP_FAST3(15, false, MDv); break; \
+        case 17: ORBHIP_FAST3(17, false, MDv); break; \
+        default: ORBHIP_FAST3(21, false, MDv); break; \
         }
+#ifdef ORBHIP_DEVTOOLS
+        P.dev = e->fast_variant % 10;
+        if (P.dev == 2 && e->fast_lds.strideW == 11) {   // stamped diagnostic build (tools/fast_ab.py)
+            if (e->fast_stage == kFastStageBatch) ORBHIP_FAST3(11, true, kFastStageBatch);
+            else if (e->fast_stage == kFastStageDense) ORBHIP_FAST3(11, true, kFastStageDense);
+            else ORBHIP_FAST3(11, true, kFastStageDma);
+        } else if (e->fast_stage == kFastStageBatch) { ORBHIP_FAST2(kFastStageBatch) }
+        else if (e->fast_stage == kFastStageDense) { ORBHIP_FAST2(kFastStageDense) }
+        else { ORBHIP_FAST2(kFastStageDma) }
+#else
+        ORBHIP_FAST2(kFastStage)
+#endif
 #undef ORBHIP_FAST2
+#undef ORBHIP_FAST3
     }
     ORBHIP_GATE_OUT(1);
     if (prof) (void)hipEventRecord(ev[2], s);
@@ -3455,7 +3538,17 @@ int orbhip_dev_set_octree_variant(orbhip_extractor *e, int v) { if (!e) return O
 int orbhip_dev_set_fast_variant(orbhip_extractor *e, int v)
 {
     if (!e) return ORBHIP_E_ARG;
-    e->fast_variant = v;                    // 0 product; 2 stamped diagnostic build; 3 / 4 exit after the prologue / after staging
+    // ones: 0 product; 2 stamped diagnostic build; 3 / 4 exit after the prologue / after staging.  Tens: the staging,
+    // 0 the product's, 1 whole batches of row groups (as before the dense layout), 2 dense through registers, 3 LDS-DMA
+    const int st = v / 10;
+    if (v < 0 || st > 3) return ORBHIP_E_ARG;
+    e->fast_variant = v;
+    e->fast_stage = st == 0 ? orbhip::kFastStage : st == 1 ? orbhip::kFastStageBatch : st == 2 ? orbhip::kFastStageDense : orbhip::kFastStageDma;
+    if (e->bound) {                         // the stagings size the LDS image differently
+        ORBHIP_HIP_CHECK(hipSetDevice(e->device));
+        ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
+        return fast_lds_layout(e);
+    }
     return ORBHIP_OK;
 }
 

@@ -17,6 +17,12 @@ struct FastLds {
     int img_words, score_words, list_words;
     int list_cap;     // survivor-list entries (uint16); a round with more survivors is repeated in row bands
 };
+// How k_fast_cells brings a cell's sub-image to LDS.  The product library has one way (kFastStage); development builds
+// instantiate the others beside it for tools/fast_ab.py (orbhip_dev_set_fast_variant).
+constexpr int kFastStageBatch = 0;       // lane = (row mod RPI, dword column) through registers, whole batches of row groups
+constexpr int kFastStageDense = 1;       // lane = row * SW + dword column through registers, exactly the cell's rows
+constexpr int kFastStageDma = 2;         // the same lanes and rows by global_load_lds_dword: no data register, no LDS store
+constexpr int kFastStage = kFastStageDma;
 // One FAST cell as k_fast_cells2 wants it: every derived quantity precomputed, one 32-byte scalar load per wavefront
 struct alignas(32) FastCell {
     uint32_t src_off;        // byte offset inside a frame's pyramid block of LDS (row 0, col 0): row y0, column gxb - 4
@@ -350,7 +356,8 @@ struct orbhip_extractor {
     int fast_lds_bytes = 0;
 #ifdef ORBHIP_DEVTOOLS
     int stage_mask = 31;        // development build (tools/coexec.py): stages launch_pipeline runs
-    int fast_variant = 0;       // development build (tools/fast_ab.py): 2 stamped build, 3 / 4 timing floors
+    int fast_variant = 0;       // development build (tools/fast_ab.py): ones 2 stamped build, 3 / 4 timing floors; tens the staging
+    int fast_stage = orbhip::kFastStage;   // staging of k_fast_cells selected by the tens of fast_variant (orbhip_dev_set_fast_variant)
     int octree_variant = 0;     // development build (tools/octree_ab.py): bit 0 workspace path for all, bit 1 stamped build
 #endif
     orbhip::CellDesc *d_cells = nullptr;

@@ -3,7 +3,12 @@
 rounds in ONE process (cdna_hip_programming.md section 5.4 rule 24).  Variants are the development switches
 exported only by the -DORBHIP_DEVTOOLS build (tools/_dev/liborbhip_dev.so, orbhip_dev_*), never part of the product library.
 
-  python tools/fast_ab.py [--rounds 8] [--frames 64] [--variants 1,0]
+  python tools/fast_ab.py [--rounds 8] [--frames 64] [--variants 10,20,30]
+
+A FAST variant is tens * 10 + ones.  Ones: 0 the whole kernel, 2 the stamped build (per-phase shares), 3 / 4 the timing
+floors (exit after the prologue / after the staging).  Tens: how a cell reaches LDS -- 0 the product's way, 1 whole batches
+of row groups with lane = (row mod RPI, dword column), 2 exactly the cell's rows with lane = row * SW + column through
+registers, 3 the same by LDS-DMA.
 """
 import argparse
 import ctypes as C
@@ -77,7 +82,7 @@ def main():
         sig = (d_n.cpu().numpy().copy(), d_d.cpu().numpy().copy(), d_k.cpu().numpy().copy())
         if ref is None:
             ref = sig
-        elif v < 3 or v >= 1000:
+        elif v % 10 < 3 or v >= 1000:
             n = ref[0]
             same = np.array_equal(n, sig[0]) and all(np.array_equal(ref[1][b, :n[b]], sig[1][b, :n[b]]) and
                                                       np.array_equal(ref[2][b, :n[b]], sig[2][b, :n[b]]) for b in range(B))
@@ -95,8 +100,10 @@ def main():
             res[v].append(ext.stage_times_us())
             ext.set_profiling(False)
     out = {}
-    if 2 in variants:                          # stamped diagnostic build: shares of the wave lifetime per phase
-        L.orbhip_dev_set_fast_variant(ext._h, 2)
+    for v in variants:                         # stamped diagnostic builds: shares of the wave lifetime per phase
+        if v >= 1000 or v % 10 != 2:
+            continue
+        L.orbhip_dev_set_fast_variant(ext._h, v)
         z = (C.c_ulonglong * 8)()
         torch.cuda.synchronize()
         L.orbhip_dev_fast_stamps(z)
@@ -106,7 +113,7 @@ def main():
         waves = max(1, z[7])
         names = ["prologue", "staging", "dense", "score", "nms_emit"]
         tot = float(sum(z[i] for i in range(5)))
-        print(json.dumps({"stamps_cycles_per_wave": {names[i]: round(z[i] / waves, 1) for i in range(5)},
+        print(json.dumps({"variant": v, "stamps_cycles_per_wave": {names[i]: round(z[i] / waves, 1) for i in range(5)},
                           "shares": {names[i]: round(z[i] / tot, 3) for i in range(5)}, "waves": int(waves)}), file=sys.stderr)
     for v in variants:
         out[str(v)] = {k: {"median": round(float(np.median([r[k] for r in res[v]])), 2),
