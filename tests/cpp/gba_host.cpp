@@ -53,7 +53,7 @@ template <class T> static void emit(FILE *f, const std::vector<T> &v)
 
 static uint8_t *aligned(std::vector<uint8_t> &ws) { return ws.data() + (256 - (size_t)ws.data() % 256) % 256; }
 
-static int run_ba(Cursor &c, FILE *out, uint8_t fill)
+static int run_ba(Cursor &c, FILE *out, uint8_t fill, bool state)
 {
     const std::vector<int32_t> h = c.take<int32_t>(24);
     const int rows = h[0], cap = h[1], np = h[2], pcap = h[3], n_levels = h[4], max_points = h[5], max_edges = h[6];
@@ -101,6 +101,7 @@ static int run_ba(Cursor &c, FILE *out, uint8_t fill)
     gba_host_run(G);
     emit(out, Tcw); emit(out, world); emit(out, TcwGBA); emit(out, posGBA); emit(out, kf_mark); emit(out, pt_mark); emit(out, point_list);
     emit(out, report);
+    if (state) emit(out, std::vector<double>{W.S->lam, W.S->rho, W.S->current});   // where the last trial left Levenberg-Marquardt
     return 0;
 }
 
@@ -135,16 +136,16 @@ static int run_apply(Cursor &c, FILE *out, uint8_t fill)
 
 int main(int argc, char **argv)
 {
-    if ((argc != 4 && argc != 5) || (strcmp(argv[1], "ba") && strcmp(argv[1], "apply"))) {
-        fprintf(stderr, "usage: gba_host ba|apply <in> <out> [fill]\n");
+    if ((argc < 4 || argc > 6) || (strcmp(argv[1], "ba") && strcmp(argv[1], "apply"))) {
+        fprintf(stderr, "usage: gba_host ba|apply <in> <out> [fill [state]]\n");
         return 2;
     }
-    const uint8_t fill = argc == 5 ? (uint8_t)strtol(argv[4], nullptr, 0) : 0;
+    const uint8_t fill = argc >= 5 ? (uint8_t)strtol(argv[4], nullptr, 0) : 0;
     std::vector<unsigned char> in = slurp(argv[2]);
     Cursor c{in, 0};
     FILE *out = fopen(argv[3], "wb");
     if (!out) { perror(argv[3]); return 2; }
-    const int rc = strcmp(argv[1], "ba") ? run_apply(c, out, fill) : run_ba(c, out, fill);
+    const int rc = strcmp(argv[1], "ba") ? run_apply(c, out, fill) : run_ba(c, out, fill, argc == 6 && !strcmp(argv[5], "state"));
     fclose(out);
     return rc;
 }
