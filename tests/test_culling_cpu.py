@@ -346,12 +346,13 @@ def test_ten_redundant_above_nine_points_equals_the_double_comparison():
 
 
 # ---- random scenes ------------------------------------------------------------------------------------------------------------
-def cull_scene(rows, seed, stereo=True, npts=300, big=False):
+def cull_scene(rows, seed, stereo=True, npts=300, big=False, cap=64, big_at=100, hub_row=None):
     """A scene of test_covisibility_cpu.random_scene with what culling reads on top.  The lists are made maps (a row once)
     and get the key-point index of the slot that holds the point; the graph is what UpdateConnections of every row gives.
     Every third row sees its points at a coarse octave, so it is redundant while enough finer rows see them too.  big: a
-    hub point seen by 70 rows, and row rows - 2 with 76 connections and 71 children that is culled."""
-    T, state, _ = random_scene(rows, seed, npts=npts, obs_lo=4, obs_hi=9)
+    hub point seen by 70 rows, and row rows - 2 with 76 connections and 71 children that is culled; those rows start at big_at.
+    cap: the slots of a bank row.  hub_row: a row every other row is connected with, both ways, weights 1-4."""
+    T, state, G = random_scene(rows, seed, npts=npts, cap=cap, obs_lo=4, obs_hi=9)
     rng = np.random.default_rng(seed + 1000)
     cap, n_pts, pcap = T["cap"], T["np"], T["pcap"]
     where = {}
@@ -366,9 +367,9 @@ def cull_scene(rows, seed, stereo=True, npts=300, big=False):
         lists.append([(r, where[(p, r)]) for r in rs if (p, r) in where])
     big_row = rows - 2
     if big:
-        assert rows >= 200
+        assert rows >= 200 and 24 <= big_at and big_at + 76 <= big_row
         hub_pt = 7
-        for r in range(100, 170):                                   # the hub point: a list that crosses a wavefront
+        for r in range(big_at, big_at + 70):                        # the hub point: a list that crosses a wavefront
             i = int(T["n"][r])
             T["slot_point"][r, i], T["n"][r] = hub_pt, i + 1
             lists[hub_pt].append((r, i))
@@ -406,7 +407,6 @@ def cull_scene(rows, seed, stereo=True, npts=300, big=False):
     T["to_be_erased"] = np.zeros(rows, u8)
     T["not_erase"] = np.zeros(rows, u8)
     # the graph: UpdateConnections of every row, then a few rows that are bad already
-    G = CV.Graph.from_dense(state)
     CV.update_connections_list(G, list(range(rows)), T["slot_point"], T["n"], T["obs_start"], T["obs_kf"], T["flags"], 0)
     for r in (3, 6, 9):                                             # a connection only the own row holds
         if r < rows and G.conn[r]:
@@ -417,18 +417,24 @@ def cull_scene(rows, seed, stereo=True, npts=300, big=False):
         T["kf_bad"][[5, 11]] = 1
         T["not_erase"][[3, 9]] = 1
     if big:
-        for c in range(100, 176):
+        for c in range(big_at, big_at + 76):
             G.conn[big_row][c] = G.conn[c][big_row] = 1 + (c * 7) % 5
         G.conn[big_row][3] = G.conn[3][big_row] = 40
-        for c in range(100, 171):
+        for c in range(big_at, big_at + 71):
             G.parent[c] = big_row
             if c % 3 == 0:
                 G.conn[c][3] = G.conn[3][c] = 2 + c % 4
             if c % 3 == 1:
                 G.conn[c][c - 1] = G.conn[c - 1][c] = 5 + c % 2
         G.parent[big_row] = 3
-        T["kf_bad"][130] = 1
-        for c in [3, big_row] + list(range(99, 176)):
+        T["kf_bad"][big_at + 30] = 1
+        for c in [3, big_row] + list(range(big_at - 1, big_at + 76)):
+            CV.update_best_covisibles(G, c)
+    if hub_row is not None:
+        for c in range(rows):
+            if c != hub_row:
+                G.conn[hub_row][c] = G.conn[c][hub_row] = 1 + (c * 5) % 4
+        for c in range(rows):
             CV.update_best_covisibles(G, c)
     fill = dict(ord_kf=np.full((rows, rows), SENTINEL, i32), ord_w=np.full((rows, rows), SENTINEL, i32),
                 covis=np.full((rows, 10), SENTINEL, i32))

@@ -168,6 +168,22 @@ def test_limit_of_2048_observations(env):
     assert_equal_to_reference(got, ref, BOTH, 4, "limit, host", device_form=False)
 
 
+def test_more_long_points_than_workgroups_of_the_worklist_kernel(env):
+    """1300 points, 1094 of them with 17 observations and 6 with 65 (map_scale_cases.upd_case): more long points than
+    k_update_points_long has workgroups, so the worklist is walked with the grid stride.  Device and host form."""
+    import map_scale_cases as SC
+    SC.preconditions("upd_long")
+    S, K = env["S"], SC.upd_case()
+    n = K["n"]
+    c = Call(env, env["bank"], S["cam"], BOTH, K["start"], K["okf"], K["oidx"], K["ref_obs"], K["world"], K["flags"], n, n + 7)
+    env["m"].sync()
+    assert_equal_to_reference(c.results(), K["ref"], BOTH, n, "long points")
+    KFs = [env["pkg"].FrameView(S["keys"][r], S["desc"][r], PC.SF, PC.BOUNDS) for r in range(MC.ROWS)]
+    got = env["m"].UpdateMapPoints(S["cam"], BOTH, KFs, S["T"], S["kf_bad"], K["start"], K["okf"], K["oidx"], K["ref_obs"], K["world"],
+                                   K["flags"], *MC.sentinels(n))
+    assert_equal_to_reference(got, K["ref"], BOTH, n, "long points, host", device_form=False)
+
+
 # ---- two calls back to back ----------------------------------------------------------------------------------------------
 def test_two_calls_back_to_back_on_one_stream(env):
     """Points 0 .. 149 and 150 .. 299 of the scene as two calls without a synchronisation between them, then the other way
