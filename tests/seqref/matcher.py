@@ -271,10 +271,26 @@ def search_for_initialization(F1, F2, prev_matched, window_size=100, nnratio=0.9
     return n, m12.astype(np.int32), prev
 
 
-def compute_stereo_matches(keys_l, desc_l, keys_r, desc_r, levels_l, levels_r, scale, inv_scale, mbf, mb):
+STEREO_EXITS = ("no_candidates", "max_u_negative", "level_gate", "ur_range", "best_dist", "window_edge", "sad_edge", "delta_range",
+                "disparity_range", "clamp", "median_cull")
+
+
+def compute_stereo_matches(keys_l, desc_l, keys_r, desc_r, levels_l, levels_r, scale, inv_scale, mbf, mb, info=None):
     """Frame::ComputeStereoMatches (src/Frame.cc:466-640) on the unpadded pyramid levels of both images.
     `mb` is an explicit argument (the reference reads it before assigning it).
-    Returns (number of keypoints with a depth, mvuRight, mvDepth)."""
+    Returns (number of keypoints with a depth, mvuRight, mvDepth).
+
+    `info`, if a dict, receives what the loop decided: "accepted" {iL: dict(sad, idx_r, vd, delta)} for every left key
+    point that reached the disparity assignment (before the median cull), "exit" {iL: name} for every left key point that
+    left the loop early or was culled, "count" {name: n} over STEREO_EXITS (level_gate and ur_range count candidates,
+    clamp counts accepted key points whose disparity was clamped; the others count left key points), and "median",
+    "th_dist", "culled" of the cull (None / [] when nothing was accepted)."""
+    count = dict.fromkeys(STEREO_EXITS, 0)
+    accepted, exits = {}, {}
+
+    def leave(iL, name):
+        count[name] += 1
+        exits[iL] = name
     kl = np.asarray(keys_l, KP_DTYPE)
     kr = np.asarray(keys_r, KP_DTYPE)
     dl = np.asarray(desc_l, np.uint8).reshape(-1, 32)
@@ -305,22 +321,28 @@ def compute_stereo_matches(keys_l, desc_l, keys_r, desc_r, levels_l, levels_r, s
         vL, uL = f32(kl["y"][iL]), f32(kl["x"][iL])
         cands = rows[int(vL)]                                              # :511, float index truncated
         if not cands:
+            leave(iL, "no_candidates")
             continue
         minU = f32(uL - maxD)
         maxU = f32(uL - minD)
         if maxU < 0:
+            leave(iL, "max_u_negative")
             continue
         best_dist, best_idx_r = TH_HIGH, 0                                 # :522-523
         for iR in cands:
             o = int(kr["octave"][iR])
             if o < levelL - 1 or o > levelL + 1:                           # :533
+                count["level_gate"] += 1
                 continue
             uR = f32(kr["x"][iR])
             if uR >= minU and uR <= maxU:                                  # :538
                 d = int(descriptor_distance(dl[iL], dr[iR]))
                 if d < best_dist:
                     best_dist, best_idx_r = d, iR
+            else:
+                count["ur_range"] += 1
         if best_dist >= th_orb:                                            # :552
+            leave(iL, "best_dist")
             continue
         uR0 = f32(kr["x"][best_idx_r])
         sfac = inv_scale[levelL]
@@ -334,6 +356,7 @@ def compute_stereo_matches(keys_l, desc_l, keys_r, desc_r, levels_l, levels_r, s
         iniu = suR0 + L - w                                                # :573-576
         endu = suR0 + L + w + 1
         if iniu < 0 or endu >= Lr.shape[1]:
+            leave(iL, "window_edge")
             continue
         best_sad, best_inc = INT_MAX, 0
         vd = [0] * (2 * L + 1)
@@ -347,20 +370,27 @@ def compute_stereo_matches(keys_l, desc_l, keys_r, desc_r, levels_l, levels_r, s
                 best_sad, best_inc = int(d), inc
             vd[L + inc] = d
         if best_inc == -L or best_inc == L:                                # :594-595
+            leave(iL, "sad_edge")
             continue
         d1, d2, d3 = vd[L + best_inc - 1], vd[L + best_inc], vd[L + best_inc + 1]
         deltaR = f32(f32(d1 - d3) / f32(f32(2.0) * f32(f32(d1 + d3) - f32(f32(2.0) * d2))))   # :602
         if deltaR < -1 or deltaR > 1:
+            leave(iL, "delta_range")
             continue
         best_uR = f32(scale[levelL] * f32(f32(f32(suR0) + f32(best_inc)) + deltaR))            # :608
         disparity = f32(uL - best_uR)
         if disparity >= minD and disparity < maxD:                         # :612-622
             if disparity <= 0:
+                count["clamp"] += 1
                 disparity = f32(0.01)
                 best_uR = f32(float(uL) - 0.01)                            # uL - 0.01 in double
             depth[iL] = f32(f32(mbf) / disparity)
             u_right[iL] = best_uR
             dist_idx.append((best_sad, iL))
+            accepted[iL] = dict(sad=best_sad, idx_r=best_idx_r, vd=[int(v) for v in vd], delta=deltaR)
+        else:
+            leave(iL, "disparity_range")
+    median = th_dist = None
     if dist_idx:                                                           # :626-639
         dist_idx.sort()
         median = f32(dist_idx[len(dist_idx) // 2][0])
@@ -370,4 +400,8 @@ def compute_stereo_matches(keys_l, desc_l, keys_r, desc_r, levels_l, levels_r, s
                 break
             u_right[dist_idx[i][1]] = -1
             depth[dist_idx[i][1]] = -1
+            leave(dist_idx[i][1], "median_cull")
+    if info is not None:
+        info.update(accepted=accepted, exit=exits, count=count, median=median, th_dist=th_dist,
+                    culled=sorted(i for i, e in exits.items() if e == "median_cull"))
     return int((depth > 0).sum()), u_right, depth

@@ -44,6 +44,7 @@ import test_seqref_projection_cpu as PC
 import test_seqref_projection_gpu as SP
 import test_sim3_gpu as RG
 import test_sim3opt_gpu as SG
+import test_stereo_cases_gpu as TC
 import test_triangulate_gpu as TR
 import test_window_search_groups_gpu as WG
 from seqref import mappoint as MP
@@ -232,7 +233,9 @@ STAGES = [
     Stage("frame-glue", [call(TM.test_undistort_keypoints, "tup3", ident="undistort"),
                          call(TM.test_distinctive_descriptors, "tup3", ident="distinctive"),
                          call(TM.test_frame_glue_grid_and_rgbd, "tup3", ident="grid-rgbd")]),
-    Stage("stereo-matches", [call(TM.test_compute_stereo_matches, "tup3", 3, 752, 480, 1000, ident="752x480"),
+    # ties: 240 rows and 20 right key points, so the row table and the record array of S_ORD and the SAD list of S_CNT shrink
+    Stage("stereo-matches", [call(TC.test_host_entry_equals_seqref, "tup2", "ties", ident="ties"),
+                             call(TM.test_compute_stereo_matches, "tup3", 3, 752, 480, 1000, ident="752x480"),
                              call(TM.test_device_batched_stereo_equals_host_api, "tup3", ident="device-batch")]),
     Stage("fuse", [call(SP.test_fuse_ties_borders_and_gates_through_every_entry, "seqproj", False, False, ident="edges-mono"),
                    call(SP.test_fuse_ties_borders_and_gates_through_every_entry, "seqproj", True, True, ident="edges-stereo-sim3"),
