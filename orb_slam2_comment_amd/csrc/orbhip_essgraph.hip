@@ -23,6 +23,7 @@
 //   k_eg_finish        one workgroup of 1024: the poses, the list of present points (a scan) and their correction, the report
 #include "orbhip_internal.h"
 #include "orbhip_ldlt.h"
+#include "orbhip_team_dev.h"
 
 namespace orbhip {
 namespace {
@@ -162,26 +163,17 @@ __global__ __launch_bounds__(kItem) void k_eg_vertex(EgWs W)
     for (int f = blockIdx.x * (kItem / 64) + (threadIdx.x >> 6); f < nf; f += teams) eg_vertex_block(W, f, eg_free_vtx(*W.S, f), lane);
 }
 
-__device__ __forceinline__ double eg_team_sum(const EgWs &W, int kind, double *s_part)
+// a team sum by a workgroup of kEgTeam lanes; s_part [kEgTeam / kEgWave]
+__device__ __forceinline__ double team_sum(const EgWs &W, int kind, double *s_part)
 {
-    const int tid = threadIdx.x;
-    double v = eg_sum_lane(W, kind, tid);
-#pragma unroll
-    for (int off = 1; off < kEgWave; off <<= 1) v = v + __shfl_xor(v, off);
-    __syncthreads();
-    if ((tid & 63) == 0) s_part[tid >> 6] = v;
-    __syncthreads();
-    double t = s_part[0];
-#pragma unroll
-    for (int w = 1; w < kEgTeam / kEgWave; ++w) t = t + s_part[w];
-    return t;
+    return team_reduce<kEgTeam>(eg_sum_lane(W, kind, threadIdx.x), TeamAdd(), s_part);
 }
 
 __global__ __launch_bounds__(kEgTeam) void k_eg_lm_begin(EgWs W)
 {
     __shared__ double s_part[kEgTeam / kEgWave];
     if (W.S->phase != kEgBuild) return;
-    const double chi = eg_team_sum(W, kEgSumLin, s_part);
+    const double chi = team_sum(W, kEgSumLin, s_part);
     __syncthreads();
     if (threadIdx.x == 0) eg_lm_begin(W, chi);
 }
@@ -237,8 +229,8 @@ __global__ __launch_bounds__(kEgTeam) void k_eg_judge(EgWs W)
 {
     __shared__ double s_part[kEgTeam / kEgWave];
     if (W.S->phase != kEgTrial) return;
-    const double chi = eg_team_sum(W, kEgSumTrial, s_part);
-    const double scale = eg_team_sum(W, kEgSumScale, s_part);
+    const double chi = team_sum(W, kEgSumTrial, s_part);
+    const double scale = team_sum(W, kEgSumScale, s_part);
     __syncthreads();
     if (threadIdx.x == 0) {
         W.S->ok2 = W.S->fail ? 0 : 1;

@@ -15,6 +15,8 @@
 //   - chi2 and computeScale: item t belongs to lane t mod kEgTeam (256), xor butterfly over a wavefront, wavefronts in order;
 //   - the factorisation: element (i, j) of the lower triangle receives a - l_ik * c_jk (eg_fnma: one multiply, one
 //     subtract) for k ascending, l_ik = c_ik / d_k, ok iff every pivot is > 0; the substitutions as lba_solve has them.
+// The Levenberg-Marquardt rule and the host replay of the team combine are orbhip_lm_core.h's; eg_lm_judge keeps the two
+// buffers, the counters, fails0 / ORBHIP_EG_SINGULAR and the phases around the rule.
 // Nothing here indexes a private array at run time.
 #pragma once
 #include "orbhip_sim3opt_core.h"
@@ -515,47 +517,23 @@ PO_HD void eg_begin(EgWs &W)
 PO_HD void eg_lm_begin(EgWs &W, double chi)
 {
     EgState &S = *W.S;
-    S.current = S.ini = chi;
-    if (S.it == 0) { S.lam = 1e-16; S.ni = 2.0; S.n_bad_lm = 0; S.fails0 = 0; }
-    S.rho = 0.0; S.qmax = 0;
+    if (S.it == 0) S.fails0 = 0;
+    lm_begin(S, chi, 1e-16);
     S.phase = kEgTrial;
 }
 PO_HD void eg_lm_judge(EgWs &W, double temp, double scale)
 {
     EgState &S = *W.S;
-    if (!S.ok2) { temp = kPoDblMax; if (S.it == 0) S.fails0 = S.fails0 + 1; }
-    double rho = S.current - temp;
-    scale = scale + 1e-3;
-    rho = rho / scale;
-    if (rho > 0 && fabs(temp) <= kPoDblMax) {
-        const double y = 2 * rho - 1;
-        double alpha = 1.0 - (y * y) * y;
-        alpha = 2.0 / 3.0 < alpha ? 2.0 / 3.0 : alpha;
-        const double sf = 1.0 / 3.0 < alpha ? alpha : 1.0 / 3.0;
-        S.lam = S.lam * sf;
-        S.ni = 2.0;
-        S.current = temp;
-        S.cur = 1 - S.cur;                                                         // discardTop: the tried estimate stands
-    } else {
-        S.lam = S.lam * S.ni;
-        S.ni = S.ni * 2;                                                           // pop: the other buffer is overwritten
-    }
-    S.rho = rho;
-    S.qmax = S.qmax + 1;
+    if (!S.ok2 && S.it == 0) S.fails0 = S.fails0 + 1;
+    // discardTop: the tried estimate stands; pop: the other buffer is overwritten by the next trial
+    if (lm_gain(S, S.ok2 != 0, temp, scale)) S.cur = 1 - S.cur;
     S.trials = S.trials + 1;
     S.fail = 0;
-    if (rho < 0 && S.qmax < 10) return;                                            // another trial
+    if (lm_retry(S)) return;                                                       // another trial
     S.its = S.its + 1;
     if (S.it == 0 && S.fails0 == S.qmax) S.status = ORBHIP_EG_SINGULAR;
     S.it = S.it + 1;
-    bool ok = true;
-    if (S.qmax == 10 || rho == 0) ok = false;
-    else {
-        if ((S.ini - S.current) * 1e3 < S.ini) S.n_bad_lm = S.n_bad_lm + 1;
-        else S.n_bad_lm = 0;
-        if (S.n_bad_lm >= 3) ok = false;
-    }
-    S.phase = (ok && S.it < 20) ? kEgBuild : kEgFinal;
+    S.phase = (lm_iteration_ok(S) && S.it < 20) ? kEgBuild : kEgFinal;
 }
 
 // ---- the epilogue (:991-1043) ---------------------------------------------------------------------------------------------------
@@ -631,16 +609,9 @@ inline size_t eg_carve(EgWs &W, uint8_t *base)
 // ---- one host thread ------------------------------------------------------------------------------------------------------
 inline double eg_host_team_sum(const EgWs &W, int kind)
 {
-    double total = 0.0;
-    for (int w0 = 0; w0 < kEgTeam; w0 += kEgWave) {
-        double lanes[kEgWave], nxt[kEgWave];
-        for (int l = 0; l < kEgWave; ++l) lanes[l] = eg_sum_lane(W, kind, w0 + l);
-        for (int off = 1; off < kEgWave; off <<= 1) {
-            for (int l = 0; l < kEgWave; ++l) nxt[l] = lanes[l] + lanes[l ^ off];
-            for (int l = 0; l < kEgWave; ++l) lanes[l] = nxt[l];
-        }
-        total = w0 == 0 ? lanes[0] : total + lanes[0];
-    }
+    double lanes[kEgTeam][1], total;
+    for (int l = 0; l < kEgTeam; ++l) lanes[l][0] = eg_sum_lane(W, kind, l);
+    host_team_combine<kEgTeam, 1>(lanes, 0, &total, TeamAdd());
     return total;
 }
 // the vertices and the edges (:809-983), sequentially

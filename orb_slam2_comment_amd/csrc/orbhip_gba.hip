@@ -32,23 +32,6 @@ using namespace lbadev;
 
 constexpr int kBig = 1024, kItem = 256, kItemBlocks = 240, kSchurBlocks = 1024, kRowsMax = 4096;
 
-// exclusive scan of v over the 1024 lanes of the workgroup; *total = the sum.  s_w [16].
-__device__ __forceinline__ int gba_block_scan(int v, int *s_w, int *total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int incl = wave_incl_scan_add(v);
-    __syncthreads();
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    int off = 0, all = 0;
-    for (int w = 0; w < kBig / 64; ++w) {
-        if (w < wv) off += s_w[w];
-        all += s_w[w];
-    }
-    *total = all;
-    return off + incl - v;
-}
-
 enum { kSMaxId = 0, kSRemoved, kSSkipped, kSNull, kSStereo, kSPoses, kSInts };
 
 __device__ void gba_setup_done(GbaWs &G, const int *s_i, int nv, int nfree, int npts, int ne, int status)
@@ -82,7 +65,7 @@ __global__ __launch_bounds__(kBig) void k_gba_setup(GbaWs G)
         const int i = base + tid, r = i < nkf ? gba_kf_at(G, i) : -1;
         const bool good = i < nkf && gba_row_good(G, r);
         int all;
-        const int pos = nv + gba_block_scan(good ? 1 : 0, s_w, &all);
+        const int pos = nv + block_excl_scan<kBig>(good ? 1 : 0, s_w, &all);
         if (good && pos < vcap) { W.lkf[pos] = r; W.vtx_row[pos] = r; W.kf_vtx[r] = pos; }
         if (good) atomicMax(&s_i[kSMaxId], G.kf_id[r]);
         nv += all;
@@ -97,7 +80,7 @@ __global__ __launch_bounds__(kBig) void k_gba_setup(GbaWs G)
         const int v = base + tid;
         const bool fr = v < nv && G.kf_id[W.vtx_row[v]] != 0;                      // setFixed(pKF->mnId == 0)
         int all;
-        const int pos = nfree + gba_block_scan(fr ? 1 : 0, s_w, &all);
+        const int pos = nfree + block_excl_scan<kBig>(fr ? 1 : 0, s_w, &all);
         if (v < nv) W.vtx_free[v] = fr ? pos : -1;
         nfree += all;
     }
@@ -122,8 +105,8 @@ __global__ __launch_bounds__(kBig) void k_gba_setup(GbaWs G)
         if (ns) atomicAdd(&s_i[kSStereo], ns);
         if (cand && c == 0) atomicAdd(&s_i[kSRemoved], 1);                         // vbNotIncludedMP
         int all_p, all_e;
-        const int pos = npts + gba_block_scan(c > 0 ? 1 : 0, s_w, &all_p);
-        const int off = ne + gba_block_scan(c, s_w, &all_e);
+        const int pos = npts + block_excl_scan<kBig>(c > 0 ? 1 : 0, s_w, &all_p);
+        const int off = ne + block_excl_scan<kBig>(c, s_w, &all_e);
         if (c > 0 && pos < W.max_points && off + c <= W.max_edges) {
             W.pt_e0[pos] = off;
             gba_point_init(G, pos, p);
@@ -195,9 +178,7 @@ __global__ __launch_bounds__(kItem) void k_gba_covis(GbaWs G)
 // ---- a linearisation --------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kItem) void k_gba_linearize(LbaWs W)
 {
-    if (W.S->phase != kLbaBuild) return;
-    const int ne = W.S->n_edges;
-    for (int j = blockIdx.x * kItem + threadIdx.x; j < ne; j += gridDim.x * kItem) lba_edge_linearize(W, j);
+    if (W.S->phase == kLbaBuild) phase_linearize<kItem>(W);
 }
 
 __global__ __launch_bounds__(kItem) void k_gba_blocks(LbaWs W)
@@ -205,38 +186,23 @@ __global__ __launch_bounds__(kItem) void k_gba_blocks(LbaWs W)
     if (W.S->phase != kLbaBuild) return;
     const int tid = threadIdx.x, lane = tid & 63, nfree = W.S->n_free, np = W.S->n_pts;
     const int waves = gridDim.x * (kItem / 64);
-    for (int f = blockIdx.x * (kItem / 64) + (tid >> 6); f < nfree; f += waves) {
-        double acc[27];
-#pragma unroll
-        for (int k = 0; k < 27; ++k) acc[k] = 0.0;
-        lba_pose_block_lane(W, f, lane, acc);
-        wave_butterfly<27>(acc);
-        if (lane == 0) {
-#pragma unroll
-            for (int q = 0; q < 21; ++q) W.Hpp[f * 21 + q] = acc[q];
-#pragma unroll
-            for (int q = 0; q < 6; ++q) W.bp[f * 6 + q] = acc[21 + q];
-        }
-    }
+    for (int f = blockIdx.x * (kItem / 64) + (tid >> 6); f < nfree; f += waves) pose_block(W, f, lane);
     for (int i = blockIdx.x * kItem + tid; i < np; i += gridDim.x * kItem) lba_point_block(W, i);
 }
 
+// a factorisation that has not failed is ok2 = 1: the solve kernels only ever clear it (GbaView::fail)
 __global__ __launch_bounds__(kLbaTeam) void k_gba_begin(LbaWs W)
 {
     __shared__ double s_part[kLbaTeam / kLbaWave];
     if (W.S->phase != kLbaBuild) return;
-    const double chi = team_sum(W, kLbaSumChi, s_part);
-    const double mx = W.S->it == 0 ? team_sum(W, kLbaSumMax, s_part) : 0.0;
-    __syncthreads();
-    if (threadIdx.x == 0) { lba_lm_begin(W, chi, mx); W.S->ok2 = 1; }
+    phase_lm_begin(W, s_part);
+    if (threadIdx.x == 0) W.S->ok2 = 1;
 }
 
 // ---- a trial ----------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kItem) void k_gba_dinv(LbaWs W)
 {
-    if (W.S->phase != kLbaTrial) return;
-    const int np = W.S->n_pts;
-    for (int i = blockIdx.x * kItem + threadIdx.x; i < np; i += gridDim.x * kItem) lba_point_dinv(W, i);
+    if (W.S->phase == kLbaTrial) phase_dinv<kItem>(W);
 }
 
 __global__ __launch_bounds__(kItem) void k_gba_schur(GbaWs G)
@@ -271,27 +237,20 @@ __global__ __launch_bounds__(kItem) void k_gba_x(LbaWs W)
 
 __global__ __launch_bounds__(kItem) void k_gba_update(LbaWs W)
 {
-    if (W.S->phase != kLbaTrial) return;
-    const int np = W.S->n_pts, nv = W.S->n_lkf, g = blockIdx.x * kItem + threadIdx.x, gs = gridDim.x * kItem;
-    for (int i = g; i < np; i += gs) lba_point_update(W, i);
-    for (int v = g; v < nv; v += gs) lba_vertex_update(W, v);
+    if (W.S->phase == kLbaTrial) phase_update<kItem>(W);
 }
 
 __global__ __launch_bounds__(kItem) void k_gba_trial(LbaWs W)
 {
-    if (W.S->phase != kLbaTrial) return;
-    const int ne = W.S->n_edges, buf = 1 - W.S->cur;
-    for (int j = blockIdx.x * kItem + threadIdx.x; j < ne; j += gridDim.x * kItem) lba_edge_error(W, j, buf);
+    if (W.S->phase == kLbaTrial) phase_trial<kItem>(W);
 }
 
 __global__ __launch_bounds__(kLbaTeam) void k_gba_judge(LbaWs W)
 {
     __shared__ double s_part[kLbaTeam / kLbaWave];
     if (W.S->phase != kLbaTrial) return;
-    const double chi = team_sum(W, kLbaSumChi, s_part);
-    const double scale = team_sum(W, kLbaSumScale, s_part);
-    __syncthreads();
-    if (threadIdx.x == 0) { lba_lm_judge(W, chi, scale); W.S->ok2 = 1; }
+    phase_lm_judge(W, s_part);
+    if (threadIdx.x == 0) W.S->ok2 = 1;
 }
 
 __global__ __launch_bounds__(kBig) void k_gba_finish(GbaWs G)

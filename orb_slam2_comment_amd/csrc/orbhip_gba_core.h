@@ -1,8 +1,9 @@
 // Optimizer::BundleAdjustment (src/Optimizer.cc:49-237; GlobalBundleAdjustemnt :41-46 is the call with null lists) and the map
 // update of LoopClosing::RunGlobalBundleAdjustment (src/LoopClosing.cc:676-737), operation by operation what
 // tests/seqref/gba.py does.  The edges, the blocks, the Schur complement, the Levenberg-Marquardt state
-// machine and the team sums are orbhip_lba_core.h's, run as one round of optimize(iterations) (LbaWs::single_its); this file
-// adds what differs: the vertices and edges of a whole map, the write-back of the two modes, and the apply step.
+// machine and the team sums are orbhip_lba_core.h's (the rule itself and the combine: orbhip_lm_core.h), run as one round of
+// optimize(iterations) (LbaWs::single_its); this file adds what differs: the vertices and edges of a whole map, the write-back
+// of the two modes, and the apply step.
 //
 // The same text serves the kernels of orbhip_gba.hip and one host thread (gba_host_run, gba_apply_host).
 //   - vertices: the listed rows that are not bad, in list order; the free poses of the reduced system are these with the rows of

@@ -33,23 +33,6 @@ constexpr int kIntMax = 0x7fffffff;
 
 __device__ __forceinline__ int ld_agent(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// exclusive scan of v over the 1024 lanes of the workgroup; *total = the sum.  s_w [16].
-__device__ __forceinline__ int block_excl_scan(int v, int *s_w, int *total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int incl = wave_incl_scan_add(v);
-    __syncthreads();
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    int off = 0, all = 0;
-    for (int w = 0; w < kSetupThreads / 64; ++w) {
-        if (w < wv) off += s_w[w];
-        all += s_w[w];
-    }
-    *total = all;
-    return off + incl - v;
-}
-
 __global__ __launch_bounds__(kSetupThreads) void k_lba_setup(LbaWs W)
 {
     __shared__ int s_w[kSetupThreads / 64];
@@ -106,7 +89,7 @@ __global__ __launch_bounds__(kSetupThreads) void k_lba_setup(LbaWs W)
             }
         }
         int all;
-        const int pos = npts + block_excl_scan(first ? 1 : 0, s_w, &all);
+        const int pos = npts + block_excl_scan<kSetupThreads>(first ? 1 : 0, s_w, &all);
         if (first && pos < W.max_points) W.lpt[pos] = p;
         npts += all;
     }
@@ -126,7 +109,7 @@ __global__ __launch_bounds__(kSetupThreads) void k_lba_setup(LbaWs W)
         int c = 0;
         if (i < npts) { const int p = W.lpt[i]; c = max(W.obs_start[p + 1] - W.obs_start[p], 0); }
         int all;
-        const int off = ncand + block_excl_scan(c, s_w, &all);
+        const int off = ncand + block_excl_scan<kSetupThreads>(c, s_w, &all);
         if (i < npts) W.pt_c0[i] = off;
         ncand += all;
     }
@@ -167,7 +150,7 @@ __global__ __launch_bounds__(kSetupThreads) void k_lba_setup(LbaWs W)
             }
         }
         int all;
-        const int off = ne + block_excl_scan(c, s_w, &all);
+        const int off = ne + block_excl_scan<kSetupThreads>(c, s_w, &all);
         if (i < npts) W.pt_e0[i] = min(off, W.max_edges);
         if (ns) atomicAdd(&s_i[3], ns);
         ne += all;
@@ -242,9 +225,7 @@ __global__ __launch_bounds__(kSetupThreads) void k_lba_setup(LbaWs W)
 
 __global__ __launch_bounds__(kItemThreads) void k_lba_linearize(LbaWs W)
 {
-    if (W.S->phase != kLbaBuild) return;
-    const int ne = W.S->n_edges;
-    for (int j = blockIdx.x * kItemThreads + threadIdx.x; j < ne; j += gridDim.x * kItemThreads) lba_edge_linearize(W, j);
+    if (W.S->phase == kLbaBuild) phase_linearize<kItemThreads>(W);
 }
 
 __global__ __launch_bounds__(kItemThreads) void k_lba_blocks(LbaWs W)
@@ -253,18 +234,7 @@ __global__ __launch_bounds__(kItemThreads) void k_lba_blocks(LbaWs W)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (blockIdx.x < kPoseBlocks) {
         const int f = blockIdx.x * 4 + wv;
-        if (f >= W.S->n_free) return;
-        double acc[27];
-#pragma unroll
-        for (int k = 0; k < 27; ++k) acc[k] = 0.0;
-        lba_pose_block_lane(W, f, lane, acc);
-        wave_butterfly<27>(acc);
-        if (lane == 0) {
-#pragma unroll
-            for (int q = 0; q < 21; ++q) W.Hpp[f * 21 + q] = acc[q];
-#pragma unroll
-            for (int q = 0; q < 6; ++q) W.bp[f * 6 + q] = acc[21 + q];
-        }
+        if (f < W.S->n_free) pose_block(W, f, lane);
         return;
     }
     const int np = W.S->n_pts, nb = gridDim.x - kPoseBlocks;
@@ -274,18 +244,12 @@ __global__ __launch_bounds__(kItemThreads) void k_lba_blocks(LbaWs W)
 __global__ __launch_bounds__(kLbaTeam) void k_lba_begin(LbaWs W)
 {
     __shared__ double s_part[kLbaTeam / kLbaWave];
-    if (W.S->phase != kLbaBuild) return;
-    const double chi = team_sum(W, kLbaSumChi, s_part);
-    const double mx = W.S->it == 0 ? team_sum(W, kLbaSumMax, s_part) : 0.0;
-    __syncthreads();
-    if (threadIdx.x == 0) lba_lm_begin(W, chi, mx);
+    if (W.S->phase == kLbaBuild) phase_lm_begin(W, s_part);
 }
 
 __global__ __launch_bounds__(kItemThreads) void k_lba_dinv(LbaWs W)
 {
-    if (W.S->phase != kLbaTrial) return;
-    const int np = W.S->n_pts;
-    for (int i = blockIdx.x * kItemThreads + threadIdx.x; i < np; i += gridDim.x * kItemThreads) lba_point_dinv(W, i);
+    if (W.S->phase == kLbaTrial) phase_dinv<kItemThreads>(W);
 }
 
 __global__ __launch_bounds__(kItemThreads) void k_lba_schur(LbaWs W)
@@ -320,27 +284,18 @@ __global__ __launch_bounds__(kSetupThreads) void k_lba_solve(LbaWs W)
 
 __global__ __launch_bounds__(kItemThreads) void k_lba_update(LbaWs W)
 {
-    if (W.S->phase != kLbaTrial) return;
-    const int np = W.S->n_pts, nv = W.S->n_lkf + W.S->n_fkf, g = blockIdx.x * kItemThreads + threadIdx.x, gs = gridDim.x * kItemThreads;
-    for (int i = g; i < np; i += gs) lba_point_update(W, i);
-    for (int v = g; v < nv; v += gs) lba_vertex_update(W, v);
+    if (W.S->phase == kLbaTrial) phase_update<kItemThreads>(W);
 }
 
 __global__ __launch_bounds__(kItemThreads) void k_lba_trial(LbaWs W)
 {
-    if (W.S->phase != kLbaTrial) return;
-    const int ne = W.S->n_edges, buf = 1 - W.S->cur;
-    for (int j = blockIdx.x * kItemThreads + threadIdx.x; j < ne; j += gridDim.x * kItemThreads) lba_edge_error(W, j, buf);
+    if (W.S->phase == kLbaTrial) phase_trial<kItemThreads>(W);
 }
 
 __global__ __launch_bounds__(kLbaTeam) void k_lba_judge(LbaWs W)
 {
     __shared__ double s_part[kLbaTeam / kLbaWave];
-    if (W.S->phase != kLbaTrial) return;
-    const double chi = team_sum(W, kLbaSumChi, s_part);
-    const double scale = team_sum(W, kLbaSumScale, s_part);
-    __syncthreads();
-    if (threadIdx.x == 0) lba_lm_judge(W, chi, scale);
+    if (W.S->phase == kLbaTrial) phase_lm_judge(W, s_part);
 }
 
 __global__ __launch_bounds__(kItemThreads) void k_lba_classify(LbaWs W)
@@ -400,7 +355,7 @@ __global__ __launch_bounds__(kSetupThreads) void k_lba_finish(LbaWs W)
                 const int j = base + tid;
                 const bool hit = j < ne && W.e_erase[j] && ((W.e_fl[j] & kLbaStereo) != 0) == (pass == 1);
                 int all;
-                const int pos = nerase + block_excl_scan(hit ? 1 : 0, s_w, &all);
+                const int pos = nerase + block_excl_scan<kSetupThreads>(hit ? 1 : 0, s_w, &all);
                 if (hit) {
                     W.o_erase[(size_t)pos * 3] = W.vtx_row[W.e_vtx[j]]; W.o_erase[(size_t)pos * 3 + 1] = W.e_idx[j];
                     W.o_erase[(size_t)pos * 3 + 2] = W.lpt[W.e_pt[j]];

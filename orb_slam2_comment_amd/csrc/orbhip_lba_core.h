@@ -13,6 +13,8 @@
 //   - a point's blocks: its edges are contiguous, added in edge order from 0.0 by one lane;
 //   - a pose's blocks and a pair's Schur block: entry k of the pose's edge index belongs to lane k mod 64;
 //   - chi2, the largest diagonal and computeScale: item t belongs to lane t mod kLbaTeam (256).
+// The Levenberg-Marquardt rule and the host replay of the combine are orbhip_lm_core.h's; lba_lm_judge keeps what is the
+// function's own around the rule: the two buffers, the trial counters, the stop byte and the phases.
 // Nothing here indexes a private array at run time.
 #pragma once
 #include "orbhip_poseopt_core.h"
@@ -136,48 +138,21 @@ PO_HD void lba_begin(LbaWs &W)
 // OptimizationAlgorithmLevenberg::solve :82-101 with the robust chi2 and the largest diagonal at the estimate
 PO_HD void lba_lm_begin(LbaWs &W, double chi, double mx)
 {
-    LbaState &S = *W.S;
-    S.current = S.ini = chi;
-    if (S.it == 0) { S.lam = 1e-5 * mx; S.ni = 2.0; S.n_bad_lm = 0; }
-    S.rho = 0.0; S.qmax = 0;
-    S.phase = kLbaTrial;
+    lm_begin(*W.S, chi, 1e-5 * mx);
+    W.S->phase = kLbaTrial;
 }
 // :123-163 with the trial's robust chi2 and computeScale
 PO_HD void lba_lm_judge(LbaWs &W, double temp, double scale)
 {
     LbaState &S = *W.S;
-    if (!S.ok2) temp = kPoDblMax;
-    double rho = S.current - temp;
-    scale = scale + 1e-3;
-    rho = rho / scale;
     S.tried = 1 - S.cur;
-    if (rho > 0 && fabs(temp) <= kPoDblMax) {
-        const double y = 2 * rho - 1;
-        double alpha = 1.0 - (y * y) * y;
-        alpha = 2.0 / 3.0 < alpha ? 2.0 / 3.0 : alpha;
-        const double sf = 1.0 / 3.0 < alpha ? alpha : 1.0 / 3.0;
-        S.lam = S.lam * sf;
-        S.ni = 2.0;
-        S.current = temp;
-        S.cur = 1 - S.cur;                                                         // discardTop: the tried estimate stands
-    } else {
-        S.lam = S.lam * S.ni;
-        S.ni = S.ni * 2;                                                           // pop: the other buffer is overwritten
-    }
-    S.rho = rho;
-    S.qmax = S.qmax + 1;
+    // discardTop: the tried estimate stands; pop: the other buffer is overwritten by the next trial
+    if (lm_gain(S, S.ok2 != 0, temp, scale)) S.cur = 1 - S.cur;
     S.trials[S.round] = S.trials[S.round] + 1;
-    if (rho < 0 && S.qmax < 10 && !lba_sample(W)) return;                          // another trial
+    if (lm_retry(S) && !lba_sample(W)) return;                                     // another trial
     S.its[S.round] = S.its[S.round] + 1;
     S.it = S.it + 1;
-    bool ok = true;
-    if (S.qmax == 10 || rho == 0) ok = false;
-    else {
-        if ((S.ini - S.current) * 1e3 < S.ini) S.n_bad_lm = S.n_bad_lm + 1;
-        else S.n_bad_lm = 0;
-        if (S.n_bad_lm >= 3) ok = false;
-    }
-    lba_iter_top(W, ok);
+    lba_iter_top(W, lm_iteration_ok(S));
 }
 
 // ---- an edge ----------------------------------------------------------------------------------------------------------
@@ -559,7 +534,10 @@ PO_HD double lba_sum_lane(const LbaWs &W, int kind, int lane)
     }
     return acc;
 }
-PO_HD double lba_sum_op(int kind, double a, double b) { return kind == kLbaSumMax ? lba_max2(a, b) : a + b; }
+struct LbaSumOp {
+    int kind;
+    PO_HD double operator()(double a, double b) const { return kind == kLbaSumMax ? lba_max2(a, b) : a + b; }
+};
 
 // ---- the epilogue ---------------------------------------------------------------------------------------------------------
 // Converter::toCvMat(SE3Quat) of a local key frame, the float of a local point (:762-776)
@@ -628,26 +606,11 @@ struct LbaHostTeam {
     int lanes() const { return 1; }
     void sync() {}
 };
-// xor butterfly over the lanes of a wavefront, lane 0's result
-inline void lba_host_butterfly(double (*lanes)[42], int n, int kind)
-{
-    for (int off = 1; off < kLbaWave; off <<= 1) {
-        double nxt[kLbaWave][42];
-        for (int l = 0; l < kLbaWave; ++l)
-            for (int k = 0; k < n; ++k) nxt[l][k] = lba_sum_op(kind, lanes[l][k], lanes[l ^ off][k]);
-        for (int l = 0; l < kLbaWave; ++l)
-            for (int k = 0; k < n; ++k) lanes[l][k] = nxt[l][k];
-    }
-}
 inline double lba_host_team_sum(const LbaWs &W, int kind)
 {
-    double total = 0.0;
-    for (int w0 = 0; w0 < kLbaTeam; w0 += kLbaWave) {
-        double lanes[kLbaWave][42];
-        for (int l = 0; l < kLbaWave; ++l) lanes[l][0] = lba_sum_lane(W, kind, w0 + l);
-        lba_host_butterfly(lanes, 1, kind);
-        total = w0 == 0 ? lanes[0][0] : lba_sum_op(kind, total, lanes[0][0]);
-    }
+    double lanes[kLbaTeam][1], total;
+    for (int l = 0; l < kLbaTeam; ++l) lanes[l][0] = lba_sum_lane(W, kind, l);
+    host_team_combine<kLbaTeam, 1>(lanes, 0, &total, LbaSumOp{kind});
     return total;
 }
 
@@ -781,10 +744,10 @@ inline void lba_host_build(LbaWs &W)
     for (int j = 0; j < S.n_edges; ++j) lba_edge_linearize(W, j);
     for (int i = 0; i < S.n_pts; ++i) lba_point_block(W, i);
     for (int f = 0; f < S.n_free; ++f) {
-        double lanes[kLbaWave][42];
+        double lanes[kLbaWave][27], sum[27];
         for (int l = 0; l < kLbaWave; ++l) { for (int k = 0; k < 27; ++k) lanes[l][k] = 0.0; lba_pose_block_lane(W, f, l, lanes[l]); }
-        lba_host_butterfly(lanes, 27, kLbaSumChi);
-        lba_pose_block_store(W, f, lanes[0]);
+        host_team_combine<kLbaWave, 27>(lanes, 0, sum, TeamAdd());
+        lba_pose_block_store(W, f, sum);
     }
     const double chi = lba_host_team_sum(W, kLbaSumChi), mx = S.it == 0 ? lba_host_team_sum(W, kLbaSumMax) : 0.0;
     lba_lm_begin(W, chi, mx);
@@ -796,10 +759,10 @@ inline void lba_host_trial(LbaWs &W)
     for (int i = 0; i < S.n_pts; ++i) lba_point_dinv(W, i);
     for (int i1 = 0; i1 < S.n_free; ++i1)
         for (int i2 = i1; i2 < S.n_free; ++i2) {
-            double lanes[kLbaWave][42];
+            double lanes[kLbaWave][42], sum[42];
             for (int l = 0; l < kLbaWave; ++l) { for (int k = 0; k < 42; ++k) lanes[l][k] = 0.0; lba_schur_lane(W, i1, i2, l, lanes[l]); }
-            lba_host_butterfly(lanes, 42, kLbaSumChi);
-            lba_schur_store(W, i1, i2, lanes[0]);
+            host_team_combine<kLbaWave, 42>(lanes, 0, sum, TeamAdd());
+            lba_schur_store(W, i1, i2, sum);
         }
     S.ok2 = lba_solve(tm, W) ? 1 : 0;
     for (int i = 0; i < S.n_pts; ++i) lba_point_update(W, i);

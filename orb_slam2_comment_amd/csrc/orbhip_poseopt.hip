@@ -12,23 +12,12 @@
 //                         The edge list lives in LDS, edge data is re-read from L2.  No float atomics, no scratch.
 #include "orbhip_internal.h"
 #include "orbhip_poseopt_core.h"
+#include "orbhip_team_dev.h"
 
 namespace orbhip {
 namespace {
 
-struct PoDevTeam {
-    int tid;
-    __device__ __forceinline__ bool is0() const { return tid == 0; }
-    __device__ __forceinline__ int first() const { return tid; }
-    __device__ __forceinline__ int stride() const { return kPoTeam; }
-    __device__ __forceinline__ void sync()
-    {
-        if (kPoTeam <= kPoWave) wave_lds_handoff(); else __syncthreads();
-    }
-    __device__ __forceinline__ void add(int *dst, int v)
-    {
-        if (v) atomicAdd(dst, v);
-    }
+struct PoDevTeam : DevTeam<kPoTeam> {
     template <bool FULL> __device__ __forceinline__ void sum(PoWs &W, const PoFrame &F, bool kernel, double *s)
     {
         double pose[7];
@@ -43,25 +32,7 @@ struct PoDevTeam {
             po_load_edge(F, j, e);
             po_edge_terms<FULL>(e, pose, F.cam, kernel, s);
         }
-#pragma unroll
-        for (int off = 1; off < kPoWave; off <<= 1) {
-#pragma unroll
-            for (int k = FULL ? 0 : 27; k < 28; ++k) s[k] = s[k] + __shfl_xor(s[k], off);
-        }
-        if (kPoTeam > kPoWave) {
-            if ((tid & (kPoWave - 1)) == 0) {
-#pragma unroll
-                for (int k = FULL ? 0 : 27; k < 28; ++k) W.part[tid / kPoWave][k] = s[k];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = FULL ? 0 : 27; k < 28; ++k) {
-                double t = W.part[0][k];
-#pragma unroll
-                for (int w = 1; w < kPoTeam / kPoWave; ++w) t = t + W.part[w][k];
-                s[k] = t;
-            }
-        }
+        team_combine<kPoTeam, FULL ? 0 : 27, 28>(s, W.part, tid);
     }
 };
 

@@ -8,18 +8,15 @@
 //     (offsets 1 .. 32), the wavefronts are added in wavefront order.  The host team replays exactly that.
 //   - first / stride: how the per-edge loops (classification, epilogue) are dealt out; they carry integers only.
 //   - is0 / sync: lane 0 runs the serial state machine over the workspace (LDS on the device), everyone else waits.
+// The Levenberg-Marquardt rule, the 6x6 solver and the host replay of the team sum are orbhip_lm_core.h's; what is here
+// around them is the function's own: the H and b of the 28 sums, the backup of the estimate, the counters.
 // Nothing here indexes a private array at run time.
 #pragma once
 #include <cmath>
 #include <cstdint>
 
 #include "orbhip.h"
-
-#if defined(__HIPCC__)
-#define PO_HD __host__ __device__ __forceinline__
-#else
-#define PO_HD inline
-#endif
+#include "orbhip_lm_core.h"
 
 namespace orbhip {
 
@@ -28,7 +25,6 @@ namespace orbhip {
 #endif
 constexpr int kPoTeam = ORBHIP_POSEOPT_TEAM;            // lanes of a team: part of the arithmetic, not of the launch
 constexpr int kPoWave = 64;
-constexpr double kPoDblMax = 1.7976931348623157e308;
 
 // ---- det_sincos64: fdlibm's __kernel_sin / __kernel_cos, a three-part Cody-Waite reduction ----------------------------
 constexpr double kS1 = -1.66666666666666324348e-01, kS2 = 8.33333333332248946124e-03, kS3 = -1.98412698298579493134e-04,
@@ -293,74 +289,6 @@ struct PoWs {
     int ne, cnt[3];
 };
 
-// pivoted LDLt of W.A (full symmetric 6x6), largest |d| first, the first of equals; W.b -> W.x when every pivot is > 0.
-// The matrix is held in registers: every index below is a compile-time constant once the loops are unrolled, and a pivot
-// found at run time is applied by comparing it with each candidate position in turn.
-PO_HD bool po_ldlt_solve(PoWs &W)
-{
-    double A[36], y[6];
-    int tr[6];
-#pragma unroll
-    for (int k = 0; k < 36; ++k) A[k] = W.A[k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        int p = k;
-        double big = fabs(A[k * 6 + k]);
-#pragma unroll
-        for (int i = k + 1; i < 6; ++i) {
-            const double v = fabs(A[i * 6 + i]);
-            if (v > big) { big = v; p = i; }
-        }
-        tr[k] = p;
-#pragma unroll
-        for (int q = k + 1; q < 6; ++q)
-            if (p == q) {
-#pragma unroll
-                for (int c = 0; c < 6; ++c) { const double t = A[k * 6 + c]; A[k * 6 + c] = A[q * 6 + c]; A[q * 6 + c] = t; }
-#pragma unroll
-                for (int r = 0; r < 6; ++r) { const double t = A[r * 6 + k]; A[r * 6 + k] = A[r * 6 + q]; A[r * 6 + q] = t; }
-            }
-        const double d = A[k * 6 + k];
-        if (!(d > 0)) return false;
-#pragma unroll
-        for (int i = k + 1; i < 6; ++i) {
-            const double l = A[i * 6 + k] / d;
-#pragma unroll
-            for (int j = k + 1; j <= i; ++j) {
-                A[i * 6 + j] = A[i * 6 + j] - l * A[j * 6 + k];
-                A[j * 6 + i] = A[i * 6 + j];
-            }
-        }
-#pragma unroll
-        for (int i = k + 1; i < 6; ++i) A[i * 6 + k] = A[i * 6 + k] / d;
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) y[k] = W.b[k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-#pragma unroll
-        for (int q = k + 1; q < 6; ++q)
-            if (tr[k] == q) { const double t = y[k]; y[k] = y[q]; y[q] = t; }
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = 0; j < i; ++j) y[i] = y[i] - A[i * 6 + j] * y[j];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) y[i] = y[i] / A[i * 6 + i];
-#pragma unroll
-    for (int i = 5; i >= 0; --i)
-#pragma unroll
-        for (int j = i + 1; j < 6; ++j) y[i] = y[i] - A[j * 6 + i] * y[j];
-#pragma unroll
-    for (int k = 5; k >= 0; --k)
-#pragma unroll
-        for (int q = k + 1; q < 6; ++q)
-            if (tr[k] == q) { const double t = y[k]; y[k] = y[q]; y[q] = t; }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) W.x[k] = y[k];
-    return true;
-}
-
 // ---- OptimizationAlgorithmLevenberg::solve, cut where the team has to sum ----------------------------------------------
 // after the sums at the estimate (:75-97)
 PO_HD void po_lm_begin(PoWs &W, const double *s)
@@ -369,19 +297,7 @@ PO_HD void po_lm_begin(PoWs &W, const double *s)
     for (int a = 0; a < 6; ++a)
         for (int b = a; b < 6; ++b) { W.H[a * 6 + b] = s[k]; W.H[b * 6 + a] = s[k]; ++k; }
     for (int a = 0; a < 6; ++a) W.b[a] = s[21 + a];
-    W.current = W.ini = s[27];
-    if (W.it == 0) {
-        double mx = 0.0;
-        for (int j = 0; j < 6; ++j) {
-            const double a = fabs(W.H[j * 6 + j]);
-            mx = a < mx ? mx : a;                                              // std::max(fabs(h), maxDiagonal)
-        }
-        W.lam = 1e-5 * mx;
-        W.ni = 2.0;
-        W.n_bad_lm = 0;
-    }
-    W.rho = 0.0;
-    W.qmax = 0;
+    lm_begin(W, s[27], W.it == 0 ? 1e-5 * lm_max_diag<6>(W.H) : 0.0);
 }
 // push, setLambda, solve, update (:103-121); returns ok2
 PO_HD bool po_lm_step(PoWs &W)
@@ -389,7 +305,7 @@ PO_HD bool po_lm_step(PoWs &W)
     for (int k = 0; k < 7; ++k) W.backup[k] = W.est[k];
     for (int k = 0; k < 36; ++k) W.A[k] = W.H[k];
     for (int j = 0; j < 6; ++j) W.A[j * 6 + j] = W.H[j * 6 + j] + W.lam;
-    const bool ok2 = po_ldlt_solve(W);                                         // a failure leaves the stale x
+    const bool ok2 = ldlt_solve_small<6>(W.A, W.b, W.x);                       // a failure leaves the stale x
     double u[6], e[7], d[7], o[7];
 #pragma unroll
     for (int k = 0; k < 6; ++k) u[k] = W.x[k];
@@ -404,35 +320,12 @@ PO_HD bool po_lm_step(PoWs &W)
 // :123-163 with the trial's chi2; sets W.again (another trial) and, when the iteration ends, W.stop (optimize() ends)
 PO_HD void po_lm_judge(PoWs &W, bool ok2, double temp)
 {
-    if (!ok2) temp = kPoDblMax;
-    double rho = W.current - temp;
-    double scale = 0.0;
-    for (int j = 0; j < 6; ++j) scale = scale + W.x[j] * (W.lam * W.x[j] + W.b[j]);
-    scale = scale + 1e-3;
-    rho = rho / scale;
-    if (rho > 0 && fabs(temp) <= kPoDblMax) {
-        const double y = 2 * rho - 1;
-        double alpha = 1.0 - (y * y) * y;
-        alpha = 2.0 / 3.0 < alpha ? 2.0 / 3.0 : alpha;                         // std::min(alpha, 2/3)
-        const double sf = 1.0 / 3.0 < alpha ? alpha : 1.0 / 3.0;                // std::max(1/3, alpha)
-        W.lam = W.lam * sf;
-        W.ni = 2.0;
-        W.current = temp;
-    } else {
-        W.lam = W.lam * W.ni;
-        W.ni = W.ni * 2;
+    if (!lm_gain(W, ok2, temp, lm_scale<6>(W.x, W.b, W.lam)))
         for (int k = 0; k < 7; ++k) W.est[k] = W.backup[k];
-    }
-    W.rho = rho;
-    W.qmax = W.qmax + 1;
-    W.again = rho < 0 && W.qmax < 10;
+    W.again = lm_retry(W);
     if (W.again) return;
     W.its_total = W.its_total + 1;
-    W.stop = 0;
-    if (W.qmax == 10 || rho == 0) { W.stop = 1; return; }
-    if ((W.ini - W.current) * 1e3 < W.ini) W.n_bad_lm = W.n_bad_lm + 1;
-    else W.n_bad_lm = 0;
-    if (W.n_bad_lm >= 3) W.stop = 1;
+    W.stop = lm_iteration_ok(W) ? 0 : 1;
 }
 
 // ---- one frame -----------------------------------------------------------------------------------------------------
@@ -588,12 +481,7 @@ template <class Team> PO_HD void po_run(Team &tm, PoWs &W, const PoFrame &F)
 }
 
 // ---- the host team: one thread that replays the device team's order ----------------------------------------------------
-struct PoHostTeam {
-    bool is0() const { return true; }
-    int first() const { return 0; }
-    int stride() const { return 1; }
-    void sync() {}
-    void add(int *dst, int v) { *dst += v; }
+struct PoHostTeam : HostTeam {
     template <bool FULL> void sum(PoWs &W, const PoFrame &F, bool kernel, double *s)
     {
         static thread_local double lanes[kPoTeam][28];
@@ -605,16 +493,7 @@ struct PoHostTeam {
             po_load_edge(F, j, e);
             po_edge_terms<FULL>(e, W.est, F.cam, kernel, lanes[j % kPoTeam]);
         }
-        for (int w0 = 0; w0 < kPoTeam; w0 += kPoWave) {
-            for (int off = 1; off < kPoWave; off <<= 1) {
-                double nxt[kPoWave][28];
-                for (int l = 0; l < kPoWave; ++l)
-                    for (int k = 0; k < 28; ++k) nxt[l][k] = lanes[w0 + l][k] + lanes[w0 + (l ^ off)][k];
-                for (int l = 0; l < kPoWave; ++l)
-                    for (int k = 0; k < 28; ++k) lanes[w0 + l][k] = nxt[l][k];
-            }
-            for (int k = 0; k < 28; ++k) s[k] = w0 == 0 ? lanes[0][k] : s[k] + lanes[w0][k];
-        }
+        host_team_combine<kPoTeam, 28>(lanes, FULL ? 0 : 27, s, TeamAdd());
     }
 };
 

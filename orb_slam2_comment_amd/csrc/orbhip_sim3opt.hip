@@ -14,23 +14,12 @@
 //                     from L2.  No float atomics, no scratch.
 #include "orbhip_internal.h"
 #include "orbhip_sim3opt_core.h"
+#include "orbhip_team_dev.h"
 
 namespace orbhip {
 namespace {
 
-struct S3oDevTeam {
-    int tid;
-    __device__ __forceinline__ bool is0() const { return tid == 0; }
-    __device__ __forceinline__ int first() const { return tid; }
-    __device__ __forceinline__ int stride() const { return kS3oTeam; }
-    __device__ __forceinline__ void sync()
-    {
-        if (kS3oTeam <= kS3oWave) wave_lds_handoff(); else __syncthreads();
-    }
-    __device__ __forceinline__ void add(int *dst, int v)
-    {
-        if (v) atomicAdd(dst, v);
-    }
+struct S3oDevTeam : DevTeam<kS3oTeam> {
     template <bool FULL> __device__ __forceinline__ void sum(S3oWs &W, const S3oCand &F, double *s)
     {
         double est[8], einv[8];
@@ -50,25 +39,7 @@ struct S3oDevTeam {
                 s3o_pair_chi(p, est, einv, F.cam, F.delta, F.dsqr, s);
             }
         }
-#pragma unroll
-        for (int off = 1; off < kS3oWave; off <<= 1) {
-#pragma unroll
-            for (int k = FULL ? 0 : kS3oSums - 1; k < kS3oSums; ++k) s[k] = s[k] + __shfl_xor(s[k], off);
-        }
-        if (kS3oTeam > kS3oWave) {
-            if ((tid & (kS3oWave - 1)) == 0) {
-#pragma unroll
-                for (int k = FULL ? 0 : kS3oSums - 1; k < kS3oSums; ++k) W.part[tid / kS3oWave][k] = s[k];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = FULL ? 0 : kS3oSums - 1; k < kS3oSums; ++k) {
-                double t = W.part[0][k];
-#pragma unroll
-                for (int w = 1; w < kS3oTeam / kS3oWave; ++w) t = t + W.part[w][k];
-                s[k] = t;
-            }
-        }
+        team_combine<kS3oTeam, FULL ? 0 : kS3oSums - 1, kS3oSums>(s, W.part, tid);
     }
 };
 

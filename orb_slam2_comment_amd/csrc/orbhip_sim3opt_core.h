@@ -9,6 +9,7 @@
 //     wavefront meet in an xor butterfly (offsets 1 .. 32), the wavefronts are added in wavefront order.
 //   - first / stride: how the per-pair loops and the 15 estimates of a linearisation are dealt out.
 //   - is0 / sync: lane 0 runs the serial state machine over the workspace (LDS on the device), everyone else waits.
+// The Levenberg-Marquardt rule, the 7x7 solver and the host replay of the team sum are orbhip_lm_core.h's, at dimension 7.
 // Nothing here indexes a private array at run time.
 #pragma once
 #include "orbhip_poseopt_core.h"
@@ -246,94 +247,14 @@ struct S3oWs {
     int ne, cnt[2];
 };
 
-// pivoted LDLt of W.A (full symmetric 7x7), largest |d| first, the first of equals; W.b -> W.x when every pivot is > 0:
-// po_ldlt_solve at N = 7, the matrix in registers, every index a compile-time constant once the loops are unrolled
-PO_HD bool s3o_ldlt_solve(S3oWs &W)
-{
-    constexpr int N = 7;
-    double A[N * N], y[N];
-    int tr[N];
-#pragma unroll
-    for (int k = 0; k < N * N; ++k) A[k] = W.A[k];
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        int p = k;
-        double big = fabs(A[k * N + k]);
-#pragma unroll
-        for (int i = k + 1; i < N; ++i) {
-            const double v = fabs(A[i * N + i]);
-            if (v > big) { big = v; p = i; }
-        }
-        tr[k] = p;
-#pragma unroll
-        for (int q = k + 1; q < N; ++q)
-            if (p == q) {
-#pragma unroll
-                for (int c = 0; c < N; ++c) { const double t = A[k * N + c]; A[k * N + c] = A[q * N + c]; A[q * N + c] = t; }
-#pragma unroll
-                for (int r = 0; r < N; ++r) { const double t = A[r * N + k]; A[r * N + k] = A[r * N + q]; A[r * N + q] = t; }
-            }
-        const double d = A[k * N + k];
-        if (!(d > 0)) return false;
-#pragma unroll
-        for (int i = k + 1; i < N; ++i) {
-            const double l = A[i * N + k] / d;
-#pragma unroll
-            for (int j = k + 1; j <= i; ++j) {
-                A[i * N + j] = A[i * N + j] - l * A[j * N + k];
-                A[j * N + i] = A[i * N + j];
-            }
-        }
-#pragma unroll
-        for (int i = k + 1; i < N; ++i) A[i * N + k] = A[i * N + k] / d;
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) y[k] = W.b[k];
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-#pragma unroll
-        for (int q = k + 1; q < N; ++q)
-            if (tr[k] == q) { const double t = y[k]; y[k] = y[q]; y[q] = t; }
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int j = 0; j < i; ++j) y[i] = y[i] - A[i * N + j] * y[j];
-#pragma unroll
-    for (int i = 0; i < N; ++i) y[i] = y[i] / A[i * N + i];
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i)
-#pragma unroll
-        for (int j = i + 1; j < N; ++j) y[i] = y[i] - A[j * N + i] * y[j];
-#pragma unroll
-    for (int k = N - 1; k >= 0; --k)
-#pragma unroll
-        for (int q = k + 1; q < N; ++q)
-            if (tr[k] == q) { const double t = y[k]; y[k] = y[q]; y[q] = t; }
-#pragma unroll
-    for (int k = 0; k < N; ++k) W.x[k] = y[k];
-    return true;
-}
-
-// ---- OptimizationAlgorithmLevenberg::solve at dimension 7, cut where the team has to sum (po_lm_* at 7) ---------------
+// ---- OptimizationAlgorithmLevenberg::solve at dimension 7, cut where the team has to sum ---------------------------------
 PO_HD void s3o_lm_begin(S3oWs &W, const double *s)
 {
     int k = 0;
     for (int a = 0; a < 7; ++a)
         for (int b = a; b < 7; ++b) { W.H[a * 7 + b] = s[k]; W.H[b * 7 + a] = s[k]; ++k; }
     for (int a = 0; a < 7; ++a) W.b[a] = s[28 + a];
-    W.current = W.ini = s[35];
-    if (W.it == 0) {
-        double mx = 0.0;
-        for (int j = 0; j < 7; ++j) {
-            const double a = fabs(W.H[j * 7 + j]);
-            mx = a < mx ? mx : a;                                              // std::max(fabs(h), maxDiagonal)
-        }
-        W.lam = 1e-5 * mx;
-        W.ni = 2.0;
-        W.n_bad_lm = 0;
-    }
-    W.rho = 0.0;
-    W.qmax = 0;
+    lm_begin(W, s[35], W.it == 0 ? 1e-5 * lm_max_diag<7>(W.H) : 0.0);
 }
 // push, setLambda, solve, oplus; returns ok2.  VertexSim3Expmap::oplusImpl zeroes update[6] in the solver's own vector
 PO_HD bool s3o_lm_step(S3oWs &W, bool fix_scale)
@@ -341,7 +262,7 @@ PO_HD bool s3o_lm_step(S3oWs &W, bool fix_scale)
     for (int k = 0; k < 8; ++k) W.backup[k] = W.est[k];
     for (int k = 0; k < 49; ++k) W.A[k] = W.H[k];
     for (int j = 0; j < 7; ++j) W.A[j * 7 + j] = W.H[j * 7 + j] + W.lam;
-    const bool ok2 = s3o_ldlt_solve(W);                                        // a failure leaves the stale x
+    const bool ok2 = ldlt_solve_small<7>(W.A, W.b, W.x);                       // a failure leaves the stale x
     if (fix_scale) W.x[6] = 0.0;
     double u[7], e[8], d[8], o[8], oi[8];
 #pragma unroll
@@ -357,35 +278,12 @@ PO_HD bool s3o_lm_step(S3oWs &W, bool fix_scale)
 }
 PO_HD void s3o_lm_judge(S3oWs &W, bool ok2, double temp)
 {
-    if (!ok2) temp = kPoDblMax;
-    double rho = W.current - temp;
-    double scale = 0.0;
-    for (int j = 0; j < 7; ++j) scale = scale + W.x[j] * (W.lam * W.x[j] + W.b[j]);
-    scale = scale + 1e-3;
-    rho = rho / scale;
-    if (rho > 0 && fabs(temp) <= kPoDblMax) {
-        const double y = 2 * rho - 1;
-        double alpha = 1.0 - (y * y) * y;
-        alpha = 2.0 / 3.0 < alpha ? 2.0 / 3.0 : alpha;                         // std::min(alpha, 2/3)
-        const double sf = 1.0 / 3.0 < alpha ? alpha : 1.0 / 3.0;                // std::max(1/3, alpha)
-        W.lam = W.lam * sf;
-        W.ni = 2.0;
-        W.current = temp;
-    } else {
-        W.lam = W.lam * W.ni;
-        W.ni = W.ni * 2;
+    if (!lm_gain(W, ok2, temp, lm_scale<7>(W.x, W.b, W.lam)))
         for (int k = 0; k < 8; ++k) W.est[k] = W.backup[k];
-    }
-    W.rho = rho;
-    W.qmax = W.qmax + 1;
-    W.again = rho < 0 && W.qmax < 10;
+    W.again = lm_retry(W);
     if (W.again) return;
     W.its = W.its + 1;
-    W.stop = 0;
-    if (W.qmax == 10 || rho == 0) { W.stop = 1; return; }
-    if ((W.ini - W.current) * 1e3 < W.ini) W.n_bad_lm = W.n_bad_lm + 1;
-    else W.n_bad_lm = 0;
-    if (W.n_bad_lm >= 3) W.stop = 1;
+    W.stop = lm_iteration_ok(W) ? 0 : 1;
 }
 
 // ---- one candidate --------------------------------------------------------------------------------------------------
@@ -593,12 +491,7 @@ template <class Team> PO_HD void s3o_run(Team &tm, S3oWs &W, const S3oCand &F)
 }
 
 // ---- the host team: one thread that replays the device team's order ----------------------------------------------------
-struct S3oHostTeam {
-    bool is0() const { return true; }
-    int first() const { return 0; }
-    int stride() const { return 1; }
-    void sync() {}
-    void add(int *dst, int v) { *dst += v; }
+struct S3oHostTeam : HostTeam {
     template <bool FULL> void sum(S3oWs &W, const S3oCand &F, double *s)
     {
         static thread_local double lanes[kS3oTeam][kS3oSums];
@@ -616,16 +509,7 @@ struct S3oHostTeam {
                 s3o_pair_chi(p, W.est, W.einv, F.cam, F.delta, F.dsqr, acc);
             }
         }
-        for (int w0 = 0; w0 < kS3oTeam; w0 += kS3oWave) {
-            for (int off = 1; off < kS3oWave; off <<= 1) {
-                double nxt[kS3oWave][kS3oSums];
-                for (int l = 0; l < kS3oWave; ++l)
-                    for (int k = 0; k < kS3oSums; ++k) nxt[l][k] = lanes[w0 + l][k] + lanes[w0 + (l ^ off)][k];
-                for (int l = 0; l < kS3oWave; ++l)
-                    for (int k = 0; k < kS3oSums; ++k) lanes[w0 + l][k] = nxt[l][k];
-            }
-            for (int k = 0; k < kS3oSums; ++k) s[k] = w0 == 0 ? lanes[0][k] : s[k] + lanes[w0][k];
-        }
+        host_team_combine<kS3oTeam, kS3oSums>(lanes, FULL ? 0 : kS3oSums - 1, s, TeamAdd());
     }
 };
 

@@ -115,6 +115,10 @@ def _case(name):
         sc, sim3 = case("A")
         one = dict(sc, C=1, kf_index=sc["kf_index"][2:3], m_points=sc["m_points"][2:3], m_slots=sc["m_slots"][2:3])
         return one, sim3[2:3]
+    if name == "nan_pair":                           # the scene of test_nan_pair_is_kept: no factorisation succeeds
+        sc = small()
+        sc["T"]["world"][int(sc["m_points"][0][3])] = np.nan
+        return sc, sim3_record(K.SIM3_A)
     raise KeyError(name)
 
 
@@ -676,7 +680,8 @@ def run_host(sc, sim3, form, fix_scale, select, tmp_path, tag, fill=0):
 
 
 HOST_CASES = [("A", S3.MATCH_POINTS, False, None), ("A", S3.MATCH_SLOTS, True, None), ("A", S3.MATCH_POINTS, False, (1, 0, 1)),
-              ("B", S3.MATCH_POINTS, False, None), ("B", S3.MATCH_POINTS, True, None), ("A_alone", S3.MATCH_POINTS, False, None)]
+              ("B", S3.MATCH_POINTS, False, None), ("B", S3.MATCH_POINTS, True, None), ("A_alone", S3.MATCH_POINTS, False, None),
+              ("nan_pair", S3.MATCH_POINTS, False, None)]
 
 
 @pytest.mark.parametrize("k,fill", with_fills(range(len(HOST_CASES))))
