@@ -263,6 +263,13 @@ int orbhip_blurred_level_download(orbhip_extractor *e, int frame, int level, uin
 /* FAST candidates of a level in reference order: x,y (relative to minBorder), score. */
 int orbhip_level_candidates(orbhip_extractor *e, int frame, int level, int32_t *x, int32_t *y,
                             int32_t *score, int cap, int *n);
+/* Host only, no device: the FAST kernel's cell records for an image size, six int32 per cell in table order -- level,
+ * sub-image width and height (detection rectangle + 6), the row multiplier ceil(2^18 / groups of four columns), the
+ * work items of a row band that cannot overflow the survivor list, the multiplier ceil(2^20 / detection columns) of
+ * the banded non-maximum suppression -- and the survivor-list capacity they were made for.  *n is the number of cells;
+ * ORBHIP_E_CAPACITY when cap is smaller (the first cap records are written). */
+int orbhip_fast_cell_table(int nfeatures, float scale_factor, int nlevels, int rows, int cols,
+                           int32_t *rec, int cap, int *n, int *list_cap);
 
 /* Per-stage device time, microseconds, averaged over the extract calls made since
  * orbhip_extractor_set_profiling(e, 1) (at most the last 256), measured with HIP events on the

@@ -238,6 +238,7 @@ SYMBOLS = [
     ("orbhip_pyramid_level_download", _i, [_vp, _i, _i, _i, _vp, _i]),
     ("orbhip_blurred_level_download", _i, [_vp, _i, _i, _vp, _i]),
     ("orbhip_level_candidates", _i, [_vp, _i, _i, _vp, _vp, _vp, _i, _pi]),
+    ("orbhip_fast_cell_table", _i, [_i, _f, _i, _i, _i, _vp, _i, _pi, _pi]),
     ("orbhip_extractor_set_profiling", _i, [_vp, _i]),
     ("orbhip_extractor_stage_times", _i, [_vp, _vp]),
     ("orbhip_matcher_create", _i, [_i, C.POINTER(_vp)]),

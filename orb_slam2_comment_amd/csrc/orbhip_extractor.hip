@@ -705,7 +705,7 @@ __device__ __forceinline__ unsigned long long stamp_now()
 #ifndef ORBHIP_FAST_WAVES
 #define ORBHIP_FAST_WAVES 8   // resident waves per SIMD = what the LDS share of bind_geometry admits (32 workgroups per CU)
 #endif
-template <int SW, bool STAMPS = false, int STAGE = kFastStage>
+template <int SW, bool STAMPS = false, int STAGE = kFastStage, int FIX = kFastFix>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORBHIP_FAST_WAVES, ORBHIP_FAST_WAVES))) void k_fast_cells(const uint8_t *__restrict__ pyr, const FastCell *__restrict__ cells,
                                                     int *__restrict__ cell_cnt, uint32_t *__restrict__ cell_kp,
                                                     FastParams P, const uint8_t *__restrict__ images, size_t frame_stride)
@@ -796,6 +796,36 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORBHIP_FAST_
                     // the compiler, so the statement that writes it reads it and puts the old value back.  The compiler does
                     // not count these loads: the s_waitcnt below is theirs.
                     const uint32_t img_lds = (uint32_t)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint32_t *)simg);
+                    if constexpr ((FIX & kFastFixDma) != 0) {
+                        // All row groups in ONE statement: M0 is saved and restored once, the global row pointer and the LDS
+                        // base advance by running scalar adds (RPI rows each), and the loop ends when the next LDS base reaches
+                        // the last group's, which is peeled: it is based at row sh - RPI wherever the running base stands
+                        // ((ngroups - 2) * RPI < sh - RPI <= (ngroups - 1) * RPI, and ngroups >= 2 because sh >= 7 > RPI).
+                        // The running pointer is a fixed register pair: the 64-bit add needs its halves by name.  Every
+                        // scalar register a DMA reads is written by a scalar instruction at least three instructions before
+                        // it, or by the s_mov / s_nop pair in front of it (the M0 rule).
+                        uintptr_t rowp = reinterpret_cast<uintptr_t>(sb);
+                        const uintptr_t lastp = reinterpret_cast<uintptr_t>(sb) + (uint32_t)(last * pitch);
+                        const uint32_t lds_last = img_lds + (uint32_t)(last * SB), step = (uint32_t)(RPI * pitch);
+                        uint32_t keep;
+                        asm volatile("s_mov_b32 %0, m0\n\t"
+                                     "s_mov_b32 m0, %4\n\t"
+                                     "s_nop 0\n"
+                                     "1:\n\t"
+                                     "global_load_lds_dword %2, s[30:31]\n\t"
+                                     "s_add_u32 m0, m0, %7\n\t"
+                                     "s_add_u32 s30, s30, %3\n\t"
+                                     "s_addc_u32 s31, s31, 0\n\t"
+                                     "s_cmp_lt_u32 m0, %5\n\t"
+                                     "s_cbranch_scc1 1b\n\t"
+                                     "s_mov_b32 m0, %5\n\t"
+                                     "s_nop 0\n\t"
+                                     "global_load_lds_dword %2, %6\n\t"
+                                     "s_mov_b32 m0, %0"
+                                     : "=&s"(keep), "+{s[30:31]}"(rowp)
+                                     : "v"(voff), "s"(step), "s"(img_lds), "s"(lds_last), "s"(lastp), "i"(RPI * SB)
+                                     : "memory", "scc");
+                    } else
                     for (int g = 0; g < ngroups; ++g) {
                         const int row = min(g * RPI, last);
                         const uintptr_t rowp = reinterpret_cast<uintptr_t>(sb) + (uint32_t)(row * pitch);
@@ -880,7 +910,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORBHIP_FAST_
     // cell within 256 entries of the capacity to the band path).  A round whose survivor count exceeds the capacity is repeated in bands
     // of rows that cannot overflow (4 * ngrp pixels per row); banded rounds leave their corners in the score map only and
     // the NMS walks the map instead of the corner list.
-    const int band_items = (P.list_cap / (4 * ngrp)) * ngrp;
+    // The band size comes with the cell record (make_fast_cell): a division here would be paid by every wave for a path
+    // that almost none takes.
+    int band_items;
+    if constexpr ((FIX & kFastFixDiv) != 0) band_items = cd.band_items;
+    else band_items = (P.list_cap / (4 * ngrp)) * ngrp;
     int total = 0;
     for (int pass = 0; pass < 2; ++pass) {
         // the reference calls FAST(iniThFAST) first and FAST(minThFAST) only for cells that kept nothing (:809-816)
@@ -925,18 +959,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORBHIP_FAST_
                     m[1 - h] = __builtin_amdgcn_ballot_w64((unsigned short)M > (unsigned short)(h ? Te_lo : Tn_lo));
                     m[3 - h] = __builtin_amdgcn_ballot_w64(M > (h ? Te_hi : Tn_hi));
                 }
-                const unsigned long long mlive = __builtin_amdgcn_ballot_w64(it4 < lim4),
-                                         mlast = __builtin_amdgcn_ballot_w64((uint8_t)ent == (uint8_t)last4);
+                // live lanes: the low band_hi - it0 of the wave (1 .. 64 and more), a shift on the scalar unit
+                unsigned long long mlive;
+                if constexpr ((FIX & kFastFixMask) != 0) mlive = ~0ull >> max(64 - (band_hi - it0), 0);
+                else mlive = __builtin_amdgcn_ballot_w64(it4 < lim4);
+                const unsigned long long mlast = __builtin_amdgcn_ballot_w64((uint8_t)ent == (uint8_t)last4);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) m[j] &= j ? mlive & ~(en[j] & mlast) : mlive;      // pixel 0 of a group is always inside
                 // ordered append: lane-major, then pixel = row-major (y, x), the order the reference emits keypoints in; every
                 // later compaction is stable, so the final list needs no sorting
-                int pos = __builtin_amdgcn_mbcnt_hi((unsigned)(m[0] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m[0], (unsigned)nsurv));
+                // the count so far seeds the chain from a register, or (kFastFixMask) enters with the list's scalar base
+                constexpr bool sseed = (FIX & kFastFixMask) != 0;
+                int pos = __builtin_amdgcn_mbcnt_hi((unsigned)(m[0] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m[0], sseed ? 0u : (unsigned)nsurv));
 #pragma unroll
                 for (int j = 1; j < 4; ++j)
                     pos = __builtin_amdgcn_mbcnt_hi((unsigned)(m[j] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m[j], (unsigned)pos));
+                lds_u16 *dst = sseed ? (slist + nsurv) + pos : slist + pos;
                 nsurv += __popcll(m[0]) + __popcll(m[1]) + __popcll(m[2]) + __popcll(m[3]);
-                lds_u16 *dst = slist + pos;
                 uint32_t ev = (uint32_t)ent;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -1018,19 +1057,42 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORBHIP_FAST_
         // ---- NMS over the corner list (banded rounds: over every pixel of the score map) + emission, row-major already ----
         int nfin = 0;
         const int ncand = banded ? dw * dh : ncorn;
-        for (int i0 = 0; i0 < ncand; i0 += 64) {
-            const int i = i0 + lane, ic = min(i, ncand - 1);
-            int y, colr;
-            if (banded) { y = ic / dw; colr = ic - y * dw; }
-            else { const unsigned e = slist[ic]; y = e >> 8; colr = e & 255; }
+        // one candidate per lane: strict maximum of its 8 neighbours -> the cell's output slots, in order
+        auto nms_emit = [&](bool live, int y, int colr) {
             const uint8_t *s = score8 + madi24(y, SS, colr);           // top-left neighbour
             const int v = s[SS + 1];
             const int nb = max3i(max3i(s[0], s[1], s[2]), max3i(s[SS], s[SS + 2], s[2 * SS]), max((int)s[2 * SS + 1], (int)s[2 * SS + 2]));
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(i < ncand) & __builtin_amdgcn_ballot_w64(v > nb);
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(live) & __builtin_amdgcn_ballot_w64(v > nb);
             const int pos = nfin + lane_prefix(m);
             if (__builtin_amdgcn_inverse_ballot_w64(m & __builtin_amdgcn_ballot_w64(pos < P.slot_cap)))
                 out[pos] = (uint32_t)(colr + kpx) | ((uint32_t)(y + kpy) << 12) | ((uint32_t)v << 24);
             nfin += __popcll(m);
+        };
+        if constexpr ((FIX & kFastFixDiv) != 0) {
+            // the banded walk has a loop of its own, so that the list-driven one carries no division for the compiler to
+            // hoist to the top of the kernel; its row comes from the record's multiplier (make_fast_cell: exact below dw * dh)
+            if (banded) {
+                const uint32_t nmag = cd.nms_magic;
+                for (int i0 = 0; i0 < ncand; i0 += 64) {
+                    const int i = i0 + lane, ic = min(i, ncand - 1);
+                    const int y = (int)(mulu24_s((uint32_t)ic, nmag) >> 20);
+                    nms_emit(i < ncand, y, ic - (int)mulu24_s((uint32_t)y, (uint32_t)dw));
+                }
+            } else {
+                for (int i0 = 0; i0 < ncand; i0 += 64) {
+                    const int i = i0 + lane;
+                    const unsigned e = slist[min(i, ncand - 1)];
+                    nms_emit(i < ncand, e >> 8, e & 255);
+                }
+            }
+        } else {
+            for (int i0 = 0; i0 < ncand; i0 += 64) {
+                const int i = i0 + lane, ic = min(i, ncand - 1);
+                int y, colr;
+                if (banded) { y = ic / dw; colr = ic - y * dw; }
+                else { const unsigned e = slist[ic]; y = e >> 8; colr = e & 255; }
+                nms_emit(i < ncand, y, colr);
+            }
         }
         total = nfin;
         FAST_STAMP(4);   // NMS + emission
@@ -2203,7 +2265,7 @@ static int build_pyr_tables(orbhip_extractor *e)
 
 // One cell of the FAST kernel's table.  img_stride > 0: a level-0 cell that reads the caller's image (row stride
 // img_stride) instead of the padded level-0 plane.
-static FastCell make_fast_cell(const PyrGeom &G, const CellDesc &c, int img_stride)
+static FastCell make_fast_cell(const PyrGeom &G, const CellDesc &c, int img_stride, int list_cap)
 {
     const LevelGeom &Lc = G.lv[c.level];
     FastCell f; memset(&f, 0, sizeof(f));
@@ -2225,6 +2287,11 @@ static FastCell make_fast_cell(const PyrGeom &G, const CellDesc &c, int img_stri
     const int dwc = sw - 6, c_lo = a + 7, c_hi = c_lo + dwc;
     const int ngrp = dwc > 0 ? ((c_hi - 1) >> 2) - (c_lo >> 2) + 1 : 1;
     f.magic = ((1u << 18) + ngrp - 1) / ngrp;
+    // what a wavefront would otherwise divide for: the row band of a round that overflowed the survivor list (whole rows
+    // of 4 * ngrp pixels that fit list_cap entries), and the row / column split of the banded NMS (exact while
+    // i * (nms_magic * dw - 2^20) < 2^20: i < dw * dh <= 66 * 66, the excess is below dw <= 66)
+    f.band_items = (unsigned short)((list_cap / (4 * ngrp)) * ngrp);
+    f.nms_magic = dwc > 0 ? ((1u << 20) + dwc - 1) / dwc : 0;
     return f;
 }
 
@@ -2277,6 +2344,7 @@ static int fast_lds_layout(orbhip_extractor *e)
 
 // Bind the handle to an image size: level geometry (:1111-1113), cell table (:769-829),
 // OpenCV resize tables, blur tiles.
+static int geometry_tables(orbhip_extractor *e, int rows, int cols);
 static int bind_geometry(orbhip_extractor *e, int rows, int cols)
 {
     if (e->bound && e->G.rows == rows && e->G.cols == cols) return ORBHIP_OK;
@@ -2284,6 +2352,26 @@ static int bind_geometry(orbhip_extractor *e, int rows, int cols)
     ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
     free_geometry(e);
     free_batch(e);
+    if (int rc = geometry_tables(e, rows, cols)) return rc;
+    if (!e->cells.empty()) {
+        ORBHIP_HIP_CHECK(hipMalloc(&e->d_cells, e->cells.size() * sizeof(CellDesc)));
+        ORBHIP_HIP_CHECK(hipMemcpyAsync(e->d_cells, e->cells.data(), e->cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice, e->stream));
+        ORBHIP_HIP_CHECK(hipMalloc(&e->d_cells2, e->cells2.size() * sizeof(FastCell)));
+        ORBHIP_HIP_CHECK(hipMemcpyAsync(e->d_cells2, e->cells2.data(), e->cells2.size() * sizeof(FastCell), hipMemcpyHostToDevice, e->stream));
+    }
+    ORBHIP_HIP_CHECK(hipMalloc(&e->d_tiles, e->tiles.size() * sizeof(TileDesc)));
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(e->d_tiles, e->tiles.data(), e->tiles.size() * sizeof(TileDesc), hipMemcpyHostToDevice, e->stream));
+    // uploads go through the handle's own stream (a legacy-stream hipMemcpy would tangle with another host thread's
+    // stream capture: the stereo constructor runs two extractors on two threads); the host vectors die at return
+    ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
+    if (int rc = build_pyr_tables(e)) return rc;
+    e->bound = true;
+    return ORBHIP_OK;
+}
+
+// The host half of bind_geometry: everything that follows from the image size alone, no device call.
+static int geometry_tables(orbhip_extractor *e, int rows, int cols)
+{
     PyrGeom &G = e->G;
     memset(&G, 0, sizeof(G));
     G.nlevels = e->nlevels; G.rows = rows; G.cols = cols; G.ini_th = e->iniTh; G.min_th = e->minTh;
@@ -2355,7 +2443,7 @@ static int bind_geometry(orbhip_extractor *e, int rows, int cols)
     memset(&e->fast_params, 0, sizeof(e->fast_params));
     if (int rc = fast_lds_layout(e)) return rc;
     e->cells2.clear();
-    for (const CellDesc &c : e->cells) e->cells2.push_back(make_fast_cell(G, c, 0));
+    for (const CellDesc &c : e->cells) e->cells2.push_back(make_fast_cell(G, c, 0, e->fast_lds.list_cap));
     e->cells_stride = 0;
     e->fast_params.ini_th = G.ini_th; e->fast_params.min_th = G.min_th;
     G.frame_bytes = off;
@@ -2383,19 +2471,6 @@ static int bind_geometry(orbhip_extractor *e, int rows, int cols)
     else { set_error("nfeatures too large for the octree kernel (per-level cap %d > 2048)", maxn); return ORBHIP_E_ARG; }
     if (G.ncells_total == 0) { /* tiny image: no FAST cells anywhere; still a valid (empty) result */ }
     e->fast_params.frame_bytes = G.frame_bytes; e->fast_params.ncells_total = G.ncells_total; e->fast_params.slot_cap = G.slot_cap;
-    if (!e->cells.empty()) {
-        ORBHIP_HIP_CHECK(hipMalloc(&e->d_cells, e->cells.size() * sizeof(CellDesc)));
-        ORBHIP_HIP_CHECK(hipMemcpyAsync(e->d_cells, e->cells.data(), e->cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice, e->stream));
-        ORBHIP_HIP_CHECK(hipMalloc(&e->d_cells2, e->cells2.size() * sizeof(FastCell)));
-        ORBHIP_HIP_CHECK(hipMemcpyAsync(e->d_cells2, e->cells2.data(), e->cells2.size() * sizeof(FastCell), hipMemcpyHostToDevice, e->stream));
-    }
-    ORBHIP_HIP_CHECK(hipMalloc(&e->d_tiles, e->tiles.size() * sizeof(TileDesc)));
-    ORBHIP_HIP_CHECK(hipMemcpyAsync(e->d_tiles, e->tiles.data(), e->tiles.size() * sizeof(TileDesc), hipMemcpyHostToDevice, e->stream));
-    // uploads go through the handle's own stream (a legacy-stream hipMemcpy would tangle with another host thread's
-    // stream capture: the stereo constructor runs two extractors on two threads); the host vectors die at return
-    ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
-    if (int rc = build_pyr_tables(e)) return rc;
-    e->bound = true;
     return ORBHIP_OK;
 }
 
@@ -2436,7 +2511,7 @@ static int begin_extraction(orbhip_extractor *e, const uint8_t *d_images, int st
         ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
         drop_graph(e);
         for (size_t i = 0; i < e->cells.size(); ++i)
-            if (e->cells[i].level == 0) e->cells2[i] = make_fast_cell(e->G, e->cells[i], want);
+            if (e->cells[i].level == 0) e->cells2[i] = make_fast_cell(e->G, e->cells[i], want, e->fast_lds.list_cap);
         ORBHIP_HIP_CHECK(hipMemcpyAsync(e->d_cells2, e->cells2.data(), e->cells2.size() * sizeof(FastCell), hipMemcpyHostToDevice, e->stream));
         ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
     }
@@ -2589,25 +2664,33 @@ static int launch_pipeline(orbhip_extractor *e, const uint8_t *d_images, int bat
         if ((unsigned long long)G.ncells_total * G.ncells_total * (unsigned long long)batch >= (1ull << 32)) {
             set_error("batch too large for the FAST kernel's work mapping"); return ORBHIP_E_SIZE;
         }
-#define ORBHIP_FAST3(SWv, STv, MDv) hipLaunchKernelGGL((k_fast_cells<SWv, STv, MDv>), grid, dim3(64), lb, s, b_pyr, e->d_cells2, b_cell_cnt, b_cell_kp, P, d_images, frame_stride)
-#define ORBHIP_FAST2(MDv) switch (e->fast_lds.strideW) { \
-        case 11: ORBHIP_FAST3(11, false, MDv); break; \
-        case 13: ORBHIP_FAST3(13, false, MDv); break; \
-        case 15: ORBHIP_FAST3(15, false, MDv); break; \
-        case 17: ORBHIP_FAST3(17, false, MDv); break; \
-        default: ORBHIP_FAST3(21, false, MDv); break; \
+#define ORBHIP_FAST3(SWv, STv, MDv, FXv) hipLaunchKernelGGL((k_fast_cells<SWv, STv, MDv, FXv>), grid, dim3(64), lb, s, b_pyr, e->d_cells2, b_cell_cnt, b_cell_kp, P, d_images, frame_stride)
+#define ORBHIP_FAST2(MDv, FXv) switch (e->fast_lds.strideW) { \
+        case 11: ORBHIP_FAST3(11, false, MDv, FXv); break; \
+        case 13: ORBHIP_FAST3(13, false, MDv, FXv); break; \
+        case 15: ORBHIP_FAST3(15, false, MDv, FXv); break; \
+        case 17: ORBHIP_FAST3(17, false, MDv, FXv); break; \
+        default: ORBHIP_FAST3(21, false, MDv, FXv); break; \
         }
 #ifdef ORBHIP_DEVTOOLS
         P.dev = e->fast_variant % 10;
+        constexpr int kFixA = kFastFixDiv, kFixAB = kFastFixDiv | kFastFixDma, kFixABC = kFixAB | kFastFixMask;
+        const int fx = e->fast_fix;   // the steps towards kFastFix exist beside the LDS-DMA staging only
         if (P.dev == 2 && e->fast_lds.strideW == 11) {   // stamped diagnostic build (tools/fast_ab.py)
-            if (e->fast_stage == kFastStageBatch) ORBHIP_FAST3(11, true, kFastStageBatch);
-            else if (e->fast_stage == kFastStageDense) ORBHIP_FAST3(11, true, kFastStageDense);
-            else ORBHIP_FAST3(11, true, kFastStageDma);
-        } else if (e->fast_stage == kFastStageBatch) { ORBHIP_FAST2(kFastStageBatch) }
-        else if (e->fast_stage == kFastStageDense) { ORBHIP_FAST2(kFastStageDense) }
-        else { ORBHIP_FAST2(kFastStageDma) }
+            if (e->fast_stage == kFastStageBatch) ORBHIP_FAST3(11, true, kFastStageBatch, kFastFix);
+            else if (e->fast_stage == kFastStageDense) ORBHIP_FAST3(11, true, kFastStageDense, kFastFix);
+            else if (fx == 0) ORBHIP_FAST3(11, true, kFastStageDma, 0);
+            else if (fx == kFixA) ORBHIP_FAST3(11, true, kFastStageDma, kFixA);
+            else if (fx == kFixAB) ORBHIP_FAST3(11, true, kFastStageDma, kFixAB);
+            else ORBHIP_FAST3(11, true, kFastStageDma, kFixABC);
+        } else if (e->fast_stage == kFastStageBatch) { ORBHIP_FAST2(kFastStageBatch, kFastFix) }
+        else if (e->fast_stage == kFastStageDense) { ORBHIP_FAST2(kFastStageDense, kFastFix) }
+        else if (fx == 0) { ORBHIP_FAST2(kFastStageDma, 0) }
+        else if (fx == kFixA) { ORBHIP_FAST2(kFastStageDma, kFixA) }
+        else if (fx == kFixAB) { ORBHIP_FAST2(kFastStageDma, kFixAB) }
+        else { ORBHIP_FAST2(kFastStageDma, kFixABC) }
 #else
-        ORBHIP_FAST2(kFastStage)
+        ORBHIP_FAST2(kFastStage, kFastFix)
 #endif
 #undef ORBHIP_FAST2
 #undef ORBHIP_FAST3
@@ -2759,24 +2842,12 @@ int orbhip_device_count(int *count)
     return ORBHIP_OK;
 }
 
-int orbhip_extractor_create(int nfeatures, float scale_factor, int nlevels, int ini_th, int min_th,
-                            int device, orbhip_extractor **out)
+// The part of a handle that needs no device: parameters, scale tables and quotas (src/ORBextractor.cc:415-446), the
+// orientation disc and the blur weights.
+static void init_host_tables(orbhip_extractor *e, int nfeatures, float scale_factor, int nlevels, int ini_th, int min_th)
 {
-    if (!out || nlevels < 1 || nlevels > ORBHIP_MAX_LEVELS || nfeatures < 0 || !(scale_factor > 1.0f)) {
-        set_error("orbhip_extractor_create: bad argument");
-        return ORBHIP_E_ARG;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_error("no HIP device %d (found %d)", device, ndev);
-        return ORBHIP_E_NODEVICE;
-    }
-    orbhip_extractor *e = new (std::nothrow) orbhip_extractor();
-    if (!e) return ORBHIP_E_ARG;
     e->nfeatures = nfeatures; e->scaleFactor = scale_factor; e->nlevels = nlevels;
     e->iniTh = std::min(std::max(ini_th, 0), 255); e->minTh = std::min(std::max(min_th, 0), 255);
-    e->device = device;
-    // scale tables and quotas, src/ORBextractor.cc:415-446
     e->sf[0] = 1.0f; e->sig2[0] = 1.0f;
     for (int i = 1; i < nlevels; ++i) { e->sf[i] = (float)(e->sf[i - 1] * e->scaleFactor); e->sig2[i] = e->sf[i] * e->sf[i]; }
     for (int i = 0; i < nlevels; ++i) { e->isf[i] = 1.0f / e->sf[i]; e->isig2[i] = 1.0f / e->sig2[i]; }
@@ -2792,6 +2863,24 @@ int orbhip_extractor_create(int nfeatures, float scale_factor, int nlevels, int 
     for (v = kHalfPatch, v0 = 0; v >= vmin; --v) { while (e->umax[v0] == e->umax[v0 + 1]) ++v0; e->umax[v] = v0; ++v0; }
     const int bw[7] = {18, 34, 49, 55, 49, 34, 18};
     for (int i = 0; i < 7; ++i) e->blurw.w[i] = bw[i];
+}
+
+int orbhip_extractor_create(int nfeatures, float scale_factor, int nlevels, int ini_th, int min_th,
+                            int device, orbhip_extractor **out)
+{
+    if (!out || nlevels < 1 || nlevels > ORBHIP_MAX_LEVELS || nfeatures < 0 || !(scale_factor > 1.0f)) {
+        set_error("orbhip_extractor_create: bad argument");
+        return ORBHIP_E_ARG;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        set_error("no HIP device %d (found %d)", device, ndev);
+        return ORBHIP_E_NODEVICE;
+    }
+    orbhip_extractor *e = new (std::nothrow) orbhip_extractor();
+    if (!e) return ORBHIP_E_ARG;
+    e->device = device;
+    init_host_tables(e, nfeatures, scale_factor, nlevels, ini_th, min_th);
 
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking) != hipSuccess) {
         set_error("hipSetDevice/hipStreamCreate failed");
@@ -3529,6 +3618,27 @@ int orbhip_level_candidates(orbhip_extractor *e, int frame, int level, int32_t *
     return k > cap ? ORBHIP_E_CAPACITY : ORBHIP_OK;
 }
 
+int orbhip_fast_cell_table(int nfeatures, float scale_factor, int nlevels, int rows, int cols, int32_t *rec, int cap, int *n, int *list_cap)
+{
+    if (!n || nlevels < 1 || nlevels > ORBHIP_MAX_LEVELS || nfeatures < 0 || !(scale_factor > 1.0f) || rows <= 0 || cols <= 0 || cap < 0) return ORBHIP_E_ARG;
+    orbhip_extractor *e = new (std::nothrow) orbhip_extractor();   // host tables only: it owns no device resource
+    if (!e) return ORBHIP_E_ARG;
+    init_host_tables(e, nfeatures, scale_factor, nlevels, 20, 7);
+    int rc = geometry_tables(e, rows, cols);
+    if (rc == ORBHIP_OK) {
+        *n = (int)e->cells2.size();
+        if (list_cap) *list_cap = e->fast_lds.list_cap;
+        for (int i = 0; rec && i < *n && i < cap; ++i) {
+            const FastCell &f = e->cells2[i];
+            int32_t *r = rec + 6 * (size_t)i;
+            r[0] = e->cells[i].level; r[1] = f.sw; r[2] = f.sh; r[3] = (int32_t)f.magic; r[4] = f.band_items; r[5] = (int32_t)f.nms_magic;
+        }
+        if (*n > cap) rc = ORBHIP_E_CAPACITY;
+    }
+    delete e;
+    return rc;
+}
+
 #ifdef ORBHIP_DEVTOOLS
 // development exports (not part of include/orbhip.h, absent from the product library): tools/coexec.py, tools/fast_ab.py
 int orbhip_dev_set_stage_mask(orbhip_extractor *e, int mask) { if (!e) return ORBHIP_E_ARG; e->stage_mask = mask; return ORBHIP_OK; }
@@ -3540,14 +3650,24 @@ int orbhip_dev_set_fast_variant(orbhip_extractor *e, int v)
     if (!e) return ORBHIP_E_ARG;
     // ones: 0 product; 2 stamped diagnostic build; 3 / 4 exit after the prologue / after staging.  Tens: the staging,
     // 0 the product's, 1 whole batches of row groups (as before the dense layout), 2 dense through registers, 3 LDS-DMA
-    const int st = v / 10;
-    if (v < 0 || st > 3) return ORBHIP_E_ARG;
+    // Hundreds: the fixed-cost parts beside the LDS-DMA staging, 0 the product's, 1 none (the kernel as it was before
+    // them), 2 the divisions, 3 + the single DMA statement, 4 + the scalar masks
+    const int st = v / 10 % 10, fx = v / 100;
+    if (v < 0 || st > 3 || fx > 4) return ORBHIP_E_ARG;
     e->fast_variant = v;
     e->fast_stage = st == 0 ? orbhip::kFastStage : st == 1 ? orbhip::kFastStageBatch : st == 2 ? orbhip::kFastStageDense : orbhip::kFastStageDma;
-    if (e->bound) {                         // the stagings size the LDS image differently
-        ORBHIP_HIP_CHECK(hipSetDevice(e->device));
+    e->fast_fix = fx == 0 ? orbhip::kFastFix : fx == 1 ? 0 : fx == 2 ? orbhip::kFastFixDiv : fx == 3 ? orbhip::kFastFixDiv | orbhip::kFastFixDma
+                : orbhip::kFastFixDiv | orbhip::kFastFixDma | orbhip::kFastFixMask;
+    if (e->bound) {                         // the stagings size the LDS image differently, and the cell records carry a
+        ORBHIP_HIP_CHECK(hipSetDevice(e->device));   // quantity of the survivor-list size that follows from it
         ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
-        return fast_lds_layout(e);
+        if (int rc = fast_lds_layout(e)) return rc;
+        if (!e->cells.empty()) {
+            for (size_t i = 0; i < e->cells.size(); ++i)
+                e->cells2[i] = make_fast_cell(e->G, e->cells[i], e->cells[i].level == 0 ? e->cells_stride : 0, e->fast_lds.list_cap);
+            ORBHIP_HIP_CHECK(hipMemcpyAsync(e->d_cells2, e->cells2.data(), e->cells2.size() * sizeof(orbhip::FastCell), hipMemcpyHostToDevice, e->stream));
+            ORBHIP_HIP_CHECK(hipStreamSynchronize(e->stream));
+        }
     }
     return ORBHIP_OK;
 }

@@ -23,6 +23,13 @@ constexpr int kFastStageBatch = 0;       // lane = (row mod RPI, dword column) t
 constexpr int kFastStageDense = 1;       // lane = row * SW + dword column through registers, exactly the cell's rows
 constexpr int kFastStageDma = 2;         // the same lanes and rows by global_load_lds_dword: no data register, no LDS store
 constexpr int kFastStage = kFastStageDma;
+// What a cell-wave pays once, around its loops ("what a cell-wave pays once").  The product library has the set
+// that was kept (kFastFix); development builds instantiate the steps towards it for tools/fast_ab.py.
+constexpr int kFastFixDiv = 1;           // no run-time division: band size and banded-NMS index split from the cell record
+constexpr int kFastFixDma = 2;           // the staging's row groups in one statement: M0 saved once, running scalar adds
+constexpr int kFastFixMask = 4;          // the live-lane mask of the dense loop and the compaction seed on the scalar unit:
+                                         // measured slower (three scalar instructions per trip for two vector ones), not kept
+constexpr int kFastFix = kFastFixDiv | kFastFixDma;
 // One FAST cell as k_fast_cells2 wants it: every derived quantity precomputed, one 32-byte scalar load per wavefront
 struct alignas(32) FastCell {
     uint32_t src_off;        // byte offset inside a frame's pyramid block of LDS (row 0, col 0): row y0, column gxb - 4
@@ -31,7 +38,9 @@ struct alignas(32) FastCell {
     short kpx, kpy;          // keypoint = (LDS col + kpx, detection row + kpy) relative to (minBorderX, minBorderY)
     unsigned char sw, sh, a; // sub-image size; a = x0 & 3
     unsigned char img;       // 1: src_off / pitch address the caller's image (level 0 without a materialised plane)
-    unsigned char pad[14];
+    unsigned short band_items;   // (list_cap / (4 * ngrp)) * ngrp: work items of a row band that cannot overflow the survivor list
+    uint32_t nms_magic;      // ceil(2^20 / dw), dw = detection columns: floor(i / dw) = (i * nms_magic) >> 20 for i < dw * dh
+    unsigned char pad[8];
 };
 static_assert(sizeof(FastCell) == 32, "FastCell is one s_load_dwordx8");
 struct FastParams {
@@ -356,8 +365,10 @@ struct orbhip_extractor {
     int fast_lds_bytes = 0;
 #ifdef ORBHIP_DEVTOOLS
     int stage_mask = 31;        // development build (tools/coexec.py): stages launch_pipeline runs
-    int fast_variant = 0;       // development build (tools/fast_ab.py): ones 2 stamped build, 3 / 4 timing floors; tens the staging
+    int fast_variant = 0;       // development build (tools/fast_ab.py): ones 2 stamped build, 3 / 4 timing floors; tens the staging;
+                                // hundreds the fixed-cost parts
     int fast_stage = orbhip::kFastStage;   // staging of k_fast_cells selected by the tens of fast_variant (orbhip_dev_set_fast_variant)
+    int fast_fix = orbhip::kFastFix;       // kFastFix* parts selected by its hundreds
     int octree_variant = 0;     // development build (tools/octree_ab.py): bit 0 workspace path for all, bit 1 stamped build
 #endif
     orbhip::CellDesc *d_cells = nullptr;

@@ -5,10 +5,13 @@ exported only by the -DORBHIP_DEVTOOLS build (tools/_dev/liborbhip_dev.so, orbhi
 
   python tools/fast_ab.py [--rounds 8] [--frames 64] [--variants 10,20,30]
 
-A FAST variant is tens * 10 + ones.  Ones: 0 the whole kernel, 2 the stamped build (per-phase shares), 3 / 4 the timing
-floors (exit after the prologue / after the staging).  Tens: how a cell reaches LDS -- 0 the product's way, 1 whole batches
-of row groups with lane = (row mod RPI, dword column), 2 exactly the cell's rows with lane = row * SW + column through
-registers, 3 the same by LDS-DMA.
+A FAST variant is hundreds * 100 + tens * 10 + ones.  Ones: 0 the whole kernel, 2 the stamped build (per-phase shares),
+3 / 4 the timing floors (exit after the prologue / after the staging).  Tens: how a cell reaches LDS -- 0 the product's
+way, 1 whole batches of row groups with lane = (row mod RPI, dword column), 2 exactly the cell's rows with lane =
+row * SW + column through registers, 3 the same by LDS-DMA.  Hundreds: what a cell-wave pays once around its loops, beside
+the LDS-DMA staging -- 0 the product's set, 1 none of it (the kernel before that work), 2 no run-time division (band size
+and banded-NMS multiplier from the cell record), 3 + all row groups of the staging in one statement, 4 + the dense loop's
+live-lane mask and compaction seed on the scalar unit.  `--variants 100,200,300,400` is the per-part comparison.
 """
 import argparse
 import ctypes as C
@@ -117,7 +120,8 @@ def main():
                           "shares": {names[i]: round(z[i] / tot, 3) for i in range(5)}, "waves": int(waves)}), file=sys.stderr)
     for v in variants:
         out[str(v)] = {k: {"median": round(float(np.median([r[k] for r in res[v]])), 2),
-                           "min": round(float(np.min([r[k] for r in res[v]])), 2)} for k in res[v][0]}
+                           "min": round(float(np.min([r[k] for r in res[v]])), 2),
+                           "max": round(float(np.max([r[k] for r in res[v]])), 2)} for k in res[v][0]}
     print(json.dumps({"frames": B, "size": args.size, "stage_us": out}))
 
 
