@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "orbhip.h"
+#include "orbhip_stage.h"   // al256 and the staging bookkeeping: HIP-free, so that a CPU test can compile them alone
 
 namespace orbhip {
 

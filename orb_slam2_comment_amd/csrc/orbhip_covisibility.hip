@@ -253,8 +253,6 @@ __global__ __launch_bounds__(256) void k_cv_children(int rows, const int *__rest
     }
 }
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 size_t covis_workspace_bytes(int U, int rows) { return al256((size_t)U * rows * sizeof(int)) + al256((size_t)U * 4 * sizeof(int)); }

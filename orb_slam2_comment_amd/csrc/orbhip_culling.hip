@@ -415,8 +415,6 @@ __global__ __launch_bounds__(256) void k_cull_scatter(CullArgs A)
     if (in && gl == 0 && !have) A.ref_obs_out[p] = -1;
 }
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 void carve(CullArgs &A, void *workspace)
 {
     uint8_t *w = (uint8_t *)workspace;

@@ -264,8 +264,6 @@ __global__ __launch_bounds__(256) void k_lm_apply(int cap, int pcap, const orbhi
     if (tid == 0) report[(size_t)f * 8 + 7] = s_cnt;
 }
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 size_t local_map_workspace_bytes(int frames, int rows, int pcap)

@@ -3739,40 +3739,6 @@ struct orbhip_matcher {
     int pnp_cap = -1;
 };
 
-static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// The inputs of a call, gathered in the pinned staging buffer and sent in one copy by stage_commit.  Every piece starts
-// on a 256-byte boundary.  A piece that would pass the size given to stage_begin is refused (null pointers) and the call
-// fails with ORBHIP_E_CAPACITY instead of writing past the buffer.
-struct Stage {
-    uint8_t *h, *d;
-    size_t off, cap;
-    bool overrun;
-    // room for `count` T, filled in place: returns the host address, *dev the device address of the same bytes
-    template <class T> T *take(size_t count, const T **dev)
-    {
-        const size_t bytes = al256(count * sizeof(T));
-        if (overrun || bytes > cap - off) { overrun = true; *dev = nullptr; return nullptr; }
-        *dev = reinterpret_cast<const T *>(d + off);
-        T *host = reinterpret_cast<T *>(h + off);
-        off += bytes;
-        return host;
-    }
-    template <class T> const T *put(const T *src, size_t count)   // a copy of src[0 .. count)
-    {
-        const T *dev;
-        T *host = take(count, &dev);
-        if (host && count) memcpy(host, src, count * sizeof(T));
-        return dev;
-    }
-    int status() const
-    {
-        if (!overrun) return ORBHIP_OK;
-        set_error("matcher: staged inputs exceed the %zu bytes reserved for them", cap);
-        return ORBHIP_E_CAPACITY;
-    }
-};
-
 static int scratch(orbhip_matcher *m, int slot, size_t bytes, void **out)
 {
     if (bytes < 256) bytes = 256;
@@ -3840,10 +3806,23 @@ static SigmaTab sigma_tab(const float *inv_level_sigma2, int n_levels)
     if (inv_level_sigma2) for (int l = 0; l < std::min(n_levels, ORBHIP_MAX_LEVELS); ++l) sig.inv_sigma2[l] = inv_level_sigma2[l];
     return sig;
 }
+// the optimisers' copy of it: every level of the table, 0 past the camera's
+static void fill_inv_sigma2(float (&inv)[ORBHIP_MAX_LEVELS], const orbhip_camera *cam, const float *inv_level_sigma2)
+{
+    for (int l = 0; l < ORBHIP_MAX_LEVELS; ++l) inv[l] = l < cam->n_levels ? inv_level_sigma2[l] : 0.f;
+}
+// the optimisers' camera: thHuber of the mono and stereo edges from their chi-square values, a float widened
+static PoCam po_cam(const orbhip_camera *cam, double chi2_mono, double chi2_stereo)
+{
+    return {(double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, (double)cam->mbf,
+            (double)(float)std::sqrt(chi2_mono), (double)(float)std::sqrt(chi2_stereo)};
+}
 
 enum { S_KEYS = 0, S_DESC, S_UR, S_ORD, S_Q, S_QDESC, S_CAND, S_CNT, S_TAKEN, S_OUT, S_QKEYS, S_MISC, S_STATE, S_CSR, S_CCAND, S_TRI, S_UPD, S_LMAP, S_COVIS, S_CULL, S_SIM3, S_SIM3LIM, S_SIM3SOLV, S_PNP, S_PNPTAB, S_PNPSOLV, S_LBA, S_EG, S_GBA, S_GBAAPPLY, S_NSLOTS };
 static_assert(S_NSLOTS == sizeof(orbhip_matcher::buf) / sizeof(void *), "one scratch buffer per slot");
 
+// The buffers of a staging image of `total` bytes: the pinned one and S_MISC, grown when too small.  Waits for the
+// stream first, because the previous call's copy may still read the pinned buffer.
 static int stage_begin(orbhip_matcher *m, size_t total, Stage *st)
 {
     total = al256(total);
@@ -3857,14 +3836,30 @@ static int stage_begin(orbhip_matcher *m, size_t total, Stage *st)
     void *d;
     int rc = scratch(m, S_MISC, total + 256, &d);
     if (rc) return rc;
-    st->h = m->h_stage; st->d = (uint8_t *)d; st->off = 0; st->cap = total; st->overrun = false;
+    *st = Stage();
+    st->h = m->h_stage; st->d = (uint8_t *)d;
     return ORBHIP_OK;
 }
 static int stage_commit(orbhip_matcher *m, Stage *st)
 {
-    if (int rc = st->status()) return rc;
     ORBHIP_HIP_CHECK(hipMemcpyAsync(st->d, st->h, st->off, hipMemcpyHostToDevice, m->stream));
     return ORBHIP_OK;
+}
+// a zeroed stand-in for an empty in/out array: a piece the kernels are handed but, with no element, never index
+template <class T> static T *stage_zeros(Stage &st, size_t count)
+{
+    return st.fill<T>(count, [=](T *h) { memset(h, 0, count * sizeof(T)); });
+}
+// The staging image of a host-form call (orbhip_stage.h): `pieces` states what is staged, once.  stage_send sizes the
+// buffers from a measuring pass over it, runs it for real and sends the image in one copy.
+template <class F> static int stage_send(orbhip_matcher *m, Stage *st, F &&pieces)
+{
+    bool out_overflow;
+    const size_t total = stage_measure(pieces, &out_overflow);
+    if (out_overflow) { set_error("matcher: a call records more than %d outputs", (int)Stage::kMaxOut); return ORBHIP_E_CAPACITY; }
+    if (int rc = stage_begin(m, total, st)) return rc;
+    pieces(*st);
+    return stage_commit(m, st);
 }
 // The outputs of a call, `bytes` at d, in one copy to the pinned out-buffer: *h = its host address once the stream drained
 static int read_back(orbhip_matcher *m, const void *d, size_t bytes, const uint8_t **h)
@@ -3879,6 +3874,15 @@ static int read_back(orbhip_matcher *m, const void *d, size_t bytes, const uint8
     ORBHIP_HIP_CHECK(hipMemcpyAsync(m->h_out, d, bytes, hipMemcpyDeviceToHost, m->stream));
     ORBHIP_HIP_CHECK(hipStreamSynchronize(m->stream));
     *h = m->h_out;
+    return ORBHIP_OK;
+}
+
+// The recorded outputs of a call (Stage::back / out / inout) in one copy, each then to its host array
+static int stage_fetch(orbhip_matcher *m, Stage *st)
+{
+    const uint8_t *h;
+    if (int rc = read_back(m, st->d + st->out_begin(), st->out_end() - st->out_begin(), &h)) return rc;
+    st->scatter(h);
     return ORBHIP_OK;
 }
 
@@ -4038,27 +4042,24 @@ static int run_search(orbhip_matcher *m, int mode, const orbhip_frame_view *trai
     const size_t n = (size_t)train->n;
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, al256(n * sizeof(orbhip_keypoint)) + al256(n * 32) + al256(n * 4) + al256(n) +
-                                 al256((size_t)nqv * sizeof(orbhip_query)) + al256((size_t)nqv * 32) +
-                                 al256((size_t)nqv * sizeof(orbhip_keypoint)), &st))) return rc;
-    const DevFrame D = dev_frame(train, st);
-    const uint8_t *d_taken = taken ? st.put(taken, n) : nullptr;
+    DevFrame D;
+    const uint8_t *d_taken, *d_qdesc;
     const orbhip_query *d_q;
-    const uint8_t *d_qdesc;
-    if (compact) {
-        orbhip_query *hq = st.take((size_t)nqv, &d_q);
-        uint8_t *hd = st.take((size_t)nqv * 32, &d_qdesc);
-        if ((rc = st.status())) return rc;
-        for (int k = 0; k < nqv; ++k) {
-            hq[k] = q[vidx[k]];
-            memcpy(hd + (size_t)k * 32, qdesc + (size_t)vidx[k] * 32, 32);
-        }
-    } else {
-        d_q = st.put(q, (size_t)nq);
-        d_qdesc = st.put(qdesc, (size_t)nq * 32);
-    }
-    const orbhip_keypoint *d_qkeys = qkeys ? st.put(qkeys, (size_t)nq) : nullptr;
-    if ((rc = stage_commit(m, &st))) return rc;
+    const orbhip_keypoint *d_qkeys;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            D = dev_frame(train, stg);
+            d_taken = taken ? stg.put(taken, n) : nullptr;
+            if (compact) {
+                d_q = stg.fill<orbhip_query>((size_t)nqv, [&](orbhip_query *hq) { for (int k = 0; k < nqv; ++k) hq[k] = q[vidx[k]]; });
+                d_qdesc = stg.fill<uint8_t>((size_t)nqv * 32, [&](uint8_t *hd) {
+                    for (int k = 0; k < nqv; ++k) memcpy(hd + (size_t)k * 32, qdesc + (size_t)vidx[k] * 32, 32);
+                });
+            } else {
+                d_q = stg.put(q, (size_t)nq);
+                d_qdesc = stg.put(qdesc, (size_t)nq * 32);
+            }
+            d_qkeys = qkeys ? stg.put(qkeys, (size_t)nq) : nullptr;
+        }))) return rc;
     void *p;
     if ((rc = scratch(m, S_OUT, (size_t)(nout + 1) * sizeof(int), &p))) return rc;
     int *d_out = (int *)p;
@@ -4120,32 +4121,32 @@ static int run_bow(orbhip_matcher *m, const orbhip_frame_view *f1, const uint32_
     const size_t n = (size_t)n2;
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, al256(n * sizeof(orbhip_keypoint)) + al256(n * 32) + al256((size_t)nt * 4) + al256((size_t)nt) +
-                                 al256((size_t)nq * 32) + al256((size_t)nq * 4) + al256((size_t)ng * sizeof(NodeGroup)), &st)))
-        return rc;
-    const orbhip_keypoint *d_tkeys = st.put(f2->keys, n);
-    const uint8_t *d_tdesc = st.put(f2->desc, n * 32);
-    const uint32_t *d_torder = st.put(reinterpret_cast<const uint32_t *>(torder.data()), (size_t)nt);
-    const uint8_t *d_matched, *d_qdesc;
+    const orbhip_keypoint *d_tkeys;
+    const uint8_t *d_tdesc, *d_qdesc;
+    const uint32_t *d_torder;
+    uint8_t *d_matched;
     const float *d_qangle;
-    uint8_t *hm = st.take((size_t)nt, &d_matched);
-    uint8_t *hqd = st.take((size_t)nq * 32, &d_qdesc);
-    float *hqa = st.take((size_t)nq, &d_qangle);
-    const NodeGroup *d_groups = st.put(groups.data(), (size_t)ng);
-    if ((rc = st.status())) return rc;
-    for (int c = 0; c < nt; ++c) hm[c] = (uint8_t)(blocked2 && blocked2[torder[c]]);
-    for (int p = 0; p < nq; ++p) {
-        memcpy(hqd + (size_t)p * 32, f1->desc + (size_t)order[p] * 32, 32);
-        hqa[p] = f1->keys[order[p]].angle;
-    }
-    if ((rc = stage_commit(m, &st))) return rc;
+    const NodeGroup *d_groups;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            d_tkeys = stg.put(f2->keys, n);
+            d_tdesc = stg.put(f2->desc, n * 32);
+            d_torder = stg.put(reinterpret_cast<const uint32_t *>(torder.data()), (size_t)nt);
+            d_matched = stg.fill<uint8_t>((size_t)nt, [&](uint8_t *hm) {
+                for (int c = 0; c < nt; ++c) hm[c] = (uint8_t)(blocked2 && blocked2[torder[c]]);
+            });
+            d_qdesc = stg.fill<uint8_t>((size_t)nq * 32, [&](uint8_t *hqd) {
+                for (int p = 0; p < nq; ++p) memcpy(hqd + (size_t)p * 32, f1->desc + (size_t)order[p] * 32, 32);
+            });
+            d_qangle = stg.fill<float>((size_t)nq, [&](float *hqa) { for (int p = 0; p < nq; ++p) hqa[p] = f1->keys[order[p]].angle; });
+            d_groups = stg.put(groups.data(), (size_t)ng);
+        }))) return rc;
     void *p;
     if ((rc = scratch(m, S_OUT, (size_t)(nq + 1) * sizeof(int), &p))) return rc;
     int *d_out = (int *)p;
     // queries whose node does not occur in f2 belong to no group: they stay at -1
     ORBHIP_HIP_CHECK(hipMemsetAsync(d_out, 0xff, (size_t)nq * sizeof(int), m->stream));
     hipLaunchKernelGGL(k_bow_groups, dim3((ng + 3) / 4), dim3(256), 0, m->stream, d_groups, ng, d_qdesc, d_torder, d_tdesc,
-                       (uint8_t *)d_matched, max_dist, nnratio, d_out);
+                       d_matched, max_dist, nnratio, d_out);
     hipLaunchKernelGGL(k_rot_cull, dim3(1), dim3(1024), 0, m->stream, d_out, nq, (const void *)d_qangle, 4, d_tkeys, check_ori,
                        d_out + nq);
     const uint8_t *h;
@@ -4185,36 +4186,38 @@ static int run_tri(orbhip_matcher *m, const TriParams *tri, const orbhip_frame_v
     const size_t n = (size_t)n2;
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, al256(n * sizeof(orbhip_keypoint)) + al256(n * 32) + 2 * al256(n * 4) + al256(n) +
-                                 al256((size_t)nq * sizeof(orbhip_query)) + al256((size_t)nq * 32), &st))) return rc;
     DevFrame D;
     D.n = n2; D.min_x = D.min_y = 0.f; D.inv_w = D.inv_h = 0.f;
-    D.keys = st.put(f2->keys, n);
-    D.desc = st.put(f2->desc, n * 32);
-    D.u_right = f2->u_right ? st.put(f2->u_right, n) : nullptr;
-    const uint32_t *d_tnode = st.put(node2, n);
-    const uint8_t *d_mask = nullptr;   // candidate filter: no map point yet (+ bOnlyStereo :725-729)
-    uint8_t *hm = (valid2 || only_stereo) ? st.take(n, &d_mask) : nullptr;
+    const uint32_t *d_tnode;
+    const uint8_t *d_mask, *d_qdesc;
     const orbhip_query *d_q;
-    const uint8_t *d_qdesc;
-    orbhip_query *hq = st.take((size_t)nq, &d_q);
-    uint8_t *hqd = st.take((size_t)nq * 32, &d_qdesc);
-    if ((rc = st.status())) return rc;
-    if (hm)
-        for (int j = 0; j < n2; ++j)
-            hm[j] = (uint8_t)((!valid2 || valid2[j]) && (!only_stereo || (f2->u_right && f2->u_right[j] >= 0)));
-    for (int p = 0; p < nq; ++p) {
-        const int i = order[p];
-        orbhip_query &Q = hq[p];
-        memset(&Q, 0, sizeof(Q));
-        Q.valid = 1;
-        Q.u = f1->keys[i].x; Q.v = f1->keys[i].y;
-        Q.ur = f1->u_right ? f1->u_right[i] : -1.0f;
-        Q.level_aux = (int32_t)node1[i];
-        Q.angle = f1->keys[i].angle;
-        memcpy(hqd + (size_t)p * 32, f1->desc + (size_t)i * 32, 32);
-    }
-    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            D.keys = stg.put(f2->keys, n);
+            D.desc = stg.put(f2->desc, n * 32);
+            D.u_right = f2->u_right ? stg.put(f2->u_right, n) : nullptr;
+            d_tnode = stg.put(node2, n);
+            d_mask = nullptr;   // candidate filter: no map point yet (+ bOnlyStereo :725-729)
+            if (valid2 || only_stereo)
+                d_mask = stg.fill<uint8_t>(n, [&](uint8_t *hm) {
+                    for (int j = 0; j < n2; ++j)
+                        hm[j] = (uint8_t)((!valid2 || valid2[j]) && (!only_stereo || (f2->u_right && f2->u_right[j] >= 0)));
+                });
+            d_q = stg.fill<orbhip_query>((size_t)nq, [&](orbhip_query *hq) {
+                for (int p = 0; p < nq; ++p) {
+                    const int i = order[p];
+                    orbhip_query &Q = hq[p];
+                    memset(&Q, 0, sizeof(Q));
+                    Q.valid = 1;
+                    Q.u = f1->keys[i].x; Q.v = f1->keys[i].y;
+                    Q.ur = f1->u_right ? f1->u_right[i] : -1.0f;
+                    Q.level_aux = (int32_t)node1[i];
+                    Q.angle = f1->keys[i].angle;
+                }
+            });
+            d_qdesc = stg.fill<uint8_t>((size_t)nq * 32, [&](uint8_t *hqd) {
+                for (int p = 0; p < nq; ++p) memcpy(hqd + (size_t)p * 32, f1->desc + (size_t)order[p] * 32, 32);
+            });
+        }))) return rc;
     void *p;
     if ((rc = scratch(m, S_OUT, (size_t)(nq + 1) * sizeof(int), &p))) return rc;
     int *d_out = (int *)p;
@@ -4402,10 +4405,9 @@ int orbhip_assign_features_to_grid(orbhip_matcher *m, const orbhip_frame_view *f
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, al256((size_t)n * sizeof(orbhip_keypoint)) + 256, &st))) return rc;
-    const orbhip_keypoint *d_keys = st.put(f->keys, (size_t)n);
-    const int *d_n = st.put(&n, 1);
-    if ((rc = stage_commit(m, &st))) return rc;
+    const orbhip_keypoint *d_keys;
+    const int *d_n;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) { d_keys = stg.put(f->keys, (size_t)n); d_n = stg.put(&n, 1); }))) return rc;
     const size_t ob = ((size_t)2 * n + kGridCells + 1) * sizeof(int);
     void *p;
     if ((rc = scratch(m, S_OUT, ob, &p))) return rc;
@@ -4449,10 +4451,9 @@ int orbhip_undistort_keypoints(orbhip_matcher *m, const orbhip_keypoint *keys, i
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, al256((size_t)n * sizeof(orbhip_keypoint)) + 256, &st))) return rc;
-    const orbhip_keypoint *d_keys = st.put(keys, (size_t)n);
-    const int *d_n = st.put(&n, 1);
-    if ((rc = stage_commit(m, &st))) return rc;
+    const orbhip_keypoint *d_keys;
+    const int *d_n;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) { d_keys = stg.put(keys, (size_t)n); d_n = stg.put(&n, 1); }))) return rc;
     void *p;
     if ((rc = scratch(m, S_OUT, (size_t)n * sizeof(orbhip_keypoint), &p))) return rc;
     if ((rc = orbhip_undistort_keypoints_device(m, 1, d_keys, d_n, n, fx, fy, cx, cy, dist5, p))) return rc;
@@ -4492,16 +4493,17 @@ int orbhip_compute_stereo_from_rgbd(orbhip_matcher *m, const orbhip_keypoint *ke
     // the depth image travels like the grey image does for extraction: packed rows through the pinned staging buffer
     Stage st;
     int rc;
-    const size_t kb = al256((size_t)n * sizeof(orbhip_keypoint)), ib = al256((size_t)rows * cols * sizeof(float));
-    if ((rc = stage_begin(m, 2 * kb + ib + 256, &st))) return rc;
-    const orbhip_keypoint *d_keys = st.put(keys, (size_t)n);
-    const orbhip_keypoint *d_un = st.put(keys_un, (size_t)n);
+    const orbhip_keypoint *d_keys, *d_un;
     const float *d_depth;
-    float *hd = st.take((size_t)rows * cols, &d_depth);
-    const int *d_n = st.put(&n, 1);
-    if ((rc = st.status())) return rc;
-    for (int r = 0; r < rows; ++r) memcpy(hd + (size_t)r * cols, depth + (size_t)r * stride_floats, (size_t)cols * sizeof(float));
-    if ((rc = stage_commit(m, &st))) return rc;
+    const int *d_n;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            d_keys = stg.put(keys, (size_t)n);
+            d_un = stg.put(keys_un, (size_t)n);
+            d_depth = stg.fill<float>((size_t)rows * cols, [&](float *hd) {
+                for (int r = 0; r < rows; ++r) memcpy(hd + (size_t)r * cols, depth + (size_t)r * stride_floats, (size_t)cols * sizeof(float));
+            });
+            d_n = stg.put(&n, 1);
+        }))) return rc;
     void *p;
     if ((rc = scratch(m, S_OUT, (size_t)2 * n * sizeof(float), &p))) return rc;
     float *d_out = (float *)p;
@@ -4555,16 +4557,17 @@ int orbhip_compute_stereo_from_rgbd_raw(orbhip_matcher *m, const orbhip_keypoint
     Stage st;
     int rc;
     const size_t esz = depth_type == ORBHIP_DEPTH_U16 ? 2 : 4, rb = (size_t)cols * esz;
-    const size_t kb = al256((size_t)n * sizeof(orbhip_keypoint)), ib = al256((size_t)rows * rb);
-    if ((rc = stage_begin(m, 2 * kb + ib + 256, &st))) return rc;
-    const orbhip_keypoint *d_keys = st.put(keys, (size_t)n);
-    const orbhip_keypoint *d_un = st.put(keys_un, (size_t)n);
+    const orbhip_keypoint *d_keys, *d_un;
     const uint8_t *d_depth;
-    uint8_t *hd = st.take((size_t)rows * rb, &d_depth);
-    const int *d_n = st.put(&n, 1);
-    if ((rc = st.status())) return rc;
-    for (int r = 0; r < rows; ++r) memcpy(hd + (size_t)r * rb, (const uint8_t *)depth + (size_t)r * stride_elems * esz, rb);
-    if ((rc = stage_commit(m, &st))) return rc;
+    const int *d_n;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            d_keys = stg.put(keys, (size_t)n);
+            d_un = stg.put(keys_un, (size_t)n);
+            d_depth = stg.fill<uint8_t>((size_t)rows * rb, [&](uint8_t *hd) {
+                for (int r = 0; r < rows; ++r) memcpy(hd + (size_t)r * rb, (const uint8_t *)depth + (size_t)r * stride_elems * esz, rb);
+            });
+            d_n = stg.put(&n, 1);
+        }))) return rc;
     void *p;
     if ((rc = scratch(m, S_OUT, (size_t)2 * n * sizeof(float), &p))) return rc;
     float *d_out = (float *)p;
@@ -4596,10 +4599,10 @@ int orbhip_distinctive_descriptors(orbhip_matcher *m, const uint8_t *desc, const
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, al256(total * 32) + al256((size_t)(npoints + 1) * 4), &st))) return rc;
-    const uint8_t *d_desc = st.put(desc, total * 32);
-    const int *d_off = st.put(offsets, (size_t)npoints + 1);
-    if ((rc = stage_commit(m, &st))) return rc;
+    const uint8_t *d_desc;
+    const int *d_off;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) { d_desc = stg.put(desc, total * 32); d_off = stg.put(offsets, (size_t)npoints + 1); })))
+        return rc;
     void *p;
     if ((rc = scratch(m, S_OUT, (size_t)npoints * sizeof(int), &p))) return rc;
     hipLaunchKernelGGL(k_distinctive, dim3((npoints + 3) / 4), dim3(256), 0, m->stream, d_desc, d_off, npoints, (int *)p);
@@ -4688,12 +4691,14 @@ int orbhip_search_best_in_window(orbhip_matcher *m, const orbhip_frame_view *kf,
     const size_t n = (size_t)kf->n;
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, al256(n * sizeof(orbhip_keypoint)) + al256(n * 32) + al256(n * 4) +
-                                 al256((size_t)nq * sizeof(orbhip_query)) + al256((size_t)nq * 32), &st))) return rc;
-    const DevFrame D = dev_frame(kf, st);
-    const orbhip_query *d_q = st.put(q, (size_t)nq);
-    const uint8_t *d_qdesc = st.put(qdesc, (size_t)nq * 32);
-    if ((rc = stage_commit(m, &st))) return rc;
+    DevFrame D;
+    const orbhip_query *d_q;
+    const uint8_t *d_qdesc;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            D = dev_frame(kf, stg);
+            d_q = stg.put(q, (size_t)nq);
+            d_qdesc = stg.put(qdesc, (size_t)nq * 32);
+        }))) return rc;
     void *p;
     if ((rc = scratch(m, S_ORD, n * sizeof(uint32_t), &p))) return rc;
     uint32_t *d_ord = (uint32_t *)p;
@@ -4886,14 +4891,18 @@ int orbhip_project_last_frame(orbhip_matcher *m, const orbhip_camera *cam, const
     if (!world || !flags || !last_keys) return ORBHIP_E_ARG;
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     Stage st;
-    int rc = stage_begin(m, 2 * al256(48) + al256((size_t)n * 12) + al256((size_t)n) + al256((size_t)n * sizeof(orbhip_keypoint)) + 256, &st);
+    const float *dT, *dL, *dW;
+    const uint8_t *dF;
+    const orbhip_keypoint *dK;
+    const int *dN;
+    int rc = stage_send(m, &st, [&](Stage &stg) {
+        dT = stg.put(Tcw, 12); dL = stg.put(Tlw, 12);
+        dW = stg.put(world, (size_t)n * 3);
+        dF = stg.put(flags, (size_t)n);
+        dK = stg.put(last_keys, (size_t)n);
+        dN = stg.put(&n, 1);
+    });
     if (rc) return rc;
-    const float *dT = st.put(Tcw, 12), *dL = st.put(Tlw, 12);
-    const float *dW = st.put(world, (size_t)n * 3);
-    const uint8_t *dF = st.put(flags, (size_t)n);
-    const orbhip_keypoint *dK = st.put(last_keys, (size_t)n);
-    const int *dN = st.put(&n, 1);
-    if ((rc = stage_commit(m, &st))) return rc;
     void *p;
     if ((rc = scratch(m, S_Q, (size_t)n * sizeof(orbhip_query), &p))) return rc;
     if ((rc = orbhip_project_last_frame_device(m, 1, cam, dT, dL, dK, dN, n, 0, 0, dW, dF, th, mono, p, nullptr))) return rc;
@@ -4912,14 +4921,17 @@ int orbhip_frustum_queries(orbhip_matcher *m, const orbhip_camera *cam, const fl
     if (!world || !normal || !max_dist || !min_dist || !flags) return ORBHIP_E_ARG;
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     Stage st;
-    int rc = stage_begin(m, al256(48) + 2 * al256((size_t)n * 12) + 2 * al256((size_t)n * 4) + al256((size_t)n) + 256, &st);
+    const float *dT, *dW, *dNr, *dMx, *dMn;
+    const uint8_t *dF;
+    const int *dN;
+    int rc = stage_send(m, &st, [&](Stage &stg) {
+        dT = stg.put(Tcw, 12);
+        dW = stg.put(world, (size_t)n * 3); dNr = stg.put(normal, (size_t)n * 3);
+        dMx = stg.put(max_dist, (size_t)n); dMn = stg.put(min_dist, (size_t)n);
+        dF = stg.put(flags, (size_t)n);
+        dN = stg.put(&n, 1);
+    });
     if (rc) return rc;
-    const float *dT = st.put(Tcw, 12);
-    const float *dW = st.put(world, (size_t)n * 3), *dNr = st.put(normal, (size_t)n * 3);
-    const float *dMx = st.put(max_dist, (size_t)n), *dMn = st.put(min_dist, (size_t)n);
-    const uint8_t *dF = st.put(flags, (size_t)n);
-    const int *dN = st.put(&n, 1);
-    if ((rc = stage_commit(m, &st))) return rc;
     // outputs contiguous: q[n] | view_cos[n] (when asked for)
     const size_t qb = (size_t)n * sizeof(orbhip_query), ob = qb + (view_cos ? (size_t)n * sizeof(float) : 0);
     void *p;
@@ -4971,33 +4983,31 @@ int orbhip_seed_stereo_points(orbhip_matcher *m, const orbhip_camera *cam, const
     counts[0] = counts[1] = counts[2] = 0;
     if (n == 0) return ORBHIP_OK;
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
-    // inputs in one copy; world | flags are staged last and order | created | counts follow them in the same device
-    // buffer, so that everything the call returns comes back in one copy as well
-    const size_t kb = al256((size_t)n * sizeof(orbhip_keypoint)), fb = al256((size_t)n * sizeof(float)), wb = al256((size_t)n * 12),
-                 bb = al256((size_t)n), ob = wb + bb + fb + bb + 256;
+    // inputs in one copy; world | flags are staged last and order | created | counts follow them, so that everything the
+    // call returns comes back in one copy as well
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, 256 + 256 + kb + fb + ob, &st))) return rc;
-    const float *dT = st.put(Tcw, 12);
-    const int *dN = st.put(&n, 1);
-    const orbhip_keypoint *dK = st.put(keys, (size_t)n);
-    const float *dZ = st.put(depth, (size_t)n);
-    const float *dW = st.put(world, (size_t)n * 3);
-    const uint8_t *dF = st.put(flags, (size_t)n);
-    if ((rc = stage_commit(m, &st))) return rc;
-    uint8_t *d_out = const_cast<uint8_t *>(reinterpret_cast<const uint8_t *>(dW));
-    int *d_order = reinterpret_cast<int *>(d_out + wb + bb);
-    uint8_t *d_created = d_out + wb + bb + fb;
-    int *d_counts = reinterpret_cast<int *>(d_out + wb + bb + fb + bb);
-    if ((rc = orbhip_seed_stereo_points_device(m, 1, cam, dT, dK, dN, n, 0, 0, dZ, th_depth, mode, created_flags, d_out,
-                                               const_cast<uint8_t *>(dF), d_order, d_created, d_counts))) return rc;
-    const uint8_t *h;
-    if ((rc = read_back(m, d_out, ob - 256 + 3 * sizeof(int), &h))) return rc;
-    memcpy(world, h, (size_t)n * 12);
-    memcpy(flags, h + wb, (size_t)n);
-    memcpy(counts, h + wb + bb + fb + bb, 3 * sizeof(int));
-    if (order) memcpy(order, h + wb + bb, (size_t)counts[1] * sizeof(int));
-    if (created) memcpy(created, h + wb + bb + fb, (size_t)n);
+    const float *dT, *dZ;
+    const int *dN;
+    const orbhip_keypoint *dK;
+    float *dW;
+    uint8_t *dF, *d_created;
+    int *d_order, *d_counts;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            dT = stg.put(Tcw, 12);
+            dN = stg.put(&n, 1);
+            dK = stg.put(keys, (size_t)n);
+            dZ = stg.put(depth, (size_t)n);
+            dW = stg.inout(world, (size_t)n * 3);
+            dF = stg.inout(flags, (size_t)n);
+            d_order = stg.out((int *)nullptr, (size_t)n);   // the caller gets the first counts[1] entries, below
+            d_created = created ? stg.out(created, (size_t)n) : stg.room<uint8_t>((size_t)n);
+            d_counts = stg.out(counts, 3);
+        }))) return rc;
+    if ((rc = orbhip_seed_stereo_points_device(m, 1, cam, dT, dK, dN, n, 0, 0, dZ, th_depth, mode, created_flags, dW, dF, d_order,
+                                               d_created, d_counts))) return rc;
+    if ((rc = stage_fetch(m, &st))) return rc;
+    if (order) memcpy(order, st.image(d_order), (size_t)counts[1] * sizeof(int));
     return ORBHIP_OK;
 }
 
@@ -5022,11 +5032,11 @@ int orbhip_count_close_points(orbhip_matcher *m, const float *depth, const uint8
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, al256((size_t)n * sizeof(float)) + al256((size_t)n) + 256, &st))) return rc;
-    const float *dZ = st.put(depth, (size_t)n);
-    const uint8_t *dF = st.put(flags, (size_t)n);
-    const int *dN = st.put(&n, 1);
-    if ((rc = stage_commit(m, &st))) return rc;
+    const float *dZ;
+    const uint8_t *dF;
+    const int *dN;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) { dZ = stg.put(depth, (size_t)n); dF = stg.put(flags, (size_t)n); dN = stg.put(&n, 1); })))
+        return rc;
     void *p;
     if ((rc = scratch(m, S_OUT, 2 * sizeof(int), &p))) return rc;
     if ((rc = orbhip_count_close_points_device(m, 1, dZ, dF, dN, n, th_depth, p))) return rc;
@@ -5115,66 +5125,46 @@ int orbhip_update_map_points(orbhip_matcher *m, const orbhip_camera *cam, int wh
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     // inputs in one copy; the in/out arrays and the two reports are staged last and next to each other, so that
     // everything the call returns comes back in one copy as well
-    const size_t kc = (size_t)std::max(K, 1) * cap, sn = (size_t)np, no = std::max(nobs, (size_t)1);
-    const size_t ob = al256(sn * 32) + 3 * al256(sn * 12) + al256(sn * 4) + al256(sn);
+    const size_t kc = (size_t)std::max(K, 1) * cap, sn = (size_t)np;
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, al256((size_t)std::max(K, 1) * 48) + al256((size_t)std::max(K, 1)) + al256(kc * sizeof(orbhip_keypoint)) +
-                                 al256(kc * 32) + al256((sn + 1) * 4) + 2 * al256(no * 4) + al256(sn * 4) + al256(sn * 12) +
-                                 al256(sn) + ob, &st))) return rc;
     const float *d_T = nullptr, *d_world = nullptr;
-    const uint8_t *d_bad = nullptr, *d_desc = nullptr;
+    const uint8_t *d_bad = nullptr, *d_desc = nullptr, *d_flags;
     const orbhip_keypoint *d_keys = nullptr;
-    const int *d_ref = nullptr;
-    if (wn) {
-        d_T = st.put(Tcw, (size_t)K * 12);
-        orbhip_keypoint *h_keys = st.take(kc, &d_keys);
-        if (h_keys)
-            for (int k = 0; k < K; ++k)
-                if (kfs[k]->n) memcpy(h_keys + (size_t)k * cap, kfs[k]->keys, (size_t)kfs[k]->n * sizeof(orbhip_keypoint));
-        d_ref = st.put(ref_obs, sn);
-        d_world = st.put(world, sn * 3);
-    }
-    if (wd) {
-        uint8_t *h_desc = st.take(kc * 32, &d_desc);
-        if (h_desc)
-            for (int k = 0; k < K; ++k)
-                if (kfs[k]->n) memcpy(h_desc + (size_t)k * cap * 32, kfs[k]->desc, (size_t)kfs[k]->n * 32);
-    }
-    if (kf_bad) d_bad = st.put(kf_bad, (size_t)K);
-    const int *d_start = st.put(obs_start, sn + 1);
-    const int *d_okf = st.put(obs_kf, nobs), *d_oidx = st.put(obs_idx, nobs);
-    const uint8_t *d_flags = st.put(flags, sn);
-    // outputs: point_desc | normal | max_dist | min_dist | best_obs | status
-    const uint8_t *d_pd = nullptr;
-    const float *d_nrm = nullptr, *d_mx = nullptr, *d_mn = nullptr;
-    const int *d_best;
-    const uint8_t *d_status;
-    const size_t out_off = st.off;
-    if (wd) d_pd = st.put(point_desc, sn * 32);
-    if (wn) { d_nrm = st.put(normal, sn * 3); d_mx = st.put(max_dist, sn); d_mn = st.put(min_dist, sn); }
-    int *h_best = st.take(sn, &d_best);
-    uint8_t *h_status = st.take(sn, &d_status);
-    if ((rc = st.status())) return rc;
-    for (size_t i = 0; i < sn; ++i) { h_best[i] = -1; h_status[i] = 0; }
-    const size_t out_bytes = st.off - out_off;
-    if ((rc = stage_commit(m, &st))) return rc;
+    const int *d_ref = nullptr, *d_start, *d_okf, *d_oidx;
+    uint8_t *d_pd = nullptr, *d_status;
+    float *d_nrm = nullptr, *d_mx = nullptr, *d_mn = nullptr;
+    int *d_best;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            if (wn) {
+                d_T = stg.put(Tcw, (size_t)K * 12);
+                d_keys = stg.fill<orbhip_keypoint>(kc, [&](orbhip_keypoint *h_keys) {
+                    for (int k = 0; k < K; ++k)
+                        if (kfs[k]->n) memcpy(h_keys + (size_t)k * cap, kfs[k]->keys, (size_t)kfs[k]->n * sizeof(orbhip_keypoint));
+                });
+                d_ref = stg.put(ref_obs, sn);
+                d_world = stg.put(world, sn * 3);
+            }
+            if (wd)
+                d_desc = stg.fill<uint8_t>(kc * 32, [&](uint8_t *h_desc) {
+                    for (int k = 0; k < K; ++k)
+                        if (kfs[k]->n) memcpy(h_desc + (size_t)k * cap * 32, kfs[k]->desc, (size_t)kfs[k]->n * 32);
+                });
+            if (kf_bad) d_bad = stg.put(kf_bad, (size_t)K);
+            d_start = stg.put(obs_start, sn + 1);
+            d_okf = stg.put(obs_kf, nobs); d_oidx = stg.put(obs_idx, nobs);
+            d_flags = stg.put(flags, sn);
+            // outputs: point_desc | normal | max_dist | min_dist | best_obs | status
+            if (wd) d_pd = stg.inout(point_desc, sn * 32);
+            if (wn) { d_nrm = stg.inout(normal, sn * 3); d_mx = stg.inout(max_dist, sn); d_mn = stg.inout(min_dist, sn); }
+            d_best = stg.fill<int>(sn, [&](int *h_best) { for (size_t i = 0; i < sn; ++i) h_best[i] = -1; });
+            if (best_obs && wd) stg.back(best_obs, d_best, sn);
+            d_status = stg.fill<uint8_t>(sn, [&](uint8_t *h_status) { memset(h_status, 0, sn); });
+            stg.back(status, d_status, sn);
+        }))) return rc;
     if ((rc = orbhip_update_map_points_device(m, cam, what, d_T, d_keys, d_desc, nullptr, cap, d_bad, np, np, d_start, d_okf, d_oidx,
-                                              d_ref, d_world, d_flags, const_cast<uint8_t *>(d_pd), const_cast<float *>(d_nrm),
-                                              const_cast<float *>(d_mx), const_cast<float *>(d_mn), const_cast<int *>(d_best),
-                                              const_cast<uint8_t *>(d_status)))) return rc;
-    const uint8_t *h;
-    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
-    const uint8_t *base = st.d + out_off;
-    if (wd) memcpy(point_desc, h + (d_pd - base), sn * 32);
-    if (wn) {
-        memcpy(normal, h + ((const uint8_t *)d_nrm - base), sn * 12);
-        memcpy(max_dist, h + ((const uint8_t *)d_mx - base), sn * 4);
-        memcpy(min_dist, h + ((const uint8_t *)d_mn - base), sn * 4);
-    }
-    if (best_obs && wd) memcpy(best_obs, h + ((const uint8_t *)d_best - base), sn * 4);
-    memcpy(status, h + (d_status - base), sn);
-    return ORBHIP_OK;
+                                              d_ref, d_world, d_flags, d_pd, d_nrm, d_mx, d_mn, d_best, d_status))) return rc;
+    return stage_fetch(m, &st);
 }
 
 // ---- local map (kernels: orbhip_localmap.hip) -----------------------------------------------------------------------
@@ -5277,62 +5267,46 @@ int orbhip_update_local_map(orbhip_matcher *m, int frames, int rows, int cap, in
     }
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     const size_t R = (size_t)rows, Cp = (size_t)cap, P = (size_t)pcap, Fr = (size_t)frames;
-    const size_t in_bytes = al256(R * Cp * 4) + 4 * al256(R * 4 + 4) + al256(R * 40) + al256(nchild * 4) + al256((size_t)np * 4 + 4) +
-                            al256(nobs * 4) + al256(P) + 2 * al256(P * 12) + 2 * al256(P * 4) + al256(P * 32) + al256(Fr * 4);
-    const size_t out_bytes_max = 2 * al256(Fr * Cp * 4) + 2 * al256(Fr * R * 4) + 2 * al256(Fr * 4) + al256(Fr * P * 4) +
-                                 2 * al256(Fr * P * 12) + 2 * al256(Fr * P * 4) + al256(Fr * P * 32) + al256(Fr * P) + al256(Fr * 32);
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, in_bytes + out_bytes_max, &st))) return rc;
     orbhip_local_map_tables dt;
     orbhip_local_map_io dio;
-    dt.slot_point = st.put(slot_point, R * Cp);
-    dt.n = st.put(n, R);
-    dt.kf_bad = t->kf_bad ? st.put((const uint8_t *)t->kf_bad, R) : nullptr;
-    dt.covis = st.put(covis, R * 10);
-    dt.child_start = st.put(child_start, R + 1);
-    dt.child = st.put(child, nchild);
-    dt.parent = st.put(parent, R);
-    dt.obs_start = st.put(obs_start, (size_t)np + 1);
-    dt.obs_kf = st.put(obs_kf, nobs);
-    dt.flags = st.put((const uint8_t *)t->flags, P);
-    dt.world = st.put((const float *)t->world, P * 3);
-    dt.normal = st.put((const float *)t->normal, P * 3);
-    dt.max_dist = st.put((const float *)t->max_dist, P);
-    dt.min_dist = st.put((const float *)t->min_dist, P);
-    dt.point_desc = st.put((const uint8_t *)t->point_desc, P * 32);
-    dio.frame_n = st.put(frame_n, Fr);
-    // in/out and output arrays next to each other, as the caller passed them: one copy brings all of them back
-    const size_t out_off = st.off;
-    struct Out { void *host; const void *dev; size_t bytes; } outs[14];
-    int no = 0;
-    auto out = [&](void *host, size_t bytes) -> void * {
-        const uint8_t *d = st.put((const uint8_t *)host, bytes);
-        outs[no].host = host; outs[no].dev = d; outs[no].bytes = bytes; ++no;
-        return const_cast<uint8_t *>(d);
-    };
-    dio.frame_point = out(io->frame_point, Fr * Cp * 4);
-    dio.local_kf = out(io->local_kf, Fr * R * 4);
-    dio.n_local_kf = out(io->n_local_kf, Fr * 4);
-    dio.votes = out(io->votes, Fr * R * 4);
-    dio.local_point = out(io->local_point, Fr * P * 4);
-    dio.world_l = out(io->world_l, Fr * P * 12);
-    dio.normal_l = out(io->normal_l, Fr * P * 12);
-    dio.max_dist_l = out(io->max_dist_l, Fr * P * 4);
-    dio.min_dist_l = out(io->min_dist_l, Fr * P * 4);
-    dio.desc_l = out(io->desc_l, Fr * P * 32);
-    dio.flags_l = out(io->flags_l, Fr * P);
-    dio.np_l = out(io->np_l, Fr * 4);
-    dio.taken = out(io->taken, Fr * Cp);
-    dio.report = out(io->report, Fr * 32);
-    const size_t out_bytes = st.off - out_off;
-    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            dt.slot_point = stg.put(slot_point, R * Cp);
+            dt.n = stg.put(n, R);
+            dt.kf_bad = t->kf_bad ? stg.put((const uint8_t *)t->kf_bad, R) : nullptr;
+            dt.covis = stg.put(covis, R * 10);
+            dt.child_start = stg.put(child_start, R + 1);
+            dt.child = stg.put(child, nchild);
+            dt.parent = stg.put(parent, R);
+            dt.obs_start = stg.put(obs_start, (size_t)np + 1);
+            dt.obs_kf = stg.put(obs_kf, nobs);
+            dt.flags = stg.put((const uint8_t *)t->flags, P);
+            dt.world = stg.put((const float *)t->world, P * 3);
+            dt.normal = stg.put((const float *)t->normal, P * 3);
+            dt.max_dist = stg.put((const float *)t->max_dist, P);
+            dt.min_dist = stg.put((const float *)t->min_dist, P);
+            dt.point_desc = stg.put((const uint8_t *)t->point_desc, P * 32);
+            dio.frame_n = stg.put(frame_n, Fr);
+            // in/out and output arrays next to each other, as the caller passed them: one copy brings all of them back
+            auto out = [&](void *host, size_t bytes) { return stg.inout((uint8_t *)host, bytes); };
+            dio.frame_point = out(io->frame_point, Fr * Cp * 4);
+            dio.local_kf = out(io->local_kf, Fr * R * 4);
+            dio.n_local_kf = out(io->n_local_kf, Fr * 4);
+            dio.votes = out(io->votes, Fr * R * 4);
+            dio.local_point = out(io->local_point, Fr * P * 4);
+            dio.world_l = out(io->world_l, Fr * P * 12);
+            dio.normal_l = out(io->normal_l, Fr * P * 12);
+            dio.max_dist_l = out(io->max_dist_l, Fr * P * 4);
+            dio.min_dist_l = out(io->min_dist_l, Fr * P * 4);
+            dio.desc_l = out(io->desc_l, Fr * P * 32);
+            dio.flags_l = out(io->flags_l, Fr * P);
+            dio.np_l = out(io->np_l, Fr * 4);
+            dio.taken = out(io->taken, Fr * Cp);
+            dio.report = out(io->report, Fr * 32);
+        }))) return rc;
     if ((rc = orbhip_update_local_map_device(m, frames, rows, cap, np, pcap, &dt, &dio))) return rc;
-    const uint8_t *h;
-    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
-    for (int i = 0; i < no; ++i)
-        if (outs[i].bytes) memcpy(outs[i].host, h + ((const uint8_t *)outs[i].dev - (st.d + out_off)), outs[i].bytes);
-    return ORBHIP_OK;
+    return stage_fetch(m, &st);
 }
 
 // ---- covisibility graph (kernels: orbhip_covisibility.hip) ------------------------------------------------------------
@@ -5423,65 +5397,47 @@ int orbhip_update_connections(orbhip_matcher *m, int rows, int cap, int np, int 
     if (U == 0 || rows == 0) return ORBHIP_OK;
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     const size_t R = (size_t)rows, Cp = (size_t)cap, T = resident.size(), Un = (size_t)U;
-    const size_t total = al256(R * 4) + al256(n_updated * Cp * 4) + al256(T * 4) + al256((size_t)np * 4 + 4) + al256(nobs * 4) +
-                         al256((size_t)np) + al256(Un * 4) + 3 * al256(T * R * 4) + 2 * al256(T * 4) + al256(T * 40) + al256(T) +
-                         al256(Un * 32);
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, total, &st))) return rc;
     orbhip_covis_tables dt;
     orbhip_covis_state ds;
-    const int32_t *d_row_slot = st.put(row_slot.data(), R);
-    {   // slot rows of the updated rows only: they hold the first slots
-        const int32_t *d;
-        int32_t *h = st.take(n_updated * Cp, &d);
-        for (size_t k = 0; h && k < n_updated; ++k) memcpy(h + k * Cp, slot_point + (size_t)resident[k] * Cp, Cp * 4);
-        dt.slot_point = d;
-        h = st.take(T, &d);
-        for (size_t k = 0; h && k < T; ++k) h[k] = n[resident[k]];
-        dt.n = d;
-    }
-    dt.obs_start = st.put(obs_start, (size_t)np + 1);
-    dt.obs_kf = st.put(obs_kf, nobs);
-    dt.flags = st.put(flags, (size_t)np);
-    const int32_t *d_update = st.put(update_rows, Un);
-    // the state rows and the report next to each other: one copy brings all of them back
-    const size_t out_off = st.off;
-    const int32_t *d_cw, *d_okf, *d_ow, *d_no, *d_cv, *d_par, *d_rep;
-    const uint8_t *d_fc;
-    int32_t *h_cw = st.take(T * R, &d_cw), *h_okf = st.take(T * R, &d_okf), *h_ow = st.take(T * R, &d_ow);
-    int32_t *h_no = st.take(T, &d_no), *h_cv = st.take(T * 10, &d_cv);
-    uint8_t *h_fc = st.take(T, &d_fc);
-    int32_t *h_par = st.take(T, &d_par);
-    st.take(Un * 8, &d_rep);
-    if ((rc = st.status())) return rc;
-    for (size_t k = 0; k < T; ++k) {
-        const size_t r = (size_t)resident[k];
-        memcpy(h_cw + k * R, conn_w + r * R, R * 4);
-        memcpy(h_okf + k * R, ord_kf + r * R, R * 4);
-        memcpy(h_ow + k * R, ord_w + r * R, R * 4);
-        memcpy(h_cv + k * 10, covis + r * 10, 40);
-        h_no[k] = n_ord[r]; h_fc[k] = first_conn[r]; h_par[k] = parent[r];
-    }
-    ds.conn_w = (void *)d_cw; ds.ord_kf = (void *)d_okf; ds.ord_w = (void *)d_ow; ds.n_ord = (void *)d_no; ds.covis = (void *)d_cv;
-    ds.first_conn = (void *)d_fc; ds.parent = (void *)d_par;
-    const size_t out_bytes = st.off - out_off;
-    if ((rc = stage_commit(m, &st))) return rc;
-    if ((rc = update_connections_launch(m, rows, cap, np, &dt, &ds, d_row_slot, id0_row, U, d_update, (void *)d_rep))) return rc;
-    const uint8_t *h;
-    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
-    auto back = [&](const void *dev) { return h + ((const uint8_t *)dev - (st.d + out_off)); };
-    for (size_t k = 0; k < T; ++k) {
-        const size_t r = (size_t)resident[k];
-        memcpy(conn_w + r * R, back(d_cw) + k * R * 4, R * 4);
-        memcpy(ord_kf + r * R, back(d_okf) + k * R * 4, R * 4);
-        memcpy(ord_w + r * R, back(d_ow) + k * R * 4, R * 4);
-        memcpy(covis + r * 10, back(d_cv) + k * 40, 40);
-        n_ord[r] = ((const int32_t *)back(d_no))[k];
-        first_conn[r] = back(d_fc)[k];
-        parent[r] = ((const int32_t *)back(d_par))[k];
-    }
-    memcpy(report, back(d_rep), Un * 32);
+    const int32_t *d_row_slot, *d_update;
+    int32_t *d_cw, *d_okf, *d_ow, *d_no, *d_cv, *d_par, *d_rep;
+    uint8_t *d_fc;
+    // a state table's resident rows, `width` T each, gathered into a piece that travels back for the scatter below
+    auto gather = [&](Stage &st, auto *table, size_t width) {
+        using E = std::remove_pointer_t<decltype(table)>;
+        E *d = st.fill<E>(T * width, [&](E *h) {
+            for (size_t k = 0; k < T; ++k) memcpy(h + k * width, table + (size_t)resident[k] * width, width * sizeof(E));
+        });
+        st.back((E *)nullptr, d, T * width);
+        return d;
+    };
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            d_row_slot = stg.put(row_slot.data(), R);
+            // slot rows of the updated rows only: they hold the first slots
+            dt.slot_point = stg.fill<int32_t>(n_updated * Cp, [&](int32_t *h) {
+                for (size_t k = 0; k < n_updated; ++k) memcpy(h + k * Cp, slot_point + (size_t)resident[k] * Cp, Cp * 4);
+            });
+            dt.n = stg.fill<int32_t>(T, [&](int32_t *h) { for (size_t k = 0; k < T; ++k) h[k] = n[resident[k]]; });
+            dt.obs_start = stg.put(obs_start, (size_t)np + 1);
+            dt.obs_kf = stg.put(obs_kf, nobs);
+            dt.flags = stg.put(flags, (size_t)np);
+            d_update = stg.put(update_rows, Un);
+            // the state rows and the report next to each other: one copy brings all of them back
+            ds.conn_w = d_cw = gather(stg, conn_w, R); ds.ord_kf = d_okf = gather(stg, ord_kf, R); ds.ord_w = d_ow = gather(stg, ord_w, R);
+            ds.n_ord = d_no = gather(stg, n_ord, 1); ds.covis = d_cv = gather(stg, covis, 10);
+            ds.first_conn = d_fc = gather(stg, first_conn, 1);
+            ds.parent = d_par = gather(stg, parent, 1);
+            d_rep = stg.out(report, Un * 8);
+        }))) return rc;
+    if ((rc = update_connections_launch(m, rows, cap, np, &dt, &ds, d_row_slot, id0_row, U, d_update, d_rep))) return rc;
+    if ((rc = stage_fetch(m, &st))) return rc;
+    auto scatter = [&](auto *table, const auto *d, size_t width) {
+        for (size_t k = 0; k < T; ++k) memcpy(table + (size_t)resident[k] * width, st.image(d) + k * width, width * sizeof(*table));
+    };
+    scatter(conn_w, d_cw, R); scatter(ord_kf, d_okf, R); scatter(ord_w, d_ow, R); scatter(n_ord, d_no, 1); scatter(covis, d_cv, 10);
+    scatter(first_conn, d_fc, 1); scatter(parent, d_par, 1);
     return ORBHIP_OK;
 }
 
@@ -5538,34 +5494,23 @@ int orbhip_covisible_targets(orbhip_matcher *m, int rows, const int32_t *ord_kf,
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     const size_t R = (size_t)rows, T = resident.size(), W = (size_t)std::min(std::max(nn, nn2), rows), Qn = (size_t)Q;
     const size_t out_cap = (size_t)nn * (1 + (size_t)nn2);
-    const size_t total = al256(R * 4) + al256(T * W * 4) + al256(T * 4) + al256(R) + al256(Qn * 4) + al256(Qn * out_cap * 4) + al256(Qn * 4);
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, total, &st))) return rc;
     CovisTargetArgs A;
-    A.row_slot = st.put(row_slot.data(), R);
-    int32_t *h_head = st.take(T * W, &A.ord_kf), *h_no = st.take(T, &A.n_ord);
-    if ((rc = st.status())) return rc;
-    for (size_t k = 0; k < T; ++k) {
-        memcpy(h_head + k * W, ord_kf + (size_t)resident[k] * R, W * 4);
-        h_no[k] = n_ord[resident[k]];
-    }
-    A.kf_bad = kf_bad ? st.put(kf_bad, R) : nullptr;
-    A.cur = st.put(cur, Qn);
-    const size_t out_off = st.off;
-    const int32_t *d_t, *d_c;
-    st.take(Qn * out_cap, &d_t);
-    st.take(Qn, &d_c);
-    const size_t out_bytes = st.off - out_off;
-    if ((rc = stage_commit(m, &st))) return rc;
-    A.targets = (int *)d_t; A.counts = (int *)d_c;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            A.row_slot = stg.put(row_slot.data(), R);
+            A.ord_kf = stg.fill<int32_t>(T * W, [&](int32_t *h_head) {
+                for (size_t k = 0; k < T; ++k) memcpy(h_head + k * W, ord_kf + (size_t)resident[k] * R, W * 4);
+            });
+            A.n_ord = stg.fill<int32_t>(T, [&](int32_t *h_no) { for (size_t k = 0; k < T; ++k) h_no[k] = n_ord[resident[k]]; });
+            A.kf_bad = kf_bad ? stg.put(kf_bad, R) : nullptr;
+            A.cur = stg.put(cur, Qn);
+            A.targets = stg.out(targets, Qn * out_cap);
+            A.counts = stg.out(counts, Qn);
+        }))) return rc;
     A.rows = rows; A.stride = (int)W; A.nn = nn; A.nn2 = nn2;
     if ((rc = launch_covisible_targets(m->stream, A, Q))) return rc;
-    const uint8_t *h;
-    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
-    memcpy(targets, h, Qn * out_cap * 4);
-    memcpy(counts, h + ((const uint8_t *)d_c - (st.d + out_off)), Qn * 4);
-    return ORBHIP_OK;
+    return stage_fetch(m, &st);
 }
 
 int orbhip_children_from_parents_device(orbhip_matcher *m, int rows, const void *d_parent, const void *d_kf_bad, void *d_child_start,
@@ -5708,8 +5653,7 @@ static int cull_check_tables(const char *who, int rows, int cap, int np, int obs
     return ORBHIP_OK;
 }
 
-// the tables both host forms stage; `outs` collects what travels back
-struct CullOut { void *host; const void *dev; size_t bytes; };
+// the tables both host forms stage
 static void cull_stage_tables(Stage &st, int rows, int cap, int np, int pcap, int obs_cap, size_t total, const orbhip_cull_tables *t,
                               orbhip_cull_tables *dt)
 {
@@ -5725,12 +5669,6 @@ static void cull_stage_tables(Stage &st, int rows, int cap, int np, int pcap, in
     dt->ref_obs = st.put((const int32_t *)t->ref_obs, (size_t)np);
     if (t->not_erase) dt->not_erase = st.put((const uint8_t *)t->not_erase, (size_t)rows);
     (void)pcap; (void)obs_cap;
-}
-static size_t cull_stage_bytes(int rows, int cap, int np, int obs_cap)
-{
-    const size_t RC = (size_t)rows * cap, R = (size_t)rows, P = (size_t)np, O = (size_t)obs_cap;
-    return al256(RC * sizeof(orbhip_keypoint)) + 3 * al256(RC * 4) + 8 * al256(R * 4 + 4) + 4 * al256(P * 4 + 4) + al256(P) + 4 * al256(O * 4) +
-           3 * al256(R * R * 4) + al256(R * 40);
 }
 
 int orbhip_cull_map_points(orbhip_matcher *m, int rows, int cap, int np, int pcap, int obs_cap, const orbhip_cull_tables *t,
@@ -5750,46 +5688,31 @@ int orbhip_cull_map_points(orbhip_matcher *m, int rows, int cap, int np, int pca
     const size_t RC = (size_t)rows * cap, P = (size_t)np, Rn = (size_t)R;
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, cull_stage_bytes(rows, cap, np, obs_cap) + 6 * al256(Rn * 4 + 4) + 3 * al256(P * 4), &st))) return rc;
     orbhip_cull_tables dt;
     orbhip_cull_io dio;
     memset(&dio, 0, sizeof(dio));
     orbhip_cull_tables th = *t;
     th.kps = nullptr; th.depth = nullptr; th.n = nullptr; th.not_erase = nullptr;       // not read by this call
-    cull_stage_tables(st, rows, cap, np, pcap, obs_cap, total, &th, &dt);
-    const int32_t *d_recent = st.put(recent, Rn), *d_found = st.put(found, P), *d_visible = st.put(visible, P);
-    const int32_t *d_first = st.put(first_kf_id, P);
-    const size_t out_off = st.off;
-    CullOut outs[9];
-    int no = 0;
-    auto inout = [&](void *host, size_t bytes) {
-        const uint8_t *d = st.put((const uint8_t *)host, bytes);
-        outs[no++] = {host, d, bytes};
-        return (void *)d;
-    };
-    auto out = [&](void *host, size_t bytes) {
-        const uint8_t *d;
-        st.take(bytes, &d);
-        outs[no++] = {host, d, bytes};
-        return (void *)d;
-    };
-    dio.slot_point = inout(io->slot_point, RC * 4);
-    dio.flags = inout(io->flags, P);
-    dio.obs_start_out = out(io->obs_start_out, (P + 1) * 4);
-    dio.obs_kf_out = inout(io->obs_kf_out, total * 4);
-    dio.obs_idx_out = inout(io->obs_idx_out, total * 4);
-    dio.ref_obs_out = out(io->ref_obs_out, P * 4);
-    void *d_recent_out = inout(recent_out, Rn * 4), *d_n_out = out(n_recent_out, 4), *d_status = out(status, Rn);
-    const size_t out_bytes = st.off - out_off;
-    if ((rc = stage_commit(m, &st))) return rc;
+    const int32_t *d_recent, *d_found, *d_visible, *d_first;
+    void *d_recent_out, *d_n_out, *d_status;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            auto inout = [&](void *host, size_t bytes) { return stg.inout((uint8_t *)host, bytes); };
+            auto out = [&](void *host, size_t bytes) { return stg.out((uint8_t *)host, bytes); };
+            cull_stage_tables(stg, rows, cap, np, pcap, obs_cap, total, &th, &dt);
+            d_recent = stg.put(recent, Rn); d_found = stg.put(found, P); d_visible = stg.put(visible, P);
+            d_first = stg.put(first_kf_id, P);
+            dio.slot_point = inout(io->slot_point, RC * 4);
+            dio.flags = inout(io->flags, P);
+            dio.obs_start_out = out(io->obs_start_out, (P + 1) * 4);
+            dio.obs_kf_out = inout(io->obs_kf_out, total * 4);
+            dio.obs_idx_out = inout(io->obs_idx_out, total * 4);
+            dio.ref_obs_out = out(io->ref_obs_out, P * 4);
+            d_recent_out = inout(recent_out, Rn * 4); d_n_out = out(n_recent_out, 4); d_status = out(status, Rn);
+        }))) return rc;
     if ((rc = cull_map_points_launch(m, rows, cap, np, obs_cap, &dt, &dio, R, d_recent, d_found, d_visible, d_first, cur_kf_id, th_obs,
                                      d_recent_out, d_n_out, d_status)))
         return rc;
-    const uint8_t *h;
-    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
-    for (int i = 0; i < no; ++i)
-        if (outs[i].bytes) memcpy(outs[i].host, h + ((const uint8_t *)outs[i].dev - (st.d + out_off)), outs[i].bytes);
-    return ORBHIP_OK;
+    return stage_fetch(m, &st);
 }
 
 int orbhip_cull_key_frames(orbhip_matcher *m, int rows, int cap, int np, int pcap, int obs_cap, const orbhip_cull_tables *t,
@@ -5823,53 +5746,38 @@ int orbhip_cull_key_frames(orbhip_matcher *m, int rows, int cap, int np, int pca
     const size_t RC = (size_t)rows * cap, P = (size_t)np, Rw = (size_t)rows, Un = (size_t)U;
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, cull_stage_bytes(rows, cap, np, obs_cap) + al256(Un * 4 + 4) + al256(Un * 32), &st))) return rc;
     orbhip_cull_tables dt;
     orbhip_cull_io dio;
     orbhip_covis_state ds;
     memset(&dio, 0, sizeof(dio));
     memset(&ds, 0, sizeof(ds));
-    cull_stage_tables(st, rows, cap, np, pcap, obs_cap, total, t, &dt);
-    const int32_t *d_cand = st.put(cand, Un);
-    const size_t out_off = st.off;
-    CullOut outs[20];
-    int no = 0;
-    auto inout = [&](void *host, size_t bytes) {
-        const uint8_t *d = st.put((const uint8_t *)host, bytes);
-        outs[no++] = {host, d, bytes};
-        return (void *)d;
-    };
-    auto out = [&](void *host, size_t bytes) {
-        const uint8_t *d;
-        st.take(bytes, &d);
-        outs[no++] = {host, d, bytes};
-        return (void *)d;
-    };
-    dio.slot_point = inout(io->slot_point, RC * 4);
-    dio.flags = inout(io->flags, P);
-    dio.kf_bad = inout(io->kf_bad, Rw);
-    if (io->to_be_erased) dio.to_be_erased = inout(io->to_be_erased, Rw);
-    dio.child_start = out(io->child_start, (Rw + 1) * 4);
-    dio.child = inout(io->child, Rw * 4);
-    dio.obs_start_out = out(io->obs_start_out, (P + 1) * 4);
-    dio.obs_kf_out = inout(io->obs_kf_out, total * 4);
-    dio.obs_idx_out = inout(io->obs_idx_out, total * 4);
-    dio.ref_obs_out = out(io->ref_obs_out, P * 4);
-    ds.conn_w = inout(s->conn_w, Rw * Rw * 4);
-    ds.ord_kf = inout(s->ord_kf, Rw * Rw * 4);
-    ds.ord_w = inout(s->ord_w, Rw * Rw * 4);
-    ds.n_ord = inout(s->n_ord, Rw * 4);
-    ds.covis = inout(s->covis, Rw * 40);
-    ds.parent = inout(s->parent, Rw * 4);
-    void *d_report = out(report, Un * 32);
-    const size_t out_bytes = st.off - out_off;
-    if ((rc = stage_commit(m, &st))) return rc;
+    const int32_t *d_cand;
+    void *d_report;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            auto inout = [&](void *host, size_t bytes) { return stg.inout((uint8_t *)host, bytes); };
+            auto out = [&](void *host, size_t bytes) { return stg.out((uint8_t *)host, bytes); };
+            cull_stage_tables(stg, rows, cap, np, pcap, obs_cap, total, t, &dt);
+            d_cand = stg.put(cand, Un);
+            dio.slot_point = inout(io->slot_point, RC * 4);
+            dio.flags = inout(io->flags, P);
+            dio.kf_bad = inout(io->kf_bad, Rw);
+            if (io->to_be_erased) dio.to_be_erased = inout(io->to_be_erased, Rw);
+            dio.child_start = out(io->child_start, (Rw + 1) * 4);
+            dio.child = inout(io->child, Rw * 4);
+            dio.obs_start_out = out(io->obs_start_out, (P + 1) * 4);
+            dio.obs_kf_out = inout(io->obs_kf_out, total * 4);
+            dio.obs_idx_out = inout(io->obs_idx_out, total * 4);
+            dio.ref_obs_out = out(io->ref_obs_out, P * 4);
+            ds.conn_w = inout(s->conn_w, Rw * Rw * 4);
+            ds.ord_kf = inout(s->ord_kf, Rw * Rw * 4);
+            ds.ord_w = inout(s->ord_w, Rw * Rw * 4);
+            ds.n_ord = inout(s->n_ord, Rw * 4);
+            ds.covis = inout(s->covis, Rw * 40);
+            ds.parent = inout(s->parent, Rw * 4);
+            d_report = out(report, Un * 32);
+        }))) return rc;
     if ((rc = cull_key_frames_launch(m, rows, cap, np, obs_cap, &dt, &dio, &ds, id0_row, U, d_cand, mono, th_depth, d_report))) return rc;
-    const uint8_t *h;
-    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
-    for (int i = 0; i < no; ++i)
-        if (outs[i].bytes) memcpy(outs[i].host, h + ((const uint8_t *)outs[i].dev - (st.d + out_off)), outs[i].bytes);
-    return ORBHIP_OK;
+    return stage_fetch(m, &st);
 }
 
 // ---- Sim3 RANSAC (kernels: orbhip_sim3.hip) ---------------------------------------------------------------------------
@@ -6075,25 +5983,22 @@ int orbhip_sim3_ransac(orbhip_matcher *m, int C, int cur, const int32_t *kf_inde
     const size_t CC = Cn * cap;
     Stage st;
     int rc;
-    const size_t in_bytes = 2 * al256(RC * 4) + al256(RC * sizeof(orbhip_keypoint)) + al256(P * 4 + 4) + 2 * al256(total * 4) + al256(P) +
-                            al256(P * 12) + al256((size_t)rows * 48) + al256((size_t)rows * 4) + al256(Cn * 4) + al256(CC * 4) +
-                            al256(Cn * max_its * 12);
-    const size_t out_size = al256(Cn * 64) + al256(CC) + al256(Cn * 32) + al256(Cn * 8);
-    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
     orbhip_sim3_tables dt;
-    dt.slot_point = st.put(slot_point, RC); dt.obs_start = st.put(obs_start, P + 1); dt.obs_kf = st.put(obs_kf, total);
-    dt.obs_idx = st.put(obs_idx, total); dt.flags = st.put((const uint8_t *)t->flags, P); dt.world = st.put((const float *)t->world, P * 3);
-    dt.Tcw = st.put((const float *)t->Tcw, (size_t)rows * 12); dt.kps = st.put(kps, RC); dt.n = st.put(n, (size_t)rows);
-    const int32_t *d_kf = st.put(kf_index, Cn), *d_matched = st.put(matched12, CC), *d_draws = st.put(draws, Cn * max_its * 3);
-    const size_t out_off = st.off;
-    const float *d_sim3 = st.put(sim3, Cn * 16);
-    const uint8_t *d_inl = st.put(inliers, CC);
-    const int32_t *d_rep = st.put(report, Cn * 8), *d_state;
-    int32_t *h_state = st.take(Cn * 2, &d_state);
-    if (h_state) {
-        if (state) memcpy(h_state, state, Cn * 8); else memset(h_state, 0, Cn * 8);
-    }
-    const size_t out_bytes = st.off - out_off;
+    const int32_t *d_kf, *d_matched, *d_draws;
+    float *d_sim3;
+    uint8_t *d_inl;
+    int32_t *d_rep, *d_state;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            dt.slot_point = stg.put(slot_point, RC); dt.obs_start = stg.put(obs_start, P + 1); dt.obs_kf = stg.put(obs_kf, total);
+            dt.obs_idx = stg.put(obs_idx, total); dt.flags = stg.put((const uint8_t *)t->flags, P);
+            dt.world = stg.put((const float *)t->world, P * 3);
+            dt.Tcw = stg.put((const float *)t->Tcw, (size_t)rows * 12); dt.kps = stg.put(kps, RC); dt.n = stg.put(n, (size_t)rows);
+            d_kf = stg.put(kf_index, Cn); d_matched = stg.put(matched12, CC); d_draws = stg.put(draws, Cn * max_its * 3);
+            d_sim3 = stg.inout(sim3, Cn * 16);
+            d_inl = stg.inout(inliers, CC);
+            d_rep = stg.inout(report, Cn * 8);
+            d_state = state ? stg.inout(state, Cn * 2) : stg.fill<int32_t>(Cn * 2, [&](int32_t *h_state) { memset(h_state, 0, Cn * 8); });
+        }))) return rc;
     // the solvers live in the handle for the length of the call
     void *sv;
     if ((rc = scratch(m, S_SIM3SOLV, 11 * al256(CC * 12), &sv))) return rc;
@@ -6103,20 +6008,13 @@ int orbhip_sim3_ransac(orbhip_matcher *m, int C, int cur, const int32_t *kf_inde
     ds.x1 = carve(CC * 12); ds.x2 = carve(CC * 12); ds.p1 = carve(CC * 8); ds.p2 = carve(CC * 8); ds.max_err1 = carve(CC * 4);
     ds.max_err2 = carve(CC * 4); ds.slot1 = carve(CC * 4); ds.n_corr = carve(Cn * 4); ds.n1 = carve(Cn * 4); ds.limit = carve(Cn * 4);
     ds.state = carve(Cn * 8);
-    if ((rc = stage_commit(m, &st))) return rc;
     if ((rc = sim3_setup_launch(m, C, cur, d_kf, cam, rows, cap, np, &dt, d_matched, match_form, level_sigma2, prob, min_inliers, max_its, &ds)))
         return rc;
     ORBHIP_HIP_CHECK(hipMemcpyAsync(ds.state, d_state, Cn * 8, hipMemcpyDeviceToDevice, m->stream));
-    if ((rc = sim3_iterate_launch(m, C, cap, cam, &ds, d_draws, max_its, n_iterations, min_inliers, fix_scale, (void *)d_sim3, (void *)d_inl,
-                                  (void *)d_rep)))
+    if ((rc = sim3_iterate_launch(m, C, cap, cam, &ds, d_draws, max_its, n_iterations, min_inliers, fix_scale, d_sim3, d_inl, d_rep)))
         return rc;
-    ORBHIP_HIP_CHECK(hipMemcpyAsync((void *)d_state, ds.state, Cn * 8, hipMemcpyDeviceToDevice, m->stream));
-    const uint8_t *h;
-    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
-    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
-    back(sim3, d_sim3, Cn * 64); back(inliers, d_inl, CC); back(report, d_rep, Cn * 32);
-    if (state) back(state, d_state, Cn * 8);
-    return ORBHIP_OK;
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(d_state, ds.state, Cn * 8, hipMemcpyDeviceToDevice, m->stream));
+    return stage_fetch(m, &st);
 }
 
 // ---- PnP RANSAC (kernels: orbhip_pnp.hip) ------------------------------------------------------------------------------
@@ -6304,35 +6202,26 @@ int orbhip_pnp_ransac(orbhip_matcher *m, int C, const orbhip_keypoint *kps, int 
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     Stage st;
     int rc;
-    const size_t in_bytes = al256((size_t)n * sizeof(orbhip_keypoint)) + al256(CC * 4) + al256(Cn * 4) + al256(RC * 4) + al256(P) +
-                            al256(P * 12) + al256(Cn * draw_rows * 16);
-    const size_t out_size = al256(Cn * 48) + al256(CC) + al256(Cn * 32) + al256(Cn * 8) + al256(CC) + al256(Cn * 48);
-    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
-    const orbhip_keypoint *d_kps = st.put(kps, (size_t)n);
-    const int32_t *d_matches = st.put(matches, CC), *d_kf = slots ? st.put(kf_index, Cn) : nullptr;
+    const orbhip_keypoint *d_kps;
+    const int32_t *d_matches, *d_kf, *d_draws;
     orbhip_pnp_map dm;
-    dm.slot_point = slots ? st.put(slot_point, RC) : nullptr;
-    dm.flags = st.put(flags, P); dm.world = st.put((const float *)map->world, P * 3);
-    const int32_t *d_draws = st.put(draws, Cn * draw_rows * 4);
-    const size_t out_off = st.off;
-    const float *d_Tcw = st.put(Tcw, Cn * 12);
-    const uint8_t *d_inl = st.put(inliers, CC);
-    const int32_t *d_rep = st.put(report, Cn * 8), *d_state;
-    int32_t *h_state = st.take(Cn * 2, &d_state);
-    if (h_state) {
-        if (state) memcpy(h_state, state, Cn * 8); else memset(h_state, 0, Cn * 8);
-    }
-    const uint8_t *d_bi;
-    uint8_t *h_bi = st.take(CC, &d_bi);
-    if (h_bi) {
-        if (best_inliers) memcpy(h_bi, best_inliers, CC); else memset(h_bi, 0, CC);
-    }
-    const float *d_bt;
-    float *h_bt = st.take(Cn * 12, &d_bt);
-    if (h_bt) {
-        if (best_Tcw) memcpy(h_bt, best_Tcw, Cn * 48); else memset(h_bt, 0, Cn * 48);
-    }
-    const size_t out_bytes = st.off - out_off;
+    float *d_Tcw, *d_bt;
+    uint8_t *d_inl, *d_bi;
+    int32_t *d_rep, *d_state;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            d_kps = stg.put(kps, (size_t)n);
+            d_matches = stg.put(matches, CC); d_kf = slots ? stg.put(kf_index, Cn) : nullptr;
+            dm.slot_point = slots ? stg.put(slot_point, RC) : nullptr;
+            dm.flags = stg.put(flags, P); dm.world = stg.put((const float *)map->world, P * 3);
+            d_draws = stg.put(draws, Cn * draw_rows * 4);
+            d_Tcw = stg.inout(Tcw, Cn * 12);
+            d_inl = stg.inout(inliers, CC);
+            d_rep = stg.inout(report, Cn * 8);
+            // state, best_inliers and best_Tcw go together: the caller's, or zeros that do not travel back
+            d_state = state ? stg.inout(state, Cn * 2) : stg.fill<int32_t>(Cn * 2, [&](int32_t *h) { memset(h, 0, Cn * 8); });
+            d_bi = state ? stg.inout(best_inliers, CC) : stg.fill<uint8_t>(CC, [&](uint8_t *h) { memset(h, 0, CC); });
+            d_bt = state ? stg.inout(best_Tcw, Cn * 12) : stg.fill<float>(Cn * 12, [&](float *h) { memset(h, 0, Cn * 48); });
+        }))) return rc;
     // the rest of the solver record lives in the handle for the length of the call
     void *sv;
     if ((rc = scratch(m, S_PNPSOLV, al256(CC * 8) + al256(CC * 12) + 2 * al256(CC * 4) + 4 * al256(Cn * 8), &sv))) return rc;
@@ -6341,20 +6230,12 @@ int orbhip_pnp_ransac(orbhip_matcher *m, int C, const orbhip_keypoint *kps, int 
     orbhip_pnp_solvers ds;
     ds.p2d = carve(CC * 8); ds.p3d = carve(CC * 12); ds.max_err = carve(CC * 4); ds.kp_index = carve(CC * 4); ds.n_corr = carve(Cn * 4);
     ds.min_inliers = carve(Cn * 4); ds.limit = carve(Cn * 4); ds.state = carve(Cn * 8);
-    ds.best_inliers = (void *)d_bi; ds.best_Tcw = (void *)d_bt;
-    if ((rc = stage_commit(m, &st))) return rc;
+    ds.best_inliers = d_bi; ds.best_Tcw = d_bt;
     if ((rc = pnp_setup_launch(m, C, d_kps, n, cap, d_matches, match_form, d_kf, rows, np, &dm, cam, level_sigma2, params, &ds))) return rc;
     ORBHIP_HIP_CHECK(hipMemcpyAsync(ds.state, d_state, Cn * 8, hipMemcpyDeviceToDevice, m->stream));
-    if ((rc = pnp_iterate_launch(m, C, n, cap, cam, params, &ds, d_draws, draw_rows, n_iterations, (void *)d_Tcw,
-                                 (void *)d_inl, (void *)d_rep)))
-        return rc;
-    ORBHIP_HIP_CHECK(hipMemcpyAsync((void *)d_state, ds.state, Cn * 8, hipMemcpyDeviceToDevice, m->stream));
-    const uint8_t *h;
-    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
-    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
-    back(Tcw, d_Tcw, Cn * 48); back(inliers, d_inl, CC); back(report, d_rep, Cn * 32);
-    if (state) { back(state, d_state, Cn * 8); back(best_inliers, d_bi, CC); back(best_Tcw, d_bt, Cn * 48); }
-    return ORBHIP_OK;
+    if ((rc = pnp_iterate_launch(m, C, n, cap, cam, params, &ds, d_draws, draw_rows, n_iterations, d_Tcw, d_inl, d_rep))) return rc;
+    ORBHIP_HIP_CHECK(hipMemcpyAsync(d_state, ds.state, Cn * 8, hipMemcpyDeviceToDevice, m->stream));
+    return stage_fetch(m, &st);
 }
 
 // ---- pose optimisation (kernel: orbhip_poseopt.hip) ----------------------------------------------------------------------
@@ -6388,11 +6269,8 @@ static int poseopt_launch(orbhip_matcher *m, int frames, const void *d_kps, cons
     A.world = (const float *)d_world; A.point_flags = (const uint8_t *)d_point_flags; A.world_row = (const int *)d_world_row;
     A.Tcw = (float *)d_Tcw; A.frame_point = (int *)d_frame_point; A.outlier = (uint8_t *)d_outlier; A.discarded = (int *)d_discarded;
     A.report = (int *)d_report;
-    for (int l = 0; l < ORBHIP_MAX_LEVELS; ++l) A.inv[l] = l < cam->n_levels ? inv_level_sigma2[l] : 0.f;
-    A.cam.fx = (double)cam->fx; A.cam.fy = (double)cam->fy; A.cam.cx = (double)cam->cx; A.cam.cy = (double)cam->cy;
-    A.cam.bf = (double)cam->mbf;
-    A.cam.delta_mono = (double)(float)std::sqrt(5.991);                       // src/Optimizer.cc:273-274
-    A.cam.delta_stereo = (double)(float)std::sqrt(7.815);
+    fill_inv_sigma2(A.inv, cam, inv_level_sigma2);
+    A.cam = po_cam(cam, 5.991, 7.815);                                        // src/Optimizer.cc:273-274
     A.frames = frames; A.cap = cap; A.wrows = wrows; A.pcap = pcap; A.n_levels = cam->n_levels; A.mode = mode; A.flags = flags;
     return launch_pose_optimization(m->stream, A);
 }
@@ -6443,32 +6321,30 @@ int orbhip_pose_optimization(orbhip_matcher *m, int frames, const orbhip_keypoin
     Stage st;
     int rc;
     const size_t Fn = (size_t)frames, FC = Fn * cap, WP = (size_t)wrows * pcap;
-    const size_t in_bytes = al256(FC * sizeof(orbhip_keypoint)) + al256(Fn * 4) + al256(FC * 4) + al256(WP * 12) + al256(WP) + al256(Fn * 4);
-    const size_t out_size = al256(Fn * 48) + al256(FC * 4) + al256(FC) + al256(FC * 4) + al256(Fn * 32);
-    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
-    const orbhip_keypoint *d_kps = st.put(kps, FC);
-    const int32_t *d_n = st.put(n, Fn);
-    const float *d_ur = u_right ? st.put(u_right, FC) : nullptr;
-    const float *d_world = st.put(world, WP * 3);
-    const uint8_t *d_pf = point_flags ? st.put(point_flags, WP) : nullptr;
-    const int32_t *d_row = world_row ? st.put(world_row, Fn) : nullptr;
-    const size_t out_off = st.off;
-    const float *d_Tcw = st.put(Tcw, Fn * 12);
-    const int32_t *d_fp = st.put(frame_point, FC);
-    const uint8_t *d_out = st.put(outlier, FC);
-    const int32_t *d_dis = discarded ? st.put(discarded, FC) : nullptr;
-    const int32_t *d_rep = st.put(report, Fn * 8);
-    const size_t out_bytes = st.off - out_off;
-    if ((rc = stage_commit(m, &st))) return rc;
+    const orbhip_keypoint *d_kps;
+    const int32_t *d_n, *d_row;
+    const float *d_ur, *d_world;
+    const uint8_t *d_pf;
+    float *d_Tcw;
+    int32_t *d_fp, *d_dis, *d_rep;
+    uint8_t *d_out;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            d_kps = stg.put(kps, FC);
+            d_n = stg.put(n, Fn);
+            d_ur = u_right ? stg.put(u_right, FC) : nullptr;
+            d_world = stg.put(world, WP * 3);
+            d_pf = point_flags ? stg.put(point_flags, WP) : nullptr;
+            d_row = world_row ? stg.put(world_row, Fn) : nullptr;
+            d_Tcw = stg.inout(Tcw, Fn * 12);
+            d_fp = stg.inout(frame_point, FC);
+            d_out = stg.inout(outlier, FC);
+            d_dis = discarded ? stg.inout(discarded, FC) : nullptr;
+            d_rep = stg.inout(report, Fn * 8);
+        }))) return rc;
     if ((rc = poseopt_launch(m, frames, d_kps, d_n, cap, d_ur, d_world, d_pf, wrows, pcap, d_row, cam, inv_level_sigma2, mode, flags,
-                             (void *)d_Tcw, (void *)d_fp, (void *)d_out, (void *)d_dis, (void *)d_rep)))
+                             d_Tcw, d_fp, d_out, d_dis, d_rep)))
         return rc;
-    const uint8_t *h;
-    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
-    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
-    back(Tcw, d_Tcw, Fn * 48); back(frame_point, d_fp, FC * 4); back(outlier, d_out, FC); back(report, d_rep, Fn * 32);
-    if (discarded) back(discarded, d_dis, FC * 4);
-    return ORBHIP_OK;
+    return stage_fetch(m, &st);
 }
 
 // ---- Sim3 optimisation (kernel: orbhip_sim3opt.hip) ----------------------------------------------------------------------
@@ -6499,7 +6375,7 @@ static int sim3opt_launch(orbhip_matcher *m, int C, int cur, const void *d_kf_in
     A.kps = (const orbhip_keypoint *)t->kps; A.world = (const float *)t->world; A.Tcw = (const float *)t->Tcw;
     A.kf_index = (const int *)d_kf_index; A.select = (const uint8_t *)d_select; A.sim3 = (const float *)d_sim3;
     A.matched12 = (int *)d_matched12; A.S12 = (double *)d_S12; A.Scw = (float *)d_Scw; A.report = (int *)d_report;
-    for (int l = 0; l < ORBHIP_MAX_LEVELS; ++l) A.inv[l] = l < cam->n_levels ? inv_level_sigma2[l] : 0.f;
+    fill_inv_sigma2(A.inv, cam, inv_level_sigma2);
     A.cam.fx = (double)cam->fx; A.cam.fy = (double)cam->fy; A.cam.cx = (double)cam->cx; A.cam.cy = (double)cam->cy;
     A.delta = (double)std::sqrt(th2);                                          // src/Optimizer.cc:1095: a float
     A.th2 = (double)th2;
@@ -6551,34 +6427,30 @@ int orbhip_optimize_sim3(orbhip_matcher *m, int C, int cur, const int32_t *kf_in
     const size_t RC = (size_t)rows * cap, P = (size_t)np, Cn = (size_t)C, CC = Cn * cap, total = (size_t)obs_start[np];
     Stage st;
     int rc;
-    const size_t in_bytes = 2 * al256(RC * 4) + al256(RC * sizeof(orbhip_keypoint)) + al256(P * 4 + 4) + 2 * al256(total * 4) + al256(P) +
-                            al256(P * 12) + al256((size_t)rows * 48) + al256((size_t)rows * 4) + al256(Cn * 4) + al256(Cn) + al256(Cn * 64);
-    const size_t out_size = al256(CC * 4) + al256(Cn * 64) + al256(Cn * 48) + al256(Cn * 32);
-    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
     orbhip_sim3_tables dt;
-    dt.slot_point = st.put(slot_point, RC); dt.obs_start = st.put(obs_start, P + 1);
-    dt.obs_kf = st.put((const int32_t *)t->obs_kf, total); dt.obs_idx = st.put((const int32_t *)t->obs_idx, total);
-    dt.flags = st.put((const uint8_t *)t->flags, P); dt.world = st.put((const float *)t->world, P * 3);
-    dt.Tcw = st.put((const float *)t->Tcw, (size_t)rows * 12); dt.kps = st.put(kps, RC); dt.n = st.put(n, (size_t)rows);
-    const int32_t *d_kf = st.put(kf_index, Cn);
-    const uint8_t *d_sel = select ? st.put(select, Cn) : nullptr;
-    const float *d_sim3 = st.put(sim3, Cn * 16);
-    const size_t out_off = st.off;
-    const int32_t *d_matched = st.put(matched12, CC);
-    const double *d_S12 = st.put(S12, Cn * 8);
-    const float *d_Scw = Scw ? st.put(Scw, Cn * 12) : nullptr;
-    const int32_t *d_rep = st.put(report, Cn * 8);
-    const size_t out_bytes = st.off - out_off;
-    if ((rc = stage_commit(m, &st))) return rc;
-    if ((rc = sim3opt_launch(m, C, cur, d_kf, cam, rows, cap, np, &dt, match_form, inv_level_sigma2, th2, fix_scale, d_sel,
-                             (void *)d_matched, d_sim3, (void *)d_S12, (void *)d_Scw, (void *)d_rep)))
+    const int32_t *d_kf;
+    const uint8_t *d_sel;
+    const float *d_sim3;
+    int32_t *d_matched, *d_rep;
+    double *d_S12;
+    float *d_Scw;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            dt.slot_point = stg.put(slot_point, RC); dt.obs_start = stg.put(obs_start, P + 1);
+            dt.obs_kf = stg.put((const int32_t *)t->obs_kf, total); dt.obs_idx = stg.put((const int32_t *)t->obs_idx, total);
+            dt.flags = stg.put((const uint8_t *)t->flags, P); dt.world = stg.put((const float *)t->world, P * 3);
+            dt.Tcw = stg.put((const float *)t->Tcw, (size_t)rows * 12); dt.kps = stg.put(kps, RC); dt.n = stg.put(n, (size_t)rows);
+            d_kf = stg.put(kf_index, Cn);
+            d_sel = select ? stg.put(select, Cn) : nullptr;
+            d_sim3 = stg.put(sim3, Cn * 16);
+            d_matched = stg.inout(matched12, CC);
+            d_S12 = stg.inout(S12, Cn * 8);
+            d_Scw = Scw ? stg.inout(Scw, Cn * 12) : nullptr;
+            d_rep = stg.inout(report, Cn * 8);
+        }))) return rc;
+    if ((rc = sim3opt_launch(m, C, cur, d_kf, cam, rows, cap, np, &dt, match_form, inv_level_sigma2, th2, fix_scale, d_sel, d_matched,
+                             d_sim3, d_S12, d_Scw, d_rep)))
         return rc;
-    const uint8_t *h;
-    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
-    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
-    back(matched12, d_matched, CC * 4); back(S12, d_S12, Cn * 64); back(report, d_rep, Cn * 32);
-    if (Scw) back(Scw, d_Scw, Cn * 48);
-    return ORBHIP_OK;
+    return stage_fetch(m, &st);
 }
 
 // ---- local bundle adjustment (kernels: orbhip_lba.hip) ---------------------------------------------------------------------
@@ -6609,11 +6481,8 @@ static int lba_launch(orbhip_matcher *m, int cur, int id0_row, const orbhip_came
     W.o_local_kf = (int *)out->local_kf; W.o_fixed_kf = (int *)out->fixed_kf; W.o_local_point = (int *)out->local_point;
     W.o_erase = (int *)out->erase; W.o_report = (int *)out->report;
     W.stop = (const uint8_t *)d_stop;
-    for (int l = 0; l < ORBHIP_MAX_LEVELS; ++l) W.inv[l] = l < cam->n_levels ? inv_level_sigma2[l] : 0.f;
-    W.cam.fx = (double)cam->fx; W.cam.fy = (double)cam->fy; W.cam.cx = (double)cam->cx; W.cam.cy = (double)cam->cy;
-    W.cam.bf = (double)cam->mbf;
-    W.cam.delta_mono = (double)(float)std::sqrt(5.991);                       // src/Optimizer.cc:569-570
-    W.cam.delta_stereo = (double)(float)std::sqrt(7.815);
+    fill_inv_sigma2(W.inv, cam, inv_level_sigma2);
+    W.cam = po_cam(cam, 5.991, 7.815);                                        // src/Optimizer.cc:569-570
     W.cur = cur; W.id0_row = id0_row; W.rows = rows; W.cap = cap; W.np = np; W.pcap = pcap; W.n_levels = cam->n_levels;
     W.max_points = max_points; W.max_edges = max_edges;
     void *ws;
@@ -6662,37 +6531,25 @@ int orbhip_local_bundle_adjustment(orbhip_matcher *m, int cur, int id0_row, cons
     const size_t MP = (size_t)max_points, ME = (size_t)max_edges;
     Stage st;
     int rc;
-    const size_t in_bytes = al256(RC * 4) + al256(R * 4) + al256(R) + al256(((size_t)np + 1) * 4) + 2 * al256(total * 4) + al256(P) +
-                            al256(RC * sizeof(orbhip_keypoint)) + al256(RC * 4) + al256(R * R * 4) + al256(R * 4) + 256;
-    const size_t out_size = al256(R * 48) + al256(P * 12) + 2 * al256(R * 4) + al256(MP * 4) + al256(ME * 12) + al256(64);
-    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
     orbhip_lba_tables dt;
-    dt.slot_point = st.put(slot_point, RC); dt.n = st.put(n, R);
-    dt.kf_bad = t->kf_bad ? st.put((const uint8_t *)t->kf_bad, R) : nullptr;
-    dt.obs_start = st.put(obs_start, (size_t)np + 1); dt.obs_kf = st.put(obs_kf, total); dt.obs_idx = st.put(obs_idx, total);
-    dt.flags = st.put((const uint8_t *)t->flags, P); dt.kps = st.put(kps, RC);
-    dt.u_right = t->u_right ? st.put((const float *)t->u_right, RC) : nullptr;
-    dt.ord_kf = st.put(ord_kf, R * R); dt.n_ord = st.put(n_ord, R);
-    const uint8_t *d_stop = stop ? st.put(stop, 1) : nullptr;
-    const size_t out_off = st.off;
-    const float *d_Tcw = st.put((const float *)t->Tcw, R * 12);
-    const float *d_world = st.put((const float *)t->world, P * 3);
     orbhip_lba_out dout;
-    const int32_t *d_lkf = st.put((const int32_t *)out->local_kf, R), *d_fkf = st.put((const int32_t *)out->fixed_kf, R);
-    const int32_t *d_lpt = st.put((const int32_t *)out->local_point, MP), *d_er = st.put((const int32_t *)out->erase, ME * 3);
-    const int32_t *d_rep = st.put((const int32_t *)out->report, 16);
-    const size_t out_bytes = st.off - out_off;
-    dt.Tcw = (void *)d_Tcw; dt.world = (void *)d_world;
-    dout.local_kf = (void *)d_lkf; dout.fixed_kf = (void *)d_fkf; dout.local_point = (void *)d_lpt; dout.erase = (void *)d_er;
-    dout.report = (void *)d_rep;
-    if ((rc = stage_commit(m, &st))) return rc;
+    const uint8_t *d_stop;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            dt.slot_point = stg.put(slot_point, RC); dt.n = stg.put(n, R);
+            dt.kf_bad = t->kf_bad ? stg.put((const uint8_t *)t->kf_bad, R) : nullptr;
+            dt.obs_start = stg.put(obs_start, (size_t)np + 1); dt.obs_kf = stg.put(obs_kf, total); dt.obs_idx = stg.put(obs_idx, total);
+            dt.flags = stg.put((const uint8_t *)t->flags, P); dt.kps = stg.put(kps, RC);
+            dt.u_right = t->u_right ? stg.put((const float *)t->u_right, RC) : nullptr;
+            dt.ord_kf = stg.put(ord_kf, R * R); dt.n_ord = stg.put(n_ord, R);
+            d_stop = stop ? stg.put(stop, 1) : nullptr;
+            dt.Tcw = stg.inout((float *)t->Tcw, R * 12);
+            dt.world = stg.inout((float *)t->world, P * 3);
+            dout.local_kf = stg.inout((int32_t *)out->local_kf, R); dout.fixed_kf = stg.inout((int32_t *)out->fixed_kf, R);
+            dout.local_point = stg.inout((int32_t *)out->local_point, MP); dout.erase = stg.inout((int32_t *)out->erase, ME * 3);
+            dout.report = stg.inout((int32_t *)out->report, 16);
+        }))) return rc;
     if ((rc = lba_launch(m, cur, id0_row, cam, rows, cap, np, pcap, &dt, inv_level_sigma2, max_points, max_edges, d_stop, &dout))) return rc;
-    const uint8_t *h;
-    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
-    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
-    back(t->Tcw, d_Tcw, R * 48); back(t->world, d_world, P * 12); back(out->local_kf, d_lkf, R * 4); back(out->fixed_kf, d_fkf, R * 4);
-    back(out->local_point, d_lpt, MP * 4); back(out->erase, d_er, ME * 12); back(out->report, d_rep, 64);
-    return ORBHIP_OK;
+    return stage_fetch(m, &st);
 }
 
 // ---- essential-graph optimisation (kernels: orbhip_essgraph.hip) -------------------------------------------------------------
@@ -6773,44 +6630,33 @@ int orbhip_optimize_essential_graph(orbhip_matcher *m, int cur, int loop_row, in
     const size_t R = (size_t)rows, P = (size_t)pcap, NL = (size_t)starts[0][rows], NC = (size_t)starts[1][rows];
     Stage st;
     int rc;
-    const size_t in_bytes = 4 * al256(R) + 3 * al256(R * 4) + 3 * al256(R * R * 4) + 2 * al256((R + 1) * 4) + al256((NL + 1) * 4) + al256((NC + 1) * 4) +
-                            2 * al256(R * 64) + al256(P + 1) + 3 * al256((P + 1) * 4) + 256;
-    const size_t out_size = al256(R * 48) + al256((P + 1) * 12) + al256((P + 1) * 4) + 2 * al256(R * 64) + al256(64);
-    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
     const int32_t zero = 0;
-    orbhip_eg_tables dt;
-    dt.kf_bad = kf_bad ? st.put(kf_bad, R) : nullptr;
-    dt.kf_id = st.put((const int32_t *)t->kf_id, R); dt.parent = st.put(parent, R);
-    dt.conn_w = st.put((const int32_t *)t->conn_w, R * R); dt.ord_kf = st.put(ord_kf, R * R); dt.ord_w = st.put((const int32_t *)t->ord_w, R * R);
-    dt.n_ord = st.put(n_ord, R);
-    dt.loop_start = st.put(starts[0], R + 1); dt.loop_kf = NL ? st.put(lists[0], NL) : st.put(&zero, 1);
-    dt.lc_start = st.put(starts[1], R + 1); dt.lc_kf = NC ? st.put(lists[1], NC) : st.put(&zero, 1);
-    dt.corrected = st.put((const double *)t->corrected, R * 8); dt.non_corrected = st.put((const double *)t->non_corrected, R * 8);
-    dt.in_corrected = st.put((const uint8_t *)t->in_corrected, R); dt.in_non_corrected = st.put((const uint8_t *)t->in_non_corrected, R);
     const uint8_t zb = 0;
-    dt.flags = P ? st.put((const uint8_t *)t->flags, P) : st.put(&zb, 1);
-    dt.ref_kf = P ? st.put(ref_kf, P) : st.put(&zero, 1);
-    dt.corrected_by_kf = P ? st.put((const int32_t *)t->corrected_by_kf, P) : st.put(&zero, 1);
-    dt.corrected_ref = P ? st.put(cref, P) : st.put(&zero, 1);
-    const size_t out_off = st.off;
-    const float fz[3] = {0.f, 0.f, 0.f};
-    const float *d_Tcw = st.put((const float *)t->Tcw, R * 12);
-    const float *d_world = P ? st.put((const float *)t->world, P * 3) : st.put(fz, 3);
-    const int32_t *d_pl = P ? st.put((const int32_t *)out->point_list, P) : st.put(&zero, 1);
-    const double *d_Scw = st.put((const double *)out->Scw, R * 8), *d_Swc = st.put((const double *)out->Swc, R * 8);
-    const int32_t *d_rep = st.put((const int32_t *)out->report, 16);
-    const size_t out_bytes = st.off - out_off;
-    dt.Tcw = (void *)d_Tcw; dt.world = (void *)d_world;
+    orbhip_eg_tables dt;
     orbhip_eg_out dout;
-    dout.point_list = (void *)d_pl; dout.Scw = (void *)d_Scw; dout.Swc = (void *)d_Swc; dout.report = (void *)d_rep;
-    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            dt.kf_bad = kf_bad ? stg.put(kf_bad, R) : nullptr;
+            dt.kf_id = stg.put((const int32_t *)t->kf_id, R); dt.parent = stg.put(parent, R);
+            dt.conn_w = stg.put((const int32_t *)t->conn_w, R * R); dt.ord_kf = stg.put(ord_kf, R * R);
+            dt.ord_w = stg.put((const int32_t *)t->ord_w, R * R);
+            dt.n_ord = stg.put(n_ord, R);
+            dt.loop_start = stg.put(starts[0], R + 1); dt.loop_kf = NL ? stg.put(lists[0], NL) : stg.put(&zero, 1);
+            dt.lc_start = stg.put(starts[1], R + 1); dt.lc_kf = NC ? stg.put(lists[1], NC) : stg.put(&zero, 1);
+            dt.corrected = stg.put((const double *)t->corrected, R * 8); dt.non_corrected = stg.put((const double *)t->non_corrected, R * 8);
+            dt.in_corrected = stg.put((const uint8_t *)t->in_corrected, R);
+            dt.in_non_corrected = stg.put((const uint8_t *)t->in_non_corrected, R);
+            dt.flags = P ? stg.put((const uint8_t *)t->flags, P) : stg.put(&zb, 1);
+            dt.ref_kf = P ? stg.put(ref_kf, P) : stg.put(&zero, 1);
+            dt.corrected_by_kf = P ? stg.put((const int32_t *)t->corrected_by_kf, P) : stg.put(&zero, 1);
+            dt.corrected_ref = P ? stg.put(cref, P) : stg.put(&zero, 1);
+            dt.Tcw = stg.inout((float *)t->Tcw, R * 12);
+            dt.world = P ? stg.inout((float *)t->world, P * 3) : stage_zeros<float>(stg, 3);
+            dout.point_list = P ? stg.inout((int32_t *)out->point_list, P) : stage_zeros<int32_t>(stg, 1);
+            dout.Scw = stg.inout((double *)out->Scw, R * 8); dout.Swc = stg.inout((double *)out->Swc, R * 8);
+            dout.report = stg.inout((int32_t *)out->report, 16);
+        }))) return rc;
     if ((rc = eg_launch(m, cur, loop_row, rows, pcap, &dt, fix_scale, max_edges, &dout))) return rc;
-    const uint8_t *h;
-    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
-    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
-    back(t->Tcw, d_Tcw, R * 48); back(out->Scw, d_Scw, R * 64); back(out->Swc, d_Swc, R * 64); back(out->report, d_rep, 64);
-    if (P) { back(t->world, d_world, P * 12); back(out->point_list, d_pl, P * 4); }
-    return ORBHIP_OK;
+    return stage_fetch(m, &st);
 }
 
 int orbhip_optimize_essential_graph_counters(orbhip_matcher *m, int32_t counters[2])
@@ -6848,11 +6694,8 @@ static int gba_launch(orbhip_matcher *m, const orbhip_camera *cam, int rows, int
     W.obs_idx = (const int *)t->obs_idx; W.flags = (const uint8_t *)t->flags; W.kps = (const orbhip_keypoint *)t->kps;
     W.u_right = (const float *)t->u_right; W.Tcw = (float *)t->Tcw; W.world = (float *)t->world;
     W.stop = (const uint8_t *)d_stop;
-    for (int l = 0; l < ORBHIP_MAX_LEVELS; ++l) W.inv[l] = l < cam->n_levels ? inv_level_sigma2[l] : 0.f;
-    W.cam.fx = (double)cam->fx; W.cam.fy = (double)cam->fy; W.cam.cx = (double)cam->cx; W.cam.cy = (double)cam->cy;
-    W.cam.bf = (double)cam->mbf;
-    W.cam.delta_mono = (double)(float)std::sqrt(5.99);                        // src/Optimizer.cc:85-86
-    W.cam.delta_stereo = (double)(float)std::sqrt(7.815);
+    fill_inv_sigma2(W.inv, cam, inv_level_sigma2);
+    W.cam = po_cam(cam, 5.99, 7.815);                                         // src/Optimizer.cc:85-86: 5.99, not 5.991
     W.cur = 0; W.id0_row = -1; W.rows = rows; W.cap = cap; W.np = np; W.pcap = pcap; W.n_levels = cam->n_levels;
     W.max_points = max_points; W.max_edges = max_edges;
     W.single_its = iterations; W.robust = robust ? 1 : 0;
@@ -6929,56 +6772,42 @@ int orbhip_global_bundle_adjustment(orbhip_matcher *m, const orbhip_camera *cam,
     const bool staged = mode == ORBHIP_GBA_STAGED;
     Stage st;
     int rc;
-    const size_t in_bytes = al256(R) + al256(R * 4) + al256(((size_t)np + 1) * 4) + 2 * al256(total * 4 + 4) + al256(P + 1) +
-                            al256(RC * sizeof(orbhip_keypoint)) + al256(RC * 4) + al256(NK * 4 + 4) + al256(NP * 4 + 4) + 256;
-    const size_t out_size = 2 * al256(R * 48) + 2 * al256(P * 12 + 12) + al256(R) + al256(P + 1) + al256(MP * 4) + al256(64);
-    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
     const int32_t zero = 0;
     const uint8_t zb = 0;
     const float fz[3] = {0.f, 0.f, 0.f};
     orbhip_gba_tables dt;
-    dt.kf_bad = kf_bad ? st.put(kf_bad, R) : nullptr; dt.kf_id = st.put(kf_id, R);
-    dt.obs_start = st.put(obs_start, (size_t)np + 1);
-    dt.obs_kf = total ? st.put(obs_kf, total) : st.put(&zero, 1); dt.obs_idx = total ? st.put(obs_idx, total) : st.put(&zero, 1);
-    dt.flags = P ? st.put(flags, P) : st.put(&zb, 1); dt.kps = st.put(kps, RC);
-    dt.u_right = t->u_right ? st.put((const float *)t->u_right, RC) : nullptr;
-    const int32_t *d_kfl = kf_list ? (NK ? st.put(kf_list, NK) : st.put(&zero, 1)) : nullptr;
-    const int32_t *d_ptl = pt_list ? (NP ? st.put(pt_list, NP) : st.put(&zero, 1)) : nullptr;
-    const uint8_t *d_stop = stop ? st.put(stop, 1) : nullptr;
-    const size_t out_off = st.off;
-    const float *d_Tcw = st.put((const float *)t->Tcw, R * 12);
-    const float *d_world = P ? st.put((const float *)t->world, P * 3) : st.put(fz, 3);
-    const float *d_TG = nullptr, *d_pG = nullptr;
-    const uint8_t *d_km = nullptr, *d_pm = nullptr;
-    const int32_t *d_pl = nullptr;
-    if (staged) {
-        d_TG = st.put((const float *)out->TcwGBA, R * 12); d_pG = P ? st.put((const float *)out->posGBA, P * 3) : st.put(fz, 3);
-        d_km = st.put((const uint8_t *)out->kf_mark, R); d_pm = P ? st.put((const uint8_t *)out->pt_mark, P) : st.put(&zb, 1);
-    } else {
-        d_pl = st.put((const int32_t *)out->point_list, MP);
-    }
-    const int32_t *d_rep = st.put((const int32_t *)out->report, 16);
-    const size_t out_bytes = st.off - out_off;
-    dt.Tcw = (void *)d_Tcw; dt.world = (void *)d_world;
     orbhip_gba_out dout;
-    dout.TcwGBA = (void *)d_TG; dout.posGBA = (void *)d_pG; dout.kf_mark = (void *)d_km; dout.pt_mark = (void *)d_pm;
-    dout.point_list = (void *)d_pl; dout.report = (void *)d_rep;
-    if ((rc = stage_commit(m, &st))) return rc;
+    memset(&dout, 0, sizeof(dout));
+    const int32_t *d_kfl, *d_ptl;
+    const uint8_t *d_stop;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            dt.kf_bad = kf_bad ? stg.put(kf_bad, R) : nullptr; dt.kf_id = stg.put(kf_id, R);
+            dt.obs_start = stg.put(obs_start, (size_t)np + 1);
+            dt.obs_kf = total ? stg.put(obs_kf, total) : stg.put(&zero, 1); dt.obs_idx = total ? stg.put(obs_idx, total) : stg.put(&zero, 1);
+            dt.flags = P ? stg.put(flags, P) : stg.put(&zb, 1); dt.kps = stg.put(kps, RC);
+            dt.u_right = t->u_right ? stg.put((const float *)t->u_right, RC) : nullptr;
+            d_kfl = kf_list ? (NK ? stg.put(kf_list, NK) : stg.put(&zero, 1)) : nullptr;
+            d_ptl = pt_list ? (NP ? stg.put(pt_list, NP) : stg.put(&zero, 1)) : nullptr;
+            d_stop = stop ? stg.put(stop, 1) : nullptr;
+            // in place: the poses, the points and the list travel back; staged: the GBA copies and the marks do
+            if (staged) {
+                dt.Tcw = const_cast<float *>(stg.put((const float *)t->Tcw, R * 12));   // read only in this mode
+                dt.world = const_cast<float *>(P ? stg.put((const float *)t->world, P * 3) : stg.put(fz, 3));
+                dout.TcwGBA = stg.inout((float *)out->TcwGBA, R * 12);
+                dout.posGBA = P ? stg.inout((float *)out->posGBA, P * 3) : stage_zeros<float>(stg, 3);
+                dout.kf_mark = stg.inout((uint8_t *)out->kf_mark, R);
+                dout.pt_mark = P ? stg.inout((uint8_t *)out->pt_mark, P) : stage_zeros<uint8_t>(stg, 1);
+            } else {
+                dt.Tcw = stg.inout((float *)t->Tcw, R * 12);
+                dt.world = P ? stg.inout((float *)t->world, P * 3) : stage_zeros<float>(stg, 3);
+                dout.point_list = stg.inout((int32_t *)out->point_list, MP);
+            }
+            dout.report = stg.inout((int32_t *)out->report, 16);
+        }))) return rc;
     if ((rc = gba_launch(m, cam, rows, cap, np, pcap, &dt, inv_level_sigma2, d_kfl, nkf, d_ptl, npt, iterations, robust, mode, max_points,
                          max_edges, d_stop, &dout)))
         return rc;
-    const uint8_t *h;
-    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
-    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
-    back(out->report, d_rep, 64);
-    if (staged) {
-        back(out->TcwGBA, d_TG, R * 48); back(out->kf_mark, d_km, R);
-        if (P) { back(out->posGBA, d_pG, P * 12); back(out->pt_mark, d_pm, P); }
-    } else {
-        back(t->Tcw, d_Tcw, R * 48); back(out->point_list, d_pl, MP * 4);
-        if (P) back(t->world, d_world, P * 12);
-    }
-    return ORBHIP_OK;
+    return stage_fetch(m, &st);
 }
 
 int orbhip_global_bundle_adjustment_counters(orbhip_matcher *m, int32_t counters[2])
@@ -7038,37 +6867,25 @@ int orbhip_apply_global_ba(orbhip_matcher *m, int n_origins, int rows, int pcap,
     const size_t R = (size_t)rows, P = (size_t)pcap, NO = (size_t)n_origins;
     Stage st;
     int rc;
-    const size_t in_bytes = al256(NO * 4 + 4) + al256(R * 4) + al256(R) + 2 * al256(P + 1) + al256(P * 12 + 12) + al256(P * 4 + 4) + 256;
-    const size_t out_size = al256(R) + 3 * al256(R * 48) + al256(P * 12 + 12) + al256(32);
-    if ((rc = stage_begin(m, in_bytes + out_size, &st))) return rc;
     const int32_t zero = 0;
     const uint8_t zb = 0;
     const float fz[3] = {0.f, 0.f, 0.f};
     orbhip_gba_apply d;
-    d.origins = NO ? st.put(origins, NO) : st.put(&zero, 1); d.parent = st.put(parent, R);
-    d.kf_bad = kf_bad ? st.put(kf_bad, R) : nullptr;
-    d.pt_mark = P ? st.put((const uint8_t *)a->pt_mark, P) : st.put(&zb, 1);
-    d.posGBA = P ? st.put((const float *)a->posGBA, P * 3) : st.put(fz, 3);
-    d.flags = P ? st.put((const uint8_t *)a->flags, P) : st.put(&zb, 1);
-    d.ref_kf = P ? st.put(ref_kf, P) : st.put(&zero, 1);
-    const size_t out_off = st.off;
-    const uint8_t *d_km = st.put(kf_mark, R);
-    const float *d_TG = st.put((const float *)a->TcwGBA, R * 12), *d_T = st.put((const float *)a->Tcw, R * 12);
-    const float *d_TB = st.put((const float *)a->TcwBefGBA, R * 12);
-    const float *d_world = P ? st.put((const float *)a->world, P * 3) : st.put(fz, 3);
-    const int32_t *d_rep = st.put((const int32_t *)a->report, 8);
-    const size_t out_bytes = st.off - out_off;
-    d.kf_mark = (void *)d_km; d.TcwGBA = (void *)d_TG; d.Tcw = (void *)d_T; d.TcwBefGBA = (void *)d_TB; d.world = (void *)d_world;
-    d.report = (void *)d_rep;
-    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            d.origins = NO ? stg.put(origins, NO) : stg.put(&zero, 1); d.parent = stg.put(parent, R);
+            d.kf_bad = kf_bad ? stg.put(kf_bad, R) : nullptr;
+            d.pt_mark = P ? stg.put((const uint8_t *)a->pt_mark, P) : stg.put(&zb, 1);
+            d.posGBA = P ? stg.put((const float *)a->posGBA, P * 3) : stg.put(fz, 3);
+            d.flags = P ? stg.put((const uint8_t *)a->flags, P) : stg.put(&zb, 1);
+            d.ref_kf = P ? stg.put(ref_kf, P) : stg.put(&zero, 1);
+            d.kf_mark = stg.inout((uint8_t *)a->kf_mark, R);
+            d.TcwGBA = stg.inout((float *)a->TcwGBA, R * 12); d.Tcw = stg.inout((float *)a->Tcw, R * 12);
+            d.TcwBefGBA = stg.inout((float *)a->TcwBefGBA, R * 12);
+            d.world = P ? stg.inout((float *)a->world, P * 3) : stage_zeros<float>(stg, 3);
+            d.report = stg.inout((int32_t *)a->report, 8);
+        }))) return rc;
     if ((rc = gba_apply_launch(m, n_origins, rows, pcap, &d))) return rc;
-    const uint8_t *h;
-    if ((rc = read_back(m, st.d + out_off, out_bytes, &h))) return rc;
-    auto back = [&](void *host, const void *dev, size_t bytes) { memcpy(host, h + ((const uint8_t *)dev - (st.d + out_off)), bytes); };
-    back(a->kf_mark, d_km, R); back(a->TcwGBA, d_TG, R * 48); back(a->Tcw, d_T, R * 48); back(a->TcwBefGBA, d_TB, R * 48);
-    back(a->report, d_rep, 32);
-    if (P) back(a->world, d_world, P * 12);
-    return ORBHIP_OK;
+    return stage_fetch(m, &st);
 }
 
 #ifdef ORBHIP_DEVTOOLS
@@ -7122,18 +6939,18 @@ int orbhip_keyframe_queries(orbhip_matcher *m, const orbhip_camera *cam, int mod
     if (!world || !max_dist || !min_dist || !flags || (mode == 0 && !normal)) return ORBHIP_E_ARG;
     ORBHIP_HIP_CHECK(hipSetDevice(m->device));
     Stage st;
-    int rc = stage_begin(m, 2 * al256(48) + 2 * al256((size_t)n * 12) + 2 * al256((size_t)n * 4) + al256((size_t)n), &st);
-    if (rc) return rc;
     KfQueryArgs A;
-    A.T1 = st.put(T1, 12);
-    A.T2 = T2 ? st.put(T2, 12) : nullptr;
-    A.world = st.put(world, (size_t)n * 3);
-    A.normal = normal ? st.put(normal, (size_t)n * 3) : nullptr;
-    A.max_dist = st.put(max_dist, (size_t)n);
-    A.min_dist = st.put(min_dist, (size_t)n);
-    A.flags = st.put(flags, (size_t)n);
+    int rc = stage_send(m, &st, [&](Stage &stg) {
+        A.T1 = stg.put(T1, 12);
+        A.T2 = T2 ? stg.put(T2, 12) : nullptr;
+        A.world = stg.put(world, (size_t)n * 3);
+        A.normal = normal ? stg.put(normal, (size_t)n * 3) : nullptr;
+        A.max_dist = stg.put(max_dist, (size_t)n);
+        A.min_dist = stg.put(min_dist, (size_t)n);
+        A.flags = stg.put(flags, (size_t)n);
+    });
+    if (rc) return rc;
     A.n = n; A.mode = mode; A.double_invz = double_invz;
-    if ((rc = stage_commit(m, &st))) return rc;
     void *p;
     if ((rc = scratch(m, S_Q, (size_t)n * sizeof(orbhip_query), &p))) return rc;
     A.q = (orbhip_query *)p;
@@ -7258,38 +7075,37 @@ int orbhip_fuse_batch(orbhip_matcher *m, int K, const orbhip_frame_view *const *
         const size_t kc = (size_t)Kb * cap, sn = (size_t)n;
         Stage st;
         int rc;
-        if ((rc = stage_begin(m, 2 * al256((size_t)Kb * 4) + al256((size_t)Kb * 48) + al256(kc * sizeof(orbhip_keypoint)) +
-                                     al256(kc * 32) + al256(kc * 4) + 2 * al256(sn * 12) + 2 * al256(sn * 4) +
-                                     al256((size_t)Kb * sn) + al256(sn * 32), &st))) return rc;
         const int *d_index, *d_n;
-        const float *d_T, *d_ur = nullptr;
+        const float *d_T, *d_ur, *d_world, *d_normal, *d_max, *d_min;
         const orbhip_keypoint *d_keys;
-        const uint8_t *d_desc, *d_flags;
-        int *h_index = st.take((size_t)Kb, &d_index), *h_n = st.take((size_t)Kb, &d_n);
-        float *h_T = st.take((size_t)Kb * 12, &d_T);
-        orbhip_keypoint *h_keys = st.take(kc, &d_keys);
-        uint8_t *h_desc = st.take(kc * 32, &d_desc);
-        float *h_ur = any_ur ? st.take(kc, &d_ur) : nullptr;
-        uint8_t *h_flags = st.take((size_t)Kb * sn, &d_flags);
-        const float *d_world = st.put(world, sn * 3), *d_normal = st.put(normal, sn * 3);
-        const float *d_max = st.put(max_dist, sn), *d_min = st.put(min_dist, sn);
-        const uint8_t *d_pdesc = st.put(point_desc, sn * 32);
-        if ((rc = st.status())) return rc;
-        for (int b = 0; b < Kb; ++b) {
-            const int k = rows[b];
-            const orbhip_frame_view *f = kfs[k];
-            const size_t fn = (size_t)f->n;
-            h_index[b] = b; h_n[b] = f->n;
-            memcpy(h_T + (size_t)b * 12, Tcw + (size_t)k * 12, 12 * sizeof(float));
-            if (fn) {
-                memcpy(h_keys + (size_t)b * cap, f->keys, fn * sizeof(orbhip_keypoint));
-                memcpy(h_desc + (size_t)b * cap * 32, f->desc, fn * 32);
-            }
-            if (h_ur)
-                for (size_t j = 0; j < fn; ++j) h_ur[(size_t)b * cap + j] = f->u_right ? f->u_right[j] : -1.0f;
-            memcpy(h_flags + (size_t)b * sn, flags + (size_t)k * sn, sn);
-        }
-        if ((rc = stage_commit(m, &st))) return rc;
+        const uint8_t *d_desc, *d_flags, *d_pdesc;
+        if ((rc = stage_send(m, &st, [&](Stage &stg) {
+                d_index = stg.room<int>((size_t)Kb); d_n = stg.room<int>((size_t)Kb);
+                d_T = stg.room<float>((size_t)Kb * 12);
+                d_keys = stg.room<orbhip_keypoint>(kc);
+                d_desc = stg.room<uint8_t>(kc * 32);
+                d_ur = any_ur ? stg.room<float>(kc) : nullptr;
+                d_flags = stg.room<uint8_t>((size_t)Kb * sn);
+                stg.sweep([&] {   // row b of these seven pieces: key frame rows[b]
+                    for (int b = 0; b < Kb; ++b) {
+                        const int k = rows[b];
+                        const orbhip_frame_view *f = kfs[k];
+                        const size_t fn = (size_t)f->n;
+                        stg.host(d_index)[b] = b; stg.host(d_n)[b] = f->n;
+                        memcpy(stg.host(d_T) + (size_t)b * 12, Tcw + (size_t)k * 12, 12 * sizeof(float));
+                        if (fn) {
+                            memcpy(stg.host(d_keys) + (size_t)b * cap, f->keys, fn * sizeof(orbhip_keypoint));
+                            memcpy(stg.host(d_desc) + (size_t)b * cap * 32, f->desc, fn * 32);
+                        }
+                        if (any_ur)
+                            for (size_t j = 0; j < fn; ++j) stg.host(d_ur)[(size_t)b * cap + j] = f->u_right ? f->u_right[j] : -1.0f;
+                        memcpy(stg.host(d_flags) + (size_t)b * sn, flags + (size_t)k * sn, sn);
+                    }
+                });
+                d_world = stg.put(world, sn * 3); d_normal = stg.put(normal, sn * 3);
+                d_max = stg.put(max_dist, sn); d_min = stg.put(min_dist, sn);
+                d_pdesc = stg.put(point_desc, sn * 32);
+            }))) return rc;
         void *p;
         const size_t ob = (size_t)Kb * sn * sizeof(int);
         if ((rc = scratch(m, S_OUT, 2 * ob, &p))) return rc;
@@ -7402,42 +7218,41 @@ int orbhip_create_new_map_points(orbhip_matcher *m, const orbhip_frame_view *cur
     const bool any_hp = has_point_cur || has_point;
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, 2 * al256((size_t)rows * 4) + al256((size_t)rows * 48) + al256(rc_ * sizeof(orbhip_keypoint)) +
-                                 al256(rc_ * 32) + 3 * al256(rc_ * 4) + al256(rc_) + al256((size_t)K * 4), &st))) return rc;
     const int *d_index, *d_n;
     const float *d_T, *d_ur = nullptr, *d_z = nullptr, *d_med = nullptr;
     const orbhip_keypoint *d_keys;
     const uint8_t *d_desc, *d_hp = nullptr;
     const uint32_t *d_node;
-    int *h_index = st.take((size_t)K, &d_index), *h_n = st.take((size_t)rows, &d_n);
-    float *h_T = st.take((size_t)rows * 12, &d_T);
-    orbhip_keypoint *h_keys = st.take(rc_, &d_keys);
-    uint8_t *h_desc = st.take(rc_ * 32, &d_desc);
-    uint32_t *h_node = st.take(rc_, &d_node);
-    float *h_ur = stereo ? st.take(rc_, &d_ur) : nullptr, *h_z = stereo ? st.take(rc_, &d_z) : nullptr;
-    uint8_t *h_hp = any_hp ? st.take(rc_, &d_hp) : nullptr;
-    if (median_depth) d_med = st.put(median_depth, (size_t)K);
-    if ((rc = st.status())) return rc;
-    for (int r = 0; r < rows; ++r) {
-        const int k = r - 1;
-        const orbhip_frame_view *f = r == 0 ? cur : kfs[k];
-        const size_t fn = (size_t)f->n, o = (size_t)r * cap;
-        const uint8_t *hp = r == 0 ? has_point_cur : (has_point ? has_point[k] : nullptr);
-        if (r > 0) h_index[k] = r;
-        h_n[r] = f->n;
-        memcpy(h_T + (size_t)r * 12, r == 0 ? Tcw_cur : Tcw + (size_t)k * 12, 12 * sizeof(float));
-        if (fn) {
-            memcpy(h_keys + o, f->keys, fn * sizeof(orbhip_keypoint));
-            memcpy(h_desc + o * 32, f->desc, fn * 32);
-            memcpy(h_node + o, r == 0 ? node_cur : node[k], fn * 4);
-            if (stereo) {
-                memcpy(h_ur + o, f->u_right, fn * 4);
-                memcpy(h_z + o, r == 0 ? depth_cur : depth[k], fn * 4);
-            }
-            if (h_hp) { if (hp) memcpy(h_hp + o, hp, fn); else memset(h_hp + o, 0, fn); }
-        }
-    }
-    if ((rc = stage_commit(m, &st))) return rc;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            d_index = stg.room<int>((size_t)K); d_n = stg.room<int>((size_t)rows);
+            d_T = stg.room<float>((size_t)rows * 12);
+            d_keys = stg.room<orbhip_keypoint>(rc_);
+            d_desc = stg.room<uint8_t>(rc_ * 32);
+            d_node = stg.room<uint32_t>(rc_);
+            if (stereo) { d_ur = stg.room<float>(rc_); d_z = stg.room<float>(rc_); }
+            if (any_hp) d_hp = stg.room<uint8_t>(rc_);
+            if (median_depth) d_med = stg.put(median_depth, (size_t)K);
+            stg.sweep([&] {   // row r of these pieces: the current key frame, then neighbour k = r - 1
+                for (int r = 0; r < rows; ++r) {
+                    const int k = r - 1;
+                    const orbhip_frame_view *f = r == 0 ? cur : kfs[k];
+                    const size_t fn = (size_t)f->n, o = (size_t)r * cap;
+                    const uint8_t *hp = r == 0 ? has_point_cur : (has_point ? has_point[k] : nullptr);
+                    if (r > 0) stg.host(d_index)[k] = r;
+                    stg.host(d_n)[r] = f->n;
+                    memcpy(stg.host(d_T) + (size_t)r * 12, r == 0 ? Tcw_cur : Tcw + (size_t)k * 12, 12 * sizeof(float));
+                    if (!fn) continue;
+                    memcpy(stg.host(d_keys) + o, f->keys, fn * sizeof(orbhip_keypoint));
+                    memcpy(stg.host(d_desc) + o * 32, f->desc, fn * 32);
+                    memcpy(stg.host(d_node) + o, r == 0 ? node_cur : node[k], fn * 4);
+                    if (stereo) {
+                        memcpy(stg.host(d_ur) + o, f->u_right, fn * 4);
+                        memcpy(stg.host(d_z) + o, r == 0 ? depth_cur : depth[k], fn * 4);
+                    }
+                    if (any_hp) { if (hp) memcpy(stg.host(d_hp) + o, hp, fn); else memset(stg.host(d_hp) + o, 0, fn); }
+                }
+            });
+        }))) return rc;
     // outputs in one block: matches12 | nmatches | x3d | f12 | epipole | status | skipped
     const size_t o_n = kc * 4, o_x = o_n + al256((size_t)K * 4), o_f = o_x + kc * 12, o_e = o_f + al256((size_t)K * 36),
                  o_s = o_e + al256((size_t)K * 8), o_k = o_s + al256(kc), total = o_k + al256((size_t)K);
@@ -7536,15 +7351,17 @@ int orbhip_compute_stereo_matches(orbhip_matcher *m, orbhip_extractor *left, int
     ORBHIP_HIP_CHECK(hipStreamSynchronize(right->stream));
     Stage st;
     int rc;
-    if ((rc = stage_begin(m, al256((size_t)nl * sizeof(orbhip_keypoint)) + al256((size_t)nl * 32) +
-                                 al256((size_t)nr * sizeof(orbhip_keypoint)) + al256((size_t)nr * 32) + 256, &st))) return rc;
-    const orbhip_keypoint *d_kl = st.put(keys_l, (size_t)nl);
-    const uint8_t *d_dl = st.put(desc_l, (size_t)nl * 32);
-    const orbhip_keypoint *d_kr = st.put(keys_r, (size_t)nr);
-    const uint8_t *d_dr = st.put(desc_r, (size_t)nr * 32);
+    const orbhip_keypoint *d_kl, *d_kr;
+    const uint8_t *d_dl, *d_dr;
     const int counts[2] = {nl, nr};
-    const int *d_counts = st.put(counts, 2);
-    if ((rc = stage_commit(m, &st))) return rc;
+    const int *d_counts;
+    if ((rc = stage_send(m, &st, [&](Stage &stg) {
+            d_kl = stg.put(keys_l, (size_t)nl);
+            d_dl = stg.put(desc_l, (size_t)nl * 32);
+            d_kr = stg.put(keys_r, (size_t)nr);
+            d_dr = stg.put(desc_r, (size_t)nr * 32);
+            d_counts = stg.put(counts, 2);
+        }))) return rc;
     // outputs contiguous: u_right[nl] | depth[nl] | n
     void *p;
     if ((rc = scratch(m, S_OUT, (size_t)(2 * nl + 1) * sizeof(float), &p))) return rc;

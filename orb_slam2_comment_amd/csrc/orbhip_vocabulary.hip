@@ -205,8 +205,6 @@ struct orbhip_vocabulary {
 
 namespace {
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct HostTree {
     int k = 0, L = 0, scoring = 0, weighting = 0;
     std::vector<int32_t> parent;      // per node (root: 0)
